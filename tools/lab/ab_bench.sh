@@ -12,7 +12,7 @@ EOF2
 for rep in 1 2; do
   for which in "$@"; do
     if [ $which = new ]; then cp /tmp/libacx_new.so $L; else cp build/labs/libacx_$which.so $L; fi
-    python bench.py --steps 40 --warmup 5 --no-cpu-baseline ${BENCH_ARGS} > /tmp/b_$which.json 2>/tmp/b_$which.err || tail -3 /tmp/b_$which.err
+    python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline ${BENCH_ARGS} > /tmp/b_$which.json 2>/tmp/b_$which.err || tail -3 /tmp/b_$which.err
     printf "%-10s" "$which:"; show /tmp/b_$which.json
   done
 done

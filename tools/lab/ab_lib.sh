@@ -13,7 +13,7 @@ for P in $PRECS; do
   for i in 1 2 3; do
     for which in base new; do
       if [ $which = base ]; then export ACX_LIB=$PWD/$BASE; else unset ACX_LIB; fi
-      python bench.py --precision $P --steps 20 --warmup 5 --no-cpu-baseline --no-extra-configs > /tmp/ab.json 2>/dev/null && echo -n "$P $which: " && summ /tmp/ab.json
+      python bench.py --full --precision $P --steps 20 --warmup 5 --no-cpu-baseline --no-extra-configs > /tmp/ab.json 2>/dev/null && echo -n "$P $which: " && summ /tmp/ab.json
     done
   done
 done
