@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -106,6 +107,28 @@ __device__ __forceinline__ unsigned acx_pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float acx_bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float acx_bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
+// ---- host-side weight image helpers (acx_finalize and the per-kernel packers) ----
+inline uint16_t to_bf16(float f) {      // round to nearest even, as v_cvt_pk_bf16_f32 does
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+// S16 form of gemm_split.hip: [rows][K/8][hi x8 | lo x8] fp16, values pre-multiplied by `scale` (a power of two)
+inline std::vector<uint16_t> s16_rows(const std::vector<float>& w, int rows, int K, float scale) {
+    std::vector<uint16_t> h((size_t)rows * K * 2);
+    for (int n = 0; n < rows; ++n)
+        for (int k = 0; k < K; ++k) {
+            const float v = w[(size_t)n * K + k] * scale;
+            const _Float16 hi = (_Float16)v;
+            const _Float16 lo = (_Float16)(v - (float)hi);
+            uint16_t* blk = h.data() + ((size_t)n * K + (size_t)(k & ~7)) * 2;
+            std::memcpy(blk + (k & 7), &hi, 2);
+            std::memcpy(blk + 8 + (k & 7), &lo, 2);
+        }
+    return h;
+}
+
 struct HostTensor {
     std::vector<float> data;
     std::vector<int64_t> shape;
@@ -114,29 +137,32 @@ struct HostTensor {
 struct BlockW {          // one ConvNeXt Block (convnext.py:44-87), kernel layouts
     float* dw = nullptr;     // [49][C]   tap-major depthwise weights
     float* dwb = nullptr;    // [C]
-    uint16_t* dw_ops = nullptr; // bf16a, stages 0-2: the depthwise weights as the B operands of dwconv_mfma.hip: [C/32][7][3][2][64 lanes][4] bf16
-    float* w1 = nullptr;     // [4C][C]   pwconv1 with the LayerNorm weight folded in
     float* b1 = nullptr;     // [4C]      pwconv1 bias + W1 . ln_bias
-    float* w1sum = nullptr;  // [4C]      sum_k w1[n][k]  (LayerNorm applied in the GEMM epilogue)
-    float* w2 = nullptr;     // [C][4C]   gamma * pwconv2
     float* b2 = nullptr;     // [C]       gamma * pwconv2 bias
-    float* wpack = nullptr;  // [4C/32][64*C]  per hidden chunk: w1 rows [32][C] then w2 columns [C][32] (fused MLP)
-    uint16_t* w1h = nullptr; // bf16 mode: [4C][Cp]  folded pwconv1 rounded to bf16, K zero-padded to Cp = pad64(C)
-    uint16_t* w2h = nullptr; // bf16 mode: [C][4C]   gamma * pwconv2 rounded to bf16
-    uint16_t* w1s = nullptr; // split mode: folded pwconv1 in S16 form (gemm_split.hip), scaled by w1s_scale
-    uint16_t* w2s = nullptr; // split mode: gamma * pwconv2 in S16 form, scaled by w2s_scale
-    uint16_t* wpack_s = nullptr; // split mode, C = 96/192: chunk-major [W1c | W2c] S16 image (mlp_fused_split.hip)
-    uint16_t* wstream_b = nullptr; // bf16 mode: the same segment stream in bf16, chunks of 64 hidden units (mlp_fused_wide_bf16.hip)
-    uint16_t* wstream_s = nullptr; // split mode, C = 384: segment stream in consumption order, LDS image order (mlp_fused_wide.hip)
-    float w1s_scale = 1.f, w2s_scale = 1.f;
-    float hid_scale = 1.f;   // split mode: power-of-two scale of the S16 hidden activation (GELU output)
+    // Weight images: acx_finalize uploads only those the launches of the context's arithmetic read; the rest stay null.
+    // W1 = pwconv1 with the LayerNorm weight folded in [4C][C], W2 = gamma * pwconv2 [C][4C].
+    float* w1 = nullptr;     // fp32, stages 2-3: W1
+    float* w1sum = nullptr;  // fp32, stages 2-3: [4C] sum_k w1[n][k]  (LayerNorm applied in the GEMM epilogue)
+    float* w2 = nullptr;     // fp32, stages 2-3: W2
+    float* wpack = nullptr;  // fp32, stages 0-1: chunk-major image of mlp_fused.hip
+    uint16_t* wpack_s = nullptr;   // fp32_split, stage 0: chunk-major S16 image of mlp_fused_split.hip
+    uint16_t* wstream_s = nullptr; // fp32_split, stages 1-2: S16 segment stream of mlp_fused_wide.hip
+    uint16_t* w1s = nullptr; // fp32_split, stage 3: W1 in S16 form (gemm_split.hip), scaled by w1s_scale
+    uint16_t* w2s = nullptr; // fp32_split, stage 3: W2 in S16 form, scaled by w2s_scale
+    uint16_t* wstream_b = nullptr; // bf16 / bf16a, stages 0-2: bf16 segment stream of mlp_fused_wide_bf16.hip
+    uint16_t* w1h = nullptr; // bf16 / bf16a, stage 3: [4C][Cp]  W1 rounded to bf16, K zero-padded to Cp = pad64(C)
+    uint16_t* w2h = nullptr; // bf16 / bf16a, stage 3: W2 rounded to bf16
+    uint16_t* dw_ops = nullptr;    // bf16a, stages 0-2: the depthwise weights as the B operands of dwconv_mfma.hip
+    float w1s_scale = 1.f, w2s_scale = 1.f;   // fp32_split: power-of-two scales of the S16 weight images
+    float hid_scale = 1.f;   // fp32_split: power-of-two scale of the S16 hidden activation (GELU output)
 };
 
 struct DownW {           // downsample_layers[i], i>=1 (convnext.py:230-235)
-    float* w = nullptr;      // [C'][4C]  k = (dy*2+dx)*C + c, LayerNorm weight folded in
     float* b = nullptr;      // [C']      bias + W . ln_bias
-    uint16_t* wh = nullptr;  // bf16 mode: [C'][4*Cp]  k = (dy*2+dx)*Cp + c
-    uint16_t* ws = nullptr;  // split mode: [C'][4C] in S16 form, scaled by ws_scale
+    // W = [C'][4C], k = (dy*2+dx)*C + c, LayerNorm weight folded in: one form per arithmetic
+    float* w = nullptr;      // fp32
+    uint16_t* ws = nullptr;  // fp32_split: in S16 form, scaled by ws_scale
+    uint16_t* wh = nullptr;  // bf16 / bf16a: [C'][4*Cp]  k = (dy*2+dx)*Cp + c
     float ws_scale = 1.f;
 };
 
@@ -185,7 +211,6 @@ struct acx_ctx {
     float* d_head_b = nullptr;    // [527]
 
     int precision = ACX_PREC_F32_SPLIT;   // acx_set_precision (include/acx.h): the default equals the Python host's
-    bool use_fused_mlp = true;    // ACX_DISABLE_FUSED_MLP=1 (native fp32 arithmetic only) turns the fused stage-0/1 MLP kernel off
     // two-way batch split over two HIP streams (fork/join by events): kernels of the two halves co-run, so
     // an HBM-bound kernel of one half fills the matrix-pipe-bound phases of the other and vice versa
     bool split_streams = true;    // ACX_SPLIT_STREAMS=0 turns it off
@@ -226,10 +251,8 @@ inline int inflight_ways() { return tls_inflight_ways > 0 ? tls_inflight_ways : 
 struct Tuning {
     std::atomic<int> gemm_mi{0};       // ACX_GEMM_MI = 1 | 2 | 4: row blocks per wave of the split / bf16 GEMM tiles (0: by launch size)
     std::atomic<int> wide_npb{0};      // ACX_WIDE_NPB = 1 | 2: pixel blocks per wave of the wide fused MLP (0: by launch size)
-    std::atomic<int> gemm_32x32{0};    // ACX_GEMM_32X32 = 1: the 32x32x16 form of the split GEMM
     std::atomic<int> wide_pers{0};     // ACX_WIDE_PERSIST: 1 = persistent wide fused MLP wherever it exists, 2 = never; 0 = by launch size
     std::atomic<int> dwm_waves{0};     // ACX_DWM_WAVES = 2..9: the matrix-pipe depthwise launch asks for that many waves per CU of its share (0: 8 = two per SIMD)
-    std::atomic<int> dw_mfma{-1};      // ACX_DW_MFMA = 0: bf16 activations go through the column / tile depthwise kernels instead of the matrix-pipe kernel (A/B timing: other bits)
     std::atomic<int> dw_stream{-1};    // ACX_DW_STREAM = 0 | 1: forces the tile / column-streaming depthwise kernels (-1: by launch size)
 };
 Tuning& tuning();
@@ -263,7 +286,8 @@ inline int stage_h0(int T) { return (T + 8 - 4) / 4 + 1; }
 constexpr int kDenseN = 1056;                    // 2 x 513 rows padded to a multiple of the GEMM's 96-column tile
 int launch_logmel(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* out, bool bn, hipStream_t s,
                   float* dense_frames = nullptr, float* dense_spec = nullptr);
-// act_bf16: the activation tensors named void* are bf16 (ACX_PREC_BF16_ACT, stages 0-2) instead of fp32
+// act_bf16: the activation tensors named void* are bf16 (ACX_PREC_BF16_ACT, stages 0-2) instead of fp32; launch_dwconv then
+// takes the matrix-pipe kernel (dwconv_mfma.hip), which reads BlockW::dw_ops
 int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hipStream_t s, bool act_bf16 = false);
 int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, int B, int H,
                   int W, hipStream_t s, bool act_bf16 = false);
@@ -274,8 +298,10 @@ constexpr int kDwSinkWindows = 128;                   // waves get sink windows 
 constexpr size_t kDwSinkWindowBytes = 64 * 1024;      // >= a row's lane offsets + 6 pixel strides
 constexpr size_t kDwSinkBytes = kDwSinkWindows * kDwSinkWindowBytes;
 int launch_dwconv_col(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H, int W,
-                      bool act_bf16, int target_waves, hipStream_t s);
-// matrix-pipe form for bf16 activations (dwconv_mfma.hip): weights rounded to bf16, fp32 accumulation; every launch size
+                      int target_waves, hipStream_t s);
+// matrix-pipe form for bf16 activations (dwconv_mfma.hip): weights rounded to bf16, fp32 accumulation; every launch size.
+// dwconv_mfma_pack: its weight operands (BlockW::dw_ops) from the depthwise weights as stored, [C][49]
+std::vector<uint16_t> dwconv_mfma_pack(const std::vector<float>& dw, int C);
 int launch_dwconv_mfma(const void* x, void* y, const void* dw_ops, const float* bias, void* sink, int B, int H, int W,
                        int target_waves, hipStream_t s);
 // element-wise fp32 <-> bf16 (the per-layer entry points of the C ABI keep fp32 tensors in every mode)
@@ -321,21 +347,28 @@ struct GemmSplitArgs {
     int epi; int cls;
 };
 int launch_gemm_split(acx_ctx* c, const GemmSplitArgs& a, hipStream_t s);
+// The fused block MLPs below read their weights as one image each, built on the host by the kernel's *_pack function from the
+// folded W1 [4C][C] and W2 [C][4C] (the S16 forms scaled by w1_scale / w2_scale).
 bool mlp_fused_supported(int C);
 // x += MLP(LN(y)) for one block, hidden activation kept in registers (mlp_fused.hip)
+std::vector<float> mlp_fused_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C);
 int launch_mlp_fused(acx_ctx* c, const BlockW& w, int C, const float* y, float* x, long long M, hipStream_t s);
 // ln_out != nullptr: do not write x; write LayerNorm(x_new) as S16 rows (the downsample GEMM's operand) there instead
 bool mlp_fused_split_supported(int C);
+std::vector<uint16_t> mlp_fused_split_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C, float w1_scale,
+                                           float w2_scale);
 int launch_mlp_fused_split(acx_ctx* c, const BlockW& w, int C, const float* y, float* x, long long M, hipStream_t s,
                            void* ln_out = nullptr);
 // the same for wide stages (C = 384, mlp_fused_wide.hip): one wave per SIMD, weights as one stream of segments
 bool mlp_fused_wide_supported(int C);
+std::vector<uint16_t> mlp_fused_wide_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C, float w1_scale,
+                                          float w2_scale);
 int launch_mlp_fused_wide(acx_ctx* c, const BlockW& w, int C, const float* y, float* x, long long M, hipStream_t s,
                           void* ln_out = nullptr);
 // bf16 arithmetic (mlp_fused_wide_bf16.hip): the fused block MLP for C = 96 / 192 / 384; ln_out (with row stride ld_out
 // bf16 elements) receives LayerNorm(x_new) as bf16 rows INSTEAD of x when non-null
 bool mlp_fused_wide_bf16_supported(int C);
-int mlp_fused_wide_bf16_swz(int C, int row);
+std::vector<uint16_t> mlp_fused_wide_bf16_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C);
 int launch_mlp_fused_wide_bf16(acx_ctx* c, const BlockW& w, int C, const void* y, void* x, long long M, hipStream_t s,
                                void* ln_out = nullptr, int ld_out = 0, bool act_bf16 = false);
 int launch_pool_head(acx_ctx* c, const float* x, int B, int H3, float* scene, float* logits, float* probs,

@@ -26,9 +26,7 @@ void tuning_reload() {
     t.gemm_mi.store(digit("ACX_GEMM_MI", "124", 0), std::memory_order_relaxed);
     t.wide_npb.store(digit("ACX_WIDE_NPB", "12", 0), std::memory_order_relaxed);
     t.wide_pers.store(digit("ACX_WIDE_PERSIST", "01", -1) < 0 ? 0 : (digit("ACX_WIDE_PERSIST", "01", 0) == 1 ? 1 : 2), std::memory_order_relaxed);
-    t.gemm_32x32.store(digit("ACX_GEMM_32X32", "1", 0), std::memory_order_relaxed);
     t.dw_stream.store(digit("ACX_DW_STREAM", "01", -1), std::memory_order_relaxed);
-    t.dw_mfma.store(digit("ACX_DW_MFMA", "01", -1), std::memory_order_relaxed);
     t.dwm_waves.store(digit("ACX_DWM_WAVES", "23456789", 0), std::memory_order_relaxed);
 }
 
@@ -120,13 +118,6 @@ static int upload(acx_ctx* c, const std::vector<T>& h, T** out) {
     return ACX_OK;
 }
 
-static uint16_t to_bf16(float f) {      // round to nearest even, as v_cvt_pk_bf16_f32 does
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 // rows x K fp32 -> rows x Kp bf16, source column k of group q (K = groups * Kg) lands at q * Kgp + k
 static std::vector<uint16_t> bf16_rows(const std::vector<float>& w, int rows, int groups, int Kg, int Kgp) {
     std::vector<uint16_t> h((size_t)rows * groups * Kgp, 0);
@@ -134,21 +125,6 @@ static std::vector<uint16_t> bf16_rows(const std::vector<float>& w, int rows, in
         for (int q = 0; q < groups; ++q)
             for (int k = 0; k < Kg; ++k)
                 h[((size_t)n * groups + q) * Kgp + k] = to_bf16(w[((size_t)n * groups + q) * Kg + k]);
-    return h;
-}
-
-// S16 form of gemm_split.hip: [rows][K/8][hi x8 | lo x8] fp16, values pre-multiplied by `scale` (a power of two)
-static std::vector<uint16_t> s16_rows(const std::vector<float>& w, int rows, int K, float scale) {
-    std::vector<uint16_t> h((size_t)rows * K * 2);
-    for (int n = 0; n < rows; ++n)
-        for (int k = 0; k < K; ++k) {
-            const float v = w[(size_t)n * K + k] * scale;
-            const _Float16 hi = (_Float16)v;
-            const _Float16 lo = (_Float16)(v - (float)hi);
-            uint16_t* blk = h.data() + ((size_t)n * K + (size_t)(k & ~7)) * 2;
-            std::memcpy(blk + (k & 7), &hi, 2);
-            std::memcpy(blk + 8 + (k & 7), &lo, 2);
-        }
     return h;
 }
 
@@ -179,8 +155,7 @@ static float hidden_scale_for(const std::vector<float>& w1, const std::vector<fl
     return std::ldexp(1.0f, e);
 }
 
-// bf16 MFMA operands (both bf16 modes); bf16 activations in HBM for the stages that keep them (ACX_PREC_BF16_ACT, stages 0-2)
-static bool is_bf16(const acx_ctx* c) { return c->precision == ACX_PREC_BF16 || c->precision == ACX_PREC_BF16_ACT; }
+// bf16 activations in HBM for the stages that keep them (ACX_PREC_BF16_ACT, stages 0-2)
 static bool act_bf16(const acx_ctx* c, int stage) { return c->precision == ACX_PREC_BF16_ACT && stage >= 0 && stage < 3; }
 
 static void free_device(acx_ctx* c) {
@@ -218,11 +193,6 @@ static int finalize_impl(acx_ctx* c) {
     }
     ACX_HIP(hipSetDevice(c->device));
     free_device(c);
-    {
-        // the two-GEMM form of stages 0-1 exists in the native fp32 arithmetic only (the 16-bit GEMMs have no N = 96 tile)
-        const char* e = std::getenv("ACX_DISABLE_FUSED_MLP");
-        c->use_fused_mlp = !(e && e[0] == '1' && c->precision == ACX_PREC_F32);
-    }
 
     // ---- frontend ---------------------------------------------------------------------------
     // The FFT stands in for the two Conv1d only if the stored buffers ARE window x DFT (any window; torchlibrosa's is the
@@ -314,14 +284,16 @@ static int finalize_impl(acx_ctx* c) {
                 }
             b[n] = (float)acc;
         }
-        ACX_TRY(upload(c, w, &c->down[i].w));
-        ACX_TRY(upload(c, b, &c->down[i].b));
-        c->down[i].wh = nullptr;
-        if (is_bf16(c)) ACX_TRY(upload(c, bf16_rows(w, Co, 4, Ci, pad64(Ci)), &c->down[i].wh));
-        c->down[i].ws = nullptr;
-        if (c->precision == ACX_PREC_F32_SPLIT) {
-            c->down[i].ws_scale = s16_scale(w);
-            ACX_TRY(upload(c, s16_rows(w, Co, 4 * Ci, c->down[i].ws_scale), &c->down[i].ws));
+        DownW& d = c->down[i];
+        d = DownW{};
+        ACX_TRY(upload(c, b, &d.b));
+        switch (c->precision) {
+            case ACX_PREC_F32: ACX_TRY(upload(c, w, &d.w)); break;
+            case ACX_PREC_F32_SPLIT:
+                d.ws_scale = s16_scale(w);
+                ACX_TRY(upload(c, s16_rows(w, Co, 4 * Ci, d.ws_scale), &d.ws));
+                break;
+            default: ACX_TRY(upload(c, bf16_rows(w, Co, 4, Ci, pad64(Ci)), &d.wh));      // bf16, bf16a
         }
     }
     // ---- blocks -----------------------------------------------------------------------------
@@ -338,25 +310,6 @@ static int finalize_impl(acx_ctx* c) {
                 for (int tap = 0; tap < 49; ++tap) t[(size_t)tap * C + ch] = dw[(size_t)ch * 49 + tap];
             ACX_TRY(upload(c, t, &bw.dw));
             ACX_TRY(upload(c, dwb, &bw.dwb));
-            if (c->precision == ACX_PREC_BF16_ACT && s < 3) {
-                // dwconv_mfma.hip: the B operands of the 16-block 4x4x4 MFMA, one 8-byte load per lane and operand.  Operand
-                // (kernel row kh, d = input quad - output quad + 1, channel set) of lane (q = lane & 3, cl = lane >> 2) holds, for
-                // k = 0..3, the weight of tap 4 d + k - q - 1 of row kh (zero outside 0..6) of channel 32 slice + 2 cl + set.
-                std::vector<uint16_t> ops((size_t)(C / 32) * 42 * 64 * 4);
-                for (int sl = 0; sl < C / 32; ++sl)
-                    for (int kh = 0; kh < 7; ++kh)
-                        for (int d = 0; d < 3; ++d)
-                            for (int st = 0; st < 2; ++st)
-                                for (int lane = 0; lane < 64; ++lane) {
-                                    const int q = lane & 3, ch = 32 * sl + 2 * (lane >> 2) + st;
-                                    for (int k = 0; k < 4; ++k) {
-                                        const int tp = 4 * d + k - q - 1;
-                                        ops[((((size_t)(sl * 7 + kh) * 3 + d) * 2 + st) * 64 + lane) * 4 + k] =
-                                            (tp >= 0 && tp < 7) ? to_bf16(dw[(size_t)ch * 49 + kh * 7 + tp]) : (uint16_t)0;
-                                    }
-                                }
-                ACX_TRY(upload(c, ops, &bw.dw_ops));
-            }
             std::vector<float> f1((size_t)4 * C * C), fb1((size_t)4 * C), fs1((size_t)4 * C);
             for (int n = 0; n < 4 * C; ++n) {
                 double acc = b1[n], csum = 0.0;
@@ -370,135 +323,45 @@ static int finalize_impl(acx_ctx* c) {
                 fb1[n] = (float)acc;
                 fs1[n] = (float)csum;
             }
-            ACX_TRY(upload(c, f1, &bw.w1));
             ACX_TRY(upload(c, fb1, &bw.b1));
-            ACX_TRY(upload(c, fs1, &bw.w1sum));
             std::vector<float> f2((size_t)C * 4 * C), fb2(C);
             for (int n = 0; n < C; ++n) {
                 for (int k = 0; k < 4 * C; ++k) f2[(size_t)n * 4 * C + k] = (float)((double)gamma[n] * w2[(size_t)n * 4 * C + k]);
                 fb2[n] = (float)((double)gamma[n] * b2[n]);
             }
-            ACX_TRY(upload(c, f2, &bw.w2));
             ACX_TRY(upload(c, fb2, &bw.b2));
-            if (is_bf16(c)) {
-                ACX_TRY(upload(c, bf16_rows(f1, 4 * C, 1, C, pad64(C)), &bw.w1h));
-                ACX_TRY(upload(c, bf16_rows(f2, C, 1, 4 * C, 4 * C), &bw.w2h));
-                if (c->use_fused_mlp && mlp_fused_wide_bf16_supported(C)) {
-                    // mlp_fused_wide_bf16.hip: one stream of 128 C-byte segments in consumption order
-                    //   W1(0) W1(1) W2(0) W1(2) W2(1) ... W1(n-1) W2(n-2) W2(n-1),   n = 4C/64 chunks of 64 hidden units,
-                    // each already in LDS image order.
-                    const int nch = 4 * C / 64;
-                    const size_t seg = (size_t)64 * C;                   // uint16 elements per segment
-                    std::vector<uint16_t> st((size_t)2 * nch * seg);
-                    for (int k = 0; k < nch; ++k) {
-                        // W1 image: row r = hidden unit 64k + r (2 C bytes = C/8 chunks of 8 channels), chunk p at p ^ swz(r)
-                        uint16_t* w1img = st.data() + (size_t)(k == 0 ? 0 : 2 * k - 1) * seg;
-                        for (int r = 0; r < 64; ++r)
-                            for (int p = 0; p < C / 8; ++p) {
-                                const int pos = p ^ mlp_fused_wide_bf16_swz(C, r);
-                                for (int e = 0; e < 8; ++e)
-                                    w1img[(size_t)r * C + (size_t)pos * 8 + e] = to_bf16(0.5f * f1[(size_t)(64 * k + r) * C + 8 * p + e]);   // 0.5 W1: the accumulator is z (gelu2h_micro)
-                            }
-                        // W2 image: row = out channel (128 B = 8 chunks); chunk b = 2 s' + h (s' = k-step 0..3) holds hidden
-                        // units 64k + 32(s' >> 1) + 16(s' & 1) + 4h + 8(jj >> 2) + (jj & 3), at position b ^ ((ch >> 1) & 7)
-                        uint16_t* w2img = st.data() + (size_t)(k == nch - 1 ? 2 * nch - 1 : 2 * k + 2) * seg;
-                        for (int ch = 0; ch < C; ++ch)
-                            for (int b = 0; b < 8; ++b) {
-                                const int sp = b >> 1, h = b & 1;
-                                const int pos = b ^ ((ch >> 1) & 7);
-                                for (int jj = 0; jj < 8; ++jj) {
-                                    const int u = 64 * k + 32 * (sp >> 1) + 16 * (sp & 1) + 4 * h + 8 * (jj >> 2) + (jj & 3);
-                                    w2img[(size_t)ch * 64 + (size_t)pos * 8 + jj] = to_bf16(f2[(size_t)ch * 4 * C + u]);
-                                }
-                            }
+            // the weight images the launches of this arithmetic read (run_block), nothing else
+            switch (c->precision) {
+                case ACX_PREC_F32:
+                    if (mlp_fused_supported(C)) {
+                        ACX_TRY(upload(c, mlp_fused_pack(f1, f2, C), &bw.wpack));
+                    } else {
+                        ACX_TRY(upload(c, f1, &bw.w1));
+                        ACX_TRY(upload(c, fs1, &bw.w1sum));
+                        ACX_TRY(upload(c, f2, &bw.w2));
                     }
-                    ACX_TRY(upload(c, st, &bw.wstream_b));
-                }
-            }
-            if (c->precision == ACX_PREC_F32_SPLIT) {
-                bw.w1s_scale = s16_scale(f1);
-                bw.w2s_scale = s16_scale(f2);
-                bw.hid_scale = hidden_scale_for(f1, fb1, 4 * C, C);
-                const std::vector<uint16_t> h1 = s16_rows(f1, 4 * C, C, bw.w1s_scale);
-                ACX_TRY(upload(c, h1, &bw.w1s));
-                ACX_TRY(upload(c, s16_rows(f2, C, 4 * C, bw.w2s_scale), &bw.w2s));
-                if (mlp_fused_split_supported(C)) {
-                    // chunk-major image for mlp_fused_split.hip: per chunk j [W1c = rows 32j..32j+31 of w1s]
-                    // [W2c: C rows x 4 blocks; block b = 2s'+h holds hidden units 32j + 16s' + 4h + 8(jj>>2) + (jj&3)]
-                    const int nch = 4 * C / 32;
-                    const size_t half = (size_t)64 * C;                    // uint16 elements per [32][C] S16 image
-                    std::vector<uint16_t> pk((size_t)nch * 2 * half);
-                    for (int j = 0; j < nch; ++j) {
-                        uint16_t* blk = pk.data() + (size_t)j * 2 * half;
-                        std::memcpy(blk, h1.data() + (size_t)j * half, half * 2);
-                        uint16_t* blk2 = blk + half;
-                        for (int ch = 0; ch < C; ++ch)
-                            for (int b = 0; b < 4; ++b)
-                                for (int jj = 0; jj < 8; ++jj) {
-                                    const int u = 32 * j + 16 * (b >> 1) + 4 * (b & 1) + 8 * (jj >> 2) + (jj & 3);
-                                    const float v = f2[(size_t)ch * 4 * C + u] * bw.w2s_scale;
-                                    const _Float16 hi = (_Float16)v;
-                                    const _Float16 lo = (_Float16)(v - (float)hi);
-                                    std::memcpy(blk2 + (size_t)ch * 64 + b * 16 + jj, &hi, 2);
-                                    std::memcpy(blk2 + (size_t)ch * 64 + b * 16 + 8 + jj, &lo, 2);
-                                }
+                    break;
+                case ACX_PREC_F32_SPLIT:
+                    bw.w1s_scale = s16_scale(f1);
+                    bw.w2s_scale = s16_scale(f2);
+                    bw.hid_scale = hidden_scale_for(f1, fb1, 4 * C, C);
+                    if (mlp_fused_split_supported(C)) {
+                        ACX_TRY(upload(c, mlp_fused_split_pack(f1, f2, C, bw.w1s_scale, bw.w2s_scale), &bw.wpack_s));
+                    } else if (mlp_fused_wide_supported(C)) {
+                        ACX_TRY(upload(c, mlp_fused_wide_pack(f1, f2, C, bw.w1s_scale, bw.w2s_scale), &bw.wstream_s));
+                    } else {
+                        ACX_TRY(upload(c, s16_rows(f1, 4 * C, C, bw.w1s_scale), &bw.w1s));
+                        ACX_TRY(upload(c, s16_rows(f2, C, 4 * C, bw.w2s_scale), &bw.w2s));
                     }
-                    ACX_TRY(upload(c, pk, &bw.wpack_s));
-                }
-            }
-            if (c->precision == ACX_PREC_F32_SPLIT && c->use_fused_mlp && mlp_fused_wide_supported(C)) {
-                // mlp_fused_wide.hip: ONE stream of 128 C-byte segments in consumption order
-                //   W1(0) W1(1) W2(0) W1(2) W2(1) ... W1(n-1) W2(n-2) W2(n-1),   n = 4C/32 hidden chunks,
-                // each already in LDS image order (XOR swizzles baked in): a 1-KB LDS-DMA piece is 1 KB of the stream.
-                const int nch = 4 * C / 32;
-                const size_t seg = (size_t)64 * C;                   // uint16 elements per segment (128 C bytes)
-                const std::vector<uint16_t> h1 = s16_rows(f1, 4 * C, C, bw.w1s_scale);      // [4C][C/8][hi8 | lo8]
-                std::vector<uint16_t> st((size_t)2 * nch * seg);
-                for (int k = 0; k < nch; ++k) {
-                    // W1 image of chunk k: row r = hidden unit 32k + r (4 C bytes = C/4 chunks of 16 B: chunk p = block p >> 1
-                    // of the row, p & 1: hi / lo halves), content chunk p at position p ^ swz(r): r & 15 when C/4 is a multiple
-                    // of 16 chunks, (r >> 1) & 7 for C = 96 (24 chunks per row: odd rows start 8 chunks further)
-                    uint16_t* w1img = st.data() + (size_t)(k == 0 ? 0 : 2 * k - 1) * seg;
-                    for (int r = 0; r < 32; ++r)
-                        for (int p = 0; p < C / 4; ++p) {
-                            const int pos = p ^ ((C % 64 == 0) ? (r & 15) : ((r >> 1) & 7));
-                            std::memcpy(w1img + ((size_t)r * 4 * C + (size_t)pos * 16) / 2,
-                                        h1.data() + ((size_t)(32 * k + r) * C * 4 + (size_t)p * 16) / 2, 16);
-                        }
-                    // W2 image of chunk k: row = out channel (128 B = 8 chunks); content chunk 2b (hi) / 2b + 1 (lo) of
-                    // block b (= k block g4 of the 16x16x32 MFMA) holds hidden units 32k + 16(jj >> 2) + 4b + (jj & 3) -- the order
-                    // in which a lane's accumulators of phase 1 become its B operand of phase 2 --, at position ^ acx_swz8(ch)
-                    uint16_t* w2img = st.data() + (size_t)(k == nch - 1 ? 2 * nch - 1 : 2 * k + 2) * seg;
-                    for (int ch = 0; ch < C; ++ch)
-                        for (int b = 0; b < 4; ++b) {
-                            uint16_t hi8[8], lo8[8];
-                            for (int jj = 0; jj < 8; ++jj) {
-                                const int u = 32 * k + 16 * (jj >> 2) + 4 * b + (jj & 3);
-                                const float v = f2[(size_t)ch * 4 * C + u] * bw.w2s_scale;
-                                const _Float16 hi = (_Float16)v;
-                                const _Float16 lo = (_Float16)(v - (float)hi);
-                                std::memcpy(&hi8[jj], &hi, 2);
-                                std::memcpy(&lo8[jj], &lo, 2);
-                            }
-                            const int sw = acx_swz8(ch);
-                            std::memcpy(w2img + ((size_t)ch * 128 + (size_t)((2 * b) ^ sw) * 16) / 2, hi8, 16);
-                            std::memcpy(w2img + ((size_t)ch * 128 + (size_t)((2 * b + 1) ^ sw) * 16) / 2, lo8, 16);
-                        }
-                }
-                ACX_TRY(upload(c, st, &bw.wstream_s));
-            }
-            if (mlp_fused_supported(C)) {       // chunk-major image for the fused kernel's LDS-DMA
-                const int nch = 4 * C / 32;
-                std::vector<float> pk((size_t)nch * 64 * C);
-                for (int j = 0; j < nch; ++j) {
-                    float* blk = pk.data() + (size_t)j * 64 * C;
-                    for (int r = 0; r < 32; ++r)
-                        for (int k = 0; k < C; ++k) blk[(size_t)r * C + k] = f1[(size_t)(32 * j + r) * C + k];
-                    float* blk2 = blk + (size_t)32 * C;
-                    for (int ch = 0; ch < C; ++ch)
-                        for (int h = 0; h < 32; ++h) blk2[(size_t)ch * 32 + h] = f2[(size_t)ch * 4 * C + 32 * j + h];
-                }
-                ACX_TRY(upload(c, pk, &bw.wpack));
+                    break;
+                default:                                                    // bf16, bf16a
+                    if (mlp_fused_wide_bf16_supported(C)) {
+                        ACX_TRY(upload(c, mlp_fused_wide_bf16_pack(f1, f2, C), &bw.wstream_b));
+                    } else {
+                        ACX_TRY(upload(c, bf16_rows(f1, 4 * C, 1, C, pad64(C)), &bw.w1h));
+                        ACX_TRY(upload(c, bf16_rows(f2, C, 1, 4 * C, 4 * C), &bw.w2h));
+                    }
+                    if (act_bf16(c, s)) ACX_TRY(upload(c, dwconv_mfma_pack(dw, C), &bw.dw_ops));
             }
             c->blocks[s].push_back(bw);
         }
@@ -574,48 +437,45 @@ static int run_mlp_split(acx_ctx* c, const BlockW& bw, int C, float* y, float* x
     return launch_gemm_split(c, g2, st);
 }
 
-// True when the last block of stage s can hand the downsample conv its LayerNorm'ed S16 operand directly
-// (fused split MLP kernel, LNOUT epilogue): x of that stage is then NOT updated by its last block.
-static bool block_can_emit_ln(const acx_ctx* c, int s) {
-    if (s < 3 && is_bf16(c) && c->use_fused_mlp && mlp_fused_wide_bf16_supported(kDims[s])) return true;
-    return s < 3 && c->precision == ACX_PREC_F32_SPLIT && c->use_fused_mlp &&
-           (mlp_fused_split_supported(kDims[s]) || mlp_fused_wide_supported(kDims[s]));
-}
+// True when the last block of stage s hands the downsample conv its LayerNorm'ed operand rows (S16 / bf16) directly: the fused
+// MLP kernels of stages 0-2 in the 16-bit arithmetics (LNOUT epilogue).  x of that stage is then NOT updated by its last block.
+static bool block_can_emit_ln(const acx_ctx* c, int s) { return s < 3 && c->precision != ACX_PREC_F32; }
 
 static int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, int B, int H, int Wd,
                      hipStream_t st, void* ln_out = nullptr) {
     const int C = kDims[s];
     const BlockW& bw = c->blocks[s][j];
     const int64_t M = (int64_t)B * H * Wd;
-    if (c->precision == ACX_PREC_F32_SPLIT) {
-        ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st));
-        if (c->use_fused_mlp && mlp_fused_wide_supported(C) && bw.wstream_s) return launch_mlp_fused_wide(c, bw, C, y, x, M, st, ln_out);
-        if (c->use_fused_mlp && mlp_fused_split_supported(C)) return launch_mlp_fused_split(c, bw, C, y, x, M, st, ln_out);
-        if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
-        return run_mlp_split(c, bw, C, y, x, hidden, M, st);
+    switch (c->precision) {
+        case ACX_PREC_F32: {
+            if (mlp_fused_supported(C)) {
+                ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st));      // LN statistics are computed in-kernel
+                return launch_mlp_fused(c, bw, C, y, x, M, st);
+            }
+            ACX_TRY(launch_dwconv(c, bw, C, x, y, stats, B, H, Wd, st));
+            GemmArgs g1{};
+            g1.A = y; g1.Wt = bw.w1; g1.bias = bw.b1; g1.out = hidden; g1.stats = stats; g1.colsum = bw.w1sum; g1.M = M; g1.N = 4 * C; g1.K = C;
+            g1.epi = EPI_GELU; g1.cls = ACX_K_PW1;
+            ACX_TRY(launch_gemm(c, g1, st));
+            GemmArgs g2{};
+            g2.A = hidden; g2.Wt = bw.w2; g2.bias = bw.b2; g2.out = x; g2.resid = x; g2.M = M; g2.N = C; g2.K = 4 * C;
+            g2.epi = EPI_RESID; g2.cls = ACX_K_PW2;
+            return launch_gemm(c, g2, st);
+        }
+        case ACX_PREC_F32_SPLIT:
+            ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st));
+            if (mlp_fused_split_supported(C)) return launch_mlp_fused_split(c, bw, C, y, x, M, st, ln_out);
+            if (mlp_fused_wide_supported(C)) return launch_mlp_fused_wide(c, bw, C, y, x, M, st, ln_out);
+            if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
+            return run_mlp_split(c, bw, C, y, x, hidden, M, st);
+        default: {                                                              // bf16, bf16a
+            const bool ab = act_bf16(c, s);         // x and y of this stage are bf16 tensors in HBM
+            ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st, ab));
+            if (mlp_fused_wide_bf16_supported(C)) return launch_mlp_fused_wide_bf16(c, bw, C, y, x, M, st, ln_out, pad64(C), ab);
+            if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
+            return run_mlp_bf16(c, bw, C, y, x, hidden, M, st);
+        }
     }
-    if (is_bf16(c)) {
-        const bool ab = act_bf16(c, s);         // x and y of this stage are bf16 tensors in HBM
-        ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st, ab));
-        if (c->use_fused_mlp && bw.wstream_b) return launch_mlp_fused_wide_bf16(c, bw, C, y, x, M, st, ln_out, pad64(C), ab);
-        if (ab) ACX_FAIL(ACX_ERR_STATE, "run_block: bf16 activations need the fused block kernel (stage %d)", s);
-        if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
-        return run_mlp_bf16(c, bw, C, y, x, hidden, M, st);
-    }
-    if (c->use_fused_mlp && mlp_fused_supported(C)) {
-        ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st));      // LN statistics are computed in-kernel
-        return launch_mlp_fused(c, bw, C, y, x, M, st);
-    }
-    ACX_TRY(launch_dwconv(c, bw, C, x, y, stats, B, H, Wd, st));
-    GemmArgs g1{};
-    g1.A = y; g1.Wt = bw.w1; g1.bias = bw.b1; g1.out = hidden; g1.stats = stats; g1.colsum = bw.w1sum; g1.M = M; g1.N = 4 * C; g1.K = C;
-    g1.epi = EPI_GELU; g1.cls = ACX_K_PW1;
-    ACX_TRY(launch_gemm(c, g1, st));
-    GemmArgs g2{};
-    g2.A = hidden; g2.Wt = bw.w2; g2.bias = bw.b2; g2.out = x; g2.resid = x; g2.M = M; g2.N = C; g2.K = 4 * C;
-    g2.epi = EPI_RESID; g2.cls = ACX_K_PW2;
-    ACX_TRY(launch_gemm(c, g2, st));
-    return ACX_OK;
 }
 
 // have_ln: xnorm already holds the normalised S16 rows (written by the last block of the previous stage)
@@ -624,31 +484,36 @@ static int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden
 static int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, int B, int H, int Wd,
                           hipStream_t st, bool have_ln = false, bool out_bf16 = false) {
     const int Ci = kDims[i - 1], Co = kDims[i];
-    if (c->precision == ACX_PREC_F32_SPLIT) {
-        if (!have_ln) ACX_TRY(launch_layernorm_rows_split(c, x, xnorm, (int64_t)B * H * Wd, Ci, st));
-        GemmSplitArgs g{};
-        g.A = xnorm; g.Wt = c->down[i].ws; g.bias = c->down[i].b; g.out = out;
-        g.gather = 1; g.H = H; g.W = Wd; g.C = Ci; g.Ho = H / 2; g.Wo = Wd / 2;
-        g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.K = 4 * Ci; g.sinv = 1.0f / (kSplitLnScale * c->down[i].ws_scale);
-        g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
-        return launch_gemm_split(c, g, st);
+    const DownW& d = c->down[i];
+    switch (c->precision) {
+        case ACX_PREC_F32: {
+            ACX_TRY(launch_layernorm_rows(c, x, xnorm, (int64_t)B * H * Wd, Ci, st));
+            GemmArgs g{};
+            g.A = xnorm; g.Wt = d.w; g.bias = d.b; g.out = out;
+            g.gather = 1; g.H = H; g.W = Wd; g.C = Ci; g.Ho = H / 2; g.Wo = Wd / 2;
+            g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.K = 4 * Ci; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
+            return launch_gemm(c, g, st);
+        }
+        case ACX_PREC_F32_SPLIT: {
+            if (!have_ln) ACX_TRY(launch_layernorm_rows_split(c, x, xnorm, (int64_t)B * H * Wd, Ci, st));
+            GemmSplitArgs g{};
+            g.A = xnorm; g.Wt = d.ws; g.bias = d.b; g.out = out;
+            g.gather = 1; g.H = H; g.W = Wd; g.C = Ci; g.Ho = H / 2; g.Wo = Wd / 2;
+            g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.K = 4 * Ci; g.sinv = 1.0f / (kSplitLnScale * d.ws_scale);
+            g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
+            return launch_gemm_split(c, g, st);
+        }
+        default: {                                                              // bf16, bf16a
+            const int Cp = pad64(Ci);
+            if (!have_ln) ACX_TRY(launch_layernorm_rows_bf16(c, x, xnorm, (int64_t)B * H * Wd, Ci, st));
+            GemmBf16Args g{};
+            g.out_bf16 = out_bf16 ? 1 : 0;
+            g.A = xnorm; g.Wt = d.wh; g.bias = d.b; g.out = out;
+            g.gather = 1; g.H = H; g.W = Wd; g.Cp = Cp; g.Ho = H / 2; g.Wo = Wd / 2;
+            g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.Kp = 4 * Cp; g.lda = Cp; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
+            return launch_gemm_bf16(c, g, st);
+        }
     }
-    if (is_bf16(c)) {
-        const int Cp = pad64(Ci);
-        if (!have_ln) ACX_TRY(launch_layernorm_rows_bf16(c, x, xnorm, (int64_t)B * H * Wd, Ci, st));
-        GemmBf16Args g{};
-        g.out_bf16 = out_bf16 ? 1 : 0;
-        g.A = xnorm; g.Wt = c->down[i].wh; g.bias = c->down[i].b; g.out = out;
-        g.gather = 1; g.H = H; g.W = Wd; g.Cp = Cp; g.Ho = H / 2; g.Wo = Wd / 2;
-        g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.Kp = 4 * Cp; g.lda = Cp; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
-        return launch_gemm_bf16(c, g, st);
-    }
-    ACX_TRY(launch_layernorm_rows(c, x, xnorm, (int64_t)B * H * Wd, Ci, st));
-    GemmArgs g{};
-    g.A = xnorm; g.Wt = c->down[i].w; g.bias = c->down[i].b; g.out = out;
-    g.gather = 1; g.H = H; g.W = Wd; g.C = Ci; g.Ho = H / 2; g.Wo = Wd / 2;
-    g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.K = 4 * Ci; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
-    return launch_gemm(c, g, st);
 }
 
 static int need_ready(const acx_ctx* c) {
@@ -909,7 +774,6 @@ static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode,
         // than the fp32 rows they would overwrite.
         if (s > 0) {
             const bool have_ln = block_can_emit_ln(c, s - 1);
-            if (act_bf16(c, s - 1) && !have_ln) ACX_FAIL(ACX_ERR_STATE, "bf16 activations: stage %d must hand its LayerNorm rows to the downsample conv", s - 1);
             ACX_TRY(run_downsample(c, s, x[s - 1], x[s], have_ln ? hidden : y, B, p.Hs[s - 1], p.Ws[s - 1], st, have_ln, act_bf16(c, s)));
         }
         for (int j = 0; j < kDepths[s]; ++j) {

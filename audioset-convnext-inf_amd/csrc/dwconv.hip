@@ -9,8 +9,6 @@
 // registers; an input row (13 LDS reads) feeds both output rows, a kernel row's 7 weights are read once for the
 // pair.  The input rows and the 49x32 weight slice are staged through LDS; the batch is streamed as ONE tall
 // image (see the kernel), every input element is fetched from HBM once per column strip.
-#include <type_traits>
-
 #include "acx_internal.h"
 
 namespace acx {
@@ -28,10 +26,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // into the ring slots of the TH oldest rows after them), so every input row is fetched once per strip
 // (the first tile-only version re-read its 6 halo rows per tile: FETCH_SIZE 1.93x the algorithmic bytes,
 // profiles/r01_c_pmc_per_kernel.csv) and HBM latency hides under the arithmetic.
-// BF: x and y are bf16 in HBM (ACX_PREC_BF16_ACT, stages 0-2): a 16-byte load carries 8 channels (a pixel's 32-channel
-// slice is 64 bytes), widened to fp32 on its way into the LDS ring; outputs are rounded to bf16 (nearest even) when they
-// leave.  Ring, weights, bias and all arithmetic stay fp32.
-template <int TW, int TH, bool BF = false>
+template <int TW, int TH>
 struct DwCfg {
     static constexpr int WT = 7;
     static constexpr int kStrips = TW / WT;
@@ -39,23 +34,21 @@ struct DwCfg {
     static constexpr int kCols = TW + 6;
     static constexpr int kRing = TH + 6;
     static constexpr int kRowF4 = kCols * 8;                      // float4 per ring row
-    static constexpr int kEPV = BF ? 8 : 4;                       // tensor elements per 16-byte load
-    static constexpr int kQ = kDwSlice / kEPV;                    // 16-byte loads per pixel slice
+    static constexpr int kQ = kDwSlice / 4;                       // float4 loads per pixel slice
     static constexpr int kStepF4 = TH * kCols * kQ;               // 16-byte loads fetched per step
     static constexpr int kStage = (kStepF4 + kThreads - 1) / kThreads;   // staging loads per thread
     static constexpr size_t kLdsBytes = (size_t)(kRing * kRowF4 + 49 * 8 + 256) * 16;   // ring + weights + sinks
 };
 
-template <int TW, int TH, bool BF>
+template <int TW, int TH>
 __global__ __launch_bounds__(256, 2) void dwconv7_kernel(const void* __restrict__ x_, void* __restrict__ y_,
                                                          const float* __restrict__ wt /*[49][C]*/,
                                                          const float* __restrict__ bias, int B, int H, int W,
                                                          int C, int tiles_w, int tiles_h, int n_seg,
                                                          unsigned magic /* floor(2^32 / (H + 3)) + 1 */) {
-    using Cfg = DwCfg<TW, TH, BF>;
-    using T = typename std::conditional<BF, __bf16, float>::type;
-    const T* __restrict__ x = reinterpret_cast<const T*>(x_);
-    T* __restrict__ y = reinterpret_cast<T*>(y_);
+    using Cfg = DwCfg<TW, TH>;
+    const float* __restrict__ x = reinterpret_cast<const float*>(x_);
+    float* __restrict__ y = reinterpret_cast<float*>(y_);
     static_assert(Cfg::kThreads == 256, "thread mapping assumes 256 threads");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* ring = reinterpret_cast<f32x4*>(smem);                  // [kRing][kCols][8]
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void dwconv7_kernel(const void* __restrict_
         if (i >= 49 * 8) i = 49 * 8 - 1;
         wreg[k] = *reinterpret_cast<const f32x4*>(wt + (i >> 3) * C + c0 + 4 * (i & 7));
     }
-    const T* xb = x + c0;
+    const float* xb = x + c0;
     // The B images of the batch form ONE tall virtual image: H rows of clip 0, 3 rows of zeros, H rows of clip 1,
     // ... (3 zero rows are all the 7x7 window ever sees between two clips, and consecutive clips are
     // consecutive in memory), so the ring streams straight through the batch and a workgroup lives for many
@@ -106,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void dwconv7_kernel(const void* __restrict_
     // Loads are UNCONDITIONAL on valid addresses (a per-element "load or zero" makes hipcc branch around every
     // load and wait for all of them on the spot); rows outside the image only occur in the first/last step of a
     // column and take the slow (clamp + zero) path, selected by a wave-uniform test.
-    const T* st_ptr[Cfg::kStage];
+    const float* st_ptr[Cfg::kStage];
     int st_row[Cfg::kStage], st_lds[Cfg::kStage];
 #pragma unroll
     for (int k = 0; k < Cfg::kStage; ++k) {
@@ -118,8 +111,8 @@ __global__ __launch_bounds__(256, 2) void dwconv7_kernel(const void* __restrict_
         st_row[k] = (i / Cfg::kQ) / Cfg::kCols;
         const int gw = w0 - 3 + col;
         const int gwc = gw < 0 ? 0 : (gw >= W ? W - 1 : gw);
-        st_ptr[k] = xb + st_row[k] * row_elems + gwc * C + Cfg::kEPV * qq;
-        st_lds[k] = (in_step && gw >= 0 && gw < W) ? (col * 8 + qq * (8 / Cfg::kQ)) : -1;     // BF: two float4 from here
+        st_ptr[k] = xb + st_row[k] * row_elems + gwc * C + 4 * qq;
+        st_lds[k] = (in_step && gw >= 0 && gw < W) ? (col * 8 + qq) : -1;
     }
     const int g_origin = t_begin * TH - 3;             // image row kept in ring row 0 of this segment
     f32x4 rg[Cfg::kStage];
@@ -150,13 +143,7 @@ __global__ __launch_bounds__(256, 2) void dwconv7_kernel(const void* __restrict_
                 if (!ok_) v = f32x4{0.f, 0.f, 0.f, 0.f};                                                  \
             }                                                                                             \
             f32x4* dst = keep ? ring + slot * Cfg::kRowF4 + st_lds[k] : dummy + tid;                      \
-            if (BF) {                               /* 8 bf16 -> two float4 (channels 8 qq .. 8 qq + 7) */   \
-                const uint4 u_ = __builtin_bit_cast(uint4, v);                                            \
-                dst[0] = f32x4{acx_bf16_lo(u_.x), acx_bf16_hi(u_.x), acx_bf16_lo(u_.y), acx_bf16_hi(u_.y)};   \
-                (keep ? dst + 1 : dst)[0] = f32x4{acx_bf16_lo(u_.z), acx_bf16_hi(u_.z), acx_bf16_lo(u_.w), acx_bf16_hi(u_.w)}; \
-            } else {                                                                                      \
-                *dst = v;                                                                                 \
-            }                                                                                             \
+            *dst = v;                                                                                     \
         }                                                                                                 \
     }
 #define ACX_DW_STORE(first_row, max_rows, edge) ACX_DW_STORE_FROM(rg, first_row, max_rows, edge)
@@ -191,15 +178,14 @@ __global__ __launch_bounds__(256, 2) void dwconv7_kernel(const void* __restrict_
     constexpr int kRowF2 = Cfg::kRowF4 * 2;
     const f32x2 bv = *reinterpret_cast<const f32x2*>(bias + c0 + 2 * l16);
     const int rd_off = (strip * Cfg::WT) * 16 + l16;   // float2 offset of this thread's first input column
-    T* const yb = y + (long long)(w0 + strip * Cfg::WT) * C + c0 + 2 * l16;
+    float* const yb = y + (long long)(w0 + strip * Cfg::WT) * C + c0 + 2 * l16;
 
     f32x2 so0[Cfg::WT], so1[Cfg::WT];
 #pragma unroll
     for (int i = 0; i < Cfg::WT; ++i) so0[i] = so1[i] = bv;
-    T *yp0 = nullptr, *yp1 = nullptr;                  // where so0[] / so1[] belong (null: nothing pending)
+    float *yp0 = nullptr, *yp1 = nullptr;                  // where so0[] / so1[] belong (null: nothing pending)
 #define ACX_DW_FLUSH1(yp_, so_) if (yp_ != nullptr) { _Pragma("unroll") for (int i = 0; i < Cfg::WT; ++i) {         \
-        if (BF) *reinterpret_cast<unsigned*>(yp_ + (long long)i * C) = acx_pack_bf16x2(so_[i].x, so_[i].y);           \
-        else *reinterpret_cast<f32x2*>(yp_ + (long long)i * C) = so_[i]; } }
+        *reinterpret_cast<f32x2*>(yp_ + (long long)i * C) = so_[i]; } }
 #define ACX_DW_FLUSH ACX_DW_FLUSH1(yp0, so0) ACX_DW_FLUSH1(yp1, so1)
     for (int t = t_begin; t < t_end; ++t) {
         const int h0 = t * TH;
@@ -464,21 +450,21 @@ int launch_layernorm_rows_bf16(acx_ctx* c, const float* x, void* out, int64_t M,
     return launch_rows<2>(c, x, reinterpret_cast<float*>(out), M, C, s);
 }
 
-template <int TW, int TH, bool BF>
+template <int TW, int TH>
 static int launch_dw_cfg(const BlockW& w, int C, const void* x, void* y, int B, int H, int W, hipStream_t s) {
     // exactness of v / (H + 3) by multiply-high needs (stacked rows) * (H + 3) < 2^32: longer batches in chunks
     const long long max_b = (0xffffffffll / (H + 3)) / (H + 3);
     if (B > max_b) {
         for (long long b0 = 0; b0 < B; b0 += max_b) {
             const int nb = (int)((B - b0) < max_b ? (B - b0) : max_b);
-            const long long off = b0 * (long long)H * W * C * (BF ? 2 : 4);
-            ACX_TRY((launch_dw_cfg<TW, TH, BF>(w, C, reinterpret_cast<const char*>(x) + off, reinterpret_cast<char*>(y) + off, nb, H, W, s)));
+            const long long off = b0 * (long long)H * W * C * 4;
+            ACX_TRY((launch_dw_cfg<TW, TH>(w, C, reinterpret_cast<const char*>(x) + off, reinterpret_cast<char*>(y) + off, nb, H, W, s)));
         }
         return ACX_OK;
     }
-    using Cfg = DwCfg<TW, TH, BF>;
+    using Cfg = DwCfg<TW, TH>;
     static DeviceOnce once;
-    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_kernel<TW, TH, BF>, Cfg::kLdsBytes));
+    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_kernel<TW, TH>, Cfg::kLdsBytes));
     const int Hv = B * (H + 3) - 3;                    // stacked rows (no gap after the last clip)
     const int tiles_w = W / TW, tiles_h = (Hv + TH - 1) / TH;
     const long long columns = (long long)tiles_w * (C / kDwSlice);
@@ -490,7 +476,7 @@ static int launch_dw_cfg(const BlockW& w, int C, const void* x, void* y, int B, 
     if (n_seg > tiles_h / 2) n_seg = tiles_h / 2;
     if (n_seg < 1) n_seg = 1;
     const long long blocks = columns * n_seg;
-    launch_kernel(&dwconv7_kernel<TW, TH, BF>, dim3((unsigned)blocks), dim3(Cfg::kThreads), Cfg::kLdsBytes, s,
+    launch_kernel(&dwconv7_kernel<TW, TH>, dim3((unsigned)blocks), dim3(Cfg::kThreads), Cfg::kLdsBytes, s,
         x, y, w.dw, w.dwb, B, H, W, C, tiles_w, tiles_h, n_seg, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
@@ -505,25 +491,22 @@ static int launch_dw_cfg(const BlockW& w, int C, const void* x, void* y, int B, 
 // streaming kernel: an input row (13 reads) feeds both output rows, a kernel row's 7 weights are read once for the pair.
 // W = 7: the two groups of a half-wave read rows two apart -- the row stride is padded by 64 B so that 2 strides = 128
 // (mod 256): disjoint banks; W = 14: they read the two strips of one row, 896 B apart: disjoint as it is.
-// BF: x and y are bf16 (ACX_PREC_BF16_ACT, stage 2): 16-byte loads carry 8 channels, widened on their way into the LDS.
-template <int W, bool BF>
+template <int W>
 struct DwTileCfg {
     static constexpr int kStrips = W / 7;
     static constexpr int kRows = 32 / kStrips;                   // output rows per tile: 16 groups = row pairs x strips
     static constexpr int kCols = W + 6;
     static constexpr int kRowBytes = kCols * 128 + (kStrips == 1 ? 64 : 0);
-    static constexpr int kEPV = BF ? 8 : 4;                      // tensor elements per 16-byte load
-    static constexpr int kQ = kDwSlice / kEPV;                   // 16-byte loads per pixel slice
+    static constexpr int kQ = kDwSlice / 4;                      // float4 loads per pixel slice
     static constexpr int kLoads = ((kRows + 6) * W * kQ + 255) / 256;     // per thread
     static constexpr size_t kLdsBytes = (size_t)(kRows + 6) * kRowBytes + 49 * 128;
 };
 
-template <int W, bool BF>
+template <int W>
 __global__ __launch_bounds__(256, 2) void dwconv7_tile_kernel(const void* __restrict__ x_, void* __restrict__ y_,
                                                               const float* __restrict__ wt /*[49][C]*/,
                                                               const float* __restrict__ bias, int H, int C, int tiles_h) {
-    using Cfg = DwTileCfg<W, BF>;
-    using T = typename std::conditional<BF, __bf16, float>::type;
+    using Cfg = DwTileCfg<W>;
     constexpr int kRowBytes = Cfg::kRowBytes, kIn = Cfg::kRows + 6;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* img = smem;                                                           // [kIn][Cfg::kCols][32] fp32, rows kRowBytes apart
@@ -536,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void dwconv7_tile_kernel(const void* __rest
     const int c0 = slice * kDwSlice;
     const int r0 = th * Cfg::kRows;                                             // first output row of the tile
     const int tid = threadIdx.x;
-    const T* xb = reinterpret_cast<const T*>(x_) + b * (long long)H * W * C + c0;
+    const float* xb = reinterpret_cast<const float*>(x_) + b * (long long)H * W * C + c0;
     // every load of the workgroup is requested before anything waits: the tile's rows r0 - 3 .. r0 + kRows + 2 (rows outside
     // the image: clamped address, zeroed below) and the 49 x 32 weights
     f32x4 v[Cfg::kLoads], wreg[2];
@@ -547,7 +530,7 @@ __global__ __launch_bounds__(256, 2) void dwconv7_tile_kernel(const void* __rest
         const int q = i % Cfg::kQ, px = i / Cfg::kQ, lr = px / W, cidx = px - lr * W;
         int r = r0 - 3 + lr;
         r = r < 0 ? 0 : (r >= H ? H - 1 : r);
-        v[k] = *reinterpret_cast<const f32x4*>(xb + (long long)(r * W + cidx) * C + Cfg::kEPV * q);
+        v[k] = *reinterpret_cast<const f32x4*>(xb + (long long)(r * W + cidx) * C + 4 * q);
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -570,15 +553,7 @@ __global__ __launch_bounds__(256, 2) void dwconv7_tile_kernel(const void* __rest
             const int r = r0 - 3 + lr;
             const bool inside = r >= 0 && r < H;
             char* dst = img + lr * kRowBytes + (cidx + 3) * 128;
-            if (BF) {                                   // 8 bf16 -> two float4 (channels 8 q .. 8 q + 7)
-                const uint4 u = __builtin_bit_cast(uint4, v[k]);
-                f32x4 lo4 = {acx_bf16_lo(u.x), acx_bf16_hi(u.x), acx_bf16_lo(u.y), acx_bf16_hi(u.y)};
-                f32x4 hi4 = {acx_bf16_lo(u.z), acx_bf16_hi(u.z), acx_bf16_lo(u.w), acx_bf16_hi(u.w)};
-                *reinterpret_cast<f32x4*>(dst + 32 * q) = inside ? lo4 : zero;
-                *reinterpret_cast<f32x4*>(dst + 32 * q + 16) = inside ? hi4 : zero;
-            } else {
-                *reinterpret_cast<f32x4*>(dst + 16 * q) = inside ? v[k] : zero;
-            }
+            *reinterpret_cast<f32x4*>(dst + 16 * q) = inside ? v[k] : zero;
         }
     }
 #pragma unroll
@@ -624,16 +599,14 @@ __global__ __launch_bounds__(256, 2) void dwconv7_tile_kernel(const void* __rest
     for (int ky = 1; ky < 7; ++ky) ACX_DWI_ROW(ky, true, true)
     ACX_DWI_ROW(7, false, true)
 #undef ACX_DWI_ROW
-    T* yb = reinterpret_cast<T*>(y_) + b * (long long)H * W * C + c0 + 2 * l16;
+    float* yb = reinterpret_cast<float*>(y_) + b * (long long)H * W * C + c0 + 2 * l16;
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
         const int r = r0 + 2 * rp + o;
         if (r < H) {
 #pragma unroll
             for (int p = 0; p < 7; ++p) {
-                T* dst = yb + (long long)(r * W + 7 * strip + p) * C;
-                if (BF) *reinterpret_cast<unsigned*>(dst) = acx_pack_bf16x2(acc[o][p].x, acc[o][p].y);
-                else *reinterpret_cast<f32x2*>(dst) = acc[o][p];
+                *reinterpret_cast<f32x2*>(yb + (long long)(r * W + 7 * strip + p) * C) = acc[o][p];
             }
         }
     }
@@ -643,23 +616,23 @@ __global__ __launch_bounds__(256, 2) void dwconv7_tile_kernel(const void* __rest
 // rows prefetched into registers (one round of 512 workgroups): 47 vs 56 us per stage-2 launch at B = 64 -- with two
 // workgroups per CU the hardware overlaps one's load phase with the other's arithmetic better than a software pipeline with
 // two barriers per tile does.
-template <int W, bool BF>
+template <int W>
 static int launch_dw_tile(const BlockW& w, int C, const void* x, void* y, int B, int H, hipStream_t s) {
-    using Cfg = DwTileCfg<W, BF>;
+    using Cfg = DwTileCfg<W>;
     const int tiles_h = (H + Cfg::kRows - 1) / Cfg::kRows;
     const long long per_clip = (long long)tiles_h * (C / kDwSlice);
     const long long max_b = 0x3fffffffll / per_clip;           // grid limit: longer batches in chunks of clips
     if (B > max_b) {
         for (long long b0 = 0; b0 < B; b0 += max_b) {
             const int nb = (int)((B - b0) < max_b ? (B - b0) : max_b);
-            const long long off = b0 * (long long)H * W * C * (BF ? 2 : 4);
-            ACX_TRY((launch_dw_tile<W, BF>(w, C, reinterpret_cast<const char*>(x) + off, reinterpret_cast<char*>(y) + off, nb, H, s)));
+            const long long off = b0 * (long long)H * W * C * 4;
+            ACX_TRY((launch_dw_tile<W>(w, C, reinterpret_cast<const char*>(x) + off, reinterpret_cast<char*>(y) + off, nb, H, s)));
         }
         return ACX_OK;
     }
     static DeviceOnce once;
-    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_tile_kernel<W, BF>, Cfg::kLdsBytes));
-    launch_kernel(&dwconv7_tile_kernel<W, BF>, dim3((unsigned)(B * per_clip)), dim3(256), Cfg::kLdsBytes, s, x, y, w.dw, w.dwb, H, C, tiles_h);
+    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_tile_kernel<W>, Cfg::kLdsBytes));
+    launch_kernel(&dwconv7_tile_kernel<W>, dim3((unsigned)(B * per_clip)), dim3(256), Cfg::kLdsBytes, s, x, y, w.dw, w.dwb, H, C, tiles_h);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
@@ -668,7 +641,7 @@ static int launch_dw_tile(const BlockW& w, int C, const void* x, void* y, int B,
 // halo rows and their prologue: one wave per SIMD of the CUs this launch may count on (all of them, or its share while
 // acx_forward runs several sub-batches side by side).  Same bits either way (same accumulation order per output element);
 // ACX_DW_STREAM = 0 | 1 forces a form (tests).
-static bool use_col_kernel(const acx_ctx* c, int B, int H, int W, bool act_bf16, int* target_waves) {
+static bool use_col_kernel(const acx_ctx* c, int B, int H, int W, int* target_waves) {
     if (!c || !c->d_dw_sink) return false;
     const int force = tuning().dw_stream.load(std::memory_order_relaxed);
     if (force == 0) return false;
@@ -678,39 +651,43 @@ static bool use_col_kernel(const acx_ctx* c, int B, int H, int W, bool act_bf16,
     const long long Vt = (long long)B * (H + 3) - 3;
     if ((Vt + 16ll * (H + 3) + 64) * (H + 3) >= 0xffffffffll) return false;   // beyond the multiply-high division of the column kernel: the ring kernel chunks
     if (force == 1) return true;
-    // rows of the stacked batch per wave segment (dwconv_col.hip: one wave per SIMD in the fp32 stages 0-1, two elsewhere)
-    const bool two = act_bf16 || W <= 14;
+    // rows of the stacked batch per wave segment (dwconv_col.hip: one wave per SIMD in stages 0-1, two in stages 2-3)
+    const bool two = W <= 14;
     const long long segs = (long long)*target_waves * (two ? 2 : 1) / 6;
     return Vt / (segs > 0 ? segs : 1) >= (two ? (W == 7 ? 6 : 10) : 40);
 }
 
 int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, int B, int H,
                   int W, hipStream_t s, bool act_bf16) {
-    if (act_bf16 && stats) ACX_FAIL(ACX_ERR_STATE, "dwconv7: row statistics are computed from fp32 activations only");
+    const bool model_shape = C == 96 * 56 / (W > 0 ? W : 1);
+    if (act_bf16) {
+        // bf16 activations (stages 0-2 of "bf16a"): the matrix-pipe kernel, at every launch size -- its arithmetic (bf16 weights,
+        // its own summation order) must not depend on the batch
+        if (stats) ACX_FAIL(ACX_ERR_STATE, "dwconv7: row statistics are computed from fp32 activations only");
+        if (!c || !c->d_dw_sink || !w.dw_ops || !model_shape || W == 7)
+            ACX_FAIL(ACX_ERR_STATE, "dwconv7: bf16 activations need the matrix-pipe kernel and its packed weights (stages 0-2)");
+        ProfScope ps(c, ACX_K_DWCONV, s);
+        int cus = 0;
+        ACX_TRY(cu_count_of_current_device(&cus));
+        const int per_cu = tuning().dwm_waves.load(std::memory_order_relaxed);
+        return launch_dwconv_mfma(x, y, w.dw_ops, w.dwb, c->d_dw_sink, B, H, W, (per_cu ? per_cu : 8) * cus / inflight_ways(), s);
+    }
     {
         ProfScope ps(c, ACX_K_DWCONV, s);
         int rc, target_waves = 0;
-        // bf16 activations (stages 0-2 of "bf16a"): the matrix-pipe kernel, at every launch size -- its arithmetic (bf16 weights,
-        // its own summation order) must not depend on the batch
-        if (act_bf16 && c && c->d_dw_sink && w.dw_ops && C == 96 * 56 / (W > 0 ? W : 1) && W != 7 && tuning().dw_mfma.load(std::memory_order_relaxed) != 0) {
-            int cus = 0;
-            ACX_TRY(cu_count_of_current_device(&cus));
-            const int per_cu = tuning().dwm_waves.load(std::memory_order_relaxed);
-            return launch_dwconv_mfma(x, y, w.dw_ops, w.dwb, c->d_dw_sink, B, H, W, (per_cu ? per_cu : 8) * cus / inflight_ways(), s);
-        }
-        if (C == 96 * 56 / (W > 0 ? W : 1) && !act_bf16 && use_col_kernel(c, B, H, W, act_bf16, &target_waves)) {
-            rc = launch_dwconv_col(x, y, w.dw, w.dwb, c->d_dw_sink, B, H, W, act_bf16, target_waves, s);
+        if (model_shape && use_col_kernel(c, B, H, W, &target_waves)) {
+            rc = launch_dwconv_col(x, y, w.dw, w.dwb, c->d_dw_sink, B, H, W, target_waves, s);
             ACX_TRY(rc);
             if (stats) ACX_TRY(launch_rowstats(c, reinterpret_cast<const float*>(y), stats, (int64_t)B * H * W, C, s));
             return ACX_OK;
         }
         switch (W) {
-            case 56: rc = act_bf16 ? launch_dw_cfg<28, 8, true>(w, C, x, y, B, H, W, s) : launch_dw_cfg<28, 8, false>(w, C, x, y, B, H, W, s); break;
-            case 28: rc = act_bf16 ? launch_dw_cfg<28, 8, true>(w, C, x, y, B, H, W, s) : launch_dw_cfg<28, 8, false>(w, C, x, y, B, H, W, s); break;
+            case 56: rc = launch_dw_cfg<28, 8>(w, C, x, y, B, H, W, s); break;
+            case 28: rc = launch_dw_cfg<28, 8>(w, C, x, y, B, H, W, s); break;
             // stages 2 and 3: one row tile of one clip per workgroup (cache-resident tensors; the streaming kernel's long-lived
             // workgroups pay off only where every input row must come from HBM exactly once)
-            case 14: rc = act_bf16 ? launch_dw_tile<14, true>(w, C, x, y, B, H, s) : launch_dw_tile<14, false>(w, C, x, y, B, H, s); break;
-            case 7: rc = act_bf16 ? launch_dw_tile<7, true>(w, C, x, y, B, H, s) : launch_dw_tile<7, false>(w, C, x, y, B, H, s); break;
+            case 14: rc = launch_dw_tile<14>(w, C, x, y, B, H, s); break;
+            case 7: rc = launch_dw_tile<7>(w, C, x, y, B, H, s); break;
             default: ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: unsupported width %d (expected 56/28/14/7)", W);
         }
         ACX_TRY(rc);

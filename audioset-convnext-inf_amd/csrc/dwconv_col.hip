@@ -27,8 +27,6 @@
 // One wave per SIMD (230 registers: a second wave would not fit, and would double the segments and their halo rows).
 // A lone wave issues v_pk_fma_f32 at ~4.6 cycles (peak 4); what it cannot hide behind a partner it hides behind its own
 // deep prefetch: the FMAs (~85 us at B = 64 in stage 0) run entirely under the memory time (~125 us).
-#include <type_traits>
-
 #include "acx_internal.h"
 
 namespace acx {
@@ -39,7 +37,7 @@ typedef float dwc_f32x4 __attribute__((ext_vector_type(4)));
 // R: rows of the wave's ring.  7 = the phases of the accumulator rotation: slot addresses are immediates of the unrolled loop
 // (one wave per SIMD has the LDS for it).  Smaller rings -- two waves per SIMD, 20 KB of LDS each -- walk their slots with two
 // running byte offsets.
-template <int W, bool BF, int R = 7>
+template <int W, int R = 7>
 struct DwColCfg {
     static constexpr int kC = 96 * 56 / W;                        // channels of the stage with this width
     static constexpr int kStrips = W >= 28 ? 4 : W / 7;           // strips of 7 output pixels per wave (16 lanes each)
@@ -49,7 +47,7 @@ struct DwColCfg {
     static constexpr int kUnits = kHalves * (kC / 32 / kSlices);  // wave columns per image row: 6 in every stage
     static constexpr int kHalo = W == 7 ? 0 : 3;                  // W = 7: the halo columns are all outside the image: their taps are skipped
     static constexpr int kSlots = kPx + 2 * kHalo;                // pixel slots of a ring row per slice
-    static constexpr int kEsz = BF ? 2 : 4;
+    static constexpr int kEsz = 4;                                // bytes per tensor element (fp32)
     static constexpr int kSlotB = 32 * kEsz;                      // bytes of a pixel's 32-channel slice
     static constexpr int kLanesPerSlot = kSlotB / 16;
     static constexpr int kSPP = 1024 / kSlotB;                    // slots per 1-KB DMA piece
@@ -58,7 +56,7 @@ struct DwColCfg {
     static constexpr int kPieces = kSlices * kPiecesPerSlice;
     static constexpr int kRowB = kSlices * kSlots * kSlotB;       // bytes of a ring row
     static constexpr int kRing = R;
-    static constexpr int kD = (BF ? 6 : 5) < R - 1 ? (BF ? 6 : 5) : R - 1;   // rows in flight ahead of the one being multiplied
+    static constexpr int kD = 5 < R - 1 ? 5 : R - 1;              // rows in flight ahead of the one being multiplied
     // Every step issues exactly kPieces DMAs and 7 stores (invalid ones go to a sink), in that order behind its wait:
     // the row of step t was requested at step t - kD, followed by that step's 7 stores and kD - 1 whole steps.
     static constexpr int kWait = 7 + (kD - 1) * (kPieces + 7);
@@ -87,7 +85,7 @@ __device__ unsigned long long acx_dwc_stamps[4096 * 8];
 #define ACX_DWC_PKFMA(acc_, a_, b_) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(acc_) : "v"(a_), "v"(b_))
 #define ACX_DWC_PKFMA_INIT(acc_, a_, b_, c_) asm volatile("v_pk_fma_f32 %0, %1, %2, %3" : "+v"(acc_) : "v"(a_), "v"(b_), "v"(c_))
 
-template <int W, bool BF>
+template <int W>
 struct DwColState {
     dwc_f32x2 acc[7][7];      // [phase slot][pixel]
     dwc_f32x2 wt[49];
@@ -95,9 +93,9 @@ struct DwColState {
 };
 
 // lanes of piece k (within a slice) that fetch in-image columns
-template <int W, bool BF, int K>
+template <int W, int K>
 constexpr unsigned long long dwc_mask() {
-    using Cfg = DwColCfg<W, BF>;
+    using Cfg = DwColCfg<W>;
     unsigned long long m = 0;
     for (int lane = 0; lane < 64; ++lane)
         if (K * Cfg::kSPP + lane / Cfg::kLanesPerSlot < Cfg::kReal) m |= 1ull << lane;
@@ -110,18 +108,18 @@ constexpr unsigned long long dwc_mask() {
 // the offsets stay non-negative).  Full pieces first, then EXEC is narrowed once for the partial ones (their lanes beyond the
 // image stay out: those LDS slots hold zeros or the next slice).  6-8 instructions per row instead of 14.
 constexpr int kDwcAdj = 4096;
-template <int W, bool BF, int P>
+template <int W, int P>
 constexpr int dwc_piece_lds_off() {          // LDS distance of piece P from piece 0
-    using Cfg = DwColCfg<W, BF>;
+    using Cfg = DwColCfg<W>;
     return (P / Cfg::kPiecesPerSlice) * Cfg::kSlots * Cfg::kSlotB + (P % Cfg::kPiecesPerSlice) * 1024;
 }
-template <int W, bool BF>
-__device__ __forceinline__ void dwc_issue_row(const char* src, const unsigned (&voff)[DwColCfg<W, BF>::kPieces], unsigned lds0) {
-    using Cfg = DwColCfg<W, BF>;
+template <int W>
+__device__ __forceinline__ void dwc_issue_row(const char* src, const unsigned (&voff)[DwColCfg<W>::kPieces], unsigned lds0) {
+    using Cfg = DwColCfg<W>;
     if (ACX_DWC_ABLATE == 2) return;
     const char* base = src - kDwcAdj;
     constexpr int kLast = Cfg::kPiecesPerSlice - 1;
-    constexpr unsigned long long kMask = dwc_mask<W, BF, kLast>();          // the partial piece(s): the last of every slice
+    constexpr unsigned long long kMask = dwc_mask<W, kLast>();          // the partial piece(s): the last of every slice
     static_assert(kMask != ~0ull, "every layout ends its slices with a partial piece");
     unsigned long long keep;
     if constexpr (Cfg::kPieces == 4 && Cfg::kSlices == 1) {                 // W = 56 / 28 fp32: 0 1 2 full, 3 partial
@@ -129,34 +127,23 @@ __device__ __forceinline__ void dwc_issue_row(const char* src, const unsigned (&
                      "global_load_lds_dwordx4 %2, %6 offset:%c7\n\tglobal_load_lds_dwordx4 %3, %6 offset:%c8\n\tglobal_load_lds_dwordx4 %4, %6 offset:%c9\n\t"
                      "s_mov_b64 exec, %11\n\tglobal_load_lds_dwordx4 %5, %6 offset:%c10\n\ts_mov_b64 exec, %0"
                      : "=&s"(keep) : "s"(lds0), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(base),
-                       "n"(dwc_piece_lds_off<W, BF, 0>()), "n"(dwc_piece_lds_off<W, BF, 1>()), "n"(dwc_piece_lds_off<W, BF, 2>()), "n"(dwc_piece_lds_off<W, BF, 3>()),
+                       "n"(dwc_piece_lds_off<W, 0>()), "n"(dwc_piece_lds_off<W, 1>()), "n"(dwc_piece_lds_off<W, 2>()), "n"(dwc_piece_lds_off<W, 3>()),
                        "s"(kMask) : "memory");
     } else if constexpr (Cfg::kPieces == 4 && Cfg::kSlices == 2) {          // W = 14 fp32: 0, 2 full; 1, 3 partial
         asm volatile("s_mov_b32 m0, %1\n\ts_mov_b64 %0, exec\n\t"
                      "global_load_lds_dwordx4 %2, %6 offset:%c7\n\tglobal_load_lds_dwordx4 %4, %6 offset:%c9\n\t"
                      "s_mov_b64 exec, %11\n\tglobal_load_lds_dwordx4 %3, %6 offset:%c8\n\tglobal_load_lds_dwordx4 %5, %6 offset:%c10\n\ts_mov_b64 exec, %0"
                      : "=&s"(keep) : "s"(lds0), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(base),
-                       "n"(dwc_piece_lds_off<W, BF, 0>()), "n"(dwc_piece_lds_off<W, BF, 1>()), "n"(dwc_piece_lds_off<W, BF, 2>()), "n"(dwc_piece_lds_off<W, BF, 3>()),
+                       "n"(dwc_piece_lds_off<W, 0>()), "n"(dwc_piece_lds_off<W, 1>()), "n"(dwc_piece_lds_off<W, 2>()), "n"(dwc_piece_lds_off<W, 3>()),
                        "s"(kMask) : "memory");
-    } else if constexpr (Cfg::kPieces == 4) {                               // W = 7: four slices, one partial piece each
+    } else {                                                                // W = 7: four slices, one partial piece each
+        static_assert(Cfg::kPieces == 4 && Cfg::kSlices == 4, "piece layout");
         asm volatile("s_mov_b32 m0, %1\n\ts_mov_b64 %0, exec\n\ts_mov_b64 exec, %11\n\t"
                      "global_load_lds_dwordx4 %2, %6 offset:%c7\n\tglobal_load_lds_dwordx4 %3, %6 offset:%c8\n\t"
                      "global_load_lds_dwordx4 %4, %6 offset:%c9\n\tglobal_load_lds_dwordx4 %5, %6 offset:%c10\n\ts_mov_b64 exec, %0"
                      : "=&s"(keep) : "s"(lds0), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(base),
-                       "n"(dwc_piece_lds_off<W, BF, 0>()), "n"(dwc_piece_lds_off<W, BF, 1>()), "n"(dwc_piece_lds_off<W, BF, 2>()), "n"(dwc_piece_lds_off<W, BF, 3>()),
+                       "n"(dwc_piece_lds_off<W, 0>()), "n"(dwc_piece_lds_off<W, 1>()), "n"(dwc_piece_lds_off<W, 2>()), "n"(dwc_piece_lds_off<W, 3>()),
                        "s"(kMask) : "memory");
-    } else if constexpr (Cfg::kPieces == 2 && Cfg::kSlices == 1) {          // W = 56 / 28 bf16: 0 full, 1 partial
-        asm volatile("s_mov_b32 m0, %1\n\ts_mov_b64 %0, exec\n\t"
-                     "global_load_lds_dwordx4 %2, %4 offset:%c5\n\t"
-                     "s_mov_b64 exec, %7\n\tglobal_load_lds_dwordx4 %3, %4 offset:%c6\n\ts_mov_b64 exec, %0"
-                     : "=&s"(keep) : "s"(lds0), "v"(voff[0]), "v"(voff[1]), "s"(base),
-                       "n"(dwc_piece_lds_off<W, BF, 0>()), "n"(dwc_piece_lds_off<W, BF, 1>()), "s"(kMask) : "memory");
-    } else {                                                                // W = 14 bf16: two slices, one partial piece each
-        static_assert(Cfg::kPieces == 2 && Cfg::kSlices == 2, "piece layout");
-        asm volatile("s_mov_b32 m0, %1\n\ts_mov_b64 %0, exec\n\ts_mov_b64 exec, %7\n\t"
-                     "global_load_lds_dwordx4 %2, %4 offset:%c5\n\tglobal_load_lds_dwordx4 %3, %4 offset:%c6\n\ts_mov_b64 exec, %0"
-                     : "=&s"(keep) : "s"(lds0), "v"(voff[0]), "v"(voff[1]), "s"(base),
-                       "n"(dwc_piece_lds_off<W, BF, 0>()), "n"(dwc_piece_lds_off<W, BF, 1>()), "s"(kMask) : "memory");
     }
 }
 
@@ -170,9 +157,9 @@ __device__ __forceinline__ void dwc_issue_row(const char* src, const unsigned (&
 // Order: input column by input column, left to right; a column meets every kernel row before the next one is touched (each
 // column is first needed 7+ FMAs after the one before it: the wave waits for the first LDS read only; an accumulator returns
 // after >= 7 other FMAs).  For one output element that is kernel column 0 .. 6 -- the order of dwconv.hip.
-template <int W, bool BF, int I, int KLO, int KHI>
-__device__ __forceinline__ void dwc_row(DwColState<W, BF>& st, const char* rowp, bool real) {
-    using Cfg = DwColCfg<W, BF>;
+template <int W, int I, int KLO, int KHI>
+__device__ __forceinline__ void dwc_row(DwColState<W>& st, const char* rowp, bool real) {
+    using Cfg = DwColCfg<W>;
     constexpr int slot0 = (I + 6) % 7;            // the output row that starts here (kernel row 0)
     if (real) {
         dwc_f32x2 in[13];
@@ -180,12 +167,7 @@ __device__ __forceinline__ void dwc_row(DwColState<W, BF>& st, const char* rowp,
         for (int j = 0; j < 13; ++j) {
             if (W == 7 && (j < 3 || j > 9)) continue;           // columns outside the image: zero, taps skipped
             const int s = W == 7 ? j - 3 : j;
-            if constexpr (BF) {
-                const unsigned u = *reinterpret_cast<const unsigned*>(rowp + s * Cfg::kSlotB);
-                in[j] = dwc_f32x2{acx_bf16_lo(u), acx_bf16_hi(u)};
-            } else {
-                in[j] = *reinterpret_cast<const dwc_f32x2*>(rowp + s * Cfg::kSlotB);
-            }
+            in[j] = *reinterpret_cast<const dwc_f32x2*>(rowp + s * Cfg::kSlotB);
         }
 #pragma unroll
         for (int j = 0; j < 13; ++j) {
@@ -213,13 +195,13 @@ __device__ __forceinline__ void dwc_row(DwColState<W, BF>& st, const char* rowp,
 // S0: a segment of n_out = 7 k7 - S0 output rows (any length >= 7) runs as a virtual segment of 7 k7 rows that starts S0 rows
 // higher and whose first S0 steps are not executed: the first and the last six executed steps then still sit at fixed phases of
 // the rotation, for every segment length (a multiple of 7 only would leave up to 12 % of the wave slots of stage 2 empty).
-template <int W, bool BF, int R, int WPS, int S0>
+template <int W, int R, int WPS, int S0>
 __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __restrict__ x_, void* __restrict__ y_,
                                                              const float* __restrict__ wt /*[49][C]*/,
                                                              const float* __restrict__ bias, void* __restrict__ sink_,
                                                              int B, int H, int k7 /* output rows per segment / 7 */, int n_items,
                                                              unsigned magic /* floor(2^32 / (H + 3)) + 1 */) {
-    using Cfg = DwColCfg<W, BF, R>;
+    using Cfg = DwColCfg<W, R>;
     static_assert(Cfg::kLdsBytes * WPS <= 160 * 1024, "the rings of a CU's waves do not fit the LDS");
     constexpr int C = Cfg::kC, kEsz = Cfg::kEsz, D = Cfg::kD;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -241,13 +223,13 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
     const int g4 = lane >> 4, l16 = lane & 15;
     const int strip = g4 % Cfg::kStrips, sl_i = g4 / Cfg::kStrips;
     const int ch = cbase + sl_i * 32 + 2 * l16;
-    DwColState<W, BF> st;
+    DwColState<W> st;
     // The 49 + 1 weight loads go out first -- 220 cycles of issue; their round trip then runs under the index arithmetic, the halo
     // zeroing and the issue of the first rows (nothing below touches them before the rows have been requested) ...
 #pragma unroll
     for (int t = 0; t < 49; ++t) st.wt[t] = *reinterpret_cast<const dwc_f32x2*>(wt + t * C + ch);
     st.bias = *reinterpret_cast<const dwc_f32x2*>(bias + ch);
-    const char* const rd = ring + sl_i * Cfg::kSlots * Cfg::kSlotB + strip * 7 * Cfg::kSlotB + l16 * (BF ? 4 : 8);
+    const char* const rd = ring + sl_i * Cfg::kSlots * Cfg::kSlotB + strip * 7 * Cfg::kSlotB + l16 * 8;
     const unsigned yoff = (unsigned)(((half * Cfg::kPx + strip * 7) * C + ch) * kEsz);
 
     // ---- DMA roles: a 1-KB piece = kSPP pixel slots, kLanesPerSlot lanes x 16 B each ----
@@ -325,7 +307,7 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
         const char* src_ = real_ ? pf_ptr : safe_src;                                                           \
         safe_src = src_;                                                                                        \
         pf_ptr += real_ ? Cfg::kGRowB : 0;                                                                      \
-        dwc_issue_row<W, BF>(src_, voff, ring_lds + (off_) + (unsigned)(first_real * Cfg::kSlotB));             \
+        dwc_issue_row<W>(src_, voff, ring_lds + (off_) + (unsigned)(first_real * Cfg::kSlotB));             \
     }
     ACX_DWC_FLAGS(0)
 #pragma unroll
@@ -343,7 +325,7 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
     {                                                                                                           \
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(ACX_DWC_ABLATE >= 2 ? 0 : Cfg::kWait) : "memory");           \
         ACX_DWC_PREFETCH((I_) + D + 3, (R == 7 ? (unsigned)((((I_) + D) % 7) * Cfg::kRowB) : pf_off))           \
-        dwc_row<W, BF, I_, KLO_, KHI_>(st, rd + (R == 7 ? (unsigned)((I_) * Cfg::kRowB) : cur_off), (rmask >> ((I_) + 3)) & 1u); \
+        dwc_row<W, I_, KLO_, KHI_>(st, rd + (R == 7 ? (unsigned)((I_) * Cfg::kRowB) : cur_off), (rmask >> ((I_) + 3)) & 1u); \
         if (R != 7) {                                                                                           \
             cur_off = cur_off + Cfg::kRowB == (unsigned)Cfg::kWaveLds ? 0u : cur_off + Cfg::kRowB;              \
             pf_off = pf_off + Cfg::kRowB == (unsigned)Cfg::kWaveLds ? 0u : pf_off + Cfg::kRowB;                 \
@@ -352,8 +334,7 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
         char* dst_ = (out_ok_ ? out_ptr : sink) + yoff;                                                         \
         out_ptr += out_ok_ ? Cfg::kGRowB : 0;                                                                   \
         _Pragma("unroll") for (int p = 0; p < (ACX_DWC_ABLATE == 3 ? 0 : 7); ++p) {                             \
-            if constexpr (BF) *reinterpret_cast<unsigned*>(dst_ + p * C * kEsz) = acx_pack_bf16x2(st.acc[I_][p].x, st.acc[I_][p].y); \
-            else *reinterpret_cast<dwc_f32x2*>(dst_ + p * C * kEsz) = st.acc[I_][p];                            \
+            *reinterpret_cast<dwc_f32x2*>(dst_ + p * C * kEsz) = st.acc[I_][p];                                 \
         }                                                                                                       \
     }
     // The first six executed steps (virtual steps S0 .. S0 + 5) meet kernel rows 0 .. step - S0 only (the output rows above the
@@ -387,12 +368,12 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
 // target_waves: how many waves the launch should consist of (one per SIMD of the CUs it may use).  Every wave takes a
 // segment of 7 k output rows of the stacked batch (the rotation has seven phases: the first and the last six steps then sit at
 // fixed phases and are compiled with their reduced kernel-row ranges).
-template <int W, bool BF, int R, int WPS, int S0>
+template <int W, int R, int WPS, int S0>
 static int launch_dw_col_s0(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H, int k7, int n_items, hipStream_t s) {
-    using Cfg = DwColCfg<W, BF, R>;
+    using Cfg = DwColCfg<W, R>;
     static DeviceOnce once;
-    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_col_kernel<W, BF, R, WPS, S0>, Cfg::kLdsBytes));
-    launch_kernel(&dwconv7_col_kernel<W, BF, R, WPS, S0>, dim3((unsigned)((n_items + 3) / 4)), dim3(256), Cfg::kLdsBytes, s,
+    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_col_kernel<W, R, WPS, S0>, Cfg::kLdsBytes));
+    launch_kernel(&dwconv7_col_kernel<W, R, WPS, S0>, dim3((unsigned)((n_items + 3) / 4)), dim3(256), Cfg::kLdsBytes, s,
         x, y, wt, bias, sink, B, H, k7, n_items, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
@@ -401,10 +382,10 @@ static int launch_dw_col_s0(const void* x, void* y, const float* wt, const float
 // target_waves: how many waves the launch should consist of (one per SIMD of the CUs it may use).  Every wave takes a segment
 // of n_out = ceil(rows / segments) output rows of the stacked batch; the kernel instantiation for n_out's remainder modulo the
 // rotation's seven phases (S0) runs it.
-template <int W, bool BF, int R, int WPS>
+template <int W, int R, int WPS>
 static int launch_dw_col_cfg(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H,
                              int target_waves, hipStream_t s) {
-    using Cfg = DwColCfg<W, BF, R>;
+    using Cfg = DwColCfg<W, R>;
     const long long Vt = (long long)B * (H + 3) - 3;
     // exactness of v / (H + 3) by multiply-high needs (stacked rows + 9 (H + 3) + slack) * (H + 3) < 2^32
     if ((Vt + 16ll * (H + 3) + 64) * (H + 3) >= 0xffffffffll)
@@ -419,31 +400,26 @@ static int launch_dw_col_cfg(const void* x, void* y, const float* wt, const floa
     const long long n_seg = (Vt + n_out - 1) / n_out;
     const int n_items = (int)(n_seg * Cfg::kUnits);
     switch (s0) {
-        case 0: return launch_dw_col_s0<W, BF, R, WPS, 0>(x, y, wt, bias, sink, B, H, k7, n_items, s);
-        case 1: return launch_dw_col_s0<W, BF, R, WPS, 1>(x, y, wt, bias, sink, B, H, k7, n_items, s);
-        case 2: return launch_dw_col_s0<W, BF, R, WPS, 2>(x, y, wt, bias, sink, B, H, k7, n_items, s);
-        case 3: return launch_dw_col_s0<W, BF, R, WPS, 3>(x, y, wt, bias, sink, B, H, k7, n_items, s);
-        case 4: return launch_dw_col_s0<W, BF, R, WPS, 4>(x, y, wt, bias, sink, B, H, k7, n_items, s);
-        case 5: return launch_dw_col_s0<W, BF, R, WPS, 5>(x, y, wt, bias, sink, B, H, k7, n_items, s);
-        default: return launch_dw_col_s0<W, BF, R, WPS, 6>(x, y, wt, bias, sink, B, H, k7, n_items, s);
+        case 0: return launch_dw_col_s0<W, R, WPS, 0>(x, y, wt, bias, sink, B, H, k7, n_items, s);
+        case 1: return launch_dw_col_s0<W, R, WPS, 1>(x, y, wt, bias, sink, B, H, k7, n_items, s);
+        case 2: return launch_dw_col_s0<W, R, WPS, 2>(x, y, wt, bias, sink, B, H, k7, n_items, s);
+        case 3: return launch_dw_col_s0<W, R, WPS, 3>(x, y, wt, bias, sink, B, H, k7, n_items, s);
+        case 4: return launch_dw_col_s0<W, R, WPS, 4>(x, y, wt, bias, sink, B, H, k7, n_items, s);
+        case 5: return launch_dw_col_s0<W, R, WPS, 5>(x, y, wt, bias, sink, B, H, k7, n_items, s);
+        default: return launch_dw_col_s0<W, R, WPS, 6>(x, y, wt, bias, sink, B, H, k7, n_items, s);
     }
 }
 
 // Occupancy by stage: the HBM-bound stages 0-1 in fp32 run one wave per SIMD (long segments: few halo rows, a deep ring);
-// wherever the FMAs are what takes the time -- the cache-resident stages 2-3, and every stage once the activations are bf16 --
-// two waves per SIMD (a second wave fills the issue slots a lone wave leaves: v_pk_fma_f32 issues every 5 cycles from one
+// wherever the FMAs are what takes the time -- the cache-resident stages 2-3 -- two waves per SIMD (a second wave fills the issue slots a lone wave leaves: v_pk_fma_f32 issues every 5 cycles from one
 // wave, every 4 from two) on half-length segments, whose extra halo rows come from the cache or weigh half.
 int launch_dwconv_col(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H, int W,
-                      bool act_bf16, int target_waves, hipStream_t s) {
-    // bf16 activations never come here in production: every launch of `bf16a` takes the matrix-pipe kernel (dwconv_mfma.hip), and
-    // the diagnostic switch ACX_DW_MFMA=0 falls back to the tile / ring kernels of dwconv.hip (same bits as this kernel).  Round 6
-    // removed the 21 bf16 instantiations of this file (1.2 MB of code objects no launch selected).
-    if (act_bf16) ACX_FAIL(ACX_ERR_STATE, "dwconv7 (column form): bf16 activations take the matrix-pipe kernel");
+                      int target_waves, hipStream_t s) {
     switch (W) {
-        case 56: return launch_dw_col_cfg<56, false, 7, 1>(x, y, wt, bias, sink, B, H, target_waves, s);
-        case 28: return launch_dw_col_cfg<28, false, 7, 1>(x, y, wt, bias, sink, B, H, target_waves, s);
-        case 14: return launch_dw_col_cfg<14, false, 4, 2>(x, y, wt, bias, sink, B, H, target_waves, s);
-        case 7: return launch_dw_col_cfg<7, false, 5, 2>(x, y, wt, bias, sink, B, H, target_waves, s);
+        case 56: return launch_dw_col_cfg<56, 7, 1>(x, y, wt, bias, sink, B, H, target_waves, s);
+        case 28: return launch_dw_col_cfg<28, 7, 1>(x, y, wt, bias, sink, B, H, target_waves, s);
+        case 14: return launch_dw_col_cfg<14, 4, 2>(x, y, wt, bias, sink, B, H, target_waves, s);
+        case 7: return launch_dw_col_cfg<7, 5, 2>(x, y, wt, bias, sink, B, H, target_waves, s);
         default: ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: unsupported width %d (expected 56/28/14/7)", W);
     }
 }

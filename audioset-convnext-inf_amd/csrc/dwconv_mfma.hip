@@ -34,7 +34,7 @@
 //     request re-reads an old row into a dummy row: the count stays fixed);
 //   * a finished tile is packed to bf16 and leaves at the start of the NEXT step, behind that step's wait: stores sit in the same
 //     in-order queue as the requests, and a wait must not stand behind stores that were issued a step ago;
-//   * the weight operands are packed once per model in exactly the register form (api.hip, BlockW::dw_ops): 42 loads per wave;
+//   * the weight operands are packed once per model in exactly the register form (dwconv_mfma_pack, BlockW::dw_ops): 42 loads per wave;
 //   * workgroups are numbered XCD-major and slices vary fastest: the two 64-byte halves of a 128-byte line and the six rows two
 //     segments share meet in one L2.
 #include "acx_internal.h"
@@ -178,7 +178,7 @@ __device__ __forceinline__ void dwm_run(const char* __restrict__ x, char* __rest
     }
     ACX_DWM_STAMP(1)
     // ---- weights: the lane's 21 x 2 operands B[kh][d = kq - jt + 1][set], packed once per model in exactly this form
-    // (api.hip, dw_ops: [slice][kh][d][set][lane] x 4 bf16): 42 coalesced 8-byte loads, in flight beside the first rows
+    // (dwconv_mfma_pack: [slice][kh][d][set][lane] x 4 bf16): 42 coalesced 8-byte loads, in flight beside the first rows
     dwm_s4 Bw[7][3][2];
     {
         const char* const ol = ops + (size_t)slice * (42 * 512) + lane * 8;
@@ -366,6 +366,26 @@ static int launch_dw_mfma_w(const void* x, void* y, const void* wt, const float*
         x, y, wt, bias, sink, B, H, (int)(rows / 4), n_groups, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
+}
+
+// The B operands of the 16-block 4x4x4 MFMA, one 8-byte load per lane and operand: [C/32][7][3][2][64 lanes][4] bf16.  Operand
+// (kernel row kh, d = input quad - output quad + 1, channel set) of lane (q = lane & 3, cl = lane >> 2) holds, for k = 0..3, the
+// weight of tap 4 d + k - q - 1 of row kh (zero outside 0..6) of channel 32 slice + 2 cl + set.
+std::vector<uint16_t> dwconv_mfma_pack(const std::vector<float>& dw, int C) {
+    std::vector<uint16_t> ops((size_t)(C / 32) * 42 * 64 * 4);
+    for (int sl = 0; sl < C / 32; ++sl)
+        for (int kh = 0; kh < 7; ++kh)
+            for (int d = 0; d < 3; ++d)
+                for (int st = 0; st < 2; ++st)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int q = lane & 3, ch = 32 * sl + 2 * (lane >> 2) + st;
+                        for (int k = 0; k < 4; ++k) {
+                            const int tp = 4 * d + k - q - 1;
+                            ops[((((size_t)(sl * 7 + kh) * 3 + d) * 2 + st) * 64 + lane) * 4 + k] =
+                                (tp >= 0 && tp < 7) ? to_bf16(dw[(size_t)ch * 49 + kh * 7 + tp]) : (uint16_t)0;
+                        }
+                    }
+    return ops;
 }
 
 // bf16 activations only (stages 0-2 of set_precision("bf16a")); target_waves as in launch_dwconv_col

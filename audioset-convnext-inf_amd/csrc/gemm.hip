@@ -62,8 +62,8 @@ __device__ __forceinline__ void lds_dma16(const float* gsrc, char* lds_wave_base
 }
 
 // GATHER: 0 plain rows, 1 2x2 patch gather (downsample)
-template <int kBM, int BN, int WM, int WN, int EPI, int GATHER, int DW>
-__global__ __launch_bounds__(256 + 64 * DW) void gemm_f32_kernel(GemmParams p) {
+template <int kBM, int BN, int WM, int WN, int EPI, int GATHER>
+__global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     constexpr int TM = kBM / (WM * 32);
     constexpr int TN = BN / (WN * 32);
     constexpr int A_TILE = kBM * kRowBytes, B_TILE = BN * kRowBytes;     // bytes
@@ -93,52 +93,6 @@ __global__ __launch_bounds__(256 + 64 * DW) void gemm_f32_kernel(GemmParams p) {
     const int n0 = tile_n * BN;
 
     const int prow = lane >> 3, pchunk = lane & 7;
-    if (DW && wave == 4) {
-        // ---- dedicated LDS-DMA wave: issues every 1-KB piece of both operand tiles, so the four MFMA waves
-        //      never spend issue slots on loads (an LDS-DMA costs 60-180 cycles of issue, MI355X_MICROARCH.md) --
-        constexpr int AP = kBM / 8, BP = BN / 8;
-        const float* a_all[AP];
-        const float* b_all[BP];
-#pragma unroll
-        for (int i = 0; i < AP; ++i) {
-            const int row = 8 * i + prow;
-            const int chunk = pchunk ^ ((row >> 1) & 7);
-            long long m = m0 + row;
-            if (m >= p.M) m = p.M - 1;
-            if (GATHER) {
-                const int wo = (int)(m % p.Wo);
-                const long long t = m / p.Wo;
-                const int ho = (int)(t % p.Ho);
-                const long long b = t / p.Ho;
-                a_all[i] = p.A + ((b * p.H + 2 * ho) * p.W + 2 * wo) * p.C + 4 * chunk;
-            } else {
-                a_all[i] = p.A + m * p.K + 4 * chunk;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < BP; ++i) {
-            const int row = 8 * i + prow;
-            const int chunk = pchunk ^ ((row >> 1) & 7);
-            b_all[i] = p.Wt + (long long)(n0 + row) * p.K + 4 * chunk;
-        }
-        const int nkd = p.K / kBK;
-        for (int kt = 0; kt < nkd; ++kt) {
-            const int k0 = kt * kBK;
-            long long koff = k0;
-            if (GATHER) {
-                const int qd = k0 / p.C;
-                koff = (long long)((qd >> 1) * p.W + (qd & 1)) * p.C + (k0 - qd * p.C);
-            }
-            char* ad = As + (kt & 1) * A_TILE;
-            char* bd = Bs + (kt & 1) * B_TILE;
-#pragma unroll
-            for (int i = 0; i < AP; ++i) lds_dma16(a_all[i] + koff, ad + i * 1024);
-#pragma unroll
-            for (int i = 0; i < BP; ++i) lds_dma16(b_all[i] + k0, bd + i * 1024);
-            __syncthreads();      // (hipcc drains the LDS-DMA first) pairs with the MFMA waves' barrier of tile kt
-        }
-        return;
-    }
     // ---- LDS-DMA source pointers: wave w stages rows [R*w, R*w+R) of each tile, 8 rows per piece ------
     const float* a_src[A_DMA];
 #pragma unroll
@@ -215,7 +169,7 @@ __global__ __launch_bounds__(256 + 64 * DW) void gemm_f32_kernel(GemmParams p) {
 #define ACX_MFMA_GROUP_DMA(af_, bf_, src_, n_, koff_, dst_)                                            \
     {                                                                                                  \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                \
-            if (!DW && e < (n_)) {                                                                     \
+            if (e < (n_)) {                                                                            \
                 lds_dma16(src_[e] + (koff_), (dst_) + e * 8 * kRowBytes);                              \
                 __builtin_amdgcn_sched_barrier(0);                                                     \
             }                                                                                          \
@@ -238,7 +192,7 @@ __global__ __launch_bounds__(256 + 64 * DW) void gemm_f32_kernel(GemmParams p) {
     }
 
     const int nk = p.K / kBK;
-    if (!DW) ACX_DMA_TILE(0, 0);
+    ACX_DMA_TILE(0, 0);
     __syncthreads();          // hipcc drains the LDS-DMA (vmcnt(0)) in front of the barrier
     // Software pipeline over k-tiles, ONE barrier per tile, placed BEFORE the last MFMA group so that
     // every wave leaves it with 4*TM*TN MFMAs already fed (barrier skew and the first LDS reads of the
@@ -365,21 +319,20 @@ __global__ __launch_bounds__(256 + 64 * DW) void gemm_f32_kernel(GemmParams p) {
 template <int BM, int BN>
 constexpr size_t gemm_lds_bytes() { return (size_t)2 * (BM + BN) * kRowBytes; }
 
-// DW = 1 builds the variant with a 5th, dedicated LDS-DMA wave.  Measured NEGATIVE on MI355X (tools/
-// gemm_lab: s2.pw1 657 vs 581 us, s2.pw2 742 vs 627 us): one wave cannot issue the 32 pieces of a tile and see
-// them land within one k-tile of MFMA time, so it becomes the critical path; 8 pieces on each MFMA wave is faster.
+// Every MFMA wave issues its own LDS-DMA pieces.  A 5th, dedicated LDS-DMA wave (removed after commit 07ba348) measured
+// NEGATIVE on MI355X (tools/gemm_lab: s2.pw1 657 vs 581 us, s2.pw2 742 vs 627 us): one wave cannot issue the 32 pieces of
+// a tile and see them land within one k-tile of MFMA time, so it becomes the critical path.
 template <int kBM, int BN, int WM, int WN, int EPI, int GATHER>
 static int launch_cfg(const GemmParams& p0, hipStream_t s) {
-    constexpr int DW = 0;
     GemmParams p = p0;
     p.tiles_n = p.N / BN;
     const long long tiles_m = (p.M + kBM - 1) / kBM;
     const long long blocks = tiles_m * p.tiles_n;
     if (blocks > 0x7fffffffLL) ACX_FAIL(ACX_ERR_SHAPE, "gemm: grid too large");
     static DeviceOnce once;
-    ACX_TRY(set_max_dynamic_lds(once, &gemm_f32_kernel<kBM, BN, WM, WN, EPI, GATHER, DW>, gemm_lds_bytes<kBM, BN>()));
+    ACX_TRY(set_max_dynamic_lds(once, &gemm_f32_kernel<kBM, BN, WM, WN, EPI, GATHER>, gemm_lds_bytes<kBM, BN>()));
     constexpr size_t lds = gemm_lds_bytes<kBM, BN>();
-    launch_kernel(&gemm_f32_kernel<kBM, BN, WM, WN, EPI, GATHER, DW>, dim3((unsigned)blocks), dim3(256 + 64 * DW), lds, s, p);
+    launch_kernel(&gemm_f32_kernel<kBM, BN, WM, WN, EPI, GATHER>, dim3((unsigned)blocks), dim3(256), lds, s, p);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

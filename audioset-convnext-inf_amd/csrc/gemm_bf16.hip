@@ -4,7 +4,7 @@
 //   A operands are bf16 in HBM: the fp32 LayerNorm pass writes its normalised rows as bf16 (ln_rows_bf16 in
 //   dwconv.hip), pwconv1's epilogue writes the hidden activation as bf16.  Weights are rounded to bf16 once
 //   at acx_finalize (K padded to a multiple of 64).
-// Same structure as gemm.hip, as 8-wave CU-exclusive workgroups (acx_internal.h): 256 x BN tiles, 128-B LDS rows (= 64 bf16 of K), both operands by LDS-DMA with
+// Same structure as gemm.hip, as 8-wave CU-exclusive workgroups (acx_internal.h): 256 / 128 x 192 tiles, 128-B LDS rows (= 64 bf16 of K), both operands by LDS-DMA with
 // the XOR swizzle on the source address, fragments double-buffered in registers, one barrier per k-tile.  A
 // fragment read is still one ds_read_b128: lane half h takes chunk 2g+h of its row = k 16g+8h .. +7, exactly
 // the A/B lane map of the 32x32x16 instruction, so one MFMA per (tile, k-group) replaces four fp32 ones.
@@ -323,22 +323,20 @@ static int launch_bf_cfg(const GemmBfParams& p0, hipStream_t s) {
 
 template <int EPI, int GATHER>
 static int launch_bf_bn(const GemmBfParams& p, int ways, hipStream_t s) {
-    if (p.N % 192 == 0) {                                                            // every N of the model
-        // 128-row tiles when all of them -- of every sub-batch in flight -- find a CU at once (small launches spread over twice the
-        // CUs; an output element sees the same MFMAs in the same order).  ACX_GEMM_MI = 1 | 2 forces them, 4 the 256-row tile.
-        int cus = 0;
-        ACX_TRY(cu_count_of_current_device(&cus));
-        bool narrow = (p.M + 127) / 128 * (p.N / 192) * ways <= cus;
-        if (const int f = tuning().gemm_mi.load(std::memory_order_relaxed)) narrow = f != 4;
-        if (narrow) return launch_bf_cfg<128, 192, 4, 2, EPI, GATHER>(p, s);
-        return launch_bf_cfg<256, 192, 4, 2, EPI, GATHER>(p, s);
-    }
-    if (p.N % 128 == 0) return launch_bf_cfg<256, 128, 4, 2, EPI, GATHER>(p, s);
-    ACX_FAIL(ACX_ERR_SHAPE, "gemm_bf16: N=%d is not a multiple of 192 or 128", p.N);
+    // 128-row tiles when all of them -- of every sub-batch in flight -- find a CU at once (small launches spread over twice the
+    // CUs; an output element sees the same MFMAs in the same order).  ACX_GEMM_MI = 1 | 2 forces them, 4 the 256-row tile.
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    bool narrow = (p.M + 127) / 128 * (p.N / 192) * ways <= cus;
+    if (const int f = tuning().gemm_mi.load(std::memory_order_relaxed)) narrow = f != 4;
+    if (narrow) return launch_bf_cfg<128, 192, 4, 2, EPI, GATHER>(p, s);
+    return launch_bf_cfg<256, 192, 4, 2, EPI, GATHER>(p, s);
 }
 
 int launch_gemm_bf16(acx_ctx* c, const GemmBf16Args& a, hipStream_t s) {
     if (a.Kp % kBfBK != 0) ACX_FAIL(ACX_ERR_SHAPE, "gemm_bf16: padded K=%d is not a multiple of %d", a.Kp, kBfBK);
+    // 192-column tiles: every N of the model (192 .. 3072) is a multiple of 192
+    if (a.N % 192 != 0) ACX_FAIL(ACX_ERR_SHAPE, "gemm_bf16: N=%d is not a multiple of 192", a.N);
     if (a.M <= 0) return ACX_OK;
     GemmBfParams p;
     p.A = reinterpret_cast<const __bf16*>(a.A); p.Wt = reinterpret_cast<const __bf16*>(a.Wt); p.bias = a.bias;
@@ -353,8 +351,7 @@ int launch_gemm_bf16(acx_ctx* c, const GemmBf16Args& a, hipStream_t s) {
     if (a.out_bf16) ACX_FAIL(ACX_ERR_ARG, "gemm_bf16: bf16 output exists for the gather (downsample) form only");
     if (a.epi == EPI_GELU) return launch_bf_bn<1, 0>(p, ways, s);
     if (a.epi == EPI_RESID) return launch_bf_bn<2, 0>(p, ways, s);
-    if (a.epi == EPI_BIAS) return launch_bf_bn<0, 0>(p, ways, s);
-    ACX_FAIL(ACX_ERR_ARG, "gemm_bf16: unknown epilogue %d", a.epi);
+    ACX_FAIL(ACX_ERR_ARG, "gemm_bf16: epilogue %d without the 2x2 gather", a.epi);
 }
 
 }  // namespace acx

@@ -11,18 +11,17 @@
 // f32-MFMA rate.  tests/test_gpu_parity.py runs its whole suite against this mode at the fp32 tolerances.
 //
 // Operand format "S16" (the same 4 bytes per element as fp32): a row of K values is K/8 blocks of 32 B,
-//   [8 x fp16 hi][8 x fp16 lo];  a 128-B LDS row = 4 blocks = 32 k.  Lane half h of a 32x32x16 MFMA needs 8
-// consecutive k of one row = one block: hi chunk 4s+2h, lo chunk 4s+2h+1 of the row (s = k-step of 16 in the tile).
+//   [8 x fp16 hi][8 x fp16 lo];  a 128-B LDS row = 4 blocks = 32 k.
 // Producers: the LayerNorm pass (dwconv.hip, rows scaled by 2^11: |LN(y)| <= sqrt(C-1) < 28), this kernel's
 // GELU epilogue (hidden activation scaled by 2^4, clamped to the fp16 range) and acx_finalize for the weights
 // (scaled per layer to max |w| in [2^14, 2^15)).  The epilogue multiplies the accumulator by the exact inverse.
 //
-// Tiling / staging as gemm.hip, but one 8-wave workgroup per CU: 256 x BN x 32 per workgroup (4 x 2 waves, each 64 x BN/2),
+// Tiling / staging as gemm.hip, but one 8-wave workgroup per CU: 256 x 192 x 32 per workgroup (4 x 2 waves, each 64 x 96),
 // both operands by LDS-DMA with the XOR swizzle on the source address, fragments double-buffered in registers.
 // The workgroup is CU-EXCLUSIVE (acx_internal.h, kCuLdsBytes): it claims all 160 KB of LDS and 512 x 256 registers, so no
 // foreign wave can be co-resident with its MFMA loop (packed-FP32 VALU work of a co-resident wave goes wrong next to
-// it on this platform -- tools/race2/).  A k-tile is only 2 x TM*TN*3 MFMAs of 32 cycles, so
-// the pipeline is deeper than the fp32 kernel's: B tile t+2 and A tiles t+2, t+3 are in flight while tile t is multiplied.
+// it on this platform -- tools/race2/).  The pipeline is deeper than the fp32 kernel's: B tile t+2 and
+// A tiles t+2, t+3 are in flight while tile t is multiplied.
 #include <cstdlib>
 
 #include <type_traits>
@@ -51,292 +50,10 @@ __device__ __forceinline__ void lds_dma16_s(const char* gsrc, char* lds_wave_bas
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// EPI: 0 bias -> fp32, 1 bias + GELU -> S16 (scaled by kHiddenScale), 2 bias + residual -> fp32
-template <int kBM, int BN, int WM, int WN, int EPI, int GATHER>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_split_kernel(GemmSParams p) {
-    constexpr int TM = kBM / (WM * 32);
-    constexpr int TN = BN / (WN * 32);
-    constexpr int NW = WM * WN;                                           // waves per workgroup (4 or 8)
-    constexpr int A_TILE = kBM * kSRowBytes, B_TILE = BN * kSRowBytes;
-    constexpr int A_DMA = kBM / (8 * NW), B_DMA = BN / (8 * NW);          // 1-KB pieces per wave per tile
-    static_assert(A_DMA * 8 * NW == kBM && B_DMA * 8 * NW == BN, "tile rows must split into 8-row pieces per wave");
-    // D = (W A^T): lane = row m, registers = 4 consecutive n -> 16-B accesses per lane in every epilogue
-    // (the un-swapped form, 4-B accesses with n on the lanes, spent 73 of 289 us in pwconv2's read-modify-write)
-    constexpr bool SWAP = true;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* As = smem;
-    char* Bs = smem + 3 * A_TILE;        // A: ring of three k-tiles, B: two (see the k loop)
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, hh = lane >> 5;
-    const int wm = wave / WN, wn = wave % WN;
-    // claim the whole register budget of two waves per SIMD (with 512 threads hipcc keeps everything, accumulators
-    // included, in v0..v255; tools/check_exclusive.py verifies the emitted descriptor)
-    static_assert(NW == 8, "CU-exclusive launch: 8 waves x 256 registers");
-    ACX_CLAIM_VGPR(255);
-    long long lid = blockIdx.x;
-    {   // XCD-contiguous tile order (see gemm.hip)
-        const long long nwg = gridDim.x, per = (nwg + 7) >> 3, full = nwg - (per - 1) * 8;
-        const long long xcd = lid & 7, k = lid >> 3;
-        lid = (xcd < full ? xcd * per : full * per + (xcd - full) * (per - 1)) + k;
-    }
-    const int tile_n = (int)(lid % p.tiles_n);
-    const long long tile_m = lid / p.tiles_n;
-    const long long m0 = tile_m * kBM;
-    const int n0 = tile_n * BN;
-
-    const int prow = lane >> 3, pchunk = lane & 7;
-    const char* a_src[A_DMA];
-#pragma unroll
-    for (int i = 0; i < A_DMA; ++i) {
-        const int row = A_DMA * 8 * wave + 8 * i + prow;
-        const int chunk = pchunk ^ acx_swz8(row);
-        long long m = m0 + row;
-        if (m >= p.M) m = p.M - 1;
-        if (GATHER) {
-            const int wo = (int)(m % p.Wo);
-            const long long t = m / p.Wo;
-            const int ho = (int)(t % p.Ho);
-            const long long b = t / p.Ho;
-            a_src[i] = p.A + (((b * p.H + 2 * ho) * p.W + 2 * wo) * p.C) * 4 + 16 * chunk;
-        } else {
-            a_src[i] = p.A + m * p.K * 4 + 16 * chunk;
-        }
-    }
-    const char* b_src[B_DMA];
-#pragma unroll
-    for (int i = 0; i < B_DMA; ++i) {
-        const int row = B_DMA * 8 * wave + 8 * i + prow;
-        const int chunk = pchunk ^ acx_swz8(row);
-        b_src[i] = p.Wt + (long long)(n0 + row) * p.K * 4 + 16 * chunk;
-    }
-    char* a_dst = As + A_DMA * 8 * wave * kSRowBytes;
-    char* b_dst = Bs + B_DMA * 8 * wave * kSRowBytes;
-    auto a_koff = [&](int k0) -> long long {        // byte offset of k-tile k0 inside an A row
-        if (GATHER) {
-            const int qd = k0 / p.C;
-            return ((long long)((qd >> 1) * p.W + (qd & 1)) * p.C + (k0 - qd * p.C)) * 4;
-        }
-        return (long long)k0 * 4;
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int sw = acx_swz8(l31);
-    int foff_hi[2], foff_lo[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        foff_hi[s] = l31 * kSRowBytes + (((4 * s + 2 * hh) ^ sw) << 4);
-        foff_lo[s] = l31 * kSRowBytes + (((4 * s + 2 * hh + 1) ^ sw) << 4);
-    }
-    const int a_frag_off = wm * TM * 32 * kSRowBytes;
-    const int b_frag_off = wn * TN * 32 * kSRowBytes;
-#define ACX_READ_FRAGS(F, abase, bbase, s)                                                              \
-    {                                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                               \
-            F##ah[i] = *reinterpret_cast<const f32x4*>((abase) + i * 32 * kSRowBytes + foff_hi[s]);    \
-            F##al[i] = *reinterpret_cast<const f32x4*>((abase) + i * 32 * kSRowBytes + foff_lo[s]);    \
-        }                                                                                              \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                               \
-            F##bh[j] = *reinterpret_cast<const f32x4*>((bbase) + j * 32 * kSRowBytes + foff_hi[s]);    \
-            F##bl[j] = *reinterpret_cast<const f32x4*>((bbase) + j * 32 * kSRowBytes + foff_lo[s]);    \
-        }                                                                                              \
-    }
-#define ACX_H8(x) __builtin_bit_cast(h8, x)
-#define ACX_MFMA1(term, i, j, F)     /* term 0: lo x hi, 1: hi x lo, 2: hi x hi */                      \
-    if (SWAP) {                                                                                        \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ACX_H8((term) == 0 ? F##bl[j] : F##bh[j]),  \
-                                                           ACX_H8((term) == 1 ? F##al[i] : F##ah[i]), acc[i][j], 0, 0, 0); \
-    } else {                                                                                           \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ACX_H8((term) == 0 ? F##al[i] : F##ah[i]),  \
-                                                           ACX_H8((term) == 1 ? F##bl[j] : F##bh[j]), acc[i][j], 0, 0, 0); \
-    }
-    // term-major order: MFMAs on the same accumulator are TM*TN instructions apart
-#define ACX_PRIO_HI
-#define ACX_PRIO_LO
-#define ACX_MFMA_STEP(F)                                                                               \
-    {                                                                                                  \
-        ACX_PRIO_HI                                                                                    \
-        _Pragma("unroll") for (int term = 0; term < 3; ++term)                                         \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                 \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) { ACX_MFMA1(term, i, j, F) }                    \
-        ACX_PRIO_LO                                                                                    \
-    }
-    // the same with LDS-DMA pieces threaded in, one piece per MFMA in program order (hipcc may move a piece by an MFMA or
-    // two; scheduling fences around every pair cost 5 %): first the B pieces of tile t+2, then -- behind one fence -- the A
-    // pieces of tile t+3 (the counted wait at the next barrier relies on this order, see the k loop)
-#define ACX_MFMA_STEP_DMA(F, koffA, aslot, k0B, bslot)                                                 \
-    {                                                                                                  \
-        static_assert(A_DMA + B_DMA <= 3 * TM * TN, "one DMA piece per MFMA");                         \
-        _Pragma("unroll") for (int term = 0; term < 3; ++term)                                         \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                 \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                               \
-            const int pc = (term * TM + i) * TN + j;                                                   \
-            if (pc == B_DMA) __builtin_amdgcn_sched_barrier(0);      /* every B piece is issued before the first A piece */ \
-            if (pc < B_DMA) lds_dma16_s(b_src[pc] + (k0B), b_dst + (bslot) * B_TILE + pc * 8 * kSRowBytes); \
-            else if (pc < A_DMA + B_DMA)                                                               \
-                lds_dma16_s(a_src[pc - B_DMA] + (koffA), a_dst + (aslot) * A_TILE + (pc - B_DMA) * 8 * kSRowBytes); \
-            ACX_MFMA1(term, i, j, F)                                                                   \
-        }                                                                                              \
-    }
-#define ACX_DMA_A(koffA, aslot)                                                                        \
-    {   _Pragma("unroll") for (int i = 0; i < A_DMA; ++i)                                              \
-            lds_dma16_s(a_src[i] + (koffA), a_dst + (aslot) * A_TILE + i * 8 * kSRowBytes); }
-#define ACX_DMA_B(k0B, bslot)                                                                          \
-    {   _Pragma("unroll") for (int i = 0; i < B_DMA; ++i)                                              \
-            lds_dma16_s(b_src[i] + (k0B), b_dst + (bslot) * B_TILE + i * 8 * kSRowBytes); }
-#define ACX_TOUCH(F)      /* see gemm.hip: keeps hipcc's lgkmcnt(0) off freshly issued reads */        \
-    {                                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i) { asm volatile("" :: "v"(F##ah[i])); asm volatile("" :: "v"(F##al[i])); } \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) { asm volatile("" :: "v"(F##bh[j])); asm volatile("" :: "v"(F##bl[j])); } \
-    }
-
-    const int nk = p.K / kSBK;
-    auto ktile = [&](int t) { return (t < nk ? t : nk - 1) * kSBK; };      // past the end: re-request the last tile (harmless, keeps the loop uniform)
-    // prologue: tile 0 landed; then B(1), A(1), A(2) in flight -- in THIS order -- and the fragments of tile 0 in registers
-    ACX_DMA_A(a_koff(0), 0)
-    ACX_DMA_B(0LL, 0)
-    __syncthreads();
-    ACX_DMA_B((long long)ktile(1) * 4, 1)                      // nk >= 2 (checked by the launcher)
-    ACX_DMA_A(a_koff(ktile(1)), 1)
-    ACX_DMA_A(a_koff(ktile(2)), 2)
-    f32x4 F0ah[TM], F0al[TM], F0bh[TN], F0bl[TN], F1ah[TM], F1al[TM], F1bh[TN], F1bl[TN];
-    {
-        const char* ab = As + a_frag_off;
-        const char* bb = Bs + b_frag_off;
-        ACX_READ_FRAGS(F0, ab, bb, 0)
-        ACX_READ_FRAGS(F1, ab, bb, 1)
-    }
-    // steady state, tile t (A slot t % 3, B slot t & 1):
-    //   MFMA s0 | counted wait + barrier (tile t+1 landed, tile t fully read by every wave) | rd s0(t+1) |
-    //   MFMA s1 threaded with DMA B(t+2) -> B slot of t, then DMA A(t+3) -> A slot of t | rd s1(t+1)
-    // The activations (A) come from HBM / the Infinity Cache: with a 2-slot ring a request had ONE k-tile (~1 us) to land
-    // and the loop spent half its time in the barrier's wait; the third A slot gives it two.  One wave's vector-memory
-    // counter retires in issue order, so "tile t+1 landed" = everything but the newest A_DMA pieces (those of A(t+2),
-    // issued last in the previous iteration) has returned: s_waitcnt vmcnt(A_DMA).
-    // (no conditional inside the loop: a branch around the DMA variant makes hipcc copy all accumulators twice per
-    //  iteration; past the last tile the requests repeat tile nk-1 into slots nobody reads again)
-    int a_cur = 0;
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        const int a_nxt = a_cur == 2 ? 0 : a_cur + 1;
-        const char* abn = As + a_nxt * A_TILE + a_frag_off;
-        const char* bbn = Bs + ((kt + 1) & 1) * B_TILE + b_frag_off;
-        const long long kb = (long long)ktile(kt + 2) * 4;
-        const long long ka = a_koff(ktile(kt + 3));
-        __builtin_amdgcn_sched_barrier(0);
-        ACX_MFMA_STEP(F0)
-        __builtin_amdgcn_sched_barrier(0);
-        ACX_TOUCH(F1)
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_DMA) : "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        ACX_READ_FRAGS(F0, abn, bbn, 0)
-        __builtin_amdgcn_sched_barrier(0);
-        ACX_MFMA_STEP_DMA(F1, ka, a_cur, kb, kt & 1)
-        __builtin_amdgcn_sched_barrier(0);
-        ACX_TOUCH(F0)
-        ACX_READ_FRAGS(F1, abn, bbn, 1)
-        a_cur = a_nxt;
-    }
-    ACX_MFMA_STEP(F0)
-    ACX_MFMA_STEP(F1)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the repeated requests of the last iterations: nothing may still be writing the LDS when the workgroup ends
-#undef ACX_READ_FRAGS
-#undef ACX_MFMA1
-#undef ACX_MFMA_STEP
-#undef ACX_MFMA_STEP_DMA
-#undef ACX_DMA_A
-#undef ACX_DMA_B
-#undef ACX_TOUCH
-#undef ACX_H8
-
-    const float sinv = p.sinv;
-    f32x4 bjq[TN][4];             // (round 4: biases loaded once, not once per store -- see gemm_split16_kernel's epilogue)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) bjq[j][q] = *reinterpret_cast<const f32x4*>(p.bias + n0 + (wn * TN + j) * 32 + 8 * q + 4 * hh);
-    if (EPI == 1) {
-        const GeluK3 gk = gelu_k3(sinv, p.hscale);      // GELU of v = a * sinv, result x p.hscale (split_math.h, third form)
-        const float binv = 1.0f / sinv;     // a power of two
-        // ---- GELU epilogue, D = W A^T: lane = row m, registers r = 4q+e hold n = 8q + 4hh + e ------------------
-        // One S16 block (8 n) = [hi x8][lo x8] is shared by the lane pair (l31, hh=0/1): after a permlane32 swap
-        // the low lane holds all 8 hi halves and the high lane all 8 lo halves -> one 16-B store each.
-        char* outb = reinterpret_cast<char*>(p.out);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const long long m = m0 + (wm * TM + i) * 32 + l31;
-            const bool ok = m < p.M;
-            char* orow = outb + (ok ? m : 0) * p.N * 4;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nb = n0 + (wn * TN + j) * 32;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 b4 = bjq[j][q];
-                    unsigned xh[2], xl[2];
-#pragma unroll
-                    for (int e2 = 0; e2 < 2; ++e2) {      // acc holds v / sinv - bias / sinv: add the pre-scaled bias first
-                        const float ax = acc[i][j][4 * q + 2 * e2] + b4[2 * e2] * binv;
-                        const float ay = acc[i][j][4 * q + 2 * e2 + 1] + b4[2 * e2 + 1] * binv;
-                        gelu3_pair(gk, ax, ay, xh[e2], xl[e2]);
-                    }
-                    // low lanes: (own hi, partner hi); high lanes: (partner lo, own lo)
-                    auto r0 = __builtin_amdgcn_permlane32_swap(xh[0], xl[0], false, false);
-                    auto r1 = __builtin_amdgcn_permlane32_swap(xh[1], xl[1], false, false);
-                    uint4 o;
-                    o.x = r0[0]; o.y = r1[0]; o.z = r0[1]; o.w = r1[1];
-                    if (ok) *reinterpret_cast<uint4*>(orow + (long long)(nb + 8 * q) * 4 + 16 * hh) = o;
-                }
-            }
-        }
-    } else {
-        // ---- fp32 epilogue, same layout: lane (l31, hh) owns row m, columns nb + 8q + 4hh .. +3 of tile (i, j) ------
-        float* outf = reinterpret_cast<float*>(p.out);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const long long m = m0 + (wm * TM + i) * 32 + l31;
-            const bool ok = m < p.M;
-            const long long row = (ok ? m : 0) * p.N;
-            f32x4 rv[TN][4];
-            if (EPI == 2) {       // all residual loads of the row tile in flight before the first store
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        rv[j][q] = *reinterpret_cast<const f32x4*>(p.resid + row + n0 + (wn * TN + j) * 32 + 8 * q + 4 * hh);
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nb = n0 + (wn * TN + j) * 32;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 b4 = bjq[j][q];
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] = fmaf(acc[i][j][4 * q + e], sinv, b4[e]);
-                        if (EPI == 2) v[e] += rv[j][q][e];
-                    }
-                    if (ok) *reinterpret_cast<f32x4*>(outf + row + nb + 8 * q + 4 * hh) = v;
-                }
-            }
-        }
-    }
-}
-
-// The same GEMM on v_mfma_f32_16x16x32_f16 (round 3).  Under MFMA load the chip holds a higher clock on this shape than
-// on 32x32x16 at equal cycles per flop (MI355X_MICROARCH.md 'DVFS give-back' item 7; profiles/r03_i_mfma_shape_rates.txt:
-// bare loops on random operands +5..10 % TFLOP/s), and a timing-only substitution in this kernel took 5-7 % off its
-// launches.  Same tiles (256 x 192 x 32, 4 x 2 waves of 64 x 96), same LDS images, same LDS-DMA schedule; what changes:
+// The GEMM runs on v_mfma_f32_16x16x32_f16 (round 3; the 32x32x16 form it replaced was removed after commit 07ba348).
+// Under MFMA load the chip holds a higher clock on this shape than on 32x32x16 at equal cycles per flop
+// (MI355X_MICROARCH.md 'DVFS give-back' item 7; profiles/r03_i_mfma_shape_rates.txt: bare loops on random operands
+// +5..10 % TFLOP/s), and a timing-only substitution took 5-7 % off the launches of the 32x32x16 form.  Compared with it:
 //   * a 16x16x32 MFMA contracts the WHOLE 32-k LDS row of 16 rows: lane l reads row l & 15, block l >> 4 (hi chunk
 //     2 (l >> 4), lo chunk + 1, XOR acx_swz8(row) as the DMA wrote it: conflict-free for the lane groups of ds_read_b128);
 //   * a k-tile is ONE step of 3 x 4 x 6 = 72 MFMAs of 16 cycles.  It runs as two halves over the weight blocks (n blocks
@@ -653,37 +370,12 @@ static int launch_s16_any(const GemmSParams& p, int ways, hipStream_t s) {
     return launch_s16_cfg<EPI, GATHER, 4>(p, s);
 }
 
-template <int kBM, int BN, int WM, int WN, int EPI, int GATHER>
-static int launch_s_cfg(const GemmSParams& p0, hipStream_t s) {
-    GemmSParams p = p0;
-    p.tiles_n = p.N / BN;
-    const long long tiles_m = (p.M + kBM - 1) / kBM;
-    const long long blocks = tiles_m * p.tiles_n;
-    if (blocks > 0x7fffffffLL) ACX_FAIL(ACX_ERR_SHAPE, "gemm_split: grid too large");
-    static_assert((size_t)(3 * kBM + 2 * BN) * kSRowBytes <= kCuLdsBytes, "tile does not fit the LDS");
-    constexpr size_t lds = kCuLdsBytes;          // all of it: CU-exclusive (see the header comment)
-    static DeviceOnce once;
-    ACX_TRY(set_max_dynamic_lds(once, &gemm_split_kernel<kBM, BN, WM, WN, EPI, GATHER>, lds));
-    launch_kernel(&gemm_split_kernel<kBM, BN, WM, WN, EPI, GATHER>, dim3((unsigned)blocks), dim3(64 * WM * WN), lds, s, p);
-    ACX_HIP(hipGetLastError());
-    return ACX_OK;
-}
-
-template <int EPI, int GATHER>
-static int launch_s_bn(const GemmSParams& p, int ways, hipStream_t s) {
-    // every N of the model (192, 384, 768, 1536, 3072) is a multiple of 192: 256 x 192 tiles -- 36 MFMAs per barrier and
-    // the fewest operand bytes per flop through the LDS-DMA path; 256 x 128 for other multiples of 128
-    if (p.N % 192 == 0) {
-        const bool old_shape = tuning().gemm_32x32.load(std::memory_order_relaxed) == 1;   // A/B switch
-        if ((p.K / kSBK) % 2 == 0 && !old_shape) return launch_s16_any<EPI, GATHER>(p, ways, s);
-        return launch_s_cfg<256, 192, 4, 2, EPI, GATHER>(p, s);
-    }
-    if (p.N % 128 == 0) return launch_s_cfg<256, 128, 4, 2, EPI, GATHER>(p, s);
-    ACX_FAIL(ACX_ERR_SHAPE, "gemm_split: N=%d is not a multiple of 192 or 128", p.N);
-}
-
 int launch_gemm_split(acx_ctx* c, const GemmSplitArgs& a, hipStream_t s) {
     if (a.K % kSBK != 0 || a.K < 2 * kSBK) ACX_FAIL(ACX_ERR_SHAPE, "gemm_split: K=%d is not a multiple of %d >= %d", a.K, kSBK, 2 * kSBK);
+    // 256 x 192 tiles (every N of the model -- 192 .. 3072 -- is a multiple of 192), the k loop unrolled by two k-tiles
+    // (every K of the model -- 384 .. 3072 -- is an even number of them)
+    if (a.N % 192 != 0 || (a.K / kSBK) % 2 != 0)
+        ACX_FAIL(ACX_ERR_SHAPE, "gemm_split: N=%d is not a multiple of 192 or K=%d not of %d", a.N, a.K, 2 * kSBK);
     if (a.M <= 0) return ACX_OK;
     GemmSParams p;
     p.A = reinterpret_cast<const char*>(a.A); p.Wt = reinterpret_cast<const char*>(a.Wt); p.bias = a.bias;
@@ -693,12 +385,11 @@ int launch_gemm_split(acx_ctx* c, const GemmSplitArgs& a, hipStream_t s) {
     const int ways = inflight_ways();
     if (a.gather) {
         if (a.epi != EPI_BIAS || a.C % kSBK != 0) ACX_FAIL(ACX_ERR_ARG, "gemm_split: bad gather configuration");
-        return launch_s_bn<0, 1>(p, ways, s);
+        return launch_s16_any<0, 1>(p, ways, s);
     }
-    if (a.epi == EPI_GELU) return launch_s_bn<1, 0>(p, ways, s);
-    if (a.epi == EPI_RESID) return launch_s_bn<2, 0>(p, ways, s);
-    if (a.epi == EPI_BIAS) return launch_s_bn<0, 0>(p, ways, s);
-    ACX_FAIL(ACX_ERR_ARG, "gemm_split: unknown epilogue %d", a.epi);
+    if (a.epi == EPI_GELU) return launch_s16_any<1, 0>(p, ways, s);
+    if (a.epi == EPI_RESID) return launch_s16_any<2, 0>(p, ways, s);
+    ACX_FAIL(ACX_ERR_ARG, "gemm_split: epilogue %d without the 2x2 gather", a.epi);
 }
 
 }  // namespace acx

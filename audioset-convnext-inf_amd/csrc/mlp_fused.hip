@@ -229,6 +229,21 @@ static int launch_fused_cfg(const BlockW& w, const float* y, float* x, long long
 
 bool mlp_fused_supported(int C) { return C == 96 || C == 192; }
 
+// chunk-major image for the kernel's LDS-DMA: per chunk j of 32 hidden units, W1 rows [32][C] then W2 columns [C][32]
+std::vector<float> mlp_fused_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C) {
+    const int nch = 4 * C / 32;
+    std::vector<float> pk((size_t)nch * 64 * C);
+    for (int j = 0; j < nch; ++j) {
+        float* blk = pk.data() + (size_t)j * 64 * C;
+        for (int r = 0; r < 32; ++r)
+            for (int k = 0; k < C; ++k) blk[(size_t)r * C + k] = w1[(size_t)(32 * j + r) * C + k];
+        float* blk2 = blk + (size_t)32 * C;
+        for (int ch = 0; ch < C; ++ch)
+            for (int h = 0; h < 32; ++h) blk2[(size_t)ch * 32 + h] = w2[(size_t)ch * 4 * C + 32 * j + h];
+    }
+    return pk;
+}
+
 int launch_mlp_fused(acx_ctx* c, const BlockW& w, int C, const float* y, float* x, long long M, hipStream_t s) {
     if (!w.wpack) ACX_FAIL(ACX_ERR_STATE, "fused MLP: chunk-major weights were not packed for C=%d", C);
     ProfScope ps(c, ACX_K_MLP_FUSED, s);

@@ -534,6 +534,32 @@ static int launch_fused_s_cfg(const BlockW& w, const float* y, float* x, long lo
 
 bool mlp_fused_split_supported(int C) { return C == 96; }     // (C = 192, 384: mlp_fused_wide.hip)
 
+// chunk-major image: per chunk j [W1c = rows 32j..32j+31 of W1 in S16 form]
+// [W2c: C rows x 4 blocks; block b = 2s'+h holds hidden units 32j + 16s' + 4h + 8(jj>>2) + (jj&3)]
+std::vector<uint16_t> mlp_fused_split_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C, float w1_scale,
+                                           float w2_scale) {
+    const std::vector<uint16_t> h1 = s16_rows(w1, 4 * C, C, w1_scale);
+    const int nch = 4 * C / 32;
+    const size_t half = (size_t)64 * C;                    // uint16 elements per [32][C] S16 image
+    std::vector<uint16_t> pk((size_t)nch * 2 * half);
+    for (int j = 0; j < nch; ++j) {
+        uint16_t* blk = pk.data() + (size_t)j * 2 * half;
+        std::memcpy(blk, h1.data() + (size_t)j * half, half * 2);
+        uint16_t* blk2 = blk + half;
+        for (int ch = 0; ch < C; ++ch)
+            for (int b = 0; b < 4; ++b)
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int u = 32 * j + 16 * (b >> 1) + 4 * (b & 1) + 8 * (jj >> 2) + (jj & 3);
+                    const float v = w2[(size_t)ch * 4 * C + u] * w2_scale;
+                    const _Float16 hi = (_Float16)v;
+                    const _Float16 lo = (_Float16)(v - (float)hi);
+                    std::memcpy(blk2 + (size_t)ch * 64 + b * 16 + jj, &hi, 2);
+                    std::memcpy(blk2 + (size_t)ch * 64 + b * 16 + 8 + jj, &lo, 2);
+                }
+    }
+    return pk;
+}
+
 int launch_mlp_fused_split(acx_ctx* c, const BlockW& w, int C, const float* y, float* x, long long M, hipStream_t s,
                            void* ln_out) {
     if (!w.wpack_s) ACX_FAIL(ACX_ERR_STATE, "fused split MLP: chunk-major S16 weights were not packed for C=%d", C);

@@ -106,7 +106,7 @@ struct WideCfg {
         return kNanoHead + ((kNano - kNanoHead) * cum_cap(m) + kCapTotal / 2) / kCapTotal;
     }
     __host__ __device__ static constexpr int nano_begin(int m) { return m == 0 ? kNanoHead : nano_end(m - 1); }
-    // W1 rows are 4 C bytes: the XOR that spreads 16 consecutive rows over the LDS banks (api.hip packs the image with it)
+    // W1 rows are 4 C bytes: the XOR that spreads 16 consecutive rows over the LDS banks (mlp_fused_wide_pack packs the image with it)
     __device__ static int swz1(int row) { return (C % 64 == 0) ? (row & 15) : ((row >> 1) & 7); }
 };
 
@@ -628,6 +628,49 @@ static int launch_wide_cfg(const BlockW& w, const float* y, float* x, long long 
 }
 
 bool mlp_fused_wide_supported(int C) { return C == 384 || C == 192; }
+
+// ONE stream of 128 C-byte segments in consumption order
+//   W1(0) W1(1) W2(0) W1(2) W2(1) ... W1(n-1) W2(n-2) W2(n-1),   n = 4C/32 hidden chunks,
+// each already in LDS image order (XOR swizzles baked in): a 1-KB LDS-DMA piece is 1 KB of the stream.
+std::vector<uint16_t> mlp_fused_wide_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C, float w1_scale,
+                                          float w2_scale) {
+    const int nch = 4 * C / 32;
+    const size_t seg = (size_t)64 * C;                   // uint16 elements per segment (128 C bytes)
+    const std::vector<uint16_t> h1 = s16_rows(w1, 4 * C, C, w1_scale);      // [4C][C/8][hi8 | lo8]
+    std::vector<uint16_t> st((size_t)2 * nch * seg);
+    for (int k = 0; k < nch; ++k) {
+        // W1 image of chunk k: row r = hidden unit 32k + r (4 C bytes = C/4 chunks of 16 B: chunk p = block p >> 1
+        // of the row, p & 1: hi / lo halves), content chunk p at position p ^ swz(r): r & 15 when C/4 is a multiple
+        // of 16 chunks, (r >> 1) & 7 for C = 96 (24 chunks per row: odd rows start 8 chunks further)
+        uint16_t* w1img = st.data() + (size_t)(k == 0 ? 0 : 2 * k - 1) * seg;
+        for (int r = 0; r < 32; ++r)
+            for (int p = 0; p < C / 4; ++p) {
+                const int pos = p ^ ((C % 64 == 0) ? (r & 15) : ((r >> 1) & 7));
+                std::memcpy(w1img + ((size_t)r * 4 * C + (size_t)pos * 16) / 2,
+                            h1.data() + ((size_t)(32 * k + r) * C * 4 + (size_t)p * 16) / 2, 16);
+            }
+        // W2 image of chunk k: row = out channel (128 B = 8 chunks); content chunk 2b (hi) / 2b + 1 (lo) of
+        // block b (= k block g4 of the 16x16x32 MFMA) holds hidden units 32k + 16(jj >> 2) + 4b + (jj & 3) -- the order
+        // in which a lane's accumulators of phase 1 become its B operand of phase 2 --, at position ^ acx_swz8(ch)
+        uint16_t* w2img = st.data() + (size_t)(k == nch - 1 ? 2 * nch - 1 : 2 * k + 2) * seg;
+        for (int ch = 0; ch < C; ++ch)
+            for (int b = 0; b < 4; ++b) {
+                uint16_t hi8[8], lo8[8];
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int u = 32 * k + 16 * (jj >> 2) + 4 * b + (jj & 3);
+                    const float v = w2[(size_t)ch * 4 * C + u] * w2_scale;
+                    const _Float16 hi = (_Float16)v;
+                    const _Float16 lo = (_Float16)(v - (float)hi);
+                    std::memcpy(&hi8[jj], &hi, 2);
+                    std::memcpy(&lo8[jj], &lo, 2);
+                }
+                const int sw = acx_swz8(ch);
+                std::memcpy(w2img + ((size_t)ch * 128 + (size_t)((2 * b) ^ sw) * 16) / 2, hi8, 16);
+                std::memcpy(w2img + ((size_t)ch * 128 + (size_t)((2 * b + 1) ^ sw) * 16) / 2, lo8, 16);
+            }
+    }
+    return st;
+}
 
 int launch_mlp_fused_wide(acx_ctx* c, const BlockW& w, int C, const float* y, float* x, long long M, hipStream_t s,
                           void* ln_out) {

@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void mlp_fused_wide_bf16_kernel(
     // bf16 rows (ABF, round 5): the residual enters through the matrix pipe -- out += I . x with x read as B fragments (lane
     // (px, hh): channels 16 u + 8 hh .. + 7, ONE 16-byte load) and I the identity as an A fragment: 1.0 x bf16 is exact in the fp32
     // accumulate, two MFMAs per out tile.  In the accumulator layout the rows were 48 eight-byte loads per pixel tile, and a
-    // load's address processing costs 4 cycles per LANE whatever its width (tools/lab/pair_lab.hip stamps: 47 k cycles of the
+    // load's address processing costs 4 cycles per LANE whatever its width (round-5 pair-kernel lab stamps, docs/lab_log.md 3g: 47 k cycles of the
     // CU's one texture-address path per 128-pixel tile, the path the LDS-DMA weight pieces queue on) -- now 24 sixteen-byte
     // loads into half the registers (C/4 per pixel tile instead of C/2).
     float4 xr[PT][(kPrefetchX && !kXM) ? C / 8 : 1];
@@ -499,7 +499,7 @@ static int launch_wide_bf16_cfg(const BlockW& w, const void* y, void* x, long lo
 // kernel above: its workgroups all moved through "load the tile / compute / store the tile" in step, so the HBM phase
 // (3 tensor passes, ~190 us per block at the HBM rate) and the compute phase (~210 us) added up; free-running waves
 // spread over all phases, memory latency hides behind the other waves' matrix and vector work, and the per-segment
-// barrier and LDS-DMA issue are gone.  Same stream layout (api.hip packs one `wstream_b` for both kernels), same
+// barrier and LDS-DMA issue are gone.  Same stream layout (mlp_fused_wide_bf16_pack builds one `wstream_b` for both kernels), same
 // arithmetic and rounding points.
 template <bool LNOUT, bool ABF>
 __global__ __launch_bounds__(512) void mlp_fused_stat_bf16_kernel(
@@ -761,9 +761,41 @@ static int launch_stat_bf16(const BlockW& w, const void* y, void* x, long long M
 
 bool mlp_fused_wide_bf16_supported(int C) { return C == 384 || C == 192 || C == 96; }
 
-// LDS position of 16-byte chunk p of row `row` of a W1 image (acx_finalize packs the stream with it)
-int mlp_fused_wide_bf16_swz(int C, int row) {
+// LDS position of 16-byte chunk p of row `row` of a W1 image
+static int wide_bf16_swz1(int C, int row) {
     return C == 384 ? WideBfCfg<384, 1>::swz1(row) : (C == 192 ? WideBfCfg<192, 1>::swz1(row) : WideBfCfg<96, 1>::swz1(row));
+}
+
+// One stream of 128 C-byte segments in consumption order
+//   W1(0) W1(1) W2(0) W1(2) W2(1) ... W1(n-1) W2(n-2) W2(n-1),   n = 4C/64 chunks of 64 hidden units,
+// each already in LDS image order.
+std::vector<uint16_t> mlp_fused_wide_bf16_pack(const std::vector<float>& w1, const std::vector<float>& w2, int C) {
+    const int nch = 4 * C / 64;
+    const size_t seg = (size_t)64 * C;                   // uint16 elements per segment
+    std::vector<uint16_t> st((size_t)2 * nch * seg);
+    for (int k = 0; k < nch; ++k) {
+        // W1 image: row r = hidden unit 64k + r (2 C bytes = C/8 chunks of 8 channels), chunk p at p ^ swz(r)
+        uint16_t* w1img = st.data() + (size_t)(k == 0 ? 0 : 2 * k - 1) * seg;
+        for (int r = 0; r < 64; ++r)
+            for (int p = 0; p < C / 8; ++p) {
+                const int pos = p ^ wide_bf16_swz1(C, r);
+                for (int e = 0; e < 8; ++e)
+                    w1img[(size_t)r * C + (size_t)pos * 8 + e] = to_bf16(0.5f * w1[(size_t)(64 * k + r) * C + 8 * p + e]);   // 0.5 W1: the accumulator is z (gelu2h_micro)
+            }
+        // W2 image: row = out channel (128 B = 8 chunks); chunk b = 2 s' + h (s' = k-step 0..3) holds hidden
+        // units 64k + 32(s' >> 1) + 16(s' & 1) + 4h + 8(jj >> 2) + (jj & 3), at position b ^ ((ch >> 1) & 7)
+        uint16_t* w2img = st.data() + (size_t)(k == nch - 1 ? 2 * nch - 1 : 2 * k + 2) * seg;
+        for (int ch = 0; ch < C; ++ch)
+            for (int b = 0; b < 8; ++b) {
+                const int sp = b >> 1, h = b & 1;
+                const int pos = b ^ ((ch >> 1) & 7);
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int u = 64 * k + 32 * (sp >> 1) + 16 * (sp & 1) + 4 * h + 8 * (jj >> 2) + (jj & 3);
+                    w2img[(size_t)ch * 64 + (size_t)pos * 8 + jj] = to_bf16(w2[(size_t)ch * 4 * C + u]);
+                }
+            }
+    }
+    return st;
 }
 
 template <bool ABF>

@@ -174,9 +174,9 @@ ACX_API int acx_dwconv7(acx_ctx* ctx, int stage, int block, const float* x, floa
 ACX_API int acx_dwconv7_bf16(acx_ctx* ctx, int stage, int block, const uint16_t* x, uint16_t* y, int B, int H, int W,
                      void* stream);
 /* K3 + K4: whole Block.forward (convnext.py:74-87) on NHWC x, in place: depthwise conv, then LayerNorm + pwconv1 + GELU +
- * pwconv2 + gamma + residual (convnext.py:78-86).  Stages 0-1 (C = 96, 192) run the MLP as ONE fused kernel that keeps
- * the hidden activation in registers; stages 2-3 run two MFMA GEMMs through the hidden scratch.  Set
- * ACX_DISABLE_FUSED_MLP=1 before acx_finalize to force the two-GEMM form everywhere (fp32 precision only).
+ * pwconv2 + gamma + residual (convnext.py:78-86).  Stages 0-1 (ACX_PREC_F32) or 0-2 (the other precisions) run the
+ * MLP as ONE fused kernel that keeps the hidden activation in registers; the remaining stages run two MFMA GEMMs through
+ * the hidden scratch.
  * scratch >= acx_block_scratch_bytes, 256-byte aligned. */
 ACX_API int acx_block(acx_ctx* ctx, int stage, int block, float* x, int B, int H, int W, void* scratch,
               size_t scratch_bytes, void* stream);
@@ -220,7 +220,7 @@ ACX_API int acx_set_frontend(acx_ctx* ctx, int mode);
  * dense matrix, which is applied as it is).  Any pointer may be NULL. */
 ACX_API int acx_frontend_info(const acx_ctx* ctx, int* dense_dft, float* stft_deviation, int* mel_taps);
 
-/* Diagnostics.  The tile-shape A/B switches ACX_GEMM_MI, ACX_WIDE_NPB, ACX_WIDE_PERSIST, ACX_GEMM_32X32 and ACX_DW_STREAM are read from the
+/* Diagnostics.  The tile-shape A/B switches ACX_GEMM_MI, ACX_WIDE_NPB, ACX_WIDE_PERSIST, ACX_DW_STREAM and ACX_DWM_WAVES are read from the
  * environment once, at the first acx_create; this re-reads them (tests force every tile shape through it and require
  * bit-identical results).  Launches never touch the environment.  No reference counterpart. */
 ACX_API int acx_tuning_refresh(void);

@@ -163,28 +163,6 @@ def test_dwconv_matrix_kernel(ctx16, model16, synth_sd, s, B, H):
     assert worst <= 1.0 and exact > 0.99
 
 
-def test_dwconv_matrix_kernel_vs_column_kernel(ctx16, model16, synth_sd):
-    """ACX_DW_MFMA = 0 sends bf16 activations through the column / tile kernels (fp32 weights, 49 FMAs): the two arithmetics differ by the
-    bf16 rounding of the weights only -- 2^-9 relative per tap, far inside the activations' own rounding."""
-    if model16.precision != "bf16a":
-        pytest.skip("bf16 activations only")
-    refresh = _ffi.lib().acx_tuning_refresh
-    s, B = 1, 4
-    C, W, H = DIMS[s], 56 >> s, 252 >> s
-    x = (torch.randn(B, H, W, C, generator=torch.Generator().manual_seed(77)) * 2.0).to(torch.bfloat16).cuda()
-    ym = _dw_bf16(ctx16, s, 0, x, B, H, W).float()
-    os.environ["ACX_DW_MFMA"] = "0"
-    refresh()
-    try:
-        yc = _dw_bf16(ctx16, s, 0, x, B, H, W).float()
-    finally:
-        del os.environ["ACX_DW_MFMA"]
-        refresh()
-    d = maxdiff(ym, yc)
-    print("matrix vs column kernel: max abs diff %.3g at |y| <= %.3g" % (d, float(yc.abs().max())))
-    assert d <= 2.0 ** -6 * float(yc.abs().max())
-
-
 def test_dwconv_matrix_kernel_segmentation_is_invisible(ctx16, model16):
     """The matrix-pipe depthwise kernel cuts the stacked batch into segments by the number of waves it is asked to fill
     (ACX_DWM_WAVES per CU; 8 by default, halved per sub-batch in flight): an output's arithmetic -- bias, then kernel rows 0-3 of its

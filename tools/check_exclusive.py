@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Build-time check of the CU-exclusive launch contract (acx_internal.h): every kernel that runs dense
-16-bit MFMA (gemm_split_kernel, mlp_fused_split_kernel, mlp_fused_wide*_kernel, gemm_bf16_kernel, ...) must ship with a
+16-bit MFMA (gemm_split16_kernel, mlp_fused_split_kernel, mlp_fused_wide*_kernel, gemm_bf16_kernel, ...) must ship with a
 register allocation that fills the SIMD -- 256 registers per lane for 512-thread workgroups, 512 for 256-thread ones.
 Second check: for EVERY kernel of the library, the highest vector / accumulator register any of its
 instructions names lies inside the allocation its descriptor declares (no register over-reach into a neighbour's file).
@@ -18,7 +18,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = os.environ.get("ACX_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 # kernels (namespace acx) that run dense 16-bit MFMA on live data
-EXCLUSIVE = ("gemm_split_kernel", "gemm_split16_kernel", "mlp_fused_split_kernel", "mlp_fused_wide_kernel", "mlp_fused_wide_bf16_kernel",
+EXCLUSIVE = ("gemm_split16_kernel", "mlp_fused_split_kernel", "mlp_fused_wide_kernel", "mlp_fused_wide_bf16_kernel",
              "mlp_fused_stat_bf16_kernel", "gemm_bf16_kernel", "dwconv7_mfma_kernel")
 
 

@@ -10,6 +10,7 @@
 
 #include "dwconv.hip"
 #include "dwconv_col.hip"
+#include "dwconv_mfma.hip"      // (launch_dwconv's bf16-activation branch links against it; this lab runs fp32 only)
 
 namespace acx {
 void set_error(const char* fmt, ...) {
@@ -25,11 +26,9 @@ using namespace acx;
 
 #define CK(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #e, hipGetErrorString(e_)); exit(1); } } while (0)
 
-static uint16_t to_bf16(float f) { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); }
-
-int run_case(int B, int H, int W, bool bf, int iters, int target_waves, bool check) {
+int run_case(int B, int H, int W, int iters, int target_waves, bool check) {
     const int C = 96 * 56 / W;
-    const size_t n = (size_t)B * H * W * C, esz = bf ? 2 : 4;
+    const size_t n = (size_t)B * H * W * C, esz = 4;
     std::mt19937 rng(1234 + B + H);
     std::uniform_real_distribution<float> d(-1.f, 1.f);
     std::vector<float> hw(49 * C), hb(C);
@@ -38,7 +37,7 @@ int run_case(int B, int H, int W, bool bf, int iters, int target_waves, bool che
     std::vector<char> hx(n * esz);
     for (size_t i = 0; i < n; ++i) {
         float v = d(rng) * 3.f;
-        if (bf) { uint16_t q = to_bf16(v); memcpy(&hx[i * 2], &q, 2); } else memcpy(&hx[i * 4], &v, 4);
+        memcpy(&hx[i * 4], &v, 4);
     }
     void *x, *y0, *y1, *sink; float *dw, *db;
     CK(hipMalloc(&x, n * esz)); CK(hipMalloc(&y0, n * esz)); CK(hipMalloc(&y1, n * esz)); CK(hipMalloc(&sink, kDwSinkBytes));
@@ -48,8 +47,8 @@ int run_case(int B, int H, int W, bool bf, int iters, int target_waves, bool che
     CK(hipMemcpy(db, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemset(y0, 0xff, n * esz)); CK(hipMemset(y1, 0xee, n * esz));
     BlockW bw; bw.dw = dw; bw.dwb = db;
-    if (launch_dwconv(nullptr, bw, C, x, y0, nullptr, B, H, W, nullptr, bf) != ACX_OK) return 1;
-    if (launch_dwconv_col(x, y1, dw, db, sink, B, H, W, bf, target_waves, nullptr) != ACX_OK) return 1;
+    if (launch_dwconv(nullptr, bw, C, x, y0, nullptr, B, H, W, nullptr) != ACX_OK) return 1;
+    if (launch_dwconv_col(x, y1, dw, db, sink, B, H, W, target_waves, nullptr) != ACX_OK) return 1;
     CK(hipDeviceSynchronize());
     int bad = 0;
     if (check) {
@@ -63,7 +62,7 @@ int run_case(int B, int H, int W, bool bf, int iters, int target_waves, bool che
             bad = 1;
             const size_t c = first % C, px = first / C, w = px % W, h = (px / W) % H, bb = px / W / H;
             float va = 0, vb = 0;
-            if (!bf) { memcpy(&va, &a[first * 4], 4); memcpy(&vb, &b[first * 4], 4); }
+            memcpy(&va, &a[first * 4], 4); memcpy(&vb, &b[first * 4], 4);
             printf("  MISMATCH: %zu of %zu elements differ; first at clip %zu row %zu col %zu ch %zu: old %g new %g\n", diff, n, bb, h, w, c, va, vb);
         }
     }
@@ -71,18 +70,18 @@ int run_case(int B, int H, int W, bool bf, int iters, int target_waves, bool che
     if (iters > 0) {
         hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
         for (int rep = 0; rep < 2; ++rep) {
-            for (int i = 0; i < 5; ++i) launch_dwconv(nullptr, bw, C, x, y0, nullptr, B, H, W, nullptr, bf);
+            for (int i = 0; i < 5; ++i) launch_dwconv(nullptr, bw, C, x, y0, nullptr, B, H, W, nullptr);
             CK(hipEventRecord(e0));
-            for (int i = 0; i < iters; ++i) launch_dwconv(nullptr, bw, C, x, y0, nullptr, B, H, W, nullptr, bf);
+            for (int i = 0; i < iters; ++i) launch_dwconv(nullptr, bw, C, x, y0, nullptr, B, H, W, nullptr);
             CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&t_old, e0, e1));
-            for (int i = 0; i < 5; ++i) launch_dwconv_col(x, y1, dw, db, sink, B, H, W, bf, target_waves, nullptr);
+            for (int i = 0; i < 5; ++i) launch_dwconv_col(x, y1, dw, db, sink, B, H, W, target_waves, nullptr);
             CK(hipEventRecord(e0));
-            for (int i = 0; i < iters; ++i) launch_dwconv_col(x, y1, dw, db, sink, B, H, W, bf, target_waves, nullptr);
+            for (int i = 0; i < iters; ++i) launch_dwconv_col(x, y1, dw, db, sink, B, H, W, target_waves, nullptr);
             CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&t_new, e0, e1));
         }
     }
     const double mb = 2.0 * n * esz / 1e6;
-    printf("B=%3d H=%3d W=%2d C=%3d %s waves=%4d  %s  old %7.1f us (%5.2f TB/s)  new %7.1f us (%5.2f TB/s)\n", B, H, W, C, bf ? "bf16" : "fp32",
+    printf("B=%3d H=%3d W=%2d C=%3d waves=%4d  %s  old %7.1f us (%5.2f TB/s)  new %7.1f us (%5.2f TB/s)\n", B, H, W, C,
            target_waves, check ? (bad ? "DIFF" : "same bits") : "unchecked", iters ? t_old * 1e3 / iters : 0.0, iters ? mb / (t_old * 1e3 / iters) : 0.0,
            iters ? t_new * 1e3 / iters : 0.0, iters ? mb / (t_new * 1e3 / iters) : 0.0);
     hipFree(x); hipFree(y0); hipFree(y1); hipFree(sink); hipFree(dw); hipFree(db);
@@ -97,7 +96,7 @@ static void stamp_case(int B, int H, int W, int waves) {
     CK(hipMemset(x, 0, n * 4)); CK(hipMemset(dw, 0, 49 * C * 4)); CK(hipMemset(db, 0, C * 4));
     std::vector<unsigned long long> st(4096 * 8, 0);
     CK(hipMemcpyToSymbol(HIP_SYMBOL(acx_dwc_stamps), st.data(), st.size() * 8));
-    for (int i = 0; i < 6; ++i) launch_dwconv_col(x, y, dw, db, sink, B, H, W, false, waves, nullptr);
+    for (int i = 0; i < 6; ++i) launch_dwconv_col(x, y, dw, db, sink, B, H, W, waves, nullptr);
     CK(hipDeviceSynchronize());
     CK(hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(acx_dwc_stamps), st.size() * 8));
     unsigned long long t0 = ~0ull, t6 = 0; int items = 0;
@@ -130,23 +129,20 @@ int main(int argc, char** argv) {
     return 0;
 #endif
     if (argc > 2) {          // timing only: B=64 at `waves`, B=32 at waves and waves/2
-        for (int s = 0; s < 4; ++s) run_case(64, Hs[s], Ws[s], false, 20, waves, false);
-        for (int s = 0; s < 4; ++s) run_case(32, Hs[s], Ws[s], false, 20, waves, false);
-        for (int s = 0; s < 3; ++s) run_case(64, Hs[s], Ws[s], true, 20, waves, false);
+        for (int s = 0; s < 4; ++s) run_case(64, Hs[s], Ws[s], 20, waves, false);
+        for (int s = 0; s < 4; ++s) run_case(32, Hs[s], Ws[s], 20, waves, false);
         return 0;
     }
     // odd shapes first (edges: 1 clip, few rows, rows fewer than the halo, many short clips)
     for (int s = 0; s < 4; ++s)
         for (int B : {1, 2, 5})
             for (int H : {1, 2, 3, 7, 23})
-                bad += run_case(B, H >> (s > 1 ? 0 : 0), Ws[s], false, 0, waves, true);
-    for (int s = 0; s < 3; ++s) bad += run_case(3, 9, Ws[s], true, 0, waves, true);
-    for (int s = 0; s < 4; ++s) bad += run_case(4, Hs[s], Ws[s], false, 0, waves, true);
+                bad += run_case(B, H >> (s > 1 ? 0 : 0), Ws[s], 0, waves, true);
+    for (int s = 0; s < 4; ++s) bad += run_case(4, Hs[s], Ws[s], 0, waves, true);
     // product shapes, timed
     for (int B : {64, 32})
-        for (int s = 0; s < 4; ++s) bad += run_case(B, Hs[s], Ws[s], false, 20, waves / (B == 32 ? 2 : 1), true);
-    for (int s = 0; s < 3; ++s) bad += run_case(64, Hs[s], Ws[s], true, 20, waves, true);
-    for (int s = 0; s < 4; ++s) bad += run_case(64, Hs[s], Ws[s], false, 20, 2 * waves, false);
+        for (int s = 0; s < 4; ++s) bad += run_case(B, Hs[s], Ws[s], 20, waves / (B == 32 ? 2 : 1), true);
+    for (int s = 0; s < 4; ++s) bad += run_case(64, Hs[s], Ws[s], 20, 2 * waves, false);
     printf(bad ? "FAILED (%d cases differ)\n" : "all cases identical\n", bad);
     return bad != 0;
 }
