@@ -16,6 +16,7 @@ MODE_LOGITS, MODE_SCENE, MODE_FRAME = 0, 1, 2
 KERNEL_CLASSES = ("frontend", "stem", "dwconv", "pw1", "pw2", "rowstats", "downsample", "poolhead", "transpose",
                   "mlp_fused", "mlp_wide")
 MIN_SAMPLES = 7360
+MAX_VARLEN_CLIPS = 256
 
 _c_int, _c_i64, _c_sz, _vp = ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_void_p
 _pint = ctypes.POINTER(ctypes.c_int)
@@ -34,6 +35,8 @@ SIGNATURES = {
     "acx_workspace_bytes": (_c_int, [_vp, _c_int, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_sub_batches": (_c_int, [_vp, _c_int, ctypes.POINTER(_c_int)]),
     "acx_forward": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_workspace_bytes_varlen": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_forward_varlen": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -150,6 +153,12 @@ class Context:
     def workspace_bytes(self, B, L, mode):
         out = _c_sz()
         check(lib().acx_workspace_bytes(self._h, int(B), int(L), int(mode), ctypes.byref(out)))
+        return out.value
+
+    def workspace_bytes_varlen(self, lengths, mode):
+        lens = (_c_i64 * max(1, len(lengths)))(*[int(n) for n in lengths])
+        out = _c_sz()
+        check(lib().acx_workspace_bytes_varlen(self._h, lens, len(lengths), int(mode), ctypes.byref(out)))
         return out.value
 
     def sub_batches(self, B):

@@ -278,7 +278,27 @@ inline void launch_kernel(K kernel, dim3 grid, dim3 block, size_t lds, hipStream
     else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
 }
 
-inline int stage_h0(int T) { return (T + 8 - 4) / 4 + 1; }
+__host__ __device__ inline int stage_h0(int T) { return (T + 8 - 4) / 4 + 1; }
+
+// ---- variable-length batches (acx_forward_varlen, varlen.hip) -------------------------------------------------------------
+// Clip i of a packed batch owns samples [soff[i], soff[i+1]), frames [foff[i], foff[i+1]) and, at stage s, image rows
+// [roff[s][i], roff[s][i+1]) (H_s,i = T_i ... as the uniform geometry).  The depthwise kernels see the stage as one tall image of
+// VIRTUAL rows: clip i starts at virtual row roff[s][i] + 3 i, and the three virtual rows after each clip are zero rows that
+// exist in no memory.  All tables live in the head of the forward's workspace and are written by one kernel per call.
+constexpr int kVarMaxClips = ACX_MAX_VARLEN_CLIPS;
+struct VarGeom {
+    const long long* soff;        // [B+1] sample offsets
+    const int* foff;              // [B+1] frame offsets
+    const int* roff[4];           // [B+1] row offsets per stage
+    const int* vclip[4];          // [vrows[s]] clip of virtual row v (a zero row belongs to the clip above it)
+    const unsigned* vbits[4];     // [vwords[s]] bit v + 32 of word (v + 32) / 32: virtual row v is an image row
+    const int* rclip0;            // [rows[0]] clip of stage-0 image row r (stem)
+    const int* irow[4];           // s = 1..3: [rows[s]] stage s-1 image row of the top-left input of stage-s row r (downsample)
+    int B;
+    // host copies of the sizes (launch geometry)
+    long long samples;
+    int frames, rows[4], vrows[4], vwords[4], maxT, maxH[4];
+};
 
 // ---- kernel launchers (each returns acx_status) ---------------------------------------------
 // dense_frames / dense_spec: scratch of the dense-DFT fallback (B*T*1024 and B*T*kDenseN floats); null: the context's own
@@ -319,6 +339,7 @@ struct GemmArgs {
     const float* resid;      // EPI_RESID: added to the result (may alias out)
     int64_t M; int N; int K;
     // 2x2 gather (downsample): A is NHWC (B,H,W,C) and row m=(b,h',w'), k=(dy*2+dx)*C+c
+    const int* irow;        // gather, variable-length batch: VarGeom::irow of the output stage (null: uniform)
     int gather; int H, W, C, Ho, Wo;
     int epi; int cls;
 };
@@ -329,6 +350,7 @@ int launch_layernorm_rows_bf16(acx_ctx* c, const float* x, void* out, int64_t M,
 struct GemmBf16Args {
     const void* A; const void* Wt; const float* bias; void* out; const float* resid;
     int64_t M; int N; int Kp; int lda;
+    const int* irow;        // gather, variable-length batch: VarGeom::irow of the output stage (null: uniform)
     int gather; int H, W, Cp, Ho, Wo;
     int epi; int cls;
     int out_bf16;            // EPI_BIAS only: write the result as bf16 (the next stage's bf16 activations)
@@ -343,6 +365,7 @@ struct GemmSplitArgs {
     const void* A; const void* Wt; const float* bias; void* out; const float* resid;
     int64_t M; int N; int K; float sinv;
     float hscale;            // EPI_GELU: power-of-two scale of the S16 output
+    const int* irow;        // gather, variable-length batch: VarGeom::irow of the output stage (null: uniform)
     int gather; int H, W, C, Ho, Wo;
     int epi; int cls;
 };
@@ -375,6 +398,23 @@ int launch_pool_head(acx_ctx* c, const float* x, int B, int H3, float* scene, fl
                      hipStream_t s);
 int launch_nhwc_to_nchw(acx_ctx* c, const float* x, float* out, int B, int H, int W, int C, hipStream_t s);
 int launch_pcm16_to_f32(const short* in, float* out, long long n, hipStream_t s);
+
+// variable-length forms (vg: tables of acx_forward_varlen; same arithmetic per element as the uniform kernels)
+int launch_logmel_varlen(acx_ctx* c, const float* wav, const VarGeom& vg, float* out, hipStream_t s, float* dense_frames,
+                         float* dense_spec);
+int launch_stem_varlen(acx_ctx* c, const float* in, const VarGeom& vg, void* out, hipStream_t s, bool act_bf16);
+int launch_dwconv_col_varlen(const void* x, void* y, const float* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
+                             int target_waves, hipStream_t s);
+int launch_dwconv_mfma_varlen(const void* x, void* y, const void* dw_ops, const float* bias, void* sink, const VarGeom& vg,
+                              int stage, int target_waves, hipStream_t s);
+int launch_dwconv_varlen(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, const VarGeom& vg, int stage,
+                         hipStream_t s, bool act_bf16);
+int launch_pool_head_varlen(acx_ctx* c, const float* x, const VarGeom& vg, float* scene, float* logits, float* probs,
+                            hipStream_t s);
+int launch_nhwc_to_nchw_varlen(acx_ctx* c, const float* x, float* out, const VarGeom& vg, hipStream_t s);
+// the tables of vg (device pointers into `ws`) from the host lengths; bytes: their size (256-byte aligned)
+int varlen_geometry(const int64_t* lengths, int B, char* ws, VarGeom* vg, size_t* bytes);
+int launch_varlen_tables(const int64_t* lengths, const VarGeom& vg, hipStream_t s);
 
 // number of CUs of the current device (one persistent workgroup each), cached per device
 inline int cu_count_of_current_device(int* out) {

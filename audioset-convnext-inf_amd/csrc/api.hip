@@ -441,18 +441,24 @@ static int run_mlp_split(acx_ctx* c, const BlockW& bw, int C, float* y, float* x
 // MLP kernels of stages 0-2 in the 16-bit arithmetics (LNOUT epilogue).  x of that stage is then NOT updated by its last block.
 static bool block_can_emit_ln(const acx_ctx* c, int s) { return s < 3 && c->precision != ACX_PREC_F32; }
 
+// vg: a variable-length batch (acx_forward_varlen) -- B = 1 and H = the stage's total rows then, so that M counts every pixel;
+// only the depthwise conv needs the per-clip tables
 static int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, int B, int H, int Wd,
-                     hipStream_t st, void* ln_out = nullptr) {
+                     hipStream_t st, void* ln_out = nullptr, const VarGeom* vg = nullptr) {
     const int C = kDims[s];
     const BlockW& bw = c->blocks[s][j];
     const int64_t M = (int64_t)B * H * Wd;
+    auto launch_dw = [&](float* row_stats, bool ab) {
+        if (vg) return launch_dwconv_varlen(c, bw, C, x, y, row_stats, *vg, s, st, ab);
+        return launch_dwconv(c, bw, C, x, y, row_stats, B, H, Wd, st, ab);
+    };
     switch (c->precision) {
         case ACX_PREC_F32: {
             if (mlp_fused_supported(C)) {
-                ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st));      // LN statistics are computed in-kernel
+                ACX_TRY(launch_dw(nullptr, false));      // LN statistics are computed in-kernel
                 return launch_mlp_fused(c, bw, C, y, x, M, st);
             }
-            ACX_TRY(launch_dwconv(c, bw, C, x, y, stats, B, H, Wd, st));
+            ACX_TRY(launch_dw(stats, false));
             GemmArgs g1{};
             g1.A = y; g1.Wt = bw.w1; g1.bias = bw.b1; g1.out = hidden; g1.stats = stats; g1.colsum = bw.w1sum; g1.M = M; g1.N = 4 * C; g1.K = C;
             g1.epi = EPI_GELU; g1.cls = ACX_K_PW1;
@@ -463,14 +469,14 @@ static int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden
             return launch_gemm(c, g2, st);
         }
         case ACX_PREC_F32_SPLIT:
-            ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st));
+            ACX_TRY(launch_dw(nullptr, false));
             if (mlp_fused_split_supported(C)) return launch_mlp_fused_split(c, bw, C, y, x, M, st, ln_out);
             if (mlp_fused_wide_supported(C)) return launch_mlp_fused_wide(c, bw, C, y, x, M, st, ln_out);
             if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
             return run_mlp_split(c, bw, C, y, x, hidden, M, st);
         default: {                                                              // bf16, bf16a
             const bool ab = act_bf16(c, s);         // x and y of this stage are bf16 tensors in HBM
-            ACX_TRY(launch_dwconv(c, bw, C, x, y, nullptr, B, H, Wd, st, ab));
+            ACX_TRY(launch_dw(nullptr, ab));
             if (mlp_fused_wide_bf16_supported(C)) return launch_mlp_fused_wide_bf16(c, bw, C, y, x, M, st, ln_out, pad64(C), ab);
             if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
             return run_mlp_bf16(c, bw, C, y, x, hidden, M, st);
@@ -481,17 +487,21 @@ static int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden
 // have_ln: xnorm already holds the normalised S16 rows (written by the last block of the previous stage)
 // out_bf16: the result is the bf16 activation tensor of stage i (ACX_PREC_BF16_ACT inside acx_forward; the per-layer entry
 // point keeps fp32)
+// vg: a variable-length batch -- B = 1 and H = the input stage's total rows; the output rows and the gather come from the tables
+// (a clip of odd height drops its last row, as the stride-2 conv does)
 static int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, int B, int H, int Wd,
-                          hipStream_t st, bool have_ln = false, bool out_bf16 = false) {
+                          hipStream_t st, bool have_ln = false, bool out_bf16 = false, const VarGeom* vg = nullptr) {
     const int Ci = kDims[i - 1], Co = kDims[i];
     const DownW& d = c->down[i];
+    const int* irow = vg ? vg->irow[i] : nullptr;
+    const int64_t Mout = vg ? (int64_t)vg->rows[i] * (Wd / 2) : (int64_t)B * (H / 2) * (Wd / 2);
     switch (c->precision) {
         case ACX_PREC_F32: {
             ACX_TRY(launch_layernorm_rows(c, x, xnorm, (int64_t)B * H * Wd, Ci, st));
             GemmArgs g{};
             g.A = xnorm; g.Wt = d.w; g.bias = d.b; g.out = out;
             g.gather = 1; g.H = H; g.W = Wd; g.C = Ci; g.Ho = H / 2; g.Wo = Wd / 2;
-            g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.K = 4 * Ci; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
+            g.M = Mout; g.N = Co; g.K = 4 * Ci; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE; g.irow = irow;
             return launch_gemm(c, g, st);
         }
         case ACX_PREC_F32_SPLIT: {
@@ -499,8 +509,8 @@ static int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* 
             GemmSplitArgs g{};
             g.A = xnorm; g.Wt = d.ws; g.bias = d.b; g.out = out;
             g.gather = 1; g.H = H; g.W = Wd; g.C = Ci; g.Ho = H / 2; g.Wo = Wd / 2;
-            g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.K = 4 * Ci; g.sinv = 1.0f / (kSplitLnScale * d.ws_scale);
-            g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
+            g.M = Mout; g.N = Co; g.K = 4 * Ci; g.sinv = 1.0f / (kSplitLnScale * d.ws_scale);
+            g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE; g.irow = irow;
             return launch_gemm_split(c, g, st);
         }
         default: {                                                              // bf16, bf16a
@@ -510,7 +520,7 @@ static int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* 
             g.out_bf16 = out_bf16 ? 1 : 0;
             g.A = xnorm; g.Wt = d.wh; g.bias = d.b; g.out = out;
             g.gather = 1; g.H = H; g.W = Wd; g.Cp = Cp; g.Ho = H / 2; g.Wo = Wd / 2;
-            g.M = (int64_t)B * g.Ho * g.Wo; g.N = Co; g.Kp = 4 * Cp; g.lda = Cp; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE;
+            g.M = Mout; g.N = Co; g.Kp = 4 * Cp; g.lda = Cp; g.epi = EPI_BIAS; g.cls = ACX_K_DOWNSAMPLE; g.irow = irow;
             return launch_gemm_bf16(c, g, st);
         }
     }
@@ -558,7 +568,7 @@ static int make_aux(acx_ctx::Aux* a) {
 extern "C" {
 
 const char* acx_last_error(void) { return g_err; }
-int acx_version(void) { return 100; }
+int acx_version(void) { return 101; }
 
 int acx_create(int hip_device, acx_ctx** out) {
     if (!out) ACX_FAIL(ACX_ERR_ARG, "acx_create: out is null");
@@ -852,6 +862,77 @@ int acx_forward(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float*
     Plan p;
     ACX_TRY(make_plan(B, L, &p));
     return forward_one(c, wav, B, L, mode, out0, out1, ws, p, st);
+}
+
+// ---- variable-length batches -------------------------------------------------------------------------------------------
+// Workspace: the geometry tables (varlen_geometry), then the tensors of make_plan sized by the sums over the clips.
+struct VarPlan {
+    VarGeom g;
+    size_t off_feat, off_x[4], off_y, off_hidden, off_stats, total;
+};
+
+static int make_plan_varlen(const int64_t* lengths, int B, char* ws, VarPlan* p) {
+    size_t off = 0;
+    ACX_TRY(varlen_geometry(lengths, B, ws, &p->g, &off));
+    const VarGeom& g = p->g;
+    p->off_feat = off; off += align_up((size_t)g.frames * kMels * 4);
+    for (int s = 0; s < 4; ++s) { p->off_x[s] = off; off += align_up((size_t)g.rows[s] * (kStemW >> s) * kDims[s] * 4); }
+    const size_t pix0 = (size_t)g.rows[0] * kStemW;
+    // (dense-DFT frontend: frames in `hidden`, spectrum in `y`, as in forward_one -- the per-clip bounds hold for the sums)
+    p->off_y = off; off += align_up(pix0 * kDims[0] * 4);
+    p->off_hidden = off; off += align_up(pix0 * 4 * kDims[0] * 4);
+    p->off_stats = off; off += align_up(pix0 * 2 * 4);
+    p->total = off;
+    return ACX_OK;
+}
+
+int acx_workspace_bytes_varlen(const acx_ctx* c, const int64_t* lengths, int B, int mode, size_t* out_bytes) {
+    (void)c;
+    if (!out_bytes || mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_workspace_bytes_varlen: bad argument");
+    VarPlan p;
+    ACX_TRY(make_plan_varlen(lengths, B, nullptr, &p));
+    *out_bytes = p.total;
+    return ACX_OK;
+}
+
+int acx_forward_varlen(acx_ctx* c, const float* wav, const int64_t* lengths, int B, int mode, float* out0, float* out1,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: null pointer");
+    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: bad mode %d", mode);
+    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: logits mode needs out1 (probs)");
+    if (((uintptr_t)workspace & 255) != 0) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    char* ws = (char*)workspace;
+    VarPlan p;
+    ACX_TRY(make_plan_varlen(lengths, B, ws, &p));
+    if (workspace_bytes < p.total)
+        ACX_FAIL(ACX_ERR_WORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, p.total);
+    hipStream_t st = (hipStream_t)stream;
+    const VarGeom& g = p.g;
+    float* feat = (float*)(ws + p.off_feat);
+    float* x[4];
+    for (int s = 0; s < 4; ++s) x[s] = (float*)(ws + p.off_x[s]);
+    float* y = (float*)(ws + p.off_y);
+    float* hidden = (float*)(ws + p.off_hidden);
+    float* stats = (float*)(ws + p.off_stats);
+    ACX_TRY(launch_varlen_tables(lengths, g, st));
+    ACX_TRY(launch_logmel_varlen(c, wav, g, feat, st, hidden, y));
+    ACX_TRY(launch_stem_varlen(c, feat, g, x[0], st, act_bf16(c, 0)));
+    for (int s = 0; s < 4; ++s) {
+        const int Wd = kStemW >> s;
+        if (s > 0) {      // as in forward_one: the last block of the stage before may have written the LayerNorm'ed rows
+            const bool have_ln = block_can_emit_ln(c, s - 1);
+            ACX_TRY(run_downsample(c, s, x[s - 1], x[s], have_ln ? hidden : y, 1, g.rows[s - 1], Wd * 2, st, have_ln,
+                                   act_bf16(c, s), &g));
+        }
+        for (int j = 0; j < kDepths[s]; ++j) {
+            void* ln_out = (j == kDepths[s] - 1 && block_can_emit_ln(c, s)) ? (void*)hidden : nullptr;
+            ACX_TRY(run_block(c, s, j, x[s], y, hidden, stats, 1, g.rows[s], Wd, st, ln_out, &g));
+        }
+    }
+    if (mode == ACX_MODE_FRAME) return launch_nhwc_to_nchw_varlen(c, x[3], out0, g, st);
+    if (mode == ACX_MODE_SCENE) return launch_pool_head_varlen(c, x[3], g, out0, nullptr, nullptr, st);
+    return launch_pool_head_varlen(c, x[3], g, nullptr, out0, out1, st);
 }
 
 int acx_logmel_bn0(acx_ctx* c, const float* wav, int B, int64_t L, float* out, int apply_bn0, void* stream) {

@@ -697,3 +697,28 @@ int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, fl
 }
 
 }  // namespace acx
+
+namespace acx {
+
+// Variable-length batch (acx_forward_varlen): the column-streaming kernel for fp32 activations at every launch size, the matrix
+// form for bf16 activations -- the forms give the same bits as the uniform launcher's choices (ACX_DW_STREAM tests), and only
+// they know the per-clip row tables.
+int launch_dwconv_varlen(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, const VarGeom& vg, int stage,
+                         hipStream_t s, bool act_bf16) {
+    if (!c || !c->d_dw_sink) ACX_FAIL(ACX_ERR_STATE, "dwconv7 (variable length): no context");
+    if (C != kDims[stage]) ACX_FAIL(ACX_ERR_SHAPE, "dwconv7 (variable length): stage %d has %d channels, got %d", stage, kDims[stage], C);
+    ProfScope ps(c, ACX_K_DWCONV, s);
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    if (act_bf16) {
+        if (stats) ACX_FAIL(ACX_ERR_STATE, "dwconv7: row statistics are computed from fp32 activations only");
+        if (!w.dw_ops || stage > 2) ACX_FAIL(ACX_ERR_STATE, "dwconv7: bf16 activations need the matrix-pipe kernel and its packed weights (stages 0-2)");
+        const int per_cu = tuning().dwm_waves.load(std::memory_order_relaxed);
+        return launch_dwconv_mfma_varlen(x, y, w.dw_ops, w.dwb, c->d_dw_sink, vg, stage, (per_cu ? per_cu : 8) * cus, s);
+    }
+    ACX_TRY(launch_dwconv_col_varlen(x, y, w.dw, w.dwb, c->d_dw_sink, vg, stage, 4 * cus, s));
+    if (stats) ACX_TRY(launch_rowstats(c, reinterpret_cast<const float*>(y), stats, (int64_t)vg.rows[stage] * (kStemW >> stage), C, s));
+    return ACX_OK;
+}
+
+}  // namespace acx

@@ -195,13 +195,19 @@ __device__ __forceinline__ void dwc_row(DwColState<W>& st, const char* rowp, boo
 // S0: a segment of n_out = 7 k7 - S0 output rows (any length >= 7) runs as a virtual segment of 7 k7 rows that starts S0 rows
 // higher and whose first S0 steps are not executed: the first and the last six executed steps then still sit at fixed phases of
 // the rotation, for every segment length (a multiple of 7 only would leave up to 12 % of the wave slots of stage 2 empty).
-template <int W, int R, int WPS, int S0>
+// VAR: a variable-length batch (S0 = 0 only).  Clip i starts at virtual row roff[i] + 3 i; bit v + 32 of vbits says whether
+// virtual row v is an image row, and the image rows above v number roff[c] + min(v - roff[c] - 3 c, H_c) with c = vclip[v] --
+// the uniform kernel's n H + min(r, H).  The row flags of a group of seven steps are one funnel shift of two scalar-loaded words.
+template <int W, int R, int WPS, int S0, bool VAR>
 __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __restrict__ x_, void* __restrict__ y_,
                                                              const float* __restrict__ wt /*[49][C]*/,
                                                              const float* __restrict__ bias, void* __restrict__ sink_,
                                                              int B, int H, int k7 /* output rows per segment / 7 */, int n_items,
-                                                             unsigned magic /* floor(2^32 / (H + 3)) + 1 */) {
+                                                             unsigned magic /* floor(2^32 / (H + 3)) + 1 */,
+                                                             const unsigned* __restrict__ vbits, int vwords,
+                                                             const int* __restrict__ vclip, const int* __restrict__ roff, int vrows) {
     using Cfg = DwColCfg<W, R>;
+    static_assert(!VAR || S0 == 0, "variable-length segments are whole groups of seven rows");
     static_assert(Cfg::kLdsBytes * WPS <= 160 * 1024, "the rings of a CU's waves do not fit the LDS");
     constexpr int C = Cfg::kC, kEsz = Cfg::kEsz, D = Cfg::kD;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -252,15 +258,26 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
     const int vbv = vb - S0;                                        // first output row of the virtual segment
     const char* const x0 = reinterpret_cast<const char*>(x_);
     const char* pf_ptr;                                             // next in-image row at or after the prefetch cursor
-    {
-        const int v0 = vb - 3 + Hp;                                 // >= 0
-        const int n1 = (int)__umulhi((unsigned)v0, magic), r0 = v0 - n1 * Hp;
-        pf_ptr = x0 + ((long long)(n1 - 1) * H + (r0 < H ? r0 : H)) * Cfg::kGRowB;
-    }
     char* out_ptr;                                                  // next in-image output row at or after vb
-    {
-        const int n = (int)__umulhi((unsigned)vb, magic), r = vb - n * Hp;
-        out_ptr = reinterpret_cast<char*>(y_) + ((long long)n * H + (r < H ? r : H)) * Cfg::kGRowB;
+    if constexpr (VAR) {
+        auto rows_above = [&](int v) -> long long {                 // image rows above virtual row v
+            if (v < 0) return 0;
+            v = v < vrows ? v : vrows - 1;
+            const int cb = vclip[v], r0 = roff[cb], hc = roff[cb + 1] - r0, r = v - r0 - 3 * cb;
+            return (long long)r0 + (r < hc ? r : hc);
+        };
+        pf_ptr = x0 + rows_above(vb - 3) * Cfg::kGRowB;
+        out_ptr = reinterpret_cast<char*>(y_) + rows_above(vb) * Cfg::kGRowB;
+    } else {
+        {
+            const int v0 = vb - 3 + Hp;                                 // >= 0
+            const int n1 = (int)__umulhi((unsigned)v0, magic), r0 = v0 - n1 * Hp;
+            pf_ptr = x0 + ((long long)(n1 - 1) * H + (r0 < H ? r0 : H)) * Cfg::kGRowB;
+        }
+        {
+            const int n = (int)__umulhi((unsigned)vb, magic), r = vb - n * Hp;
+            out_ptr = reinterpret_cast<char*>(y_) + ((long long)n * H + (r < H ? r : H)) * Cfg::kGRowB;
+        }
     }
     // Stores of rows that are not this wave's (the six steps above its segment, the rows between clips) go to a sink.  Every wave
     // gets a window of its own there (modulo kDwSinkWindows): a thousand waves storing to the same lines serialise in one L2 channel.
@@ -270,8 +287,24 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
     // lane l looks at step u = 7 g - 3 + l; bit l of rmask: that input row is inside an image; bit l of omask: it is an
     // output row this wave stores.
     unsigned rmask = 0, omask = 0;
+    // lanes l in [lo, hi) of a 32-bit mask
+    auto lane_range = [](int lo, int hi) -> unsigned {
+        lo = lo < 0 ? 0 : (lo > 32 ? 32 : lo);
+        hi = hi < 0 ? 0 : (hi > 32 ? 32 : hi);
+        if (hi <= lo) return 0u;
+        const unsigned below_hi = hi >= 32 ? ~0u : (1u << hi) - 1u, below_lo = (1u << lo) - 1u;
+        return below_hi & ~below_lo;
+    };
 #define ACX_DWC_FLAGS(g_)                                                                                       \
-    {                                                                                                           \
+    if constexpr (VAR) {                                                                                        \
+        const int vl0_ = vbv - 6 + 7 * (g_);                          /* virtual row of lane 0: >= -6 */         \
+        const int w_ = (vl0_ + 32) >> 5, sh_ = (vl0_ + 32) & 31;                                                \
+        const unsigned lo_ = w_ < vwords ? vbits[w_] : 0u, hi_ = w_ + 1 < vwords ? vbits[w_ + 1] : 0u;          \
+        const unsigned bits_ = (unsigned)((((unsigned long long)hi_ << 32) | lo_) >> sh_);                      \
+        /* lane l is virtual step u = 7 g - 3 + l */                                                            \
+        rmask = bits_ & lane_range(S0 + 3 - 7 * (g_), 7 * k7 + 9 - 7 * (g_));                                   \
+        omask = bits_ & lane_range(S0 + 6 - 7 * (g_), 7 * k7 + 6 - 7 * (g_));                                   \
+    } else {                                                                                                    \
         const int u_ = 7 * (g_) - 3 + lane;                           /* virtual step */                        \
         const int v_ = vbv - 3 + u_;                                                                            \
         const unsigned vv_ = (unsigned)(v_ + 9 * Hp);                 /* >= 0: v_ >= -15, Hp >= 4 */            \
@@ -372,9 +405,10 @@ template <int W, int R, int WPS, int S0>
 static int launch_dw_col_s0(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H, int k7, int n_items, hipStream_t s) {
     using Cfg = DwColCfg<W, R>;
     static DeviceOnce once;
-    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_col_kernel<W, R, WPS, S0>, Cfg::kLdsBytes));
-    launch_kernel(&dwconv7_col_kernel<W, R, WPS, S0>, dim3((unsigned)((n_items + 3) / 4)), dim3(256), Cfg::kLdsBytes, s,
-        x, y, wt, bias, sink, B, H, k7, n_items, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u);
+    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_col_kernel<W, R, WPS, S0, false>, Cfg::kLdsBytes));
+    launch_kernel(&dwconv7_col_kernel<W, R, WPS, S0, false>, dim3((unsigned)((n_items + 3) / 4)), dim3(256), Cfg::kLdsBytes, s,
+        x, y, wt, bias, sink, B, H, k7, n_items, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u, (const unsigned*)nullptr, 0,
+        (const int*)nullptr, (const int*)nullptr, 0);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
@@ -382,6 +416,29 @@ static int launch_dw_col_s0(const void* x, void* y, const float* wt, const float
 // target_waves: how many waves the launch should consist of (one per SIMD of the CUs it may use).  Every wave takes a segment
 // of n_out = ceil(rows / segments) output rows of the stacked batch; the kernel instantiation for n_out's remainder modulo the
 // rotation's seven phases (S0) runs it.
+// variable-length batch: segments of a multiple of seven rows (the S0 = 0 instantiation only)
+template <int W, int R, int WPS>
+static int launch_dw_col_var(const void* x, void* y, const float* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
+                             int target_waves, hipStream_t s) {
+    using Cfg = DwColCfg<W, R>;
+    const long long Vt = (long long)vg.vrows[stage] - 3;
+    long long segs = (long long)target_waves * WPS / Cfg::kUnits;
+    if (segs < 1) segs = 1;
+    long long n_out = (Vt + segs - 1) / segs;
+    const long long nmin = WPS == 2 ? 7 : kDwColMinRows;
+    if (n_out < nmin) n_out = nmin;
+    n_out = (n_out + 6) / 7 * 7;
+    const long long n_seg = (Vt + n_out - 1) / n_out;
+    const int n_items = (int)(n_seg * Cfg::kUnits);
+    static DeviceOnce once;
+    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_col_kernel<W, R, WPS, 0, true>, Cfg::kLdsBytes));
+    launch_kernel(&dwconv7_col_kernel<W, R, WPS, 0, true>, dim3((unsigned)((n_items + 3) / 4)), dim3(256), Cfg::kLdsBytes, s,
+        x, y, wt, bias, sink, vg.B, 0, (int)(n_out / 7), n_items, 0u, vg.vbits[stage], vg.vwords[stage], vg.vclip[stage],
+        vg.roff[stage], vg.vrows[stage]);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
 template <int W, int R, int WPS>
 static int launch_dw_col_cfg(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H,
                              int target_waves, hipStream_t s) {
@@ -421,6 +478,17 @@ int launch_dwconv_col(const void* x, void* y, const float* wt, const float* bias
         case 14: return launch_dw_col_cfg<14, 4, 2>(x, y, wt, bias, sink, B, H, target_waves, s);
         case 7: return launch_dw_col_cfg<7, 5, 2>(x, y, wt, bias, sink, B, H, target_waves, s);
         default: ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: unsupported width %d (expected 56/28/14/7)", W);
+    }
+}
+
+int launch_dwconv_col_varlen(const void* x, void* y, const float* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
+                             int target_waves, hipStream_t s) {
+    switch (stage) {
+        case 0: return launch_dw_col_var<56, 7, 1>(x, y, wt, bias, sink, vg, 0, target_waves, s);
+        case 1: return launch_dw_col_var<28, 7, 1>(x, y, wt, bias, sink, vg, 1, target_waves, s);
+        case 2: return launch_dw_col_var<14, 4, 2>(x, y, wt, bias, sink, vg, 2, target_waves, s);
+        case 3: return launch_dw_col_var<7, 5, 2>(x, y, wt, bias, sink, vg, 3, target_waves, s);
+        default: ACX_FAIL(ACX_ERR_ARG, "dwconv7: no stage %d", stage);
     }
 }
 

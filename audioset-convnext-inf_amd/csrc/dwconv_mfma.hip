@@ -96,10 +96,14 @@ __device__ __forceinline__ const char* dwm_scalar(const char* p) {
 }
 __device__ __forceinline__ dwm_s4 dwm_op(unsigned r0, unsigned r1) { dwm_u2 v; v.x = r0; v.y = r1; return __builtin_bit_cast(dwm_s4, v); }
 
-template <int W, int S, int LEFT, int RIGHT>
+// VAR: a variable-length batch.  The cursors carry the height of their clip (qH / oH) instead of the uniform H: a cursor finds its
+// clip once (vclip of its first virtual row), and at every wrap into the next clip reads that clip's height from roff.  Clip -1
+// (the three rows above the first clip) has height 0, and so has every "clip" past the last.
+template <int W, int S, int LEFT, int RIGHT, bool VAR>
 __device__ __forceinline__ void dwm_run(const char* __restrict__ x, char* __restrict__ y, const char* __restrict__ ops,
                                         const float* __restrict__ bias, char* sink, char* lds, int piece, int B, int H, int steps, int seg,
-                                        int slice, int jt0, unsigned magic, int item) {
+                                        int slice, int jt0, unsigned magic, int item, const int* __restrict__ roff,
+                                        const int* __restrict__ vclip, int vrows) {
     using Cfg = DwmCfg<W, S, LEFT, RIGHT>;
     using G = DwmGeom<W>;
     constexpr int C = Cfg::kC, Q = Cfg::kQ, kPitch = G::kPitch, R = kDwmRing;
@@ -124,20 +128,35 @@ __device__ __forceinline__ void dwm_run(const char* __restrict__ x, char* __rest
     int qn, qr, qleft = Lrows + 6;                         // the request cursor; rows the segment still needs: vb - 3 .. vb + L + 2
     unsigned qoff = 0;                                     // byte offset of its ring slot (row vb - 3 sits in slot 0)
     const char* qptr;
-    {
+    int qH = H;                                            // VAR: height of the request cursor's clip
+    const char* safe_src;
+    auto clip_h = [&](int n) -> int { return n >= 0 && n < B ? roff[n + 1] - roff[n] : 0; };
+    if constexpr (VAR) {
+        const int v0 = vb - 3;
+        if (v0 < 0) {
+            qn = -1; qr = v0 + 3; qH = 0;
+            qptr = dwm_scalar(x);
+        } else {
+            const int cb = vclip[v0 < vrows ? v0 : vrows - 1];
+            const int r0 = roff[cb];
+            qn = cb; qH = roff[cb + 1] - r0; qr = v0 - r0 - 3 * cb;
+            qptr = dwm_scalar(x + ((long long)r0 + (qr < qH ? qr : qH)) * G::kGRowB);
+        }
+        safe_src = dwm_scalar(x + (long long)roff[qn < 0 ? 0 : qn] * G::kGRowB);
+    } else {
         const int v0 = vb - 3 + Hp;                        // >= 0
         const int n1 = (int)__umulhi((unsigned)v0, magic);
         qr = v0 - n1 * Hp; qn = n1 - 1;
         // (64-bit products are vector instructions even on uniform values: back to scalar registers once, here -- the cursors then
         // advance by scalar adds; without this every request re-read its pointer out of vector registers)
         qptr = dwm_scalar(x + ((long long)qn * H + (qr < H ? qr : H)) * G::kGRowB);
+        safe_src = dwm_scalar(x + (long long)(qn < 0 ? 0 : (qn < B ? qn : B - 1)) * H * G::kGRowB);   // for the requests of non-image rows: a row of this wave's own neighbourhood
     }
-    const char* safe_src = dwm_scalar(x + (long long)(qn < 0 ? 0 : (qn < B ? qn : B - 1)) * H * G::kGRowB);   // for the requests of non-image rows: a row of this wave's own neighbourhood
     // One request per call, always (the counted waits rely on it).  A row between clips: zeros written by the wave itself, the
     // request re-reads the wave's latest row into the dummy row; a row past the segment's last: the same without the zeros.
     auto request = [&]() {
         const bool need = qleft > 0;
-        const bool real = need && qr < H && (unsigned)qn < (unsigned)B;
+        const bool real = need && qr < (VAR ? qH : H) && (unsigned)qn < (unsigned)B;
         const char* const src = real ? qptr : safe_src;
         const unsigned dst = ring_lds + poff + (real ? qoff : (unsigned)(R * kPitch));
         if (need && !real) {
@@ -146,16 +165,23 @@ __device__ __forceinline__ void dwm_run(const char* __restrict__ x, char* __rest
         safe_src = src;
         qptr += real ? G::kGRowB : 0;
         qoff = qoff + kPitch == (unsigned)(R * kPitch) ? 0u : qoff + kPitch;
-        const bool wrap = qr + 1 == Hp;
+        const bool wrap = qr + 1 == (VAR ? qH + 3 : Hp);
         qr = wrap ? 0 : qr + 1;
         qn += wrap ? 1 : 0;
+        if constexpr (VAR) { if (wrap) qH = clip_h(qn); }
         qleft -= 1;
         if (ACX_DWM_ABLATE == 2) return;
         if (vok) acx_glds16_s(dwm_scalar(src), voff, __builtin_amdgcn_readfirstlane(dst));
     };
     int on, orow;                                          // the output cursor
     char* optr;
-    {
+    int oH = H;                                            // VAR: height of the output cursor's clip
+    if constexpr (VAR) {
+        const int cb = vclip[vb < vrows ? vb : vrows - 1];
+        const int r0 = roff[cb];
+        on = cb; oH = roff[cb + 1] - r0; orow = vb - r0 - 3 * cb;
+        optr = const_cast<char*>(dwm_scalar(y + ((long long)r0 + (orow < oH ? orow : oH)) * G::kGRowB));
+    } else {
         const int n = (int)__umulhi((unsigned)vb, magic);
         on = n; orow = vb - n * Hp;
         optr = const_cast<char*>(dwm_scalar(y + ((long long)n * H + (orow < H ? orow : H)) * G::kGRowB));
@@ -264,12 +290,13 @@ __device__ __forceinline__ void dwm_run(const char* __restrict__ x, char* __rest
 #define ACX_DWM_STORE()                                                                                         \
     {                                                                                                           \
         _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                      \
-            const bool real_ = ACX_DWM_ABLATE != 5 && live > 1 && orow < H && on < B;                           \
+            const bool real_ = ACX_DWM_ABLATE != 5 && live > 1 && orow < (VAR ? oH : H) && on < B;              \
             /* scalar base + 32-bit lane offset: the address costs no vector instruction; W = 14: the two lanes of the last \
                quad that lie outside the image are masked out of the store */                                   \
             char* const d_ = real_ ? optr : sink;                                                               \
             optr += real_ ? G::kGRowB : 0;                                                                      \
-            { const bool wrap_ = orow + 1 == Hp; orow = live > 1 ? (wrap_ ? 0 : orow + 1) : orow; on += (live > 1 && wrap_) ? 1 : 0; } \
+            { const bool wrap_ = orow + 1 == (VAR ? oH + 3 : Hp); orow = live > 1 ? (wrap_ ? 0 : orow + 1) : orow; on += (live > 1 && wrap_) ? 1 : 0; \
+              if constexpr (VAR) { if (live > 1 && wrap_) oH = clip_h(on); } }                                  \
             _Pragma("unroll") for (int jt_ = 0; jt_ < S; ++jt_) {                                               \
                 if (!(W == 14 && jt_ == 3 && q >= 2))                                                           \
                     *reinterpret_cast<unsigned*>(d_ + (size_t)(lane_off + (unsigned)(jt_ * 4 * C * 2))) = outp[jt_][i_]; \
@@ -311,10 +338,11 @@ __device__ __forceinline__ void dwm_run(const char* __restrict__ x, char* __rest
 // ADVICE r05): ONE workgroup of eight waves per CU -- two waves per SIMD as before, 512 threads x 256 registers claimed, all of the
 // LDS requested at launch -- so that no foreign wave (packed-FP32 code of another stream or process) is ever co-resident with it.
 // tools/check_exclusive.py verifies the descriptor of the shipped kernel.
-template <int W>
+template <int W, bool VAR>
 __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const void* __restrict__ x_, void* __restrict__ y_, const void* __restrict__ ops_ /* dw_ops */,
                                                               const float* __restrict__ bias, void* __restrict__ sink_, int B, int H,
-                                                              int steps /* 4-row steps per segment */, int n_groups, unsigned magic) {
+                                                              int steps /* 4-row steps per segment */, int n_groups, unsigned magic,
+                                                              const int* __restrict__ roff, const int* __restrict__ vclip, int vrows) {
     using G = DwmGeom<W>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -335,15 +363,15 @@ __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const void* __restric
     char* sink = reinterpret_cast<char*>(sink_) + (size_t)(item % kDwSinkWindows) * kDwSinkWindowBytes;
     char* lds = smem + (wave / G::kStrips) * G::kGroupLds;
     if constexpr (W == 56) {
-        if (strip == 0) dwm_run<56, 4, 0, 1>(x, y, wt, bias, sink, lds, 0, B, H, steps, seg, slice, 0, magic, item);
-        else if (strip == 1) dwm_run<56, 4, 1, 1>(x, y, wt, bias, sink, lds, 1, B, H, steps, seg, slice, 4, magic, item);
-        else if (strip == 2) dwm_run<56, 3, 1, 1>(x, y, wt, bias, sink, lds, 2, B, H, steps, seg, slice, 8, magic, item);
-        else dwm_run<56, 3, 1, 0>(x, y, wt, bias, sink, lds, 3, B, H, steps, seg, slice, 11, magic, item);
+        if (strip == 0) dwm_run<56, 4, 0, 1, VAR>(x, y, wt, bias, sink, lds, 0, B, H, steps, seg, slice, 0, magic, item, roff, vclip, vrows);
+        else if (strip == 1) dwm_run<56, 4, 1, 1, VAR>(x, y, wt, bias, sink, lds, 1, B, H, steps, seg, slice, 4, magic, item, roff, vclip, vrows);
+        else if (strip == 2) dwm_run<56, 3, 1, 1, VAR>(x, y, wt, bias, sink, lds, 2, B, H, steps, seg, slice, 8, magic, item, roff, vclip, vrows);
+        else dwm_run<56, 3, 1, 0, VAR>(x, y, wt, bias, sink, lds, 3, B, H, steps, seg, slice, 11, magic, item, roff, vclip, vrows);
     } else if constexpr (W == 28) {
-        if (strip == 0) dwm_run<28, 4, 0, 1>(x, y, wt, bias, sink, lds, 0, B, H, steps, seg, slice, 0, magic, item);
-        else dwm_run<28, 3, 1, 0>(x, y, wt, bias, sink, lds, 1, B, H, steps, seg, slice, 4, magic, item);
+        if (strip == 0) dwm_run<28, 4, 0, 1, VAR>(x, y, wt, bias, sink, lds, 0, B, H, steps, seg, slice, 0, magic, item, roff, vclip, vrows);
+        else dwm_run<28, 3, 1, 0, VAR>(x, y, wt, bias, sink, lds, 1, B, H, steps, seg, slice, 4, magic, item, roff, vclip, vrows);
     } else {
-        dwm_run<14, 4, 0, 0>(x, y, wt, bias, sink, lds, 0, B, H, steps, seg, slice, 0, magic, item);
+        dwm_run<14, 4, 0, 0, VAR>(x, y, wt, bias, sink, lds, 0, B, H, steps, seg, slice, 0, magic, item, roff, vclip, vrows);
     }
 }
 
@@ -361,11 +389,43 @@ static int launch_dw_mfma_w(const void* x, void* y, const void* wt, const float*
     const long long n_seg = (Vt + rows - 1) / rows;
     const int n_groups = (int)(n_seg * G::kSlices);
     static DeviceOnce once;
-    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_mfma_kernel<W>, kCuLdsBytes));
-    launch_kernel(&dwconv7_mfma_kernel<W>, dim3((unsigned)((n_groups + G::kGroups - 1) / G::kGroups)), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
-        x, y, wt, bias, sink, B, H, (int)(rows / 4), n_groups, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u);
+    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_mfma_kernel<W, false>, kCuLdsBytes));
+    launch_kernel(&dwconv7_mfma_kernel<W, false>, dim3((unsigned)((n_groups + G::kGroups - 1) / G::kGroups)), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
+        x, y, wt, bias, sink, B, H, (int)(rows / 4), n_groups, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u,
+        (const int*)nullptr, (const int*)nullptr, 0);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
+}
+
+// variable-length batch: the same segmentation over the virtual rows of the stage
+template <int W>
+static int launch_dw_mfma_var(const void* x, void* y, const void* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
+                              int target_waves, hipStream_t s) {
+    using G = DwmGeom<W>;
+    const long long Vt = (long long)vg.vrows[stage] - 3;
+    long long segs = target_waves / (G::kStrips * G::kSlices);
+    if (segs < 1) segs = 1;
+    long long rows = (Vt + segs - 1) / segs;
+    rows = (rows + 3) / 4 * 4;
+    if (rows < 8) rows = 8;
+    const long long n_seg = (Vt + rows - 1) / rows;
+    const int n_groups = (int)(n_seg * G::kSlices);
+    static DeviceOnce once;
+    ACX_TRY(set_max_dynamic_lds(once, &dwconv7_mfma_kernel<W, true>, kCuLdsBytes));
+    launch_kernel(&dwconv7_mfma_kernel<W, true>, dim3((unsigned)((n_groups + G::kGroups - 1) / G::kGroups)), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
+        x, y, wt, bias, sink, vg.B, 0, (int)(rows / 4), n_groups, 0u, vg.roff[stage], vg.vclip[stage], vg.vrows[stage]);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int launch_dwconv_mfma_varlen(const void* x, void* y, const void* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
+                              int target_waves, hipStream_t s) {
+    switch (stage) {
+        case 0: return launch_dw_mfma_var<56>(x, y, wt, bias, sink, vg, 0, target_waves, s);
+        case 1: return launch_dw_mfma_var<28>(x, y, wt, bias, sink, vg, 1, target_waves, s);
+        case 2: return launch_dw_mfma_var<14>(x, y, wt, bias, sink, vg, 2, target_waves, s);
+        default: ACX_FAIL(ACX_ERR_SHAPE, "dwconv7 (matrix form): no bf16 activations in stage %d", stage);
+    }
 }
 
 // The B operands of the 16-block 4x4x4 MFMA, one 8-byte load per lane and operand: [C/32][7][3][2][64 lanes][4] bf16.  Operand

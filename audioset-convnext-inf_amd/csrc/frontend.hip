@@ -33,6 +33,18 @@ struct FrontLds {
     cf buf[kFrontWaves][2][kFftBufSlots];      // buf[w][1] doubles as the power spectrum P (513 floats) once pass 3 has
 };                                             // read it: 49 KB per workgroup = 3 workgroups per CU
 
+// VAR: a variable-length batch -- frame f of clip b = the clip whose frame range [foff[b], foff[b+1]) holds f; its samples start
+// at soff[b] and number soff[b+1] - soff[b] (reflect padding at the clip's own ends).  L and T are unused then.
+__device__ __forceinline__ int var_frame_clip(const int* __restrict__ foff, int B, long long f) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (foff[mid] <= f) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <bool VAR>
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ wav, long long L, int T,
                                                      long long nframes, const float* __restrict__ hann,
                                                      const float* __restrict__ twiddle,
@@ -41,7 +53,8 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
                                                      const int* __restrict__ mel_off,
                                                      const float* __restrict__ mel_w, int mel_w_len,
                                                      const float* __restrict__ bn_scale,
-                                                     const float* __restrict__ bn_shift, float* __restrict__ out) {
+                                                     const float* __restrict__ bn_shift, float* __restrict__ out,
+                                                     const long long* __restrict__ soff, const int* __restrict__ foff, int B) {
     __shared__ FrontLds lds;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -105,13 +118,24 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
     for (long long it = 0; it < iters; ++it) {
         const long long f = it * per_iter + (long long)blockIdx.x * kFrontWaves + wave;
         const bool valid = f < nframes;
-        const long long b = valid ? f / T : 0;
-        const int t = valid ? (int)(f - b * T) : 0;
-        const float* x = wav + b * L;
+        long long b, Lc;
+        int t;
+        const float* x;
+        if (VAR) {
+            b = var_frame_clip(foff, B, valid ? f : 0);
+            t = valid ? (int)(f - foff[b]) : 0;
+            x = wav + soff[b];
+            Lc = soff[b + 1] - soff[b];
+        } else {
+            b = valid ? f / T : 0;
+            t = valid ? (int)(f - b * T) : 0;
+            x = wav + b * L;
+            Lc = L;
+        }
         const long long p0 = 320LL * t;
 
         cf v[8];
-        const bool interior = (p0 >= 512) && (p0 + 512 <= L);
+        const bool interior = (p0 >= 512) && (p0 + 512 <= Lc);
         if (interior) {
             const float* xs = x + (p0 - 512);
 #pragma unroll
@@ -124,8 +148,8 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 int n = 2 * (lane + 64 * r);
-                float a = x[reflect_index(p0 + n, L)];
-                float c = x[reflect_index(p0 + n + 1, L)];
+                float a = x[reflect_index(p0 + n, Lc)];
+                float c = x[reflect_index(p0 + n + 1, Lc)];
                 v[r] = cf_make(a * hw[r].x, c * hw[r].y);
             }
         }
@@ -195,12 +219,25 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
 //   frames [B T, 1024] (reflect-padded, NO window: it is inside the stored weights) . [conv_real; conv_imag]^T -> [B T, 2 x 513]
 // on the f32-input matrix cores (gemm.hip, the native fp32 GEMM: in every precision mode the frontend stays fp32), then
 // |.|^2, the banded mel filter, dB and bn0 exactly as in logmel_kernel.
-__global__ __launch_bounds__(256) void frames_kernel(const float* __restrict__ wav, long long L, int T, long long nframes,
-                                                     float* __restrict__ frames) {
+template <bool VAR>
+__global__ __launch_bounds__(256) void frames_kernel(const float* __restrict__ wav, long long L_, int T, long long nframes,
+                                                     float* __restrict__ frames, const long long* __restrict__ soff,
+                                                     const int* __restrict__ foff, int B) {
     for (long long f = blockIdx.x; f < nframes; f += gridDim.x) {
-        const long long b = f / T;
-        const int t = (int)(f - b * T);
-        const float* x = wav + b * L;
+        long long b, L;
+        int t;
+        const float* x;
+        if (VAR) {
+            b = var_frame_clip(foff, B, f);
+            t = (int)(f - foff[b]);
+            x = wav + soff[b];
+            L = soff[b + 1] - soff[b];
+        } else {
+            L = L_;
+            b = f / T;
+            t = (int)(f - b * T);
+            x = wav + b * L;
+        }
         const long long p0 = 320LL * t;
         float4 v;
         const int n = 4 * threadIdx.x;
@@ -238,8 +275,8 @@ __global__ __launch_bounds__(256) void spec_to_logmel_kernel(const float* __rest
 }
 
 static int launch_logmel_dense(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* out, bool bn, hipStream_t s,
-                               float* frames, float* spec) {
-    const long long nframes = (long long)B * T;
+                               float* frames, float* spec, const VarGeom* vg = nullptr) {
+    const long long nframes = vg ? (long long)vg->frames : (long long)B * T;
     // per-kernel entry point (acx_logmel_bn0; the forward passes its own workspace): frames + spectrum of THIS call, allocated and
     // released in stream order on `s` -- calls on different streams or threads never share scratch (one grown-on-demand
     // buffer per context was shared by every call in flight)
@@ -259,7 +296,9 @@ static int launch_logmel_dense(acx_ctx* c, const float* wav, int B, int64_t L, i
     } scratch_free{call_scratch, s};
     ProfScope ps(c, ACX_K_FRONTEND, s);
     long long blocks = nframes < 4096 ? nframes : 4096;
-    launch_kernel(&frames_kernel, dim3((unsigned)blocks), dim3(256), 0, s, wav, L, T, nframes, frames);
+    if (vg) launch_kernel(&frames_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)0, 0, nframes, frames, vg->soff, vg->foff, vg->B);
+    else launch_kernel(&frames_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)L, T, nframes, frames,
+                       (const long long*)nullptr, (const int*)nullptr, 0);
     ACX_HIP(hipGetLastError());
     GemmArgs g{};
     g.A = frames; g.Wt = c->d_stft_w; g.bias = c->d_stft_zero; g.out = spec; g.M = nframes; g.N = kDenseN; g.K = kNFFT;
@@ -282,10 +321,26 @@ int launch_logmel(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* 
     // is paid once per ~10 frames of a wave (with 4 096 workgroups it was once per 4: 184 -> 167 us at B = 64)
     if (blocks > 1536) blocks = 1536;
     ProfScope ps(c, ACX_K_FRONTEND, s);
-    launch_kernel(&logmel_kernel, dim3((unsigned)blocks), dim3(256), 0, s, wav, L, T, nframes, c->d_hann, c->d_twiddle,
+    launch_kernel(&logmel_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)L, T, nframes, c->d_hann, c->d_twiddle,
                                                                 c->d_mel_start, c->d_mel_len, c->d_mel_off,
                                                                 c->d_mel_w, c->mel_w_len, bn ? c->d_bn_scale : c->d_bn_one,
-                                                                bn ? c->d_bn_shift : c->d_bn_zero, out);
+                                                                bn ? c->d_bn_shift : c->d_bn_zero, out, (const long long*)nullptr,
+                                                                (const int*)nullptr, 0);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int launch_logmel_varlen(acx_ctx* c, const float* wav, const VarGeom& vg, float* out, hipStream_t s, float* dense_frames,
+                         float* dense_spec) {
+    if (!dense_frames || !dense_spec) ACX_FAIL(ACX_ERR_ARG, "logmel (variable length): the forward's scratch is required");
+    if (c->dense_stft) return launch_logmel_dense(c, wav, vg.B, 0, 0, out, true, s, dense_frames, dense_spec, &vg);
+    const long long nframes = vg.frames;
+    long long blocks = (nframes + kFrontWaves - 1) / kFrontWaves;
+    if (blocks > 1536) blocks = 1536;
+    ProfScope ps(c, ACX_K_FRONTEND, s);
+    launch_kernel(&logmel_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)0, 0, nframes, c->d_hann, c->d_twiddle,
+                  c->d_mel_start, c->d_mel_len, c->d_mel_off, c->d_mel_w, c->mel_w_len, c->d_bn_scale, c->d_bn_shift, out,
+                  vg.soff, vg.foff, vg.B);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

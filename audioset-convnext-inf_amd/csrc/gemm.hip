@@ -54,6 +54,7 @@ struct GemmParams {
     long long M; int N; int K;
     int H, W, C, Ho, Wo;      // gather mode (A is NHWC (B,H,W,C); row m = (b,ho,wo); k = (dy*2+dx)*C + c)
     int tiles_n;
+    const int* irow;          // GATHER 2 (variable-length batch): input row of output row m / Wo (VarGeom::irow)
 };
 
 __device__ __forceinline__ void lds_dma16(const float* gsrc, char* lds_wave_base) {
@@ -61,7 +62,7 @@ __device__ __forceinline__ void lds_dma16(const float* gsrc, char* lds_wave_base
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// GATHER: 0 plain rows, 1 2x2 patch gather (downsample)
+// GATHER: 0 plain rows, 1 2x2 patch gather (downsample), 2 the same with the input row from p.irow (variable-length batch)
 template <int kBM, int BN, int WM, int WN, int EPI, int GATHER>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     constexpr int TM = kBM / (WM * 32);
@@ -101,7 +102,11 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
         const int chunk = pchunk ^ ((row >> 1) & 7);
         long long m = m0 + row;
         if (m >= p.M) m = p.M - 1;
-        if (GATHER) {
+        if (GATHER == 2) {
+            const int wo = (int)(m % p.Wo);
+            const long long t = m / p.Wo;
+            a_src[i] = p.A + ((long long)p.irow[t] * p.W + 2 * wo) * p.C + 4 * chunk;
+        } else if (GATHER) {
             const int wo = (int)(m % p.Wo);
             const long long t = m / p.Wo;
             const int ho = (int)(t % p.Ho);
@@ -357,10 +362,11 @@ int launch_gemm(acx_ctx* c, const GemmArgs& a, hipStream_t s) {
     GemmParams p;
     p.A = a.A; p.Wt = a.Wt; p.bias = a.bias; p.out = a.out; p.stats = a.stats; p.colsum = a.colsum; p.resid = a.resid;
     p.M = a.M; p.N = a.N; p.K = a.K; p.H = a.H; p.W = a.W; p.C = a.C; p.Ho = a.Ho; p.Wo = a.Wo;
-    p.tiles_n = 0;
+    p.tiles_n = 0; p.irow = a.irow;
     ProfScope ps(c, a.cls, s);
     if (a.gather) {
         if (a.epi != EPI_BIAS || a.C % kBK != 0) ACX_FAIL(ACX_ERR_ARG, "gemm: bad gather configuration");
+        if (a.irow) return launch_bn<EPI_BIAS, 2>(p, s);
         return launch_bn<EPI_BIAS, 1>(p, s);
     }
     if (a.epi == EPI_GELU) {

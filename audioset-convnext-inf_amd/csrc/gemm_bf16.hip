@@ -30,6 +30,7 @@ struct GemmBfParams {
     long long M; int N; int Kp; int lda;      // Kp: padded K (multiple of 64) = row stride of Wt; lda: row stride of A
     int H, W, Cp, Ho, Wo;                     // gather mode: A is (B,H,W,Cp) bf16, row m = (b,ho,wo), k = (dy*2+dx)*Cp + c
     int tiles_n;
+    const int* irow;                          // GATHER 2 (variable-length batch): input row of output row m / Wo (VarGeom::irow)
 };
 
 // One 1-KB piece (8 rows x 128 B): scalar base of the tile's first row + a 32-bit offset per lane (its row's distance from that
@@ -75,6 +76,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmBfParams p)
     const int prow = lane >> 3, pchunk = lane & 7;
     // element index of the first k of row m of A (rows of a tile ascend in memory in both modes: offsets from row m0 are >= 0)
     auto a_row = [&](long long m) -> long long {
+        if (GATHER == 2) {               // (irow ascends with m: the rows of a tile still ascend in memory)
+            const int wo = (int)(m % p.Wo);
+            const long long t = m / p.Wo;
+            return ((long long)p.irow[t] * p.W + 2 * wo) * p.Cp;
+        }
         if (GATHER) {
             const int wo = (int)(m % p.Wo);
             const long long t = m / p.Wo;
@@ -341,11 +347,12 @@ int launch_gemm_bf16(acx_ctx* c, const GemmBf16Args& a, hipStream_t s) {
     GemmBfParams p;
     p.A = reinterpret_cast<const __bf16*>(a.A); p.Wt = reinterpret_cast<const __bf16*>(a.Wt); p.bias = a.bias;
     p.out = a.out; p.resid = a.resid; p.M = a.M; p.N = a.N; p.Kp = a.Kp; p.lda = a.lda;
-    p.H = a.H; p.W = a.W; p.Cp = a.Cp; p.Ho = a.Ho; p.Wo = a.Wo; p.tiles_n = 0;
+    p.H = a.H; p.W = a.W; p.Cp = a.Cp; p.Ho = a.Ho; p.Wo = a.Wo; p.tiles_n = 0; p.irow = a.irow;
     ProfScope ps(c, a.cls, s);
     const int ways = inflight_ways();
     if (a.gather) {
         if (a.epi != EPI_BIAS || a.Cp % kBfBK != 0) ACX_FAIL(ACX_ERR_ARG, "gemm_bf16: bad gather configuration");
+        if (a.irow) return a.out_bf16 ? launch_bf_bn<3, 2>(p, ways, s) : launch_bf_bn<0, 2>(p, ways, s);
         return a.out_bf16 ? launch_bf_bn<3, 1>(p, ways, s) : launch_bf_bn<0, 1>(p, ways, s);
     }
     if (a.out_bf16) ACX_FAIL(ACX_ERR_ARG, "gemm_bf16: bf16 output exists for the gather (downsample) form only");

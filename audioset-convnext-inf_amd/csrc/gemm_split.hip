@@ -43,6 +43,7 @@ struct GemmSParams {
     float hscale;              // EPI 1: scale of the S16 result (power of two)
     int H, W, C, Ho, Wo;       // gather mode: A is (B,H,W,C) S16 rows; row m = (b,ho,wo), k = (dy*2+dx)*C + c
     int tiles_n;
+    const int* irow;           // GATHER 2 (variable-length batch): input row of output row m / Wo (VarGeom::irow)
 };
 
 __device__ __forceinline__ void lds_dma16_s(const char* gsrc, char* lds_wave_base) {
@@ -100,7 +101,11 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(GemmSParams p) {
         const int chunk = pchunk ^ acx_swz8(row);
         long long m = m0 + row;
         if (m >= p.M) m = p.M - 1;
-        if (GATHER) {
+        if (GATHER == 2) {
+            const int wo = (int)(m % p.Wo);
+            const long long t = m / p.Wo;
+            a_src[i] = p.A + ((((long long)p.irow[t]) * p.W + 2 * wo) * p.C) * 4 + 16 * chunk;
+        } else if (GATHER) {
             const int wo = (int)(m % p.Wo);
             const long long t = m / p.Wo;
             const int ho = (int)(t % p.Ho);
@@ -380,11 +385,12 @@ int launch_gemm_split(acx_ctx* c, const GemmSplitArgs& a, hipStream_t s) {
     GemmSParams p;
     p.A = reinterpret_cast<const char*>(a.A); p.Wt = reinterpret_cast<const char*>(a.Wt); p.bias = a.bias;
     p.out = a.out; p.resid = a.resid; p.M = a.M; p.N = a.N; p.K = a.K; p.sinv = a.sinv; p.hscale = a.hscale;
-    p.H = a.H; p.W = a.W; p.C = a.C; p.Ho = a.Ho; p.Wo = a.Wo; p.tiles_n = 0;
+    p.H = a.H; p.W = a.W; p.C = a.C; p.Ho = a.Ho; p.Wo = a.Wo; p.tiles_n = 0; p.irow = a.irow;
     ProfScope ps(c, a.cls, s);
     const int ways = inflight_ways();
     if (a.gather) {
         if (a.epi != EPI_BIAS || a.C % kSBK != 0) ACX_FAIL(ACX_ERR_ARG, "gemm_split: bad gather configuration");
+        if (a.irow) return launch_s16_any<0, 2>(p, ways, s);
         return launch_s16_any<0, 1>(p, ways, s);
     }
     if (a.epi == EPI_GELU) return launch_s16_any<1, 0>(p, ways, s);

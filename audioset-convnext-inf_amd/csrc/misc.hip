@@ -16,11 +16,13 @@ __device__ __forceinline__ float wave_sum(float v) {
 // Thread = (float4 of channels, one of 4 time phases): every thread streams ~H3/4 rows x 7 columns of
 // independent 16-B loads (the first version walked all H3 rows serially per thread: latency-bound, 143 us),
 // partial (max, sum) meet in LDS.
-__global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict__ x, int H3,
+// VAR: a variable-length batch -- clip b has H3 = roff3[b + 1] - roff3[b] rows from row roff3[b] on (same reduction order)
+template <bool VAR>
+__global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict__ x, int H3_,
                                                         const float* __restrict__ nw, const float* __restrict__ nb,
                                                         const float* __restrict__ hw, const float* __restrict__ hb,
                                                         float* __restrict__ scene, float* __restrict__ logits,
-                                                        float* __restrict__ probs) {
+                                                        float* __restrict__ probs, const int* __restrict__ roff3) {
     __shared__ __attribute__((aligned(16))) float pmax[4][768];
     __shared__ __attribute__((aligned(16))) float psum[4][768];
     __shared__ __attribute__((aligned(16))) float emb[768];
@@ -28,7 +30,9 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
     const int tid = threadIdx.x;
     const int cg = tid % 192, ph = tid / 192;
     const long long b = blockIdx.x;
-    const float* xb = x + b * (long long)H3 * 7 * 768 + 4 * cg;
+    const int H3 = VAR ? roff3[b + 1] - roff3[b] : H3_;
+    const long long row0 = VAR ? (long long)roff3[b] : b * (long long)H3;
+    const float* xb = x + row0 * 7 * 768 + 4 * cg;
     float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY), sm = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int h = ph; h < H3; h += 4) {
         const float* r = xb + (long long)h * 7 * 768;
@@ -106,21 +110,36 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
 int launch_pool_head(acx_ctx* c, const float* x, int B, int H3, float* scene, float* logits, float* probs,
                      hipStream_t s) {
     ProfScope ps(c, ACX_K_POOLHEAD, s);
-    launch_kernel(&pool_head_kernel, dim3(B), dim3(768), 0, s, x, H3, c->d_norm_w, c->d_norm_b, c->d_head_w, c->d_head_b,
-                                                   scene, logits, probs);
+    launch_kernel(&pool_head_kernel<false>, dim3(B), dim3(768), 0, s, x, H3, c->d_norm_w, c->d_norm_b, c->d_head_w, c->d_head_b,
+                                                   scene, logits, probs, (const int*)nullptr);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int launch_pool_head_varlen(acx_ctx* c, const float* x, const VarGeom& vg, float* scene, float* logits, float* probs,
+                            hipStream_t s) {
+    ProfScope ps(c, ACX_K_POOLHEAD, s);
+    launch_kernel(&pool_head_kernel<true>, dim3(vg.B), dim3(768), 0, s, x, 0, c->d_norm_w, c->d_norm_b, c->d_head_w, c->d_head_b,
+                  scene, logits, probs, vg.roff[3]);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
 
 // out[b][c][p] = x[b][p][c], p = h*W + w.  32x32 tiles through LDS (+1 pad), coalesced both ways.
+// VAR: a variable-length batch -- clip b is the block of P = (roff3[b + 1] - roff3[b]) x W pixels from pixel roff3[b] W on,
+// in the input and in the output alike (the grid covers the tallest clip)
+template <bool VAR>
 __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restrict__ x, float* __restrict__ out,
-                                                           int P, int C) {
+                                                           int P_, int C, const int* __restrict__ roff3, int W) {
     __shared__ float t[32][33];
     const long long b = blockIdx.z;
+    const int P = VAR ? (roff3[b + 1] - roff3[b]) * W : P_;
+    const long long base = VAR ? (long long)roff3[b] * W * C : b * (long long)P * C;
     const int p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    if (VAR && p0 >= P) return;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
-    const float* xb = x + b * (long long)P * C;
-    float* ob = out + b * (long long)P * C;
+    const float* xb = x + base;
+    float* ob = out + base;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int p = p0 + ty + 8 * i;
@@ -139,7 +158,16 @@ int launch_nhwc_to_nchw(acx_ctx* c, const float* x, float* out, int B, int H, in
     if (C % 32 != 0) ACX_FAIL(ACX_ERR_SHAPE, "nhwc_to_nchw: C=%d is not a multiple of 32", C);
     const int P = H * W;
     ProfScope ps(c, ACX_K_TRANSPOSE, s);
-    launch_kernel(&nhwc_to_nchw_kernel, dim3((P + 31) / 32, C / 32, B), dim3(256), 0, s, x, out, P, C);
+    launch_kernel(&nhwc_to_nchw_kernel<false>, dim3((P + 31) / 32, C / 32, B), dim3(256), 0, s, x, out, P, C, (const int*)nullptr, W);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int launch_nhwc_to_nchw_varlen(acx_ctx* c, const float* x, float* out, const VarGeom& vg, hipStream_t s) {
+    const int W = kStemW >> 3, C = kDims[3];
+    const int Pmax = vg.maxH[3] * W;
+    ProfScope ps(c, ACX_K_TRANSPOSE, s);
+    launch_kernel(&nhwc_to_nchw_kernel<true>, dim3((Pmax + 31) / 32, C / 32, vg.B), dim3(256), 0, s, x, out, 0, C, vg.roff[3], W);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

@@ -54,11 +54,15 @@ struct __attribute__((packed, aligned(4))) StemF3 { float a, b, c; };
 struct __attribute__((packed, aligned(4))) StemU3 { unsigned a, b, c; };
 
 // OBF: the output tensor is bf16 (ACX_PREC_BF16_ACT)
-template <bool OBF>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void stem_kernel(const float* __restrict__ in, int T, int H0, long long nrows,
+// VAR: a variable-length batch -- row r belongs to clip rclip0[r], whose rows start at roff0[] and frames at foff[] (the time
+// padding of 4 frames is at the clip's own ends); T and H0 are unused then
+template <bool OBF, bool VAR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void stem_kernel(const float* __restrict__ in, int T_, int H0, long long nrows,
                                                    const float* __restrict__ w /*[96][16]*/,
                                                    const float* __restrict__ bias, const float* __restrict__ lnw,
-                                                   const float* __restrict__ lnb, void* __restrict__ out_) {
+                                                   const float* __restrict__ lnb, void* __restrict__ out_,
+                                                   const int* __restrict__ rclip0, const int* __restrict__ roff0,
+                                                   const int* __restrict__ foff) {
     // [buffer][row of the pair][ky][pixel pair][A.x B.x A.y B.y A.z B.z A.w B.w]: double-buffered, one barrier per row pair
     __shared__ __attribute__((aligned(16))) float patch[2][2][4][kStemPairs][8];
     const int tid = threadIdx.x;
@@ -82,13 +86,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     auto fetch = [&](long long row64) -> float4 {
         unsigned row = (unsigned)row64;
         if (row >= (unsigned)nrows) row = (unsigned)nrows - 1;
-        const unsigned bq = row / (unsigned)H0;
-        const int h = (int)(row - bq * (unsigned)H0);
-        const long long b = bq;
+        int h, T;
+        long long f0;                                   // first frame of the row's clip
+        if (VAR) {
+            const int cb = rclip0[row];
+            h = (int)row - roff0[cb];
+            f0 = foff[cb];
+            T = foff[cb + 1] - foff[cb];
+        } else {
+            const unsigned bq = row / (unsigned)H0;
+            h = (int)(row - bq * (unsigned)H0);
+            T = T_;
+            f0 = (long long)bq * T;
+        }
         int t = 4 * h - 4 + sky;
         const bool rok = stager && t >= 0 && t < T;
         t = t < 0 ? 0 : (t >= T ? T - 1 : t);           // clamped address, zeroed below (no branchy loads)
-        float4 v = *reinterpret_cast<const float4*>(in + (b * T + t) * kMels + 4 * (stager ? sw : 0));
+        float4 v = *reinterpret_cast<const float4*>(in + (f0 + t) * kMels + 4 * (stager ? sw : 0));
         if (!rok) v = make_float4(0.f, 0.f, 0.f, 0.f);
         return v;
     };
@@ -179,12 +193,28 @@ int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hi
     const long long npairs = (nrows + 1) / 2;
     long long blocks = npairs < 2048 ? npairs : 2048;   // 8 resident workgroups per CU, every workgroup walks ~4 row pairs at B = 64
     ProfScope ps(c, ACX_K_STEM, s);
+    const int* nil = nullptr;
     if (act_bf16)
-        launch_kernel(&stem_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, in, T, H0, nrows, c->d_stem_w, c->d_stem_b,
-                                                                        c->d_stem_lnw, c->d_stem_lnb, out);
+        launch_kernel(&stem_kernel<true, false>, dim3((unsigned)blocks), dim3(256), 0, s, in, T, H0, nrows, c->d_stem_w, c->d_stem_b,
+                                                                        c->d_stem_lnw, c->d_stem_lnb, out, nil, nil, nil);
     else
-        launch_kernel(&stem_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, in, T, H0, nrows, c->d_stem_w, c->d_stem_b,
-                                                                         c->d_stem_lnw, c->d_stem_lnb, out);
+        launch_kernel(&stem_kernel<false, false>, dim3((unsigned)blocks), dim3(256), 0, s, in, T, H0, nrows, c->d_stem_w, c->d_stem_b,
+                                                                         c->d_stem_lnw, c->d_stem_lnb, out, nil, nil, nil);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int launch_stem_varlen(acx_ctx* c, const float* in, const VarGeom& vg, void* out, hipStream_t s, bool act_bf16) {
+    const long long nrows = vg.rows[0];
+    const long long npairs = (nrows + 1) / 2;
+    long long blocks = npairs < 2048 ? npairs : 2048;
+    ProfScope ps(c, ACX_K_STEM, s);
+    if (act_bf16)
+        launch_kernel(&stem_kernel<true, true>, dim3((unsigned)blocks), dim3(256), 0, s, in, 0, 0, nrows, c->d_stem_w, c->d_stem_b,
+                      c->d_stem_lnw, c->d_stem_lnb, out, vg.rclip0, vg.roff[0], vg.foff);
+    else
+        launch_kernel(&stem_kernel<false, true>, dim3((unsigned)blocks), dim3(256), 0, s, in, 0, 0, nrows, c->d_stem_w, c->d_stem_b,
+                      c->d_stem_lnw, c->d_stem_lnb, out, vg.rclip0, vg.roff[0], vg.foff);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

@@ -11,6 +11,7 @@ pointers to libacx (HIP kernels, include/acx.h) on the current torch stream.
 Inference only, GPU only: there is no CPU fallback and no training branch (the reference's
 augmentations / mixup / DropPath only run under `self.training`, convnext.py:288-313).
 """
+import ctypes
 import os
 
 import torch
@@ -322,6 +323,97 @@ class ConvNeXt(nn.Module):
                                               _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(x.device)))
         return out0, out1
 
+    def _check_run(self, device):
+        if self.training:
+            raise RuntimeError("inference-only path: call model.eval() first (the reference's training branches -- "
+                               "augmentations, SpecAugment, mixup -- are not part of this build)")
+        wdev = self.head_audioset.weight.device
+        if wdev.type != "cuda" or device.type != "cuda":
+            raise RuntimeError("the MI355X path runs on the GPU only (model on %s, input on %s): "
+                               "move both with .to('cuda'); there is no CPU fallback" % (wdev, device))
+        if device != wdev:
+            raise RuntimeError("input on %s but model on %s" % (device, wdev))
+
+    def _run_varlen(self, wav, lengths, mode):
+        """wav: packed 1-D fp32 CUDA tensor, lengths: list of <= 256 ints summing to wav.numel()."""
+        B = len(lengths)
+        with torch.cuda.device(wav.device):
+            ctx = self.native_context(wav.device)
+            ws = self._workspace(wav.device, ctx.workspace_bytes_varlen(lengths, mode))
+            if mode == _ffi.MODE_LOGITS:
+                out0 = torch.empty((B, 527), dtype=torch.float32, device=wav.device)
+                out1 = torch.empty((B, 527), dtype=torch.float32, device=wav.device)
+            elif mode == _ffi.MODE_SCENE:
+                out0, out1 = torch.empty((B, 768), dtype=torch.float32, device=wav.device), None
+            else:
+                out0, out1 = torch.empty(varlen_frame_layout(lengths)[-1], dtype=torch.float32, device=wav.device), None
+            lens = (ctypes.c_int64 * B)(*lengths)
+            _ffi.check(_ffi.lib().acx_forward_varlen(ctx.handle, _ffi.ptr(wav), lens, B, mode, _ffi.ptr(out0), _ffi.ptr(out1),
+                                                     _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(wav.device)))
+        return out0, out1
+
+    def forward_varlen(self, clips, lengths=None, what="logits"):
+        """Clips of different lengths in one packed forward (acx_forward_varlen); every clip's result is bit-identical to the
+        uniform forward of that clip alone.  clips: a list of 1-D CUDA tensors, or one packed 1-D CUDA tensor plus `lengths`.
+        what: "logits" -> {"clipwise_output", "clipwise_logits"} each (B, 527); "scene" -> (B, 768); "frame" -> a list of
+        (768, T'_i, 7) views into one output buffer.  More than 256 clips run as several calls."""
+        if what not in ("logits", "scene", "frame"):
+            raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
+        if isinstance(clips, torch.Tensor):
+            if lengths is None:
+                raise ValueError("a packed tensor needs `lengths`")
+            if clips.dim() != 1:
+                raise ValueError("expected a packed 1-D waveform tensor, got shape %r" % (tuple(clips.shape),))
+            lengths = [int(n) for n in lengths]
+            if sum(lengths) != clips.numel():
+                raise ValueError("lengths sum to %d samples but the packed tensor holds %d" % (sum(lengths), clips.numel()))
+            wav = clips
+        else:
+            clips = list(clips)
+            if lengths is not None:
+                raise ValueError("`lengths` goes with a packed tensor, not with a list of clips")
+            for c in clips:
+                if not isinstance(c, torch.Tensor) or c.dim() != 1:
+                    raise ValueError("expected 1-D waveform tensors, got %r" % (getattr(c, "shape", type(c)),))
+            lengths = [int(c.numel()) for c in clips]
+            if not clips:
+                raise ValueError("forward_varlen needs at least one clip")
+            devs = {c.device for c in clips}
+            if len(devs) != 1:
+                raise RuntimeError("clips on several devices: %s" % sorted(str(d) for d in devs))
+            self._check_run(clips[0].device)
+            wav = torch.cat([c.detach().to(torch.float32) for c in clips])
+        if not lengths:
+            raise ValueError("forward_varlen needs at least one clip")
+        self._check_run(wav.device)
+        for i, n in enumerate(lengths):
+            if n < _ffi.MIN_SAMPLES:
+                raise RuntimeError("clip %d of %d samples is too short: kernel size can't be greater than actual input size "
+                                   "(minimum is %d samples)" % (i, n, _ffi.MIN_SAMPLES))
+        wav = wav.detach().to(torch.float32).contiguous()
+        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
+        cap = _ffi.MAX_VARLEN_CLIPS
+        parts, s0 = [], 0
+        for c0 in range(0, len(lengths), cap):
+            chunk = lengths[c0:c0 + cap]
+            n = sum(chunk)
+            parts.append(self._run_varlen(wav[s0:s0 + n], chunk, mode))
+            s0 += n
+        if what == "frame":
+            views = []
+            for (buf, _), c0 in zip(parts, range(0, len(lengths), cap)):
+                chunk = lengths[c0:c0 + cap]
+                offs = varlen_frame_layout(chunk)
+                for i, L in enumerate(chunk):
+                    h3 = (offs[i + 1] - offs[i]) // (768 * 7)
+                    views.append(buf[offs[i]:offs[i + 1]].view(768, h3, 7))
+            return views
+        out0 = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
+        if what == "scene":
+            return out0
+        out1 = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
+        return {"clipwise_output": out1, "clipwise_logits": out0}
+
     # ----------------------------------------------------------------------------- public surface
     def forward(self, x, mixup_lambda=None):
         """(B, L) waveform -> {"clipwise_output": probs, "clipwise_logits": logits} (convnext.py:287-331)."""
@@ -374,6 +466,16 @@ class ConvNeXt(nn.Module):
                               use_speed_perturb=False)
         load_checkpoint(model, path_, map_location or "cpu")
         return model
+
+
+def varlen_frame_layout(lengths):
+    """Element offsets of the clips' (768, T'_i, 7) blocks in the frame output of acx_forward_varlen: B + 1 ascending values,
+    the last one the buffer's size.  T' follows acx_stage_hw: T = L // 320 + 1, H0 = (T + 4) // 4 + 1, T' = H0 // 8."""
+    offs = [0]
+    for L in lengths:
+        h0 = (int(L) // 320 + 1 + 4) // 4 + 1
+        offs.append(offs[-1] + 768 * (h0 // 2 // 2 // 2) * 7)
+    return offs
 
 
 def load_checkpoint(model, path, map_location="cpu"):

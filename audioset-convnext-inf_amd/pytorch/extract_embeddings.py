@@ -14,8 +14,71 @@ def bucket_by_length(lengths):
     return buckets
 
 
+def pack_groups(lengths, max_batch=64, max_samples=64 * 320000):
+    """Indices grouped for packed (variable-length) forwards: sorted by length, at most `max_batch` clips and -- unless one clip
+    alone is longer -- at most `max_samples` samples per group."""
+    order = sorted(range(len(lengths)), key=lambda i: -int(lengths[i]))
+    groups, cur, tot = [], [], 0
+    for i in order:
+        n = int(lengths[i])
+        if cur and (len(cur) >= max_batch or tot + n > max_samples):
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(i)
+        tot += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
 @torch.no_grad()
-def extract(model, waveforms, what="logits", max_batch=64):
+def _extract_packed(model, waveforms, what, max_batch, max_samples):
+    import numpy as np
+    device = next(model.parameters()).device
+    n = len(waveforms)
+    out = [None] * n
+    groups = pack_groups([len(w) for w in waveforms], max_batch, max_samples)
+    sizes = [sum(len(waveforms[i]) for i in g) for g in groups]
+    pin = torch.empty(max(sizes), dtype=torch.float32).pin_memory()
+    pin_np = pin.numpy()
+    staged = torch.cuda.Event()
+    staged.record()
+    rows = None
+    for g, size in zip(groups, sizes):
+        staged.synchronize()                                       # the previous group has left the pinned buffer
+        lengths, off = [], 0
+        for i in g:
+            w = waveforms[i]
+            w = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
+            np.copyto(pin_np[off:off + len(w)], w, casting="same_kind")
+            lengths.append(len(w))
+            off += len(w)
+        packed = pin[:size].to(device, non_blocking=True)
+        staged.record()
+        res = model.forward_varlen(packed, lengths, what=what)
+        if what == "frame":                                        # one device -> host copy per output buffer, not per clip
+            hosts = {}
+            for j, i in enumerate(g):
+                v = res[j]
+                base = v._base if v._base is not None else v
+                if id(base) not in hosts:
+                    hosts[id(base)] = (base, base.cpu())
+                o = v.storage_offset() - base.storage_offset()
+                out[i] = hosts[id(base)][1].reshape(-1)[o:o + v.numel()].view(v.shape).clone()
+            continue
+        res = res["clipwise_logits"] if what == "logits" else res
+        if rows is None:
+            rows = torch.empty(n, res.shape[1], dtype=res.dtype, device=device)
+        rows[torch.as_tensor(g, device=device)] = res
+    if rows is not None:
+        rows = rows.cpu()
+        for i in range(n):
+            out[i] = rows[i].clone()
+    return out
+
+
+@torch.no_grad()
+def extract(model, waveforms, what="logits", max_batch=64, pack=False, max_samples=64 * 320000):
     """waveforms: list of 1-D float tensors/arrays of arbitrary lengths (>= 7360 samples).
     what: 'logits' -> (527,), 'scene' -> (768,), 'frame' -> (768, T', 7) per clip.  Returns a list (CPU tensors, input order).
 
@@ -23,7 +86,14 @@ def extract(model, waveforms, what="logits", max_batch=64):
     a pageable copy and a synchronising .cpu() per clip cost ten times that): chunks run largest first, so the model's workspace
     and the pinned staging buffer are sized once instead of growing with every longer clip; a chunk's clips are copied into the
     pinned buffer with plain memcpys and cross PCIe asynchronously; logits / scene rows collect in one device tensor that is
-    fetched once at the end (frame embeddings, whose shapes differ, are fetched per chunk)."""
+    fetched once at the end (frame embeddings, whose shapes differ, are fetched per chunk).
+
+    pack=True: clips of any lengths share a launch (model.forward_varlen): sorted by length, at most `max_batch` clips and
+    `max_samples` samples per call.  Same results, bit for bit."""
+    if pack:
+        if what not in ("logits", "scene", "frame"):
+            raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
+        return _extract_packed(model, waveforms, what, max_batch, max_samples) if len(waveforms) else []
     import numpy as np
     device = next(model.parameters()).device
     fn = {"logits": lambda x: model(x)["clipwise_logits"], "scene": model.forward_scene_embeddings,

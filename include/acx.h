@@ -85,6 +85,7 @@ enum acx_kernel_class {
 #define ACX_MIN_SAMPLES 7360  /* shortest clip the reference accepts (last 2x2 downsample needs H>=2) */
 #define ACX_NUM_CLASSES 527   /* convnext.py:654 */
 #define ACX_EMBED_DIM 768     /* convnext.py:656 */
+#define ACX_MAX_VARLEN_CLIPS 256  /* clips per acx_forward_varlen call */
 
 ACX_API const char* acx_last_error(void);
 ACX_API int acx_version(void);
@@ -139,6 +140,18 @@ ACX_API int acx_sub_batches(const acx_ctx* ctx, int B, int* out);
  *   ACX_MODE_FRAME : out0 = NCHW (B,768,H3,7), out1 ignored */
 ACX_API int acx_forward(acx_ctx* ctx, const float* wav, int B, int64_t L, int mode, float* out0,
                 float* out1, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Variable-length batches: B clips of different lengths in one forward (reference extract_embeddings.py:64-99 feeds clips
+ * un-padded, one at a time).  wav: the B clips back to back (sum(lengths) fp32 samples, device memory); lengths: HOST array of
+ * the B clip lengths, each >= ACX_MIN_SAMPLES; 1 <= B <= ACX_MAX_VARLEN_CLIPS.
+ *   ACX_MODE_LOGITS / ACX_MODE_SCENE: out0 / out1 as acx_forward, one row per clip
+ *   ACX_MODE_FRAME : out0 = the clips' NCHW blocks (768, H3_i, 7) back to back in clip order
+ * Every clip's result is bit-identical to acx_forward of that clip alone.  Same launch contract as acx_forward (all work on
+ * `stream`, no allocation, no synchronisation, capturable): the per-clip geometry tables are written into the head of the
+ * workspace by the first kernel of the call, from the lengths passed by value.  Runs on the caller's stream (no batch split). */
+ACX_API int acx_workspace_bytes_varlen(const acx_ctx* ctx, const int64_t* lengths, int B, int mode, size_t* out_bytes);
+ACX_API int acx_forward_varlen(acx_ctx* ctx, const float* wav, const int64_t* lengths, int B, int mode, float* out0,
+                               float* out1, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- multi-GPU: the one collective of the path -----------------------------------------------------------------
  * One process per GPU, full weight replica, clips sharded; logits / probabilities / scene rows are all-gathered over xGMI by
