@@ -51,6 +51,12 @@ SIGNATURES = {
     "acx_allgather": (_c_int, [_vp, _vp, _vp, _c_sz, _vp]),
     "acx_comm_info": (_c_int, [_vp, _pint, _pint]),
     "acx_pcm16_to_f32": (_c_int, [_vp, _vp, _c_i64, _vp]),
+    "acx_resample_geometry": (_c_int, [_c_int, _c_int, _pint, _pint, _pint, _pint]),
+    "acx_resample_taps": (_c_int, [_c_int, _c_int, _pint, _pint, ctypes.POINTER(ctypes.c_float), _c_sz]),
+    "acx_resampled_length": (_c_int, [_c_int, _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
+    "acx_resampler_create": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_vp)]),
+    "acx_resampler_destroy": (None, [_vp]),
+    "acx_resample": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _vp, _vp]),
     "acx_frontend_info": (_c_int, [_vp, _pint, ctypes.POINTER(ctypes.c_float), _pint]),
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
@@ -205,6 +211,54 @@ class Context:
         n = (ctypes.c_int64 * len(KERNEL_CLASSES))()
         check(lib().acx_profile_read(self._h, ms, n))
         return {k: (ms[i], n[i]) for i, k in enumerate(KERNEL_CLASSES)}
+
+
+class Resampler:
+    """Owns one acx_resampler: the band tables of orig_hz -> new_hz on one GPU (include/acx.h, acx_resample)."""
+
+    def __init__(self, device_index, orig_hz, new_hz):
+        self._h = _vp()
+        check(lib().acx_resampler_create(int(device_index), int(orig_hz), int(new_hz), ctypes.byref(self._h)))
+        self.device_index, self.orig_hz, self.new_hz = int(device_index), int(orig_hz), int(new_hz)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().acx_resampler_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def run(self, wav, lengths, out):
+        """wav: packed fp32 device tensor of the clips, lengths: <= MAX_VARLEN_CLIPS ints, out: packed output tensor."""
+        lens = (_c_i64 * len(lengths))(*[int(n) for n in lengths])
+        check(lib().acx_resample(self._h, ptr(wav), lens, len(lengths), ptr(out), stream_ptr(wav.device)))
+
+
+def resample_geometry(orig_hz, new_hz):
+    """(of, nf, width, max_band) of orig_hz -> new_hz (acx_resample_geometry; host only)."""
+    v = [_c_int() for _ in range(4)]
+    check(lib().acx_resample_geometry(int(orig_hz), int(new_hz), *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def resample_taps(orig_hz, new_hz):
+    """(band_start[nf], band_count[nf], taps) as lists: the stored taps of each phase, phase after phase (acx_resample_taps)."""
+    _, nf, _, mb = resample_geometry(orig_hz, new_hz)
+    start, count = (_c_int * nf)(), (_c_int * nf)()
+    taps = (ctypes.c_float * max(1, nf * mb))()
+    check(lib().acx_resample_taps(int(orig_hz), int(new_hz), start, count, taps, nf * mb))
+    n = sum(count)
+    return list(start), list(count), list(taps[:n])
+
+
+def resampled_length(orig_hz, new_hz, L):
+    out = _c_i64()
+    check(lib().acx_resampled_length(int(orig_hz), int(new_hz), int(L), ctypes.byref(out)))
+    return out.value
 
 
 def stage_hw(L, stage):

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from .. import _ffi
 from .. import frontend_tables as ft
+from . import resample as _rs
 
 HF_PYTORCH_WEIGHTS_NAME = "model.safetensors"     # convnext.py:29
 HF_CONFIG_NAME = "config.yaml"                    # convnext.py:31
@@ -142,6 +143,7 @@ class ConvNeXt(nn.Module):
         self._ws_retired = []   # replaced workspaces that a captured graph may still reference (only those) stay alive
         self._weights_epoch = 0  # bumped by load_state_dict / _apply / refresh(): forces a repack of the native weights
         self._sig_cache = None  # (epoch, [parameter and buffer tensors]) -- see _signature
+        self._resamplers = {}   # (device index, input rate, 32000) -> _ffi.Resampler: the band tables of forward(sample_rate=)
 
     def _init_weights(self, m):
         if isinstance(m, (nn.Conv2d, nn.Linear)):
@@ -200,6 +202,8 @@ class ConvNeXt(nn.Module):
             self._ctx.pop(idx)[0].close()
         for key in [k for k in self._ws if k[0] != keep]:
             self._ws.pop(key)
+        for key in [k for k in self._resamplers if k[0] != keep]:
+            self._resamplers.pop(key).close()
         if keep is None:
             self._ws_retired.clear()
             self._ws_captured.clear()
@@ -209,6 +213,7 @@ class ConvNeXt(nn.Module):
         # native handles (ctypes) and scratch tensors are per-process state, rebuilt on demand
         state = self.__dict__.copy()
         state["_ctx"], state["_ws"], state["_ws_retired"], state["_ws_captured"], state["_sig_cache"] = {}, {}, [], set(), None
+        state["_resamplers"] = {}
         return state
 
     def __deepcopy__(self, memo):
@@ -217,7 +222,7 @@ class ConvNeXt(nn.Module):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k in ("_ctx", "_ws"):
+            if k in ("_ctx", "_ws", "_resamplers"):
                 new.__dict__[k] = {}
             elif k == "_ws_retired":
                 new.__dict__[k] = []
@@ -352,11 +357,32 @@ class ConvNeXt(nn.Module):
                                                      _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(wav.device)))
         return out0, out1
 
-    def forward_varlen(self, clips, lengths=None, what="logits"):
+    def _rate(self, sample_rate):
+        """None when the input is at the model rate (today's path, nothing extra launched), else the checked integer rate."""
+        if sample_rate is None:
+            return None
+        rate = _rs.check_rate(sample_rate)
+        return None if rate == _rs.MODEL_RATE else rate
+
+    def _resampled(self, x, sample_rate):
+        """(B, L) at sample_rate -> (B, ceil(nf L / of)) at 32 kHz, on x's stream (acx_resample)."""
+        rate = self._rate(sample_rate)
+        if rate is None:
+            return x
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise ValueError("expected a (batch, samples) waveform tensor, got %r" % (getattr(x, "shape", type(x)),))
+        self._check_run(x.device)
+        _rs.check_min_length(x.shape[1], rate)
+        return _rs.resample(x, rate, _rs.MODEL_RATE, _cache=self._resamplers)
+
+    def forward_varlen(self, clips, lengths=None, what="logits", sample_rate=None):
         """Clips of different lengths in one packed forward (acx_forward_varlen); every clip's result is bit-identical to the
         uniform forward of that clip alone.  clips: a list of 1-D CUDA tensors, or one packed 1-D CUDA tensor plus `lengths`.
         what: "logits" -> {"clipwise_output", "clipwise_logits"} each (B, 527); "scene" -> (B, 768); "frame" -> a list of
-        (768, T'_i, 7) views into one output buffer.  More than 256 clips run as several calls."""
+        (768, T'_i, 7) views into one output buffer.  More than 256 clips run as several calls.
+        sample_rate: the clips' rate (lengths count input samples); other than None / 32000 they are resampled to 32 kHz on
+        the device first (acx_resample), each clip's bits the same as model(clip[None], sample_rate=...)."""
+        rate = self._rate(sample_rate)
         if what not in ("logits", "scene", "frame"):
             raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
         if isinstance(clips, torch.Tensor):
@@ -386,6 +412,10 @@ class ConvNeXt(nn.Module):
         if not lengths:
             raise ValueError("forward_varlen needs at least one clip")
         self._check_run(wav.device)
+        if rate is not None:
+            for i, n in enumerate(lengths):
+                _rs.check_min_length(n, rate, index=i)
+            wav, lengths = _rs.resample(wav, rate, _rs.MODEL_RATE, lengths=lengths, _cache=self._resamplers)
         for i, n in enumerate(lengths):
             if n < _ffi.MIN_SAMPLES:
                 raise RuntimeError("clip %d of %d samples is too short: kernel size can't be greater than actual input size "
@@ -415,18 +445,21 @@ class ConvNeXt(nn.Module):
         return {"clipwise_output": out1, "clipwise_logits": out0}
 
     # ----------------------------------------------------------------------------- public surface
-    def forward(self, x, mixup_lambda=None):
+    # sample_rate (all three): the rate of x; None or 32000 is the model's own.  Any other integer rate is resampled to 32 kHz
+    # on x's stream first (acx_resample, the interpolation of torchaudio.functional.resample that the reference's demo runs on
+    # the host, demo_convnext.py:53-59); the result equals the forward of pytorch.resample.resample(x, sample_rate) bit for bit.
+    def forward(self, x, mixup_lambda=None, sample_rate=None):
         """(B, L) waveform -> {"clipwise_output": probs, "clipwise_logits": logits} (convnext.py:287-331)."""
-        logits, probs = self._run(x, _ffi.MODE_LOGITS)
+        logits, probs = self._run(self._resampled(x, sample_rate), _ffi.MODE_LOGITS)
         return {"clipwise_output": probs, "clipwise_logits": logits}
 
-    def forward_scene_embeddings(self, x, mixup_lambda=None):
+    def forward_scene_embeddings(self, x, mixup_lambda=None, sample_rate=None):
         """(B, L) -> (B, 768) (convnext.py:333-366)."""
-        return self._run(x, _ffi.MODE_SCENE)[0]
+        return self._run(self._resampled(x, sample_rate), _ffi.MODE_SCENE)[0]
 
-    def forward_frame_embeddings(self, x, mixup_lambda=None):
+    def forward_frame_embeddings(self, x, mixup_lambda=None, sample_rate=None):
         """(B, L) -> NCHW (B, 768, T', 7) (convnext.py:369-402)."""
-        return self._run(x, _ffi.MODE_FRAME)[0]
+        return self._run(self._resampled(x, sample_rate), _ffi.MODE_FRAME)[0]
 
     @classmethod
     def from_pretrained(cls, pretrained_checkpoint_path, map_location=None, use_auth_token=None):

@@ -10,6 +10,11 @@ Parity is UNPINNED by the reference (it holds no vector for this step); tests/te
 restatement against a direct float64 evaluation of the interpolation formula and against analytic tones.
 
 Host-side I/O, like the reference (which resamples on the CPU before `.to(device)`): not part of the GPU hot path.
+The GPU path is `pytorch.resample.resample` / `forward(..., sample_rate=)` (acx_resample, include/acx.h): the same
+interpolation and output length, but its taps are evaluated in float64 and rounded to fp32 once, and the taps outside the
+window's support |t| < 6 are exactly zero and skipped.  The float32 taps built here differ from those by up to 1.5e-5 at
+44.1 kHz (t is formed in float32 from k / 441), within 1e-7 at 48 and 16 kHz, and are ~3e-24 instead of 0 outside the band.
+Non-finite input: a NaN spreads over every output of this dense form (459 at 44.1 kHz), over ~17 on the GPU path.
 """
 import math
 

@@ -153,6 +153,44 @@ ACX_API int acx_workspace_bytes_varlen(const acx_ctx* ctx, const int64_t* length
 ACX_API int acx_forward_varlen(acx_ctx* ctx, const float* wav, const int64_t* lengths, int B, int mode, float* out0,
                                float* out1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- input resampling: clips at any integer rate -> the model's 32 kHz ---------------------------------------------------
+ * The reference resamples on the host before `.to(device)`: torchaudio.functional.resample with its defaults in the demo
+ * (demo_convnext.py:53-59), librosa.load(sr=32000) in its extraction script (pytorch/extract_embeddings.py).  This is the
+ * same band-limited interpolation as torchaudio 0.11's (Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99), on the
+ * device.  With g = gcd(orig, new), of = orig / g, nf = new / g, base = min(of, nf) * 0.99, width = ceil(6 of / base):
+ *   output n = j nf + i:  y[n] = sum_k h_i[k] x[j of + k - width]      (x = 0 outside the clip), ceil(nf L / of) outputs
+ *   h_i[k] = (base / of) sinc(t) cos^2(pi t / 12),  t = (-i / nf + (k - width) / of) base
+ * The taps are evaluated in float64 and rounded to fp32 once; a tap with |t| >= 6 is exactly zero and is not stored (~17 of
+ * torchaudio's 459 per output remain at 44.1 kHz).  utils/resample.py, the host path, evaluates its taps in float32 (up to
+ * 1.5e-5 from the formula at 44.1 kHz, ~3e-24 instead of 0 outside the band): the two agree to about that.
+ * Each output is an fp32 FMA chain over its phase's stored band in ascending k, whatever the batch, the clip's position or
+ * the tile: a clip's resampled bits are the same alone, in a uniform batch or packed among other clips.  fp32 in every
+ * precision mode.  Non-finite input is out of scope: a NaN spreads over the ~17 outputs whose band holds it.
+ * Rates are integers in [1, 768000]; a reduced ratio whose table exceeds nf * max_band = 2^22 taps (or whose input span per
+ * 256 outputs exceeds the kernel's LDS budget) is ACX_ERR_UNSUPPORTED, the message naming of/nf.  44101 -> 32000 Hz
+ * (32000 phases x 17 taps) fits.
+ *
+ * Host only (no device needed):
+ *   acx_resample_geometry: of, nf, width and the longest band (any pointer may be NULL).
+ *   acx_resample_taps: band_start[nf] (first stored k of each phase, 0 <= k < 2 width + of), band_count[nf], and the stored
+ *     taps of phase 0, 1, ... back to back in taps[n_taps] (n_taps >= the sum of band_count; nf * max_band always suffices).
+ *   acx_resampled_length: ceil(nf L / of), the output length of utils/resample.py.
+ * Device:
+ *   acx_resampler_create builds the tables and uploads them to `hip_device` (allocates and synchronises: call it outside a
+ *   stream capture); acx_resample allocates nothing later.
+ *   acx_resample: in = B clips back to back (sum(lengths) fp32 samples), out = their resampled clips back to back (the sum of
+ *   acx_resampled_length), device memory; lengths = HOST array, 0 <= lengths[i] < 2^31, 1 <= B <= ACX_MAX_VARLEN_CLIPS (a
+ *   uniform (B, L) batch is B equal lengths).  acx_forward's launch contract: one kernel on `stream`, the lengths passed by
+ *   value, no allocation, no synchronisation, capturable.  Chain it with acx_forward / acx_forward_varlen on the same stream
+ *   (INTEGRATION.md). */
+typedef struct acx_resampler acx_resampler;
+ACX_API int acx_resample_geometry(int orig_hz, int new_hz, int* of, int* nf, int* width, int* max_band);
+ACX_API int acx_resample_taps(int orig_hz, int new_hz, int* band_start, int* band_count, float* taps, size_t n_taps);
+ACX_API int acx_resampled_length(int orig_hz, int new_hz, int64_t L, int64_t* out);
+ACX_API int acx_resampler_create(int hip_device, int orig_hz, int new_hz, acx_resampler** out);
+ACX_API void acx_resampler_destroy(acx_resampler* rs);
+ACX_API int acx_resample(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, void* stream);
+
 /* ---- multi-GPU: the one collective of the path -----------------------------------------------------------------
  * One process per GPU, full weight replica, clips sharded; logits / probabilities / scene rows are all-gathered over xGMI by
  * RCCL (ncclAllGather), frame embeddings stay sharded.  The reference has no inference-time collective (training DDP only,
