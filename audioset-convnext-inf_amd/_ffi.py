@@ -37,6 +37,11 @@ SIGNATURES = {
     "acx_forward": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_workspace_bytes_varlen": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_forward_varlen": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_window_count": (_c_int, [ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
+    "acx_workspace_bytes_windows": (_c_int, [_vp, _c_int, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_forward_windows": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp,
+                                     _vp, _c_sz, _vp]),
+    "acx_window_timeline": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_int, _vp, _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -167,6 +172,11 @@ class Context:
         check(lib().acx_workspace_bytes_varlen(self._h, lens, len(lengths), int(mode), ctypes.byref(out)))
         return out.value
 
+    def workspace_bytes_windows(self, count, window, mode):
+        out = _c_sz()
+        check(lib().acx_workspace_bytes_windows(self._h, int(count), int(window), int(mode), ctypes.byref(out)))
+        return out.value
+
     def sub_batches(self, B):
         """How many sub-batches (on separate streams) a forward of B clips runs as (acx_sub_batches)."""
         out = _c_int()
@@ -258,6 +268,14 @@ def resample_taps(orig_hz, new_hz):
 def resampled_length(orig_hz, new_hz, L):
     out = _c_i64()
     check(lib().acx_resampled_length(int(orig_hz), int(new_hz), int(L), ctypes.byref(out)))
+    return out.value
+
+
+def window_count(lengths, window, hop):
+    """Windows of `window` samples every `hop` samples over recordings of `lengths` samples (acx_window_count; host only)."""
+    lens = (_c_i64 * max(1, len(lengths)))(*[int(n) for n in lengths])
+    out = _c_i64()
+    check(lib().acx_window_count(lens, len(lengths), int(window), int(hop), ctypes.byref(out)))
     return out.value
 
 

@@ -304,8 +304,10 @@ struct VarGeom {
 // dense_frames / dense_spec: scratch of the dense-DFT fallback (B*T*1024 and B*T*kDenseN floats); null: the context's own
 // scratch, grown on demand (per-kernel entry point only: not capturable)
 constexpr int kDenseN = 1056;                    // 2 x 513 rows padded to a multiple of the GEMM's 96-column tile
+// wstart: windows of acx_forward_windows -- clip b's L samples start at wav + wstart[b] (device table) instead of wav + b L;
+// needs the forward's scratch
 int launch_logmel(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* out, bool bn, hipStream_t s,
-                  float* dense_frames = nullptr, float* dense_spec = nullptr);
+                  float* dense_frames = nullptr, float* dense_spec = nullptr, const long long* wstart = nullptr);
 // act_bf16: the activation tensors named void* are bf16 (ACX_PREC_BF16_ACT, stages 0-2) instead of fp32; launch_dwconv then
 // takes the matrix-pipe kernel (dwconv_mfma.hip), which reads BlockW::dw_ops
 int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hipStream_t s, bool act_bf16 = false);
@@ -415,6 +417,16 @@ int launch_nhwc_to_nchw_varlen(acx_ctx* c, const float* x, float* out, const Var
 // the tables of vg (device pointers into `ws`) from the host lengths; bytes: their size (256-byte aligned)
 int varlen_geometry(const int64_t* lengths, int B, char* ws, VarGeom* vg, size_t* bytes);
 int launch_varlen_tables(const int64_t* lengths, const VarGeom& vg, hipStream_t s);
+
+// ---- sliding windows (acx_forward_windows / acx_window_timeline, windows.hip) --------------------------------------------------
+// R recordings of lengths[r] samples back to back; window j of recording r starts at min(j hop, max(0, L_r - window)) and the
+// windows are numbered recording by recording.  Checks window / hop / R / lengths; *n_windows (may be null): their total.
+int window_check(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t* n_windows);
+// wstart[i] = absolute sample offset (into the packed recordings) of window first + i, i < count
+int launch_window_table(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t first, int count, long long* wstart,
+                        hipStream_t s);
+int launch_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce,
+                           float* out, hipStream_t s);
 
 // number of CUs of the current device (one persistent workgroup each), cached per device
 inline int cu_count_of_current_device(int* out) {

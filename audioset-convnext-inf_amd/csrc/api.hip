@@ -764,8 +764,9 @@ static void release_aux(acx_ctx* c, hipStream_t st) {
     if (it != c->aux.end() && it->second.users > 0) it->second.users -= 1;
 }
 
+// wstart: windows (acx_forward_windows) -- clip b's samples start at wav + wstart[b] (device table), not at wav + b L
 static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws,
-                       const Plan& p, hipStream_t st) {
+                       const Plan& p, hipStream_t st, const long long* wstart = nullptr) {
     float* feat = (float*)(ws + p.off_feat);
     float* x[4];
     for (int s = 0; s < 4; ++s) x[s] = (float*)(ws + p.off_x[s]);
@@ -775,7 +776,7 @@ static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode,
 
     // (dense-DFT fallback: frames in `hidden`, spectrum in `y` -- both idle until the first block, both large enough:
     // T * 4096 <= H0 * 86016 and T * 4 kDenseN <= H0 * 21504 bytes per clip with H0 >= (T + 1) / 4)
-    ACX_TRY(launch_logmel(c, wav, B, L, p.T, feat, true, st, hidden, y));
+    ACX_TRY(launch_logmel(c, wav, B, L, p.T, feat, true, st, hidden, y, wstart));
     ACX_TRY(launch_stem(c, feat, B, p.T, p.Hs[0], x[0], st, act_bf16(c, 0)));
     for (int s = 0; s < 4; ++s) {
         // The last block of stages 0-2 writes LayerNorm(x) as GEMM operand rows (S16 / bf16) instead of x: nothing else
@@ -796,18 +797,10 @@ static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode,
     return launch_pool_head(c, x[3], B, p.Hs[3], nullptr, out0, out1, st);
 }
 
-int acx_forward(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, void* workspace,
-                size_t workspace_bytes, void* stream) {
-    ACX_TRY(need_ready(c));
-    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward: null pointer");
-    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward: bad mode %d", mode);
-    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward: logits mode needs out1 (probs)");
-    size_t need = 0;
-    ACX_TRY(acx_workspace_bytes(c, B, L, mode, &need));
-    if (workspace_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    if (((uintptr_t)workspace & 255) != 0) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
+// The uniform forward of acx_forward and acx_forward_windows (arguments checked by the caller).  wstart: the window table --
+// sub-batch i gets its slice of it and the whole of wav.
+static int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws,
+                           hipStream_t st, const long long* wstart) {
     // Clips are independent: a large batch runs as sub-batches on separate streams (fork/join with events, so the call
     // still looks like one unit of work on `stream` and stays graph-capturable).  Per-kernel event profiling runs
     // un-split to keep launch durations clean.  The kernels of the 16-bit arithmetics are CU-exclusive -- nothing
@@ -841,8 +834,8 @@ int acx_forward(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float*
                 if (he != hipSuccess) { set_error("hipStreamWaitEvent(fork) failed: %s", hipGetErrorString(he)); rc = ACX_ERR_HIP; break; }
                 forked = i;
             }
-            rc = forward_one(c, wav + (size_t)b_off * L, Bi, L, mode, out0 + b_off * per_clip,
-                             out1 ? out1 + b_off * per_clip : nullptr, ws + ws_off, pi, si);
+            rc = forward_one(c, wstart ? wav : wav + (size_t)b_off * L, Bi, L, mode, out0 + b_off * per_clip,
+                             out1 ? out1 + b_off * per_clip : nullptr, ws + ws_off, pi, si, wstart ? wstart + b_off : nullptr);
             ws_off += pi.total;
             b_off += Bi;
             if (rc == ACX_OK && c->fail_sub.load(std::memory_order_relaxed) == i) {
@@ -861,7 +854,69 @@ int acx_forward(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float*
     }
     Plan p;
     ACX_TRY(make_plan(B, L, &p));
-    return forward_one(c, wav, B, L, mode, out0, out1, ws, p, st);
+    return forward_one(c, wav, B, L, mode, out0, out1, ws, p, st, wstart);
+}
+
+int acx_forward(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, void* workspace,
+                size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward: null pointer");
+    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward: bad mode %d", mode);
+    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward: logits mode needs out1 (probs)");
+    size_t need = 0;
+    ACX_TRY(acx_workspace_bytes(c, B, L, mode, &need));
+    if (workspace_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    return forward_uniform(c, wav, B, L, mode, out0, out1, (char*)workspace, (hipStream_t)stream, nullptr);
+}
+
+// ---- sliding windows -----------------------------------------------------------------------------------------------------
+// Workspace: the window table (count absolute sample offsets), then the uniform forward's workspace of count clips of W samples.
+int acx_window_count(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t* n_windows) {
+    if (!n_windows) ACX_FAIL(ACX_ERR_ARG, "acx_window_count: n_windows is null");
+    return window_check(lengths, R, window, hop, n_windows);
+}
+
+int acx_workspace_bytes_windows(const acx_ctx* c, int count, int64_t window, int mode, size_t* out_bytes) {
+    if (!out_bytes || mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_workspace_bytes_windows: bad argument");
+    size_t fwd = 0;
+    ACX_TRY(acx_workspace_bytes(c, count, window, mode, &fwd));
+    *out_bytes = align_up((size_t)count * 8) + fwd;
+    return ACX_OK;
+}
+
+int acx_forward_windows(acx_ctx* c, const float* wav, const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t first,
+                        int count, int mode, float* out0, float* out1, void* workspace, size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: null pointer");
+    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: bad mode %d", mode);
+    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: logits mode needs out1 (probs)");
+    int64_t n = 0;
+    ACX_TRY(window_check(lengths, R, window, hop, &n));
+    for (int r = 0; r < R; ++r)
+        if (lengths[r] < window)
+            ACX_FAIL(ACX_ERR_SHAPE, "recording %d of %lld samples is shorter than the window of %lld: run it as one clip "
+                     "(acx_forward_varlen)", r, (long long)lengths[r], (long long)window);
+    if (count <= 0 || first < 0 || first + count > n)
+        ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: windows [%lld, %lld) outside the %lld of these recordings", (long long)first,
+                 (long long)first + count, (long long)n);
+    size_t need = 0;
+    ACX_TRY(acx_workspace_bytes_windows(c, count, window, mode, &need));
+    if (workspace_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    long long* wstart = (long long*)workspace;
+    // on the caller's stream, before forward_uniform records the fork event: every sub-batch reads its slice after it
+    ACX_TRY(launch_window_table(lengths, R, window, hop, first, count, wstart, st));
+    return forward_uniform(c, wav, count, window, mode, out0, out1, (char*)workspace + align_up((size_t)count * 8), st, wstart);
+}
+
+int acx_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce, float* out,
+                        void* stream) {
+    if (!probs || !out) ACX_FAIL(ACX_ERR_ARG, "acx_window_timeline: null pointer");
+    if (reduce != 0 && reduce != 1) ACX_FAIL(ACX_ERR_ARG, "acx_window_timeline: bad reduce %d (0 mean, 1 max)", reduce);
+    ACX_TRY(window_check(lengths, R, window, hop, nullptr));
+    return launch_window_timeline(probs, lengths, R, window, hop, reduce, out, (hipStream_t)stream);
 }
 
 // ---- variable-length batches -------------------------------------------------------------------------------------------

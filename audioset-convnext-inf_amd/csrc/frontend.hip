@@ -33,8 +33,12 @@ struct FrontLds {
     cf buf[kFrontWaves][2][kFftBufSlots];      // buf[w][1] doubles as the power spectrum P (513 floats) once pass 3 has
 };                                             // read it: 49 KB per workgroup = 3 workgroups per CU
 
+// How a frame finds its clip's samples.  UNIFORM: B clips of L samples back to back, frame f = frame f % T of clip f / T.
 // VAR: a variable-length batch -- frame f of clip b = the clip whose frame range [foff[b], foff[b+1]) holds f; its samples start
 // at soff[b] and number soff[b+1] - soff[b] (reflect padding at the clip's own ends).  L and T are unused then.
+// WIN: windows of acx_forward_windows -- frame f = frame f % T of window b = f / T, as UNIFORM, but window b's L samples start
+// at soff[b] (the window table, windows.hip) instead of b L: windows overlap and need not be evenly spaced.
+enum FrontForm : int { kFrontUniform = 0, kFrontVar = 1, kFrontWin = 2 };
 __device__ __forceinline__ int var_frame_clip(const int* __restrict__ foff, int B, long long f) {
     int lo = 0, hi = B - 1;
     while (lo < hi) {
@@ -44,7 +48,7 @@ __device__ __forceinline__ int var_frame_clip(const int* __restrict__ foff, int 
     return lo;
 }
 
-template <bool VAR>
+template <FrontForm F>
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ wav, long long L, int T,
                                                      long long nframes, const float* __restrict__ hann,
                                                      const float* __restrict__ twiddle,
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
         long long b, Lc;
         int t;
         const float* x;
-        if (VAR) {
+        if (F == kFrontVar) {
             b = var_frame_clip(foff, B, valid ? f : 0);
             t = valid ? (int)(f - foff[b]) : 0;
             x = wav + soff[b];
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
         } else {
             b = valid ? f / T : 0;
             t = valid ? (int)(f - b * T) : 0;
-            x = wav + b * L;
+            x = wav + (F == kFrontWin ? soff[b] : b * L);
             Lc = L;
         }
         const long long p0 = 320LL * t;
@@ -219,7 +223,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
 //   frames [B T, 1024] (reflect-padded, NO window: it is inside the stored weights) . [conv_real; conv_imag]^T -> [B T, 2 x 513]
 // on the f32-input matrix cores (gemm.hip, the native fp32 GEMM: in every precision mode the frontend stays fp32), then
 // |.|^2, the banded mel filter, dB and bn0 exactly as in logmel_kernel.
-template <bool VAR>
+template <FrontForm F>
 __global__ __launch_bounds__(256) void frames_kernel(const float* __restrict__ wav, long long L_, int T, long long nframes,
                                                      float* __restrict__ frames, const long long* __restrict__ soff,
                                                      const int* __restrict__ foff, int B) {
@@ -227,7 +231,7 @@ __global__ __launch_bounds__(256) void frames_kernel(const float* __restrict__ w
         long long b, L;
         int t;
         const float* x;
-        if (VAR) {
+        if (F == kFrontVar) {
             b = var_frame_clip(foff, B, f);
             t = (int)(f - foff[b]);
             x = wav + soff[b];
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(256) void frames_kernel(const float* __restrict__ w
             L = L_;
             b = f / T;
             t = (int)(f - b * T);
-            x = wav + b * L;
+            x = wav + (F == kFrontWin ? soff[b] : b * L);
         }
         const long long p0 = 320LL * t;
         float4 v;
@@ -275,7 +279,7 @@ __global__ __launch_bounds__(256) void spec_to_logmel_kernel(const float* __rest
 }
 
 static int launch_logmel_dense(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* out, bool bn, hipStream_t s,
-                               float* frames, float* spec, const VarGeom* vg = nullptr) {
+                               float* frames, float* spec, const VarGeom* vg = nullptr, const long long* wstart = nullptr) {
     const long long nframes = vg ? (long long)vg->frames : (long long)B * T;
     // per-kernel entry point (acx_logmel_bn0; the forward passes its own workspace): frames + spectrum of THIS call, allocated and
     // released in stream order on `s` -- calls on different streams or threads never share scratch (one grown-on-demand
@@ -296,9 +300,9 @@ static int launch_logmel_dense(acx_ctx* c, const float* wav, int B, int64_t L, i
     } scratch_free{call_scratch, s};
     ProfScope ps(c, ACX_K_FRONTEND, s);
     long long blocks = nframes < 4096 ? nframes : 4096;
-    if (vg) launch_kernel(&frames_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)0, 0, nframes, frames, vg->soff, vg->foff, vg->B);
-    else launch_kernel(&frames_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)L, T, nframes, frames,
-                       (const long long*)nullptr, (const int*)nullptr, 0);
+    if (vg) launch_kernel(&frames_kernel<kFrontVar>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)0, 0, nframes, frames, vg->soff, vg->foff, vg->B);
+    else launch_kernel(wstart ? &frames_kernel<kFrontWin> : &frames_kernel<kFrontUniform>, dim3((unsigned)blocks), dim3(256), 0, s,
+                       wav, (long long)L, T, nframes, frames, wstart, (const int*)nullptr, 0);
     ACX_HIP(hipGetLastError());
     GemmArgs g{};
     g.A = frames; g.Wt = c->d_stft_w; g.bias = c->d_stft_zero; g.out = spec; g.M = nframes; g.N = kDenseN; g.K = kNFFT;
@@ -313,19 +317,19 @@ static int launch_logmel_dense(acx_ctx* c, const float* wav, int B, int64_t L, i
 }
 
 int launch_logmel(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* out, bool bn, hipStream_t s,
-                  float* dense_frames, float* dense_spec) {
-    if (c->dense_stft) return launch_logmel_dense(c, wav, B, L, T, out, bn, s, dense_frames, dense_spec);
+                  float* dense_frames, float* dense_spec, const long long* wstart) {
+    if (wstart && (!dense_frames || !dense_spec)) ACX_FAIL(ACX_ERR_ARG, "logmel (windows): the forward's scratch is required");
+    if (c->dense_stft) return launch_logmel_dense(c, wav, B, L, T, out, bn, s, dense_frames, dense_spec, nullptr, wstart);
     long long nframes = (long long)B * T;
     long long blocks = (nframes + kFrontWaves - 1) / kFrontWaves;
     // 6 workgroups per CU (3 resident): a workgroup's setup -- twiddle and mel tables into the LDS, lane twiddles into registers --
     // is paid once per ~10 frames of a wave (with 4 096 workgroups it was once per 4: 184 -> 167 us at B = 64)
     if (blocks > 1536) blocks = 1536;
     ProfScope ps(c, ACX_K_FRONTEND, s);
-    launch_kernel(&logmel_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)L, T, nframes, c->d_hann, c->d_twiddle,
-                                                                c->d_mel_start, c->d_mel_len, c->d_mel_off,
-                                                                c->d_mel_w, c->mel_w_len, bn ? c->d_bn_scale : c->d_bn_one,
-                                                                bn ? c->d_bn_shift : c->d_bn_zero, out, (const long long*)nullptr,
-                                                                (const int*)nullptr, 0);
+    launch_kernel(wstart ? &logmel_kernel<kFrontWin> : &logmel_kernel<kFrontUniform>, dim3((unsigned)blocks), dim3(256), 0, s, wav,
+                  (long long)L, T, nframes, c->d_hann, c->d_twiddle, c->d_mel_start, c->d_mel_len, c->d_mel_off, c->d_mel_w,
+                  c->mel_w_len, bn ? c->d_bn_scale : c->d_bn_one, bn ? c->d_bn_shift : c->d_bn_zero, out, wstart,
+                  (const int*)nullptr, 0);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
@@ -338,7 +342,7 @@ int launch_logmel_varlen(acx_ctx* c, const float* wav, const VarGeom& vg, float*
     long long blocks = (nframes + kFrontWaves - 1) / kFrontWaves;
     if (blocks > 1536) blocks = 1536;
     ProfScope ps(c, ACX_K_FRONTEND, s);
-    launch_kernel(&logmel_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)0, 0, nframes, c->d_hann, c->d_twiddle,
+    launch_kernel(&logmel_kernel<kFrontVar>, dim3((unsigned)blocks), dim3(256), 0, s, wav, (long long)0, 0, nframes, c->d_hann, c->d_twiddle,
                   c->d_mel_start, c->d_mel_len, c->d_mel_off, c->d_mel_w, c->mel_w_len, c->d_bn_scale, c->d_bn_shift, out,
                   vg.soff, vg.foff, vg.B);
     ACX_HIP(hipGetLastError());

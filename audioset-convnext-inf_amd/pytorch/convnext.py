@@ -20,6 +20,7 @@ import torch.nn as nn
 from .. import _ffi
 from .. import frontend_tables as ft
 from . import resample as _rs
+from . import windows as _win
 
 HF_PYTORCH_WEIGHTS_NAME = "model.safetensors"     # convnext.py:29
 HF_CONFIG_NAME = "config.yaml"                    # convnext.py:31
@@ -443,6 +444,129 @@ class ConvNeXt(nn.Module):
             return out0
         out1 = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
         return {"clipwise_output": out1, "clipwise_logits": out0}
+
+    def _run_windows(self, wav, lengths, W, H, mode, max_batch):
+        """Every window of recordings longer than W (<= 256, packed in wav) through acx_forward_windows, max_batch at a time.
+        Returns (out0, out1) with one row (frame mode: one (768, T'_W, 7) block) per window, in window order."""
+        n = _ffi.window_count(lengths, W, H)
+        dev = wav.device
+        with torch.cuda.device(dev):
+            ctx = self.native_context(dev)
+            if mode == _ffi.MODE_LOGITS:
+                out0 = torch.empty((n, 527), dtype=torch.float32, device=dev)
+                out1 = torch.empty((n, 527), dtype=torch.float32, device=dev)
+            elif mode == _ffi.MODE_SCENE:
+                out0, out1 = torch.empty((n, 768), dtype=torch.float32, device=dev), None
+            else:
+                out0, out1 = torch.empty((n,) + (768,) + _ffi.stage_hw(W, 3), dtype=torch.float32, device=dev), None
+            ws = self._workspace(dev, ctx.workspace_bytes_windows(min(n, max_batch), W, mode))
+            lens = (ctypes.c_int64 * len(lengths))(*lengths)
+            for first in range(0, n, max_batch):
+                count = min(max_batch, n - first)
+                o0 = out0[first:first + count]
+                o1 = None if out1 is None else out1[first:first + count]
+                _ffi.check(_ffi.lib().acx_forward_windows(ctx.handle, _ffi.ptr(wav), lens, len(lengths), W, H, first, count, mode,
+                                                          _ffi.ptr(o0), _ffi.ptr(o1), _ffi.ptr(ws), ws.numel(),
+                                                          _ffi.stream_ptr(dev)))
+        return out0, out1
+
+    def forward_windows(self, recordings, window=10.0, hop=None, what="logits", sample_rate=None, max_batch=64,
+                        timeline="mean"):
+        """Sliding-window tagging of long recordings (pytorch/windows.py has the definition).  Every window's outputs are
+        bit-identical to the uniform forward of that window cut out and run alone.
+
+        recordings: one 1-D CUDA tensor (returns one dict) or a list of them (returns a list of dicts).  window / hop: seconds,
+        whole numbers of samples at 32 kHz; hop=None means hop = window.  Each dict has "starts" (float64 CPU tensor, window
+        starts in seconds) and, by `what`: "logits" -> "clipwise_output" / "clipwise_logits" (n, 527) plus "timeline"
+        (ceil(L / hop), 527), the per-step mean or max of the probabilities over the windows covering the step's midpoint
+        (timeline="mean" | "max" | None); "scene" -> "scene" (n, 768); "frame" -> "frame" (n, 768, T', 7).  Recordings longer
+        than the window run max_batch windows per call (acx_forward_windows); shorter ones are one window, the clip itself
+        (forward_varlen).  sample_rate: the recordings' rate; they are resampled to 32 kHz on the device first (acx_resample)
+        and the starts stay in seconds of the original audio."""
+        rate = self._rate(sample_rate)
+        if what not in ("logits", "scene", "frame"):
+            raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
+        if timeline not in ("mean", "max", None):
+            raise ValueError("timeline must be 'mean', 'max' or None (got %r)" % (timeline,))
+        if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
+            raise ValueError("max_batch must be a positive integer (got %r)" % (max_batch,))
+        W = _win.seconds_to_samples(window, "window")
+        H = W if hop is None else _win.seconds_to_samples(hop, "hop")
+        _win.check_window(W, H)
+        single = isinstance(recordings, torch.Tensor)
+        recs = [recordings] if single else list(recordings)
+        if not recs:
+            raise ValueError("forward_windows needs at least one recording")
+        for r in recs:
+            if not isinstance(r, torch.Tensor) or r.dim() != 1:
+                raise ValueError("expected 1-D waveform tensors, got %r" % (getattr(r, "shape", type(r)),))
+        devs = {r.device for r in recs}
+        if len(devs) != 1:
+            raise RuntimeError("recordings on several devices: %s" % sorted(str(d) for d in devs))
+        self._check_run(recs[0].device)
+        lengths = [int(r.numel()) for r in recs]
+        wav = recs[0].detach() if len(recs) == 1 else torch.cat([r.detach().to(torch.float32) for r in recs])
+        wav = wav.to(torch.float32).contiguous()
+        if rate is not None:
+            wav, lengths = _rs.resample(wav, rate, _rs.MODEL_RATE, lengths=lengths, _cache=self._resamplers)
+        for i, n in enumerate(lengths):
+            if n < _ffi.MIN_SAMPLES:
+                raise RuntimeError("recording %d of %d samples at %d Hz is too short: kernel size can't be greater than actual "
+                                   "input size (minimum is %d samples)" % (i, n, _rs.MODEL_RATE, _ffi.MIN_SAMPLES))
+        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
+        key ={"logits": "clipwise_logits", "scene": "scene", "frame": "frame"}[what]
+        offs = [0]
+        for n in lengths:
+            offs.append(offs[-1] + n)
+        results = []
+        cap = _ffi.MAX_VARLEN_CLIPS
+        for c0 in range(0, len(lengths), cap):
+            idx = range(c0, min(c0 + cap, len(lengths)))
+            long_ = [i for i in idx if lengths[i] > W]
+            short = [i for i in idx if lengths[i] <= W]
+            per = {}                  # recording -> (out0 rows, out1 rows or None)
+            if long_:
+                if long_ == list(range(long_[0], long_[-1] + 1)):        # back to back in wav already: no copy
+                    packed = wav[offs[long_[0]]:offs[long_[-1] + 1]]
+                else:
+                    packed = torch.cat([wav[offs[i]:offs[i + 1]] for i in long_])
+                out0, out1 = self._run_windows(packed, [lengths[i] for i in long_], W, H, mode, max_batch)
+                w0 = 0
+                for i in long_:
+                    n = _win.window_count(lengths[i], W, H)
+                    per[i] = (out0[w0:w0 + n], None if out1 is None else out1[w0:w0 + n])
+                    w0 += n
+            if short:
+                res = self.forward_varlen([wav[offs[i]:offs[i + 1]] for i in short], what=what)
+                for k, i in enumerate(short):
+                    if what == "logits":
+                        per[i] = (res["clipwise_logits"][k:k + 1], res["clipwise_output"][k:k + 1])
+                    elif what == "scene":
+                        per[i] = (res[k:k + 1], None)
+                    else:
+                        per[i] = (res[k][None], None)
+            tl = None
+            if what == "logits" and timeline is not None:
+                probs = torch.cat([per[i][1] for i in idx]).contiguous()
+                chunk = [lengths[i] for i in idx]
+                tl = torch.empty((len(_win.timeline_steps(chunk, W, H)), 527), dtype=torch.float32, device=wav.device)
+                lens = (ctypes.c_int64 * len(chunk))(*chunk)
+                with torch.cuda.device(wav.device):
+                    _ffi.check(_ffi.lib().acx_window_timeline(_ffi.ptr(probs), lens, len(chunk), W, H,
+                                                              1 if timeline == "max" else 0, _ffi.ptr(tl),
+                                                              _ffi.stream_ptr(wav.device)))
+            t0 = 0
+            for i in idx:
+                starts = _win.window_starts([lengths[i]], W, H)
+                d = {"starts": torch.tensor(starts, dtype=torch.float64) / _rs.MODEL_RATE, key: per[i][0]}
+                if what == "logits":
+                    d["clipwise_output"] = per[i][1]
+                    if tl is not None:
+                        steps = (lengths[i] + H - 1) // H
+                        d["timeline"] = tl[t0:t0 + steps]
+                        t0 += steps
+                results.append(d)
+        return results[0] if single else results
 
     # ----------------------------------------------------------------------------- public surface
     # sample_rate (all three): the rate of x; None or 32000 is the model's own.  Any other integer rate is resampled to 32 kHz

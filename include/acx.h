@@ -153,6 +153,31 @@ ACX_API int acx_workspace_bytes_varlen(const acx_ctx* ctx, const int64_t* length
 ACX_API int acx_forward_varlen(acx_ctx* ctx, const float* wav, const int64_t* lengths, int B, int mode, float* out0,
                                float* out1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sliding windows over long recordings: tagging over time ---------------------------------------------------------------
+ * No reference counterpart: the reference tags a clip as a whole; PANNs-style harnesses reserve a "segmentwise_output" key
+ * (pytorch/pytorch_utils.py:63-137).  All lengths in samples at 32 kHz.  R recordings of lengths[r] samples (HOST array,
+ * 0 <= lengths[r] < 2^31, 1 <= R <= ACX_MAX_VARLEN_CLIPS) lie back to back in wav; window >= ACX_MIN_SAMPLES, 1 <= hop <= window.
+ *   Recording r has n_r = 1 window if L_r <= window, else 1 + ceil((L_r - window) / hop).  Window j starts at
+ *   s_j = min(j hop, max(0, L_r - window)) -- the last one ends with the recording -- and holds min(window, L_r) samples.
+ *   Windows are numbered recording by recording, then by j.
+ *   acx_window_count: *n_windows = sum of n_r (host only; checks the arguments as the calls below do).
+ *   acx_forward_windows: windows [first, first + count) as a uniform batch of count clips of `window` samples: outputs as
+ *   acx_forward with B = count, L = window, each row bit-identical to acx_forward of that window cut out and run alone.
+ *   Every L_r must be >= window (a shorter recording is one clip: ACX_ERR_SHAPE, run it through acx_forward_varlen).
+ *   acx_forward's launch contract: lengths by value, no allocation or synchronisation, capturable, the same sub-batch split;
+ *   the window table (count absolute sample offsets) is written into the head of the workspace on `stream` first.
+ *   acx_window_timeline: probs = the (sum n_r, 527) probabilities of ALL windows of the R recordings, in window order; out =
+ *   sum_r ceil(L_r / hop) rows of 527.  Row k of recording r has the midpoint m_k = min(k hop + hop / 2, L_r - 1) (integer
+ *   division) and reduces over the windows with s_j <= m_k < s_j + window: reduce 0 = mean (an fp32 sum in ascending j, then
+ *   one fp32 division by their count), 1 = max.  One kernel on `stream`, no allocation, capturable. */
+ACX_API int acx_window_count(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t* n_windows);
+ACX_API int acx_workspace_bytes_windows(const acx_ctx* ctx, int count, int64_t window, int mode, size_t* out_bytes);
+ACX_API int acx_forward_windows(acx_ctx* ctx, const float* wav, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                                int64_t first, int count, int mode, float* out0, float* out1, void* workspace,
+                                size_t workspace_bytes, void* stream);
+ACX_API int acx_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                                int reduce /* 0 mean, 1 max */, float* out, void* stream);
+
 /* ---- input resampling: clips at any integer rate -> the model's 32 kHz ---------------------------------------------------
  * The reference resamples on the host before `.to(device)`: torchaudio.functional.resample with its defaults in the demo
  * (demo_convnext.py:53-59), librosa.load(sr=32000) in its extraction script (pytorch/extract_embeddings.py).  This is the
