@@ -62,6 +62,8 @@ SIGNATURES = {
     "acx_resampler_create": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_vp)]),
     "acx_resampler_destroy": (None, [_vp]),
     "acx_resample": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _vp, _vp]),
+    "acx_metrics_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_tagging_metrics": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_frontend_info": (_c_int, [_vp, _pint, ctypes.POINTER(ctypes.c_float), _pint]),
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
@@ -277,6 +279,23 @@ def window_count(lengths, window, hop):
     out = _c_i64()
     check(lib().acx_window_count(lens, len(lengths), int(window), int(hop), ctypes.byref(out)))
     return out.value
+
+
+TARGET_F32, TARGET_U8 = 0, 1                 # enum acx_target_dtype
+METRICS_NONFINITE, METRICS_BAD_TARGET = 1, 2  # bits of acx_tagging_metrics' status word
+
+
+def metrics_workspace_bytes(n, classes):
+    """Workspace of acx_tagging_metrics for n rows of `classes` scores (host only)."""
+    out = _c_sz()
+    check(lib().acx_metrics_workspace_bytes(int(n), int(classes), ctypes.byref(out)))
+    return out.value
+
+
+def tagging_metrics(scores, ld_scores, target, target_dtype, ld_target, n, classes, ap, auc, dprime, status, ws, stream):
+    """acx_tagging_metrics on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_tagging_metrics(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes), ap,
+                                    auc, dprime, status, ws[0], int(ws[1]), stream))
 
 
 def stage_hw(L, stage):

@@ -1,0 +1,368 @@
+// Per-class AudioSet statistics on the device (acx_tagging_metrics, include/acx.h): average precision, ROC-AUC and d' of the
+// reference's evaluate.py:44-58 (sklearn average_precision_score / roc_auc_score with average=None, scipy norm.ppf).
+//
+// A class's statistics depend only on the order of its scores, so they are computed exactly from two sorted runs:
+//   key(s)  = the float32 bits mapped to an unsigned order (-0.0 canonicalised to +0.0 first: equal scores, equal keys)
+//   for every positive i with key t:  TP(>= t) = P - #pos(< t),  FP(>= t) = Nn - #neg(< t)
+//   AP  = (1/P) sum_i TP / (TP + FP)                      (float64; = sum over distinct positive thresholds of npos * precision)
+//   AUC = sum_i (#neg(< t) + #neg(<= t)) / (2 P Nn)     (numerator in int64: Mann-Whitney with mid-ranks; one float64 division)
+//   d'  = 2 erfinv(2 AUC - 1)                             (= sqrt(2) Phi^-1(AUC))
+// P = 0: AP 0, AUC and d' NaN; Nn = 0: AP 1, AUC and d' NaN (sklearn 1.7.2 warns and returns these).
+//
+// Three launches on the caller's stream: the status word is cleared; metrics_prep_kernel transposes the (N, C) scores and
+// targets into per-class keys / labels in the workspace and ORs invalid inputs into the status word; one workgroup per class
+// then splits its keys into a positives run and a negatives run, sorts both (bitonic network, in LDS up to kMetLdsKeys keys,
+// through the workspace beyond) and counts every positive against them by binary search.  Partial sums are reduced per wave and
+// combined in a fixed order: the results are the same bits on every call.
+#include <cmath>
+
+#include "acx_internal.h"
+
+namespace acx {
+
+constexpr int kMetThreads = 1024;                 // one workgroup per class
+constexpr int kMetWaves = kMetThreads / 64;
+constexpr int kMetLdsKeys = 32768;                // N <= this: both runs sorted in LDS (128 KiB); beyond: LDS chunks of this size
+constexpr int kMetTile = 64;                      // prep: 64 rows x 64 classes per workgroup of 256 threads
+constexpr long long kMetMaxN = 1LL << 30;
+
+__device__ __forceinline__ int met_pow2(int n) { return n <= 1 ? 1 : 1 << (32 - __clz(n - 1)); }
+
+// comparator t of stage (k, j) of the bitonic network that sorts ascending with every comparator (lo < hi) putting the smaller
+// key at lo: the first stage of each block of k pairs r with k - 1 - r, the others are half-cleaners of distance j.  Over a run
+// of n keys padded to a power of two with +infinity, every comparator with hi >= n leaves both keys in place: it is skipped.
+__device__ __forceinline__ void met_pair(int t, int k, int j, int& lo, int& hi) {
+    lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+    hi = (j == (k >> 1)) ? (lo ^ (k - 1)) : (lo + j);
+}
+
+template <typename T>
+__device__ __forceinline__ void met_cmpx(T* a, int lo, int hi) {
+    const unsigned x = a[lo], y = a[hi];
+    if (x > y) { a[lo] = y; a[hi] = x; }
+}
+
+// first index of a[0, n) with a[i] >= t (upper = false) or a[i] > t (upper = true); a sorted ascending
+template <typename T>
+__device__ __forceinline__ int met_bound(const T* a, int n, unsigned t, bool upper) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const unsigned v = a[mid];
+        if (v < t || (upper && v == t)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// global-memory stores of one workgroup made visible to its other waves
+__device__ __forceinline__ void met_gsync() {
+    __threadfence();
+    __syncthreads();
+    __threadfence();
+}
+
+// stages k = k_first .. k_last (all their half-cleaners) over s[0, m), m <= kMetLdsKeys, in LDS
+__device__ void met_lds_network(unsigned* s, int m, int k_first, int k_last) {
+    const int half = met_pow2(m) >> 1;
+    for (int k = k_first; k <= k_last; k <<= 1)
+        for (int j = k >> 1; j >= 1; j >>= 1) {
+            for (int t = threadIdx.x; t < half; t += kMetThreads) {
+                int lo, hi;
+                met_pair(t, k, j, lo, hi);
+                if (hi < m) met_cmpx(s, lo, hi);
+            }
+            __syncthreads();
+        }
+}
+
+// the half-cleaners j = jtop .. 1 of a stage of block size k > kMetLdsKeys, over one chunk s[0, m) in LDS
+__device__ void met_lds_tail(unsigned* s, int m, int k, int jtop) {
+    const int half = met_pow2(m) >> 1;
+    for (int j = jtop; j >= 1; j >>= 1) {
+        for (int t = threadIdx.x; t < half; t += kMetThreads) {
+            int lo, hi;
+            met_pair(t, k, j, lo, hi);
+            if (hi < m) met_cmpx(s, lo, hi);
+        }
+        __syncthreads();
+    }
+}
+
+// sorts g[0, n) in global memory with the whole workgroup: stages whose comparators stay inside a chunk of kMetLdsKeys run on
+// the chunk in LDS (s), the others over global memory
+__device__ void met_global_sort(unsigned* g, int n, unsigned* s) {
+    if (n <= 1) return;
+    const int np = met_pow2(n);
+    const int CH = kMetLdsKeys;
+    const int chunks = (n + CH - 1) / CH;
+    for (int q = 0; q < chunks; ++q) {            // every chunk sorted on its own: stages k = 2 .. min(np, CH)
+        const int m = min(CH, n - q * CH);
+        for (int e = threadIdx.x; e < m; e += kMetThreads) s[e] = g[(long long)q * CH + e];
+        __syncthreads();
+        met_lds_network(s, m, 2, min(np, CH));
+        for (int e = threadIdx.x; e < m; e += kMetThreads) g[(long long)q * CH + e] = s[e];
+        met_gsync();
+    }
+    for (int k = 2 * CH; k <= np; k <<= 1) {
+        for (int j = k >> 1; j >= CH; j >>= 1) {
+            for (int t = threadIdx.x; t < (np >> 1); t += kMetThreads) {
+                int lo, hi;
+                met_pair(t, k, j, lo, hi);
+                if (hi < n) met_cmpx(g, lo, hi);
+            }
+            met_gsync();
+        }
+        for (int q = 0; q < chunks; ++q) {
+            const int m = min(CH, n - q * CH);
+            for (int e = threadIdx.x; e < m; e += kMetThreads) s[e] = g[(long long)q * CH + e];
+            __syncthreads();
+            met_lds_tail(s, m, k, CH >> 1);
+            for (int e = threadIdx.x; e < m; e += kMetThreads) g[(long long)q * CH + e] = s[e];
+            met_gsync();
+        }
+    }
+}
+
+// scores (N, C) row stride ld_s and targets (N, C) row stride ld_t -> keys[c][i] and labels[c][i] of the workspace, coalesced
+// both ways through an LDS tile.  Any non-finite score sets ACX_METRICS_NONFINITE, any target other than 0 or 1
+// ACX_METRICS_BAD_TARGET in *status (one atomic per wave that saw one).
+__global__ __launch_bounds__(256) void metrics_prep_kernel(const float* __restrict__ scores, long long ld_s,
+                                                           const void* __restrict__ target, int u8, long long ld_t, int n,
+                                                           int C, unsigned* __restrict__ keys, unsigned char* __restrict__ labs,
+                                                           int* status) {
+    __shared__ unsigned s_key[kMetTile][kMetTile + 1];
+    __shared__ unsigned char s_lab[kMetTile][kMetTile + 4];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const long long r0 = (long long)blockIdx.x * kMetTile;
+    const int c0 = blockIdx.y * kMetTile;
+    int bad = 0;
+    for (int rr = ty; rr < kMetTile; rr += 4) {
+        const long long r = r0 + rr;
+        const int c = c0 + tx;
+        if (r < n && c < C) {
+            const float v = scores[r * ld_s + c];
+            unsigned u = __float_as_uint(v);
+            if ((u & 0x7f800000u) == 0x7f800000u) bad |= ACX_METRICS_NONFINITE;
+            if (v == 0.0f) u = 0u;                                   // -0.0 == +0.0: one key
+            s_key[rr][tx] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+            unsigned char l;
+            if (u8) {
+                const unsigned char t = static_cast<const unsigned char*>(target)[r * ld_t + c];
+                if (t > 1) bad |= ACX_METRICS_BAD_TARGET;
+                l = t != 0;
+            } else {
+                const float t = static_cast<const float*>(target)[r * ld_t + c];
+                if (!(t == 0.0f || t == 1.0f)) bad |= ACX_METRICS_BAD_TARGET;
+                l = t == 1.0f;
+            }
+            s_lab[rr][tx] = l;
+        }
+    }
+    __syncthreads();
+    for (int cc = ty; cc < kMetTile; cc += 4) {
+        const int c = c0 + cc;
+        const long long r = r0 + tx;
+        if (r < n && c < C) {
+            keys[(long long)c * n + r] = s_key[tx][cc];
+            labs[(long long)c * n + r] = s_lab[tx][cc];
+        }
+    }
+    const unsigned long long b1 = __ballot(bad & ACX_METRICS_NONFINITE), b2 = __ballot(bad & ACX_METRICS_BAD_TARGET);
+    const int bits = (b1 ? ACX_METRICS_NONFINITE : 0) | (b2 ? ACX_METRICS_BAD_TARGET : 0);
+    if (__lane_id() == 0 && bits) atomicOr(status, bits);
+}
+
+// the keys of class c split into positives (from dst[0] up) and negatives (from dst[n - 1] down); returns P (all threads)
+template <typename T>
+__device__ int met_split(const unsigned* __restrict__ key, const unsigned char* __restrict__ lab, int n, T* dst, int* s_cnt) {
+    if (threadIdx.x == 0) { s_cnt[0] = 0; s_cnt[1] = 0; }
+    __syncthreads();
+    const int lane = __lane_id();
+    const unsigned long long below = (1ULL << lane) - 1;
+    for (int i0 = 0; i0 < n; i0 += kMetThreads) {
+        const int i = i0 + threadIdx.x;
+        const bool in = i < n;
+        const unsigned k = in ? key[i] : 0u;
+        const bool pos = in && lab[i];
+        const unsigned long long bp = __ballot(pos), bn = __ballot(in && !pos);
+        int bpos = 0, bneg = 0;
+        if (lane == 0) {
+            bpos = atomicAdd(&s_cnt[0], __popcll(bp));
+            bneg = atomicAdd(&s_cnt[1], __popcll(bn));
+        }
+        bpos = __shfl(bpos, 0);
+        bneg = __shfl(bneg, 0);
+        if (pos) dst[bpos + __popcll(bp & below)] = k;
+        else if (in) dst[n - 1 - (bneg + __popcll(bn & below))] = k;
+    }
+    __syncthreads();
+    return s_cnt[0];
+}
+
+// every positive against the sorted runs pos[0, P) and neg[0, Nn); the class's three results written by thread 0
+template <typename T>
+__device__ void met_count(const T* pos, int P, const T* neg, int Nn, double* s_ap, long long* s_auc, int c, double* ap,
+                          double* auc, double* dprime) {
+    double a = 0.0;
+    long long u = 0;
+    for (int j = threadIdx.x; j < P; j += kMetThreads) {
+        const unsigned t = pos[j];
+        const int lbp = met_bound(pos, P, t, false);
+        const int lbn = met_bound(neg, Nn, t, false);
+        const int ubn = met_bound(neg, Nn, t, true);
+        const long long tp = P - lbp, fp = Nn - lbn;
+        a += (double)tp / (double)(tp + fp);
+        u += (long long)lbn + ubn;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        a += __shfl_xor(a, off);
+        u += __shfl_xor(u, off);
+    }
+    const int w = threadIdx.x >> 6;
+    if (__lane_id() == 0) { s_ap[w] = a; s_auc[w] = u; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sa = 0.0;
+        long long su = 0;
+        for (int i = 0; i < kMetWaves; ++i) { sa += s_ap[i]; su += s_auc[i]; }
+        const double au = (P > 0 && Nn > 0) ? (double)su / (double)(2LL * P * (long long)Nn) : __builtin_nan("");
+        ap[c] = P > 0 ? sa / (double)P : 0.0;
+        auc[c] = au;
+        dprime[c] = 2.0 * erfinv(2.0 * au - 1.0);
+    }
+}
+
+__device__ __forceinline__ bool met_failed(const int* status, int c, double* ap, double* auc, double* dprime) {
+    if (*status == 0) return false;
+    if (threadIdx.x == 0) {
+        const double nan = __builtin_nan("");
+        ap[c] = nan; auc[c] = nan; dprime[c] = nan;
+    }
+    return true;
+}
+
+// N <= kMetLdsKeys: both runs in LDS (dynamic, n keys)
+__global__ __launch_bounds__(kMetThreads) void metrics_lds_kernel(const unsigned* __restrict__ keys,
+                                                                  const unsigned char* __restrict__ labs, int n,
+                                                                  const int* status, double* ap, double* auc, double* dprime) {
+    extern __shared__ unsigned s_k[];
+    __shared__ int s_cnt[2];
+    __shared__ double s_ap[kMetWaves];
+    __shared__ long long s_auc[kMetWaves];
+    const int c = blockIdx.x;
+    if (met_failed(status, c, ap, auc, dprime)) return;
+    const int P = met_split(keys + (long long)c * n, labs + (long long)c * n, n, s_k, s_cnt);
+    const int Nn = n - P;
+    // both runs through one network loop: comparators of the positives first, then those of the negatives
+    const int npP = met_pow2(P), npN = met_pow2(Nn);
+    const int kmax = max(npP, npN);
+    for (int k = 2; k <= kmax; k <<= 1)
+        for (int j = k >> 1; j >= 1; j >>= 1) {
+            const int hp = k <= npP ? npP >> 1 : 0, hn = k <= npN ? npN >> 1 : 0;
+            for (int t = threadIdx.x; t < hp + hn; t += kMetThreads) {
+                const bool inp = t < hp;
+                unsigned* base = inp ? s_k : s_k + P;
+                int lo, hi;
+                met_pair(inp ? t : t - hp, k, j, lo, hi);
+                if (hi < (inp ? P : Nn)) met_cmpx(base, lo, hi);
+            }
+            __syncthreads();
+        }
+    met_count(s_k, P, s_k + P, Nn, s_ap, s_auc, c, ap, auc, dprime);
+}
+
+// N > kMetLdsKeys: the runs of class c in runs[c][0, n) of the workspace, sorted chunk-wise in LDS and across chunks in place
+__global__ __launch_bounds__(kMetThreads) void metrics_global_kernel(const unsigned* __restrict__ keys,
+                                                                     const unsigned char* __restrict__ labs, int n,
+                                                                     unsigned* runs, const int* status, double* ap,
+                                                                     double* auc, double* dprime) {
+    extern __shared__ unsigned s_k[];
+    __shared__ int s_cnt[2];
+    __shared__ double s_ap[kMetWaves];
+    __shared__ long long s_auc[kMetWaves];
+    const int c = blockIdx.x;
+    if (met_failed(status, c, ap, auc, dprime)) return;
+    unsigned* g = runs + (long long)c * n;
+    const int P = met_split(keys + (long long)c * n, labs + (long long)c * n, n, g, s_cnt);
+    const int Nn = n - P;
+    met_gsync();
+    met_global_sort(g, P, s_k);
+    met_global_sort(g + P, Nn, s_k);
+    met_count((const unsigned*)g, P, (const unsigned*)(g + P), Nn, s_ap, s_auc, c, ap, auc, dprime);
+}
+
+static size_t met_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// keys, labels and (N > kMetLdsKeys) the global runs, each 256-byte aligned
+static void met_layout(long long n, long long C, size_t* keys_off, size_t* labs_off, size_t* runs_off, size_t* total) {
+    const size_t kb = met_align((size_t)n * C * 4), lb = met_align((size_t)n * C);
+    *keys_off = 0;
+    *labs_off = kb;
+    *runs_off = kb + lb;
+    *total = kb + lb + (n > kMetLdsKeys ? kb : 0);
+}
+
+static int met_check_shape(int64_t n, int classes) {
+    if (n < 1) ACX_FAIL(ACX_ERR_ARG, "tagging metrics: n = %lld (expected >= 1)", (long long)n);
+    if (classes < 1) ACX_FAIL(ACX_ERR_ARG, "tagging metrics: %d classes (expected >= 1)", classes);
+    if (n > kMetMaxN) ACX_FAIL(ACX_ERR_UNSUPPORTED, "tagging metrics: n = %lld (at most 2^30 rows)", (long long)n);
+    return ACX_OK;
+}
+
+}  // namespace acx
+
+using namespace acx;
+
+extern "C" {
+
+int acx_metrics_workspace_bytes(int64_t n, int classes, size_t* out_bytes) {
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "acx_metrics_workspace_bytes: out_bytes is null");
+    ACX_TRY(met_check_shape(n, classes));
+    size_t k, l, r;
+    met_layout(n, classes, &k, &l, &r, out_bytes);
+    return ACX_OK;
+}
+
+int acx_tagging_metrics(const float* scores, int64_t ld_scores, const void* target, int target_dtype, int64_t ld_target,
+                        int64_t n, int classes, double* ap, double* auc, double* dprime, int32_t* status, void* ws,
+                        size_t ws_bytes, void* stream) {
+    if (!scores || !target || !ap || !auc || !dprime || !status || !ws)
+        ACX_FAIL(ACX_ERR_ARG, "acx_tagging_metrics: null argument");
+    if (target_dtype != ACX_TARGET_F32 && target_dtype != ACX_TARGET_U8)
+        ACX_FAIL(ACX_ERR_ARG, "acx_tagging_metrics: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", target_dtype);
+    ACX_TRY(met_check_shape(n, classes));
+    if (ld_scores < classes || ld_target < classes)
+        ACX_FAIL(ACX_ERR_ARG, "acx_tagging_metrics: row strides %lld / %lld are shorter than %d classes", (long long)ld_scores,
+                 (long long)ld_target, classes);
+    size_t koff, loff, roff, need;
+    met_layout(n, classes, &koff, &loff, &roff, &need);
+    if (ws_bytes < need)
+        ACX_FAIL(ACX_ERR_WORKSPACE, "acx_tagging_metrics: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws) & 255)
+        ACX_FAIL(ACX_ERR_WORKSPACE, "acx_tagging_metrics: workspace is not 256-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    char* w = static_cast<char*>(ws);
+    unsigned* keys = reinterpret_cast<unsigned*>(w + koff);
+    unsigned char* labs = reinterpret_cast<unsigned char*>(w + loff);
+    ACX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    const dim3 pgrid((unsigned)((n + kMetTile - 1) / kMetTile), (unsigned)((classes + kMetTile - 1) / kMetTile));
+    launch_kernel(&metrics_prep_kernel, pgrid, dim3(256), 0, s, scores, (long long)ld_scores, target,
+                  target_dtype == ACX_TARGET_U8 ? 1 : 0, (long long)ld_target, (int)n, classes, keys, labs, (int*)status);
+    ACX_HIP(hipGetLastError());
+    if (n <= kMetLdsKeys) {
+        static DeviceOnce once;
+        ACX_TRY(set_max_dynamic_lds(once, &metrics_lds_kernel, (size_t)kMetLdsKeys * 4));
+        launch_kernel(&metrics_lds_kernel, dim3(classes), dim3(kMetThreads), (size_t)n * 4, s, (const unsigned*)keys,
+                      (const unsigned char*)labs, (int)n, (const int*)status, ap, auc, dprime);
+    } else {
+        static DeviceOnce once;
+        ACX_TRY(set_max_dynamic_lds(once, &metrics_global_kernel, (size_t)kMetLdsKeys * 4));
+        launch_kernel(&metrics_global_kernel, dim3(classes), dim3(kMetThreads), (size_t)kMetLdsKeys * 4, s, (const unsigned*)keys,
+                      (const unsigned char*)labs, (int)n, reinterpret_cast<unsigned*>(w + roff), (const int*)status, ap, auc,
+                      dprime);
+    }
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+}  // extern "C"

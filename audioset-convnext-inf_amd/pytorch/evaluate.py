@@ -346,21 +346,43 @@ def calculate_statistics(target, clipwise_output):
     return {"average_precision": average_precision, "auc": auc, "d_prime": sqrt(2) * norm.ppf(auc)}
 
 
+METRICS = ("sklearn", "gpu")
+
+
+def _check_metrics(metrics):
+    if metrics not in METRICS:
+        raise ValueError("metrics must be one of %s (got %r)" % (METRICS, metrics))
+
+
+def gpu_statistics(target, clipwise_output, device=None):
+    """calculate_statistics on the GPU (pytorch/metrics.py, acx_tagging_metrics): the same dict, exact up to float64 rounding."""
+    from .metrics import tagging_metrics
+    return tagging_metrics(target, clipwise_output, device=device)
+
+
 class Evaluator(object):
-    def __init__(self, model, use_torchaudio=False):
+    def __init__(self, model, use_torchaudio=False, metrics="sklearn"):
+        """metrics: "sklearn" (the reference's host calls, calculate_statistics) or "gpu" (the same statistics on the model's
+        device, gpu_statistics)."""
         if use_torchaudio:
             raise NotImplementedError("Kaldi-fbank input is outside the inference contract")
+        _check_metrics(metrics)
         self.model = model
+        self.metrics = metrics
 
     def evaluate(self, data_loader):
         """-> {'average_precision': (classes,), 'auc': (classes,), 'd_prime': (classes,)}"""
         out = forward(self.model, data_loader, return_target=True)
+        if self.metrics == "gpu":
+            return gpu_statistics(out["target"], out["clipwise_output"], device=next(self.model.parameters()).device)
         return calculate_statistics(out["target"], out["clipwise_output"])
 
 
-def evaluate_sharded(model, shard, batch_size=256):
+def evaluate_sharded(model, shard, batch_size=256, metrics="sklearn"):
     """Multi-GPU sweep: rank r scores batches r, r+W, ...; scores and targets are gathered ONCE
-    at the end (all_gather of padded per-rank blocks), every rank then computes the same statistics."""
+    at the end (all_gather of padded per-rank blocks), every rank then computes the same statistics -- on the host with
+    metrics="sklearn", on its own GPU with metrics="gpu" (the gathered blocks stay on the device)."""
+    _check_metrics(metrics)
     import torch.distributed as dist
     from ..utils.data_generator import evaluate_batches
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -383,7 +405,14 @@ def evaluate_sharded(model, shard, batch_size=256):
         t_all = torch.empty((world * per_rank, classes), device=device)
         dist.all_gather_into_tensor(s_all, pad(scores if scores is not None else np.zeros((0, classes), np.float32)))
         dist.all_gather_into_tensor(t_all, pad(target if target is not None else np.zeros((0, classes), np.float32)))
+        if metrics == "gpu":
+            s_all, t_all = s_all.view(world, per_rank, classes), t_all.view(world, per_rank, classes)
+            rows = [int(counts[r]) for r in range(world)]
+            return gpu_statistics(torch.cat([t_all[r, : rows[r]] for r in range(world)]),
+                                  torch.cat([s_all[r, : rows[r]] for r in range(world)]), device=device)
         s_all, t_all = s_all.view(world, per_rank, classes).cpu().numpy(), t_all.view(world, per_rank, classes).cpu().numpy()
         scores = np.concatenate([s_all[r, : int(counts[r])] for r in range(world)])
         target = np.concatenate([t_all[r, : int(counts[r])] for r in range(world)])
+    elif metrics == "gpu":
+        return gpu_statistics(target, scores, device=next(model.parameters()).device)
     return calculate_statistics(target, scores)

@@ -4,6 +4,9 @@ evaluate_convnext_on_audioset.py: bs=256 sequential batches, mAP / AUC / d-prime
 `Validate <set> <metric>: x.xxx`.  One process per GPU under torchrun (clips sharded by batch, scores
 gathered once at the end); a single process works too.
 
+Scores: --metrics gpu (default) computes the per-class statistics on each rank's GPU (pytorch/metrics.py, exact up to float64
+rounding); --metrics sklearn makes the reference's host calls.
+
 Data: either the reference's packed HDF5 files (needs h5py) or .npy shards (int16 waveforms (N,320000) +
 targets (N,527)).  Without data, --synthetic N scores a seeded synthetic set (sanity check of the plumbing
 and a clips/s figure for the whole sweep including the int16 -> fp32 conversion and the H2D copy).
@@ -68,7 +71,7 @@ def evaluate(args):
     for name, shard in sets:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        stats = evaluate_sharded(model, shard, batch_size=args.batch_size)
+        stats = evaluate_sharded(model, shard, batch_size=args.batch_size, metrics=args.metrics)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         if rank == 0:
@@ -87,4 +90,6 @@ if __name__ == "__main__":
     p.add_argument("--hdf5", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)
     p.add_argument("--batch_size", type=int, default=256)
+    p.add_argument("--metrics", choices=("gpu", "sklearn"), default="gpu",
+                   help="where mAP / AUC / d-prime are computed: on each rank's GPU (default) or by the reference's sklearn calls")
     evaluate(p.parse_args())

@@ -275,6 +275,34 @@ ACX_API int acx_nhwc_to_nchw(const float* x, float* out, int B, int H, int W, in
  * in stream order in front of acx_forward.  Both buffers on the device, 16-byte aligned; n samples. */
 ACX_API int acx_pcm16_to_f32(const int16_t* pcm, float* out, int64_t n, void* stream);
 
+/* ---- evaluation statistics: per-class AP, ROC-AUC and d' on the device ----------------------------------------------------
+ * The reference scores its evaluation on the host (pytorch/evaluate.py:44-58): sklearn average_precision_score and
+ * roc_auc_score with average=None, then sqrt(2) * scipy.stats.norm.ppf(auc).  These are the same statistics, exact up to
+ * float64 rounding.  For class c with scores s (float32; -0.0 == +0.0, equal values are one threshold), labels y in {0, 1},
+ * P positives and Nn negatives:
+ *   ap[c]     = (1/P) sum over distinct positive scores t of npos(s == t) TP(>= t) / (TP(>= t) + FP(>= t));   P = 0: 0.0
+ *   auc[c]    = sum over positives i of (2 #neg(s < s_i) + #neg(s == s_i)), an exact int64, divided once by 2 P Nn (float64);
+ *               P = 0 or Nn = 0: NaN
+ *   dprime[c] = 2 erfinv(2 auc - 1) = sqrt(2) Phi^-1(auc): +inf at auc = 1, -inf at auc = 0, NaN stays NaN
+ * scores: device (n, classes) fp32 with row stride ld_scores; target: device (n, classes) of target_dtype (ACX_TARGET_F32 or
+ * ACX_TARGET_U8, e.g. a bool tensor) with row stride ld_target; both may be column slices of wider rows.  ap / auc / dprime:
+ * device float64 [classes]; status: one device int32.
+ *   acx_metrics_workspace_bytes: workspace for (n, classes), non-decreasing in both (host only).
+ *   acx_tagging_metrics: ARGUMENT errors return a negative status (null pointer, n < 1, classes < 1, a row stride shorter than
+ *   classes, a workspace too small or not 256-byte aligned; n > 2^30 is ACX_ERR_UNSUPPORTED).  DATA errors are reported only
+ *   through *status, which the call sets to the OR of ACX_METRICS_NONFINITE (a NaN or +-inf score) and ACX_METRICS_BAD_TARGET
+ *   (a target other than 0 or 1), 0 when the data is valid; on a data error every output is NaN.  acx_forward's launch
+ *   contract: every launch in order on `stream` (a 4-byte clear of *status and two kernels), no allocation, no synchronisation,
+ *   capturable; the results are the same bits on every call whatever the workspace holds.  n <= 32768 sorts each class in LDS;
+ *   larger n goes through the workspace. */
+enum acx_target_dtype { ACX_TARGET_F32 = 0, ACX_TARGET_U8 = 1 };
+#define ACX_METRICS_NONFINITE 1
+#define ACX_METRICS_BAD_TARGET 2
+ACX_API int acx_metrics_workspace_bytes(int64_t n, int classes, size_t* out_bytes);
+ACX_API int acx_tagging_metrics(const float* scores, int64_t ld_scores, const void* target, int target_dtype,
+                                int64_t ld_target, int64_t n, int classes, double* ap, double* auc, double* dprime,
+                                int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* Which evaluation of the STFT the frontend uses (round 6).  ACX_FRONTEND_AUTO (default): the FFT kernel when the stored buffers are
  * window x DFT, the dense contraction otherwise (acx_finalize above).  ACX_FRONTEND_DENSE: ALWAYS the dense contraction with the
  * stored `conv_real` / `conv_imag` weights -- the reference's own formulation (two Conv1d, convnext.py:179-187,298) -- 2.1 GFLOP
