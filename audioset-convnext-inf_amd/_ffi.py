@@ -56,6 +56,16 @@ SIGNATURES = {
     "acx_allgather": (_c_int, [_vp, _vp, _vp, _c_sz, _vp]),
     "acx_comm_info": (_c_int, [_vp, _pint, _pint]),
     "acx_pcm16_to_f32": (_c_int, [_vp, _vp, _c_i64, _vp]),
+    "acx_stream_schedule": (_c_int, [_c_i64, _c_i64, _c_int, _c_i64, _c_int, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64),
+                                     ctypes.POINTER(_c_i64)]),
+    "acx_stream_create": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_int, _c_i64, _c_int, ctypes.POINTER(_vp)]),
+    "acx_stream_destroy": (None, [_vp]),
+    "acx_stream_push": (_c_int, [_vp, _vp, _pint, ctypes.POINTER(_c_i64), _c_int, _vp]),
+    "acx_stream_close": (_c_int, [_vp, _pint, _c_int, _vp]),
+    "acx_stream_pending": (_c_int, [_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
+    "acx_stream_next": (_c_int, [_vp, _c_int, _pint, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _pint]),
+    "acx_stream_forward": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_stream_timeline": (_c_int, [_vp, _c_int, _c_i64, _vp, _pint, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _vp]),
     "acx_resample_geometry": (_c_int, [_c_int, _c_int, _pint, _pint, _pint, _pint]),
     "acx_resample_taps": (_c_int, [_c_int, _c_int, _pint, _pint, ctypes.POINTER(ctypes.c_float), _c_sz]),
     "acx_resampled_length": (_c_int, [_c_int, _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
@@ -308,3 +318,12 @@ def num_frames(L):
     t = _c_int()
     check(lib().acx_num_frames(int(L), ctypes.byref(t)))
     return t.value
+
+
+def stream_schedule(window, hop, orig_hz, pushed, closed):
+    """(final 32 kHz samples, windows, timeline rows) emitted so far by one slot of a live stream (acx_stream_schedule; host
+    only): `pushed` input samples at orig_hz, the recording open or closed."""
+    v = [_c_i64(), _c_i64(), _c_i64()]
+    check(lib().acx_stream_schedule(int(window), int(hop), int(orig_hz), int(pushed), 1 if closed else 0,
+                                    *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)

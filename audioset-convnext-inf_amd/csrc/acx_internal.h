@@ -15,6 +15,13 @@
 
 #include "../../include/acx.h"
 
+struct acx_resampler {
+    int device, orig, target, of, nf, width, max_band, per_thread;
+    size_t lds_bytes;
+    int2* band;         // [nf] {start_i - width (input offset of the band's first sample from j * of), count_i}
+    float* taps;        // [max_band][nf]: tap r of phase i at taps[r * nf + i] (lanes on consecutive phases read consecutively)
+};
+
 namespace acx {
 
 constexpr int kDepths[4] = {3, 3, 9, 3};        // convnext.py:655
@@ -427,6 +434,45 @@ int launch_window_table(const int64_t* lengths, int R, int64_t window, int64_t h
                         hipStream_t s);
 int launch_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce,
                            float* out, hipStream_t s);
+
+// The window definition (include/acx.h), shared by windows.hip and stream.hip: windows of a recording of L samples, the start of
+// window j and the timeline steps.
+__host__ __device__ __forceinline__ long long win_count(long long L, long long W, long long H) {
+    return L <= W ? 1 : 1 + (L - W + H - 1) / H;
+}
+__host__ __device__ __forceinline__ long long win_start(long long j, long long L, long long W, long long H) {
+    const long long last = L > W ? L - W : 0;
+    return j * H < last ? j * H : last;
+}
+__host__ __device__ __forceinline__ long long win_steps(long long L, long long H) { return (L + H - 1) / H; }
+
+// The timeline reduction of class c over windows j0 .. j0 + cnt - 1 (cnt >= 1); row(j) points at window j's 527 probabilities.
+// mean: an fp32 sum in ascending j, then one division by the count; max: fmaxf.
+template <class Row>
+__device__ __forceinline__ float win_reduce(Row row, long long j0, long long cnt, int c, int reduce) {
+    float acc = reduce ? -INFINITY : 0.f;
+    for (long long j = j0; j < j0 + cnt; ++j) {
+        const float v = row(j)[c];
+        acc = reduce ? fmaxf(acc, v) : acc + v;
+    }
+    return reduce ? acc : acc / (float)cnt;
+}
+
+// ---- resampling (resample.hip, stream.hip) ------------------------------------------------------------------------------
+// Output n = j nf + i of phase i: the fp32 FMA chain in ascending r over the band's count taps; xs = the staged input of the
+// band's first sample, h = tap 0 of phase i (tap r at h[r nf]).  Both resample kernels call this one chain.
+__device__ __forceinline__ float res_chain(const float* xs, const float* h, int nf, int count) {
+    float acc = 0.0f;
+    for (int r = 0; r < count; ++r) acc = __builtin_fmaf(h[(long long)r * nf], xs[r], acc);
+    return acc;
+}
+
+// ---- live streams (stream.hip) ------------------------------------------------------------------------------------------
+// The uniform forward of count windows of L samples at ring + wstart[b] (api.hip's forward_uniform, the acx_forward_windows
+// path); the caller has written the table on `st` and checked the arguments.
+int forward_windows_at(acx_ctx* c, const float* ring, int count, int64_t L, int mode, float* out0, float* out1, char* ws,
+                       hipStream_t st, const long long* wstart);
+int ctx_ready(const acx_ctx* c);
 
 // number of CUs of the current device (one persistent workgroup each), cached per device
 inline int cu_count_of_current_device(int* out) {

@@ -857,6 +857,18 @@ static int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int m
     return forward_one(c, wav, B, L, mode, out0, out1, ws, p, st, wstart);
 }
 
+}  // extern "C"
+
+namespace acx {
+int forward_windows_at(acx_ctx* c, const float* ring, int count, int64_t L, int mode, float* out0, float* out1, char* ws,
+                       hipStream_t st, const long long* wstart) {
+    return forward_uniform(c, ring, count, L, mode, out0, out1, ws, st, wstart);
+}
+int ctx_ready(const acx_ctx* c) { return need_ready(c); }
+}  // namespace acx
+
+extern "C" {
+
 int acx_forward(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, void* workspace,
                 size_t workspace_bytes, void* stream) {
     ACX_TRY(need_ready(c));

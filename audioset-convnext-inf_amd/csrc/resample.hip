@@ -13,13 +13,6 @@
 
 #include "acx_internal.h"
 
-struct acx_resampler {
-    int device, orig, target, of, nf, width, max_band, per_thread;
-    size_t lds_bytes;
-    int2* band;         // [nf] {start_i - width (input offset of the band's first sample from j * of), count_i}
-    float* taps;        // [max_band][nf]: tap r of phase i at taps[r * nf + i] (lanes on consecutive phases read consecutively)
-};
-
 namespace acx {
 
 constexpr int kResThreads = 256;
@@ -163,10 +156,7 @@ __global__ __launch_bounds__(kResThreads) void resample_kernel(ResClips a, ResGe
                 const int i = (int)(ii - jj * (unsigned)g.nf);
                 const int2 bc = band[i];
                 const float* xs = s_in + (int)jj * g.of + bc.x + base_off;
-                const float* h = taps + i;
-                float acc = 0.0f;
-                for (int r = 0; r < bc.y; ++r) acc = __builtin_fmaf(h[(long long)r * g.nf], xs[r], acc);
-                y[d] = acc;
+                y[d] = res_chain(xs, taps + i, g.nf, bc.y);
             }
         }
         __syncthreads();

@@ -16,15 +16,6 @@ struct WinArgs {
     int len[kVarMaxClips];
 };
 
-__host__ __device__ __forceinline__ long long win_count(long long L, long long W, long long H) {
-    return L <= W ? 1 : 1 + (L - W + H - 1) / H;
-}
-__host__ __device__ __forceinline__ long long win_start(long long j, long long L, long long W, long long H) {
-    const long long last = L > W ? L - W : 0;
-    return j * H < last ? j * H : last;
-}
-__host__ __device__ __forceinline__ long long win_steps(long long L, long long H) { return (L + H - 1) / H; }
-
 // largest i in [0, R) with off[i] <= v (off ascending, off[0] = 0 <= v)
 __device__ __forceinline__ int win_find(const long long* off, int R, long long v) {
     int lo = 0, hi = R - 1;
@@ -79,16 +70,11 @@ __global__ __launch_bounds__(256) void window_timeline_kernel(WinArgs a, const f
         long long m = k * a.H + a.H / 2;
         if (m > L - 1) m = L - 1;
         const long long j0 = m >= a.W ? (m - a.W) / a.H + 1 : 0;
-        const float* pr = probs + (p.woff[r] + j0) * kClasses;
-        for (int c = threadIdx.x; c < kClasses; c += 256) {
-            float acc = reduce ? -INFINITY : 0.f;          // at least one window qualifies (j0 itself: j0 H <= m - W + H <= m)
-            int cnt = 0;
-            for (long long j = j0; j < n && win_start(j, L, a.W, a.H) <= m; ++j, ++cnt) {
-                const float v = pr[(j - j0) * kClasses + c];
-                acc = reduce ? fmaxf(acc, v) : acc + v;
-            }
-            out[row * kClasses + c] = reduce ? acc : acc / (float)cnt;
-        }
+        long long j1 = j0;                                 // at least one window qualifies (j0 itself: j0 H <= m - W + H <= m)
+        while (j1 < n && win_start(j1, L, a.W, a.H) <= m) ++j1;
+        const float* pr = probs + p.woff[r] * kClasses;
+        for (int c = threadIdx.x; c < kClasses; c += 256)
+            out[row * kClasses + c] = win_reduce([pr](long long j) { return pr + j * kClasses; }, j0, j1 - j0, c, reduce);
     }
 }
 

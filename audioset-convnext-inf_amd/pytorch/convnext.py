@@ -21,6 +21,7 @@ from .. import _ffi
 from .. import frontend_tables as ft
 from . import resample as _rs
 from . import windows as _win
+from . import stream as _stream
 
 HF_PYTORCH_WEIGHTS_NAME = "model.safetensors"     # convnext.py:29
 HF_CONFIG_NAME = "config.yaml"                    # convnext.py:31
@@ -567,6 +568,20 @@ class ConvNeXt(nn.Module):
                         t0 += steps
                 results.append(d)
         return results[0] if single else results
+
+    def stream(self, slots=256, window=10.0, hop=1.0, what="logits", sample_rate=None, timeline="mean", max_push=2.0,
+               max_batch=64):
+        """A live-stream handle (pytorch/stream.py): `slots` recordings pushed chunk by chunk, each tagged window by window as
+        soon as a window is complete, with the bits of forward_windows over the whole recording for any chunking.
+        st.push(chunks) -- a list of `slots` 1-D CUDA tensors or None, or {slot: tensor} -- and st.close(slots=None) return
+        one flat dict per call: "slot" / "starts" (CPU) and, by `what`, the outputs of the windows emitted by the call;
+        "timeline" / "timeline_slot" / "timeline_step" for the rows that became final (logits with a timeline; a row trails the
+        newest window by about one window length); "short": the slots whose recording ended under the model's minimum
+        length and emitted nothing.  window / hop: seconds, whole samples at 32 kHz; sample_rate: the input rate of every
+        slot; max_push: the longest chunk the device state is sized for, in seconds -- a longer one is pushed in pieces;
+        max_batch: windows per forward."""
+        return _stream.Stream(self, slots=slots, window=window, hop=hop, what=what, sample_rate=sample_rate,
+                              timeline=timeline, max_push=max_push, max_batch=max_batch)
 
     # ----------------------------------------------------------------------------- public surface
     # sample_rate (all three): the rate of x; None or 32000 is the model's own.  Any other integer rate is resampled to 32 kHz

@@ -178,6 +178,60 @@ ACX_API int acx_forward_windows(acx_ctx* ctx, const float* wav, const int64_t* l
 ACX_API int acx_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop,
                                 int reduce /* 0 mean, 1 max */, float* out, void* stream);
 
+/* ---- live streams: tagging recordings that arrive chunk by chunk ----------------------------------------------------------
+ * No reference counterpart.  A handle has `slots`; each slot holds one recording at a time.  Samples pushed to a slot are
+ * appended to its open recording; acx_stream_close ends it and the slot's next push starts a new one.  Window W, hop H, the
+ * input rate orig_hz and the timeline are fixed at create.  THE INVARIANT: everything a recording emits over all its pushes
+ * and its close -- window starts, per-window outputs in the same order, timeline rows -- equals acx_forward_windows /
+ * acx_window_timeline of the whole recording (after acx_resample of it at its rate), bit for bit, for any chunking.
+ *
+ * THE SCHEDULE (host only: acx_stream_schedule gives it for one slot from the geometry and its totals).  R = the final 32 kHz
+ * samples of the open recording.  At 32 kHz a sample is final when pushed.  Resampling, output n = j nf + i is final once every
+ * input sample its band reads has been pushed (and every earlier output is final); at close all ceil(nf L / of) outputs are,
+ * reading zeros past the end as acx_resample does.  Then, cumulatively:
+ *   - windows: while open, window j (start j H) once j H + W <= R.  At close, with L = the recording's 32 kHz length:
+ *     L >= W: all n = 1 + ceil((L - W) / H), the last end-aligned at L - W;  ACX_MIN_SAMPLES <= L < W: one window, the clip
+ *     itself;  L < ACX_MIN_SAMPLES: nothing (the recording is SHORT; no error, the other slots go on).
+ *   - timeline rows: while open, row k once k H + H / 2 < R - W -- only then can no window still to come cover its midpoint,
+ *     so the timeline trails the newest window by about one window length; at close, all ceil(L / H) rows (none if short).
+ *   acx_stream_schedule: *samples = R, *windows / *rows = the windows / rows emitted so far by a recording with `pushed` input
+ *   samples, open (closed = 0) or closed (closed = 1).  Any output pointer may be NULL.
+ *
+ * acx_stream_create: allocates the device state on ctx's device and synchronises (call it outside any capture): per slot a
+ * 32 kHz ring of 2 (W + the largest 32 kHz advance of one push) samples, an input history when orig_hz != 32000, and with
+ * timeline = 1 the probabilities of about (W + max_push) / H + 4 windows.  max_push: the longest chunk, in input samples.
+ * Every other call allocates nothing and synchronises nothing; the launch calls run on `stream`, which must keep the handle's
+ * work in order (one stream, or an event between two).  Slots, lengths and positions go to the kernels BY VALUE.
+ *   acx_stream_push: n (1 .. ACX_MAX_VARLEN_CLIPS) chunks back to back in `chunks` (device fp32), chunk k of lengths[k]
+ *   (0 .. max_push) input samples to slot[k]; the slots of one call are distinct.  acx_stream_close: end the recordings of
+ *   the n listed slots (a slot never pushed to closes an empty recording).  Both return ACX_ERR_STATE for a slot with windows
+ *   or rows that are not fetched yet: call acx_stream_forward until acx_stream_pending reports no window, then
+ *   acx_stream_timeline, before the next push or close of that slot.
+ *   acx_stream_pending: the windows and rows emitted and not fetched yet (host only).
+ *   acx_stream_next: the next run of pending windows, in slot order and then start order, that share one length -- at most
+ *   `max`: *count of them, *length (W, or a short clip's L), their slots and starts (32 kHz samples within the recording) in
+ *   slot_of / start_of (host arrays of max, may be NULL).  Host only.
+ *   acx_stream_forward: forwards the first `count` pending windows (a run of acx_stream_next) as acx_forward_windows does:
+ *   outputs as acx_forward with B = count, L = length; workspace: acx_workspace_bytes_windows(ctx, count, length, mode).  With
+ *   a timeline the mode must be ACX_MODE_LOGITS, and the probabilities are also kept for the rows.
+ *   acx_stream_timeline: the pending rows (at most max_rows) of slots whose windows are all forwarded, in slot order and then
+ *   step order: out = (rows, 527) device fp32, slot_of / step_of host arrays, *n_rows their number.  reduce 0 = mean, 1 = max,
+ *   the reduction of acx_window_timeline. */
+typedef struct acx_stream acx_stream;
+ACX_API int acx_stream_schedule(int64_t window, int64_t hop, int orig_hz, int64_t pushed, int closed, int64_t* samples,
+                                int64_t* windows, int64_t* rows);
+ACX_API int acx_stream_create(acx_ctx* ctx, int slots, int64_t window, int64_t hop, int orig_hz, int64_t max_push, int timeline,
+                              acx_stream** out);
+ACX_API void acx_stream_destroy(acx_stream* st);
+ACX_API int acx_stream_push(acx_stream* st, const float* chunks, const int* slot, const int64_t* lengths, int n, void* stream);
+ACX_API int acx_stream_close(acx_stream* st, const int* slot, int n, void* stream);
+ACX_API int acx_stream_pending(const acx_stream* st, int64_t* windows, int64_t* rows);
+ACX_API int acx_stream_next(const acx_stream* st, int max, int* slot_of, int64_t* start_of, int64_t* length, int* count);
+ACX_API int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* out1, void* workspace,
+                               size_t workspace_bytes, void* stream);
+ACX_API int acx_stream_timeline(acx_stream* st, int reduce, int64_t max_rows, float* out, int* slot_of, int64_t* step_of,
+                                int64_t* n_rows, void* stream);
+
 /* ---- input resampling: clips at any integer rate -> the model's 32 kHz ---------------------------------------------------
  * The reference resamples on the host before `.to(device)`: torchaudio.functional.resample with its defaults in the demo
  * (demo_convnext.py:53-59), librosa.load(sr=32000) in its extraction script (pytorch/extract_embeddings.py).  This is the
