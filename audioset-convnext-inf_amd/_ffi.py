@@ -17,6 +17,8 @@ KERNEL_CLASSES = ("frontend", "stem", "dwconv", "pw1", "pw2", "rowstats", "downs
                   "mlp_fused", "mlp_wide")
 MIN_SAMPLES = 7360
 MAX_VARLEN_CLIPS = 256
+NUM_CLASSES = 527          # the AudioSet head (ACX_NUM_CLASSES)
+MAX_CLASSES = 32768        # widest classifier head a context takes (ACX_MAX_CLASSES)
 
 _c_int, _c_i64, _c_sz, _vp = ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_void_p
 _pint = ctypes.POINTER(ctypes.c_int)
@@ -30,6 +32,7 @@ SIGNATURES = {
     "acx_set_weight": (_c_int, [_vp, ctypes.c_char_p, _vp, ctypes.POINTER(_c_i64), _c_int]),
     "acx_finalize": (_c_int, [_vp]),
     "acx_set_precision": (_c_int, [_vp, _c_int]),
+    "acx_num_classes": (_c_int, [_vp, _pint]),
     "acx_num_frames": (_c_int, [_c_i64, _pint]),
     "acx_stage_hw": (_c_int, [_c_i64, _c_int, _pint, _pint]),
     "acx_workspace_bytes": (_c_int, [_vp, _c_int, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
@@ -42,6 +45,7 @@ SIGNATURES = {
     "acx_forward_windows": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp,
                                      _vp, _c_sz, _vp]),
     "acx_window_timeline": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_int, _vp, _vp]),
+    "acx_window_timeline_classes": (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_int, _vp, _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -172,6 +176,12 @@ class Context:
             shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
             check(l.acx_set_weight(self._h, k.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()))
         check(l.acx_finalize(self._h))
+
+    def num_classes(self):
+        """N, the class count of the finalized head (acx_num_classes)."""
+        out = _c_int()
+        check(lib().acx_num_classes(self._h, ctypes.byref(out)))
+        return out.value
 
     def workspace_bytes(self, B, L, mode):
         out = _c_sz()

@@ -27,7 +27,12 @@ namespace acx {
 constexpr int kDepths[4] = {3, 3, 9, 3};        // convnext.py:655
 constexpr int kDims[4] = {96, 192, 384, 768};   // convnext.py:656
 constexpr int kNFFT = 1024, kHop = 320, kBins = 513, kMels = 224;   // convnext.py:168-172
-constexpr int kClasses = ACX_NUM_CLASSES;
+constexpr int kClasses = ACX_NUM_CLASSES;      // the AudioSet head; a context's own class count is acx_ctx::num_classes
+// Heads of this many classes or more run as pooling (scene rows into the workspace) + the class-tiled head kernel (misc.hip,
+// head_tiled_kernel); narrower ones, the AudioSet head included, as the fused pool_head_kernel.  Both give the same bits.  The
+// first measured N past the crossover of the two at bs 64, where the fused kernel costs ~0.06 us per class and the tiled one
+// ~0.046 ms flat (at bs 1 the tiled one is faster from N = 527 on); profiles/r12_a_heads_bench.txt, DESIGN.md 2.
+constexpr int kHeadTiledMin = 640;
 constexpr int kStemW = 56;                      // 224 mel bins / 4
 
 void set_error(const char* fmt, ...);
@@ -214,8 +219,9 @@ struct acx_ctx {
     // tail
     float* d_norm_w = nullptr;    // [768]
     float* d_norm_b = nullptr;
-    float* d_head_w = nullptr;    // [527][768]
-    float* d_head_b = nullptr;    // [527]
+    float* d_head_w = nullptr;    // [N][768]
+    float* d_head_b = nullptr;    // [N]
+    int num_classes = 0;          // N of the finalized head (0 while not finalized)
 
     int precision = ACX_PREC_F32_SPLIT;   // acx_set_precision (include/acx.h): the default equals the Python host's
     // two-way batch split over two HIP streams (fork/join by events): kernels of the two halves co-run, so
@@ -261,6 +267,7 @@ struct Tuning {
     std::atomic<int> wide_pers{0};     // ACX_WIDE_PERSIST: 1 = persistent wide fused MLP wherever it exists, 2 = never; 0 = by launch size
     std::atomic<int> dwm_waves{0};     // ACX_DWM_WAVES = 2..9: the matrix-pipe depthwise launch asks for that many waves per CU of its share (0: 8 = two per SIMD)
     std::atomic<int> dw_stream{-1};    // ACX_DW_STREAM = 0 | 1: forces the tile / column-streaming depthwise kernels (-1: by launch size)
+    std::atomic<int> head_path{0};     // ACX_HEAD_PATH = 1 | 2: forces the fused / class-tiled head in the forwards (0: by N, kHeadTiledMin)
 };
 Tuning& tuning();
 void tuning_reload();
@@ -405,6 +412,10 @@ int launch_mlp_fused_wide_bf16(acx_ctx* c, const BlockW& w, int C, const void* y
                                void* ln_out = nullptr, int ld_out = 0, bool act_bf16 = false);
 int launch_pool_head(acx_ctx* c, const float* x, int B, int H3, float* scene, float* logits, float* probs,
                      hipStream_t s);
+// logits / probs (B, N) of B scene rows (B, 768) with the context's head: the class-tiled kernel, same bits as pool_head_kernel
+int launch_head_tiled(acx_ctx* c, const float* scene, int B, float* logits, float* probs, hipStream_t s);
+// the head path of a forward: true = pooling into scene rows + launch_head_tiled
+bool head_tiled(const acx_ctx* c);
 int launch_nhwc_to_nchw(acx_ctx* c, const float* x, float* out, int B, int H, int W, int C, hipStream_t s);
 int launch_pcm16_to_f32(const short* in, float* out, long long n, hipStream_t s);
 
@@ -432,8 +443,8 @@ int window_check(const int64_t* lengths, int R, int64_t window, int64_t hop, int
 // wstart[i] = absolute sample offset (into the packed recordings) of window first + i, i < count
 int launch_window_table(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t first, int count, long long* wstart,
                         hipStream_t s);
-int launch_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce,
-                           float* out, hipStream_t s);
+int launch_window_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                           int reduce, float* out, hipStream_t s);
 
 // The window definition (include/acx.h), shared by windows.hip and stream.hip: windows of a recording of L samples, the start of
 // window j and the timeline steps.
@@ -446,7 +457,7 @@ __host__ __device__ __forceinline__ long long win_start(long long j, long long L
 }
 __host__ __device__ __forceinline__ long long win_steps(long long L, long long H) { return (L + H - 1) / H; }
 
-// The timeline reduction of class c over windows j0 .. j0 + cnt - 1 (cnt >= 1); row(j) points at window j's 527 probabilities.
+// The timeline reduction of class c over windows j0 .. j0 + cnt - 1 (cnt >= 1); row(j) points at window j's probabilities.
 // mean: an fp32 sum in ascending j, then one division by the count; max: fmaxf.
 template <class Row>
 __device__ __forceinline__ float win_reduce(Row row, long long j0, long long cnt, int c, int reduce) {

@@ -28,6 +28,7 @@ void tuning_reload() {
     t.wide_pers.store(digit("ACX_WIDE_PERSIST", "01", -1) < 0 ? 0 : (digit("ACX_WIDE_PERSIST", "01", 0) == 1 ? 1 : 2), std::memory_order_relaxed);
     t.dw_stream.store(digit("ACX_DW_STREAM", "01", -1), std::memory_order_relaxed);
     t.dwm_waves.store(digit("ACX_DWM_WAVES", "23456789", 0), std::memory_order_relaxed);
+    t.head_path.store(digit("ACX_HEAD_PATH", "12", 0), std::memory_order_relaxed);
 }
 
 void set_error(const char* fmt, ...) {
@@ -63,6 +64,7 @@ void prof_next_events(hipEvent_t* a, hipEvent_t* b) {
 }
 
 struct KeySpec { std::string key; std::vector<int64_t> shape; };
+constexpr int64_t kAnyClasses = -1;     // a KeySpec dim of the classifier head: N, 1 .. ACX_MAX_CLASSES
 
 static std::vector<KeySpec> required_keys() {
     std::vector<KeySpec> v;
@@ -98,8 +100,8 @@ static std::vector<KeySpec> required_keys() {
     }
     v.push_back({"norm.weight", {kDims[3]}});
     v.push_back({"norm.bias", {kDims[3]}});
-    v.push_back({"head_audioset.weight", {kClasses, kDims[3]}});
-    v.push_back({"head_audioset.bias", {kClasses}});
+    v.push_back({"head_audioset.weight", {kAnyClasses, kDims[3]}});
+    v.push_back({"head_audioset.bias", {kAnyClasses}});
     return v;
 }
 
@@ -163,6 +165,7 @@ static void free_device(acx_ctx* c) {
     c->allocs.clear();
     for (int s = 0; s < 4; ++s) c->blocks[s].clear();
     c->d_dw_sink = nullptr;
+    c->num_classes = 0;
     c->finalized = false;
 }
 
@@ -191,6 +194,10 @@ static int finalize_impl(acx_ctx* c) {
         auto it = c->host.find(ks.key);
         if (it == c->host.end()) ACX_FAIL(ACX_ERR_STATE, "missing weight '%s'", ks.key.c_str());
     }
+    const int64_t n_w = c->host.at("head_audioset.weight").shape[0], n_b = c->host.at("head_audioset.bias").shape[0];
+    if (n_w != n_b)
+        ACX_FAIL(ACX_ERR_SHAPE, "'head_audioset.weight' has %lld rows but 'head_audioset.bias' has %lld entries: the classifier "
+                 "head's weight and bias must have one row per class", (long long)n_w, (long long)n_b);
     ACX_HIP(hipSetDevice(c->device));
     free_device(c);
 
@@ -371,6 +378,7 @@ static int finalize_impl(acx_ctx* c) {
     ACX_TRY(upload(c, W(c, "norm.bias"), &c->d_norm_b));
     ACX_TRY(upload(c, W(c, "head_audioset.weight"), &c->d_head_w));
     ACX_TRY(upload(c, W(c, "head_audioset.bias"), &c->d_head_b));
+    c->num_classes = (int)n_w;
     c->finalized = true;
     return ACX_OK;
 }
@@ -616,15 +624,22 @@ void acx_destroy(acx_ctx* c) {
 }
 
 int acx_set_weight(acx_ctx* c, const char* key, const float* host_data, const int64_t* shape, int ndim) {
-    if (!c || !key || !host_data || (ndim > 0 && !shape)) ACX_FAIL(ACX_ERR_ARG, "acx_set_weight: null argument");
+    if (!c || !key || (ndim > 0 && !shape)) ACX_FAIL(ACX_ERR_ARG, "acx_set_weight: null argument");
     for (const auto& ks : key_table()) {
         if (ks.key != key) continue;
         if ((int)ks.shape.size() != ndim) ACX_FAIL(ACX_ERR_SHAPE, "'%s': expected %d dims, got %d", key, (int)ks.shape.size(), ndim);
         size_t n = 1;
         for (int d = 0; d < ndim; ++d) {
-            if (shape[d] != ks.shape[d]) ACX_FAIL(ACX_ERR_SHAPE, "'%s': dim %d is %lld, expected %lld", key, d, (long long)shape[d], (long long)ks.shape[d]);
+            if (ks.shape[d] == kAnyClasses) {
+                if (shape[d] < 1 || shape[d] > ACX_MAX_CLASSES)
+                    ACX_FAIL(ACX_ERR_SHAPE, "'%s': dim %d is %lld classes, expected 1 .. %d", key, d, (long long)shape[d],
+                             ACX_MAX_CLASSES);
+            } else if (shape[d] != ks.shape[d]) {
+                ACX_FAIL(ACX_ERR_SHAPE, "'%s': dim %d is %lld, expected %lld", key, d, (long long)shape[d], (long long)ks.shape[d]);
+            }
             n *= (size_t)shape[d];
         }
+        if (!host_data) ACX_FAIL(ACX_ERR_ARG, "acx_set_weight: null argument");     // (after the shape: a 0-row head has no data)
         HostTensor& t = c->host[key];
         t.shape.assign(shape, shape + ndim);
         t.data.assign(host_data, host_data + n);
@@ -640,6 +655,13 @@ int acx_finalize(acx_ctx* c) {
     int rc = finalize_impl(c);
     if (rc != ACX_OK) { free_device(c); }
     return rc;
+}
+
+int acx_num_classes(const acx_ctx* c, int* n) {
+    ACX_TRY(need_ready(c));
+    if (!n) ACX_FAIL(ACX_ERR_ARG, "acx_num_classes: n is null");
+    *n = c->num_classes;
+    return ACX_OK;
 }
 
 int acx_set_precision(acx_ctx* c, int precision) {
@@ -794,6 +816,10 @@ static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode,
     }
     if (mode == ACX_MODE_FRAME) return launch_nhwc_to_nchw(c, x[3], out0, B, p.Hs[3], p.Ws[3], kDims[3], st);
     if (mode == ACX_MODE_SCENE) return launch_pool_head(c, x[3], B, p.Hs[3], out0, nullptr, nullptr, st);
+    if (head_tiled(c)) {       // wide head: scene rows into `feat` (idle since the stem, >= 24 x 224 floats per clip), then the head
+        ACX_TRY(launch_pool_head(c, x[3], B, p.Hs[3], feat, nullptr, nullptr, st));
+        return launch_head_tiled(c, feat, B, out0, out1, st);
+    }
     return launch_pool_head(c, x[3], B, p.Hs[3], nullptr, out0, out1, st);
 }
 
@@ -827,7 +853,7 @@ static int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int m
             rc = make_plan(Bi, L, &pi);
             if (rc != ACX_OK) break;
             const size_t per_clip = mode == ACX_MODE_FRAME ? (size_t)kDims[3] * pi.Hs[3] * pi.Ws[3]
-                                                           : (mode == ACX_MODE_SCENE ? (size_t)kDims[3] : (size_t)kClasses);
+                                                           : (mode == ACX_MODE_SCENE ? (size_t)kDims[3] : (size_t)c->num_classes);
             hipStream_t si = i == 0 ? st : aux.streams[i - 1];
             if (i > 0) {
                 he = hipStreamWaitEvent(si, aux.fork, 0);
@@ -923,12 +949,19 @@ int acx_forward_windows(acx_ctx* c, const float* wav, const int64_t* lengths, in
     return forward_uniform(c, wav, count, window, mode, out0, out1, (char*)workspace + align_up((size_t)count * 8), st, wstart);
 }
 
-int acx_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce, float* out,
-                        void* stream) {
+int acx_window_timeline_classes(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                                int reduce, float* out, void* stream) {
     if (!probs || !out) ACX_FAIL(ACX_ERR_ARG, "acx_window_timeline: null pointer");
+    if (classes < 1 || classes > ACX_MAX_CLASSES)
+        ACX_FAIL(ACX_ERR_ARG, "acx_window_timeline: %d classes (expected 1 .. %d)", classes, ACX_MAX_CLASSES);
     if (reduce != 0 && reduce != 1) ACX_FAIL(ACX_ERR_ARG, "acx_window_timeline: bad reduce %d (0 mean, 1 max)", reduce);
     ACX_TRY(window_check(lengths, R, window, hop, nullptr));
-    return launch_window_timeline(probs, lengths, R, window, hop, reduce, out, (hipStream_t)stream);
+    return launch_window_timeline(probs, classes, lengths, R, window, hop, reduce, out, (hipStream_t)stream);
+}
+
+int acx_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce, float* out,
+                        void* stream) {
+    return acx_window_timeline_classes(probs, kClasses, lengths, R, window, hop, reduce, out, stream);
 }
 
 // ---- variable-length batches -------------------------------------------------------------------------------------------
@@ -999,6 +1032,10 @@ int acx_forward_varlen(acx_ctx* c, const float* wav, const int64_t* lengths, int
     }
     if (mode == ACX_MODE_FRAME) return launch_nhwc_to_nchw_varlen(c, x[3], out0, g, st);
     if (mode == ACX_MODE_SCENE) return launch_pool_head_varlen(c, x[3], g, out0, nullptr, nullptr, st);
+    if (head_tiled(c)) {       // as in forward_one: scene rows into `feat` (>= 24 x 224 floats per clip), then the tiled head
+        ACX_TRY(launch_pool_head_varlen(c, x[3], g, feat, nullptr, nullptr, st));
+        return launch_head_tiled(c, feat, B, out0, out1, st);
+    }
     return launch_pool_head_varlen(c, x[3], g, nullptr, out0, out1, st);
 }
 

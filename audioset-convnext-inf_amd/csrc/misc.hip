@@ -12,7 +12,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // One workgroup of 768 threads per clip.  x NHWC (B,H3,7,768):
 //   mean over the 7 frequency columns (torch.mean(x, dim=3)), then max over time + mean over time,
-//   nn.LayerNorm(768, eps=1e-6) -> scene embedding; Linear 768->527 -> logits; sigmoid -> probs.
+//   nn.LayerNorm(768, eps=1e-6) -> scene embedding; Linear 768->N -> logits; sigmoid -> probs.
 // Thread = (float4 of channels, one of 4 time phases): every thread streams ~H3/4 rows x 7 columns of
 // independent 16-B loads (the first version walked all H3 rows serially per thread: latency-bound, 143 us),
 // partial (max, sum) meet in LDS.
@@ -22,7 +22,7 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
                                                         const float* __restrict__ nw, const float* __restrict__ nb,
                                                         const float* __restrict__ hw, const float* __restrict__ hb,
                                                         float* __restrict__ scene, float* __restrict__ logits,
-                                                        float* __restrict__ probs, const int* __restrict__ roff3) {
+                                                        float* __restrict__ probs, const int* __restrict__ roff3, int N) {
     __shared__ __attribute__((aligned(16))) float pmax[4][768];
     __shared__ __attribute__((aligned(16))) float psum[4][768];
     __shared__ __attribute__((aligned(16))) float emb[768];
@@ -78,12 +78,13 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
 #pragma unroll
     for (int k = 0; k < 3; ++k) e[k] = *reinterpret_cast<const float4*>(&emb[4 * (lane + 64 * k)]);
     // four rows of the head per wave and pass: 12 independent 16-byte loads per lane in flight (one row at a time was a chain
-    // of 44 L2 round trips per wave)
-    for (int n0 = wave; n0 < kClasses; n0 += 48) {
+    // of 44 L2 round trips per wave).  The per-class arithmetic -- lane l's chunks l, l + 64, l + 128, 12 fmaf in chunk and
+    // then component order, wave_sum, + b[n], the sigmoid -- is head_tiled_kernel's as well: both give the same bits.
+    for (int n0 = wave; n0 < N; n0 += 48) {
         float4 w4[4][3];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int n = n0 + 12 * r < kClasses ? n0 + 12 * r : n0;
+            const int n = n0 + 12 * r < N ? n0 + 12 * r : n0;
             const float4* wr = reinterpret_cast<const float4*>(hw + (long long)n * 768);
 #pragma unroll
             for (int k = 0; k < 3; ++k) w4[r][k] = wr[lane + 64 * k];
@@ -98,20 +99,108 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
             }
             s = wave_sum(s);
             const int n = n0 + 12 * r;
-            if (lane == 0 && n < kClasses) {
+            if (lane == 0 && n < N) {
                 const float z = s + hb[n];
-                if (logits) logits[b * kClasses + n] = z;
-                if (probs) probs[b * kClasses + n] = 1.0f / (1.0f + expf(-z));
+                if (logits) logits[b * N + n] = z;
+                if (probs) probs[b * N + n] = 1.0f / (1.0f + expf(-z));
             }
         }
     }
+}
+
+// Class-tiled head for wide heads (kHeadTiledMin): logits / probs (B, N) from the scene rows (B, 768) that pool_head_kernel wrote.
+// pool_head_kernel reads the whole head once per clip (N = 16384: 48 MiB per clip, one busy CU per clip); here a workgroup holds
+// kHeadBt scene rows in LDS and applies the kHeadNt rows of its class tile to all of them, so the head is read ceil(B / kHeadBt)
+// times and the grid fills the chip.  Every (clip, class) value is pool_head_kernel's arithmetic: lane l holds chunks l, l + 64,
+// l + 128 of the row and of the embedding, 12 fmaf in chunk and then component order, wave_sum, + b[n], 1 / (1 + expf(-z)).
+// Plain fp32 VALU, no MFMA: the bits stay, and the kernel is not CU-exclusive.
+// 4 waves; wave w takes classes w * 4 .. w * 4 + 3 of each group of 16, 4 rows in flight as in pool_head_kernel.  After the
+// wave_sums every lane holds each sum; lane r * 16 + i keeps (class r, clip i) of a pass of 16 clips, so that all 64 lanes add
+// the bias, take the sigmoid and store (64 values per store instruction instead of one from lane 0).
+// Grid: one workgroup per (clip tile, class tile), numbered so that the clip tiles of a class tile share blockIdx.x % 8 -- one
+// XCD under round-robin placement, so they read its rows through one L2 (speed only).
+constexpr int kHeadBt = 16;     // clips per workgroup
+constexpr int kHeadNt = 64;     // classes per workgroup
+__global__ __launch_bounds__(256) void head_tiled_kernel(const float* __restrict__ scene, int B, int N,
+                                                         const float* __restrict__ hw, const float* __restrict__ hb,
+                                                         float* __restrict__ logits, float* __restrict__ probs, int ctiles) {
+    __shared__ __attribute__((aligned(16))) float emb[kHeadBt][768];
+    const int btiles = (B + kHeadBt - 1) / kHeadBt;
+    const int g = blockIdx.x;
+    const int q = g / (8 * btiles), rem = g - q * 8 * btiles;
+    const int bt = rem / 8, ct = q * 8 + (rem & 7);
+    if (ct >= ctiles) return;                       // (the class-tile count is padded to a multiple of 8)
+    const int b0 = bt * kHeadBt, nb = B - b0 < kHeadBt ? B - b0 : kHeadBt;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < nb * 192; i += 256) {
+        const int r = i / 192, c4 = i - r * 192;
+        *reinterpret_cast<float4*>(&emb[r][4 * c4]) = reinterpret_cast<const float4*>(scene + (long long)(b0 + r) * 768)[c4];
+    }
+    __syncthreads();
+    for (int n0 = ct * kHeadNt + wave * 4; n0 < (ct + 1) * kHeadNt && n0 < N; n0 += 16) {
+        float4 w4[4][3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = n0 + r < N ? n0 + r : n0;
+            const float4* wr = reinterpret_cast<const float4*>(hw + (long long)n * 768);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w4[r][k] = wr[lane + 64 * k];
+        }
+        const int nr = lane >> 4;                  // the class this lane stores: n0 + nr
+        const float bias = hb[n0 + nr < N ? n0 + nr : n0];
+        for (int i0 = 0; i0 < nb; i0 += 16) {
+            float mine = 0.f;
+            for (int i = i0; i < i0 + 16 && i < nb; ++i) {
+                float4 e[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) e[k] = *reinterpret_cast<const float4*>(&emb[i][4 * (lane + 64 * k)]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        s = fmaf(e[k].x, w4[r][k].x, s); s = fmaf(e[k].y, w4[r][k].y, s);
+                        s = fmaf(e[k].z, w4[r][k].z, s); s = fmaf(e[k].w, w4[r][k].w, s);
+                    }
+                    s = wave_sum(s);
+                    if (lane == r * 16 + (i - i0)) mine = s;
+                }
+            }
+            const int i = i0 + (lane & 15), n = n0 + nr;
+            if (i < nb && n < N) {
+                const float z = mine + bias;
+                const long long o = (long long)(b0 + i) * N + n;
+                if (logits) logits[o] = z;
+                if (probs) probs[o] = 1.0f / (1.0f + expf(-z));
+            }
+        }
+    }
+}
+
+bool head_tiled(const acx_ctx* c) {
+    const int force = tuning().head_path.load(std::memory_order_relaxed);
+    if (force == 1) return false;
+    if (force == 2) return true;
+    return c->num_classes >= kHeadTiledMin;
+}
+
+int launch_head_tiled(acx_ctx* c, const float* scene, int B, float* logits, float* probs, hipStream_t s) {
+    const int N = c->num_classes;
+    const int btiles = (B + kHeadBt - 1) / kHeadBt, ctiles = (N + kHeadNt - 1) / kHeadNt;
+    const long long blocks = (long long)((ctiles + 7) / 8) * 8 * btiles;
+    if (blocks > 0x7fffffffLL) ACX_FAIL(ACX_ERR_SHAPE, "head: %d clips x %d classes is too large a grid", B, N);
+    ProfScope ps(c, ACX_K_POOLHEAD, s);
+    launch_kernel(&head_tiled_kernel, dim3((unsigned)blocks), dim3(256), 0, s, scene, B, N, c->d_head_w, c->d_head_b, logits,
+                  probs, ctiles);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
 }
 
 int launch_pool_head(acx_ctx* c, const float* x, int B, int H3, float* scene, float* logits, float* probs,
                      hipStream_t s) {
     ProfScope ps(c, ACX_K_POOLHEAD, s);
     launch_kernel(&pool_head_kernel<false>, dim3(B), dim3(768), 0, s, x, H3, c->d_norm_w, c->d_norm_b, c->d_head_w, c->d_head_b,
-                                                   scene, logits, probs, (const int*)nullptr);
+                                                   scene, logits, probs, (const int*)nullptr, c->num_classes);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
@@ -120,7 +209,7 @@ int launch_pool_head_varlen(acx_ctx* c, const float* x, const VarGeom& vg, float
                             hipStream_t s) {
     ProfScope ps(c, ACX_K_POOLHEAD, s);
     launch_kernel(&pool_head_kernel<true>, dim3(vg.B), dim3(768), 0, s, x, 0, c->d_norm_w, c->d_norm_b, c->d_head_w, c->d_head_b,
-                  scene, logits, probs, vg.roff[3]);
+                  scene, logits, probs, vg.roff[3], c->num_classes);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

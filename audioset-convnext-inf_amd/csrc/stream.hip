@@ -212,12 +212,12 @@ struct StrStash {
     int n;
     long long row[kStrTable];
 };
-// window b's probabilities -> history row a.row[b]
-__global__ __launch_bounds__(kStrThreads) void stream_stash_kernel(StrStash a, const float* __restrict__ probs,
+// window b's N probabilities -> history row a.row[b]
+__global__ __launch_bounds__(kStrThreads) void stream_stash_kernel(StrStash a, const float* __restrict__ probs, int N,
                                                                   float* __restrict__ hist) {
     const int b = blockIdx.x;
-    for (int c = threadIdx.x; c < kClasses; c += kStrThreads)
-        hist[a.row[b] * kClasses + c] = probs[(long long)b * kClasses + c];
+    for (int c = threadIdx.x; c < N; c += kStrThreads)
+        hist[a.row[b] * N + c] = probs[(long long)b * N + c];
 }
 
 struct StrRows {
@@ -226,10 +226,10 @@ struct StrRows {
     int slot[kStrBatch], rows[kStrBatch];
     long long k0[kStrBatch], L[kStrBatch];
 };
-// One workgroup per row (grid-stride), one thread per class: row k of entry e's slot, as window_timeline_kernel forms it,
+// One workgroup per row (grid-stride), threads striding over the N classes: row k of entry e's slot, as window_timeline_kernel forms it,
 // over the slot's window history (window j at row j mod Hw).  L = kStrOpen while the recording is open.
-__global__ __launch_bounds__(kStrThreads) void stream_timeline_kernel(StrRows a, const float* __restrict__ hist, int reduce,
-                                                                     float* __restrict__ out) {
+__global__ __launch_bounds__(kStrThreads) void stream_timeline_kernel(StrRows a, const float* __restrict__ hist, int N,
+                                                                     int reduce, float* __restrict__ out) {
     __shared__ long long s_roff[kStrBatch + 1];
     if (threadIdx.x == 0) {
         long long t = 0;
@@ -247,11 +247,10 @@ __global__ __launch_bounds__(kStrThreads) void stream_timeline_kernel(StrRows a,
         const long long j0 = m >= a.W ? (m - a.W) / a.H + 1 : 0;
         long long j1 = j0;
         while (j1 < n && win_start(j1, L, a.W, a.H) <= m) ++j1;
-        const float* hs = hist + (long long)a.slot[e] * a.Hw * kClasses;
+        const float* hs = hist + (long long)a.slot[e] * a.Hw * N;
         const long long Hw = a.Hw;
-        for (int c = threadIdx.x; c < kClasses; c += kStrThreads)
-            out[row * kClasses + c] = win_reduce([hs, Hw](long long j) { return hs + (j % Hw) * kClasses; }, j0, j1 - j0, c,
-                                                 reduce);
+        for (int c = threadIdx.x; c < N; c += kStrThreads)
+            out[row * N + c] = win_reduce([hs, Hw, N](long long j) { return hs + (j % Hw) * N; }, j0, j1 - j0, c, reduce);
     }
 }
 
@@ -262,6 +261,7 @@ using namespace acx;
 struct acx_stream {
     acx_ctx* ctx = nullptr;
     int device = 0, slots = 0;
+    int classes = 0;                        // N of the context at create: the width of the probability history and the rows
     bool timeline = false;
     StrGeom g;
     long long max_push = 0, adv_max = 0, C = 0, Ch = 0, Hw = 0;
@@ -375,10 +375,19 @@ int acx_stream_schedule(int64_t window, int64_t hop, int orig_hz, int64_t pushed
     return ACX_OK;
 }
 
+// the handle's rows are `classes` wide: a context finalized since with another N must not get them
+static int check_classes(const acx_stream* st, const char* who) {
+    if (st->ctx->num_classes != st->classes)
+        ACX_FAIL(ACX_ERR_STATE, "%s: the context now has %d classes, the stream was created for %d: create a new stream", who,
+                 st->ctx->num_classes, st->classes);
+    return ACX_OK;
+}
+
 int acx_stream_create(acx_ctx* c, int slots, int64_t window, int64_t hop, int orig_hz, int64_t max_push, int timeline,
                       acx_stream** out) {
     if (!c || !out) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: null argument");
     *out = nullptr;
+    ACX_TRY(ctx_ready(c));
     if (slots < 1 || slots > (1 << 20)) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: %d slots (expected 1 .. 2^20)", slots);
     if (timeline != 0 && timeline != 1) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: timeline must be 0 or 1 (got %d)", timeline);
     StrGeom g;
@@ -393,9 +402,10 @@ int acx_stream_create(acx_ctx* c, int slots, int64_t window, int64_t hop, int or
     const long long Hw = timeline ? (window + adv) / hop + 4 : 0;
     if (C > 0x7fffffffLL) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: window + max_push exceed 2^31 samples at 32 kHz");
     const size_t ring_b = sizeof(float) * 2 * (size_t)C * slots, hin_b = sizeof(float) * (size_t)Ch * slots;
-    const size_t hist_b = sizeof(float) * (size_t)Hw * kClasses * slots;
+    const size_t hist_b = sizeof(float) * (size_t)Hw * c->num_classes * slots;
     acx_stream* st = new acx_stream();
     st->ctx = c; st->device = c->device; st->slots = slots; st->timeline = timeline != 0; st->g = g;
+    st->classes = c->num_classes;
     st->max_push = max_push; st->adv_max = adv; st->C = C; st->Ch = Ch; st->Hw = Hw;
     st->s.assign(slots, acx_stream::Slot{});
     if (res) {
@@ -553,6 +563,7 @@ int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* 
                        void* stream) {
     if (!st) ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: null handle");
     ACX_TRY(ctx_ready(st->ctx));
+    ACX_TRY(check_classes(st, "acx_stream_forward"));
     if (!out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: null pointer");
     if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: bad mode %d", mode);
     if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: logits mode needs out1 (probs)");
@@ -597,8 +608,8 @@ int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* 
             StrStash a{};
             a.n = std::min(kStrTable, count - b0);
             for (int k = 0; k < a.n; ++k) a.row[k] = row[b0 + k];
-            launch_kernel(&stream_stash_kernel, dim3(a.n), dim3(kStrThreads), 0, s, a, (const float*)(out1 + (size_t)b0 * kClasses),
-                          st->hist);
+            launch_kernel(&stream_stash_kernel, dim3(a.n), dim3(kStrThreads), 0, s, a,
+                          (const float*)(out1 + (size_t)b0 * st->classes), st->classes, st->hist);
             ACX_HIP(hipGetLastError());
         }
     }
@@ -611,6 +622,7 @@ int acx_stream_timeline(acx_stream* st, int reduce, int64_t max_rows, float* out
     if (!st || !n_rows) ACX_FAIL(ACX_ERR_ARG, "acx_stream_timeline: null argument");
     *n_rows = 0;
     if (!st->timeline) ACX_FAIL(ACX_ERR_STATE, "acx_stream_timeline: the handle was created without a timeline");
+    ACX_TRY(check_classes(st, "acx_stream_timeline"));
     if (reduce != 0 && reduce != 1) ACX_FAIL(ACX_ERR_ARG, "acx_stream_timeline: bad reduce %d (0 mean, 1 max)", reduce);
     if (max_rows < 0) ACX_FAIL(ACX_ERR_ARG, "acx_stream_timeline: max_rows %lld", (long long)max_rows);
     long long want = 0;
@@ -632,7 +644,7 @@ int acx_stream_timeline(acx_stream* st, int reduce, int64_t max_rows, float* out
     auto flush = [&]() -> int {
         if (a.n == 0) return ACX_OK;
         launch_kernel(&stream_timeline_kernel, dim3((unsigned)std::min(in_launch, 4096LL)), dim3(kStrThreads), 0, s, a,
-                      (const float*)st->hist, reduce, out + (size_t)base * kClasses);
+                      (const float*)st->hist, st->classes, reduce, out + (size_t)base * st->classes);
         ACX_HIP(hipGetLastError());
         base += in_launch;
         in_launch = 0;

@@ -55,11 +55,11 @@ __global__ __launch_bounds__(256) void window_table_kernel(WinArgs a, long long 
     }
 }
 
-// One workgroup per timeline row (grid-stride), one thread per class.  Row k of recording r has the midpoint
-// m = min(k H + H / 2, L_r - 1); the windows with s_j <= m < s_j + W are a run of consecutive j: those with j H > m - W (an
-// earlier window ends at or before m) up to the last with s_j <= m (s_j does not decrease).  mean: an fp32 sum in ascending
+// One workgroup per timeline row (grid-stride), threads striding over the row's N classes.  Row k of recording r has the
+// midpoint m = min(k H + H / 2, L_r - 1); the windows with s_j <= m < s_j + W are a run of consecutive j: those with j H > m - W
+// (an earlier window ends at or before m) up to the last with s_j <= m (s_j does not decrease).  mean: an fp32 sum in ascending
 // j, then one division by the count; max: the largest value.
-__global__ __launch_bounds__(256) void window_timeline_kernel(WinArgs a, const float* __restrict__ probs, int reduce,
+__global__ __launch_bounds__(256) void window_timeline_kernel(WinArgs a, const float* __restrict__ probs, int N, int reduce,
                                                               float* __restrict__ out) {
     __shared__ WinPrefix p;
     win_prefix(a, p);
@@ -72,9 +72,9 @@ __global__ __launch_bounds__(256) void window_timeline_kernel(WinArgs a, const f
         const long long j0 = m >= a.W ? (m - a.W) / a.H + 1 : 0;
         long long j1 = j0;                                 // at least one window qualifies (j0 itself: j0 H <= m - W + H <= m)
         while (j1 < n && win_start(j1, L, a.W, a.H) <= m) ++j1;
-        const float* pr = probs + p.woff[r] * kClasses;
-        for (int c = threadIdx.x; c < kClasses; c += 256)
-            out[row * kClasses + c] = win_reduce([pr](long long j) { return pr + j * kClasses; }, j0, j1 - j0, c, reduce);
+        const float* pr = probs + p.woff[r] * N;
+        for (int c = threadIdx.x; c < N; c += 256)
+            out[row * N + c] = win_reduce([pr, N](long long j) { return pr + j * N; }, j0, j1 - j0, c, reduce);
     }
 }
 
@@ -115,13 +115,14 @@ int launch_window_table(const int64_t* lengths, int R, int64_t window, int64_t h
     return ACX_OK;
 }
 
-int launch_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce,
-                           float* out, hipStream_t s) {
+int launch_window_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                           int reduce, float* out, hipStream_t s) {
     long long rows = 0;
     for (int r = 0; r < R; ++r) rows += win_steps(lengths[r], hop);
     if (rows == 0) return ACX_OK;
     const unsigned blocks = (unsigned)(rows < 4096 ? rows : 4096);
-    launch_kernel(&window_timeline_kernel, dim3(blocks), dim3(256), 0, s, win_args(lengths, R, window, hop), probs, reduce, out);
+    launch_kernel(&window_timeline_kernel, dim3(blocks), dim3(256), 0, s, win_args(lengths, R, window, hop), probs, classes, reduce,
+                  out);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

@@ -91,15 +91,18 @@ class LogmelFilterBank(nn.Module):
 
 class ConvNeXt(nn.Module):
     """Drop-in for the reference `ConvNeXt` restricted to what its shipped entry points build:
-    ConvNeXt-Tiny, 527 classes, the [252,56] audio stem, 32 kHz / 1024 / 320 / 224-mel frontend."""
+    ConvNeXt-Tiny, the [252,56] audio stem, 32 kHz / 1024 / 320 / 224-mel frontend.  The classifier head
+    (`head_audioset`, convnext.py:257) may have any num_classes N in [1, 32768]: 527 for AudioSet, the task's label count for a
+    fine-tuned model; every (B, 527) output below is (B, N) then."""
 
     def __init__(self, in_chans=3, num_classes=1000, depths=[3, 3, 9, 3], dims=[96, 192, 384, 768],
                  drop_path_rate=0.0, use_pydub_augment=False, use_roll_augment=False, use_speed_perturb=False,
                  use_torchaudio=False, layer_scale_init_value=1e-6, head_init_scale=1.0):
         super().__init__()
-        if list(depths) != _TINY_DEPTHS or list(dims) != _TINY_DIMS or num_classes != 527:
-            raise NotImplementedError("the MI355X path implements ConvNeXt-Tiny / 527 classes (convnext_tiny()); "
-                                      "got depths=%r dims=%r num_classes=%r" % (depths, dims, num_classes))
+        if list(depths) != _TINY_DEPTHS or list(dims) != _TINY_DIMS:
+            raise NotImplementedError("the MI355X path implements ConvNeXt-Tiny (convnext_tiny()); "
+                                      "got depths=%r dims=%r" % (depths, dims))
+        check_num_classes(num_classes)
         if use_torchaudio:
             raise NotImplementedError("use_torchaudio=True (Kaldi fbank input) is outside the inference contract")
         if layer_scale_init_value <= 0:
@@ -259,17 +262,37 @@ class ConvNeXt(nn.Module):
         self.frontend = mode
         return self
 
+    @property
+    def num_classes(self):
+        """N, the width of the logits and probabilities: the classifier head's out_features (527 for AudioSet)."""
+        return self.head_audioset.out_features
+
+    def _check_head(self):
+        """A replaced head (`model.head_audioset = nn.Linear(768, N)`) must be a 768 -> N linear map with a bias."""
+        h = self.head_audioset
+        if not isinstance(h, nn.Linear) or h.in_features != _TINY_DIMS[-1]:
+            raise ValueError("head_audioset must be an nn.Linear(768, N) (got %r)" % (h,))
+        check_num_classes(h.out_features)
+        if h.bias is None:
+            raise ValueError("head_audioset.bias is missing: the classifier head needs a bias (nn.Linear(768, %d, bias=True), "
+                             "as the reference's head_audioset)" % h.out_features)
+        if tuple(h.weight.shape) != (h.out_features, h.in_features) or tuple(h.bias.shape) != (h.out_features,):
+            raise ValueError("head_audioset.weight %s / head_audioset.bias %s do not match nn.Linear(768, %d)"
+                             % (tuple(h.weight.shape), tuple(h.bias.shape), h.out_features))
+
     def native_context(self, device):
-        """The libacx context holding this module's weights on `device` (rebuilt when they change)."""
+        """The libacx context holding this module's weights on `device` (rebuilt when they change).  ctx.classes: N."""
         idx = device.index if device.index is not None else torch.cuda.current_device()
         sig = self._signature()
         hit = self._ctx.get(idx)
         if hit is not None and hit[1] == sig:
             return hit[0]
+        self._check_head()
         ctx = hit[0] if hit is not None else _ffi.Context(idx)
         ctx.set_precision(self.precision)
         ctx.set_frontend(self.frontend)
         ctx.load_state_dict(self.state_dict())
+        ctx.classes = ctx.num_classes()
         self._ctx[idx] = (ctx, sig)
         return ctx
 
@@ -319,8 +342,8 @@ class ConvNeXt(nn.Module):
             ctx = self.native_context(x.device)
             ws = self._workspace(x.device, ctx.workspace_bytes(B, L, mode))
             if mode == _ffi.MODE_LOGITS:
-                out0 = torch.empty((B, 527), dtype=torch.float32, device=x.device)
-                out1 = torch.empty((B, 527), dtype=torch.float32, device=x.device)
+                out0 = torch.empty((B, ctx.classes), dtype=torch.float32, device=x.device)
+                out1 = torch.empty((B, ctx.classes), dtype=torch.float32, device=x.device)
             elif mode == _ffi.MODE_SCENE:
                 out0, out1 = torch.empty((B, 768), dtype=torch.float32, device=x.device), None
             else:
@@ -348,8 +371,8 @@ class ConvNeXt(nn.Module):
             ctx = self.native_context(wav.device)
             ws = self._workspace(wav.device, ctx.workspace_bytes_varlen(lengths, mode))
             if mode == _ffi.MODE_LOGITS:
-                out0 = torch.empty((B, 527), dtype=torch.float32, device=wav.device)
-                out1 = torch.empty((B, 527), dtype=torch.float32, device=wav.device)
+                out0 = torch.empty((B, ctx.classes), dtype=torch.float32, device=wav.device)
+                out1 = torch.empty((B, ctx.classes), dtype=torch.float32, device=wav.device)
             elif mode == _ffi.MODE_SCENE:
                 out0, out1 = torch.empty((B, 768), dtype=torch.float32, device=wav.device), None
             else:
@@ -380,7 +403,7 @@ class ConvNeXt(nn.Module):
     def forward_varlen(self, clips, lengths=None, what="logits", sample_rate=None):
         """Clips of different lengths in one packed forward (acx_forward_varlen); every clip's result is bit-identical to the
         uniform forward of that clip alone.  clips: a list of 1-D CUDA tensors, or one packed 1-D CUDA tensor plus `lengths`.
-        what: "logits" -> {"clipwise_output", "clipwise_logits"} each (B, 527); "scene" -> (B, 768); "frame" -> a list of
+        what: "logits" -> {"clipwise_output", "clipwise_logits"} each (B, N); "scene" -> (B, 768); "frame" -> a list of
         (768, T'_i, 7) views into one output buffer.  More than 256 clips run as several calls.
         sample_rate: the clips' rate (lengths count input samples); other than None / 32000 they are resampled to 32 kHz on
         the device first (acx_resample), each clip's bits the same as model(clip[None], sample_rate=...)."""
@@ -454,8 +477,8 @@ class ConvNeXt(nn.Module):
         with torch.cuda.device(dev):
             ctx = self.native_context(dev)
             if mode == _ffi.MODE_LOGITS:
-                out0 = torch.empty((n, 527), dtype=torch.float32, device=dev)
-                out1 = torch.empty((n, 527), dtype=torch.float32, device=dev)
+                out0 = torch.empty((n, ctx.classes), dtype=torch.float32, device=dev)
+                out1 = torch.empty((n, ctx.classes), dtype=torch.float32, device=dev)
             elif mode == _ffi.MODE_SCENE:
                 out0, out1 = torch.empty((n, 768), dtype=torch.float32, device=dev), None
             else:
@@ -478,8 +501,8 @@ class ConvNeXt(nn.Module):
 
         recordings: one 1-D CUDA tensor (returns one dict) or a list of them (returns a list of dicts).  window / hop: seconds,
         whole numbers of samples at 32 kHz; hop=None means hop = window.  Each dict has "starts" (float64 CPU tensor, window
-        starts in seconds) and, by `what`: "logits" -> "clipwise_output" / "clipwise_logits" (n, 527) plus "timeline"
-        (ceil(L / hop), 527), the per-step mean or max of the probabilities over the windows covering the step's midpoint
+        starts in seconds) and, by `what`: "logits" -> "clipwise_output" / "clipwise_logits" (n, N) plus "timeline"
+        (ceil(L / hop), N), the per-step mean or max of the probabilities over the windows covering the step's midpoint
         (timeline="mean" | "max" | None); "scene" -> "scene" (n, 768); "frame" -> "frame" (n, 768, T', 7).  Recordings longer
         than the window run max_batch windows per call (acx_forward_windows); shorter ones are one window, the clip itself
         (forward_varlen).  sample_rate: the recordings' rate; they are resampled to 32 kHz on the device first (acx_resample)
@@ -550,12 +573,13 @@ class ConvNeXt(nn.Module):
             if what == "logits" and timeline is not None:
                 probs = torch.cat([per[i][1] for i in idx]).contiguous()
                 chunk = [lengths[i] for i in idx]
-                tl = torch.empty((len(_win.timeline_steps(chunk, W, H)), 527), dtype=torch.float32, device=wav.device)
+                n_cls = probs.shape[1]
+                tl = torch.empty((len(_win.timeline_steps(chunk, W, H)), n_cls), dtype=torch.float32, device=wav.device)
                 lens = (ctypes.c_int64 * len(chunk))(*chunk)
                 with torch.cuda.device(wav.device):
-                    _ffi.check(_ffi.lib().acx_window_timeline(_ffi.ptr(probs), lens, len(chunk), W, H,
-                                                              1 if timeline == "max" else 0, _ffi.ptr(tl),
-                                                              _ffi.stream_ptr(wav.device)))
+                    _ffi.check(_ffi.lib().acx_window_timeline_classes(_ffi.ptr(probs), n_cls, lens, len(chunk), W, H,
+                                                                      1 if timeline == "max" else 0, _ffi.ptr(tl),
+                                                                      _ffi.stream_ptr(wav.device)))
             t0 = 0
             for i in idx:
                 starts = _win.window_starts([lengths[i]], W, H)
@@ -588,7 +612,7 @@ class ConvNeXt(nn.Module):
     # on x's stream first (acx_resample, the interpolation of torchaudio.functional.resample that the reference's demo runs on
     # the host, demo_convnext.py:53-59); the result equals the forward of pytorch.resample.resample(x, sample_rate) bit for bit.
     def forward(self, x, mixup_lambda=None, sample_rate=None):
-        """(B, L) waveform -> {"clipwise_output": probs, "clipwise_logits": logits} (convnext.py:287-331)."""
+        """(B, L) waveform -> {"clipwise_output": probs, "clipwise_logits": logits}, each (B, N) (convnext.py:287-331)."""
         logits, probs = self._run(self._resampled(x, sample_rate), _ffi.MODE_LOGITS)
         return {"clipwise_output": probs, "clipwise_logits": logits}
 
@@ -604,7 +628,8 @@ class ConvNeXt(nn.Module):
     def from_pretrained(cls, pretrained_checkpoint_path, map_location=None, use_auth_token=None):
         """Local file first, then a Zenodo URL, then a Hugging Face model id[@revision]
         (convnext.py:404-511).  Accepts both `model.safetensors` and the `.pth` ({"model": sd}) form that
-        evaluate_convnext_on_audioset.py:36-38 loads.  Returns None when the HF repo does not exist."""
+        evaluate_convnext_on_audioset.py:36-38 loads; the head is sized from the checkpoint's `head_audioset.weight` (527 rows
+        for AudioSet, N for a fine-tuned model).  Returns None when the HF repo does not exist."""
         if os.path.isfile(pretrained_checkpoint_path):
             print("Ckpt already on local disk")
             path_ = pretrained_checkpoint_path
@@ -650,15 +675,42 @@ def varlen_frame_layout(lengths):
     return offs
 
 
+def check_num_classes(n):
+    """The class counts a classifier head may have: 1 .. 32768 (ACX_MAX_CLASSES)."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= _ffi.MAX_CLASSES:
+        raise ValueError("num_classes must be an integer in [1, %d] (got %r)" % (_ffi.MAX_CLASSES, n))
+    return n
+
+
+def _size_head(model, shape):
+    """Give `model` a fresh nn.Linear(768, N) head when the checkpoint's head_audioset.weight has N rows and the model's has not
+    (a fine-tuned checkpoint); its values come from the checkpoint right after."""
+    if shape is None or len(shape) != 2:
+        return
+    n = int(shape[0])
+    if n != model.head_audioset.out_features:
+        check_num_classes(n)
+        dev = model.head_audioset.weight.device
+        model.head_audioset = nn.Linear(int(shape[1]), n).to(dev)
+
+
 def load_checkpoint(model, path, map_location="cpu"):
     """`.safetensors` via safetensors.torch.load_model (strict, convnext.py:507); anything else as a torch
-    checkpoint holding {"model": state_dict} (evaluate_convnext_on_audioset.py:36-38)."""
+    checkpoint holding {"model": state_dict} (evaluate_convnext_on_audioset.py:36-38).  The head is sized from the
+    checkpoint's `head_audioset.weight`: a 527-row checkpoint loads as before, an N-row one gives an N-class model."""
     if str(path).endswith(".safetensors"):
+        from safetensors import safe_open
         from safetensors.torch import load_model as st_load_model
+        with safe_open(str(path), framework="pt") as f:
+            if "head_audioset.weight" in f.keys():
+                _size_head(model, f.get_slice("head_audioset.weight").get_shape())
         st_load_model(model, path)
     else:
         ckpt = torch.load(path, map_location=map_location)
-        model.load_state_dict(ckpt["model"] if "model" in ckpt else ckpt)
+        sd = ckpt["model"] if "model" in ckpt else ckpt
+        w = sd.get("head_audioset.weight")
+        _size_head(model, None if w is None else tuple(w.shape))
+        model.load_state_dict(sd)
     return model
 
 

@@ -400,7 +400,9 @@ def evaluate_sharded(model, shard, batch_size=256, metrics="sklearn"):
         n_local = torch.tensor([0 if scores is None else scores.shape[0]], device=device)
         counts = [torch.zeros_like(n_local) for _ in range(world)]
         dist.all_gather(counts, n_local)
-        classes = 527
+        # from the model's head, not from the outputs: a rank with no batches has none (a scorer without one: AudioSet's 527)
+        head = getattr(model, "head_audioset", None)
+        classes = head.out_features if head is not None else 527
         s_all = torch.empty((world * per_rank, classes), device=device)
         t_all = torch.empty((world * per_rank, classes), device=device)
         dist.all_gather_into_tensor(s_all, pad(scores if scores is not None else np.zeros((0, classes), np.float32)))

@@ -87,7 +87,8 @@ def _extract_packed(model, waveforms, what, max_batch, max_samples, rate=None):
 @torch.no_grad()
 def extract(model, waveforms, what="logits", max_batch=64, pack=False, max_samples=64 * 320000, sample_rate=None):
     """waveforms: list of 1-D float tensors/arrays of arbitrary lengths (>= 7360 samples).
-    what: 'logits' -> (527,), 'scene' -> (768,), 'frame' -> (768, T', 7) per clip.  Returns a list (CPU tensors, input order).
+    what: 'logits' -> (N,) (the head's classes, 527 for AudioSet), 'scene' -> (768,), 'frame' -> (768, T', 7) per clip.
+    Returns a list (CPU tensors, input order).
 
     The host side is kept off the critical path (with one clip per launch a forward is ~1.5 ms; torch.stack on a many-core host,
     a pageable copy and a synchronising .cpu() per clip cost ten times that): chunks run largest first, so the model's workspace

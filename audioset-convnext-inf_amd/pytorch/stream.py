@@ -58,6 +58,7 @@ class Stream:
             _ffi.check(_ffi.lib().acx_stream_create(ctx.handle, slots, self.window, self.hop, self.rate, self.max_push,
                                                     1 if self.timeline else 0, ctypes.byref(h)))
         self._h = h
+        self.classes = ctx.classes  # N of the model's head at create: the handle's rows are this wide
         self._pushed = {}           # slot -> input samples of its open recording
         self._last = None           # the torch stream of the previous call
 
@@ -177,8 +178,8 @@ class Stream:
                 ctx = self.model.native_context(dev)
                 ws = self.model._workspace(dev, ctx.workspace_bytes_windows(n, L, mode))
                 if mode == _ffi.MODE_LOGITS:
-                    o0 = torch.empty((n, 527), dtype=torch.float32, device=dev)
-                    o1 = torch.empty((n, 527), dtype=torch.float32, device=dev)
+                    o0 = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
+                    o1 = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
                 elif mode == _ffi.MODE_SCENE:
                     o0, o1 = torch.empty((n, 768), dtype=torch.float32, device=dev), None
                 else:
@@ -191,7 +192,7 @@ class Stream:
                 _ffi.check(lib.acx_stream_pending(self._h, None, ctypes.byref(rows)))
                 r = rows.value
                 if r:
-                    tl = torch.empty((r, 527), dtype=torch.float32, device=dev)
+                    tl = torch.empty((r, self.classes), dtype=torch.float32, device=dev)
                     ts, tk, got = (ctypes.c_int * r)(), (ctypes.c_int64 * r)(), ctypes.c_int64()
                     _ffi.check(lib.acx_stream_timeline(self._h, 1 if self.timeline == "max" else 0, r, _ffi.ptr(tl), ts, tk,
                                                        ctypes.byref(got), _ffi.stream_ptr(dev)))
@@ -239,8 +240,8 @@ class _Result:
             return t if order is None else t[torch.tensor(order, device=dev)]
 
         if st.what == "logits":
-            d["clipwise_logits"] = rows(self.o0, (0, 527))
-            d["clipwise_output"] = rows(self.o1, (0, 527))
+            d["clipwise_logits"] = rows(self.o0, (0, st.classes))
+            d["clipwise_output"] = rows(self.o1, (0, st.classes))
         elif st.what == "scene":
             d["scene"] = rows(self.o0, (0, 768))
         else:
@@ -252,7 +253,7 @@ class _Result:
                 d["frame"] = [each[i] for i in order] if order else each
         if st.timeline:
             torder = self._order(list(zip(self.tslot, self.tstep)))
-            tl = torch.empty((0, 527), dtype=torch.float32, device=dev) if not self.tl else (
+            tl = torch.empty((0, st.classes), dtype=torch.float32, device=dev) if not self.tl else (
                 self.tl[0] if len(self.tl) == 1 else torch.cat(self.tl))
             if torder is not None:
                 tl = tl[torch.tensor(torder, device=dev)]

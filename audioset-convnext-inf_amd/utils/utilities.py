@@ -37,6 +37,20 @@ def default_label_map():
             {mid: i for i, mid in enumerate(ids)}, {i: mid for i, mid in enumerate(ids)})
 
 
+def label_names_for(num_classes, labels_path=None):
+    """The class names to print for a model with num_classes outputs: (ix_to_lb, None) when the label table has exactly that
+    many rows, else (None, reason) -- a fine-tuned head's classes are not AudioSet's, and the caller prints class indices.
+    labels_path: the reference's CSV (index,mid,display_name); missing or None -> the packaged AudioSet table."""
+    if labels_path and os.path.isfile(labels_path):
+        ix_to_lb, src = read_audioset_label_tags(labels_path)[1], labels_path
+    else:
+        ix_to_lb, src = default_label_map()[1], "the packaged AudioSet label table"
+    if len(ix_to_lb) != num_classes:
+        return None, ("%s has %d classes but the model has %d: printing class indices instead of names"
+                      % (src, len(ix_to_lb), num_classes))
+    return ix_to_lb, None
+
+
 def float32_to_int16(x):
     return (np.clip(x, -1, 1) * 32767.0).astype(np.int16)
 

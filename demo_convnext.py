@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from audioset_convnext_inf_amd.pytorch.convnext import ConvNeXt, convnext_tiny      # noqa: E402
-from audioset_convnext_inf_amd.utils.utilities import default_label_map, read_audioset_label_tags, read_wav_pcm16, prepare_clip  # noqa: E402
+from audioset_convnext_inf_amd.utils.utilities import label_names_for, read_wav_pcm16, prepare_clip  # noqa: E402
 
 
 def main():
@@ -71,10 +71,13 @@ def main():
     print("Predicted labels using activity threshold %.2f:\n" % args.threshold)
     print(sample_labels)
     # the reference reads metadata/class_labels_indices.csv (demo_convnext.py:29, utilities.py:195-216); without that file the
-    # packaged copy of the same table names the classes
-    _, ix_to_lb, _, _ = read_audioset_label_tags(args.labels) if os.path.isfile(args.labels) else default_label_map()
+    # packaged copy of the same table names the classes.  A fine-tuned head (N != 527 classes) prints indices unless the table
+    # has N rows.
+    ix_to_lb, why = label_names_for(probs.shape[1], args.labels)
+    if why:
+        print(why)
     for l in sample_labels:
-        print("%s: %.3f" % (ix_to_lb[l], probs[0, l]))
+        print("%s: %.3f" % (ix_to_lb[l] if ix_to_lb else "class %d" % l, probs[0, l]))
 
     with torch.no_grad():
         scene = model.forward_scene_embeddings(waveform)

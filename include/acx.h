@@ -83,7 +83,8 @@ enum acx_kernel_class {
 };
 
 #define ACX_MIN_SAMPLES 7360  /* shortest clip the reference accepts (last 2x2 downsample needs H>=2) */
-#define ACX_NUM_CLASSES 527   /* convnext.py:654 */
+#define ACX_NUM_CLASSES 527   /* convnext.py:654: the AudioSet head */
+#define ACX_MAX_CLASSES 32768 /* widest classifier head a context takes (convnext.py:145-158, num_classes) */
 #define ACX_EMBED_DIM 768     /* convnext.py:656 */
 #define ACX_MAX_VARLEN_CLIPS 256  /* clips per acx_forward_varlen call */
 
@@ -98,9 +99,19 @@ ACX_API void acx_destroy(acx_ctx* ctx);
 /* Weights enter under the reference's own state_dict keys (the 190-key contract of
  * `load_state_dict` / `safetensors.torch.load_model`, convnext.py:507,
  * evaluate_convnext_on_audioset.py:36-38).  `host_data` is fp32, C-contiguous, HOST memory,
- * borrowed for the duration of the call.  `bn0.num_batches_tracked` (int64) is not needed. */
+ * borrowed for the duration of the call.  `bn0.num_batches_tracked` (int64) is not needed.
+ * Classifier heads of any size (a fine-tuned `head_audioset = nn.Linear(768, N)`, convnext.py:257): `head_audioset.weight`
+ * is (N, 768) and `head_audioset.bias` (N,) with 1 <= N <= ACX_MAX_CLASSES; every other key has its fixed shape.  The
+ * context's class count N is the row count of the head it was finalized with (acx_finalize fails with ACX_ERR_SHAPE, naming
+ * both keys, when weight and bias disagree).  Every output that is 527 wide with the AudioSet head is N wide: "(B, N)" below.
+ * A class's logit depends only on the clip's scene embedding and that head row -- not on N, on the row's position, on the
+ * batch or on which head kernel computed it -- bit for bit. */
 ACX_API int acx_set_weight(acx_ctx* ctx, const char* state_dict_key, const float* host_data,
                    const int64_t* shape, int ndim);
+
+/* *n = N, the class count of the finalized weights (ACX_NUM_CLASSES for the AudioSet head); ACX_ERR_STATE before
+ * acx_finalize. */
+ACX_API int acx_num_classes(const acx_ctx* ctx, int* n);
 
 /* Folds and repacks for the kernels, uploads to the device:
  *   bn0 -> per-mel scale/shift (convnext.py:304-306); melW -> banded form (any matrix: a band may span all 513 bins);
@@ -123,6 +134,9 @@ ACX_API int acx_set_precision(acx_ctx* ctx, int precision);
 ACX_API int acx_num_frames(int64_t L, int* T);
 ACX_API int acx_stage_hw(int64_t L, int stage, int* H, int* W);
 
+/* Workspace of acx_forward.  It does not depend on N: the wide-head path keeps its scene rows in the frontend's feature
+ * buffer, which is idle once the stem has run and holds at least 24 x 224 floats per clip ("Classifier heads of
+ * any size"). */
 ACX_API int acx_workspace_bytes(const acx_ctx* ctx, int B, int64_t L, int mode, size_t* out_bytes);
 
 /* How acx_forward runs a batch of B clips: as *out sub-batches side by side on separate streams (clips are independent in
@@ -134,7 +148,7 @@ ACX_API int acx_workspace_bytes(const acx_ctx* ctx, int B, int64_t L, int mode, 
 ACX_API int acx_sub_batches(const acx_ctx* ctx, int B, int* out);
 
 /* The hot path.  wav: device (B, L) fp32.
- *   ACX_MODE_LOGITS: out0 = logits (B,527), out1 = probs (B,527)   [dict keys
+ *   ACX_MODE_LOGITS: out0 = logits (B,N), out1 = probs (B,N)   [dict keys
  *                    "clipwise_logits" / "clipwise_output", convnext.py:329]
  *   ACX_MODE_SCENE : out0 = (B,768), out1 ignored
  *   ACX_MODE_FRAME : out0 = NCHW (B,768,H3,7), out1 ignored */
@@ -166,10 +180,11 @@ ACX_API int acx_forward_varlen(acx_ctx* ctx, const float* wav, const int64_t* le
  *   Every L_r must be >= window (a shorter recording is one clip: ACX_ERR_SHAPE, run it through acx_forward_varlen).
  *   acx_forward's launch contract: lengths by value, no allocation or synchronisation, capturable, the same sub-batch split;
  *   the window table (count absolute sample offsets) is written into the head of the workspace on `stream` first.
- *   acx_window_timeline: probs = the (sum n_r, 527) probabilities of ALL windows of the R recordings, in window order; out =
- *   sum_r ceil(L_r / hop) rows of 527.  Row k of recording r has the midpoint m_k = min(k hop + hop / 2, L_r - 1) (integer
- *   division) and reduces over the windows with s_j <= m_k < s_j + window: reduce 0 = mean (an fp32 sum in ascending j, then
- *   one fp32 division by their count), 1 = max.  One kernel on `stream`, no allocation, capturable. */
+ *   acx_window_timeline_classes: probs = the (sum n_r, classes) probabilities of ALL windows of the R recordings, in window
+ *   order (1 <= classes <= ACX_MAX_CLASSES: an N-class model's rows); out = sum_r ceil(L_r / hop) rows of `classes`.  Row k of
+ *   recording r has the midpoint m_k = min(k hop + hop / 2, L_r - 1) (integer division) and reduces over the windows with
+ *   s_j <= m_k < s_j + window: reduce 0 = mean (an fp32 sum in ascending j, then one fp32 division by their count), 1 = max.
+ *   One kernel on `stream`, no allocation, capturable.  acx_window_timeline: the same with classes = 527 (the AudioSet head). */
 ACX_API int acx_window_count(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t* n_windows);
 ACX_API int acx_workspace_bytes_windows(const acx_ctx* ctx, int count, int64_t window, int mode, size_t* out_bytes);
 ACX_API int acx_forward_windows(acx_ctx* ctx, const float* wav, const int64_t* lengths, int R, int64_t window, int64_t hop,
@@ -177,6 +192,8 @@ ACX_API int acx_forward_windows(acx_ctx* ctx, const float* wav, const int64_t* l
                                 size_t workspace_bytes, void* stream);
 ACX_API int acx_window_timeline(const float* probs, const int64_t* lengths, int R, int64_t window, int64_t hop,
                                 int reduce /* 0 mean, 1 max */, float* out, void* stream);
+ACX_API int acx_window_timeline_classes(const float* probs, int classes, const int64_t* lengths, int R, int64_t window,
+                                        int64_t hop, int reduce, float* out, void* stream);
 
 /* ---- live streams: tagging recordings that arrive chunk by chunk ----------------------------------------------------------
  * No reference counterpart.  A handle has `slots`; each slot holds one recording at a time.  Samples pushed to a slot are
@@ -197,9 +214,12 @@ ACX_API int acx_window_timeline(const float* probs, const int64_t* lengths, int 
  *   acx_stream_schedule: *samples = R, *windows / *rows = the windows / rows emitted so far by a recording with `pushed` input
  *   samples, open (closed = 0) or closed (closed = 1).  Any output pointer may be NULL.
  *
- * acx_stream_create: allocates the device state on ctx's device and synchronises (call it outside any capture): per slot a
+ * acx_stream_create: needs a finalized ctx; allocates the device state on ctx's device and synchronises (call it outside any
+ * capture): per slot a
  * 32 kHz ring of 2 (W + the largest 32 kHz advance of one push) samples, an input history when orig_hz != 32000, and with
- * timeline = 1 the probabilities of about (W + max_push) / H + 4 windows.  max_push: the longest chunk, in input samples.
+ * timeline = 1 the probabilities of about (W + max_push) / H + 4 windows, N floats each (N: the context's class count at
+ * create).  max_push: the longest chunk, in input samples.  If the context is finalized again with a different N, the
+ * handle's acx_stream_forward and acx_stream_timeline return ACX_ERR_STATE and write nothing.
  * Every other call allocates nothing and synchronises nothing; the launch calls run on `stream`, which must keep the handle's
  * work in order (one stream, or an event between two).  Slots, lengths and positions go to the kernels BY VALUE.
  *   acx_stream_push: n (1 .. ACX_MAX_VARLEN_CLIPS) chunks back to back in `chunks` (device fp32), chunk k of lengths[k]
@@ -215,7 +235,7 @@ ACX_API int acx_window_timeline(const float* probs, const int64_t* lengths, int 
  *   outputs as acx_forward with B = count, L = length; workspace: acx_workspace_bytes_windows(ctx, count, length, mode).  With
  *   a timeline the mode must be ACX_MODE_LOGITS, and the probabilities are also kept for the rows.
  *   acx_stream_timeline: the pending rows (at most max_rows) of slots whose windows are all forwarded, in slot order and then
- *   step order: out = (rows, 527) device fp32, slot_of / step_of host arrays, *n_rows their number.  reduce 0 = mean, 1 = max,
+ *   step order: out = (rows, N) device fp32, slot_of / step_of host arrays, *n_rows their number.  reduce 0 = mean, 1 = max,
  *   the reduction of acx_window_timeline. */
 typedef struct acx_stream acx_stream;
 ACX_API int acx_stream_schedule(int64_t window, int64_t hop, int orig_hz, int64_t pushed, int closed, int64_t* samples,
@@ -317,7 +337,8 @@ ACX_API int acx_block_scratch_bytes(int stage, int B, int H, int W, size_t* out_
 ACX_API int acx_downsample(acx_ctx* ctx, int i, const float* x, float* out, float* scratch, int B, int H,
                    int W, void* stream);
 /* K6: pooling + final LayerNorm + head + sigmoid (convnext.py:279-285,321-325).
- * x NHWC (B,H3,7,768). Any of scene/logits/probs may be NULL. */
+ * x NHWC (B,H3,7,768); scene (B,768), logits / probs (B,N). Any of scene/logits/probs may be NULL.  Always the fused
+ * one-workgroup-per-clip kernel (the forwards take the class-tiled head kernel for wide heads; both give the same bits). */
 ACX_API int acx_pool_head(acx_ctx* ctx, const float* x, int B, int H3, float* scene, float* logits,
                   float* probs, void* stream);
 /* NHWC -> NCHW (the layout forward_frame_embeddings returns, convnext.py:276-277). */
@@ -378,7 +399,8 @@ ACX_API int acx_set_frontend(acx_ctx* ctx, int mode);
  * dense matrix, which is applied as it is).  Any pointer may be NULL. */
 ACX_API int acx_frontend_info(const acx_ctx* ctx, int* dense_dft, float* stft_deviation, int* mel_taps);
 
-/* Diagnostics.  The tile-shape A/B switches ACX_GEMM_MI, ACX_WIDE_NPB, ACX_WIDE_PERSIST, ACX_DW_STREAM and ACX_DWM_WAVES are read from the
+/* Diagnostics.  The tile-shape A/B switches ACX_GEMM_MI, ACX_WIDE_NPB, ACX_WIDE_PERSIST, ACX_DW_STREAM and ACX_DWM_WAVES, and
+ * ACX_HEAD_PATH (1: the fused head kernel, 2: the class-tiled one, whatever N), are read from the
  * environment once, at the first acx_create; this re-reads them (tests force every tile shape through it and require
  * bit-identical results).  Launches never touch the environment.  No reference counterpart. */
 ACX_API int acx_tuning_refresh(void);
