@@ -23,6 +23,16 @@ MAX_CLASSES = 32768        # widest classifier head a context takes (ACX_MAX_CLA
 _c_int, _c_i64, _c_sz, _vp = ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_void_p
 _pint = ctypes.POINTER(ctypes.c_int)
 
+
+
+class AcxAdam(ctypes.Structure):
+    """struct acx_adam: the optimiser settings of acx_head_fit_step / acx_adam_update."""
+    _fields_ = [("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("amsgrad", ctypes.c_int), ("decoupled", ctypes.c_int)]
+
+
+_padam, _c_dbl = ctypes.POINTER(AcxAdam), ctypes.c_double
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -78,6 +88,12 @@ SIGNATURES = {
     "acx_resample": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _vp, _vp]),
     "acx_metrics_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_tagging_metrics": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_head_fit_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_head_fit_step": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _padam, _c_i64, _c_dbl, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_head_fit_grad": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _c_sz, _vp]),
+    "acx_adam_update": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _padam, _c_i64, _c_dbl, _vp]),
     "acx_frontend_info": (_c_int, [_vp, _pint, ctypes.POINTER(ctypes.c_float), _pint]),
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
@@ -316,6 +332,21 @@ def tagging_metrics(scores, ld_scores, target, target_dtype, ld_target, n, class
     """acx_tagging_metrics on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
     check(lib().acx_tagging_metrics(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes), ap,
                                     auc, dprime, status, ws[0], int(ws[1]), stream))
+
+
+FIT_BAD_INDEX = 1                              # bit of the status word of acx_head_fit_step / acx_head_fit_grad
+
+
+def adam(beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, amsgrad=True, decoupled=False):
+    """An acx_adam struct (the defaults are the reference's fine-tuning settings)."""
+    return AcxAdam(float(beta1), float(beta2), float(eps), float(weight_decay), 1 if amsgrad else 0, 1 if decoupled else 0)
+
+
+def head_fit_workspace_bytes(rows_max, classes):
+    """Workspace of acx_head_fit_step / acx_head_fit_grad for steps of up to rows_max rows (host only)."""
+    out = _c_sz()
+    check(lib().acx_head_fit_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
+    return out.value
 
 
 def stage_hw(L, stage):

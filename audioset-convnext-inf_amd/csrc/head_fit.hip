@@ -1,0 +1,461 @@
+// Training a classifier head on frozen scene embeddings (acx_head_fit_step / acx_head_fit_grad / acx_adam_update, include/acx.h):
+// what the reference's fine-tuning loop does to `head_audioset` with the base frozen (pytorch/finetune_audiocaps.py: BCELoss on
+// clipwise_output, optim.Adam(amsgrad=True); pytorch/main.py:648 uses AdamW the same way), without autograd and without the
+// backbone: the head reads norm(pool(x)) (convnext.py:285,321), which never changes while the backbone is frozen.
+//
+// One optimisation step on a mini-batch of `rows` embeddings E[idx[r]] (K = 768) for a head of N classes is two launches:
+//   fit_grad_kernel   tiles of S rows x S classes: z = E[idx] W^T + b, p = sigmoid(z), G = (p - y) / (rows N) -> workspace,
+//                     and the tile's partial of the loss  -[y max(log p, -100) + (1 - y) max(log(1 - p), -100)]
+//                     (torch's binary_cross_entropy with its -100 clamp; the mean's 1 / (rows N) is applied once, to the sum).
+//   fit_update_kernel tiles of S classes x S of the 768 inputs: dW = G^T E[idx] over K = rows.  Every element of dW has exactly
+//                     one owner thread, which applies Adam / AdamW to W, m, v, vmax in place: dW never goes to memory.  The
+//                     blocks behind the tiles reduce db = sum_rows G (64 classes each) and update b; the last block adds the
+//                     loss partials in index order and writes the step's loss.  Stream order keeps these writes of W behind
+//                     the gradient kernel's reads.
+// The batch rows are gathered through idx in both kernels: no shuffled copy of the data set exists.
+//
+// Arithmetic: fp32 products, fp32 accumulation on the f32-input matrix cores (v_mfma_f32_32x32x2_f32 when the launch has
+// at least one 32 x 32 tile per CU, v_mfma_f32_16x16x4_f32 otherwise, so that a 50-class head with 64 rows still spreads over
+// 16 + 192 workgroups) -- bit-equal to an fmaf chain.  The four waves of a workgroup split the contraction (K = 768 or the rows)
+// four ways and their partial tiles are added in wave order through LDS; nothing is accumulated with atomics, so the same
+// inputs give the same bits on every run.  model.set_precision() has no influence here: training state is fp32.
+//
+// The gradient of the logits is the exact (sigmoid(z) - y) / (rows N) -- the BCEWithLogitsLoss form.  The reference's
+// sigmoid-then-BCELoss product form equals it except where the fp32 sigmoid saturates (|z| >~ 16.6: p rounds to 0 or 1,
+// log(1 - p) hits the clamp and autograd returns 0 for that logit); this kernel keeps the exact gradient there.
+//
+// Optimiser: torch.optim.Adam / AdamW, single-tensor form, step t = 1, 2, ...:
+//   g <- g + wd p (Adam)  or  p <- p (1 - lr wd) (AdamW);  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2;
+//   amsgrad: vmax <- max(vmax, v), used for v below;  p <- p - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// eps sits outside the root, after the bias correction.  What depends only on the hyper-parameters and t is evaluated on the
+// host in double and rounded to fp32 once (adam_scalars); the decay and the step are applied to p in ONE fused multiply-add.
+#include <cmath>
+
+#include "acx_internal.h"
+
+namespace acx {
+
+typedef float fit_f32x16 __attribute__((ext_vector_type(16)));
+typedef float fit_f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kFitK = 768;                        // inputs of the head (convnext.py:656, dims[-1])
+constexpr int kFitThreads = 256;                  // four waves: the contraction is split four ways
+constexpr int kFitDbCols = 64;                    // classes per db block
+constexpr long long kFitMaxRows = 1LL << 22;
+
+struct AdamK {          // fp32 roundings of the host's double evaluations
+    float beta1, omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt;
+    int amsgrad;
+};
+
+// One element of the update.  Contraction is off and the fused operations are spelled out: the fused step and
+// acx_adam_update run this function in different kernels and must produce the same bits.
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float* vmax, const AdamK& a) {
+#pragma clang fp contract(off)
+    const float p0 = p;
+    g = __builtin_fmaf(a.wd, p0, g);                              // Adam: wd p added to the gradient (a.wd = 0 for AdamW)
+    const float mn = __builtin_fmaf(a.beta1, m, a.omb1 * g);
+    const float vn = __builtin_fmaf(a.beta2, v, a.omb2 * (g * g));
+    float vv = vn;
+    if (a.amsgrad) {
+        vv = fmaxf(*vmax, vn);
+        *vmax = vv;
+    }
+    const float denom = sqrtf(vv) / a.bc2_sqrt + a.eps;
+    const float upd = a.step_size * (mn / denom);
+    m = mn;
+    v = vn;
+    p = __builtin_fmaf(p0, a.decay, -upd);                        // AdamW: decay = 1 - lr wd; Adam: 1
+}
+
+template <int S> struct FitTile;
+template <> struct FitTile<32> {
+    typedef fit_f32x16 acc_t;
+    static constexpr int NACC = 1, REGS = 16;
+    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+};
+template <> struct FitTile<16> {
+    typedef fit_f32x4 acc_t;
+    static constexpr int NACC = 2, REGS = 4;       // two accumulators: the dependent latency (40) exceeds the issue interval (32)
+    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int i, int h) { return 4 * h + i; }
+};
+
+// the wave's S x S partial tile -> red[wave][row * S + col] (the lanes hold the columns: conflict-free)
+template <int S>
+__device__ __forceinline__ void fit_spill(const typename FitTile<S>::acc_t* acc, float* red, int lane) {
+    using T = FitTile<S>;
+    const int r = lane % S, h = lane / S;
+#pragma unroll
+    for (int i = 0; i < T::REGS; ++i) {
+        float v = acc[0][i];
+        if (T::NACC == 2) v += acc[T::NACC - 1][i];
+        red[T::row(i, h) * S + r] = v;
+    }
+}
+
+struct FitGradP {
+    const float* E; long long ld_e; long long n_total;
+    const void* Y; int y_u8; long long ld_y;
+    const long long* idx; int rows; int N;
+    const float* W; const float* b;
+    float* z;            // optional (rows, N)
+    float* G;            // (rows, N)
+    float* part;         // [gridDim.x] loss partials
+    int* status; float inv; int tiles_n;
+};
+
+template <int S>
+__global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) {
+    using T = FitTile<S>;
+    constexpr int KB = (64 / S) * 4;               // k per block of four MFMAs: lane group h holds k = 4 h .. 4 h + 3
+    constexpr int KW = kFitK / 4;                  // k per wave
+    __shared__ float red[4][S * S];
+    __shared__ long long s_idx[S];
+    __shared__ float s_loss[4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane % S, h = lane / S;
+    const int tile_c = blockIdx.x % p.tiles_n, tile_r = blockIdx.x / p.tiles_n;
+    const int row0 = tile_r * S, c0 = tile_c * S;
+
+    // rows past the batch and classes past N repeat the last valid one: loads stay inside the buffers, results are dropped
+    long long src = p.idx[min(row0 + r, p.rows - 1)];
+    const bool bad = src < 0 || src >= p.n_total;
+    src = src < 0 ? 0 : src >= p.n_total ? p.n_total - 1 : src;
+    if (wave == 0 && h == 0) {
+        s_idx[r] = src;
+        if (__ballot(bad) && lane == 0) atomicOr(p.status, ACX_FIT_BAD_INDEX);
+    }
+    const float* ea = p.E + src * p.ld_e + wave * KW + 4 * h;
+    const float* wb = p.W + (long long)min(c0 + r, p.N - 1) * kFitK + wave * KW + 4 * h;
+
+    typename T::acc_t acc[T::NACC];
+#pragma unroll
+    for (int a = 0; a < T::NACC; ++a)
+#pragma unroll
+        for (int i = 0; i < T::REGS; ++i) acc[a][i] = 0.f;
+#pragma unroll 4
+    for (int kb = 0; kb < KW / KB; ++kb) {
+        const float4 av = *reinterpret_cast<const float4*>(ea + kb * KB);
+        const float4 bv = *reinterpret_cast<const float4*>(wb + kb * KB);
+        acc[0] = T::mfma(av.x, bv.x, acc[0]);
+        acc[T::NACC - 1] = T::mfma(av.y, bv.y, acc[T::NACC - 1]);
+        acc[0] = T::mfma(av.z, bv.z, acc[0]);
+        acc[T::NACC - 1] = T::mfma(av.w, bv.w, acc[T::NACC - 1]);
+    }
+    fit_spill<S>(acc, red[wave], lane);
+    __syncthreads();
+
+    float lsum = 0.f;
+#pragma unroll
+    for (int q = 0; q < S * S / kFitThreads; ++q) {
+        const int e = tid + kFitThreads * q;
+        const int rr = e / S, cc = e % S;
+        const int row = row0 + rr, c = c0 + cc;
+        if (row < p.rows && c < p.N) {
+            const float zz = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e] + p.b[c];
+            const long long yo = s_idx[rr] * p.ld_y + c;
+            const float y = p.y_u8 ? (static_cast<const unsigned char*>(p.Y)[yo] ? 1.f : 0.f) : static_cast<const float*>(p.Y)[yo];
+            // sigmoid and both logarithms from e = exp(-|z|): log p = min(z, 0) - log1p(e), log(1 - p) = min(-z, 0) - log1p(e)
+            const float ex = expf(-fabsf(zz));
+            const float den = 1.f + ex;
+            const float pr = (zz >= 0.f ? 1.f : ex) / den;
+            const float l1 = log1pf(ex);
+            const float lp = fmaxf(fminf(zz, 0.f) - l1, -100.f), lq = fmaxf(fminf(-zz, 0.f) - l1, -100.f);
+            lsum -= y * lp + (1.f - y) * lq;
+            const long long o = (long long)row * p.N + c;
+            p.G[o] = (pr - y) * p.inv;
+            if (p.z) p.z[o] = zz;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) lsum += __shfl_xor(lsum, off);
+    if (lane == 0) s_loss[wave] = lsum;
+    __syncthreads();
+    if (tid == 0) p.part[blockIdx.x] = ((s_loss[0] + s_loss[1]) + s_loss[2]) + s_loss[3];
+}
+
+struct FitUpdP {
+    const float* E; long long ld_e; long long n_total;
+    const long long* idx; int rows; int N;
+    const float* G;
+    float *W, *mW, *vW, *vmaxW;        // APPLY
+    float *b, *mb, *vb, *vmaxb;
+    float *dW, *db;                    // !APPLY
+    const float* part; int nparts; float* loss; float inv;
+    AdamK a;
+    int tiles;                         // ceil(N / S) * (768 / S); then ceil(N / 64) db blocks; then the loss block
+};
+
+template <int S, bool APPLY>
+__global__ __launch_bounds__(kFitThreads) void fit_update_kernel(FitUpdP p) {
+    using T = FitTile<S>;
+    constexpr int KB = (64 / S) * 4;               // batch rows per block of four MFMAs
+    constexpr int TK = kFitK / S;
+    __shared__ float red[4][S * S];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bid = blockIdx.x;
+
+    if (bid < p.tiles) {
+        const int r = lane % S, h = lane / S;
+        const int c0 = (bid / TK) * S, k0 = (bid % TK) * S;
+        const float* gcol = p.G + min(c0 + r, p.N - 1);       // A[m = class][k = row] = G[row][class]
+        const float* ecol = p.E + k0 + r;                     // B[k = row][n = input] = E[idx[row]][input]
+        const int nblk = (p.rows + KB - 1) / KB, per = (nblk + 3) / 4;
+        const int b_lo = wave * per, b_hi = min(nblk, b_lo + per);
+        typename T::acc_t acc[T::NACC];
+#pragma unroll
+        for (int a = 0; a < T::NACC; ++a)
+#pragma unroll
+            for (int i = 0; i < T::REGS; ++i) acc[a][i] = 0.f;
+        for (int blk = b_lo; blk < b_hi; ++blk) {
+            float gv[4], ev[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int row = blk * KB + 4 * h + j;
+                const bool in = row < p.rows;
+                long long src = p.idx[in ? row : p.rows - 1];
+                src = src < 0 ? 0 : src >= p.n_total ? p.n_total - 1 : src;
+                const float g = gcol[(long long)(in ? row : p.rows - 1) * p.N];
+                const float e = ecol[src * p.ld_e];
+                gv[j] = in ? g : 0.f;
+                ev[j] = in ? e : 0.f;
+            }
+            acc[0] = T::mfma(gv[0], ev[0], acc[0]);
+            acc[T::NACC - 1] = T::mfma(gv[1], ev[1], acc[T::NACC - 1]);
+            acc[0] = T::mfma(gv[2], ev[2], acc[0]);
+            acc[T::NACC - 1] = T::mfma(gv[3], ev[3], acc[T::NACC - 1]);
+        }
+        fit_spill<S>(acc, red[wave], lane);
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < S * S / kFitThreads; ++q) {
+            const int e = tid + kFitThreads * q;
+            const int c = c0 + e / S, k = k0 + e % S;
+            if (c < p.N) {
+                const float dw = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+                const long long o = (long long)c * kFitK + k;
+                if (APPLY) {
+                    float w = p.W[o], m = p.mW[o], v = p.vW[o];
+                    adam_elem(w, dw, m, v, p.a.amsgrad ? p.vmaxW + o : nullptr, p.a);
+                    p.W[o] = w; p.mW[o] = m; p.vW[o] = v;
+                } else {
+                    p.dW[o] = dw;
+                }
+            }
+        }
+        return;
+    }
+    const int ndb = (p.N + kFitDbCols - 1) / kFitDbCols;
+    if (bid < p.tiles + ndb) {                                     // db of 64 classes: four row quarters, added in order
+        const int c = (bid - p.tiles) * kFitDbCols + lane;
+        const int per = (p.rows + 3) / 4;
+        const int r_lo = wave * per, r_hi = min(p.rows, r_lo + per);
+        float s = 0.f;
+        if (c < p.N)
+            for (int row = r_lo; row < r_hi; ++row) s += p.G[(long long)row * p.N + c];
+        red[wave][lane] = s;
+        __syncthreads();
+        if (wave == 0 && c < p.N) {
+            const float d = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+            if (APPLY) {
+                float w = p.b[c], m = p.mb[c], v = p.vb[c];
+                adam_elem(w, d, m, v, p.a.amsgrad ? p.vmaxb + c : nullptr, p.a);
+                p.b[c] = w; p.mb[c] = m; p.vb[c] = v;
+            } else {
+                p.db[c] = d;
+            }
+        }
+        return;
+    }
+    // the loss: partials in index order per thread, threads by the shuffle tree, waves in order
+    float s = 0.f;
+    for (int i = tid; i < p.nparts; i += kFitThreads) s += p.part[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) red[0][wave] = s;
+    __syncthreads();
+    if (tid == 0) *p.loss = (((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) * p.inv;
+}
+
+__global__ __launch_bounds__(256) void adam_update_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                          float* __restrict__ m, float* __restrict__ v, float* vmax,
+                                                          long long n, AdamK a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float w = param[i], mm = m[i], vv = v[i];
+    adam_elem(w, grad[i], mm, vv, a.amsgrad ? vmax + i : nullptr, a);
+    param[i] = w; m[i] = mm; v[i] = vv;
+}
+
+static size_t fit_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// workspace: G (rows_max, classes) fp32, then the loss partials of the finest tiling (16 x 16)
+static void fit_layout(long long rows, long long N, size_t* part_off, size_t* total) {
+    const size_t gb = fit_align((size_t)rows * N * 4);
+    const size_t pb = fit_align((size_t)((rows + 15) / 16) * ((N + 15) / 16) * 4);
+    *part_off = gb;
+    *total = gb + pb;
+}
+
+static int fit_check_shape(const char* who, int64_t rows, int classes) {
+    if (rows < 1) ACX_FAIL(ACX_ERR_ARG, "%s: rows = %lld (expected >= 1)", who, (long long)rows);
+    if (classes < 1 || classes > ACX_MAX_CLASSES)
+        ACX_FAIL(ACX_ERR_ARG, "%s: classes = %d (expected 1 .. %d)", who, classes, ACX_MAX_CLASSES);
+    if (rows > kFitMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: rows = %lld (at most 2^22 per step)", who, (long long)rows);
+    return ACX_OK;
+}
+
+static int adam_scalars(const char* who, const acx_adam* hp, int64_t t, double lr, AdamK* a) {
+    if (!hp) ACX_FAIL(ACX_ERR_ARG, "%s: hp is null", who);
+    if (!(hp->beta1 >= 0.0 && hp->beta1 < 1.0)) ACX_FAIL(ACX_ERR_ARG, "%s: hp->beta1 = %g (expected 0 <= beta1 < 1)", who, hp->beta1);
+    if (!(hp->beta2 >= 0.0 && hp->beta2 < 1.0)) ACX_FAIL(ACX_ERR_ARG, "%s: hp->beta2 = %g (expected 0 <= beta2 < 1)", who, hp->beta2);
+    if (!(hp->eps > 0.0) || !std::isfinite(hp->eps)) ACX_FAIL(ACX_ERR_ARG, "%s: hp->eps = %g (expected > 0)", who, hp->eps);
+    if (!(hp->weight_decay >= 0.0) || !std::isfinite(hp->weight_decay))
+        ACX_FAIL(ACX_ERR_ARG, "%s: hp->weight_decay = %g (expected >= 0)", who, hp->weight_decay);
+    if (t < 1) ACX_FAIL(ACX_ERR_ARG, "%s: step_t = %lld (steps count from 1)", who, (long long)t);
+    if (!(lr >= 0.0) || !std::isfinite(lr)) ACX_FAIL(ACX_ERR_ARG, "%s: lr = %g (expected >= 0)", who, lr);
+    a->beta1 = (float)hp->beta1;
+    a->omb1 = (float)(1.0 - hp->beta1);
+    a->beta2 = (float)hp->beta2;
+    a->omb2 = (float)(1.0 - hp->beta2);
+    a->eps = (float)hp->eps;
+    a->wd = hp->decoupled ? 0.f : (float)hp->weight_decay;
+    a->decay = hp->decoupled ? (float)(1.0 - lr * hp->weight_decay) : 1.f;
+    a->step_size = (float)(lr / (1.0 - std::pow(hp->beta1, (double)t)));
+    a->bc2_sqrt = (float)std::sqrt(1.0 - std::pow(hp->beta2, (double)t));
+    a->amsgrad = hp->amsgrad ? 1 : 0;
+    return ACX_OK;
+}
+
+struct FitCall {        // the arguments the step and its component form share
+    const float* E; int64_t ld_e; int64_t n_total; const void* Y; int y_dtype; int64_t ld_y; const int64_t* idx; int64_t rows;
+    int classes; const float* W; const float* b; int32_t* status; void* ws; size_t ws_bytes;
+};
+
+static int fit_check_call(const char* who, const FitCall& c, size_t* part_off) {
+    if (!c.E) ACX_FAIL(ACX_ERR_ARG, "%s: E is null", who);
+    if (!c.Y) ACX_FAIL(ACX_ERR_ARG, "%s: target is null", who);
+    if (!c.idx) ACX_FAIL(ACX_ERR_ARG, "%s: idx is null", who);
+    if (!c.W) ACX_FAIL(ACX_ERR_ARG, "%s: W is null", who);
+    if (!c.b) ACX_FAIL(ACX_ERR_ARG, "%s: b is null", who);
+    if (!c.status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    if (!c.ws) ACX_FAIL(ACX_ERR_ARG, "%s: workspace is null", who);
+    if (c.y_dtype != ACX_TARGET_F32 && c.y_dtype != ACX_TARGET_U8)
+        ACX_FAIL(ACX_ERR_ARG, "%s: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", who, c.y_dtype);
+    ACX_TRY(fit_check_shape(who, c.rows, c.classes));
+    if (c.n_total < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n_rows_total = %lld (expected >= 1)", who, (long long)c.n_total);
+    if (c.ld_e < kFitK) ACX_FAIL(ACX_ERR_ARG, "%s: ld_e = %lld is shorter than a row of %d", who, (long long)c.ld_e, kFitK);
+    if ((c.ld_e & 3) || (reinterpret_cast<uintptr_t>(c.E) & 15) || (reinterpret_cast<uintptr_t>(c.W) & 15))
+        ACX_FAIL(ACX_ERR_ARG, "%s: E and W must be 16-byte aligned and ld_e a multiple of 4 (ld_e = %lld)", who, (long long)c.ld_e);
+    if (c.ld_y < c.classes)
+        ACX_FAIL(ACX_ERR_ARG, "%s: ld_target = %lld is shorter than %d classes", who, (long long)c.ld_y, c.classes);
+    size_t need;
+    fit_layout(c.rows, c.classes, part_off, &need);
+    if (c.ws_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, c.ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(c.ws) & 255) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace is not 256-byte aligned", who);
+    return ACX_OK;
+}
+
+// The two launches.  apply: W, b and the moments updated in place (u.a set); otherwise dW / db written.  The tile shape of each
+// launch depends on (rows, classes, CUs) alone, so the step and its component form run the same kernels.
+static int fit_launch(const FitCall& c, float* z, float* G, float* part, FitUpdP u, bool apply, float* loss, hipStream_t s) {
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    const int rows = (int)c.rows, N = c.classes;
+    const float inv = (float)(1.0 / ((double)rows * (double)N));
+    FitGradP g;
+    g.E = c.E; g.ld_e = c.ld_e; g.n_total = c.n_total;
+    g.Y = c.Y; g.y_u8 = c.y_dtype == ACX_TARGET_U8; g.ld_y = c.ld_y;
+    g.idx = reinterpret_cast<const long long*>(c.idx); g.rows = rows; g.N = N;
+    g.W = c.W; g.b = c.b; g.z = z; g.G = G; g.part = part; g.status = (int*)c.status; g.inv = inv;
+    const bool g32 = (long long)((rows + 31) / 32) * ((N + 31) / 32) >= cus;
+    const int gs = g32 ? 32 : 16;
+    g.tiles_n = (N + gs - 1) / gs;
+    const int gtiles = ((rows + gs - 1) / gs) * g.tiles_n;
+    if (g32) launch_kernel(&fit_grad_kernel<32>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
+    else launch_kernel(&fit_grad_kernel<16>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
+    ACX_HIP(hipGetLastError());
+
+    u.E = c.E; u.ld_e = c.ld_e; u.n_total = c.n_total; u.idx = g.idx; u.rows = rows; u.N = N;
+    u.G = G; u.part = part; u.nparts = gtiles; u.loss = loss; u.inv = inv;
+    const bool u32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
+    const int us = u32 ? 32 : 16;
+    u.tiles = ((N + us - 1) / us) * (kFitK / us);
+    const dim3 grid(u.tiles + (N + kFitDbCols - 1) / kFitDbCols + 1);
+    if (apply) {
+        if (u32) launch_kernel(&fit_update_kernel<32, true>, grid, dim3(kFitThreads), 0, s, u);
+        else launch_kernel(&fit_update_kernel<16, true>, grid, dim3(kFitThreads), 0, s, u);
+    } else {
+        if (u32) launch_kernel(&fit_update_kernel<32, false>, grid, dim3(kFitThreads), 0, s, u);
+        else launch_kernel(&fit_update_kernel<16, false>, grid, dim3(kFitThreads), 0, s, u);
+    }
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+}  // namespace acx
+
+using namespace acx;
+
+extern "C" {
+
+int acx_head_fit_workspace_bytes(int64_t rows_max, int classes, size_t* out_bytes) {
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "acx_head_fit_workspace_bytes: out_bytes is null");
+    ACX_TRY(fit_check_shape("acx_head_fit_workspace_bytes", rows_max, classes));
+    size_t po;
+    fit_layout(rows_max, classes, &po, out_bytes);
+    return ACX_OK;
+}
+
+int acx_head_fit_step(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                      int64_t ld_target, const int64_t* idx, int64_t rows, int classes, float* W, float* b, float* mW, float* vW,
+                      float* vmaxW, float* mb, float* vb, float* vmaxb, const acx_adam* hp, int64_t step_t, double lr,
+                      float* loss_out, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "acx_head_fit_step";
+    const FitCall c{E, ld_e, n_rows_total, target, target_dtype, ld_target, idx, rows, classes, W, b, status, ws, ws_bytes};
+    size_t part_off;
+    ACX_TRY(fit_check_call(who, c, &part_off));
+    if (!mW || !vW || !mb || !vb) ACX_FAIL(ACX_ERR_ARG, "%s: a moment buffer (mW, vW, mb, vb) is null", who);
+    if (!loss_out) ACX_FAIL(ACX_ERR_ARG, "%s: loss_out is null", who);
+    FitUpdP u{};
+    ACX_TRY(adam_scalars(who, hp, step_t, lr, &u.a));
+    if (hp->amsgrad && (!vmaxW || !vmaxb)) ACX_FAIL(ACX_ERR_ARG, "%s: vmaxW / vmaxb is null with hp->amsgrad set", who);
+    u.W = W; u.mW = mW; u.vW = vW; u.vmaxW = vmaxW;
+    u.b = b; u.mb = mb; u.vb = vb; u.vmaxb = vmaxb;
+    char* w = static_cast<char*>(ws);
+    return fit_launch(c, nullptr, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + part_off), u, true, loss_out,
+                      (hipStream_t)stream);
+}
+
+int acx_head_fit_grad(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                      int64_t ld_target, const int64_t* idx, int64_t rows, int classes, const float* W, const float* b, float* z,
+                      float* G, float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "acx_head_fit_grad";
+    const FitCall c{E, ld_e, n_rows_total, target, target_dtype, ld_target, idx, rows, classes, W, b, status, ws, ws_bytes};
+    size_t part_off;
+    ACX_TRY(fit_check_call(who, c, &part_off));
+    if (!z || !G || !dW || !db || !loss) ACX_FAIL(ACX_ERR_ARG, "%s: an output (z, G, dW, db, loss) is null", who);
+    FitUpdP u{};
+    u.dW = dW; u.db = db;
+    return fit_launch(c, z, G, reinterpret_cast<float*>(static_cast<char*>(ws) + part_off), u, false, loss, (hipStream_t)stream);
+}
+
+int acx_adam_update(float* param, const float* grad, float* m, float* v, float* vmax, int64_t n, const acx_adam* hp,
+                    int64_t step_t, double lr, void* stream) {
+    static const char* who = "acx_adam_update";
+    if (!param || !grad || !m || !v) ACX_FAIL(ACX_ERR_ARG, "%s: param, grad, m or v is null", who);
+    if (n < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n = %lld (expected >= 1)", who, (long long)n);
+    AdamK a;
+    ACX_TRY(adam_scalars(who, hp, step_t, lr, &a));
+    if (hp->amsgrad && !vmax) ACX_FAIL(ACX_ERR_ARG, "%s: vmax is null with hp->amsgrad set", who);
+    launch_kernel(&adam_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v,
+                  vmax, (long long)n, a);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+}  // extern "C"

@@ -607,6 +607,31 @@ class ConvNeXt(nn.Module):
         return _stream.Stream(self, slots=slots, window=window, hop=hop, what=what, sample_rate=sample_rate,
                               timeline=timeline, max_push=max_push, max_batch=max_batch)
 
+    def fit_head(self, data, target, sample_rate=None, **kw):
+        """Train a new classifier head on this (frozen) backbone and install it (pytorch/finetune.py, fit_head): `data` is an
+        (n, 768) tensor of scene embeddings, or a list of waveforms at `sample_rate`, whose scene embeddings are extracted
+        first (extract(..., what="scene", pack=True)); target: (n, N) bool / uint8 / float labels; **kw: fit_head's settings.
+        Afterwards head_audioset is an nn.Linear(768, N) with the fitted weights on the model's device -- the next forward
+        runs it, state_dict() saves a checkpoint that from_pretrained loads as a fine-tuned model.  The model stays in eval
+        mode.  Returns the HeadFit."""
+        from . import finetune as _ft
+        from .extract_embeddings import extract
+        dev = self.head_audioset.weight.device
+        if isinstance(data, torch.Tensor) and data.dim() == 2:
+            emb = data
+        else:
+            emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
+        if isinstance(target, torch.Tensor) and target.device != emb.device:
+            target = target.to(emb.device)
+        fit = _ft.fit_head(emb, target, **kw)
+        head = nn.Linear(_ft.EMBED_DIM, fit.weight.shape[0]).to(dev)
+        with torch.no_grad():
+            head.weight.copy_(fit.weight)
+            head.bias.copy_(fit.bias)
+        head.train(self.training)
+        self.head_audioset = head
+        return fit
+
     # ----------------------------------------------------------------------------- public surface
     # sample_rate (all three): the rate of x; None or 32000 is the model's own.  Any other integer rate is resampled to 32 kHz
     # on x's stream first (acx_resample, the interpolation of torchaudio.functional.resample that the reference's demo runs on

@@ -1,0 +1,198 @@
+"""Fitting a classifier head on frozen scene embeddings, on the GPU (acx_head_fit_step in include/acx.h).
+
+The reference fine-tunes with the whole model in train mode (pytorch/finetune_audiocaps.py: base frozen, BCELoss on
+clipwise_output, optim.Adam(lr=1e-4, amsgrad=True), mAP per epoch).  With the backbone frozen the head's input -- the scene
+embedding -- never changes, so the embeddings are computed once and the training is logits = E W^T + b, binary cross-entropy,
+Adam / AdamW, two launches per step:
+
+    from audioset_convnext_inf_amd.pytorch.finetune import fit_head
+    fit = fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4)     # emb (n, 768) fp32 CUDA, target (n, N) bool / uint8 / float
+    fit.weight, fit.bias, fit.loss                                     # (N, 768), (N,), (steps,) on the device
+    fit.history                                                        # per epoch: mean loss and, with val=, mAP / AUC / d'
+
+The epoch order is part of the contract: torch.randperm(n, generator=g) drawn once per epoch from ONE CPU generator
+g = torch.Generator().manual_seed(seed) (shuffle=False: arange); the last batch of an epoch is short unless drop_last.  The
+initial weights (init=None) come from a second generator seeded with `seed` too: trunc_normal_(std=0.02) weight, zero bias
+(convnext.py:263-267).  Every step of a fit is enqueued on the current stream without a host synchronisation."""
+import ctypes
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from .. import _ffi
+
+EMBED_DIM = 768
+HeadFit = namedtuple("HeadFit", ["weight", "bias", "loss", "history"])
+
+
+def epoch_batches(n, batch_size, drop_last=False):
+    """[(start, rows)] of the mini-batches of one epoch over a permutation of n rows: consecutive runs of batch_size, the last
+    one short unless drop_last."""
+    n, batch_size = int(n), int(batch_size)
+    full = n // batch_size
+    out = [(i * batch_size, batch_size) for i in range(full)]
+    if n % batch_size and not drop_last:
+        out.append((full * batch_size, n % batch_size))
+    return out
+
+
+def epoch_orders(n, epochs, seed=0, shuffle=True):
+    """(epochs, n) int64 CPU tensor: row e is the order in which epoch e visits the data set (see the module docstring)."""
+    g = torch.Generator().manual_seed(int(seed))
+    rows = [torch.randperm(n, generator=g) if shuffle else torch.arange(n) for _ in range(int(epochs))]
+    return torch.stack(rows) if rows else torch.empty((0, n), dtype=torch.int64)
+
+
+def init_head(classes, seed=0):
+    """(weight (N, 768), bias (N,)) as the model initialises head_audioset (convnext.py:263-267): trunc_normal_(std=0.02) from a
+    CPU generator seeded with `seed`, zero bias."""
+    g = torch.Generator().manual_seed(int(seed))
+    w = torch.empty(int(classes), EMBED_DIM)
+    torch.nn.init.trunc_normal_(w, std=0.02, generator=g)
+    return w, torch.zeros(int(classes))
+
+
+def _check_hyper(epochs, batch_size, betas, eps, weight_decay):
+    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 0:
+        raise ValueError("epochs must be an integer >= 0 (got %r)" % (epochs,))
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError("batch_size must be an integer >= 1 (got %r)" % (batch_size,))
+    if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+        raise ValueError("betas must be two values in [0, 1) (got %r)" % (betas,))
+    if not float(eps) > 0.0:
+        raise ValueError("eps must be > 0 (got %r)" % (eps,))
+    if not float(weight_decay) >= 0.0:
+        raise ValueError("weight_decay must be >= 0 (got %r)" % (weight_decay,))
+
+
+def _lr_schedule(lr, steps):
+    """One learning rate per step: a float repeated, or the caller's sequence (its length must be the step count)."""
+    if isinstance(lr, (int, float)):
+        lrs = [float(lr)] * steps
+        bad = not (float(lr) >= 0.0 and np.isfinite(float(lr)))
+    else:
+        lrs = [float(v) for v in lr]
+        if len(lrs) != steps:
+            raise ValueError("lr has %d values for %d steps (one value per step, or one float)" % (len(lrs), steps))
+        bad = any(not (v >= 0.0 and np.isfinite(v)) for v in lrs)
+    if bad:
+        raise ValueError("lr must be finite and >= 0")
+    return lrs
+
+
+def _check_pair(emb, target, name="emb", tname="target"):
+    """Shapes, dtypes, devices and values of one (embeddings, targets) pair; -> (emb, target tensor for the kernel, dtype code)."""
+    if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
+        raise ValueError("%s must be a (n, %d) tensor (got %s)" % (name, EMBED_DIM, getattr(emb, "shape", type(emb))))
+    if emb.dtype != torch.float32:
+        raise ValueError("%s must be float32 (got %s)" % (name, emb.dtype))
+    if not emb.is_cuda:
+        raise ValueError("%s must be a CUDA (HIP) tensor: fit_head runs on the GPU only (got device %s)" % (name, emb.device))
+    if emb.shape[0] < 1:
+        raise ValueError("%s holds no rows" % name)
+    if not isinstance(target, torch.Tensor) or target.dim() != 2 or target.shape[0] != emb.shape[0]:
+        raise ValueError("%s must be a (%d, N) tensor (got %s)" % (tname, emb.shape[0], getattr(target, "shape", type(target))))
+    if target.device != emb.device:
+        raise ValueError("%s is on %s, %s on %s" % (tname, target.device, name, emb.device))
+    N = int(target.shape[1])
+    if not 1 <= N <= _ffi.MAX_CLASSES:
+        raise ValueError("%s has N = %d classes (expected 1 .. %d)" % (tname, N, _ffi.MAX_CLASSES))
+    if target.dtype == torch.bool:
+        t = target.view(torch.uint8)
+    elif target.dtype.is_floating_point:
+        t = target if target.dtype == torch.float32 else target.to(torch.float32)
+        if not bool(((t >= 0) & (t <= 1)).all()):
+            raise ValueError("%s holds values outside [0, 1]" % tname)
+    elif target.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        if not bool(((target == 0) | (target == 1)).all()):
+            raise ValueError("%s holds values other than 0 and 1" % tname)
+        t = target if target.dtype == torch.uint8 else target.to(torch.uint8)
+    else:
+        raise ValueError("%s must be bool, an integer type or floating point (got %s)" % (tname, target.dtype))
+    if t.stride(1) != 1 or t.stride(0) < N:
+        t = t.contiguous()
+    if emb.stride(1) != 1 or emb.stride(0) < EMBED_DIM or emb.stride(0) % 4 or emb.data_ptr() % 16:
+        emb = emb.contiguous()
+    return emb, t, (_ffi.TARGET_U8 if t.dtype == torch.uint8 else _ffi.TARGET_F32)
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _validate(weight, bias, emb_val, target_val):
+    from .metrics import tagging_metrics
+    probs = torch.sigmoid(torch.addmm(bias, emb_val, weight.t()))
+    stats = tagging_metrics(target_val, probs)
+    return {"average_precision": stats["average_precision"], "auc": stats["auc"], "d_prime": stats["d_prime"],
+            "mAP": float(np.mean(stats["average_precision"])), "mAUC": float(np.nanmean(stats["auc"]))}
+
+
+def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=True,
+             decoupled=False, init=None, seed=0, shuffle=True, drop_last=False, val=None):
+    """Train an nn.Linear(768, N) head on (n, 768) scene embeddings with binary cross-entropy and Adam (decoupled=True: AdamW);
+    the defaults are the reference's fine-tuning settings.  lr: a float, or one value per step.  init: None (seeded
+    trunc_normal(std=0.02) weight, zero bias) or (weight, bias) to continue from a head; the moments always start at zero.
+    val: (emb_val, target_val) -> per-epoch tagging_metrics in the history (this synchronises once per epoch).
+    Returns HeadFit(weight, bias, loss, history): device tensors and a list of one dict per epoch, whose "loss" is a 0-d
+    device tensor (the mean of the epoch's step losses)."""
+    _check_hyper(epochs, batch_size, betas, eps, weight_decay)
+    emb, tgt, tdtype = _check_pair(emb, target)
+    n, N = int(emb.shape[0]), int(tgt.shape[1])
+    device = emb.device
+    if val is not None:
+        if len(val) != 2:
+            raise ValueError("val must be (emb_val, target_val)")
+        emb_val, target_val, _ = _check_pair(val[0], val[1], "emb_val", "target_val")
+        if target_val.shape[1] != N:
+            raise ValueError("target_val has %d classes, target %d" % (target_val.shape[1], N))
+        if emb_val.device != device:
+            raise ValueError("emb_val is on %s, emb on %s" % (emb_val.device, device))
+    if init is None:
+        w0, b0 = init_head(N, seed)
+    else:
+        if len(init) != 2:
+            raise ValueError("init must be (weight, bias)")
+        w0, b0 = init
+        if tuple(w0.shape) != (N, EMBED_DIM) or tuple(b0.shape) != (N,):
+            raise ValueError("init must be a (%d, %d) weight and a (%d,) bias (got %s and %s)"
+                             % (N, EMBED_DIM, N, tuple(w0.shape), tuple(b0.shape)))
+    batches = epoch_batches(n, batch_size, drop_last)
+    steps = epochs * len(batches)
+    lrs = _lr_schedule(lr, steps)
+
+    with torch.no_grad(), torch.cuda.device(device):
+        W = w0.detach().to(device=device, dtype=torch.float32, copy=True).contiguous()
+        b = b0.detach().to(device=device, dtype=torch.float32, copy=True).contiguous()
+        loss = torch.zeros(steps, dtype=torch.float32, device=device)
+        history = []
+        if steps == 0:
+            return HeadFit(W, b, loss, history)
+        order = epoch_orders(n, epochs, seed, shuffle).to(device)
+        mom = torch.zeros((3, N, EMBED_DIM), dtype=torch.float32, device=device)
+        momb = torch.zeros((3, N), dtype=torch.float32, device=device)
+        status = torch.zeros(1, dtype=torch.int32, device=device)
+        ws_bytes = _ffi.head_fit_workspace_bytes(min(batch_size, n), N)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        hp = _ffi.adam(betas[0], betas[1], eps, weight_decay, amsgrad, decoupled)
+        step_fn = _ffi.lib().acx_head_fit_step
+        stream = _ffi.stream_ptr(device)
+        fixed_a = (_vp(emb), emb.stride(0), n, _vp(tgt), tdtype, tgt.stride(0))
+        fixed_b = (N, _vp(W), _vp(b), _vp(mom[0]), _vp(mom[1]), _vp(mom[2]) if amsgrad else None, _vp(momb[0]), _vp(momb[1]),
+                   _vp(momb[2]) if amsgrad else None, ctypes.byref(hp))
+        tail = (_vp(status), _vp(ws), ws_bytes, stream)
+        order_ptr, loss_ptr = order.data_ptr(), loss.data_ptr()
+        t = 0
+        for e in range(epochs):
+            for start, rows in batches:
+                rc = step_fn(*fixed_a, ctypes.c_void_p(order_ptr + 8 * (e * n + start)), rows, *fixed_b, t + 1, lrs[t],
+                             ctypes.c_void_p(loss_ptr + 4 * t), *tail)
+                if rc != _ffi.OK:
+                    _ffi.check(rc)
+                t += 1
+            rec = {"epoch": e, "loss": loss[e * len(batches):(e + 1) * len(batches)].mean()}
+            if val is not None:
+                rec.update(_validate(W, b, emb_val, target_val))
+            history.append(rec)
+    return HeadFit(W, b, loss, history)

@@ -1,0 +1,136 @@
+#!/usr/bin/env python
+"""Fine-tune a classifier head on this backbone -- counterpart of the reference's pytorch/finetune_audiocaps.py with the base
+frozen: scene embeddings are extracted once, the head is fitted on them on the GPU (ConvNeXt.fit_head), and the result is saved
+as a checkpoint that ConvNeXt.from_pretrained loads as an N-class model.
+
+    python demo_finetune.py --ckpt checkpoints/model.safetensors --data sounds/ --out my_tagger/        # sounds/<class>/*.wav
+    python demo_finetune.py --ckpt ... --csv clips.csv --out my_tagger/        # lines: path.wav,label[;label...]
+    python demo_finetune.py --synthetic --out /tmp/tagger                      # seeded weights and clips, no files needed
+
+Writes <out>/model.safetensors, <out>/model.pth ({"model": state_dict}) and <out>/labels.txt (one class name per line, in head
+order).  16-bit PCM WAV files at any rate (resampled on the device)."""
+import argparse
+import csv
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+from audioset_convnext_inf_amd.pytorch.convnext import ConvNeXt, convnext_tiny      # noqa: E402
+from audioset_convnext_inf_amd.pytorch.extract_embeddings import extract            # noqa: E402
+from audioset_convnext_inf_amd.utils.utilities import read_wav_pcm16                # noqa: E402
+
+
+def folder_items(root):
+    """[(path, [class])] of root/<class>/*.wav"""
+    items = []
+    for cls in sorted(os.listdir(root)):
+        d = os.path.join(root, cls)
+        if os.path.isdir(d):
+            items += [(os.path.join(d, f), [cls]) for f in sorted(os.listdir(d)) if f.lower().endswith(".wav")]
+    return items
+
+
+def csv_items(path):
+    """[(path, [labels])] of lines `file.wav,label;label` (paths relative to the CSV's folder)"""
+    base = os.path.dirname(os.path.abspath(path))
+    with open(path, newline="") as f:
+        return [(os.path.join(base, r[0]), [s.strip() for s in r[1].split(";") if s.strip()])
+                for r in csv.reader(f) if len(r) >= 2 and r[0].lower().endswith(".wav")]
+
+
+def synthetic_items(clips, classes, seconds, seed=0):
+    """Seeded clips whose class decides a tone mixed into noise -> (waveforms, (clips, classes) bool targets, names)"""
+    g = torch.Generator().manual_seed(seed)
+    label = torch.randint(0, classes, (clips,), generator=g)
+    t = torch.arange(int(seconds * 32000)) / 32000.0
+    waves = [0.1 * torch.randn(t.numel(), generator=g) + 0.3 * torch.sin(2 * torch.pi * (200.0 + 150.0 * int(c)) * t) for c in label]
+    target = torch.zeros(clips, classes, dtype=torch.bool)
+    target[torch.arange(clips), label] = True
+    return waves, target, ["tone_%d" % c for c in range(classes)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ckpt", default="topel/ConvNeXt-Tiny-AT", help="local .safetensors/.pth, Zenodo URL or HF model id")
+    ap.add_argument("--data", help="folder with one sub-folder of .wav files per class")
+    ap.add_argument("--csv", help="CSV of `path.wav,label[;label...]`")
+    ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights and clips (2 000 x 1 s, 50 classes)")
+    ap.add_argument("--clips", type=int, default=2000)
+    ap.add_argument("--classes", type=int, default=50)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--epochs", type=int, default=20)
+    ap.add_argument("--batch-size", type=int, default=64)
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--weight-decay", type=float, default=0.0)
+    ap.add_argument("--adamw", action="store_true")
+    ap.add_argument("--val-fraction", type=float, default=0.1)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("this build runs on an MI355X; no GPU is visible")
+
+    rate = None
+    if a.synthetic:
+        from audioset_convnext_inf_amd import synth
+        model = convnext_tiny(pretrained=False, strict=False, drop_path_rate=0.0, after_stem_dim=[252, 56], use_speed_perturb=False)
+        model.load_state_dict(synth.synth_state_dict(0))
+        waves, target, names = synthetic_items(a.clips, a.classes, 1.0, a.seed)
+    else:
+        if not (a.data or a.csv):
+            sys.exit("give --data, --csv or --synthetic")
+        model = ConvNeXt.from_pretrained(a.ckpt, map_location="cpu")
+        if model is None:
+            sys.exit(1)
+        items = folder_items(a.data) if a.data else csv_items(a.csv)
+        if not items:
+            sys.exit("no .wav files found")
+        names = sorted({l for _, ls in items for l in ls})
+        col = {n: i for i, n in enumerate(names)}
+        waves, target = [], torch.zeros(len(items), len(names), dtype=torch.bool)
+        for i, (path, labels) in enumerate(items):
+            wav, sr = read_wav_pcm16(path)
+            if rate is None:
+                rate = sr
+            elif sr != rate:
+                sys.exit("%s is at %d Hz, the clips before it at %d Hz: one rate per run" % (path, sr, rate))
+            waves.append(torch.from_numpy(wav[0]))
+            target[i, [col[l] for l in labels]] = True
+    model = model.to("cuda").eval()
+    print("%d clips, %d classes" % (len(waves), len(names)))
+
+    t0 = time.perf_counter()
+    emb = torch.stack(extract(model, waves, what="scene", pack=True, sample_rate=rate)).cuda()
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    n_val = int(len(waves) * a.val_fraction) if len(waves) >= 20 else 0
+    order = torch.randperm(len(waves), generator=torch.Generator().manual_seed(a.seed)).cuda()
+    tr, va = order[n_val:], order[:n_val]
+    target = target.cuda()
+    fit = model.fit_head(emb[tr], target[tr], epochs=a.epochs, batch_size=a.batch_size, lr=a.lr, weight_decay=a.weight_decay,
+                         decoupled=a.adamw, seed=a.seed, val=(emb[va], target[va]) if n_val else None)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    for rec in fit.history:
+        print("epoch %2d  loss %.4f%s" % (rec["epoch"], float(rec["loss"]),
+                                          "  val mAP %.3f  AUC %.3f" % (rec["mAP"], rec["mAUC"]) if n_val else ""))
+    print("extraction %.2f s (%.0f clips/s), fit %.2f s (%d steps%s)" % (t1 - t0, len(waves) / (t1 - t0), t2 - t1, fit.loss.numel(),
+                                                                           ", validation included" if n_val else ""))
+
+    os.makedirs(a.out, exist_ok=True)
+    sd = {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}
+    torch.save({"model": sd}, os.path.join(a.out, "model.pth"))
+    from safetensors.torch import save_file
+    save_file(sd, os.path.join(a.out, "model.safetensors"))
+    with open(os.path.join(a.out, "labels.txt"), "w") as f:
+        f.write("\n".join(names) + "\n")
+    print("wrote %s: model.safetensors, model.pth, labels.txt -- ConvNeXt.from_pretrained(%r) loads it as a %d-class model"
+          % (a.out, os.path.join(a.out, "model.safetensors"), len(names)))
+
+
+if __name__ == "__main__":
+    main()

@@ -378,6 +378,54 @@ ACX_API int acx_tagging_metrics(const float* scores, int64_t ld_scores, const vo
                                 int64_t ld_target, int64_t n, int classes, double* ap, double* auc, double* dprime,
                                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- fitting a classifier head on frozen scene embeddings -----------------------------------------------------------------
+ * The reference fine-tunes with the whole model in train mode (pytorch/finetune_audiocaps.py: base frozen, BCELoss on
+ * clipwise_output, optim.Adam(amsgrad=True); pytorch/main.py:648 AdamW).  With the backbone frozen the head's input -- the scene
+ * embedding norm(pool(x)), convnext.py:285,321 -- never changes, so training is logits = E W^T + b, binary cross-entropy, Adam,
+ * on embeddings computed once.  Stateless: the caller owns every buffer (all on the device, fp32 unless said otherwise):
+ *   E (n_rows_total, 768) with row stride ld_e (16-byte aligned, ld_e a multiple of 4); target (n_rows_total, classes) of
+ *   target_dtype (ACX_TARGET_U8: 0 / 1; ACX_TARGET_F32: any value in [0, 1], soft targets allowed) with row stride ld_target;
+ *   idx: `rows` int64 row numbers into E / target, the mini-batch (repeats allowed; nothing is copied or shuffled in memory);
+ *   W (classes, 768) 16-byte aligned, b (classes); the moments mW, vW, vmaxW like W and mb, vb, vmaxb like b, zero before step 1
+ *   (vmax* may be NULL unless hp->amsgrad); status: one int32, which the calls OR into and never clear.
+ * One step t = 1, 2, ... with G = (sigmoid(z) - y) / (rows classes), z = E[idx] W^T + b:
+ *   g = G^T E[idx] (for W), sum_rows G (for b);   Adam: g += weight_decay p;   AdamW (hp->decoupled): p *= 1 - lr weight_decay;
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;  amsgrad: vmax = max(vmax, v) replaces v below;
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)           -- torch.optim.Adam / AdamW, single-tensor form
+ *   *loss_out = mean over (rows, classes) of -[y max(log p, -100) + (1 - y) max(log(1 - p), -100)]   (F.binary_cross_entropy)
+ * The scalars that depend on hp, step_t and lr alone are evaluated in double and rounded to fp32 once.  G is the exact
+ * BCE-with-logits gradient; the reference's sigmoid-then-BCELoss autograd equals it except where the fp32 sigmoid saturates
+ * (|z| >~ 16.6), where autograd returns 0.  Products and sums are fp32 (f32 matrix instructions), combined in a fixed order: the
+ * same inputs give the same bits on every call; acx_set_precision has no influence.
+ *   acx_head_fit_workspace_bytes: workspace for steps of up to rows_max rows, non-decreasing in both arguments (host only).
+ *   acx_head_fit_step: the step above, W / b / moments updated in place.  Two launches.
+ *   acx_head_fit_grad: the same gradient pass without an update: z and G (rows, classes), dW (classes, 768), db (classes) and
+ *     *loss to caller buffers.  acx_adam_update: the element-wise update of n parameters from a gradient buffer.
+ *     acx_head_fit_grad, then acx_adam_update on (W, dW) and (b, db), leaves the bits of acx_head_fit_step.
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable; step_t and lr
+ * travel by value.  ARGUMENT errors return a negative status before any launch, acx_last_error naming the argument: a null
+ * pointer, rows < 1, classes outside 1 .. ACX_MAX_CLASSES, a row stride shorter than its row, E or W not 16-byte aligned or
+ * ld_e not a multiple of 4, a workspace too small or not 256-byte aligned (ACX_ERR_WORKSPACE), beta outside [0, 1), eps <= 0, weight_decay < 0, lr < 0, step_t < 1; rows > 2^22 is
+ * ACX_ERR_UNSUPPORTED.  An idx entry outside [0, n_rows_total) is a DATA error: it is clamped into the range (nothing outside E
+ * or target is read) and ACX_FIT_BAD_INDEX is ORed into *status. */
+typedef struct acx_adam {
+    double beta1, beta2, eps, weight_decay;
+    int amsgrad;     /* keep the running maximum of v and divide by it */
+    int decoupled;   /* 0: Adam (weight decay added to the gradient), 1: AdamW */
+} acx_adam;
+#define ACX_FIT_BAD_INDEX 1
+ACX_API int acx_head_fit_workspace_bytes(int64_t rows_max, int classes, size_t* out_bytes);
+ACX_API int acx_head_fit_step(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                              int64_t ld_target, const int64_t* idx, int64_t rows, int classes, float* W, float* b, float* mW,
+                              float* vW, float* vmaxW, float* mb, float* vb, float* vmaxb, const acx_adam* hp, int64_t step_t,
+                              double lr, float* loss_out, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_head_fit_grad(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                              int64_t ld_target, const int64_t* idx, int64_t rows, int classes, const float* W, const float* b,
+                              float* z, float* G, float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes,
+                              void* stream);
+ACX_API int acx_adam_update(float* param, const float* grad, float* m, float* v, float* vmax, int64_t n, const acx_adam* hp,
+                            int64_t step_t, double lr, void* stream);
+
 /* Which evaluation of the STFT the frontend uses (round 6).  ACX_FRONTEND_AUTO (default): the FFT kernel when the stored buffers are
  * window x DFT, the dense contraction otherwise (acx_finalize above).  ACX_FRONTEND_DENSE: ALWAYS the dense contraction with the
  * stored `conv_real` / `conv_imag` weights -- the reference's own formulation (two Conv1d, convnext.py:179-187,298) -- 2.1 GFLOP
