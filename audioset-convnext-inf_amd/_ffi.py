@@ -17,6 +17,9 @@ KERNEL_CLASSES = ("frontend", "stem", "dwconv", "pw1", "pw2", "rowstats", "downs
                   "mlp_fused", "mlp_wide")
 MIN_SAMPLES = 7360
 MAX_VARLEN_CLIPS = 256
+SEG_OUTPUT, SEG_EMBED = 0, 1         # enum acx_segment_what
+SEGMENT_SAMPLES = 10240              # ACX_SEGMENT_SAMPLES: 32 STFT frames of 320 samples
+MAX_SEGMENT_POOL = 31                # ACX_MAX_SEGMENT_POOL
 NUM_CLASSES = 527          # the AudioSet head (ACX_NUM_CLASSES)
 MAX_CLASSES = 32768        # widest classifier head a context takes (ACX_MAX_CLASSES)
 
@@ -56,6 +59,19 @@ SIGNATURES = {
                                      _vp, _c_sz, _vp]),
     "acx_window_timeline": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_int, _vp, _vp]),
     "acx_window_timeline_classes": (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_int, _vp, _vp]),
+    "acx_segment_count": (_c_int, [_c_i64, _pint]),
+    "acx_workspace_bytes_segments": (_c_int, [_vp, _c_int, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_forward_segments": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_workspace_bytes_segments_varlen": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_forward_segments_varlen": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_sz,
+                                             _vp]),
+    "acx_workspace_bytes_segments_windows": (_c_int, [_vp, _c_int, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_forward_segments_windows": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
+                                              _c_int, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_segment_head": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "acx_segment_expand": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "acx_segment_expand_varlen": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _vp]),
+    "acx_segment_timeline": (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_int, _vp, _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -215,6 +231,22 @@ class Context:
         check(lib().acx_workspace_bytes_windows(self._h, int(count), int(window), int(mode), ctypes.byref(out)))
         return out.value
 
+    def workspace_bytes_segments(self, B, L, what):
+        out = _c_sz()
+        check(lib().acx_workspace_bytes_segments(self._h, int(B), int(L), int(what), ctypes.byref(out)))
+        return out.value
+
+    def workspace_bytes_segments_varlen(self, lengths, what):
+        lens = (_c_i64 * max(1, len(lengths)))(*[int(n) for n in lengths])
+        out = _c_sz()
+        check(lib().acx_workspace_bytes_segments_varlen(self._h, lens, len(lengths), int(what), ctypes.byref(out)))
+        return out.value
+
+    def workspace_bytes_segments_windows(self, count, window, what):
+        out = _c_sz()
+        check(lib().acx_workspace_bytes_segments_windows(self._h, int(count), int(window), int(what), ctypes.byref(out)))
+        return out.value
+
     def sub_batches(self, B):
         """How many sub-batches (on separate streams) a forward of B clips runs as (acx_sub_batches)."""
         out = _c_int()
@@ -346,6 +378,13 @@ def head_fit_workspace_bytes(rows_max, classes):
     """Workspace of acx_head_fit_step / acx_head_fit_grad for steps of up to rows_max rows (host only)."""
     out = _c_sz()
     check(lib().acx_head_fit_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
+    return out.value
+
+
+def segment_count(L):
+    """S, the segments of a clip of L samples (acx_segment_count; host only)."""
+    out = _c_int()
+    check(lib().acx_segment_count(int(L), ctypes.byref(out)))
     return out.value
 
 

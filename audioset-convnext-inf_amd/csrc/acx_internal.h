@@ -469,6 +469,22 @@ __device__ __forceinline__ float win_reduce(Row row, long long j0, long long cnt
     return reduce ? acc : acc / (float)cnt;
 }
 
+// ---- sound event detection (segments.hip; the segment timeline in windows.hip) ---------------------------------------------
+constexpr int kSegSamples = ACX_SEGMENT_SAMPLES;
+// segments of a clip of L samples: the stage-3 height ((T + 4) / 4 + 1) / 8 = (T + 8) / 32, T = L / 320 + 1
+__host__ __device__ inline int seg_count(long long L) { return (int)((L / kHop + 1 + 8) / 32); }
+// x NHWC (rows of 7 x 768) -> segment embeddings, one row of 768 per segment.  Uniform: B clips of S rows; roff3 != null: a
+// variable-length batch of B clips, clip b owning rows [roff3[b], roff3[b + 1]) of x and of emb (maxS: the tallest clip)
+int launch_segment_pool(acx_ctx* c, const float* x, int B, int S, int pool, float* emb, const int* roff3, int maxS, hipStream_t s);
+// logits / probs (M, N) of M embedding rows with the context's head, on the f32 matrix cores
+int launch_segment_head(acx_ctx* c, const float* emb, long long M, float* logits, float* probs, hipStream_t s);
+// clip[b][n] = max_t probs[b][t][n]; roff3 as above
+int launch_segment_clipmax(const float* probs, int B, int S, int N, float* clip, const int* roff3, hipStream_t s);
+int launch_segment_expand(const float* probs, int B, int S, int N, int T, float* frame, hipStream_t s);
+int launch_segment_expand_varlen(const float* probs, const int64_t* lengths, int B, int N, float* frame, hipStream_t s);
+int launch_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                            int reduce, float* out, hipStream_t s);
+
 // ---- resampling (resample.hip, stream.hip) ------------------------------------------------------------------------------
 // Output n = j nf + i of phase i: the fp32 FMA chain in ascending r over the band's count taps; xs = the staged input of the
 // band's first sample, h = tap 0 of phase i (tap r at h[r nf]).  Both resample kernels call this one chain.

@@ -786,9 +786,27 @@ static void release_aux(acx_ctx* c, hipStream_t st) {
     if (it != c->aux.end() && it->second.users > 0) it->second.users -= 1;
 }
 
+// The tail of the segment forwards (acx_forward_segments*): what to compute from the stage-3 map instead of `mode`'s output.
+struct SegTail {
+    int pool, what;
+    float* clip;        // ACX_SEG_OUTPUT: (clips, N) maximum over segments, or null
+};
+
+// ACX_SEG_EMBED: the segment embeddings go straight to out0.  ACX_SEG_OUTPUT: they go to `feat` (idle since the stem; 768 S <=
+// 24 (T + 8) <= 224 T floats per clip), the head reads them there.  roff3 / maxS: a variable-length batch (B clips, rows rows).
+static int run_segment_tail(acx_ctx* c, const SegTail& sg, const float* x3, int B, int S, long long rows, float* feat, float* out0,
+                            float* out1, const int* roff3, int maxS, hipStream_t st) {
+    if (sg.what == ACX_SEG_EMBED) return launch_segment_pool(c, x3, B, S, sg.pool, out0, roff3, maxS, st);
+    ACX_TRY(launch_segment_pool(c, x3, B, S, sg.pool, feat, roff3, maxS, st));
+    ACX_TRY(launch_segment_head(c, feat, rows, out0, out1, st));
+    if (sg.clip) return launch_segment_clipmax(out1, B, S, c->num_classes, sg.clip, roff3, st);
+    return ACX_OK;
+}
+
 // wstart: windows (acx_forward_windows) -- clip b's samples start at wav + wstart[b] (device table), not at wav + b L
+// seg: the segment tail instead of `mode`'s
 static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws,
-                       const Plan& p, hipStream_t st, const long long* wstart = nullptr) {
+                       const Plan& p, hipStream_t st, const long long* wstart = nullptr, const SegTail* seg = nullptr) {
     float* feat = (float*)(ws + p.off_feat);
     float* x[4];
     for (int s = 0; s < 4; ++s) x[s] = (float*)(ws + p.off_x[s]);
@@ -814,6 +832,7 @@ static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode,
             ACX_TRY(run_block(c, s, j, x[s], y, hidden, stats, B, p.Hs[s], p.Ws[s], st, ln_out));
         }
     }
+    if (seg) return run_segment_tail(c, *seg, x[3], B, p.Hs[3], (long long)B * p.Hs[3], feat, out0, out1, nullptr, p.Hs[3], st);
     if (mode == ACX_MODE_FRAME) return launch_nhwc_to_nchw(c, x[3], out0, B, p.Hs[3], p.Ws[3], kDims[3], st);
     if (mode == ACX_MODE_SCENE) return launch_pool_head(c, x[3], B, p.Hs[3], out0, nullptr, nullptr, st);
     if (head_tiled(c)) {       // wide head: scene rows into `feat` (idle since the stem, >= 24 x 224 floats per clip), then the head
@@ -826,7 +845,7 @@ static int forward_one(acx_ctx* c, const float* wav, int B, int64_t L, int mode,
 // The uniform forward of acx_forward and acx_forward_windows (arguments checked by the caller).  wstart: the window table --
 // sub-batch i gets its slice of it and the whole of wav.
 static int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws,
-                           hipStream_t st, const long long* wstart) {
+                           hipStream_t st, const long long* wstart, const SegTail* seg = nullptr) {
     // Clips are independent: a large batch runs as sub-batches on separate streams (fork/join with events, so the call
     // still looks like one unit of work on `stream` and stays graph-capturable).  Per-kernel event profiling runs
     // un-split to keep launch durations clean.  The kernels of the 16-bit arithmetics are CU-exclusive -- nothing
@@ -852,8 +871,11 @@ static int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int m
             Plan pi;
             rc = make_plan(Bi, L, &pi);
             if (rc != ACX_OK) break;
-            const size_t per_clip = mode == ACX_MODE_FRAME ? (size_t)kDims[3] * pi.Hs[3] * pi.Ws[3]
+            const size_t per_clip = seg ? (size_t)pi.Hs[3] * (seg->what == ACX_SEG_EMBED ? (size_t)kDims[3] : (size_t)c->num_classes)
+                                  : mode == ACX_MODE_FRAME ? (size_t)kDims[3] * pi.Hs[3] * pi.Ws[3]
                                                            : (mode == ACX_MODE_SCENE ? (size_t)kDims[3] : (size_t)c->num_classes);
+            SegTail sgi{};
+            if (seg) { sgi = *seg; if (sgi.clip) sgi.clip += (size_t)b_off * c->num_classes; }
             hipStream_t si = i == 0 ? st : aux.streams[i - 1];
             if (i > 0) {
                 he = hipStreamWaitEvent(si, aux.fork, 0);
@@ -861,7 +883,8 @@ static int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int m
                 forked = i;
             }
             rc = forward_one(c, wstart ? wav : wav + (size_t)b_off * L, Bi, L, mode, out0 + b_off * per_clip,
-                             out1 ? out1 + b_off * per_clip : nullptr, ws + ws_off, pi, si, wstart ? wstart + b_off : nullptr);
+                             out1 ? out1 + b_off * per_clip : nullptr, ws + ws_off, pi, si, wstart ? wstart + b_off : nullptr,
+                             seg ? &sgi : nullptr);
             ws_off += pi.total;
             b_off += Bi;
             if (rc == ACX_OK && c->fail_sub.load(std::memory_order_relaxed) == i) {
@@ -880,7 +903,7 @@ static int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int m
     }
     Plan p;
     ACX_TRY(make_plan(B, L, &p));
-    return forward_one(c, wav, B, L, mode, out0, out1, ws, p, st, wstart);
+    return forward_one(c, wav, B, L, mode, out0, out1, ws, p, st, wstart, seg);
 }
 
 }  // extern "C"
@@ -923,12 +946,9 @@ int acx_workspace_bytes_windows(const acx_ctx* c, int count, int64_t window, int
     return ACX_OK;
 }
 
-int acx_forward_windows(acx_ctx* c, const float* wav, const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t first,
-                        int count, int mode, float* out0, float* out1, void* workspace, size_t workspace_bytes, void* stream) {
-    ACX_TRY(need_ready(c));
-    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: null pointer");
-    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: bad mode %d", mode);
-    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: logits mode needs out1 (probs)");
+static int forward_windows_impl(acx_ctx* c, const float* wav, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                                int64_t first, int count, int mode, float* out0, float* out1, void* workspace,
+                                size_t workspace_bytes, void* stream, const SegTail* seg) {
     int64_t n = 0;
     ACX_TRY(window_check(lengths, R, window, hop, &n));
     for (int r = 0; r < R; ++r)
@@ -946,7 +966,17 @@ int acx_forward_windows(acx_ctx* c, const float* wav, const int64_t* lengths, in
     long long* wstart = (long long*)workspace;
     // on the caller's stream, before forward_uniform records the fork event: every sub-batch reads its slice after it
     ACX_TRY(launch_window_table(lengths, R, window, hop, first, count, wstart, st));
-    return forward_uniform(c, wav, count, window, mode, out0, out1, (char*)workspace + align_up((size_t)count * 8), st, wstart);
+    return forward_uniform(c, wav, count, window, mode, out0, out1, (char*)workspace + align_up((size_t)count * 8), st, wstart, seg);
+}
+
+int acx_forward_windows(acx_ctx* c, const float* wav, const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t first,
+                        int count, int mode, float* out0, float* out1, void* workspace, size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: null pointer");
+    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: bad mode %d", mode);
+    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward_windows: logits mode needs out1 (probs)");
+    return forward_windows_impl(c, wav, lengths, R, window, hop, first, count, mode, out0, out1, workspace, workspace_bytes, stream,
+                                nullptr);
 }
 
 int acx_window_timeline_classes(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
@@ -995,12 +1025,8 @@ int acx_workspace_bytes_varlen(const acx_ctx* c, const int64_t* lengths, int B, 
     return ACX_OK;
 }
 
-int acx_forward_varlen(acx_ctx* c, const float* wav, const int64_t* lengths, int B, int mode, float* out0, float* out1,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-    ACX_TRY(need_ready(c));
-    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: null pointer");
-    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: bad mode %d", mode);
-    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: logits mode needs out1 (probs)");
+static int forward_varlen_impl(acx_ctx* c, const float* wav, const int64_t* lengths, int B, int mode, float* out0, float* out1,
+                               void* workspace, size_t workspace_bytes, void* stream, const SegTail* seg) {
     if (((uintptr_t)workspace & 255) != 0) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     char* ws = (char*)workspace;
     VarPlan p;
@@ -1030,6 +1056,7 @@ int acx_forward_varlen(acx_ctx* c, const float* wav, const int64_t* lengths, int
             ACX_TRY(run_block(c, s, j, x[s], y, hidden, stats, 1, g.rows[s], Wd, st, ln_out, &g));
         }
     }
+    if (seg) return run_segment_tail(c, *seg, x[3], B, 0, g.rows[3], feat, out0, out1, g.roff[3], g.maxH[3], st);
     if (mode == ACX_MODE_FRAME) return launch_nhwc_to_nchw_varlen(c, x[3], out0, g, st);
     if (mode == ACX_MODE_SCENE) return launch_pool_head_varlen(c, x[3], g, out0, nullptr, nullptr, st);
     if (head_tiled(c)) {       // as in forward_one: scene rows into `feat` (>= 24 x 224 floats per clip), then the tiled head
@@ -1037,6 +1064,125 @@ int acx_forward_varlen(acx_ctx* c, const float* wav, const int64_t* lengths, int
         return launch_head_tiled(c, feat, B, out0, out1, st);
     }
     return launch_pool_head_varlen(c, x[3], g, nullptr, out0, out1, st);
+}
+
+int acx_forward_varlen(acx_ctx* c, const float* wav, const int64_t* lengths, int B, int mode, float* out0, float* out1,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (!wav || !out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: null pointer");
+    if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: bad mode %d", mode);
+    if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "acx_forward_varlen: logits mode needs out1 (probs)");
+    return forward_varlen_impl(c, wav, lengths, B, mode, out0, out1, workspace, workspace_bytes, stream, nullptr);
+}
+
+// ---- sound event detection: segment-wise outputs (segments.hip) --------------------------------------------------------------
+static int seg_check(const char* who, int pool, int what, const void* wav, const float* out0, const float* out1, const void* ws) {
+    if (!wav || !out0 || !ws) ACX_FAIL(ACX_ERR_ARG, "%s: null pointer", who);
+    if (what != ACX_SEG_OUTPUT && what != ACX_SEG_EMBED) ACX_FAIL(ACX_ERR_ARG, "%s: bad `what` %d", who, what);
+    if (what == ACX_SEG_OUTPUT && !out1) ACX_FAIL(ACX_ERR_ARG, "%s: ACX_SEG_OUTPUT needs out1 (segment probabilities)", who);
+    if (pool < 1 || pool > ACX_MAX_SEGMENT_POOL || !(pool & 1))
+        ACX_FAIL(ACX_ERR_ARG, "%s: pool = %d (expected an odd number in 1 .. %d)", who, pool, ACX_MAX_SEGMENT_POOL);
+    return ACX_OK;
+}
+
+int acx_segment_count(int64_t L, int* S) {
+    if (!S) ACX_FAIL(ACX_ERR_ARG, "acx_segment_count: S is null");
+    Plan p;
+    ACX_TRY(make_plan(1, L, &p));
+    *S = p.Hs[3];
+    return ACX_OK;
+}
+
+int acx_workspace_bytes_segments(const acx_ctx* c, int B, int64_t L, int what, size_t* out_bytes) {
+    if (what != ACX_SEG_OUTPUT && what != ACX_SEG_EMBED) ACX_FAIL(ACX_ERR_ARG, "acx_workspace_bytes_segments: bad `what` %d", what);
+    return acx_workspace_bytes(c, B, L, ACX_MODE_LOGITS, out_bytes);
+}
+
+int acx_forward_segments(acx_ctx* c, const float* wav, int B, int64_t L, int pool, int what, float* out0, float* out1, float* clip,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    ACX_TRY(seg_check("acx_forward_segments", pool, what, wav, out0, out1, workspace));
+    size_t need = 0;
+    ACX_TRY(acx_workspace_bytes(c, B, L, ACX_MODE_LOGITS, &need));
+    if (workspace_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    const SegTail sg{pool, what, what == ACX_SEG_OUTPUT ? clip : nullptr};
+    return forward_uniform(c, wav, B, L, ACX_MODE_LOGITS, out0, out1, (char*)workspace, (hipStream_t)stream, nullptr, &sg);
+}
+
+int acx_workspace_bytes_segments_varlen(const acx_ctx* c, const int64_t* lengths, int B, int what, size_t* out_bytes) {
+    if (what != ACX_SEG_OUTPUT && what != ACX_SEG_EMBED)
+        ACX_FAIL(ACX_ERR_ARG, "acx_workspace_bytes_segments_varlen: bad `what` %d", what);
+    return acx_workspace_bytes_varlen(c, lengths, B, ACX_MODE_LOGITS, out_bytes);
+}
+
+int acx_forward_segments_varlen(acx_ctx* c, const float* wav, const int64_t* lengths, int B, int pool, int what, float* out0,
+                                float* out1, float* clip, void* workspace, size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    ACX_TRY(seg_check("acx_forward_segments_varlen", pool, what, wav, out0, out1, workspace));
+    const SegTail sg{pool, what, what == ACX_SEG_OUTPUT ? clip : nullptr};
+    return forward_varlen_impl(c, wav, lengths, B, ACX_MODE_LOGITS, out0, out1, workspace, workspace_bytes, stream, &sg);
+}
+
+int acx_workspace_bytes_segments_windows(const acx_ctx* c, int count, int64_t window, int what, size_t* out_bytes) {
+    if (what != ACX_SEG_OUTPUT && what != ACX_SEG_EMBED)
+        ACX_FAIL(ACX_ERR_ARG, "acx_workspace_bytes_segments_windows: bad `what` %d", what);
+    return acx_workspace_bytes_windows(c, count, window, ACX_MODE_LOGITS, out_bytes);
+}
+
+int acx_forward_segments_windows(acx_ctx* c, const float* wav, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                                 int64_t first, int count, int pool, int what, float* out0, float* out1, float* clip,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    ACX_TRY(seg_check("acx_forward_segments_windows", pool, what, wav, out0, out1, workspace));
+    const SegTail sg{pool, what, what == ACX_SEG_OUTPUT ? clip : nullptr};
+    return forward_windows_impl(c, wav, lengths, R, window, hop, first, count, ACX_MODE_LOGITS, out0, out1, workspace,
+                                workspace_bytes, stream, &sg);
+}
+
+int acx_segment_head(acx_ctx* c, const float* x, int B, int S, int pool, float* emb, float* logits, float* probs, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (!x || !emb) ACX_FAIL(ACX_ERR_ARG, "acx_segment_head: null pointer");
+    if (!logits != !probs) ACX_FAIL(ACX_ERR_ARG, "acx_segment_head: logits and probs go together (both or neither)");
+    if (pool < 1 || pool > ACX_MAX_SEGMENT_POOL || !(pool & 1))
+        ACX_FAIL(ACX_ERR_ARG, "acx_segment_head: pool = %d (expected an odd number in 1 .. %d)", pool, ACX_MAX_SEGMENT_POOL);
+    if (B <= 0 || S <= 0) ACX_FAIL(ACX_ERR_SHAPE, "acx_segment_head: %d clips of %d segments", B, S);
+    ACX_TRY(launch_segment_pool(c, x, B, S, pool, emb, nullptr, S, (hipStream_t)stream));
+    if (!logits) return ACX_OK;
+    return launch_segment_head(c, emb, (long long)B * S, logits, probs, (hipStream_t)stream);
+}
+
+int acx_segment_expand(const float* probs, int B, int S, int N, int T, float* frame, void* stream) {
+    if (!probs || !frame) ACX_FAIL(ACX_ERR_ARG, "acx_segment_expand: null pointer");
+    if (N < 1 || N > ACX_MAX_CLASSES) ACX_FAIL(ACX_ERR_ARG, "acx_segment_expand: %d classes (expected 1 .. %d)", N, ACX_MAX_CLASSES);
+    if (B <= 0 || S <= 0 || T <= 0) ACX_FAIL(ACX_ERR_SHAPE, "acx_segment_expand: %d clips, %d segments, %d frames", B, S, T);
+    return launch_segment_expand(probs, B, S, N, T, frame, (hipStream_t)stream);
+}
+
+int acx_segment_expand_varlen(const float* probs, const int64_t* lengths, int B, int N, float* frame, void* stream) {
+    if (!probs || !frame || !lengths) ACX_FAIL(ACX_ERR_ARG, "acx_segment_expand_varlen: null pointer");
+    if (N < 1 || N > ACX_MAX_CLASSES)
+        ACX_FAIL(ACX_ERR_ARG, "acx_segment_expand_varlen: %d classes (expected 1 .. %d)", N, ACX_MAX_CLASSES);
+    if (B <= 0 || B > kVarMaxClips) ACX_FAIL(ACX_ERR_ARG, "acx_segment_expand_varlen: %d clips (expected 1 .. %d)", B, kVarMaxClips);
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] < ACX_MIN_SAMPLES || lengths[b] > 0x7fffffffLL)
+            ACX_FAIL(ACX_ERR_SHAPE, "acx_segment_expand_varlen: clip %d has %lld samples (expected %d .. 2^31 - 1)", b,
+                     (long long)lengths[b], ACX_MIN_SAMPLES);
+    return launch_segment_expand_varlen(probs, lengths, B, N, frame, (hipStream_t)stream);
+}
+
+int acx_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop, int reduce,
+                         float* out, void* stream) {
+    if (!probs || !out) ACX_FAIL(ACX_ERR_ARG, "acx_segment_timeline: null pointer");
+    if (classes < 1 || classes > ACX_MAX_CLASSES)
+        ACX_FAIL(ACX_ERR_ARG, "acx_segment_timeline: %d classes (expected 1 .. %d)", classes, ACX_MAX_CLASSES);
+    if (reduce != 0 && reduce != 1) ACX_FAIL(ACX_ERR_ARG, "acx_segment_timeline: bad reduce %d (0 mean, 1 max)", reduce);
+    ACX_TRY(window_check(lengths, R, window, hop, nullptr));
+    for (int r = 0; r < R; ++r)
+        if (lengths[r] != 0 && lengths[r] < ACX_MIN_SAMPLES)
+            ACX_FAIL(ACX_ERR_SHAPE, "acx_segment_timeline: recording %d of %lld samples is shorter than the %d a clip needs", r,
+                     (long long)lengths[r], ACX_MIN_SAMPLES);
+    return launch_segment_timeline(probs, classes, lengths, R, window, hop, reduce, out, (hipStream_t)stream);
 }
 
 int acx_logmel_bn0(acx_ctx* c, const float* wav, int B, int64_t L, float* out, int apply_bn0, void* stream) {

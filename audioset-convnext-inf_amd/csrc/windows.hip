@@ -78,6 +78,48 @@ __global__ __launch_bounds__(256) void window_timeline_kernel(WinArgs a, const f
     }
 }
 
+// The timeline at segment resolution (acx_segment_timeline).  Window j of recording r holds min(W, L_r) samples and
+// S_r = seg_count(min(W, L_r)) segments of 10240 samples, the last one reaching to the window's end; probs holds the windows'
+// (S_r, N) blocks in window order.  Row k of recording r has the midpoint m = min(10240 k + 5120, L_r - 1); the windows that
+// cover it are the run of window_timeline_kernel, and each contributes the one segment min((m - s_j) / 10240, S_r - 1).
+struct SegWinPrefix {
+    long long poff[kVarMaxClips], toff[kVarMaxClips + 1];       // first probs row / first timeline row of recording r
+};
+__global__ __launch_bounds__(256) void segment_timeline_kernel(WinArgs a, const float* __restrict__ probs, int N, int reduce,
+                                                               float* __restrict__ out) {
+    __shared__ SegWinPrefix p;
+    if (threadIdx.x == 0) {
+        long long w = 0, t = 0;
+        for (int r = 0; r < a.R; ++r) {
+            const long long L = a.len[r];
+            p.poff[r] = w; p.toff[r] = t;
+            w += win_count(L, a.W, a.H) * seg_count(L < a.W ? L : a.W);
+            t += (L + kSegSamples - 1) / kSegSamples;
+        }
+        p.toff[a.R] = t;
+    }
+    __syncthreads();
+    const long long rows = p.toff[a.R];
+    for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int r = win_find(p.toff, a.R, row);
+        const long long L = a.len[r], k = row - p.toff[r], n = win_count(L, a.W, a.H);
+        const int Sr = seg_count(L < a.W ? L : a.W);
+        long long m = k * kSegSamples + kSegSamples / 2;
+        if (m > L - 1) m = L - 1;
+        const long long j0 = m >= a.W ? (m - a.W) / a.H + 1 : 0;
+        long long j1 = j0;
+        while (j1 < n && win_start(j1, L, a.W, a.H) <= m) ++j1;
+        const float* pr = probs + p.poff[r] * N;
+        const long long W = a.W, H = a.H;
+        auto seg_row = [pr, N, Sr, m, L, W, H](long long j) {
+            long long i = (m - win_start(j, L, W, H)) / kSegSamples;
+            if (i > Sr - 1) i = Sr - 1;
+            return pr + (j * Sr + i) * N;
+        };
+        for (int c = threadIdx.x; c < N; c += 256) out[row * N + c] = win_reduce(seg_row, j0, j1 - j0, c, reduce);
+    }
+}
+
 int window_check(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t* n_windows) {
     if (window < ACX_MIN_SAMPLES)
         ACX_FAIL(ACX_ERR_SHAPE,
@@ -123,6 +165,18 @@ int launch_window_timeline(const float* probs, int classes, const int64_t* lengt
     const unsigned blocks = (unsigned)(rows < 4096 ? rows : 4096);
     launch_kernel(&window_timeline_kernel, dim3(blocks), dim3(256), 0, s, win_args(lengths, R, window, hop), probs, classes, reduce,
                   out);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int launch_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                            int reduce, float* out, hipStream_t s) {
+    long long rows = 0;
+    for (int r = 0; r < R; ++r) rows += (lengths[r] + kSegSamples - 1) / kSegSamples;
+    if (rows == 0) return ACX_OK;
+    const unsigned blocks = (unsigned)(rows < 4096 ? rows : 4096);
+    launch_kernel(&segment_timeline_kernel, dim3(blocks), dim3(256), 0, s, win_args(lengths, R, window, hop), probs, classes,
+                  reduce, out);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

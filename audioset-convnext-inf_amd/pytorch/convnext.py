@@ -22,6 +22,7 @@ from .. import frontend_tables as ft
 from . import resample as _rs
 from . import windows as _win
 from . import stream as _stream
+from . import segments as _seg
 
 HF_PYTORCH_WEIGHTS_NAME = "model.safetensors"     # convnext.py:29
 HF_CONFIG_NAME = "config.yaml"                    # convnext.py:31
@@ -400,16 +401,115 @@ class ConvNeXt(nn.Module):
         _rs.check_min_length(x.shape[1], rate)
         return _rs.resample(x, rate, _rs.MODEL_RATE, _cache=self._resamplers)
 
-    def forward_varlen(self, clips, lengths=None, what="logits", sample_rate=None):
+    def _run_segments(self, x, pool, what):
+        """(B, L) at 32 kHz -> acx_forward_segments: (logits, probs, clip maximum) each over (B, S, N) / (B, N) for
+        what = SEG_OUTPUT, (embeddings (B, S, 768), None, None) for SEG_EMBED."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise ValueError("expected a (batch, samples) waveform tensor, got %r" % (getattr(x, "shape", type(x)),))
+        self._check_run(x.device)
+        x = x.detach().to(torch.float32).contiguous()
+        B, L = x.shape
+        if L < _ffi.MIN_SAMPLES:
+            raise RuntimeError("clip of %d samples is too short: kernel size can't be greater than actual input size "
+                               "(minimum is %d samples)" % (L, _ffi.MIN_SAMPLES))
+        S = _seg.segment_count(L)
+        with torch.cuda.device(x.device):
+            ctx = self.native_context(x.device)
+            ws = self._workspace(x.device, ctx.workspace_bytes_segments(B, L, what))
+            if what == _ffi.SEG_OUTPUT:
+                out0 = torch.empty((B, S, ctx.classes), dtype=torch.float32, device=x.device)
+                out1 = torch.empty((B, S, ctx.classes), dtype=torch.float32, device=x.device)
+                clip = torch.empty((B, ctx.classes), dtype=torch.float32, device=x.device)
+            else:
+                out0, out1, clip = torch.empty((B, S, 768), dtype=torch.float32, device=x.device), None, None
+            _ffi.check(_ffi.lib().acx_forward_segments(ctx.handle, _ffi.ptr(x), B, L, pool, what, _ffi.ptr(out0), _ffi.ptr(out1),
+                                                       _ffi.ptr(clip), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(x.device)))
+        return out0, out1, clip
+
+    def _run_varlen_segments(self, wav, lengths, pool, what):
+        """_run_varlen for the segment outputs: rows of all clips back to back, sum(S_i) of them."""
+        B = len(lengths)
+        rows = sum(_seg.segment_count(n) for n in lengths)
+        dev = wav.device
+        with torch.cuda.device(dev):
+            ctx = self.native_context(dev)
+            ws = self._workspace(dev, ctx.workspace_bytes_segments_varlen(lengths, what))
+            if what == _ffi.SEG_OUTPUT:
+                out0 = torch.empty((rows, ctx.classes), dtype=torch.float32, device=dev)
+                out1 = torch.empty((rows, ctx.classes), dtype=torch.float32, device=dev)
+                clip = torch.empty((B, ctx.classes), dtype=torch.float32, device=dev)
+            else:
+                out0, out1, clip = torch.empty((rows, 768), dtype=torch.float32, device=dev), None, None
+            lens = (ctypes.c_int64 * B)(*lengths)
+            _ffi.check(_ffi.lib().acx_forward_segments_varlen(ctx.handle, _ffi.ptr(wav), lens, B, pool, what, _ffi.ptr(out0),
+                                                              _ffi.ptr(out1), _ffi.ptr(clip), _ffi.ptr(ws), ws.numel(),
+                                                              _ffi.stream_ptr(dev)))
+        return out0, out1, clip
+
+    def _check_segment_call(self, pool):
+        """ValueError for a bad pool or a model in train mode, before anything touches the GPU."""
+        _seg.check_pool(pool)
+        if self.training:
+            raise ValueError("inference-only path: call model.eval() first (segment outputs have no training branch)")
+
+    def forward_segments(self, x, pool=3, resolution="segment", sample_rate=None):
+        """Sound event detection: WHEN inside a clip something happens, at the cost of one forward.  The reference's
+        decision-level recipe (pytorch/models.py:5757-5771) on this trunk's stage-3 map, whose rows are segments of 0.32 s
+        (pytorch/segments.py): mean over frequency, max + average over `pool` segments (odd, 1 .. 31), the final LayerNorm and
+        the head per segment, sigmoid.  (B, L) -> dict:
+          "segmentwise_logits" / "segmentwise_output"  (B, S, N), S = L // 10240 up to rounding (segments.segment_count);
+          "clipwise_output"   (B, N), the maximum over segments (models.py:5767) -- NOT model(x)["clipwise_output"], which
+                              pools the whole clip before the head;
+          "segment_edges"     float64 CPU tensor of S + 1 boundaries in seconds of the input audio;
+          "framewise_output"  (B, T, N) with resolution="frame": every segment repeated over its 32 STFT frames, the last one to
+                              the clip's end (interpolate + pad_framewise_output, pytorch_utils.py:140-176) -- the key
+                              pytorch/inference.py:156 (sound_event_detection) reads.
+        The tail is fp32 in every precision mode.  A clip's rows are bit-identical alone, anywhere in a batch, through
+        forward_varlen and as a window of forward_windows.  The reference ConvNeXt was trained with global pooling only: these
+        are its decision-level recipe applied to it, not outputs its authors evaluated."""
+        self._check_segment_call(pool)
+        if resolution not in ("segment", "frame"):
+            raise ValueError("resolution must be 'segment' or 'frame' (got %r)" % (resolution,))
+        rate = self._rate(sample_rate)
+        x_in = x
+        x = self._resampled(x_in, sample_rate)
+        logits, probs, clip = self._run_segments(x, pool, _ffi.SEG_OUTPUT)
+        B, S, N = probs.shape
+        L = x.shape[1]
+        duration = None if rate is None else x_in.shape[1] / rate        # (both calls above have checked the input's shape)
+        out = {"segmentwise_logits": logits, "segmentwise_output": probs, "clipwise_output": clip,
+               "segment_edges": torch.from_numpy(_seg.segment_edges(L, duration))}
+        if resolution == "frame":
+            T = _ffi.num_frames(L)
+            frame = torch.empty((B, T, N), dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                _ffi.check(_ffi.lib().acx_segment_expand(_ffi.ptr(probs), B, S, N, T, _ffi.ptr(frame), _ffi.stream_ptr(x.device)))
+            out["framewise_output"] = frame
+        return out
+
+    def forward_segment_embeddings(self, x, pool=3, sample_rate=None):
+        """(B, L) -> (B, S, 768): the embedding of every 0.32 s segment -- forward_segments' rows in front of the head, i.e.
+        forward_scene_embeddings' recipe (convnext.py:279-285) with the pooling over `pool` segments instead of the clip.  The
+        rows are valid fit_head / tagging_metrics inputs as they are (`.reshape(-1, 768)`), so a head can be trained and scored
+        on strong labels."""
+        self._check_segment_call(pool)
+        return self._run_segments(self._resampled(x, sample_rate), pool, _ffi.SEG_EMBED)[0]
+
+    def forward_varlen(self, clips, lengths=None, what="logits", sample_rate=None, pool=3):
         """Clips of different lengths in one packed forward (acx_forward_varlen); every clip's result is bit-identical to the
         uniform forward of that clip alone.  clips: a list of 1-D CUDA tensors, or one packed 1-D CUDA tensor plus `lengths`.
         what: "logits" -> {"clipwise_output", "clipwise_logits"} each (B, N); "scene" -> (B, 768); "frame" -> a list of
-        (768, T'_i, 7) views into one output buffer.  More than 256 clips run as several calls.
+        (768, T'_i, 7) views into one output buffer; "segment" -> a list with one dict per clip, "segmentwise_logits" /
+        "segmentwise_output" (S_i, N) and "clipwise_output" (N,), the maximum over the clip's segments; "segment_embeddings" ->
+        a list of (S_i, 768) views (forward_segments / forward_segment_embeddings with `pool`).  More than 256 clips run as
+        several calls.
         sample_rate: the clips' rate (lengths count input samples); other than None / 32000 they are resampled to 32 kHz on
         the device first (acx_resample), each clip's bits the same as model(clip[None], sample_rate=...)."""
         rate = self._rate(sample_rate)
-        if what not in ("logits", "scene", "frame"):
-            raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
+        if what not in ("logits", "scene", "frame", "segment", "segment_embeddings"):
+            raise ValueError("what must be 'logits', 'scene', 'frame', 'segment' or 'segment_embeddings' (got %r)" % (what,))
+        if what in ("segment", "segment_embeddings"):
+            self._check_segment_call(pool)
         if isinstance(clips, torch.Tensor):
             if lengths is None:
                 raise ValueError("a packed tensor needs `lengths`")
@@ -446,8 +546,26 @@ class ConvNeXt(nn.Module):
                 raise RuntimeError("clip %d of %d samples is too short: kernel size can't be greater than actual input size "
                                    "(minimum is %d samples)" % (i, n, _ffi.MIN_SAMPLES))
         wav = wav.detach().to(torch.float32).contiguous()
-        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
         cap = _ffi.MAX_VARLEN_CLIPS
+        if what in ("segment", "segment_embeddings"):
+            res, s0 = [], 0
+            for c0 in range(0, len(lengths), cap):
+                chunk = lengths[c0:c0 + cap]
+                n = sum(chunk)
+                out0, out1, clip = self._run_varlen_segments(wav[s0:s0 + n], chunk, pool,
+                                                             _ffi.SEG_OUTPUT if what == "segment" else _ffi.SEG_EMBED)
+                s0 += n
+                r0 = 0
+                for i, L in enumerate(chunk):
+                    r1 = r0 + _seg.segment_count(L)
+                    if what == "segment":
+                        res.append({"segmentwise_logits": out0[r0:r1], "segmentwise_output": out1[r0:r1],
+                                    "clipwise_output": clip[i]})
+                    else:
+                        res.append(out0[r0:r1])
+                    r0 = r1
+            return res
+        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
         parts, s0 = [], 0
         for c0 in range(0, len(lengths), cap):
             chunk = lengths[c0:c0 + cap]
@@ -494,8 +612,88 @@ class ConvNeXt(nn.Module):
                                                           _ffi.stream_ptr(dev)))
         return out0, out1
 
+    def _run_windows_segments(self, wav, lengths, W, H, pool, what, max_batch):
+        """_run_windows for the segment outputs: (n, S_W, .) blocks in window order, plus the (n, N) clip maxima."""
+        n = _ffi.window_count(lengths, W, H)
+        S = _seg.segment_count(W)
+        dev = wav.device
+        with torch.cuda.device(dev):
+            ctx = self.native_context(dev)
+            if what == _ffi.SEG_OUTPUT:
+                out0 = torch.empty((n, S, ctx.classes), dtype=torch.float32, device=dev)
+                out1 = torch.empty((n, S, ctx.classes), dtype=torch.float32, device=dev)
+                clip = torch.empty((n, ctx.classes), dtype=torch.float32, device=dev)
+            else:
+                out0, out1, clip = torch.empty((n, S, 768), dtype=torch.float32, device=dev), None, None
+            ws = self._workspace(dev, ctx.workspace_bytes_segments_windows(min(n, max_batch), W, what))
+            lens = (ctypes.c_int64 * len(lengths))(*lengths)
+            for first in range(0, n, max_batch):
+                count = min(max_batch, n - first)
+                sl = slice(first, first + count)
+                _ffi.check(_ffi.lib().acx_forward_segments_windows(
+                    ctx.handle, _ffi.ptr(wav), lens, len(lengths), W, H, first, count, pool, what, _ffi.ptr(out0[sl]),
+                    _ffi.ptr(None if out1 is None else out1[sl]), _ffi.ptr(None if clip is None else clip[sl]), _ffi.ptr(ws),
+                    ws.numel(), _ffi.stream_ptr(dev)))
+        return out0, out1, clip
+
+    def _forward_windows_segments(self, wav, lengths, offs, W, H, what, pool, timeline, max_batch):
+        """The per-recording dicts of forward_windows(what="segment" | "segment_embeddings")."""
+        results = []
+        cap = _ffi.MAX_VARLEN_CLIPS
+        seg_what = _ffi.SEG_OUTPUT if what == "segment" else _ffi.SEG_EMBED
+        for c0 in range(0, len(lengths), cap):
+            idx = range(c0, min(c0 + cap, len(lengths)))
+            long_ = [i for i in idx if lengths[i] > W]
+            short = [i for i in idx if lengths[i] <= W]
+            per = {}                  # recording -> (out0 blocks, out1 blocks or None, clip rows or None)
+            if long_:
+                if long_ == list(range(long_[0], long_[-1] + 1)):
+                    packed = wav[offs[long_[0]]:offs[long_[-1] + 1]]
+                else:
+                    packed = torch.cat([wav[offs[i]:offs[i + 1]] for i in long_])
+                out0, out1, clip = self._run_windows_segments(packed, [lengths[i] for i in long_], W, H, pool, seg_what, max_batch)
+                w0 = 0
+                for i in long_:
+                    n = _win.window_count(lengths[i], W, H)
+                    per[i] = (out0[w0:w0 + n], None if out1 is None else out1[w0:w0 + n], None if clip is None else clip[w0:w0 + n])
+                    w0 += n
+            if short:
+                res = self.forward_varlen([wav[offs[i]:offs[i + 1]] for i in short], what=what, pool=pool)
+                for k, i in enumerate(short):
+                    if what == "segment":
+                        per[i] = (res[k]["segmentwise_logits"][None], res[k]["segmentwise_output"][None],
+                                  res[k]["clipwise_output"][None])
+                    else:
+                        per[i] = (res[k][None], None, None)
+            tl = None
+            if what == "segment" and timeline is not None:
+                n_cls = per[idx[0]][1].shape[-1]
+                probs = torch.cat([per[i][1].reshape(-1, n_cls) for i in idx]).contiguous()
+                chunk = [lengths[i] for i in idx]
+                rows = sum((n + _seg.SEGMENT_SAMPLES - 1) // _seg.SEGMENT_SAMPLES for n in chunk)
+                tl = torch.empty((rows, n_cls), dtype=torch.float32, device=wav.device)
+                lens = (ctypes.c_int64 * len(chunk))(*chunk)
+                with torch.cuda.device(wav.device):
+                    _ffi.check(_ffi.lib().acx_segment_timeline(_ffi.ptr(probs), n_cls, lens, len(chunk), W, H,
+                                                               1 if timeline == "max" else 0, _ffi.ptr(tl),
+                                                               _ffi.stream_ptr(wav.device)))
+            t0 = 0
+            for i in idx:
+                starts = _win.window_starts([lengths[i]], W, H)
+                d = {"starts": torch.tensor(starts, dtype=torch.float64) / _rs.MODEL_RATE}
+                if what == "segment":
+                    d["segmentwise_logits"], d["segmentwise_output"], d["clipwise_output"] = per[i]
+                    if tl is not None:
+                        steps = (lengths[i] + _seg.SEGMENT_SAMPLES - 1) // _seg.SEGMENT_SAMPLES
+                        d["timeline"] = tl[t0:t0 + steps]
+                        t0 += steps
+                else:
+                    d["segment_embeddings"] = per[i][0]
+                results.append(d)
+        return results
+
     def forward_windows(self, recordings, window=10.0, hop=None, what="logits", sample_rate=None, max_batch=64,
-                        timeline="mean"):
+                        timeline="mean", pool=3):
         """Sliding-window tagging of long recordings (pytorch/windows.py has the definition).  Every window's outputs are
         bit-identical to the uniform forward of that window cut out and run alone.
 
@@ -505,11 +703,18 @@ class ConvNeXt(nn.Module):
         (ceil(L / hop), N), the per-step mean or max of the probabilities over the windows covering the step's midpoint
         (timeline="mean" | "max" | None); "scene" -> "scene" (n, 768); "frame" -> "frame" (n, 768, T', 7).  Recordings longer
         than the window run max_batch windows per call (acx_forward_windows); shorter ones are one window, the clip itself
-        (forward_varlen).  sample_rate: the recordings' rate; they are resampled to 32 kHz on the device first (acx_resample)
+        (forward_varlen).  what="segment" (forward_segments with `pool` on every window) -> "segmentwise_logits" /
+        "segmentwise_output" (n, S_W, N), "clipwise_output" (n, N) and "timeline" at SEGMENT resolution: ceil(L / 10240) rows of
+        0.32 s, row k the mean or max over the windows covering its midpoint of the one segment of each that holds it
+        (pytorch/segments.py, segment_timeline_cover) -- with hop = window a gap-free 0.32 s timeline for one forward per
+        window; "segment_embeddings" -> "segment_embeddings" (n, S_W, 768).  A recording not longer than the window gives one
+        block of its own S rows.  sample_rate: the recordings' rate; they are resampled to 32 kHz on the device first (acx_resample)
         and the starts stay in seconds of the original audio."""
         rate = self._rate(sample_rate)
-        if what not in ("logits", "scene", "frame"):
-            raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
+        if what not in ("logits", "scene", "frame", "segment", "segment_embeddings"):
+            raise ValueError("what must be 'logits', 'scene', 'frame', 'segment' or 'segment_embeddings' (got %r)" % (what,))
+        if what in ("segment", "segment_embeddings"):
+            self._check_segment_call(pool)
         if timeline not in ("mean", "max", None):
             raise ValueError("timeline must be 'mean', 'max' or None (got %r)" % (timeline,))
         if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
@@ -537,11 +742,14 @@ class ConvNeXt(nn.Module):
             if n < _ffi.MIN_SAMPLES:
                 raise RuntimeError("recording %d of %d samples at %d Hz is too short: kernel size can't be greater than actual "
                                    "input size (minimum is %d samples)" % (i, n, _rs.MODEL_RATE, _ffi.MIN_SAMPLES))
-        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
-        key ={"logits": "clipwise_logits", "scene": "scene", "frame": "frame"}[what]
         offs = [0]
         for n in lengths:
             offs.append(offs[-1] + n)
+        if what in ("segment", "segment_embeddings"):
+            results = self._forward_windows_segments(wav, lengths, offs, W, H, what, pool, timeline, max_batch)
+            return results[0] if single else results
+        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
+        key ={"logits": "clipwise_logits", "scene": "scene", "frame": "frame"}[what]
         results = []
         cap = _ffi.MAX_VARLEN_CLIPS
         for c0 in range(0, len(lengths), cap):
@@ -603,7 +811,8 @@ class ConvNeXt(nn.Module):
         newest window by about one window length); "short": the slots whose recording ended under the model's minimum
         length and emitted nothing.  window / hop: seconds, whole samples at 32 kHz; sample_rate: the input rate of every
         slot; max_push: the longest chunk the device state is sized for, in seconds -- a longer one is pushed in pieces;
-        max_batch: windows per forward."""
+        max_batch: windows per forward.  Segment outputs (forward_segments) are not part of live streams: run
+        forward_windows(what="segment") on the finished recording."""
         return _stream.Stream(self, slots=slots, window=window, hop=hop, what=what, sample_rate=sample_rate,
                               timeline=timeline, max_push=max_push, max_batch=max_batch)
 

@@ -27,7 +27,9 @@ def schedule(window, hop, sample_rate, pushed, closed):
 
 
 class Stream:
-    """One acx_stream handle on the model's device (see ConvNeXt.stream)."""
+    """One acx_stream handle on the model's device (see ConvNeXt.stream).  Clip-level outputs per window only: the segment-wise /
+    frame-wise outputs of ConvNeXt.forward_segments are not part of live streams (run forward_windows(what="segment") on the
+    finished recording)."""
 
     def __init__(self, model, slots=256, window=10.0, hop=1.0, what="logits", sample_rate=None, timeline="mean", max_push=2.0,
                  max_batch=64):

@@ -4,6 +4,7 @@ load / resample / pad a WAV, three forwards, labels above the 0.25 threshold).
 
     python demo_convnext.py --ckpt checkpoints/model.safetensors --wav clip.wav --labels metadata/class_labels_indices.csv
     python demo_convnext.py --synthetic-weights --wav clip.wav        # no checkpoint at hand: seeded weights
+    python demo_convnext.py --wav clip.wav --sed --top 10              # sound event detection: WHEN the top classes happen
 
 Prints the same lines as the reference (`# params`, sizes, predicted label indices, names, embedding shapes).
 """
@@ -32,6 +33,9 @@ def main():
     ap.add_argument("--wav", required=True)
     ap.add_argument("--labels", default=os.path.join(ROOT, "metadata", "class_labels_indices.csv"))
     ap.add_argument("--threshold", type=float, default=0.25)
+    ap.add_argument("--sed", action="store_true", help="also print the top classes by maximum framewise probability and their "
+                                                       "events (the reference's sound_event_detection, inference.py:96-200)")
+    ap.add_argument("--top", type=int, default=10, help="--sed: how many classes")
     args = ap.parse_args()
 
     if args.synthetic_weights:
@@ -85,6 +89,20 @@ def main():
     with torch.no_grad():
         frame = model.forward_frame_embeddings(waveform)
     print("\nFrame-level embeddings, shape:", frame.size())
+
+    if args.sed:
+        from audioset_convnext_inf_amd.pytorch import segments
+        with torch.no_grad():
+            sed = model.forward_segments(waveform, resolution="frame")
+        framewise = sed["framewise_output"][0].cpu().numpy()                         # inference.py:156
+        print("\nSound event detection, framewise_output shape:", framewise.shape)
+        ranked = np.argsort(np.max(framewise, axis=0))[::-1][:args.top]              # inference.py:165-168
+        name = lambda c: ix_to_lb[c] if ix_to_lb else "class %d" % c
+        events = segments.decode_events(sed["segmentwise_output"][0], threshold=args.threshold, step=sed["segment_edges"].numpy())
+        for c in ranked:
+            print("%s: max %.3f" % (name(c), framewise[:, c].max()))
+            for _, on, off, peak, mean in [e for e in events if e[0] == c]:
+                print("    %6.2f - %6.2f s  peak %.3f mean %.3f" % (on, off, peak, mean))
 
 
 if __name__ == "__main__":

@@ -195,6 +195,73 @@ ACX_API int acx_window_timeline(const float* probs, const int64_t* lengths, int 
 ACX_API int acx_window_timeline_classes(const float* probs, int classes, const int64_t* lengths, int R, int64_t window,
                                         int64_t hop, int reduce, float* out, void* stream);
 
+/* ---- sound event detection: segment-wise and frame-wise outputs ---------------------------------------------------------------
+ * The reference's decision-level recipe (pytorch/models.py:5757-5771: mean over frequency, max_pool1d(3,1,1) + avg_pool1d(3,1,1)
+ * over time, the head per segment, sigmoid, clipwise = max over segments, interpolate(.., 32) + pad_framewise_output,
+ * pytorch/pytorch_utils.py:140-176) applied to the ConvNeXt trunk: the keys "segmentwise_output" / "framewise_output" that
+ * pytorch/inference.py:96-200 (sound_event_detection, :156) and pytorch_utils.py:78,108-119 read, and that the reference's
+ * ConvNeXt class never fills.  For a clip of L samples with stage-3 map x (768, S, 7), S = acx_stage_hw(L, 3).H (one segment
+ * per 32 STFT frames = 10240 samples; *S of acx_segment_count), and odd pool, 1 <= pool <= ACX_MAX_SEGMENT_POOL:
+ *   z[c, t] = mean_f x[c, t, f]                                                                        (convnext.py:279)
+ *   p[c, t] = max_{|s-t| <= pool/2, 0 <= s < S} z[c, s] + (1 / pool) sum_{|s-t| <= pool/2, 0 <= s < S} z[c, s]
+ *             (F.max_pool1d(z, pool, 1, pool / 2) + F.avg_pool1d(z, pool, 1, pool / 2): the average always divides by pool,
+ *              rows beyond the clip count as zeros; the max ignores them; the sum runs in ascending s)
+ *   e[t, :] = LayerNorm_768(p[:, t]; norm.weight, norm.bias, eps 1e-6)       segment embedding         (convnext.py:285)
+ *   l[t, :] = head_audioset(e[t, :]);  q[t, :] = 1 / (1 + expf(-l[t, :]))    segment logits / output   (convnext.py:321-325)
+ *   clip[n] = max_t q[t, n]                                                                            (models.py:5767)
+ *   frame[u, :] = q[min(u / 32, S - 1), :],  0 <= u < T = L / 320 + 1        (interpolate + pad_framewise_output)
+ * Everything after the trunk is fp32 in every precision mode.  The head runs on the f32-input matrix cores
+ * (v_mfma_f32_32x32x2_f32, v_mfma_f32_16x16x4_f32 for small launches) with a fixed contraction order and no atomics: a value
+ * (clip, segment, class) depends only on that segment's embedding row and that head row -- not on N, on the batch, on the
+ * sub-batch split or on the tile shape -- bit for bit.  Not the arithmetic of acx_forward's head: "clip" is the maximum over
+ * segments, NOT the clipwise_output of ACX_MODE_LOGITS.
+ *
+ * what = ACX_SEG_OUTPUT: out0 = segment logits, out1 = segment probabilities, one row of N per segment; clip (may be NULL) =
+ *   (clips, N).  what = ACX_SEG_EMBED: out0 = segment embeddings, one row of 768 per segment; out1 and clip are ignored.
+ * acx_forward_segments: acx_forward's arguments; rows (B, S, .).  acx_forward_segments_varlen: acx_forward_varlen's; clip i's
+ *   S_i rows back to back in clip order.  acx_forward_segments_windows: acx_forward_windows's; rows (count, S_window, .), each
+ *   window bit-identical to acx_forward_segments of that window cut out.  A clip's rows are the same bits through all three.
+ * Launch contract of acx_forward: work on `stream` only, no allocation, no synchronisation, capturable, and for the uniform and
+ * window forms the same sub-batch split.  The embeddings of the ACX_SEG_OUTPUT forms live in the frontend's feature buffer
+ * (idle after the stem, 224 T >= 768 S floats per clip): the workspace equals the one of the corresponding acx_forward call.
+ *
+ * acx_segment_head (per-layer entry, in the style of acx_pool_head): x NHWC (B, S, 7, 768) -> emb (B S, 768), logits / probs
+ *   (B S, N); logits and probs may be NULL (both or neither).
+ * acx_segment_expand: frame (B, T, N) from probs (B, S, N), frame[b, u] = probs[b, min(u / 32, S - 1)]; 1 <= S, 1 <= T.
+ * acx_segment_expand_varlen: the same for packed clips of lengths[i] samples (HOST array, B <= ACX_MAX_VARLEN_CLIPS): probs =
+ *   the clips' (S_i, N) blocks back to back, frame = their (T_i, N) blocks back to back.
+ * acx_segment_timeline: a timeline at segment resolution over the windows of R recordings, defined as
+ *   acx_window_timeline_classes is.  probs = the segment probabilities of ALL windows in window order: n_r blocks of
+ *   (S_window, classes) for a recording longer than the window, one block (S(L_r), classes) for any other (one clip, as
+ *   acx_forward_windows treats it).  Recording r gets ceil(L_r / 10240) rows; row k has the midpoint
+ *   m_k = min(10240 k + 5120, L_r - 1) and reduces over the (window j, segment i) pairs with
+ *   s_j + 10240 i <= m_k < s_j + 10240 (i + 1), where the last segment of a window reaches to the window's end: at most one
+ *   segment per window.  reduce 0 = mean (an fp32 sum in ascending j, then one fp32 division by the count), 1 = max.
+ *   Every L_r must be >= ACX_MIN_SAMPLES or 0.  One kernel on `stream`, no allocation, capturable.
+ * Argument errors (ACX_ERR_ARG: null pointer, pool even or out of range, bad `what`; ACX_ERR_SHAPE: a clip too short, S or T
+ * not positive) are returned before any launch. */
+enum acx_segment_what { ACX_SEG_OUTPUT = 0, ACX_SEG_EMBED = 1 };
+#define ACX_SEGMENT_SAMPLES 10240   /* 32 STFT frames of 320 samples: the four 2x strides of the trunk along time */
+#define ACX_MAX_SEGMENT_POOL 31
+ACX_API int acx_segment_count(int64_t L, int* S);
+ACX_API int acx_workspace_bytes_segments(const acx_ctx* ctx, int B, int64_t L, int what, size_t* out_bytes);
+ACX_API int acx_forward_segments(acx_ctx* ctx, const float* wav, int B, int64_t L, int pool, int what, float* out0, float* out1,
+                                 float* clip, void* workspace, size_t workspace_bytes, void* stream);
+ACX_API int acx_workspace_bytes_segments_varlen(const acx_ctx* ctx, const int64_t* lengths, int B, int what, size_t* out_bytes);
+ACX_API int acx_forward_segments_varlen(acx_ctx* ctx, const float* wav, const int64_t* lengths, int B, int pool, int what,
+                                        float* out0, float* out1, float* clip, void* workspace, size_t workspace_bytes,
+                                        void* stream);
+ACX_API int acx_workspace_bytes_segments_windows(const acx_ctx* ctx, int count, int64_t window, int what, size_t* out_bytes);
+ACX_API int acx_forward_segments_windows(acx_ctx* ctx, const float* wav, const int64_t* lengths, int R, int64_t window,
+                                         int64_t hop, int64_t first, int count, int pool, int what, float* out0, float* out1,
+                                         float* clip, void* workspace, size_t workspace_bytes, void* stream);
+ACX_API int acx_segment_head(acx_ctx* ctx, const float* x, int B, int S, int pool, float* emb, float* logits, float* probs,
+                             void* stream);
+ACX_API int acx_segment_expand(const float* probs, int B, int S, int N, int T, float* frame, void* stream);
+ACX_API int acx_segment_expand_varlen(const float* probs, const int64_t* lengths, int B, int N, float* frame, void* stream);
+ACX_API int acx_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
+                                 int reduce, float* out, void* stream);
+
 /* ---- live streams: tagging recordings that arrive chunk by chunk ----------------------------------------------------------
  * No reference counterpart.  A handle has `slots`; each slot holds one recording at a time.  Samples pushed to a slot are
  * appended to its open recording; acx_stream_close ends it and the slot's next push starts a new one.  Window W, hop H, the
