@@ -36,6 +36,21 @@ class AcxAdam(ctypes.Structure):
 
 _padam, _c_dbl = ctypes.POINTER(AcxAdam), ctypes.c_double
 
+
+class AcxEvent(ctypes.Structure):
+    """struct acx_event: one row of the event table of acx_decode_events (32 bytes)."""
+    _fields_ = [("clip", ctypes.c_int32), ("cls", ctypes.c_int32), ("begin", ctypes.c_int32), ("end", ctypes.c_int32),
+                ("peak", ctypes.c_float), ("reserved", ctypes.c_float), ("mean", ctypes.c_double)]
+
+
+class AcxEventParams(ctypes.Structure):
+    """struct acx_event_params: the decoding settings of acx_decode_events."""
+    _fields_ = [("threshold", ctypes.c_float), ("low", ctypes.c_float), ("median", ctypes.c_int),
+                ("min_duration", ctypes.c_double), ("merge_gap", ctypes.c_double)]
+
+
+_pevp, _pdbl = ctypes.POINTER(AcxEventParams), ctypes.POINTER(ctypes.c_double)
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -72,6 +87,11 @@ SIGNATURES = {
     "acx_segment_expand": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "acx_segment_expand_varlen": (_c_int, [_vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _vp]),
     "acx_segment_timeline": (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_i64, _c_i64, _c_int, _vp, _vp]),
+    "acx_events_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_decode_events": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _pevp, _c_dbl, _c_dbl, _vp, _c_i64, _vp, _vp, _vp, _c_sz,
+                                   _vp]),
+    "acx_decode_events_varlen": (_c_int, [_vp, _c_i64, _pint, _pdbl, _c_int, _c_int, _pevp, _c_dbl, _vp, _c_i64, _vp, _vp, _vp,
+                                          _c_sz, _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -378,6 +398,25 @@ def head_fit_workspace_bytes(rows_max, classes):
     """Workspace of acx_head_fit_step / acx_head_fit_grad for steps of up to rows_max rows (host only)."""
     out = _c_sz()
     check(lib().acx_head_fit_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
+    return out.value
+
+
+MAX_EVENT_MEDIAN = 101                        # ACX_MAX_EVENT_MEDIAN
+EVENTS_NONFINITE, EVENTS_OVERFLOW = 1, 2      # bits of acx_decode_events' status word
+EVENT_BYTES = ctypes.sizeof(AcxEvent)         # 32
+
+
+def event_params(threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=0.0):
+    """An acx_event_params struct (decode_events' defaults: low=None means low = threshold).  threshold and low are rounded
+    to fp32 here, as numpy rounds a Python float compared with a float32 array."""
+    return AcxEventParams(float(threshold), float(threshold if low is None else low), int(median), float(min_duration),
+                          float(merge_gap))
+
+
+def events_workspace_bytes(B, N):
+    """Workspace of acx_decode_events / acx_decode_events_varlen for B clips of N classes (host only)."""
+    out = _c_sz()
+    check(lib().acx_events_workspace_bytes(int(B), int(N), ctypes.byref(out)))
     return out.value
 
 

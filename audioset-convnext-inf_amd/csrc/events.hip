@@ -1,0 +1,451 @@
+// Event decoding on the device (include/acx.h "sound event decoding"): probabilities over time -> one compact, ordered table of
+// events, the batched form of pytorch/segments.py::decode_events.
+//
+// One WAVE per (clip, 64 classes), a lane per class, walking down time: every row read is one coalesced 256-byte line, and each
+// lane runs the whole per-column state machine -- running median, hysteresis runs, merge, minimum duration -- in registers.
+// Three launches on the caller's stream, no atomics that could order anything:
+//   events_kernel<.., false>  counts the events of every column (counts[unit][lane]) and of every wave (unit_off[unit]);
+//   events_scan_kernel        turns the wave totals into exclusive offsets, writes *count and the overflow bit;
+//   events_kernel<.., true>   walks again and writes event i of a column at offset(unit) + prefix(lane) + i.
+// The table is therefore ordered by (clip, class, begin) and has the same bits on every call.
+//
+// The median is a per-lane SORTED sliding window: stepping removes the value that leaves and inserts the value that enters in
+// one pass over the window (one compare-select chain per slot, no sort).  Widths up to kEvRegMedian live in registers, wider
+// ones in LDS as [slot][lane] (conflict-free: a lane only ever touches its own column of banks).  The value that leaves is
+// re-read from memory (row t - median / 2, a line the wave read median rows earlier).  Both row streams are loaded kEvDepth
+// rows ahead of their use.
+//
+// float64 appears only where decode_events has it: the boundaries (k * step_seconds), their differences against merge_gap /
+// min_duration, and the sum behind an event's mean.  Built with -fno-slp-vectorize like segments.hip (csrc/Makefile).
+#include "acx_internal.h"
+
+namespace acx {
+
+constexpr int kEvDepth = 8;          // rows of each stream in flight per wave
+constexpr int kEvRegMedian = 7;      // widest median window kept in registers
+constexpr long long kEvMaxUnits = 2147483647LL;   // one workgroup per unit: the grid's x limit
+constexpr int kEvMaxSteps = 1 << 30;              // row numbers plus the look-ahead stay inside an int
+
+struct EvArgs {
+    const float* probs;
+    long long ld;
+    int steps;                 // uniform batches; varlen: tab_steps[clip]
+    int N, G;                  // classes, units per clip = ceil(N / 64)
+    float thr, low;
+    int median;
+    double min_dur, gap, step, end;      // end: uniform batches (already resolved); varlen: tab_end[clip]
+    const long long* tab_row0;           // varlen: first row of each clip (null: clip * steps)
+    const int* tab_steps;
+    const double* tab_end;
+    int* counts;               // [units][64] events of each column
+    long long* unit_off;       // [units] events of each unit, then (after the scan) their exclusive prefix
+    int* status;
+    acx_event* events;
+    long long capacity;
+};
+
+// The sorted window of one lane.  WR > 0: WR registers; WR == 0: `w` LDS slots, slot k of this lane at l[k * 64].
+template <int WR>
+struct EvWindow {
+    float r[WR > 0 ? WR : 1];
+    float* l;
+    int w;
+    __device__ __forceinline__ void fill(float v) {
+        if constexpr (WR > 0) {
+#pragma unroll
+            for (int k = 0; k < WR; ++k) r[k] = v;
+        } else {
+            for (int k = 0; k < w; ++k) l[k * 64] = v;
+        }
+    }
+    __device__ __forceinline__ float median() const {
+        if constexpr (WR > 0) return r[WR / 2];
+        else return l[(w / 2) * 64];
+    }
+    // One slot of the update: a = the window as it was, rem[k] = (a[k] < o ? a[k] : a[k + 1]) = a without one `o`,
+    // new[k] = rem[k - 1] if rem[k - 1] > n, else rem[k] if rem[k] <= n, else n.
+    static __device__ __forceinline__ float slot(float ak, float ak1, float o, float n, float& rprev, bool first) {
+        const float rk = ak < o ? ak : ak1;
+        const float b = (!first && !(rprev <= n)) ? rprev : (rk <= n ? rk : n);
+        rprev = rk;
+        return b;
+    }
+    // remove one `o` (which the window holds), insert `n`; the window stays sorted
+    __device__ __forceinline__ void update(float o, float n) {
+        float rprev = 0.f;
+        if constexpr (WR > 0) {
+#pragma unroll
+            for (int k = 0; k < WR; ++k) {
+                const float ak1 = k + 1 < WR ? r[k + 1] : INFINITY;
+                r[k] = slot(r[k], ak1, o, n, rprev, k == 0);
+            }
+        } else {
+            float ak = l[0];
+            for (int k = 0; k < w; ++k) {
+                const float ak1 = k + 1 < w ? l[(k + 1) * 64] : INFINITY;
+                l[k * 64] = slot(ak, ak1, o, n, rprev, k == 0);
+                ak = ak1;
+            }
+        }
+    }
+};
+
+__device__ __forceinline__ bool ev_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// The per-column state machine of decode_events, one step of time per call; [eb, ee) is the pending (possibly merged) event,
+// emax / esum run from eb over EVERY row since (gap rows included) so that a merge can adopt them, epeak / esnap are their
+// values at ee.
+template <bool EMIT>
+struct EvColumn {
+    const EvArgs& a;
+    int steps;
+    double end;
+    bool live;
+    int clip, cls;
+    long long base;          // EMIT: table index of this column's first event
+    int n = 0;               // events so far
+    bool in_run = false, rvalid = false, have = false;
+    int rb = 0, eb = 0, ee = 0;
+    float rmax = 0.f, emax = 0.f, epeak = 0.f;
+    double rsum = 0.0, esum = 0.0, esnap = 0.0;
+
+    __device__ __forceinline__ EvColumn(const EvArgs& a_, int steps_, double end_, bool live_, int clip_, int cls_, long long base_)
+        : a(a_), steps(steps_), end(end_), live(live_), clip(clip_), cls(cls_), base(base_) {}
+    __device__ __forceinline__ double edge(int k) const { return k < steps ? (double)k * a.step : end; }
+    __device__ __forceinline__ void finish_event() {
+        if (!(edge(ee) - edge(eb) < a.min_dur)) {
+            if constexpr (EMIT) {
+                const long long i = base + n;
+                if (i < a.capacity) {
+                    acx_event e;
+                    e.clip = clip; e.cls = cls; e.begin = eb; e.end = ee;
+                    e.peak = epeak; e.reserved = 0.f;
+                    e.mean = esnap / (double)(ee - eb);
+                    a.events[i] = e;
+                }
+            }
+            ++n;
+        }
+    }
+    // the run [rb, t) has ended
+    __device__ __forceinline__ void end_run(int t) {
+        in_run = false;
+        if (!rvalid) return;
+        if (have && edge(rb) - edge(ee) < a.gap) {
+            ee = t; epeak = emax; esnap = esum;
+        } else {
+            if (have) finish_event();
+            have = true;
+            eb = rb; ee = t;
+            epeak = emax = rmax;
+            esnap = esum = rsum;
+        }
+    }
+    __device__ __forceinline__ void step(int t, float p) {
+        const bool on = live && p >= a.low;
+        if (!on && in_run) end_run(t);
+        if (have) { emax = fmaxf(emax, p); esum += (double)p; }
+        if (on) {
+            if (!in_run) { in_run = true; rb = t; rvalid = false; rmax = p; rsum = 0.0; }
+            rmax = fmaxf(rmax, p);
+            rsum += (double)p;
+            rvalid = rvalid || p >= a.thr;
+        }
+    }
+    __device__ __forceinline__ void finish() {
+        if (in_run) end_run(steps);
+        if (have) finish_event();
+    }
+};
+
+template <int WR, bool EMIT>
+__global__ __launch_bounds__(64) void events_kernel(EvArgs a) {
+    extern __shared__ float s_win[];
+    const int lane = threadIdx.x;
+    const long long unit = blockIdx.x;
+    const int clip = (int)(unit / a.G), g = (int)(unit - (long long)clip * a.G);
+    const int cls = g * 64 + lane;
+    const bool live = cls < a.N;
+
+    long long base = 0;
+    if constexpr (EMIT) {
+        if (*a.status & ACX_EVENTS_NONFINITE) return;
+        // exclusive prefix of the lanes' counts; a unit without events has nothing to write
+        const int mine = a.counts[unit * 64 + lane];
+        int incl = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (__shfl(incl, 63, 64) == 0) return;
+        base = a.unit_off[unit] + (incl - mine);
+        if (base >= a.capacity) base = a.capacity;     // nothing of this column fits; keeps base + n from wrapping
+    }
+
+    int steps = a.steps;
+    long long row0 = (long long)clip * a.steps;
+    double end = a.end;
+    if (a.tab_steps) { steps = a.tab_steps[clip]; row0 = a.tab_row0[clip]; end = a.tab_end[clip]; }
+    const float* x = a.probs + row0 * a.ld + (live ? cls : a.N - 1);     // idle lanes re-read the last class: in bounds
+    const int h = a.median / 2, last = steps - 1;
+    auto row = [&](int r) { return x[(long long)(r < 0 ? 0 : r > last ? last : r) * a.ld]; };
+
+    EvWindow<WR> win;
+    win.l = s_win + lane;
+    win.w = a.median;
+    const float x0 = row(0);
+    bool bad = ev_nonfinite(x0);
+    if constexpr (WR != 1) {
+        // the window of t = 0: rows -h .. h with the ends repeated
+        win.fill(x0);
+        for (int j = 1; j <= h; ++j) {
+            const float v = row(j);
+            bad = bad || ev_nonfinite(v);
+            win.update(x0, v);
+        }
+    } else {
+        win.r[0] = x0;
+    }
+
+    EvColumn<EMIT> col(a, steps, end, live, clip, cls, base);
+    // step t reads the window's median, then trades row t - h for row t + h + 1; both streams run kEvDepth rows ahead
+    float cin[kEvDepth], cout[kEvDepth], nin[kEvDepth], nout[kEvDepth];
+#pragma unroll
+    for (int j = 0; j < kEvDepth; ++j) {
+        cin[j] = row(j + h + 1);
+        cout[j] = WR == 1 ? 0.f : row(j - h);
+    }
+    for (int t0 = 0; t0 < steps; t0 += kEvDepth) {
+#pragma unroll
+        for (int j = 0; j < kEvDepth; ++j) {      // (rows past the end clamp to the last one: in bounds, unused)
+            nin[j] = row(t0 + kEvDepth + j + h + 1);
+            nout[j] = WR == 1 ? 0.f : row(t0 + kEvDepth + j - h);
+        }
+#pragma unroll
+        for (int j = 0; j < kEvDepth; ++j) {
+            const int t = t0 + j;
+            if (t < steps) {
+                col.step(t, win.median());
+                bad = bad || ev_nonfinite(cin[j]);
+                if constexpr (WR == 1) win.r[0] = cin[j];
+                else win.update(cout[j], cin[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kEvDepth; ++j) { cin[j] = nin[j]; cout[j] = nout[j]; }
+    }
+    col.finish();
+
+    if constexpr (!EMIT) {
+        a.counts[unit * 64 + lane] = col.n;
+        long long tot = col.n;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d, 64);
+        if (lane == 0) a.unit_off[unit] = tot;
+        if (__any(bad) && lane == 0) atomicOr(a.status, ACX_EVENTS_NONFINITE);     // an OR: no order to depend on
+    }
+}
+
+// unit totals -> exclusive offsets (in place), *count, the overflow bit.  One workgroup: thread i owns a contiguous chunk.
+__global__ __launch_bounds__(1024) void events_scan_kernel(long long* unit_off, long long units, long long capacity,
+                                                           long long* count, int* status) {
+    __shared__ long long s_wave[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long chunk = (units + 1023) / 1024;
+    const long long lo = tid * chunk < units ? tid * chunk : units, hi = lo + chunk < units ? lo + chunk : units;
+    long long mine = 0;
+    for (long long i = lo; i < hi; ++i) mine += unit_off[i];
+    long long incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    long long before = 0, total = 0;
+    for (int w = 0; w < 16; ++w) {
+        if (w < wave) before += s_wave[w];
+        total += s_wave[w];
+    }
+    long long run = before + incl - mine;
+    for (long long i = lo; i < hi; ++i) {
+        const long long c = unit_off[i];
+        unit_off[i] = run;
+        run += c;
+    }
+    if (tid == 0) {
+        const int st = *status;
+        if (st & ACX_EVENTS_NONFINITE) {
+            *count = 0;
+        } else {
+            *count = total;
+            if (total > capacity) *status = st | ACX_EVENTS_OVERFLOW;
+        }
+    }
+}
+
+// varlen: the clips' first rows, step counts and last boundaries, from the values passed by value
+struct EvTabArgs {
+    int steps[kVarMaxClips];
+    double end[kVarMaxClips];      // <= 0: steps * step
+    int B;
+    double step;
+};
+__global__ __launch_bounds__(kVarMaxClips) void events_table_kernel(EvTabArgs t, long long* row0, int* steps, double* end) {
+    const int i = threadIdx.x;
+    if (i >= t.B) return;
+    long long r = 0;
+    for (int j = 0; j < i; ++j) r += t.steps[j];
+    row0[i] = r;
+    steps[i] = t.steps[i];
+    end[i] = t.end[i] > 0.0 ? t.end[i] : (double)t.steps[i] * t.step;
+}
+
+static size_t ev_align(size_t v) { return (v + 255) & ~(size_t)255; }
+// workspace: unit_off [units] int64 | counts [units][64] int32 | row0 [256] int64 | end [256] double | steps [256] int32
+static void ev_layout(long long units, size_t* counts, size_t* row0, size_t* end, size_t* steps, size_t* total) {
+    *counts = ev_align((size_t)units * 8);
+    *row0 = *counts + ev_align((size_t)units * 64 * 4);
+    *end = *row0 + ev_align(kVarMaxClips * 8);
+    *steps = *end + ev_align(kVarMaxClips * 8);
+    *total = *steps + ev_align(kVarMaxClips * 4);
+}
+
+static int ev_units(const char* who, int64_t B, int N, long long* units) {
+    if (B < 1) ACX_FAIL(ACX_ERR_SHAPE, "%s: B = %lld (expected >= 1)", who, (long long)B);
+    if (N < 1 || N > ACX_MAX_CLASSES)
+        ACX_FAIL(ACX_ERR_SHAPE, "%s: %d classes (expected 1 .. %d)", who, N, ACX_MAX_CLASSES);
+    const long long G = (N + 63) / 64;
+    if (B > kEvMaxUnits / G)
+        ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: %lld clips of %d classes need more than %lld workgroups", who, (long long)B, N,
+                 kEvMaxUnits);
+    *units = B * G;
+    return ACX_OK;
+}
+
+static int ev_check_params(const char* who, const acx_event_params* p, double step_seconds, int64_t capacity) {
+    if (p->median < 1 || p->median > ACX_MAX_EVENT_MEDIAN || p->median % 2 == 0)
+        ACX_FAIL(ACX_ERR_ARG, "%s: median %d (expected an odd width in 1 .. %d)", who, p->median, ACX_MAX_EVENT_MEDIAN);
+    if (!(p->low >= 0.f && p->low <= p->threshold))
+        ACX_FAIL(ACX_ERR_ARG, "%s: low %g must be in [0, threshold = %g]", who, (double)p->low, (double)p->threshold);
+    if (!(p->min_duration >= 0.0) || !(p->merge_gap >= 0.0))
+        ACX_FAIL(ACX_ERR_ARG, "%s: min_duration %g and merge_gap %g must not be negative", who, p->min_duration, p->merge_gap);
+    if (!(step_seconds > 0.0)) ACX_FAIL(ACX_ERR_ARG, "%s: step_seconds %g (expected > 0)", who, step_seconds);
+    if (capacity < 0) ACX_FAIL(ACX_ERR_ARG, "%s: capacity %lld (expected >= 0)", who, (long long)capacity);
+    return ACX_OK;
+}
+
+template <bool EMIT>
+static void ev_launch(const EvArgs& a, long long units, hipStream_t s) {
+    const dim3 grid((unsigned)units), block(64);
+    switch (a.median) {
+        case 1: launch_kernel(&events_kernel<1, EMIT>, grid, block, 0, s, a); break;
+        case 3: launch_kernel(&events_kernel<3, EMIT>, grid, block, 0, s, a); break;
+        case 5: launch_kernel(&events_kernel<5, EMIT>, grid, block, 0, s, a); break;
+        case 7: launch_kernel(&events_kernel<7, EMIT>, grid, block, 0, s, a); break;
+        default: launch_kernel(&events_kernel<0, EMIT>, grid, block, (size_t)a.median * 64 * 4, s, a); break;
+    }
+    static_assert(kEvRegMedian == 7, "one case per register width");
+}
+
+// everything after the argument checks: clear the status, count, scan, emit
+static int ev_run(EvArgs a, long long units, long long* count, hipStream_t s) {
+    ACX_HIP(hipMemsetAsync(a.status, 0, sizeof(int), s));
+    ev_launch<false>(a, units, s);
+    ACX_HIP(hipGetLastError());
+    launch_kernel(&events_scan_kernel, dim3(1), dim3(1024), 0, s, a.unit_off, units, a.capacity, count, a.status);
+    ACX_HIP(hipGetLastError());
+    ev_launch<true>(a, units, s);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+static int ev_check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (ws_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    if (reinterpret_cast<uintptr_t>(ws) & 255) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace is not 256-byte aligned", who);
+    return ACX_OK;
+}
+
+}  // namespace acx
+
+using namespace acx;
+
+extern "C" {
+
+int acx_events_workspace_bytes(int64_t B, int N, size_t* bytes) {
+    if (!bytes) ACX_FAIL(ACX_ERR_ARG, "acx_events_workspace_bytes: bytes is null");
+    long long units;
+    ACX_TRY(ev_units("acx_events_workspace_bytes", B, N, &units));
+    size_t c, r, e, st;
+    ev_layout(units, &c, &r, &e, &st, bytes);
+    return ACX_OK;
+}
+
+int acx_decode_events(const float* probs, int64_t ld, int64_t B, int steps, int N, const acx_event_params* p, double step_seconds,
+                      double end_seconds, acx_event* events, int64_t capacity, int64_t* count, int* status, void* ws,
+                      size_t ws_bytes, void* stream) {
+    const char* who = "acx_decode_events";
+    if (!probs || !p || !events || !count || !status || !ws) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    ACX_TRY(ev_check_params(who, p, step_seconds, capacity));
+    if (steps < 1 || steps > kEvMaxSteps) ACX_FAIL(ACX_ERR_SHAPE, "%s: %d steps (expected 1 .. 2^30)", who, steps);
+    long long units;
+    ACX_TRY(ev_units(who, B, N, &units));
+    if (ld < N) ACX_FAIL(ACX_ERR_SHAPE, "%s: row stride %lld is shorter than %d classes", who, (long long)ld, N);
+    size_t coff, roff, eoff, soff, need;
+    ev_layout(units, &coff, &roff, &eoff, &soff, &need);
+    ACX_TRY(ev_check_ws(who, ws, ws_bytes, need));
+    char* w = static_cast<char*>(ws);
+    EvArgs a{};
+    a.probs = probs; a.ld = ld; a.steps = steps; a.N = N; a.G = (N + 63) / 64;
+    a.thr = p->threshold; a.low = p->low; a.median = p->median;
+    a.min_dur = p->min_duration; a.gap = p->merge_gap; a.step = step_seconds;
+    a.end = end_seconds > 0.0 ? end_seconds : (double)steps * step_seconds;
+    a.counts = reinterpret_cast<int*>(w + coff);
+    a.unit_off = reinterpret_cast<long long*>(w);
+    a.status = status; a.events = events; a.capacity = capacity;
+    return ev_run(a, units, reinterpret_cast<long long*>(count), (hipStream_t)stream);
+}
+
+int acx_decode_events_varlen(const float* probs, int64_t ld, const int* steps, const double* end_seconds, int B, int N,
+                             const acx_event_params* p, double step_seconds, acx_event* events, int64_t capacity, int64_t* count,
+                             int* status, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "acx_decode_events_varlen";
+    if (!probs || !steps || !p || !events || !count || !status || !ws) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    ACX_TRY(ev_check_params(who, p, step_seconds, capacity));
+    if (B < 1 || B > kVarMaxClips) ACX_FAIL(ACX_ERR_SHAPE, "%s: %d clips (expected 1 .. %d)", who, B, kVarMaxClips);
+    for (int i = 0; i < B; ++i)
+        if (steps[i] < 1 || steps[i] > kEvMaxSteps)
+            ACX_FAIL(ACX_ERR_SHAPE, "%s: clip %d has %d steps (expected 1 .. 2^30)", who, i, steps[i]);
+    long long units;
+    ACX_TRY(ev_units(who, B, N, &units));
+    if (ld < N) ACX_FAIL(ACX_ERR_SHAPE, "%s: row stride %lld is shorter than %d classes", who, (long long)ld, N);
+    size_t coff, roff, eoff, soff, need;
+    ev_layout(units, &coff, &roff, &eoff, &soff, &need);
+    ACX_TRY(ev_check_ws(who, ws, ws_bytes, need));
+    const hipStream_t s = (hipStream_t)stream;
+    char* w = static_cast<char*>(ws);
+    EvTabArgs t{};
+    t.B = B; t.step = step_seconds;
+    for (int i = 0; i < B; ++i) {
+        t.steps[i] = steps[i];
+        t.end[i] = end_seconds ? end_seconds[i] : 0.0;
+    }
+    long long* row0 = reinterpret_cast<long long*>(w + roff);
+    double* end = reinterpret_cast<double*>(w + eoff);
+    int* stp = reinterpret_cast<int*>(w + soff);
+    launch_kernel(&events_table_kernel, dim3(1), dim3(kVarMaxClips), 0, s, t, row0, stp, end);
+    ACX_HIP(hipGetLastError());
+    EvArgs a{};
+    a.probs = probs; a.ld = ld; a.steps = 0; a.N = N; a.G = (N + 63) / 64;
+    a.thr = p->threshold; a.low = p->low; a.median = p->median;
+    a.min_dur = p->min_duration; a.gap = p->merge_gap; a.step = step_seconds;
+    a.tab_row0 = row0; a.tab_steps = stp; a.tab_end = end;
+    a.counts = reinterpret_cast<int*>(w + coff);
+    a.unit_off = reinterpret_cast<long long*>(w);
+    a.status = status; a.events = events; a.capacity = capacity;
+    return ev_run(a, units, reinterpret_cast<long long*>(count), s);
+}
+
+}  // extern "C"

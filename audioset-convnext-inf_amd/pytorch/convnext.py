@@ -487,6 +487,20 @@ class ConvNeXt(nn.Module):
             out["framewise_output"] = frame
         return out
 
+    def detect_events(self, waveform, pool=3, sample_rate=None, **decode_args):
+        """forward_segments followed by the event decoding, both on the GPU and on the same stream: WHAT happens WHEN, as a
+        table.  Returns forward_segments' dict (segment resolution) plus "events": an EventTable over the batch, decoded from
+        "segmentwise_output" with the clip's "segment_edges" (pytorch/segments.py, decode_events_gpu).  decode_args: threshold,
+        low, median, min_duration, merge_gap, capacity -- decode_events' arguments; they are checked before the forward runs.
+        Nothing synchronises until the table is read (len(), .to_lists(labels), .check())."""
+        if "step" in decode_args or "steps" in decode_args:
+            raise TypeError("detect_events takes its boundaries from the clip: step / steps are not arguments")
+        _seg.check_event_args(decode_args.get("threshold", 0.5), decode_args.get("low"), decode_args.get("median", 1),
+                              decode_args.get("min_duration", 0.0), decode_args.get("merge_gap", 0.0))
+        out = self.forward_segments(waveform, pool=pool, sample_rate=sample_rate)
+        out["events"] = _seg.decode_events_gpu(out["segmentwise_output"], step=out["segment_edges"].numpy(), **decode_args)
+        return out
+
     def forward_segment_embeddings(self, x, pool=3, sample_rate=None):
         """(B, L) -> (B, S, 768): the embedding of every 0.32 s segment -- forward_segments' rows in front of the head, i.e.
         forward_scene_embeddings' recipe (convnext.py:279-285) with the pooling over `pool` segments instead of the clip.  The

@@ -1,12 +1,15 @@
 """Sound event detection on the host side (ConvNeXt.forward_segments / forward_segment_embeddings, include/acx.h "sound event
 detection"): the geometry of segments, frames and the segment timeline -- one definition shared with the C ABI -- and the
-decoding of probabilities over time into events.  Nothing here touches the GPU.
+decoding of probabilities over time into events: decode_events on the host -- nothing down to it touches the GPU -- and
+decode_events_gpu / EventTable, the same decoding for whole batches on the device (acx_decode_events).
 
 The trunk halves time four times after a stride-4 stem on hop-320 frames, so one row of the stage-3 map -- one SEGMENT -- stands
 for 32 STFT frames = 10240 samples = 0.32 s at 32 kHz.  A clip of L samples has T = L // 320 + 1 frames and
 S = ((T + 4) // 4 + 1) // 8 = (T + 8) // 32 segments (acx_stage_hw(L, 3)); segment t covers samples [10240 t, 10240 (t + 1)) and the
 last one reaches to the clip's end.  Frame u belongs to segment min(u // 32, S - 1): the reference's interpolate(x, 32) followed
 by pad_framewise_output (pytorch/pytorch_utils.py:140-176)."""
+import ctypes
+
 import numpy as np
 
 from .. import _ffi
@@ -148,3 +151,238 @@ def decode_events(probs, threshold=0.5, low=None, median=1, min_duration=0.0, me
                            float(col[b:e].max()), float(col[b:e].mean())))
     events.sort(key=lambda ev: (ev[1], ev[2], str(ev[0])))
     return events
+
+
+# ---- the same decoding on the device (include/acx.h "sound event decoding", csrc/events.hip) ---------------------------------
+
+_GPU_EDGES = "only uniform steps with a free last boundary run on the GPU (edges k * step for k < steps, then the clip's end)"
+
+
+def check_event_args(threshold, low, median, min_duration, merge_gap):
+    """decode_events' argument checks and messages, plus the device's cap on `median`.  Returns low with None resolved."""
+    low = threshold if low is None else low
+    if not 0.0 <= low <= threshold:
+        raise ValueError("low must be in [0, threshold] (got low=%r, threshold=%r)" % (low, threshold))
+    if isinstance(median, bool) or not isinstance(median, int) or median < 1 or median % 2 == 0:
+        raise ValueError("median must be an odd positive integer (got %r)" % (median,))
+    if median > _ffi.MAX_EVENT_MEDIAN:
+        raise ValueError("median must be at most %d on the GPU (got %r)" % (_ffi.MAX_EVENT_MEDIAN, median))
+    if min_duration < 0 or merge_gap < 0:
+        raise ValueError("min_duration and merge_gap must not be negative")
+    return low
+
+
+def _uniform_edges(edges, n):
+    """(step or None, end) of one clip's n + 1 boundaries when they are k * step for k < n plus a free, positive last one;
+    ValueError otherwise.  step is None for a single step (any step fits)."""
+    e = np.asarray(edges, dtype=np.float64)
+    if e.shape != (n + 1,):
+        raise ValueError("%d boundaries for %d steps (expected steps + 1)" % (e.size, n))
+    if e[0] != 0.0 or not e[n] > 0.0:
+        raise ValueError(_GPU_EDGES)
+    if n == 1:
+        return None, float(e[1])
+    step = float(e[1])
+    if not step > 0.0 or not np.array_equal(e[:n], np.arange(n, dtype=np.float64) * step):
+        raise ValueError(_GPU_EDGES)
+    return step, float(e[n])
+
+
+class EventTable:
+    """The events of a batch, on the device: one (capacity, 32-byte) buffer of acx_event rows ordered by (clip, cls, begin),
+    of which the first `count` are valid.  clip / cls / begin / end (int32), peak (fp32) and mean (fp64) are views of it;
+    count (int64) and status (int32) are device tensors of one element; edges: per clip the float64 boundaries in seconds
+    (host).  Creating a table does not synchronise; len(), to_lists() and check() do."""
+
+    def __init__(self, table, count, status, edges, classes, rerun=None):
+        self._set(table, count, status)
+        self.edges = edges
+        self.classes = classes
+        self._rerun = rerun          # capacity -> (table, count, status): decodes again into a larger table
+        self._n = None
+
+    def _set(self, table, count, status):
+        self.table, self.count, self.status = table, count, status
+        self.clip, self.cls, self.begin, self.end = (table[:, i] for i in range(4))
+        self.peak = table.view(_torch().float32)[:, 4]
+        self.mean = table.view(_torch().float64)[:, 3]
+
+    @property
+    def capacity(self):
+        return self.table.shape[0]
+
+    def check(self):
+        """Waits for the decoding.  ValueError when the probabilities held a NaN or an infinity; a table that was too small is
+        decoded once more at the exact size.  Returns self."""
+        if self._n is None:
+            n, st = int(self.count.cpu()), int(self.status.cpu())
+            if st & _ffi.EVENTS_NONFINITE:
+                raise ValueError("the probabilities hold a NaN or an infinity")
+            if st & _ffi.EVENTS_OVERFLOW or n > self.capacity:
+                if self._rerun is None:
+                    raise ValueError("%d events for a table of %d rows" % (n, self.capacity))
+                self._set(*self._rerun(n))
+                n, st = int(self.count.cpu()), int(self.status.cpu())
+                if st or n > self.capacity:
+                    raise RuntimeError("event table: status %d, %d events for %d rows after the second pass" % (st, n, self.capacity))
+            self._n = n
+        return self
+
+    def __len__(self):
+        return self.check()._n
+
+    def to_lists(self, labels=None):
+        """One list per clip of (class, onset_s, offset_s, peak, mean), sorted like decode_events' output, by
+        (onset, offset, str(class)); class is labels[c] when labels are given, else c."""
+        if labels is not None and len(labels) != self.classes:
+            raise ValueError("%d labels for %d classes" % (len(labels), self.classes))
+        n = len(self)
+        rows = self.table[:n].cpu().contiguous().numpy()
+        clip, cls, begin, end = (rows[:, i].tolist() for i in range(4))
+        peak = rows.view(np.float32)[:, 4].tolist()
+        mean = rows.view(np.float64)[:, 3].tolist()
+        out = [[] for _ in self.edges]
+        for i in range(n):
+            e = self.edges[clip[i]]
+            c = cls[i]
+            out[clip[i]].append((labels[c] if labels is not None else c, float(e[begin[i]]), float(e[end[i]]), peak[i], mean[i]))
+        for events in out:
+            events.sort(key=lambda ev: (ev[1], ev[2], str(ev[0])))
+        return out
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def decode_events_gpu(probs, threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=0.0, step=SEGMENT_SECONDS,
+                      capacity=None, steps=None):
+    """decode_events for whole batches on the GPU (acx_decode_events): the same events, bit for bit, except that `mean` is the
+    float64 mean of the event's rows (decode_events takes numpy's float32 one).  probs: a fp32 CUDA tensor (steps, N) or
+    (B, steps, N) -- the last stride must be 1; a row stride is passed on where the layout allows it, else a contiguous copy is
+    made -- or up to 256 clips of different lengths: a list of (steps_i, N) tensors, or one packed (sum(steps), N) tensor with
+    steps=[...].  step: seconds per row, or boundaries as segment_edges gives them ((steps + 1,), or one such array per clip):
+    k * step for k < steps and any positive last one; other boundaries raise ValueError.  capacity: rows of the table
+    (default max(1024, 16 * clips)); a table that turns out too small is decoded again at the exact size when it is first
+    read.  Runs on the current stream without synchronising.  Returns an EventTable."""
+    torch = _torch()
+    low = check_event_args(threshold, low, median, min_duration, merge_gap)
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0):
+        raise ValueError("capacity must be a non-negative integer (got %r)" % (capacity,))
+    # ---- the clips: uniform (B, S, N) or ragged (steps per clip over packed rows)
+    ragged = None
+    if isinstance(probs, (list, tuple)):
+        if steps is not None:
+            raise ValueError("steps= goes with one packed tensor, not with a list of clips")
+        if not probs:
+            raise ValueError("decode_events_gpu expects at least one clip")
+        if len(probs) > _ffi.MAX_VARLEN_CLIPS:
+            raise ValueError("at most %d clips of different lengths per call (got %d)" % (_ffi.MAX_VARLEN_CLIPS, len(probs)))
+        for t in probs:
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != probs[0].shape[1]:
+                raise ValueError("decode_events_gpu expects a list of (steps, classes) tensors of one class count")
+        ragged = [int(t.shape[0]) for t in probs]
+        first = probs[0]
+    else:
+        if not isinstance(probs, torch.Tensor):
+            raise ValueError("decode_events_gpu expects CUDA tensors (got %s); decode_events takes arrays" % type(probs).__name__)
+        first = probs
+        if steps is not None:
+            ragged = [int(n) for n in steps]
+            if len(ragged) > _ffi.MAX_VARLEN_CLIPS:
+                raise ValueError("at most %d clips of different lengths per call (got %d)" % (_ffi.MAX_VARLEN_CLIPS, len(ragged)))
+            if probs.dim() != 2 or not ragged or sum(ragged) != probs.shape[0]:
+                raise ValueError("steps=%r do not add up to the %r packed rows" % (ragged, tuple(probs.shape)))
+        elif probs.dim() not in (2, 3):
+            raise ValueError("decode_events_gpu expects (steps, classes) or (batch, steps, classes) probabilities, got shape %r"
+                             % (tuple(probs.shape),))
+    if ragged is not None:
+        clip_steps = ragged
+    elif probs.dim() == 2:
+        clip_steps = [int(probs.shape[0])]
+    else:
+        clip_steps = [int(probs.shape[1])] * int(probs.shape[0])
+    N = int(first.shape[-1])
+    if not clip_steps or min(clip_steps) < 1 or N < 1:
+        raise ValueError("decode_events_gpu needs at least one step and one class per clip (steps %r, %d classes)"
+                         % (clip_steps if len(clip_steps) <= 8 else clip_steps[:8] + ["..."], N))
+    B = len(clip_steps)
+    # ---- the boundaries: one step and a last boundary per clip
+    ends = None
+    per_clip = isinstance(step, (list, tuple)) and len(step) > 0 and np.ndim(step[0]) == 1
+    if not per_clip and np.ndim(step) == 0:
+        if not step > 0:
+            raise ValueError("step must be positive (got %r)" % (step,))
+        step_s = float(step)
+    else:
+        if per_clip and len(step) != B:
+            raise ValueError("%d boundary arrays for %d clips" % (len(step), B))
+        if not per_clip and len(set(clip_steps)) != 1:
+            raise ValueError("clips of different lengths need one boundary array each")
+        found = [_uniform_edges(step[i] if per_clip else step, clip_steps[i]) for i in range(B if per_clip else 1)]
+        known = {s for s, _ in found if s is not None}
+        if len(known) > 1:
+            raise ValueError(_GPU_EDGES + "; the clips' boundaries have different steps: %r" % (sorted(known),))
+        step_s = known.pop() if known else found[0][1]
+        ends = [e for _, e in found] * (1 if per_clip else B)
+    edges = []
+    memo = {}
+    for i, n in enumerate(clip_steps):
+        key = (n, None if ends is None else ends[i])
+        if key not in memo:
+            e = np.arange(n + 1, dtype=np.float64) * step_s
+            if ends is not None:
+                e[n] = ends[i]
+            memo[key] = e
+        edges.append(memo[key])
+    # ---- device, dtype, layout
+    tensors = list(probs) if isinstance(probs, (list, tuple)) else [probs]
+    for t in tensors:
+        if not t.is_cuda:
+            raise ValueError("decode_events_gpu expects CUDA tensors (got a %s tensor); decode_events decodes on the host"
+                             % t.device.type)
+        if t.dtype != torch.float32:
+            raise ValueError("decode_events_gpu expects float32 probabilities (got %s)" % (t.dtype,))
+        if t.device != first.device:
+            raise ValueError("the clips lie on different devices")
+    dev = first.device
+    if isinstance(probs, (list, tuple)):
+        x = torch.cat([t.detach() for t in probs]) if len(probs) > 1 else probs[0].detach().contiguous()
+    else:
+        x = probs.detach()
+    rows_of = x.shape[-2]
+    if x.stride(-1) != 1 and N > 1:
+        x = x.contiguous()
+    ld = x.stride(-2) if rows_of > 1 else (x.stride(0) if x.dim() == 3 and x.shape[0] > 1 else N)
+    if ld < N or (x.dim() == 3 and x.shape[0] > 1 and x.stride(0) != rows_of * ld):
+        x = x.contiguous()
+        ld = N
+    uniform_end = None
+    if ragged is None and (ends is None or len(set(ends)) == 1):
+        uniform_end = 0.0 if ends is None else ends[0]
+    elif B > _ffi.MAX_VARLEN_CLIPS:
+        raise ValueError("at most %d clips with boundaries of their own per call (got %d)" % (_ffi.MAX_VARLEN_CLIPS, B))
+    params = _ffi.event_params(threshold, low, median, min_duration, merge_gap)
+    cap0 = max(1024, 16 * B) if capacity is None else capacity
+
+    def run(cap):
+        with torch.cuda.device(dev):
+            table = torch.zeros((max(cap, 1), _ffi.EVENT_BYTES // 4), dtype=torch.int32, device=dev)
+            meta = torch.zeros(4, dtype=torch.int32, device=dev)
+            count, status = meta[:2].view(torch.int64), meta[2:3]
+            ws = torch.empty(_ffi.events_workspace_bytes(B, N), dtype=torch.uint8, device=dev)
+            if uniform_end is not None:
+                _ffi.check(_ffi.lib().acx_decode_events(x.data_ptr(), ld, B, clip_steps[0], N, ctypes.byref(params), step_s,
+                                                        uniform_end, table.data_ptr(), cap, count.data_ptr(), status.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), _ffi.stream_ptr(dev)))
+            else:
+                c_steps = (ctypes.c_int * B)(*clip_steps)
+                c_ends = None if ends is None else (ctypes.c_double * B)(*ends)
+                _ffi.check(_ffi.lib().acx_decode_events_varlen(x.data_ptr(), ld, c_steps, c_ends, B, N, ctypes.byref(params),
+                                                               step_s, table.data_ptr(), cap, count.data_ptr(),
+                                                               status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                               _ffi.stream_ptr(dev)))
+        return table, count, status
+
+    return EventTable(*run(cap0), edges=edges, classes=N, rerun=run)

@@ -262,6 +262,50 @@ ACX_API int acx_segment_expand_varlen(const float* probs, const int64_t* lengths
 ACX_API int acx_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
                                  int reduce, float* out, void* stream);
 
+/* ---- sound event decoding: probabilities over time -> a table of events --------------------------------------------------------
+ * The reference leaves this step to its harness (pytorch/inference.py:156-200 thresholds "framewise_output" on the host).  The
+ * definition here is pytorch/segments.py::decode_events, the host function of this project, restated for a batch; the device
+ * table equals its output bit for bit except `mean`, which is float64 here (decode_events takes numpy's float32 mean).
+ * probs: device fp32, rows of N classes with row stride ld >= N floats; clip i owns steps_i consecutive rows (acx_decode_events:
+ * rows [i steps, (i + 1) steps); acx_decode_events_varlen: the clips back to back, steps[i] rows each, B <= ACX_MAX_VARLEN_CLIPS).
+ * For every (clip, class) column, independently:
+ *   1. median: an odd running median of width p->median over time, the ends repeating the first / last row (the width may
+ *      exceed steps_i; 1 = identity).  A selection: the result is one of the input values.
+ *   2. boundaries, float64: edges[k] = (double)k * step_seconds for k < steps_i, edges[steps_i] = the clip's end_seconds, or
+ *      (double)steps_i * step_seconds when that is <= 0 (varlen: or end_seconds == NULL) -- segments.segment_edges().
+ *   3. runs: a maximal stretch of filtered q >= p->low is a run; it is valid if it holds a q >= p->threshold (fp32 comparisons).
+ *   4. merge, in time order: a valid run [b, e) joins the previous (possibly merged) event when edges[b] - edges[prev end] <
+ *      p->merge_gap (float64); the event then reaches to e and contains the gap rows and any invalid runs between.
+ *   5. minimum duration: an event with edges[end] - edges[begin] < p->min_duration (float64) is dropped, after merging.
+ *   6. per event: begin, end (exclusive) in steps; peak = the fp32 maximum of q over [begin, end); mean = the float64 sum of
+ *      those q in ascending time, divided by their count.
+ * events: device table of `capacity` rows, written in the order (clip, cls, begin), the same bits on every call (offsets come
+ * from a count pass and an exclusive scan; no atomic orders anything).  *count (device int64) = the TOTAL number of events; when
+ * it exceeds capacity the first `capacity` rows in table order are written and ACX_EVENTS_OVERFLOW is set in *status (device
+ * int): call again with capacity >= *count.  A NaN or +-inf in any probs row read sets ACX_EVENTS_NONFINITE, *count = 0, and
+ * nothing is written.  *status is cleared first.  Rows past *count are left untouched.
+ * acx_forward's launch contract: everything in order on `stream` (a 4-byte clear, three kernels, one more for the varlen
+ * tables, whose steps / end_seconds travel by value), no allocation, no synchronisation, capturable.  Stateless: no acx_ctx.
+ * ws: acx_events_workspace_bytes(B, N) bytes, 256-byte aligned (host only; non-decreasing in both arguments).
+ * Argument errors are returned before anything touches the device.  ACX_ERR_ARG: a null pointer; median even, < 1 or >
+ * ACX_MAX_EVENT_MEDIAN; low outside [0, threshold]; negative min_duration or merge_gap; step_seconds <= 0; capacity < 0.
+ * ACX_ERR_SHAPE: steps < 1 (or > 2^30); N < 1 or N > ACX_MAX_CLASSES; ld < N; B < 1 (varlen: B > ACX_MAX_VARLEN_CLIPS).
+ * ACX_ERR_WORKSPACE: ws too small or not 256-byte aligned.  ACX_ERR_UNSUPPORTED: B * ceil(N / 64) beyond a launchable grid
+ * (2^31 - 1 workgroups). */
+typedef struct acx_event { int32_t clip, cls, begin, end; float peak, reserved; double mean; } acx_event;   /* 32 bytes; reserved = 0 */
+typedef struct acx_event_params { float threshold, low; int median; double min_duration, merge_gap; } acx_event_params;
+#define ACX_MAX_EVENT_MEDIAN 101          /* ~1 s of frames, 32 s of segments */
+#define ACX_EVENTS_NONFINITE 1
+#define ACX_EVENTS_OVERFLOW  2
+ACX_API int acx_events_workspace_bytes(int64_t B, int N, size_t* bytes);                                   /* host only */
+ACX_API int acx_decode_events(const float* probs, int64_t ld, int64_t B, int steps, int N, const acx_event_params* p,
+                              double step_seconds, double end_seconds /* <= 0: steps * step_seconds */, acx_event* events,
+                              int64_t capacity, int64_t* count, int* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_decode_events_varlen(const float* probs, int64_t ld, const int* steps /* HOST, B */,
+                                     const double* end_seconds /* HOST, B, or NULL */, int B /* <= ACX_MAX_VARLEN_CLIPS */, int N,
+                                     const acx_event_params* p, double step_seconds, acx_event* events, int64_t capacity,
+                                     int64_t* count, int* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- live streams: tagging recordings that arrive chunk by chunk ----------------------------------------------------------
  * No reference counterpart.  A handle has `slots`; each slot holds one recording at a time.  Samples pushed to a slot are
  * appended to its open recording; acx_stream_close ends it and the slot's next push starts a new one.  Window W, hop H, the
