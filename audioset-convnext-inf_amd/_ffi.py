@@ -185,6 +185,9 @@ def stream_ptr(device):
 
 PRECISIONS = {"fp32": 0, "bf16": 1, "fp32_split": 2, "bf16a": 3}
 FRONTENDS = {"auto": 0, "dense": 1}      # enum acx_frontend
+# the five output kinds of the forwards (`what=`): enum acx_mode, and enum acx_segment_what of the acx_forward_segments* calls
+MODES = {"logits": MODE_LOGITS, "scene": MODE_SCENE, "frame": MODE_FRAME}
+SEG_WHAT = {"segment": SEG_OUTPUT, "segment_embeddings": SEG_EMBED}
 
 
 class Context:
@@ -235,37 +238,24 @@ class Context:
         check(lib().acx_num_classes(self._h, ctypes.byref(out)))
         return out.value
 
-    def workspace_bytes(self, B, L, mode):
+    def _workspace_bytes(self, geometry, kind, *args):
+        """acx_workspace_bytes<geometry> for an output kind: a key of MODES (or the acx_mode value itself), or a key of
+        SEG_WHAT, which goes to the _segments form of the call."""
+        seg = kind in SEG_WHAT
+        fn = getattr(lib(), "acx_workspace_bytes" + ("_segments" if seg else "") + geometry)
         out = _c_sz()
-        check(lib().acx_workspace_bytes(self._h, int(B), int(L), int(mode), ctypes.byref(out)))
+        check(fn(self._h, *args, SEG_WHAT[kind] if seg else int(MODES.get(kind, kind)), ctypes.byref(out)))
         return out.value
 
-    def workspace_bytes_varlen(self, lengths, mode):
+    def workspace_bytes(self, B, L, kind):
+        return self._workspace_bytes("", kind, int(B), int(L))
+
+    def workspace_bytes_varlen(self, lengths, kind):
         lens = (_c_i64 * max(1, len(lengths)))(*[int(n) for n in lengths])
-        out = _c_sz()
-        check(lib().acx_workspace_bytes_varlen(self._h, lens, len(lengths), int(mode), ctypes.byref(out)))
-        return out.value
+        return self._workspace_bytes("_varlen", kind, lens, len(lengths))
 
-    def workspace_bytes_windows(self, count, window, mode):
-        out = _c_sz()
-        check(lib().acx_workspace_bytes_windows(self._h, int(count), int(window), int(mode), ctypes.byref(out)))
-        return out.value
-
-    def workspace_bytes_segments(self, B, L, what):
-        out = _c_sz()
-        check(lib().acx_workspace_bytes_segments(self._h, int(B), int(L), int(what), ctypes.byref(out)))
-        return out.value
-
-    def workspace_bytes_segments_varlen(self, lengths, what):
-        lens = (_c_i64 * max(1, len(lengths)))(*[int(n) for n in lengths])
-        out = _c_sz()
-        check(lib().acx_workspace_bytes_segments_varlen(self._h, lens, len(lengths), int(what), ctypes.byref(out)))
-        return out.value
-
-    def workspace_bytes_segments_windows(self, count, window, what):
-        out = _c_sz()
-        check(lib().acx_workspace_bytes_segments_windows(self._h, int(count), int(window), int(what), ctypes.byref(out)))
-        return out.value
+    def workspace_bytes_windows(self, count, window, kind):
+        return self._workspace_bytes("_windows", kind, int(count), int(window))
 
     def sub_batches(self, B):
         """How many sub-batches (on separate streams) a forward of B clips runs as (acx_sub_batches)."""

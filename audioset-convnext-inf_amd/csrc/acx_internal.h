@@ -375,7 +375,7 @@ int launch_gemm_bf16(acx_ctx* c, const GemmBf16Args& a, hipStream_t s);
 // fp32 operands as two fp16 halves (gemm_split.hip): A, Wt in S16 form; EPI_GELU writes S16, the others fp32
 constexpr float kSplitLnScale = 2048.0f;      // LayerNorm rows: |LN(y)| <= sqrt(C-1) < 28 -> < 2^15.8
 // The GELU output (hidden activation) is scaled per block by BlockW::hid_scale, a power of two chosen at acx_finalize
-// from a rigorous bound on |pwconv1 output| (api.hip, hidden_scale_for): the fp16 range cannot be exceeded.
+// from a rigorous bound on |pwconv1 output| (weights.hip, hidden_scale_for): the fp16 range cannot be exceeded.
 int launch_layernorm_rows_split(acx_ctx* c, const float* x, void* out, int64_t M, int C, hipStream_t s);
 struct GemmSplitArgs {
     const void* A; const void* Wt; const float* bias; void* out; const float* resid;
@@ -494,12 +494,45 @@ __device__ __forceinline__ float res_chain(const float* xs, const float* h, int 
     return acc;
 }
 
-// ---- live streams (stream.hip) ------------------------------------------------------------------------------------------
-// The uniform forward of count windows of L samples at ring + wstart[b] (api.hip's forward_uniform, the acx_forward_windows
-// path); the caller has written the table on `st` and checked the arguments.
-int forward_windows_at(acx_ctx* c, const float* ring, int count, int64_t L, int mode, float* out0, float* out1, char* ws,
-                       hipStream_t st, const long long* wstart);
-int ctx_ready(const acx_ctx* c);
+// ---- host code shared by api.hip, weights.hip, forward.hip and stream.hip ------------------------------------------------
+// bf16 activations in HBM for the stages that keep them (ACX_PREC_BF16_ACT, stages 0-2)
+inline bool act_bf16(const acx_ctx* c, int stage) { return c->precision == ACX_PREC_BF16_ACT && stage >= 0 && stage < 3; }
+inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+int need_ready(const acx_ctx* c);                     // api.hip: a context with finalized weights
+void free_device(acx_ctx* c);                         // weights.hip: every device allocation of the context
+int make_aux(acx_ctx::Aux* a);                        // forward.hip: one fork/join set of the batch split
+void destroy_aux(acx_ctx::Aux& a);
+// "workspace of %zu bytes is smaller than the %zu needed" / "must be 256-byte aligned", in that order
+int check_workspace(const void* ptr, size_t bytes, size_t need);
+// The scratch of one block over pix pixels of C channels, carved from `off` on: y [pix][C], hidden [pix][4C], stats [pix][2]
+// (fp32 each, 256-byte aligned); end = the first byte after it.
+struct BlockScratch { size_t y, hidden, stats, end; };
+inline BlockScratch carve_block_scratch(size_t pix, int C, size_t off) {
+    BlockScratch b;
+    b.y = off; off += align_up(pix * C * 4);
+    b.hidden = off; off += align_up(pix * 4 * C * 4);
+    b.stats = off; off += align_up(pix * 2 * 4);
+    b.end = off;
+    return b;
+}
+// one block / one downsample layer (forward.hip), shared by the forward and the per-layer entry points
+// vg: a variable-length batch (acx_forward_varlen) -- B = 1 and H = the stage's total rows then, so that M counts every pixel;
+// only the depthwise conv needs the per-clip tables
+int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, int B, int H, int Wd, hipStream_t st,
+              void* ln_out = nullptr, const VarGeom* vg = nullptr);
+// have_ln: xnorm already holds the normalised S16 rows (written by the last block of the previous stage)
+// out_bf16: the result is the bf16 activation tensor of stage i (ACX_PREC_BF16_ACT inside acx_forward; the per-layer entry
+// point keeps fp32)
+// vg: a variable-length batch -- B = 1 and H = the input stage's total rows; the output rows and the gather come from the tables
+// (a clip of odd height drops its last row, as the stride-2 conv does)
+int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, int B, int H, int Wd, hipStream_t st,
+                   bool have_ln = false, bool out_bf16 = false, const VarGeom* vg = nullptr);
+// The uniform forward of B clips of L samples with the batch split (acx_forward; arguments checked by the caller).  wstart: the
+// window table of acx_forward_windows / acx_stream_forward, written on `st` by the caller -- clip b's samples start at
+// wav + wstart[b], sub-batch i gets its slice of the table and the whole of wav.  seg: the segment tail instead of `mode`'s.
+struct SegTail;
+int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws, hipStream_t st,
+                    const long long* wstart, const SegTail* seg = nullptr);
 
 // number of CUs of the current device (one persistent workgroup each), cached per device
 inline int cu_count_of_current_device(int* out) {

@@ -387,7 +387,7 @@ int acx_stream_create(acx_ctx* c, int slots, int64_t window, int64_t hop, int or
                       acx_stream** out) {
     if (!c || !out) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: null argument");
     *out = nullptr;
-    ACX_TRY(ctx_ready(c));
+    ACX_TRY(need_ready(c));
     if (slots < 1 || slots > (1 << 20)) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: %d slots (expected 1 .. 2^20)", slots);
     if (timeline != 0 && timeline != 1) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: timeline must be 0 or 1 (got %d)", timeline);
     StrGeom g;
@@ -562,7 +562,7 @@ int acx_stream_next(const acx_stream* st, int max, int* slot_of, int64_t* start_
 int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* out1, void* workspace, size_t workspace_bytes,
                        void* stream) {
     if (!st) ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: null handle");
-    ACX_TRY(ctx_ready(st->ctx));
+    ACX_TRY(need_ready(st->ctx));
     ACX_TRY(check_classes(st, "acx_stream_forward"));
     if (!out0 || !workspace) ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: null pointer");
     if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: bad mode %d", mode);
@@ -579,8 +579,7 @@ int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* 
         ACX_FAIL(ACX_ERR_ARG, "acx_stream_forward: %d windows asked, %d pending of one length (acx_stream_next)", count, got);
     size_t need = 0;
     ACX_TRY(acx_workspace_bytes_windows(st->ctx, count, L, mode, &need));
-    if (workspace_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-    if (((uintptr_t)workspace & 255) != 0) ACX_FAIL(ACX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    ACX_TRY(check_workspace(workspace, workspace_bytes, need));
     hipStream_t s = (hipStream_t)stream;
     DeviceGuard dg(st->device);
     long long* wstart = (long long*)workspace;
@@ -594,7 +593,7 @@ int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* 
         ACX_HIP(hipGetLastError());
     }
     const size_t head = ((size_t)count * 8 + 255) & ~(size_t)255;
-    ACX_TRY(forward_windows_at(st->ctx, st->ring, count, L, mode, out0, out1, (char*)workspace + head, s, wstart));
+    ACX_TRY(forward_uniform(st->ctx, st->ring, count, L, mode, out0, out1, (char*)workspace + head, s, wstart));
     if (st->timeline) {
         // window j of slot i -> history row i Hw + j mod Hw; slot i's windows are listed in order from its win_done on
         std::vector<long long> next(st->slots, -1), row(count);

@@ -215,11 +215,13 @@ class ConvNeXt(nn.Module):
             self._ws_captured.clear()
         return out
 
+    # native handles (ctypes) and scratch tensors are per-process state, rebuilt on demand: field -> its empty value
+    _PER_PROCESS = {"_ctx": dict, "_ws": dict, "_resamplers": dict, "_ws_retired": list, "_ws_captured": set,
+                    "_sig_cache": lambda: None}
+
     def __getstate__(self):
-        # native handles (ctypes) and scratch tensors are per-process state, rebuilt on demand
         state = self.__dict__.copy()
-        state["_ctx"], state["_ws"], state["_ws_retired"], state["_ws_captured"], state["_sig_cache"] = {}, {}, [], set(), None
-        state["_resamplers"] = {}
+        state.update((k, make()) for k, make in self._PER_PROCESS.items())
         return state
 
     def __deepcopy__(self, memo):
@@ -228,16 +230,7 @@ class ConvNeXt(nn.Module):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k in ("_ctx", "_ws", "_resamplers"):
-                new.__dict__[k] = {}
-            elif k == "_ws_retired":
-                new.__dict__[k] = []
-            elif k == "_ws_captured":
-                new.__dict__[k] = set()
-            elif k == "_sig_cache":
-                new.__dict__[k] = None
-            else:
-                new.__dict__[k] = copy.deepcopy(v, memo)
+            new.__dict__[k] = self._PER_PROCESS[k]() if k in self._PER_PROCESS else copy.deepcopy(v, memo)
         return new
 
     def set_precision(self, precision):
@@ -322,37 +315,10 @@ class ConvNeXt(nn.Module):
         if ws.data_ptr() in self._ws_captured:
             self._ws_retired.append(ws)
 
-    def _run(self, x, mode):
-        if self.training:
-            raise RuntimeError("inference-only path: call model.eval() first (the reference's training branches -- "
-                               "augmentations, SpecAugment, mixup -- are not part of this build)")
+    @staticmethod
+    def _check_batch(x):
         if not isinstance(x, torch.Tensor) or x.dim() != 2:
             raise ValueError("expected a (batch, samples) waveform tensor, got %r" % (getattr(x, "shape", type(x)),))
-        wdev = self.head_audioset.weight.device
-        if wdev.type != "cuda" or x.device.type != "cuda":
-            raise RuntimeError("the MI355X path runs on the GPU only (model on %s, input on %s): "
-                               "move both with .to('cuda'); there is no CPU fallback" % (wdev, x.device))
-        if x.device != wdev:
-            raise RuntimeError("input on %s but model on %s" % (x.device, wdev))
-        x = x.detach().to(torch.float32).contiguous()
-        B, L = x.shape
-        if L < _ffi.MIN_SAMPLES:
-            raise RuntimeError("clip of %d samples is too short: kernel size can't be greater than actual input size "
-                               "(minimum is %d samples)" % (L, _ffi.MIN_SAMPLES))
-        with torch.cuda.device(x.device):
-            ctx = self.native_context(x.device)
-            ws = self._workspace(x.device, ctx.workspace_bytes(B, L, mode))
-            if mode == _ffi.MODE_LOGITS:
-                out0 = torch.empty((B, ctx.classes), dtype=torch.float32, device=x.device)
-                out1 = torch.empty((B, ctx.classes), dtype=torch.float32, device=x.device)
-            elif mode == _ffi.MODE_SCENE:
-                out0, out1 = torch.empty((B, 768), dtype=torch.float32, device=x.device), None
-            else:
-                h3, w3 = _ffi.stage_hw(L, 3)
-                out0, out1 = torch.empty((B, 768, h3, w3), dtype=torch.float32, device=x.device), None
-            _ffi.check(_ffi.lib().acx_forward(ctx.handle, _ffi.ptr(x), B, L, mode, _ffi.ptr(out0), _ffi.ptr(out1),
-                                              _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(x.device)))
-        return out0, out1
 
     def _check_run(self, device):
         if self.training:
@@ -365,23 +331,94 @@ class ConvNeXt(nn.Module):
         if device != wdev:
             raise RuntimeError("input on %s but model on %s" % (device, wdev))
 
-    def _run_varlen(self, wav, lengths, mode):
-        """wav: packed 1-D fp32 CUDA tensor, lengths: list of <= 256 ints summing to wav.numel()."""
-        B = len(lengths)
-        with torch.cuda.device(wav.device):
-            ctx = self.native_context(wav.device)
-            ws = self._workspace(wav.device, ctx.workspace_bytes_varlen(lengths, mode))
-            if mode == _ffi.MODE_LOGITS:
-                out0 = torch.empty((B, ctx.classes), dtype=torch.float32, device=wav.device)
-                out1 = torch.empty((B, ctx.classes), dtype=torch.float32, device=wav.device)
-            elif mode == _ffi.MODE_SCENE:
-                out0, out1 = torch.empty((B, 768), dtype=torch.float32, device=wav.device), None
+    @staticmethod
+    def _outputs(kind, lead, classes, L, device, clips=None):
+        """The (out0, out1, clip) of one ABI call of output kind `kind` (a key of _ffi.MODES or _ffi.SEG_WHAT).  `lead`: the
+        leading shape -- clips or windows of L samples each, or (L = None) the packed rows of a variable-length batch, whose
+        "segment" clip maxima have `clips` rows.  What a kind does not have is None."""
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        if kind == "logits":
+            return new(*lead, classes), new(*lead, classes), None
+        if kind == "scene":
+            return new(*lead, 768), None, None
+        if kind == "frame":
+            return (new(*lead) if L is None else new(*lead, 768, *_ffi.stage_hw(L, 3))), None, None
+        if L is not None:
+            lead = lead + (_seg.segment_count(L),)
+        if kind == "segment":
+            return new(*lead, classes), new(*lead, classes), new(lead[0] if clips is None else clips, classes)
+        return new(*lead, 768), None, None
+
+    # The three runners: one ABI call (windows: one per max_batch windows) of any output kind on packed 32 kHz fp32 audio.  Each
+    # returns (out0, out1, clip) as _outputs names them; `pool` matters to the two segment kinds only.
+    def _run(self, x, kind, pool=3):
+        """(B, L) -> acx_forward / acx_forward_segments."""
+        self._check_batch(x)
+        self._check_run(x.device)
+        x = x.detach().to(torch.float32).contiguous()
+        B, L = x.shape
+        if L < _ffi.MIN_SAMPLES:
+            raise RuntimeError("clip of %d samples is too short: kernel size can't be greater than actual input size "
+                               "(minimum is %d samples)" % (L, _ffi.MIN_SAMPLES))
+        dev, seg = x.device, _ffi.SEG_WHAT.get(kind)
+        with torch.cuda.device(dev):
+            ctx = self.native_context(dev)
+            ws = self._workspace(dev, ctx.workspace_bytes(B, L, kind))
+            out0, out1, clip = self._outputs(kind, (B,), ctx.classes, L, dev)
+            if seg is None:
+                _ffi.check(_ffi.lib().acx_forward(ctx.handle, _ffi.ptr(x), B, L, _ffi.MODES[kind], _ffi.ptr(out0), _ffi.ptr(out1),
+                                                  _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
             else:
-                out0, out1 = torch.empty(varlen_frame_layout(lengths)[-1], dtype=torch.float32, device=wav.device), None
+                _ffi.check(_ffi.lib().acx_forward_segments(ctx.handle, _ffi.ptr(x), B, L, pool, seg, _ffi.ptr(out0), _ffi.ptr(out1),
+                                                           _ffi.ptr(clip), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
+        return out0, out1, clip
+
+    def _run_varlen(self, wav, lengths, kind, pool=3):
+        """wav: packed 1-D tensor, lengths: list of <= 256 ints summing to wav.numel() -> acx_forward_varlen /
+        acx_forward_segments_varlen.  Frame blocks (varlen_frame_layout) and segment rows (sum(S_i)) lie back to back."""
+        B, dev, seg = len(lengths), wav.device, _ffi.SEG_WHAT.get(kind)
+        if kind == "frame":
+            lead = (varlen_frame_layout(lengths)[-1],)
+        else:
+            lead = (B if seg is None else sum(_seg.segment_count(n) for n in lengths),)
+        with torch.cuda.device(dev):
+            ctx = self.native_context(dev)
+            ws = self._workspace(dev, ctx.workspace_bytes_varlen(lengths, kind))
+            out0, out1, clip = self._outputs(kind, lead, ctx.classes, None, dev, clips=B)
             lens = (ctypes.c_int64 * B)(*lengths)
-            _ffi.check(_ffi.lib().acx_forward_varlen(ctx.handle, _ffi.ptr(wav), lens, B, mode, _ffi.ptr(out0), _ffi.ptr(out1),
-                                                     _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(wav.device)))
-        return out0, out1
+            if seg is None:
+                _ffi.check(_ffi.lib().acx_forward_varlen(ctx.handle, _ffi.ptr(wav), lens, B, _ffi.MODES[kind], _ffi.ptr(out0),
+                                                         _ffi.ptr(out1), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
+            else:
+                _ffi.check(_ffi.lib().acx_forward_segments_varlen(ctx.handle, _ffi.ptr(wav), lens, B, pool, seg, _ffi.ptr(out0),
+                                                                  _ffi.ptr(out1), _ffi.ptr(clip), _ffi.ptr(ws), ws.numel(),
+                                                                  _ffi.stream_ptr(dev)))
+        return out0, out1, clip
+
+    def _run_windows(self, wav, lengths, W, H, kind, max_batch, pool=3):
+        """Every window of recordings longer than W (<= 256, packed in wav) -> acx_forward_windows /
+        acx_forward_segments_windows, max_batch at a time: one row (frame, segment kinds: one block) per window, in window
+        order."""
+        n = _ffi.window_count(lengths, W, H)
+        dev, seg = wav.device, _ffi.SEG_WHAT.get(kind)
+        with torch.cuda.device(dev):
+            ctx = self.native_context(dev)
+            out0, out1, clip = self._outputs(kind, (n,), ctx.classes, W, dev)
+            ws = self._workspace(dev, ctx.workspace_bytes_windows(min(n, max_batch), W, kind))
+            lens = (ctypes.c_int64 * len(lengths))(*lengths)
+            for first in range(0, n, max_batch):
+                count = min(max_batch, n - first)
+                o0, o1, cl = (None if t is None else _ffi.ptr(t[first:first + count]) for t in (out0, out1, clip))
+                if seg is None:
+                    _ffi.check(_ffi.lib().acx_forward_windows(ctx.handle, _ffi.ptr(wav), lens, len(lengths), W, H, first, count,
+                                                              _ffi.MODES[kind], o0, o1, _ffi.ptr(ws), ws.numel(),
+                                                              _ffi.stream_ptr(dev)))
+                else:
+                    _ffi.check(_ffi.lib().acx_forward_segments_windows(ctx.handle, _ffi.ptr(wav), lens, len(lengths), W, H, first,
+                                                                       count, pool, seg, o0, o1, cl, _ffi.ptr(ws), ws.numel(),
+                                                                       _ffi.stream_ptr(dev)))
+        return out0, out1, clip
 
     def _rate(self, sample_rate):
         """None when the input is at the model rate (today's path, nothing extra launched), else the checked integer rate."""
@@ -395,56 +432,10 @@ class ConvNeXt(nn.Module):
         rate = self._rate(sample_rate)
         if rate is None:
             return x
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise ValueError("expected a (batch, samples) waveform tensor, got %r" % (getattr(x, "shape", type(x)),))
+        self._check_batch(x)
         self._check_run(x.device)
         _rs.check_min_length(x.shape[1], rate)
         return _rs.resample(x, rate, _rs.MODEL_RATE, _cache=self._resamplers)
-
-    def _run_segments(self, x, pool, what):
-        """(B, L) at 32 kHz -> acx_forward_segments: (logits, probs, clip maximum) each over (B, S, N) / (B, N) for
-        what = SEG_OUTPUT, (embeddings (B, S, 768), None, None) for SEG_EMBED."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise ValueError("expected a (batch, samples) waveform tensor, got %r" % (getattr(x, "shape", type(x)),))
-        self._check_run(x.device)
-        x = x.detach().to(torch.float32).contiguous()
-        B, L = x.shape
-        if L < _ffi.MIN_SAMPLES:
-            raise RuntimeError("clip of %d samples is too short: kernel size can't be greater than actual input size "
-                               "(minimum is %d samples)" % (L, _ffi.MIN_SAMPLES))
-        S = _seg.segment_count(L)
-        with torch.cuda.device(x.device):
-            ctx = self.native_context(x.device)
-            ws = self._workspace(x.device, ctx.workspace_bytes_segments(B, L, what))
-            if what == _ffi.SEG_OUTPUT:
-                out0 = torch.empty((B, S, ctx.classes), dtype=torch.float32, device=x.device)
-                out1 = torch.empty((B, S, ctx.classes), dtype=torch.float32, device=x.device)
-                clip = torch.empty((B, ctx.classes), dtype=torch.float32, device=x.device)
-            else:
-                out0, out1, clip = torch.empty((B, S, 768), dtype=torch.float32, device=x.device), None, None
-            _ffi.check(_ffi.lib().acx_forward_segments(ctx.handle, _ffi.ptr(x), B, L, pool, what, _ffi.ptr(out0), _ffi.ptr(out1),
-                                                       _ffi.ptr(clip), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(x.device)))
-        return out0, out1, clip
-
-    def _run_varlen_segments(self, wav, lengths, pool, what):
-        """_run_varlen for the segment outputs: rows of all clips back to back, sum(S_i) of them."""
-        B = len(lengths)
-        rows = sum(_seg.segment_count(n) for n in lengths)
-        dev = wav.device
-        with torch.cuda.device(dev):
-            ctx = self.native_context(dev)
-            ws = self._workspace(dev, ctx.workspace_bytes_segments_varlen(lengths, what))
-            if what == _ffi.SEG_OUTPUT:
-                out0 = torch.empty((rows, ctx.classes), dtype=torch.float32, device=dev)
-                out1 = torch.empty((rows, ctx.classes), dtype=torch.float32, device=dev)
-                clip = torch.empty((B, ctx.classes), dtype=torch.float32, device=dev)
-            else:
-                out0, out1, clip = torch.empty((rows, 768), dtype=torch.float32, device=dev), None, None
-            lens = (ctypes.c_int64 * B)(*lengths)
-            _ffi.check(_ffi.lib().acx_forward_segments_varlen(ctx.handle, _ffi.ptr(wav), lens, B, pool, what, _ffi.ptr(out0),
-                                                              _ffi.ptr(out1), _ffi.ptr(clip), _ffi.ptr(ws), ws.numel(),
-                                                              _ffi.stream_ptr(dev)))
-        return out0, out1, clip
 
     def _check_segment_call(self, pool):
         """ValueError for a bad pool or a model in train mode, before anything touches the GPU."""
@@ -473,7 +464,7 @@ class ConvNeXt(nn.Module):
         rate = self._rate(sample_rate)
         x_in = x
         x = self._resampled(x_in, sample_rate)
-        logits, probs, clip = self._run_segments(x, pool, _ffi.SEG_OUTPUT)
+        logits, probs, clip = self._run(x, "segment", pool)
         B, S, N = probs.shape
         L = x.shape[1]
         duration = None if rate is None else x_in.shape[1] / rate        # (both calls above have checked the input's shape)
@@ -507,7 +498,7 @@ class ConvNeXt(nn.Module):
         rows are valid fit_head / tagging_metrics inputs as they are (`.reshape(-1, 768)`), so a head can be trained and scored
         on strong labels."""
         self._check_segment_call(pool)
-        return self._run_segments(self._resampled(x, sample_rate), pool, _ffi.SEG_EMBED)[0]
+        return self._run(self._resampled(x, sample_rate), "segment_embeddings", pool)[0]
 
     def forward_varlen(self, clips, lengths=None, what="logits", sample_rate=None, pool=3):
         """Clips of different lengths in one packed forward (acx_forward_varlen); every clip's result is bit-identical to the
@@ -561,14 +552,23 @@ class ConvNeXt(nn.Module):
                                    "(minimum is %d samples)" % (i, n, _ffi.MIN_SAMPLES))
         wav = wav.detach().to(torch.float32).contiguous()
         cap = _ffi.MAX_VARLEN_CLIPS
-        if what in ("segment", "segment_embeddings"):
-            res, s0 = [], 0
-            for c0 in range(0, len(lengths), cap):
-                chunk = lengths[c0:c0 + cap]
-                n = sum(chunk)
-                out0, out1, clip = self._run_varlen_segments(wav[s0:s0 + n], chunk, pool,
-                                                             _ffi.SEG_OUTPUT if what == "segment" else _ffi.SEG_EMBED)
-                s0 += n
+        parts, s0 = [], 0                 # (lengths of the call, out0, out1, clip)
+        for c0 in range(0, len(lengths), cap):
+            chunk = lengths[c0:c0 + cap]
+            n = sum(chunk)
+            parts.append((chunk,) + self._run_varlen(wav[s0:s0 + n], chunk, what, pool))
+            s0 += n
+        if what == "frame":
+            views = []
+            for chunk, buf, _, _ in parts:
+                offs = varlen_frame_layout(chunk)
+                for i in range(len(chunk)):
+                    h3 = (offs[i + 1] - offs[i]) // (768 * 7)
+                    views.append(buf[offs[i]:offs[i + 1]].view(768, h3, 7))
+            return views
+        if what in _ffi.SEG_WHAT:
+            res = []
+            for chunk, out0, out1, clip in parts:
                 r0 = 0
                 for i, L in enumerate(chunk):
                     r1 = r0 + _seg.segment_count(L)
@@ -579,132 +579,11 @@ class ConvNeXt(nn.Module):
                         res.append(out0[r0:r1])
                     r0 = r1
             return res
-        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
-        parts, s0 = [], 0
-        for c0 in range(0, len(lengths), cap):
-            chunk = lengths[c0:c0 + cap]
-            n = sum(chunk)
-            parts.append(self._run_varlen(wav[s0:s0 + n], chunk, mode))
-            s0 += n
-        if what == "frame":
-            views = []
-            for (buf, _), c0 in zip(parts, range(0, len(lengths), cap)):
-                chunk = lengths[c0:c0 + cap]
-                offs = varlen_frame_layout(chunk)
-                for i, L in enumerate(chunk):
-                    h3 = (offs[i + 1] - offs[i]) // (768 * 7)
-                    views.append(buf[offs[i]:offs[i + 1]].view(768, h3, 7))
-            return views
-        out0 = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
+        out0 = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
         if what == "scene":
             return out0
-        out1 = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
+        out1 = parts[0][2] if len(parts) == 1 else torch.cat([p[2] for p in parts])
         return {"clipwise_output": out1, "clipwise_logits": out0}
-
-    def _run_windows(self, wav, lengths, W, H, mode, max_batch):
-        """Every window of recordings longer than W (<= 256, packed in wav) through acx_forward_windows, max_batch at a time.
-        Returns (out0, out1) with one row (frame mode: one (768, T'_W, 7) block) per window, in window order."""
-        n = _ffi.window_count(lengths, W, H)
-        dev = wav.device
-        with torch.cuda.device(dev):
-            ctx = self.native_context(dev)
-            if mode == _ffi.MODE_LOGITS:
-                out0 = torch.empty((n, ctx.classes), dtype=torch.float32, device=dev)
-                out1 = torch.empty((n, ctx.classes), dtype=torch.float32, device=dev)
-            elif mode == _ffi.MODE_SCENE:
-                out0, out1 = torch.empty((n, 768), dtype=torch.float32, device=dev), None
-            else:
-                out0, out1 = torch.empty((n,) + (768,) + _ffi.stage_hw(W, 3), dtype=torch.float32, device=dev), None
-            ws = self._workspace(dev, ctx.workspace_bytes_windows(min(n, max_batch), W, mode))
-            lens = (ctypes.c_int64 * len(lengths))(*lengths)
-            for first in range(0, n, max_batch):
-                count = min(max_batch, n - first)
-                o0 = out0[first:first + count]
-                o1 = None if out1 is None else out1[first:first + count]
-                _ffi.check(_ffi.lib().acx_forward_windows(ctx.handle, _ffi.ptr(wav), lens, len(lengths), W, H, first, count, mode,
-                                                          _ffi.ptr(o0), _ffi.ptr(o1), _ffi.ptr(ws), ws.numel(),
-                                                          _ffi.stream_ptr(dev)))
-        return out0, out1
-
-    def _run_windows_segments(self, wav, lengths, W, H, pool, what, max_batch):
-        """_run_windows for the segment outputs: (n, S_W, .) blocks in window order, plus the (n, N) clip maxima."""
-        n = _ffi.window_count(lengths, W, H)
-        S = _seg.segment_count(W)
-        dev = wav.device
-        with torch.cuda.device(dev):
-            ctx = self.native_context(dev)
-            if what == _ffi.SEG_OUTPUT:
-                out0 = torch.empty((n, S, ctx.classes), dtype=torch.float32, device=dev)
-                out1 = torch.empty((n, S, ctx.classes), dtype=torch.float32, device=dev)
-                clip = torch.empty((n, ctx.classes), dtype=torch.float32, device=dev)
-            else:
-                out0, out1, clip = torch.empty((n, S, 768), dtype=torch.float32, device=dev), None, None
-            ws = self._workspace(dev, ctx.workspace_bytes_segments_windows(min(n, max_batch), W, what))
-            lens = (ctypes.c_int64 * len(lengths))(*lengths)
-            for first in range(0, n, max_batch):
-                count = min(max_batch, n - first)
-                sl = slice(first, first + count)
-                _ffi.check(_ffi.lib().acx_forward_segments_windows(
-                    ctx.handle, _ffi.ptr(wav), lens, len(lengths), W, H, first, count, pool, what, _ffi.ptr(out0[sl]),
-                    _ffi.ptr(None if out1 is None else out1[sl]), _ffi.ptr(None if clip is None else clip[sl]), _ffi.ptr(ws),
-                    ws.numel(), _ffi.stream_ptr(dev)))
-        return out0, out1, clip
-
-    def _forward_windows_segments(self, wav, lengths, offs, W, H, what, pool, timeline, max_batch):
-        """The per-recording dicts of forward_windows(what="segment" | "segment_embeddings")."""
-        results = []
-        cap = _ffi.MAX_VARLEN_CLIPS
-        seg_what = _ffi.SEG_OUTPUT if what == "segment" else _ffi.SEG_EMBED
-        for c0 in range(0, len(lengths), cap):
-            idx = range(c0, min(c0 + cap, len(lengths)))
-            long_ = [i for i in idx if lengths[i] > W]
-            short = [i for i in idx if lengths[i] <= W]
-            per = {}                  # recording -> (out0 blocks, out1 blocks or None, clip rows or None)
-            if long_:
-                if long_ == list(range(long_[0], long_[-1] + 1)):
-                    packed = wav[offs[long_[0]]:offs[long_[-1] + 1]]
-                else:
-                    packed = torch.cat([wav[offs[i]:offs[i + 1]] for i in long_])
-                out0, out1, clip = self._run_windows_segments(packed, [lengths[i] for i in long_], W, H, pool, seg_what, max_batch)
-                w0 = 0
-                for i in long_:
-                    n = _win.window_count(lengths[i], W, H)
-                    per[i] = (out0[w0:w0 + n], None if out1 is None else out1[w0:w0 + n], None if clip is None else clip[w0:w0 + n])
-                    w0 += n
-            if short:
-                res = self.forward_varlen([wav[offs[i]:offs[i + 1]] for i in short], what=what, pool=pool)
-                for k, i in enumerate(short):
-                    if what == "segment":
-                        per[i] = (res[k]["segmentwise_logits"][None], res[k]["segmentwise_output"][None],
-                                  res[k]["clipwise_output"][None])
-                    else:
-                        per[i] = (res[k][None], None, None)
-            tl = None
-            if what == "segment" and timeline is not None:
-                n_cls = per[idx[0]][1].shape[-1]
-                probs = torch.cat([per[i][1].reshape(-1, n_cls) for i in idx]).contiguous()
-                chunk = [lengths[i] for i in idx]
-                rows = sum((n + _seg.SEGMENT_SAMPLES - 1) // _seg.SEGMENT_SAMPLES for n in chunk)
-                tl = torch.empty((rows, n_cls), dtype=torch.float32, device=wav.device)
-                lens = (ctypes.c_int64 * len(chunk))(*chunk)
-                with torch.cuda.device(wav.device):
-                    _ffi.check(_ffi.lib().acx_segment_timeline(_ffi.ptr(probs), n_cls, lens, len(chunk), W, H,
-                                                               1 if timeline == "max" else 0, _ffi.ptr(tl),
-                                                               _ffi.stream_ptr(wav.device)))
-            t0 = 0
-            for i in idx:
-                starts = _win.window_starts([lengths[i]], W, H)
-                d = {"starts": torch.tensor(starts, dtype=torch.float64) / _rs.MODEL_RATE}
-                if what == "segment":
-                    d["segmentwise_logits"], d["segmentwise_output"], d["clipwise_output"] = per[i]
-                    if tl is not None:
-                        steps = (lengths[i] + _seg.SEGMENT_SAMPLES - 1) // _seg.SEGMENT_SAMPLES
-                        d["timeline"] = tl[t0:t0 + steps]
-                        t0 += steps
-                else:
-                    d["segment_embeddings"] = per[i][0]
-                results.append(d)
-        return results
 
     def forward_windows(self, recordings, window=10.0, hop=None, what="logits", sample_rate=None, max_batch=64,
                         timeline="mean", pool=3):
@@ -759,59 +638,63 @@ class ConvNeXt(nn.Module):
         offs = [0]
         for n in lengths:
             offs.append(offs[-1] + n)
-        if what in ("segment", "segment_embeddings"):
-            results = self._forward_windows_segments(wav, lengths, offs, W, H, what, pool, timeline, max_batch)
-            return results[0] if single else results
-        mode = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}[what]
-        key ={"logits": "clipwise_logits", "scene": "scene", "frame": "frame"}[what]
+        # by kind: the dict keys of (out0, out1, clip), and what the timeline steps over (None: the kind has no timeline)
+        keys, tl_call, step = {
+            "logits": (("clipwise_logits", "clipwise_output", None), "acx_window_timeline_classes", H),
+            "scene": (("scene", None, None), None, None),
+            "frame": (("frame", None, None), None, None),
+            "segment": (("segmentwise_logits", "segmentwise_output", "clipwise_output"), "acx_segment_timeline",
+                        _seg.SEGMENT_SAMPLES),
+            "segment_embeddings": (("segment_embeddings", None, None), None, None)}[what]
         results = []
         cap = _ffi.MAX_VARLEN_CLIPS
         for c0 in range(0, len(lengths), cap):
             idx = range(c0, min(c0 + cap, len(lengths)))
             long_ = [i for i in idx if lengths[i] > W]
             short = [i for i in idx if lengths[i] <= W]
-            per = {}                  # recording -> (out0 rows, out1 rows or None)
+            per = {}                  # recording -> its windows' (out0, out1 or None, clip or None)
             if long_:
                 if long_ == list(range(long_[0], long_[-1] + 1)):        # back to back in wav already: no copy
                     packed = wav[offs[long_[0]]:offs[long_[-1] + 1]]
                 else:
                     packed = torch.cat([wav[offs[i]:offs[i + 1]] for i in long_])
-                out0, out1 = self._run_windows(packed, [lengths[i] for i in long_], W, H, mode, max_batch)
+                outs = self._run_windows(packed, [lengths[i] for i in long_], W, H, what, max_batch, pool)
                 w0 = 0
                 for i in long_:
                     n = _win.window_count(lengths[i], W, H)
-                    per[i] = (out0[w0:w0 + n], None if out1 is None else out1[w0:w0 + n])
+                    per[i] = tuple(None if t is None else t[w0:w0 + n] for t in outs)
                     w0 += n
-            if short:
-                res = self.forward_varlen([wav[offs[i]:offs[i + 1]] for i in short], what=what)
+            if short:                 # one window each, the clip itself: forward_varlen's per-clip results as blocks of one window
+                res = self.forward_varlen([wav[offs[i]:offs[i + 1]] for i in short], what=what, pool=pool)
                 for k, i in enumerate(short):
                     if what == "logits":
-                        per[i] = (res["clipwise_logits"][k:k + 1], res["clipwise_output"][k:k + 1])
+                        per[i] = (res["clipwise_logits"][k:k + 1], res["clipwise_output"][k:k + 1], None)
                     elif what == "scene":
-                        per[i] = (res[k:k + 1], None)
+                        per[i] = (res[k:k + 1], None, None)
+                    elif what == "segment":
+                        per[i] = tuple(res[k][key][None] for key in keys)
                     else:
-                        per[i] = (res[k][None], None)
+                        per[i] = (res[k][None], None, None)
             tl = None
-            if what == "logits" and timeline is not None:
-                probs = torch.cat([per[i][1] for i in idx]).contiguous()
+            if tl_call is not None and timeline is not None:
+                n_cls = per[idx[0]][1].shape[-1]
+                probs = torch.cat([per[i][1].reshape(-1, n_cls) for i in idx]).contiguous()
                 chunk = [lengths[i] for i in idx]
-                n_cls = probs.shape[1]
-                tl = torch.empty((len(_win.timeline_steps(chunk, W, H)), n_cls), dtype=torch.float32, device=wav.device)
+                tl = torch.empty((sum((n + step - 1) // step for n in chunk), n_cls), dtype=torch.float32, device=wav.device)
                 lens = (ctypes.c_int64 * len(chunk))(*chunk)
                 with torch.cuda.device(wav.device):
-                    _ffi.check(_ffi.lib().acx_window_timeline_classes(_ffi.ptr(probs), n_cls, lens, len(chunk), W, H,
-                                                                      1 if timeline == "max" else 0, _ffi.ptr(tl),
-                                                                      _ffi.stream_ptr(wav.device)))
+                    _ffi.check(getattr(_ffi.lib(), tl_call)(_ffi.ptr(probs), n_cls, lens, len(chunk), W, H,
+                                                            1 if timeline == "max" else 0, _ffi.ptr(tl),
+                                                            _ffi.stream_ptr(wav.device)))
             t0 = 0
             for i in idx:
                 starts = _win.window_starts([lengths[i]], W, H)
-                d = {"starts": torch.tensor(starts, dtype=torch.float64) / _rs.MODEL_RATE, key: per[i][0]}
-                if what == "logits":
-                    d["clipwise_output"] = per[i][1]
-                    if tl is not None:
-                        steps = (lengths[i] + H - 1) // H
-                        d["timeline"] = tl[t0:t0 + steps]
-                        t0 += steps
+                d = {"starts": torch.tensor(starts, dtype=torch.float64) / _rs.MODEL_RATE}
+                d.update((key, t) for key, t in zip(keys, per[i]) if key is not None)
+                if tl is not None:
+                    steps = (lengths[i] + step - 1) // step
+                    d["timeline"] = tl[t0:t0 + steps]
+                    t0 += steps
                 results.append(d)
         return results[0] if single else results
 
@@ -861,16 +744,16 @@ class ConvNeXt(nn.Module):
     # the host, demo_convnext.py:53-59); the result equals the forward of pytorch.resample.resample(x, sample_rate) bit for bit.
     def forward(self, x, mixup_lambda=None, sample_rate=None):
         """(B, L) waveform -> {"clipwise_output": probs, "clipwise_logits": logits}, each (B, N) (convnext.py:287-331)."""
-        logits, probs = self._run(self._resampled(x, sample_rate), _ffi.MODE_LOGITS)
+        logits, probs, _ = self._run(self._resampled(x, sample_rate), "logits")
         return {"clipwise_output": probs, "clipwise_logits": logits}
 
     def forward_scene_embeddings(self, x, mixup_lambda=None, sample_rate=None):
         """(B, L) -> (B, 768) (convnext.py:333-366)."""
-        return self._run(self._resampled(x, sample_rate), _ffi.MODE_SCENE)[0]
+        return self._run(self._resampled(x, sample_rate), "scene")[0]
 
     def forward_frame_embeddings(self, x, mixup_lambda=None, sample_rate=None):
         """(B, L) -> NCHW (B, 768, T', 7) (convnext.py:369-402)."""
-        return self._run(self._resampled(x, sample_rate), _ffi.MODE_FRAME)[0]
+        return self._run(self._resampled(x, sample_rate), "frame")[0]
 
     @classmethod
     def from_pretrained(cls, pretrained_checkpoint_path, map_location=None, use_auth_token=None):

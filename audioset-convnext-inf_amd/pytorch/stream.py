@@ -16,8 +16,6 @@ from .. import _ffi
 from . import resample as _rs
 from . import windows as _win
 
-_MODES = {"logits": _ffi.MODE_LOGITS, "scene": _ffi.MODE_SCENE, "frame": _ffi.MODE_FRAME}
-
 
 def schedule(window, hop, sample_rate, pushed, closed):
     """(final 32 kHz samples, windows, timeline rows) emitted so far by one slot after `pushed` input samples at sample_rate,
@@ -33,7 +31,7 @@ class Stream:
 
     def __init__(self, model, slots=256, window=10.0, hop=1.0, what="logits", sample_rate=None, timeline="mean", max_push=2.0,
                  max_batch=64):
-        if what not in _MODES:
+        if what not in _ffi.MODES:
             raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
         if timeline not in ("mean", "max", None):
             raise ValueError("timeline must be 'mean', 'max' or None (got %r)" % (timeline,))
@@ -168,7 +166,7 @@ class Stream:
 
     def _drain(self, out):
         """Forward every pending window (max_batch at a time), then fetch the timeline rows that became final."""
-        lib, dev, mode, mb = _ffi.lib(), self.device, _MODES[self.what], self.max_batch
+        lib, dev, mode, mb = _ffi.lib(), self.device, _ffi.MODES[self.what], self.max_batch
         slot_of, start_of = (ctypes.c_int * mb)(), (ctypes.c_int64 * mb)()
         length, count = ctypes.c_int64(), ctypes.c_int()
         with torch.cuda.device(dev):
@@ -179,13 +177,7 @@ class Stream:
                     break
                 ctx = self.model.native_context(dev)
                 ws = self.model._workspace(dev, ctx.workspace_bytes_windows(n, L, mode))
-                if mode == _ffi.MODE_LOGITS:
-                    o0 = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
-                    o1 = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
-                elif mode == _ffi.MODE_SCENE:
-                    o0, o1 = torch.empty((n, 768), dtype=torch.float32, device=dev), None
-                else:
-                    o0, o1 = torch.empty((n, 768) + _ffi.stage_hw(L, 3), dtype=torch.float32, device=dev), None
+                o0, o1, _ = self.model._outputs(self.what, (n,), self.classes, L, dev)
                 _ffi.check(lib.acx_stream_forward(self._h, n, mode, _ffi.ptr(o0), _ffi.ptr(o1), _ffi.ptr(ws), ws.numel(),
                                                   _ffi.stream_ptr(dev)))
                 out.add(list(slot_of[:n]), list(start_of[:n]), o0, o1)

@@ -418,10 +418,10 @@ def test_c_abi_errors(model):
     assert failed(lib.acx_segment_timeline(_ffi.ptr(o1), 527, lens, 2, 16000, 20000, 0, _ffi.ptr(fr), st), ARG)
     # the workspace queries: the sizes of the clip-level forwards (the embeddings live in the frontend's feature buffer)
     nb = ctypes.c_size_t()
-    for what in (_ffi.SEG_OUTPUT, _ffi.SEG_EMBED):
-        assert ctx.workspace_bytes_segments(B, L, what) == ctx.workspace_bytes(B, L, _ffi.MODE_LOGITS)
-        assert ctx.workspace_bytes_segments_varlen([L, 7360], what) == ctx.workspace_bytes_varlen([L, 7360], _ffi.MODE_LOGITS)
-        assert ctx.workspace_bytes_segments_windows(5, L, what) == ctx.workspace_bytes_windows(5, L, _ffi.MODE_LOGITS)
+    for what in ("segment", "segment_embeddings"):       # the acx_workspace_bytes_segments* calls
+        assert ctx.workspace_bytes(B, L, what) == ctx.workspace_bytes(B, L, _ffi.MODE_LOGITS)
+        assert ctx.workspace_bytes_varlen([L, 7360], what) == ctx.workspace_bytes_varlen([L, 7360], _ffi.MODE_LOGITS)
+        assert ctx.workspace_bytes_windows(5, L, what) == ctx.workspace_bytes_windows(5, L, _ffi.MODE_LOGITS)
     assert failed(lib.acx_workspace_bytes_segments(ctx.handle, B, L, 2, ctypes.byref(nb)), ARG)
     assert failed(lib.acx_workspace_bytes_segments_varlen(ctx.handle, lens, 2, -1, ctypes.byref(nb)), ARG)
     assert failed(lib.acx_workspace_bytes_segments_windows(ctx.handle, 5, L, 7, ctypes.byref(nb)), ARG)

@@ -47,7 +47,7 @@ def report(sd, tol=1e-6, out=sys.stdout):
         rel = d / float(np.abs(want[k]).max())
         worst = max(worst, d)
         print("%-48s max |delta| %.3e  (%.3e of the largest entry)  %s" % (k, d, rel, "ok" if d <= tol else "DEVIATES"), file=out)
-    # what libacx's acx_finalize will decide (api.hip: stft_deviation_from_dft, the window is read from bin 0)
+    # what libacx's acx_finalize will decide (weights.hip: stft_deviation_from_dft, the window is read from bin 0)
     re, im = np.asarray(sd[KEYS[0]], np.float64)[:, 0, :], np.asarray(sd[KEYS[1]], np.float64)[:, 0, :]
     win = re[0].astype(np.float32).astype(np.float64)
     n, k = np.arange(ft.N_FFT)[None, :], np.arange(ft.N_BINS)[:, None]
