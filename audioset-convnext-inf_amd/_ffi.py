@@ -130,6 +130,13 @@ SIGNATURES = {
     "acx_head_fit_grad": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _c_sz, _vp]),
     "acx_adam_update": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _padam, _c_i64, _c_dbl, _vp]),
+    "acx_knn_row_norms": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp]),
+    "acx_knn_workspace_bytes": (_c_int, [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_knn_slices": (_c_int, [_c_i64, _c_i64, _c_int, _pint]),
+    "acx_knn_search": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp,
+                                _c_sz, _vp]),
+    "acx_knn_vote": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, ctypes.c_float, _vp, _c_i64,
+                              _vp, _vp]),
     "acx_frontend_info": (_c_int, [_vp, _pint, ctypes.POINTER(ctypes.c_float), _pint]),
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
@@ -389,6 +396,46 @@ def head_fit_workspace_bytes(rows_max, classes):
     out = _c_sz()
     check(lib().acx_head_fit_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
     return out.value
+
+
+KNN_DOT, KNN_COSINE = 0, 1                    # enum acx_knn_metric
+KNN_UNIFORM, KNN_SIMILARITY = 0, 1            # enum acx_knn_weighting
+KNN_MAX_K, KNN_MAX_DIM = 128, 4096            # ACX_KNN_MAX_K, ACX_KNN_MAX_DIM
+KNN_NONFINITE, KNN_BAD_INDEX = 1, 2           # bits of the status words of acx_knn_search / acx_knn_row_norms and acx_knn_vote
+KNN_METRICS = {"dot": KNN_DOT, "cosine": KNN_COSINE}
+KNN_WEIGHTS = {"uniform": KNN_UNIFORM, "similarity": KNN_SIMILARITY}
+
+
+def knn_workspace_bytes(nq, n, k):
+    """Workspace of acx_knn_search for nq queries, n database rows and k neighbours (host only)."""
+    out = _c_sz()
+    check(lib().acx_knn_workspace_bytes(int(nq), int(n), int(k), ctypes.byref(out)))
+    return out.value
+
+
+def knn_slices(nq, n, k):
+    """Slices of the database rows a search of this shape runs as (acx_knn_slices; host only)."""
+    out = _c_int()
+    check(lib().acx_knn_slices(int(nq), int(n), int(k), ctypes.byref(out)))
+    return out.value
+
+
+def knn_row_norms(x, ld, n, dim, inv_norm, status, stream):
+    """acx_knn_row_norms on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_knn_row_norms(x, int(ld), int(n), int(dim), inv_norm, status, stream))
+
+
+def knn_search(q, ld_q, q_inv_norm, nq, d, ld_d, d_inv_norm, n, dim, metric, k, exclude, indices, scores, status, ws, stream):
+    """acx_knn_search on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_knn_search(q, int(ld_q), q_inv_norm, int(nq), d, int(ld_d), d_inv_norm, int(n), int(dim), int(metric), int(k),
+                               exclude, indices, scores, status, ws[0], int(ws[1]), stream))
+
+
+def knn_vote(indices, scores, nq, k, target, target_dtype, ld_target, n, classes, weighting, temperature, out, ld_out, status,
+             stream):
+    """acx_knn_vote on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_knn_vote(indices, scores, int(nq), int(k), target, int(target_dtype), int(ld_target), int(n), int(classes),
+                             int(weighting), float(temperature), out, int(ld_out), status, stream))
 
 
 MAX_EVENT_MEDIAN = 101                        # ACX_MAX_EVENT_MEDIAN

@@ -28,6 +28,9 @@ void tuning_reload() {
     t.dw_stream.store(digit("ACX_DW_STREAM", "01", -1), std::memory_order_relaxed);
     t.dwm_waves.store(digit("ACX_DWM_WAVES", "23456789", 0), std::memory_order_relaxed);
     t.head_path.store(digit("ACX_HEAD_PATH", "12", 0), std::memory_order_relaxed);
+    const char* sr = std::getenv("ACX_KNN_SLICE_ROWS");
+    const long srv = sr && sr[0] ? std::strtol(sr, nullptr, 10) : 0;
+    t.knn_slice_rows.store(srv >= 16 && srv <= (1L << 30) ? (int)srv : 0, std::memory_order_relaxed);
 }
 
 void set_error(const char* fmt, ...) {

@@ -1,0 +1,553 @@
+// Nearest-neighbour search over embeddings (acx_knn_row_norms / acx_knn_search / acx_knn_vote, include/acx.h): the k best
+// database rows per query by dot product or cosine, and kNN tagging from the neighbours' targets.
+//
+//   knn_norm_kernel    r[i] = 1 / sqrt(sum x^2) per row (one wave per row, fixed order), 0 for a zero row.
+//   knn_search_kernel  grid (query tiles, slices).  A workgroup owns TQ = 32 or 64 queries and one slice of the database, which
+//                      it streams once in steps of 256 rows: each of the four waves forms the TQ x 64 score tile of its 64 rows
+//                      on the f32 matrix cores (v_mfma_f32_32x32x2_f32, operands straight from global memory: a lane reads
+//                      32 contiguous bytes of its row per 16 columns of the contraction) and filters it against the queries'
+//                      thresholds into per-query candidate buffers in LDS.  The scores never go to memory.
+//   knn_merge_kernel   one wave per query: the k best out of the slices' lists, decoded to indices / scores.
+//   knn_vote_kernel    out[q][c] = sum_j w_j y[idx[q][j]][c] / sum_j w_j, a gather.
+//
+// Order.  A candidate is ONE 64-bit key: the order-preserving image of its fp32 score (-0.0 taken as +0.0) in the high word,
+// the complemented database index in the low word.  Larger key = better neighbour: score descending, then index ascending, and
+// no two keys are equal.  Key 0 is "no candidate" (no finite score and index < 2^30 maps to it).  Everything below selects on
+// keys, so the result is the first k of that one total order whatever the arrival order of the LDS atomics was.
+//
+// Keeping the top k.  Query q of the tile has CAP = 64 R slots (R = 1, 2, 4 for k <= 32, 64, 128: CAP >= 2 k), a count and a
+// threshold key (the k-th best so far, 0 until k candidates were seen).  A score whose key beats the threshold takes a slot by
+// an LDS atomic on the count.  When a query runs out of slots the workgroup stops (the block-wide OR of __syncthreads_or), one
+// wave per full query sorts its CAP keys in registers (bitonic network over lane shuffles, no barrier inside), keeps the first
+// k and raises the threshold, and the lanes whose candidates found no slot try again against the new threshold.  On random data
+// the threshold soon rejects almost everything and trims are rare; on adversarial data (every score beats the last) there is
+// one trim per CAP - k rows, and the result is the same.
+//
+// Bits.  The contraction of a (query, row) pair runs over the whole of `dim` inside one wave, in one fixed order (16 columns
+// per group of eight MFMAs, the lane halves taking columns 0-7 and 8-15 of the group), whatever the pair's position in its
+// tile, the tile's in the grid, nq, n, k or the number of slices: the same pair has the same score bits everywhere.  Cosine
+// scores are (acc * rq[i]) * rd[j], two roundings.  A non-finite accumulator (a NaN or inf in Q or D always gives one, as every
+// query meets every row) sets ACX_KNN_NONFINITE, and the merge then writes index -1 / score NaN everywhere.
+#include <cmath>
+
+#include "acx_internal.h"
+
+namespace acx {
+
+typedef float knn_f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned long long knn_key;
+
+constexpr int kKnnThreads = 256;
+constexpr int kKnnStepRows = 256;            // database rows per step of a workgroup: four waves x 64
+constexpr int kKnnTargetWgs = 512;           // the slice count aims at this many workgroups: two per CU of an MI355X
+constexpr int kKnnMaxSlices = 1024;
+constexpr long long kKnnMaxRows = 1LL << 30;
+
+__device__ __forceinline__ knn_key knn_make_key(float s, long long idx) {
+    unsigned u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0u;                                   // -0.0 orders as +0.0
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((knn_key)u << 32) | (knn_key)(~(unsigned)idx);
+}
+__device__ __forceinline__ float knn_key_score(knn_key key) {
+    unsigned u = (unsigned)(key >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ int knn_key_index(knn_key key) { return (int)~(unsigned)key; }
+
+// Element e = lane + 64 r of a wave's 64 R keys, sorted descending (bitonic network: strides under 64 by lane shuffles, the
+// others between the lane's own registers).
+template <int R>
+__device__ __forceinline__ void knn_sort_desc(knn_key (&v)[R], int lane) {
+#pragma unroll
+    for (int size = 2; size <= 64 * R; size <<= 1) {
+#pragma unroll
+        for (int j = size >> 1; j >= 1; j >>= 1) {
+            if (j >= 64) {
+                const int jr = j >> 6;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if ((r & jr) == 0) {
+                        const bool desc = ((r << 6) & size) == 0;
+                        const knn_key a = v[r], b = v[r | jr];
+                        const bool sw = desc ? (a < b) : (a > b);
+                        v[r] = sw ? b : a;
+                        v[r | jr] = sw ? a : b;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const bool desc = ((lane + (r << 6)) & size) == 0;
+                    const bool lower = (lane & j) == 0;
+                    const knn_key o = __shfl_xor(v[r], j);
+                    const knn_key hi = v[r] > o ? v[r] : o, lo = v[r] > o ? o : v[r];
+                    v[r] = (lower == desc) ? hi : lo;
+                }
+            }
+        }
+    }
+}
+
+// v[] <- the cnt keys of buf (the other elements 0), sorted descending.  One wave.
+template <int R>
+__device__ __forceinline__ void knn_load_sorted(const knn_key* buf, int cnt, knn_key (&v)[R], int lane) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int e = lane + 64 * r;
+        v[r] = e < cnt ? buf[e] : 0ull;
+    }
+    knn_sort_desc<R>(v, lane);
+}
+
+__global__ __launch_bounds__(256) void knn_norm_kernel(const float* __restrict__ x, long long ld, long long n, int dim,
+                                                       float* __restrict__ inv_norm, int* status) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float* xr = x + row * ld;
+    float s = 0.f;
+    bool bad = false;
+    for (int k = lane * 4; k < dim; k += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(xr + k);
+        s = __builtin_fmaf(v.x, v.x, s);
+        s = __builtin_fmaf(v.y, v.y, s);
+        s = __builtin_fmaf(v.z, v.z, s);
+        s = __builtin_fmaf(v.w, v.w, s);
+        bad |= !(fabsf(v.x) <= 3.4028234664e38f) || !(fabsf(v.y) <= 3.4028234664e38f) || !(fabsf(v.z) <= 3.4028234664e38f) ||
+               !(fabsf(v.w) <= 3.4028234664e38f);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if (__ballot(bad) && lane == 0) atomicOr(status, ACX_KNN_NONFINITE);
+    if (lane == 0) inv_norm[row] = s > 0.f ? 1.0f / sqrtf(s) : 0.f;
+}
+
+struct KnnSearchP {
+    const float* q; long long ld_q; const float* rq; long long nq;
+    const float* d; long long ld_d; const float* rd; long long n;
+    int dim, k;
+    const int* exclude;
+    knn_key* ws;             // [nq][slices][k]
+    int* status;
+    int slices; long long slice_rows;
+};
+
+// row of accumulator register i in the 32 x 32 MFMA tile, lane half h
+__device__ __forceinline__ int knn_acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+template <int QT, int R>
+__global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p) {
+    constexpr int TQ = 32 * QT, CAP = 64 * R;
+    extern __shared__ knn_key s_buf[];           // [TQ][CAP]
+    __shared__ knn_key s_thr[TQ];
+    __shared__ int s_cnt[TQ];
+    __shared__ int s_excl[TQ];
+    __shared__ float s_rq[TQ];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r32 = lane & 31, h = lane >> 5;
+    const long long q0 = (long long)blockIdx.x * TQ;
+    const long long j_lo = (long long)blockIdx.y * p.slice_rows;
+    const long long j_hi = min(p.n, j_lo + p.slice_rows);
+    const bool cosine = p.rq != nullptr;
+
+    if (tid < TQ) {
+        const long long qi = q0 + tid;
+        s_thr[tid] = 0ull;
+        s_cnt[tid] = 0;
+        s_excl[tid] = (p.exclude && qi < p.nq) ? p.exclude[qi] : -1;
+        s_rq[tid] = cosine ? p.rq[min(qi, p.nq - 1)] : 1.f;
+    }
+    __syncthreads();
+
+    // rows past nq / the slice repeat the last valid one: loads stay inside the buffers, results are dropped
+    const float* qa[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) qa[t] = p.q + min(q0 + 32 * t + r32, p.nq - 1) * p.ld_q + 8 * h;
+    const int full = p.dim >> 4, rem = p.dim & 15;
+    const bool tail0 = rem >= 4 + 8 * h, tail1 = rem >= 8 + 8 * h;
+    bool bad = false;
+
+    for (long long j0 = j_lo; j0 < j_hi; j0 += kKnnStepRows) {
+        const long long jw = j0 + wave * 64;
+        const bool active = jw < j_hi;               // wave-uniform
+        knn_f32x16 acc[QT][2];
+        float rdv[2] = {1.f, 1.f};
+        if (active) {
+            const float* db[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const long long j = min(jw + 32 * u + r32, j_hi - 1);
+                db[u] = p.d + j * p.ld_d + 8 * h;
+                if (cosine) rdv[u] = p.rd[j];
+            }
+#pragma unroll
+            for (int t = 0; t < QT; ++t)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) acc[t][u][i] = 0.f;
+            const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#define KNN_MFMA(A, B, C)                                                                                      \
+    _Pragma("unroll") for (int t = 0; t < QT; ++t) _Pragma("unroll") for (int u = 0; u < 2; ++u)               \
+        acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(A[t].C, B[u].C, acc[t][u], 0, 0, 0);
+#define KNN_GROUP                                                                               \
+    KNN_MFMA(a0, b0, x) KNN_MFMA(a0, b0, y) KNN_MFMA(a0, b0, z) KNN_MFMA(a0, b0, w)             \
+    KNN_MFMA(a1, b1, x) KNN_MFMA(a1, b1, y) KNN_MFMA(a1, b1, z) KNN_MFMA(a1, b1, w)
+            float4 a0[QT], a1[QT], b0[2], b1[2];
+            for (int kb = 0; kb < full; ++kb) {
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    a0[t] = *reinterpret_cast<const float4*>(qa[t] + kb * 16);
+                    a1[t] = *reinterpret_cast<const float4*>(qa[t] + kb * 16 + 4);
+                }
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    b0[u] = *reinterpret_cast<const float4*>(db[u] + kb * 16);
+                    b1[u] = *reinterpret_cast<const float4*>(db[u] + kb * 16 + 4);
+                }
+                KNN_GROUP
+            }
+            if (rem) {                               // the last 4, 8 or 12 columns: the lane halves past dim contribute zeros
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    a0[t] = tail0 ? *reinterpret_cast<const float4*>(qa[t] + full * 16) : zero4;
+                    a1[t] = tail1 ? *reinterpret_cast<const float4*>(qa[t] + full * 16 + 4) : zero4;
+                }
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    b0[u] = tail0 ? *reinterpret_cast<const float4*>(db[u] + full * 16) : zero4;
+                    b1[u] = tail1 ? *reinterpret_cast<const float4*>(db[u] + full * 16 + 4) : zero4;
+                }
+                KNN_GROUP
+            }
+#undef KNN_GROUP
+#undef KNN_MFMA
+        }
+
+        // filter the tile into the candidate buffers; lanes left without a slot try again after the trim
+        unsigned long long pend = active ? (QT == 2 ? ~0ull : 0xffffffffull) : 0ull;
+        for (;;) {
+            int over = 0;
+            if (pend) {
+#pragma unroll
+                for (int t = 0; t < QT; ++t)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            const int bit = (t * 2 + u) * 16 + i;
+                            if ((pend >> bit) & 1ull) {
+                                const int ql = 32 * t + knn_acc_row(i, h);
+                                const long long j = jw + 32 * u + r32;
+                                bool keep = false;
+                                if (q0 + ql < p.nq && j < j_hi) {
+                                    float s = acc[t][u][i];
+                                    if (!(fabsf(s) <= 3.4028234664e38f)) bad = true;
+                                    if (j != (long long)s_excl[ql]) {
+                                        if (cosine) {
+#pragma clang fp contract(off)
+                                            s = (s * s_rq[ql]) * rdv[u];
+                                        }
+                                        const knn_key key = knn_make_key(s, j);
+                                        if (key > s_thr[ql]) {
+                                            const int slot = atomicAdd(&s_cnt[ql], 1);
+                                            if (slot < CAP) s_buf[ql * CAP + slot] = key;
+                                            else { keep = true; over = 1; }
+                                        }
+                                    }
+                                }
+                                if (!keep) pend &= ~(1ull << bit);
+                            }
+                        }
+            }
+            if (!__syncthreads_or(over)) break;
+            for (int ql = wave; ql < TQ; ql += 4) {
+                const int cnt = s_cnt[ql];           // wave-uniform
+                if (cnt >= CAP) {
+                    knn_key v[R];
+                    knn_load_sorted<R>(s_buf + ql * CAP, CAP, v, lane);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const int e = lane + 64 * r;
+                        s_buf[ql * CAP + e] = v[r];
+                        if (e == p.k - 1) s_thr[ql] = v[r];
+                    }
+                    if (lane == 0) s_cnt[ql] = p.k;
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // the slice's k best of each query, sorted, to the workspace (0 keys where the slice holds fewer than k candidates)
+    for (int ql = wave; ql < TQ; ql += 4) {
+        if (q0 + ql >= p.nq) break;
+        knn_key v[R];
+        knn_load_sorted<R>(s_buf + ql * CAP, min(s_cnt[ql], CAP), v, lane);
+        knn_key* out = p.ws + ((q0 + ql) * p.slices + blockIdx.y) * p.k;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int e = lane + 64 * r;
+            if (e < p.k) out[e] = v[r];
+        }
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(p.status, ACX_KNN_NONFINITE);
+}
+
+// One wave per query: the k best keys of its slices' lists (slices * k keys, contiguous), decoded.
+template <int R>
+__global__ __launch_bounds__(kKnnThreads) void knn_merge_kernel(const knn_key* __restrict__ ws, long long nq, int slices, int k,
+                                                                int* __restrict__ indices, float* __restrict__ scores,
+                                                                const int* status) {
+    constexpr int CAP = 64 * R;
+    const int lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;
+    const knn_key* flat = ws + q * slices * k;
+    const long long total = (long long)slices * k;
+    knn_key v[R];
+    knn_load_sorted<R>(flat, (int)min(total, (long long)CAP), v, lane);
+    for (long long pos = CAP; pos < total; pos += CAP - k) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int e = lane + 64 * r;
+            if (e >= k) v[r] = pos + (e - k) < total ? flat[pos + (e - k)] : 0ull;
+        }
+        knn_sort_desc<R>(v, lane);
+    }
+    const bool nonfinite = (*status & ACX_KNN_NONFINITE) != 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int e = lane + 64 * r;
+        if (e < k) {
+            const bool none = nonfinite || v[r] == 0ull;
+            indices[q * k + e] = none ? -1 : knn_key_index(v[r]);
+            scores[q * k + e] = none ? __uint_as_float(0x7fc00000u) : knn_key_score(v[r]);
+        }
+    }
+}
+
+struct KnnVoteP {
+    const int* indices; const float* scores; int k;
+    const void* y; int y_u8; long long ld_y; long long n; int classes;
+    int similarity; float temperature;
+    float* out; long long ld_out; int* status;
+};
+
+__global__ __launch_bounds__(256) void knn_vote_kernel(KnnVoteP p) {
+    __shared__ int s_idx[ACX_KNN_MAX_K];
+    __shared__ float s_w[ACX_KNN_MAX_K];
+    const long long q = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (tid < p.k) {
+        const int idx = p.indices[q * p.k + tid];
+        const bool bad = idx < 0 || idx >= p.n;
+        if (bad) atomicOr(p.status, ACX_KNN_BAD_INDEX);
+        s_idx[tid] = bad ? -1 : idx;
+        s_w[tid] = p.similarity ? expf((p.scores[q * p.k + tid] - p.scores[q * p.k]) / p.temperature) : 1.f;
+    }
+    __syncthreads();
+    const int c = blockIdx.y * 256 + tid;
+    if (c >= p.classes) return;
+    float res;
+    if (!p.similarity && p.y_u8) {
+        int count = 0;
+        for (int j = 0; j < p.k; ++j)
+            if (s_idx[j] >= 0) count += static_cast<const unsigned char*>(p.y)[s_idx[j] * p.ld_y + c] ? 1 : 0;
+        res = (float)count / (float)p.k;
+    } else {
+        float num = 0.f, den = 0.f;
+        for (int j = 0; j < p.k; ++j) {
+            const float w = s_w[j];
+            den += w;
+            if (s_idx[j] >= 0) {
+                const long long o = s_idx[j] * p.ld_y + c;
+                const float y = p.y_u8 ? (static_cast<const unsigned char*>(p.y)[o] ? 1.f : 0.f) : static_cast<const float*>(p.y)[o];
+                num = __builtin_fmaf(w, y, num);
+            }
+        }
+        res = num / den;
+    }
+    p.out[q * p.ld_out + c] = res;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+struct KnnPlan { int qt, r, slices; long long slice_rows; };
+
+static long long knn_cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+// The launch shape of a search: a function of (nq, n, k) and ACX_KNN_SLICE_ROWS alone.
+static KnnPlan knn_plan(long long nq, long long n, int k) {
+    KnnPlan pl;
+    pl.qt = nq <= 32 ? 1 : 2;
+    pl.r = k <= 32 ? 1 : k <= 64 ? 2 : 4;
+    const long long qtiles = knn_cdiv(nq, 32 * pl.qt);
+    const int forced = tuning().knn_slice_rows.load(std::memory_order_relaxed);
+    long long rows, slices;
+    if (forced > 0) {
+        rows = forced;
+        if (knn_cdiv(n, rows) > kKnnMaxSlices) rows = knn_cdiv(n, kKnnMaxSlices);
+    } else {
+        slices = std::min(std::max(knn_cdiv(kKnnTargetWgs, qtiles), 1LL), knn_cdiv(n, kKnnStepRows));
+        rows = knn_cdiv(knn_cdiv(n, slices), kKnnStepRows) * kKnnStepRows;
+    }
+    slices = knn_cdiv(n, rows);
+    pl.slices = (int)slices;
+    pl.slice_rows = rows;
+    return pl;
+}
+
+// Workspace: nq * slices lists of k keys.  The bound below covers every plan and is non-decreasing in nq, n and k:
+// nq * slices <= nq * ceil(n / 256), and <= 64 * 512 + nq because slices <= ceil(512 / qtiles) and nq <= 64 qtiles.
+static size_t knn_ws_bytes(long long nq, long long n, int k) {
+    const int forced = tuning().knn_slice_rows.load(std::memory_order_relaxed);
+    long long cells;
+    if (forced > 0) cells = nq * std::min<long long>(kKnnMaxSlices, knn_cdiv(n, forced));
+    else cells = std::min(nq * knn_cdiv(n, kKnnStepRows), 64LL * kKnnTargetWgs + nq);
+    return align_up((size_t)cells * (size_t)k * sizeof(knn_key));
+}
+
+static int knn_check_shape(const char* who, int64_t nq, int64_t n, int k) {
+    if (nq < 1) ACX_FAIL(ACX_ERR_ARG, "%s: nq = %lld (expected >= 1)", who, (long long)nq);
+    if (n < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n = %lld (expected >= 1)", who, (long long)n);
+    if (k < 1 || k > ACX_KNN_MAX_K) ACX_FAIL(ACX_ERR_ARG, "%s: k = %d (expected 1 .. %d)", who, k, ACX_KNN_MAX_K);
+    if (n > kKnnMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
+    if (nq > kKnnMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: nq = %lld (at most 2^30 queries per call)", who, (long long)nq);
+    return ACX_OK;
+}
+
+static int knn_check_rows(const char* who, const char* name, const float* x, int64_t ld, int dim) {
+    if (!x) ACX_FAIL(ACX_ERR_ARG, "%s: %s is null", who, name);
+    if (dim < 4 || dim > ACX_KNN_MAX_DIM || (dim & 3))
+        ACX_FAIL(ACX_ERR_ARG, "%s: dim = %d (expected a multiple of 4 in 4 .. %d)", who, dim, ACX_KNN_MAX_DIM);
+    if (ld < dim || (ld & 3))
+        ACX_FAIL(ACX_ERR_ARG, "%s: row stride of %s = %lld (expected a multiple of 4, at least dim = %d)", who, name, (long long)ld, dim);
+    if (reinterpret_cast<uintptr_t>(x) & 15) ACX_FAIL(ACX_ERR_ARG, "%s: %s is not 16-byte aligned", who, name);
+    return ACX_OK;
+}
+
+static DeviceOnce g_knn_lds[2][3];
+
+template <int QT, int R>
+static int knn_launch_search(const KnnSearchP& p, long long qtiles, DeviceOnce& once, hipStream_t s) {
+    const size_t lds = (size_t)32 * QT * 64 * R * sizeof(knn_key);
+    ACX_TRY(set_max_dynamic_lds(once, &knn_search_kernel<QT, R>, lds));
+    launch_kernel(&knn_search_kernel<QT, R>, dim3((unsigned)qtiles, (unsigned)p.slices), dim3(kKnnThreads), lds, s, p);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+}  // namespace acx
+
+using namespace acx;
+
+extern "C" {
+
+int acx_knn_row_norms(const float* x, int64_t ld, int64_t n, int dim, float* inv_norm, int32_t* status, void* stream) {
+    static const char* who = "acx_knn_row_norms";
+    if (n < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n = %lld (expected >= 1)", who, (long long)n);
+    if (n > kKnnMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
+    ACX_TRY(knn_check_rows(who, "x", x, ld, dim));
+    if (!inv_norm) ACX_FAIL(ACX_ERR_ARG, "%s: inv_norm is null", who);
+    if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    launch_kernel(&knn_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (long long)ld, (long long)n,
+                  dim, inv_norm, (int*)status);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int acx_knn_workspace_bytes(int64_t nq, int64_t n, int k, size_t* out_bytes) {
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "acx_knn_workspace_bytes: out_bytes is null");
+    ACX_TRY(knn_check_shape("acx_knn_workspace_bytes", nq, n, k));
+    *out_bytes = knn_ws_bytes(nq, n, k);
+    return ACX_OK;
+}
+
+int acx_knn_slices(int64_t nq, int64_t n, int k, int* out_slices) {
+    if (!out_slices) ACX_FAIL(ACX_ERR_ARG, "acx_knn_slices: out_slices is null");
+    ACX_TRY(knn_check_shape("acx_knn_slices", nq, n, k));
+    *out_slices = knn_plan(nq, n, k).slices;
+    return ACX_OK;
+}
+
+int acx_knn_search(const float* q, int64_t ld_q, const float* q_inv_norm, int64_t nq, const float* d, int64_t ld_d,
+                   const float* d_inv_norm, int64_t n, int dim, int metric, int k, const int32_t* exclude, int32_t* indices,
+                   float* scores, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "acx_knn_search";
+    ACX_TRY(knn_check_shape(who, nq, n, k));
+    if (metric != ACX_KNN_DOT && metric != ACX_KNN_COSINE)
+        ACX_FAIL(ACX_ERR_ARG, "%s: metric %d (expected ACX_KNN_DOT or ACX_KNN_COSINE)", who, metric);
+    ACX_TRY(knn_check_rows(who, "q", q, ld_q, dim));
+    ACX_TRY(knn_check_rows(who, "d", d, ld_d, dim));
+    if (metric == ACX_KNN_COSINE && (!q_inv_norm || !d_inv_norm))
+        ACX_FAIL(ACX_ERR_ARG, "%s: q_inv_norm / d_inv_norm is null with ACX_KNN_COSINE", who);
+    if (!indices || !scores) ACX_FAIL(ACX_ERR_ARG, "%s: indices / scores is null", who);
+    if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    if (!ws) ACX_FAIL(ACX_ERR_ARG, "%s: workspace is null", who);
+    if (k > n - (exclude ? 1 : 0))
+        ACX_FAIL(ACX_ERR_ARG, "%s: k = %d exceeds the %lld rows a query may return%s", who, k, (long long)(n - (exclude ? 1 : 0)),
+                 exclude ? " (n - 1 with exclude)" : "");
+    ACX_TRY(check_workspace(ws, ws_bytes, knn_ws_bytes(nq, n, k)));
+    hipStream_t s = (hipStream_t)stream;
+    const KnnPlan pl = knn_plan(nq, n, k);
+    KnnSearchP p;
+    p.q = q; p.ld_q = ld_q; p.rq = metric == ACX_KNN_COSINE ? q_inv_norm : nullptr; p.nq = nq;
+    p.d = d; p.ld_d = ld_d; p.rd = metric == ACX_KNN_COSINE ? d_inv_norm : nullptr; p.n = n;
+    p.dim = dim; p.k = k; p.exclude = exclude; p.ws = static_cast<knn_key*>(ws); p.status = (int*)status;
+    p.slices = pl.slices; p.slice_rows = pl.slice_rows;
+    ACX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    const long long qtiles = knn_cdiv(nq, 32 * pl.qt);
+    const int ri = pl.r == 1 ? 0 : pl.r == 2 ? 1 : 2;
+    DeviceOnce& once = g_knn_lds[pl.qt - 1][ri];
+    int rc;
+    if (pl.qt == 1) rc = ri == 0 ? knn_launch_search<1, 1>(p, qtiles, once, s) : ri == 1 ? knn_launch_search<1, 2>(p, qtiles, once, s)
+                                                                                         : knn_launch_search<1, 4>(p, qtiles, once, s);
+    else rc = ri == 0 ? knn_launch_search<2, 1>(p, qtiles, once, s) : ri == 1 ? knn_launch_search<2, 2>(p, qtiles, once, s)
+                                                                              : knn_launch_search<2, 4>(p, qtiles, once, s);
+    ACX_TRY(rc);
+    const dim3 mgrid((unsigned)((nq + 3) / 4));
+    if (ri == 0) launch_kernel(&knn_merge_kernel<1>, mgrid, dim3(kKnnThreads), 0, s, (const knn_key*)p.ws, (long long)nq, pl.slices, k, (int*)indices, scores, (const int*)status);
+    else if (ri == 1) launch_kernel(&knn_merge_kernel<2>, mgrid, dim3(kKnnThreads), 0, s, (const knn_key*)p.ws, (long long)nq, pl.slices, k, (int*)indices, scores, (const int*)status);
+    else launch_kernel(&knn_merge_kernel<4>, mgrid, dim3(kKnnThreads), 0, s, (const knn_key*)p.ws, (long long)nq, pl.slices, k, (int*)indices, scores, (const int*)status);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int acx_knn_vote(const int32_t* indices, const float* scores, int64_t nq, int k, const void* target, int target_dtype,
+                 int64_t ld_target, int64_t n, int classes, int weighting, float temperature, float* out, int64_t ld_out,
+                 int32_t* status, void* stream) {
+    static const char* who = "acx_knn_vote";
+    ACX_TRY(knn_check_shape(who, nq, n, k));
+    if (!indices) ACX_FAIL(ACX_ERR_ARG, "%s: indices is null", who);
+    if (!target) ACX_FAIL(ACX_ERR_ARG, "%s: target is null", who);
+    if (!out) ACX_FAIL(ACX_ERR_ARG, "%s: out is null", who);
+    if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    if (target_dtype != ACX_TARGET_F32 && target_dtype != ACX_TARGET_U8)
+        ACX_FAIL(ACX_ERR_ARG, "%s: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", who, target_dtype);
+    if (classes < 1 || classes > ACX_MAX_CLASSES)
+        ACX_FAIL(ACX_ERR_ARG, "%s: classes = %d (expected 1 .. %d)", who, classes, ACX_MAX_CLASSES);
+    if (ld_target < classes) ACX_FAIL(ACX_ERR_ARG, "%s: ld_target = %lld is shorter than %d classes", who, (long long)ld_target, classes);
+    if (ld_out < classes) ACX_FAIL(ACX_ERR_ARG, "%s: ld_out = %lld is shorter than %d classes", who, (long long)ld_out, classes);
+    if (weighting != ACX_KNN_UNIFORM && weighting != ACX_KNN_SIMILARITY)
+        ACX_FAIL(ACX_ERR_ARG, "%s: weighting %d (expected ACX_KNN_UNIFORM or ACX_KNN_SIMILARITY)", who, weighting);
+    if (weighting == ACX_KNN_SIMILARITY) {
+        if (!scores) ACX_FAIL(ACX_ERR_ARG, "%s: scores is null with ACX_KNN_SIMILARITY", who);
+        if (!(temperature > 0.f) || !std::isfinite(temperature))
+            ACX_FAIL(ACX_ERR_ARG, "%s: temperature = %g (expected > 0)", who, (double)temperature);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    KnnVoteP p;
+    p.indices = (const int*)indices; p.scores = scores; p.k = k;
+    p.y = target; p.y_u8 = target_dtype == ACX_TARGET_U8; p.ld_y = ld_target; p.n = n; p.classes = classes;
+    p.similarity = weighting == ACX_KNN_SIMILARITY; p.temperature = temperature;
+    p.out = out; p.ld_out = ld_out; p.status = (int*)status;
+    ACX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    launch_kernel(&knn_vote_kernel, dim3((unsigned)nq, (unsigned)((classes + 255) / 256)), dim3(256), 0, s, p);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+}  // extern "C"

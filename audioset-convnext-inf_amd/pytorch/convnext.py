@@ -738,6 +738,27 @@ class ConvNeXt(nn.Module):
         self.head_audioset = head
         return fit
 
+    def build_index(self, data, target=None, sample_rate=None, metric="cosine"):
+        """An EmbeddingIndex (pytorch/retrieval.py) over scene embeddings on the model's device: `data` is an (n, 768) tensor
+        of embeddings, or a list of waveforms at `sample_rate`, whose scene embeddings are extracted first
+        (extract(..., what="scene", pack=True), as fit_head does); target: optional (n, C) labels for idx.classify."""
+        from .extract_embeddings import extract
+        from .retrieval import EmbeddingIndex
+        dev = self.head_audioset.weight.device
+        if getattr(data, "ndim", None) == 2:
+            emb = data
+        else:
+            emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
+        return EmbeddingIndex(emb, metric=metric, target=target, device=dev)
+
+    def search(self, index, waveform, k=10, sample_rate=None):
+        """Query by example: {"scores" (B, k) fp32, "indices" (B, k) int64, "scene" (B, 768)} of a (B, L) waveform batch --
+        forward_scene_embeddings, then index.search, on one stream with no host synchronisation (capturable as a whole).
+        index.check() reports a NaN or infinity met on the way."""
+        scene = self.forward_scene_embeddings(waveform, sample_rate=sample_rate)
+        scores, indices = index.search(scene, k=k)
+        return {"scores": scores, "indices": indices, "scene": scene}
+
     # ----------------------------------------------------------------------------- public surface
     # sample_rate (all three): the rate of x; None or 32000 is the model's own.  Any other integer rate is resampled to 32 kHz
     # on x's stream first (acx_resample, the interpolation of torchaudio.functional.resample that the reference's demo runs on

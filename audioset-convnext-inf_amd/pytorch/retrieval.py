@@ -1,0 +1,369 @@
+"""Nearest-neighbour search over embeddings on the GPU (acx_knn_search / acx_knn_vote in include/acx.h): query by example and
+the kNN probe of a frozen representation, next to the linear probe of `finetune.fit_head`.
+
+    from audioset_convnext_inf_amd.pytorch.retrieval import EmbeddingIndex, search_host, vote_host
+    idx = EmbeddingIndex(emb, metric="cosine", target=None)    # emb (n, dim); keeps the inverse norms
+    idx.add(more_emb, target=None)                             # earlier rows keep their indices
+    scores, indices = idx.search(queries, k=10, exclude=None)  # (q, k) fp32 / int64 device tensors, best first
+    scores, indices = idx.search(None, k=10)                   # self-search: every row against the others
+    probs = idx.classify(queries, k=10, weights="uniform")     # (q, C) fp32: kNN tagging, needs target=
+    idx.check()                                                # synchronises; ValueError if a search met a NaN or inf
+
+Order: score descending, then database index ascending, -0.0 as +0.0 -- one total order, so the result does not depend on how
+the kernel got there.  A (query, row) pair has the same score bits whatever the batch, the index size, k or the chunking.
+The (queries x database) score matrix is never written: a workgroup keeps the running top k of its queries on chip.
+
+Nothing here synchronises with the host, and every call can be captured in a torch.cuda.graph.  Data errors therefore travel
+in a status word on the device: a NaN or infinity in the queries or the index makes every index of that search -1 and every
+score NaN, and `idx.check()` -- the one call that synchronises -- raises ValueError("... NaN or infinite ...") for any search
+or classify since the last check.
+
+`search_host` / `vote_host` are the documented host equivalents in numpy float64 (the tests' reference), as
+`segments.decode_events` is for the event decoder."""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _ffi
+
+METRICS = tuple(_ffi.KNN_METRICS)
+WEIGHTS = tuple(_ffi.KNN_WEIGHTS)
+MAX_K = _ffi.KNN_MAX_K
+MAX_DIM = _ffi.KNN_MAX_DIM
+WORKSPACE_LIMIT = 256 << 20          # bytes of search workspace per chunk of queries
+
+
+def _vp(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _check_metric(metric):
+    if metric not in _ffi.KNN_METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (METRICS, metric))
+
+
+def _check_2d(x, name):
+    shape = tuple(getattr(x, "shape", ()))
+    if len(shape) != 2:
+        raise ValueError("%s must be 2-D (rows, dim), got shape %s" % (name, shape))
+    return shape
+
+
+def _check_k(k, n, excluding):
+    if int(k) != k or k < 1 or k > MAX_K:
+        raise ValueError("k = %r (expected an integer in 1 .. %d)" % (k, MAX_K))
+    if k > n - (1 if excluding else 0):
+        raise ValueError("k = %d exceeds the %d rows a query may return%s" % (k, n - (1 if excluding else 0),
+                                                                             " (the index size - 1 with exclude)" if excluding else ""))
+
+
+# ---- the host equivalents (numpy float64) ---------------------------------------------------------------------------------
+def search_host(queries, emb, k, metric="cosine", exclude=None):
+    """(scores (q, k) float64, indices (q, k) int64) of the k nearest rows of `emb` per query: float64 dot products (cosine:
+    times 1 / norm of each side, 0 for a zero row), ordered by score descending then index ascending (a stable sort);
+    exclude: per query one index that is not returned (-1: none)."""
+    _check_metric(metric)
+    q = np.asarray(queries, dtype=np.float64)
+    d = np.asarray(emb, dtype=np.float64)
+    qs, ds = _check_2d(q, "queries"), _check_2d(d, "emb")
+    if qs[1] != ds[1]:
+        raise ValueError("queries have dim %d, the embeddings dim %d" % (qs[1], ds[1]))
+    if ds[0] < 1:
+        raise ValueError("the index is empty")
+    _check_k(k, ds[0], exclude is not None)
+    s = q @ d.T
+    if metric == "cosine":
+        def inv(x):
+            nrm = np.sqrt((x * x).sum(axis=1))
+            return np.where(nrm > 0, 1.0 / np.where(nrm > 0, nrm, 1.0), 0.0)
+        s = s * inv(q)[:, None] * inv(d)[None, :]
+    s = s + 0.0                                               # -0.0 -> +0.0
+    key = -s
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64)
+        if ex.shape != (qs[0],):
+            raise ValueError("exclude must hold one index per query, got shape %s" % (ex.shape,))
+        rows = np.nonzero((ex >= 0) & (ex < ds[0]))[0]
+        key[rows, ex[rows]] = np.inf
+    order = np.argsort(key, axis=1, kind="stable")[:, :k]
+    return np.take_along_axis(s, order, axis=1), order.astype(np.int64)
+
+
+def vote_host(indices, scores, target, weights="uniform", temperature=0.07):
+    """(q, C) float64: sum_j w_j target[indices[q, j]] / sum_j w_j with w_j = 1 ("uniform") or exp((s_j - s_0) / temperature)
+    ("similarity")."""
+    if weights not in _ffi.KNN_WEIGHTS:
+        raise ValueError("weights must be one of %s, got %r" % (WEIGHTS, weights))
+    idx = np.asarray(indices, dtype=np.int64)
+    y = np.asarray(target, dtype=np.float64)
+    _check_2d(idx, "indices")
+    _check_2d(y, "target")
+    if weights == "uniform":
+        w = np.ones(idx.shape, dtype=np.float64)
+    else:
+        if not temperature > 0:
+            raise ValueError("temperature = %r (expected > 0)" % (temperature,))
+        s = np.asarray(scores, dtype=np.float64)
+        w = np.exp((s - s[:, :1]) / float(temperature))
+    return (w[:, :, None] * y[idx]).sum(axis=1) / w.sum(axis=1)[:, None]
+
+
+# ---- the device path -------------------------------------------------------------------------------------------------------
+def _device_of(device):
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("the search runs on a CUDA (HIP) device, not %s" % device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _readable(x):
+    """True if the kernels can read the rows of x where they are: unit column stride, a row stride that is a multiple of 4 and
+    no shorter than the row, 16-byte aligned."""
+    return (x.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]
+            and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0)
+
+
+def _rows(x, device, dim=None, name="embeddings"):
+    """x (rows, dim) -> an fp32 tensor on `device` the kernels can read, zero-padded to a multiple of 4 columns.  A CUDA tensor
+    that is already readable -- a column slice of a wider tensor too -- is returned as it is."""
+    shape = _check_2d(x, name)
+    if dim is not None and shape[1] != dim:
+        raise ValueError("%s have dim %d, the index dim %d" % (name, shape[1], dim))
+    if shape[1] < 1 or shape[1] > MAX_DIM:
+        raise ValueError("dim = %d (expected 1 .. %d)" % (shape[1], MAX_DIM))
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    x = x.detach().to(device=device, dtype=torch.float32)
+    if x.shape[1] % 4:
+        x = torch.nn.functional.pad(x, (0, 4 - x.shape[1] % 4))
+    if x.shape[0] and not _readable(x):
+        x = x.contiguous()
+    return x
+
+
+def _target(t, rows, device):
+    """-> a (rows, C) uint8 or fp32 device tensor with unit column stride."""
+    shape = _check_2d(t, "target")
+    if shape[0] != rows:
+        raise ValueError("target has %d rows, the embeddings %d" % (shape[0], rows))
+    if shape[1] < 1 or shape[1] > _ffi.MAX_CLASSES:
+        raise ValueError("target has %d classes (expected 1 .. %d)" % (shape[1], _ffi.MAX_CLASSES))
+    if not isinstance(t, torch.Tensor):
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    t = t.detach().to(device)
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype not in (torch.uint8, torch.float32):
+        t = t.to(torch.float32)
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
+def row_norms(x, status=None):
+    """1 / sqrt(sum x^2) per row of a readable (rows, dim) device tensor (0 for a zero row), on the current stream."""
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _ffi.knn_row_norms(_vp(x), x.stride(0), x.shape[0], x.shape[1], _vp(out), _vp(status), _ffi.stream_ptr(x.device))
+    return out
+
+
+def vote(indices, scores, target, weights="uniform", temperature=0.07, status=None):
+    """(q, C) fp32 on the device: the kNN vote of acx_knn_vote over `indices` (q, k) int32 / int64 into `target` (n, C) uint8 /
+    bool / fp32.  status: an int32 device word that receives ACX_KNN_BAD_INDEX for an index outside the target's rows."""
+    if weights not in _ffi.KNN_WEIGHTS:
+        raise ValueError("weights must be one of %s, got %r" % (WEIGHTS, weights))
+    if weights == "similarity" and not temperature > 0:
+        raise ValueError("temperature = %r (expected > 0)" % (temperature,))
+    q, k = _check_2d(indices, "indices")
+    if k < 1 or k > MAX_K:
+        raise ValueError("k = %d (expected 1 .. %d)" % (k, MAX_K))
+    dev = indices.device
+    target = _target(target, target.shape[0], dev)
+    idx32 = indices.to(torch.int32).contiguous()
+    sc = None if scores is None else scores.to(torch.float32).contiguous()
+    if weights == "similarity" and sc is None:
+        raise ValueError("similarity weights need the scores")
+    out = torch.empty((q, target.shape[1]), dtype=torch.float32, device=dev)
+    word = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.knn_vote(_vp(idx32), _vp(sc), q, k, _vp(target), _ffi.TARGET_U8 if target.dtype == torch.uint8 else _ffi.TARGET_F32,
+                      target.stride(0), target.shape[0], target.shape[1], _ffi.KNN_WEIGHTS[weights], temperature, _vp(out),
+                      out.stride(0), _vp(word), _ffi.stream_ptr(dev))
+    if status is not None:
+        status.bitwise_or_(word)
+    return out
+
+
+class EmbeddingIndex:
+    """A growing table of embeddings on one GPU with their inverse norms and, optionally, one target row each.
+
+    emb: (n, dim) -- a CUDA tensor is read where it is when its layout allows (a column slice of a wider tensor too) and is
+    then SHARED with the caller until the first add() that outgrows it; CPU tensors and numpy arrays are copied to `device`.
+    A dim that is not a multiple of 4 is zero-padded, which changes neither dots nor norms.  workspace_limit: bytes of search
+    workspace per chunk of queries; the chunking never changes a bit of the result."""
+
+    def __init__(self, emb, metric="cosine", target=None, device=None, workspace_limit=WORKSPACE_LIMIT):
+        _check_metric(metric)
+        shape = _check_2d(emb, "embeddings")
+        if isinstance(emb, torch.Tensor) and emb.is_cuda and device is None:
+            device = emb.device
+        self.device = _device_of(device)
+        self.metric = metric
+        self.dim = int(shape[1])
+        self.workspace_limit = int(workspace_limit)
+        self._n = 0
+        self._buf = None
+        self._inv = None
+        self._tgt = None
+        self._has_target = target is not None
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if shape[0]:
+            self.add(emb, target)
+        elif target is not None:
+            raise ValueError("target given with no embeddings")
+
+    # ---- contents
+    def __len__(self):
+        return self._n
+
+    @property
+    def embeddings(self):
+        """(n, dim) fp32 view of the stored rows."""
+        if self._buf is None:
+            return torch.empty((0, self.dim), dtype=torch.float32, device=self.device)
+        return self._buf[:self._n, :self.dim]
+
+    @property
+    def target(self):
+        return None if self._tgt is None else self._tgt[:self._n]
+
+    @property
+    def inverse_norms(self):
+        return None if self._inv is None else self._inv[:self._n]
+
+    def add(self, emb, target=None):
+        """Append rows (amortised growth: the capacity at least doubles when it runs out); earlier rows keep their indices and
+        their bits.  target: one row per new row if and only if the index was built with targets."""
+        x = _rows(emb, self.device, self.dim)
+        m = x.shape[0]
+        if (target is not None) != self._has_target:
+            raise ValueError("this index was built %s targets: add() must be called the same way"
+                             % ("with" if self._has_target else "without"))
+        if m == 0:
+            return self
+        t = _target(target, m, self.device) if target is not None else None
+        if t is not None and self._tgt is not None and (t.shape[1] != self._tgt.shape[1] or t.dtype != self._tgt.dtype):
+            raise ValueError("target rows of %d classes (%s) added to an index of %d classes (%s)"
+                             % (t.shape[1], t.dtype, self._tgt.shape[1], self._tgt.dtype))
+        with torch.cuda.device(self.device):
+            inv = row_norms(x, self._status) if self.metric == "cosine" else None
+            if self._buf is None:
+                self._buf, self._inv, self._tgt = x, inv, t
+            else:
+                n0, cap = self._n, self._buf.shape[0]
+                if n0 + m > cap:
+                    cap = max(2 * cap, n0 + m)
+                    buf = torch.empty((cap, x.shape[1]), dtype=torch.float32, device=self.device)
+                    buf[:n0] = self._buf[:n0]
+                    self._buf = buf
+                    if inv is not None:
+                        nv = torch.empty(cap, dtype=torch.float32, device=self.device)
+                        nv[:n0] = self._inv[:n0]
+                        self._inv = nv
+                    if t is not None:
+                        nt = torch.empty((cap, t.shape[1]), dtype=t.dtype, device=self.device)
+                        nt[:n0] = self._tgt[:n0]
+                        self._tgt = nt
+                self._buf[n0:n0 + m] = x
+                if inv is not None:
+                    self._inv[n0:n0 + m] = inv
+                if t is not None:
+                    self._tgt[n0:n0 + m] = t
+            self._n += m
+        return self
+
+    # ---- search
+    def _chunk(self, nq, k):
+        """The most queries per call whose workspace fits workspace_limit (at least one)."""
+        fits = lambda c: _ffi.knn_workspace_bytes(c, self._n, k) <= self.workspace_limit
+        if fits(nq):
+            return nq
+        lo, hi = 1, nq                  # fits(lo) assumed, fits(hi) false: the size is non-decreasing in the query count
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+        return lo
+
+    def search(self, queries, k=10, exclude=None):
+        """(scores (q, k) fp32, indices (q, k) int64), best first, on the device and the current stream; nothing synchronises.
+        queries: (q, dim), or None for a self-search -- every row of the index against the others (exclude = its own row).
+        exclude: None or one database index per query that is never returned (-1: none)."""
+        if self._n == 0:
+            raise ValueError("the index is empty")
+        if queries is None:
+            if exclude is not None:
+                raise ValueError("a self-search excludes each row itself: exclude must be None")
+            q, rq = self._buf[:self._n], self.inverse_norms
+            exclude = torch.arange(self._n, dtype=torch.int32, device=self.device)
+            _check_k(k, self._n, True)
+        else:
+            _check_2d(queries, "queries")
+            _check_k(k, self._n, exclude is not None)
+            q, rq = _rows(queries, self.device, self.dim, "queries"), None
+            if exclude is not None:
+                if not isinstance(exclude, torch.Tensor):
+                    exclude = torch.from_numpy(np.ascontiguousarray(exclude))
+                if tuple(exclude.shape) != (q.shape[0],):
+                    raise ValueError("exclude must hold one index per query, got shape %s" % (tuple(exclude.shape),))
+                exclude = exclude.to(device=self.device, dtype=torch.int32).contiguous()
+        nq, k = q.shape[0], int(k)
+        dev = self.device
+        indices = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        if nq == 0:
+            return scores, indices.to(torch.int64)
+        d = self._buf[:self._n]
+        cosine = self.metric == "cosine"
+        with torch.cuda.device(dev):
+            if cosine and rq is None:
+                rq = row_norms(q)
+            chunk = self._chunk(nq, k)
+            ws_bytes = _ffi.knn_workspace_bytes(min(chunk, nq), self._n, k)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            words = torch.empty((nq + chunk - 1) // chunk, dtype=torch.int32, device=dev)
+            stream = _ffi.stream_ptr(dev)
+            for i, a in enumerate(range(0, nq, chunk)):
+                b = min(nq, a + chunk)
+                _ffi.knn_search(_vp(q[a:b]), q.stride(0), _vp(rq[a:b]) if cosine else None, b - a, _vp(d), d.stride(0),
+                                _vp(self._inv) if cosine else None, self._n, q.shape[1], _ffi.KNN_METRICS[self.metric], k,
+                                _vp(exclude[a:b]) if exclude is not None else None, _vp(indices[a:b]), _vp(scores[a:b]),
+                                _vp(words[i:]), (_vp(ws), ws_bytes), stream)
+            self._status.bitwise_or_(words if words.numel() == 1 else words.amax())      # each word is 0 or ACX_KNN_NONFINITE
+        return scores, indices.to(torch.int64)
+
+    def classify(self, queries, k=10, weights="uniform", temperature=0.07):
+        """(q, C) fp32 on the device: kNN tagging -- the mean of the k nearest rows' targets, uniform or weighted by
+        exp((s_j - s_0) / temperature).  Equals search() followed by vote()."""
+        if self._tgt is None:
+            raise ValueError("classify needs an index built with target=")
+        if weights not in _ffi.KNN_WEIGHTS:
+            raise ValueError("weights must be one of %s, got %r" % (WEIGHTS, weights))
+        scores, indices = self.search(queries, k)
+        return vote(indices, scores, self.target, weights, temperature, status=self._status)
+
+    def check(self):
+        """Synchronise and raise ValueError if a search or classify since the last check met bad data."""
+        st = int(self._status.cpu()[0])
+        if st:
+            self._status.zero_()
+        if st & _ffi.KNN_NONFINITE:
+            raise ValueError("the queries or the indexed embeddings hold NaN or infinite values")
+        if st & _ffi.KNN_BAD_INDEX:
+            raise ValueError("a neighbour index lies outside the target rows")
+        return self

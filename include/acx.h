@@ -537,6 +537,56 @@ ACX_API int acx_head_fit_grad(const float* E, int64_t ld_e, int64_t n_rows_total
 ACX_API int acx_adam_update(float* param, const float* grad, float* m, float* v, float* vmax, int64_t n, const acx_adam* hp,
                             int64_t step_t, double lr, void* stream);
 
+/* ---- nearest-neighbour search over embeddings: top-k by dot product or cosine, and kNN tagging ----------------------------------
+ * The reference's checkpoint is "for audio tagging and embedding extraction"; this is what the embeddings are extracted for:
+ * query by example, and the kNN probe of a frozen representation.  Stateless: the caller owns every buffer (all on the device).
+ *   q (nq, dim) and d (n, dim) fp32 with row strides ld_q / ld_d (16-byte aligned, strides multiples of 4; column slices of
+ *   wider rows are read in place); dim a multiple of 4 in 4 .. ACX_KNN_MAX_DIM (pad with zero columns: neither dots nor norms
+ *   change); 1 <= k <= ACX_KNN_MAX_K.
+ * Score of (query i, row j): the fp32 dot product over dim (f32 matrix instructions, one fixed order per pair); for
+ * ACX_KNN_COSINE it is then (dot * q_inv_norm[i]) * d_inv_norm[j], with inv_norm = 1 / sqrt(sum x^2) from acx_knn_row_norms
+ * (0 for a zero row: every cosine with it is 0, never NaN).  A pair's score has the SAME BITS however it is reached: any nq, n,
+ * k, number of slices, position of the query or the row, a sub-range of the database.
+ * ONE TOTAL ORDER: neighbours are ordered by score descending, then database index ascending; -0.0 counts as +0.0.  Row t of
+ * `indices` (nq, k) int32 / `scores` (nq, k) fp32 holds the first k of that order over the computed fp32 scores, best first.
+ * exclude: NULL or device int32[nq], per query one database index that is never returned (-1: none); a self-search passes 0, 1,
+ * ..., n - 1.
+ *   acx_knn_row_norms: inv_norm[i] for n rows; ORs ACX_KNN_NONFINITE into *status if a row holds a NaN or +-inf (never clears).
+ *   acx_knn_workspace_bytes: workspace of a search, non-decreasing in nq, n and k (host only).
+ *   acx_knn_slices: into how many slices of the database rows a search of this shape is cut, so that a small nq still fills
+ *     the device (host only; a function of the three sizes and ACX_KNN_SLICE_ROWS alone).
+ *   acx_knn_search: a 4-byte clear of *status, the search kernel over (query tiles) x (slices), which keeps a running top k per
+ *     query on chip and never writes the (nq, n) score matrix, and the merge of the slices' lists.  DATA errors go through
+ *     *status: ACX_KNN_NONFINITE for a NaN or +-inf in q or d (or a dot product that overflows); every index is then -1 and
+ *     every score NaN.  0 when the data is valid.
+ *   acx_knn_vote: out[q][c] = sum_j w_j y[indices[q][j]][c] / sum_j w_j over the k neighbours, y = target (n, classes) of
+ *     target_dtype with row stride ld_target, out (nq, classes) fp32 with row stride ld_out.  ACX_KNN_UNIFORM: w_j = 1; with
+ *     ACX_TARGET_U8 the count is an integer and the result exactly float(count) / float(k).  ACX_KNN_SIMILARITY: w_j =
+ *     exp((s_j - s_0) / temperature) in fp32, s = scores, sums in neighbour order j = 0 .. k - 1.  Clears *status, then ORs
+ *     ACX_KNN_BAD_INDEX for an index outside [0, n): that neighbour contributes nothing (nothing outside target is read).
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable; the same
+ * inputs give the same bits on every call whatever the workspace holds.  No global atomics except on *status.  ARGUMENT errors
+ * return a negative status before any launch: a null pointer (q_inv_norm / d_inv_norm may be NULL for ACX_KNN_DOT, scores for
+ * ACX_KNN_UNIFORM), nq < 1, n < 1, k < 1, k > ACX_KNN_MAX_K, k > n (k > n - 1 with exclude), dim not a multiple of 4 or outside
+ * 4 .. ACX_KNN_MAX_DIM, a row stride shorter than its row or not a multiple of 4, an unaligned pointer, temperature <= 0, a
+ * workspace too small or not 256-byte aligned (ACX_ERR_WORKSPACE); n > 2^30 is ACX_ERR_UNSUPPORTED.  acx_set_precision has no
+ * influence; the kernels use no 16-bit matrix instruction and may run beside a forward on another stream. */
+enum acx_knn_metric { ACX_KNN_DOT = 0, ACX_KNN_COSINE = 1 };
+enum acx_knn_weighting { ACX_KNN_UNIFORM = 0, ACX_KNN_SIMILARITY = 1 };
+#define ACX_KNN_MAX_K 128      /* candidate buffers of 2 k keys for 64 queries: 128 KiB of the CU's 160 KiB of LDS */
+#define ACX_KNN_MAX_DIM 4096
+#define ACX_KNN_NONFINITE 1
+#define ACX_KNN_BAD_INDEX 2
+ACX_API int acx_knn_row_norms(const float* x, int64_t ld, int64_t n, int dim, float* inv_norm, int32_t* status, void* stream);
+ACX_API int acx_knn_workspace_bytes(int64_t nq, int64_t n, int k, size_t* out_bytes);
+ACX_API int acx_knn_slices(int64_t nq, int64_t n, int k, int* out_slices);
+ACX_API int acx_knn_search(const float* q, int64_t ld_q, const float* q_inv_norm, int64_t nq, const float* d, int64_t ld_d,
+                           const float* d_inv_norm, int64_t n, int dim, int metric, int k, const int32_t* exclude,
+                           int32_t* indices, float* scores, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_knn_vote(const int32_t* indices, const float* scores, int64_t nq, int k, const void* target, int target_dtype,
+                         int64_t ld_target, int64_t n, int classes, int weighting, float temperature, float* out,
+                         int64_t ld_out, int32_t* status, void* stream);
+
 /* Which evaluation of the STFT the frontend uses (round 6).  ACX_FRONTEND_AUTO (default): the FFT kernel when the stored buffers are
  * window x DFT, the dense contraction otherwise (acx_finalize above).  ACX_FRONTEND_DENSE: ALWAYS the dense contraction with the
  * stored `conv_real` / `conv_imag` weights -- the reference's own formulation (two Conv1d, convnext.py:179-187,298) -- 2.1 GFLOP
@@ -559,7 +609,8 @@ ACX_API int acx_set_frontend(acx_ctx* ctx, int mode);
 ACX_API int acx_frontend_info(const acx_ctx* ctx, int* dense_dft, float* stft_deviation, int* mel_taps);
 
 /* Diagnostics.  The tile-shape A/B switches ACX_GEMM_MI, ACX_WIDE_NPB, ACX_WIDE_PERSIST, ACX_DW_STREAM and ACX_DWM_WAVES, and
- * ACX_HEAD_PATH (1: the fused head kernel, 2: the class-tiled one, whatever N), are read from the
+ * ACX_HEAD_PATH (1: the fused head kernel, 2: the class-tiled one, whatever N), and ACX_KNN_SLICE_ROWS (database rows per slice of
+ * acx_knn_search, 16 .. 2^30: tests run many slices on a small database) are read from the
  * environment once, at the first acx_create; this re-reads them (tests force every tile shape through it and require
  * bit-identical results).  Launches never touch the environment.  No reference counterpart. */
 ACX_API int acx_tuning_refresh(void);
