@@ -1,4 +1,5 @@
-// Internal declarations shared by the libacx translation units (gfx950 only).
+// Host-side declarations shared by the libacx translation units (gfx950 only): the context, the launcher prototypes and the
+// host helpers.  What kernels share lives in device_common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -79,45 +80,6 @@ inline int set_max_dynamic_lds(DeviceOnce& once, K kernel, size_t bytes) {
 // is launched this way: next to such a kernel, packed-FP32 VALU instructions (v_pk_*_f32) of a co-resident foreign
 // wave return wrong results on this platform (tools/race2/).
 constexpr size_t kCuLdsBytes = 160 * 1024;
-// forces the register allocation of the calling kernel up to `v<n>` (asm clobber of the highest register wanted)
-#define ACX_CLAIM_VGPR(n) asm volatile("" ::: "v" #n)
-#define ACX_CLAIM_AGPR(n) asm volatile("" ::: "a" #n)
-
-// XOR swizzle of the 16-byte chunks of a 128-byte LDS row (the S16 k-tile rows of gemm_split.hip, the W2c images of
-// mlp_fused_wide.hip): chunk c of row r sits at position c ^ acx_swz8(r).  A permutation of the plain (r >> 1) & 7 chosen for
-// the lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... -- MI355X_MICROARCH.md, LDS): with it the
-// fragment reads of BOTH MFMA shapes are conflict-free -- 32x32x16 (lane = row l & 31, two k blocks) and 16x16x32 (lane =
-// row l & 15, k block l >> 4), where the plain form is 2-way (profiles/r03_p_split_pmc_per_kernel.csv: 0.09-0.14 conflict
-// cycles per CU cycle in the first 16x16x32 build).
-__host__ __device__ constexpr int acx_swz8(int row) {
-    const int t = (row >> 1) & 7;
-    return (t & 4) | ((t & 1) << 1) | (((t >> 1) ^ (t >> 2) ^ 1) & 1);
-}
-
-// Lanes l and l + 32 -- the two channel halves of one pixel row in the 32 x 32 MFMA layouts -- trade one register each
-// (v_permlane32_swap_b32): afterwards the LOWER lane holds (its own a, the upper lane's a) in (a, b) and the UPPER lane
-// (the lower lane's b, its own b).  Epilogues use it to turn two 8-byte pieces per lane, interleaved with the partner's,
-// into one 16-byte piece per lane: 32 contiguous bytes per row and store instruction instead of 16.
-__device__ __forceinline__ void acx_pair_swap(unsigned& a, unsigned& b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-}
-// The same between lanes l and l ^ 16 (v_permlane16_swap_b32: the odd rows of 16 lanes of a trade with the even rows of b):
-// the lane of the EVEN row ends up with (its own a, the odd row's a), the lane of the ODD row with (the even row's b, its
-// own b) -- the 16x16 MFMA layouts, where the lanes (g4, g4 ^ 1) of a pixel row hold adjacent groups of four channels.
-__device__ __forceinline__ void acx_pair_swap16(unsigned& a, unsigned& b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-}
-
-// ---- bf16 activations in HBM (ACX_PREC_BF16_ACT, stages 0-2): packed pairs, round to nearest even (v_cvt_pk_bf16_f32) ---
-typedef __bf16 acx_bf2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned acx_pack_bf16x2(float lo, float hi) {
-    acx_bf2 v; v.x = (__bf16)lo; v.y = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float acx_bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float acx_bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
 // ---- host-side weight image helpers (acx_finalize and the per-kernel packers) ----
 inline uint16_t to_bf16(float f) {      // round to nearest even, as v_cvt_pk_bf16_f32 does
@@ -458,18 +420,6 @@ __host__ __device__ __forceinline__ long long win_start(long long j, long long L
 }
 __host__ __device__ __forceinline__ long long win_steps(long long L, long long H) { return (L + H - 1) / H; }
 
-// The timeline reduction of class c over windows j0 .. j0 + cnt - 1 (cnt >= 1); row(j) points at window j's probabilities.
-// mean: an fp32 sum in ascending j, then one division by the count; max: fmaxf.
-template <class Row>
-__device__ __forceinline__ float win_reduce(Row row, long long j0, long long cnt, int c, int reduce) {
-    float acc = reduce ? -INFINITY : 0.f;
-    for (long long j = j0; j < j0 + cnt; ++j) {
-        const float v = row(j)[c];
-        acc = reduce ? fmaxf(acc, v) : acc + v;
-    }
-    return reduce ? acc : acc / (float)cnt;
-}
-
 // ---- sound event detection (segments.hip; the segment timeline in windows.hip) ---------------------------------------------
 constexpr int kSegSamples = ACX_SEGMENT_SAMPLES;
 // segments of a clip of L samples: the stage-3 height ((T + 4) / 4 + 1) / 8 = (T + 8) / 32, T = L / 320 + 1
@@ -486,15 +436,6 @@ int launch_segment_expand_varlen(const float* probs, const int64_t* lengths, int
 int launch_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
                             int reduce, float* out, hipStream_t s);
 
-// ---- resampling (resample.hip, stream.hip) ------------------------------------------------------------------------------
-// Output n = j nf + i of phase i: the fp32 FMA chain in ascending r over the band's count taps; xs = the staged input of the
-// band's first sample, h = tap 0 of phase i (tap r at h[r nf]).  Both resample kernels call this one chain.
-__device__ __forceinline__ float res_chain(const float* xs, const float* h, int nf, int count) {
-    float acc = 0.0f;
-    for (int r = 0; r < count; ++r) acc = __builtin_fmaf(h[(long long)r * nf], xs[r], acc);
-    return acc;
-}
-
 // ---- host code shared by api.hip, weights.hip, forward.hip and stream.hip ------------------------------------------------
 // bf16 activations in HBM for the stages that keep them (ACX_PREC_BF16_ACT, stages 0-2)
 inline bool act_bf16(const acx_ctx* c, int stage) { return c->precision == ACX_PREC_BF16_ACT && stage >= 0 && stage < 3; }
@@ -505,6 +446,9 @@ int make_aux(acx_ctx::Aux* a);                        // forward.hip: one fork/j
 void destroy_aux(acx_ctx::Aux& a);
 // "workspace of %zu bytes is smaller than the %zu needed" / "must be 256-byte aligned", in that order
 int check_workspace(const void* ptr, size_t bytes, size_t need);
+// the stand-alone modules (metrics.hip, head_fit.hip, events.hip), which name the entry point: "<who>: workspace of %zu bytes,
+// %zu needed" / "<who>: workspace is not 256-byte aligned", in that order
+int check_workspace_for(const char* who, const void* ptr, size_t bytes, size_t need);
 // The scratch of one block over pix pixels of C channels, carved from `off` on: y [pix][C], hidden [pix][4C], stats [pix][2]
 // (fp32 each, 256-byte aligned); end = the first byte after it.
 struct BlockScratch { size_t y, hidden, stats, end; };
@@ -549,6 +493,5 @@ inline int cu_count_of_current_device(int* out) {
     *out = v;
     return ACX_OK;
 }
-
 
 }  // namespace acx

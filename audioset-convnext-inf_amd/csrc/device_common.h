@@ -1,0 +1,168 @@
+// Device primitives shared by the libacx kernels (gfx950 only).  Every "same bits" promise between two kernels
+// rests on ONE function of this file that both sides call; acx_internal.h holds the host declarations and the launchers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace acx {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// forces the register allocation of the calling kernel up to `v<n>` (asm clobber of the highest register wanted)
+#define ACX_CLAIM_VGPR(n) asm volatile("" ::: "v" #n)
+#define ACX_CLAIM_AGPR(n) asm volatile("" ::: "a" #n)
+
+// XOR swizzle of the 16-byte chunks of a 128-byte LDS row (the S16 k-tile rows of gemm_split.hip, the W2c images of
+// mlp_fused_wide.hip): chunk c of row r sits at position c ^ acx_swz8(r).  A permutation of the plain (r >> 1) & 7 chosen for
+// the lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... -- MI355X_MICROARCH.md, LDS): with it the
+// fragment reads of BOTH MFMA shapes are conflict-free -- 32x32x16 (lane = row l & 31, two k blocks) and 16x16x32 (lane =
+// row l & 15, k block l >> 4), where the plain form is 2-way (profiles/r03_p_split_pmc_per_kernel.csv: 0.09-0.14 conflict
+// cycles per CU cycle in the first 16x16x32 build).
+__host__ __device__ constexpr int acx_swz8(int row) {
+    const int t = (row >> 1) & 7;
+    return (t & 4) | ((t & 1) << 1) | (((t >> 1) ^ (t >> 2) ^ 1) & 1);
+}
+
+// Lanes l and l + 32 -- the two channel halves of one pixel row in the 32 x 32 MFMA layouts -- trade one register each
+// (v_permlane32_swap_b32): afterwards the LOWER lane holds (its own a, the upper lane's a) in (a, b) and the UPPER lane
+// (the lower lane's b, its own b).  Epilogues use it to turn two 8-byte pieces per lane, interleaved with the partner's,
+// into one 16-byte piece per lane: 32 contiguous bytes per row and store instruction instead of 16.
+__device__ __forceinline__ void acx_pair_swap(unsigned& a, unsigned& b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = r[0]; b = r[1];
+}
+// The same between lanes l and l ^ 16 (v_permlane16_swap_b32: the odd rows of 16 lanes of a trade with the even rows of b):
+// the lane of the EVEN row ends up with (its own a, the odd row's a), the lane of the ODD row with (the even row's b, its
+// own b) -- the 16x16 MFMA layouts, where the lanes (g4, g4 ^ 1) of a pixel row hold adjacent groups of four channels.
+__device__ __forceinline__ void acx_pair_swap16(unsigned& a, unsigned& b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0]; b = r[1];
+}
+
+// ---- bf16 activations in HBM (ACX_PREC_BF16_ACT, stages 0-2): packed pairs, round to nearest even (v_cvt_pk_bf16_f32) ---
+__device__ __forceinline__ unsigned acx_pack_bf16x2(float lo, float hi) {
+    bf16x2 v; v.x = (__bf16)lo; v.y = (__bf16)hi;
+    return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ float acx_bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
+__device__ __forceinline__ float acx_bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
+
+// One 1-KB LDS-DMA piece by the builtin (global_load_lds_dwordx4): lane l's 16 bytes from gsrc land at lds_wave_base + 16 l.
+// (The inline-asm forms that keep the compiler's s_waitcnt out of persistent loops are split_math.h's acx_glds16*.)
+__device__ __forceinline__ void lds_dma16(const void* gsrc, char* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// ---- reductions ---------------------------------------------------------------------------------------------------------
+// The xor butterfly 32 -> 1 over the 64 lanes of a wave: every lane ends with the same bits (an add is commutative).
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// The partial results of a workgroup's four waves, added in wave order.
+__device__ __forceinline__ float sum4(float w0, float w1, float w2, float w3) { return ((w0 + w1) + w2) + w3; }
+
+// ---- S x S tiles on the f32-input matrix cores (head_fit.hip, segments.hip, knn.hip) ---------------------------------------
+// Lane = (column r = lane % S, lane group h = lane / S); accumulator register i of lane group h holds row row(i, h).
+template <int S> struct F32Tile;
+template <> struct F32Tile<32> {
+    typedef f32x16 acc_t;
+    static constexpr int REGS = 16;
+    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+};
+template <> struct F32Tile<16> {
+    typedef f32x4 acc_t;
+    static constexpr int REGS = 4;
+    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ int row(int i, int h) { return 4 * h + i; }
+};
+// lane (r, h)'s share of a wave's S x S partial tile -> red[row * S + col] (the lanes hold the columns: conflict-free);
+// reg(i) = the value of accumulator register i (a kernel with two accumulators adds them there)
+template <int S, class Reg>
+__device__ __forceinline__ void tile_spill(Reg reg, float* red, int r, int h) {
+    using T = F32Tile<S>;
+#pragma unroll
+    for (int i = 0; i < T::REGS; ++i) red[T::row(i, h) * S + r] = reg(i);
+}
+// element e of the tile: the four waves' spilled partials in wave order
+template <int N>
+__device__ __forceinline__ float tile_sum4(const float (&red)[4][N], int e) {
+    return sum4(red[0][e], red[1][e], red[2][e], red[3][e]);
+}
+
+// ---- the head (misc.hip: pool_head_kernel, head_tiled_kernel; segments.hip) ------------------------------------------------
+// One lane's share of a head row's dot product with an embedding: lane l holds chunks l, l + 64, l + 128 of both, 12 fmaf in
+// chunk and then component order.  wave_sum of it, + b[n], is the logit.
+__device__ __forceinline__ float head_dot(const float4 (&e)[3], const float4 (&w)[3]) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        s = fmaf(e[k].x, w[k].x, s); s = fmaf(e[k].y, w[k].y, s);
+        s = fmaf(e[k].z, w[k].z, s); s = fmaf(e[k].w, w[k].w, s);
+    }
+    return s;
+}
+__device__ __forceinline__ float head_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
+// torch.mean(x, dim=3) of four channels of one stage-3 row: r = the row's first frequency column (7 columns of 768 channels),
+// seven 16-byte loads, summed in ascending column order, * (1 / 7)
+__device__ __forceinline__ float4 freq_mean7(const float* r) {
+    float4 v[7];
+#pragma unroll
+    for (int w = 0; w < 7; ++w) v[w] = *reinterpret_cast<const float4*>(r + w * 768);
+    float4 s = v[0];
+#pragma unroll
+    for (int w = 1; w < 7; ++w) { s.x += v[w].x; s.y += v[w].y; s.z += v[w].z; s.w += v[w].w; }
+    s.x *= (1.0f / 7.0f); s.y *= (1.0f / 7.0f); s.z *= (1.0f / 7.0f); s.w *= (1.0f / 7.0f);
+    return s;
+}
+
+// ---- the native-fp32 GELU (gemm.hip, mlp_fused.hip) ------------------------------------------------------------------------
+// nn.GELU() default (approximate='none'): 0.5 v (1 + erf(v / sqrt 2)), with erf from Abramowitz-Stegun
+// 7.1.26 (|erf error| <= 1.5e-7, so |gelu error| <= 0.75e-7 |v|):
+//   erf(u) = sign(u) (1 - q),  q = (a1 t + ... + a5 t^5) exp(-u^2),  t = 1 / (1 + p |u|)
+//   gelu(v) = max(v, 0) - 0.5 |v| q          (since v sign(v) = |v|)
+// 14 VALU per element, two of them transcendental (v_rcp_f32, v_exp_f32).
+__device__ __forceinline__ float gelu_erf(float v) {
+    const float av = fabsf(v);
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678f, av, 1.0f));
+    float pl = fmaf(1.061405429f, t, -1.453152027f);
+    pl = fmaf(pl, t, 1.421413741f);
+    pl = fmaf(pl, t, -0.284496736f);
+    pl = fmaf(pl, t, 0.254829592f);
+    const float e = __builtin_amdgcn_exp2f(v * v * -0.72134752f);      // exp(-v^2 / 2)
+    const float q = pl * t * e;
+    return fmaf(-0.5f * av, q, fmaxf(v, 0.0f));
+}
+
+// ---- sliding windows (windows.hip, stream.hip) ------------------------------------------------------------------------------
+// The timeline reduction of class c over windows j0 .. j0 + cnt - 1 (cnt >= 1); row(j) points at window j's probabilities.
+// mean: an fp32 sum in ascending j, then one division by the count; max: fmaxf.
+template <class Row>
+__device__ __forceinline__ float win_reduce(Row row, long long j0, long long cnt, int c, int reduce) {
+    float acc = reduce ? -INFINITY : 0.f;
+    for (long long j = j0; j < j0 + cnt; ++j) {
+        const float v = row(j)[c];
+        acc = reduce ? fmaxf(acc, v) : acc + v;
+    }
+    return reduce ? acc : acc / (float)cnt;
+}
+
+// ---- resampling (resample.hip, stream.hip) ------------------------------------------------------------------------------
+// Output n = j nf + i of phase i: the fp32 FMA chain in ascending r over the band's count taps; xs = the staged input of the
+// band's first sample, h = tap 0 of phase i (tap r at h[r nf]).  Both resample kernels call this one chain.
+__device__ __forceinline__ float res_chain(const float* xs, const float* h, int nf, int count) {
+    float acc = 0.0f;
+    for (int r = 0; r < count; ++r) acc = __builtin_fmaf(h[(long long)r * nf], xs[r], acc);
+    return acc;
+}
+
+}  // namespace acx

@@ -10,13 +10,11 @@
 // pair.  The input rows and the 49x32 weight slice are staged through LDS; the batch is streamed as ONE tall
 // image (see the kernel), every input element is fetched from HBM once per column strip.
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 
 constexpr int kDwSlice = 32;      // channels per workgroup (staged as 8 x float4, computed as 16 lanes x float2)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define ACX_STAMP(var)
 

@@ -18,6 +18,7 @@
 // float64 appears only where decode_events has it: the boundaries (k * step_seconds), their differences against merge_gap /
 // min_duration, and the sum behind an event's mean.  Built with -fno-slp-vectorize like segments.hip (csrc/Makefile).
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 
@@ -239,9 +240,7 @@ __global__ __launch_bounds__(64) void events_kernel(EvArgs a) {
 
     if constexpr (!EMIT) {
         a.counts[unit * 64 + lane] = col.n;
-        long long tot = col.n;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d, 64);
+        const long long tot = wave_sum((long long)col.n);
         if (lane == 0) a.unit_off[unit] = tot;
         if (__any(bad) && lane == 0) atomicOr(a.status, ACX_EVENTS_NONFINITE);     // an OR: no order to depend on
     }
@@ -303,14 +302,13 @@ __global__ __launch_bounds__(kVarMaxClips) void events_table_kernel(EvTabArgs t,
     end[i] = t.end[i] > 0.0 ? t.end[i] : (double)t.steps[i] * t.step;
 }
 
-static size_t ev_align(size_t v) { return (v + 255) & ~(size_t)255; }
 // workspace: unit_off [units] int64 | counts [units][64] int32 | row0 [256] int64 | end [256] double | steps [256] int32
 static void ev_layout(long long units, size_t* counts, size_t* row0, size_t* end, size_t* steps, size_t* total) {
-    *counts = ev_align((size_t)units * 8);
-    *row0 = *counts + ev_align((size_t)units * 64 * 4);
-    *end = *row0 + ev_align(kVarMaxClips * 8);
-    *steps = *end + ev_align(kVarMaxClips * 8);
-    *total = *steps + ev_align(kVarMaxClips * 4);
+    *counts = align_up((size_t)units * 8);
+    *row0 = *counts + align_up((size_t)units * 64 * 4);
+    *end = *row0 + align_up(kVarMaxClips * 8);
+    *steps = *end + align_up(kVarMaxClips * 8);
+    *total = *steps + align_up(kVarMaxClips * 4);
 }
 
 static int ev_units(const char* who, int64_t B, int N, long long* units) {
@@ -362,12 +360,6 @@ static int ev_run(EvArgs a, long long units, long long* count, hipStream_t s) {
     return ACX_OK;
 }
 
-static int ev_check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
-    if (ws_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace is not 256-byte aligned", who);
-    return ACX_OK;
-}
-
 }  // namespace acx
 
 using namespace acx;
@@ -395,7 +387,7 @@ int acx_decode_events(const float* probs, int64_t ld, int64_t B, int steps, int 
     if (ld < N) ACX_FAIL(ACX_ERR_SHAPE, "%s: row stride %lld is shorter than %d classes", who, (long long)ld, N);
     size_t coff, roff, eoff, soff, need;
     ev_layout(units, &coff, &roff, &eoff, &soff, &need);
-    ACX_TRY(ev_check_ws(who, ws, ws_bytes, need));
+    ACX_TRY(check_workspace_for(who, ws, ws_bytes, need));
     char* w = static_cast<char*>(ws);
     EvArgs a{};
     a.probs = probs; a.ld = ld; a.steps = steps; a.N = N; a.G = (N + 63) / 64;
@@ -423,7 +415,7 @@ int acx_decode_events_varlen(const float* probs, int64_t ld, const int* steps, c
     if (ld < N) ACX_FAIL(ACX_ERR_SHAPE, "%s: row stride %lld is shorter than %d classes", who, (long long)ld, N);
     size_t coff, roff, eoff, soff, need;
     ev_layout(units, &coff, &roff, &eoff, &soff, &need);
-    ACX_TRY(ev_check_ws(who, ws, ws_bytes, need));
+    ACX_TRY(check_workspace_for(who, ws, ws_bytes, need));
     const hipStream_t s = (hipStream_t)stream;
     char* w = static_cast<char*>(ws);
     EvTabArgs t{};

@@ -71,6 +71,12 @@ int check_workspace(const void* ptr, size_t bytes, size_t need) {
     return ACX_OK;
 }
 
+int check_workspace_for(const char* who, const void* ptr, size_t bytes, size_t need) {
+    if (bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, bytes, need);
+    if (reinterpret_cast<uintptr_t>(ptr) & 255) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace is not 256-byte aligned", who);
+    return ACX_OK;
+}
+
 // bf16 precision: y -> fp32 LayerNorm -> bf16 rows; pwconv1 + GELU -> bf16 hidden; pwconv2 + residual -> fp32 x.
 // Both bf16 arrays live in the `hidden` scratch (sized for the fp32 hidden activation): [M][4C] then [M][Cp].
 static int run_mlp_bf16(acx_ctx* c, const BlockW& bw, int C, const float* y, float* x, float* hidden, int64_t M,

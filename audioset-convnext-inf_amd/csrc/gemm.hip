@@ -18,33 +18,14 @@
 // A fragment read is one ds_read_b128 per 4 k-steps: lane half h takes chunk 2g+h of its row, so MFMA j
 // of group g contracts k = {8g+j, 8g+4+j} (A and B use the same permutation).
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define ACX_GSTAMP(var)
 
 constexpr int kBK = 32;
 constexpr int kRowBytes = kBK * 4;        // 128-B LDS rows
-
-// nn.GELU() default (approximate='none'): 0.5 v (1 + erf(v / sqrt 2)), with erf from Abramowitz-Stegun
-// 7.1.26 (|erf error| <= 1.5e-7, so |gelu error| <= 0.75e-7 |v|):
-//   erf(u) = sign(u) (1 - q),  q = (a1 t + ... + a5 t^5) exp(-u^2),  t = 1 / (1 + p |u|)
-//   gelu(v) = max(v, 0) - 0.5 |v| q          (since v sign(v) = |v|)
-// 14 VALU per element, two of them transcendental (v_rcp_f32, v_exp_f32).
-__device__ __forceinline__ float gelu_erf(float v) {
-    const float av = fabsf(v);
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678f, av, 1.0f));
-    float pl = fmaf(1.061405429f, t, -1.453152027f);
-    pl = fmaf(pl, t, 1.421413741f);
-    pl = fmaf(pl, t, -0.284496736f);
-    pl = fmaf(pl, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(v * v * -0.72134752f);      // exp(-v^2 / 2)
-    const float q = pl * t * e;
-    return fmaf(-0.5f * av, q, fmaxf(v, 0.0f));
-}
 
 struct GemmParams {
     const float* A; const float* Wt; const float* bias; float* out;
@@ -56,11 +37,6 @@ struct GemmParams {
     int tiles_n;
     const int* irow;          // GATHER 2 (variable-length batch): input row of output row m / Wo (VarGeom::irow)
 };
-
-__device__ __forceinline__ void lds_dma16(const float* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // GATHER: 0 plain rows, 1 2x2 patch gather (downsample), 2 the same with the input row from p.irow (variable-length batch)
 template <int kBM, int BN, int WM, int WN, int EPI, int GATHER>

@@ -16,14 +16,8 @@
 
 namespace acx {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kBfRowBytes = 128;        // 64 bf16 per LDS row
 constexpr int kBfBK = 64;
-
-__device__ __forceinline__ float gelu_erf_b(float v) { return gelu3_unit(v); }     // split_math.h, third form
 
 struct GemmBfParams {
     const __bf16* A; const __bf16* Wt; const float* bias; void* out; const float* resid;
@@ -33,11 +27,9 @@ struct GemmBfParams {
     const int* irow;                          // GATHER 2 (variable-length batch): input row of output row m / Wo (VarGeom::irow)
 };
 
-// One 1-KB piece (8 rows x 128 B): scalar base of the tile's first row + a 32-bit offset per lane (its row's distance from that
-// row + its chunk) -- the form whose issue costs one instruction instead of five (split_math.h, acx_glds16_s; round 5).
-__device__ __forceinline__ void lds_dma16_b(const char* sbase, unsigned voff, char* lds_wave_base) {
-    acx_glds16_s(sbase, voff, acx_lds_addr(lds_wave_base));
-}
+// The 1-KB LDS-DMA pieces (8 rows x 128 B) below are acx_glds16_s (split_math.h): scalar base of the tile's first row + a 32-bit
+// offset per lane (its row's distance from that row + its chunk) -- the form whose issue costs one instruction instead of five
+// (round 5).
 
 // EPI: 0 bias -> fp32, 1 bias + GELU -> bf16, 2 bias + residual -> fp32, 3 bias -> bf16 (the downsample conv feeding a stage
 // whose activations live in HBM as bf16: ACX_PREC_BF16_ACT)
@@ -122,12 +114,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmBfParams p)
     {                                                                                                  \
         const long long koff = a_koff(k0);                                                             \
         _Pragma("unroll") for (int i = 0; i < A_DMA; ++i)                                              \
-            lds_dma16_b(a_base + koff * 2, a_src[i], a_dst + (slot) * A_TILE + i * 8 * kBfRowBytes);   \
+            acx_glds16_s(a_base + koff * 2, a_src[i], acx_lds_addr(a_dst + (slot) * A_TILE + i * 8 * kBfRowBytes)); \
     }
 #define ACX_DMA_B(k0, slot)                                                                            \
     {                                                                                                  \
         _Pragma("unroll") for (int i = 0; i < B_DMA; ++i)                                              \
-            lds_dma16_b(b_base + (long long)(k0) * 2, b_src[i], b_dst + (slot) * B_TILE + i * 8 * kBfRowBytes); \
+            acx_glds16_s(b_base + (long long)(k0) * 2, b_src[i], acx_lds_addr(b_dst + (slot) * B_TILE + i * 8 * kBfRowBytes)); \
     }
 
     f32x16 acc[TM][TN];
@@ -166,7 +158,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmBfParams p)
         _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                 \
         _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                               \
             if (i * TN + j < (n_)) {                                                                   \
-                lds_dma16_b((base_) + (koff_) * 2, src_[i * TN + j], (dst_) + (i * TN + j) * 8 * kBfRowBytes); \
+                acx_glds16_s((base_) + (koff_) * 2, src_[i * TN + j], acx_lds_addr((dst_) + (i * TN + j) * 8 * kBfRowBytes)); \
                 __builtin_amdgcn_sched_barrier(0);                                                     \
             }                                                                                          \
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af_[i]),    \
@@ -295,7 +287,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmBfParams p)
                         const long long off = (mb + dr) * p.N + n;
                         float v = acc[i][j][r] + bn;
                         if (EPI == 1) {
-                            reinterpret_cast<__bf16*>(p.out)[off] = (__bf16)gelu_erf_b(v);
+                            reinterpret_cast<__bf16*>(p.out)[off] = (__bf16)gelu3_unit(v);      // split_math.h, third form
                         } else if (EPI == 3) {
                             reinterpret_cast<__bf16*>(p.out)[off] = (__bf16)v;
                         } else {

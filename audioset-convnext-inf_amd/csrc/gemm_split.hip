@@ -46,11 +46,6 @@ struct GemmSParams {
     const int* irow;           // GATHER 2 (variable-length batch): input row of output row m / Wo (VarGeom::irow)
 };
 
-__device__ __forceinline__ void lds_dma16_s(const char* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // The GEMM runs on v_mfma_f32_16x16x32_f16 (round 3; the 32x32x16 form it replaced was removed after commit 07ba348).
 // Under MFMA load the chip holds a higher clock on this shape than on 32x32x16 at equal cycles per flop
 // (MI355X_MICROARCH.md 'DVFS give-back' item 7; profiles/r03_i_mfma_shape_rates.txt: bare loops on random operands
@@ -186,9 +181,9 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(GemmSParams p) {
             __builtin_amdgcn_sched_barrier(0);                                                         \
             if ((mc & 1) == 0) {                                                                       \
                 const int pc = mc >> 1;                                                                \
-                if (pc < B_DMA) lds_dma16_s(b_src[pc] + (k0B), b_dst + (bslot) * B_TILE + pc * 8 * kSRowBytes); \
+                if (pc < B_DMA) lds_dma16(b_src[pc] + (k0B), b_dst + (bslot) * B_TILE + pc * 8 * kSRowBytes); \
                 else if (pc < A_DMA + B_DMA)                                                           \
-                    lds_dma16_s(a_src[pc - B_DMA] + (koffA), a_dst + (aslot) * A_TILE + (pc - B_DMA) * 8 * kSRowBytes); \
+                    lds_dma16(a_src[pc - B_DMA] + (koffA), a_dst + (aslot) * A_TILE + (pc - B_DMA) * 8 * kSRowBytes); \
             }                                                                                          \
             if (mc < 2 * MI) ANX[mc >> 1][mc & 1] = *reinterpret_cast<const f32x4*>((abn_) + (mc >> 1) * 16 * kSRowBytes + ((mc & 1) ? foff_lo : foff_hi)); \
             else if (mc < 2 * MI + 6) BLX[(mc - 2 * MI) >> 1][mc & 1] = *reinterpret_cast<const f32x4*>((bbn_) + ((mc - 2 * MI) >> 1) * 16 * kSRowBytes + ((mc & 1) ? foff_lo : foff_hi)); \
@@ -196,10 +191,10 @@ __global__ __launch_bounds__(512) void gemm_split16_kernel(GemmSParams p) {
         } }
 #define ACX_DMA_A(koffA, aslot)                                                                        \
     {   _Pragma("unroll") for (int i = 0; i < A_DMA; ++i)                                              \
-            lds_dma16_s(a_src[i] + (koffA), a_dst + (aslot) * A_TILE + i * 8 * kSRowBytes); }
+            lds_dma16(a_src[i] + (koffA), a_dst + (aslot) * A_TILE + i * 8 * kSRowBytes); }
 #define ACX_DMA_B(k0B, bslot)                                                                          \
     {   _Pragma("unroll") for (int i = 0; i < B_DMA; ++i)                                              \
-            lds_dma16_s(b_src[i] + (k0B), b_dst + (bslot) * B_TILE + i * 8 * kSRowBytes); }
+            lds_dma16(b_src[i] + (k0B), b_dst + (bslot) * B_TILE + i * 8 * kSRowBytes); }
 #define ACX_TOUCH_A(F) { _Pragma("unroll") for (int i = 0; i < MI; ++i) { asm volatile("" :: "v"(F[i][0])); asm volatile("" :: "v"(F[i][1])); } }
 #define ACX_TOUCH_B(F) { _Pragma("unroll") for (int j = 0; j < 3; ++j) { asm volatile("" :: "v"(F[j][0])); asm volatile("" :: "v"(F[j][1])); } }
 

@@ -32,11 +32,9 @@
 #include <cmath>
 
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
-
-typedef float fit_f32x16 __attribute__((ext_vector_type(16)));
-typedef float fit_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kFitK = 768;                        // inputs of the head (convnext.py:656, dims[-1])
 constexpr int kFitThreads = 256;                  // four waves: the contraction is split four ways
@@ -68,31 +66,20 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
     p = __builtin_fmaf(p0, a.decay, -upd);                        // AdamW: decay = 1 - lr wd; Adam: 1
 }
 
-template <int S> struct FitTile;
-template <> struct FitTile<32> {
-    typedef fit_f32x16 acc_t;
-    static constexpr int NACC = 1, REGS = 16;
-    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-};
-template <> struct FitTile<16> {
-    typedef fit_f32x4 acc_t;
-    static constexpr int NACC = 2, REGS = 4;       // two accumulators: the dependent latency (40) exceeds the issue interval (32)
-    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int i, int h) { return 4 * h + i; }
+// F32Tile (device_common.h) + the accumulators an S x S tile alternates between, MFMA by MFMA
+template <int S> struct FitTile : F32Tile<S> {
+    static constexpr int NACC = S == 16 ? 2 : 1;   // 16 x 16: the dependent latency (40) exceeds the issue interval (32)
 };
 
-// the wave's S x S partial tile -> red[wave][row * S + col] (the lanes hold the columns: conflict-free)
+// the wave's accumulators, added -> red (tile_spill)
 template <int S>
 __device__ __forceinline__ void fit_spill(const typename FitTile<S>::acc_t* acc, float* red, int lane) {
     using T = FitTile<S>;
-    const int r = lane % S, h = lane / S;
-#pragma unroll
-    for (int i = 0; i < T::REGS; ++i) {
+    tile_spill<S>([&](int i) {
         float v = acc[0][i];
         if (T::NACC == 2) v += acc[T::NACC - 1][i];
-        red[T::row(i, h) * S + r] = v;
-    }
+        return v;
+    }, red, lane % S, lane / S);
 }
 
 struct FitGradP {
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) {
         const int rr = e / S, cc = e % S;
         const int row = row0 + rr, c = c0 + cc;
         if (row < p.rows && c < p.N) {
-            const float zz = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e] + p.b[c];
+            const float zz = tile_sum4(red, e) + p.b[c];
             const long long yo = s_idx[rr] * p.ld_y + c;
             const float y = p.y_u8 ? (static_cast<const unsigned char*>(p.Y)[yo] ? 1.f : 0.f) : static_cast<const float*>(p.Y)[yo];
             // sigmoid and both logarithms from e = exp(-|z|): log p = min(z, 0) - log1p(e), log(1 - p) = min(-z, 0) - log1p(e)
@@ -170,11 +157,10 @@ __global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) {
             if (p.z) p.z[o] = zz;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lsum += __shfl_xor(lsum, off);
+    lsum = wave_sum(lsum);
     if (lane == 0) s_loss[wave] = lsum;
     __syncthreads();
-    if (tid == 0) p.part[blockIdx.x] = ((s_loss[0] + s_loss[1]) + s_loss[2]) + s_loss[3];
+    if (tid == 0) p.part[blockIdx.x] = sum4(s_loss[0], s_loss[1], s_loss[2], s_loss[3]);
 }
 
 struct FitUpdP {
@@ -236,7 +222,7 @@ __global__ __launch_bounds__(kFitThreads) void fit_update_kernel(FitUpdP p) {
             const int e = tid + kFitThreads * q;
             const int c = c0 + e / S, k = k0 + e % S;
             if (c < p.N) {
-                const float dw = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+                const float dw = tile_sum4(red, e);
                 const long long o = (long long)c * kFitK + k;
                 if (APPLY) {
                     float w = p.W[o], m = p.mW[o], v = p.vW[o];
@@ -260,7 +246,7 @@ __global__ __launch_bounds__(kFitThreads) void fit_update_kernel(FitUpdP p) {
         red[wave][lane] = s;
         __syncthreads();
         if (wave == 0 && c < p.N) {
-            const float d = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+            const float d = tile_sum4(red, lane);
             if (APPLY) {
                 float w = p.b[c], m = p.mb[c], v = p.vb[c];
                 adam_elem(w, d, m, v, p.a.amsgrad ? p.vmaxb + c : nullptr, p.a);
@@ -274,11 +260,10 @@ __global__ __launch_bounds__(kFitThreads) void fit_update_kernel(FitUpdP p) {
     // the loss: partials in index order per thread, threads by the shuffle tree, waves in order
     float s = 0.f;
     for (int i = tid; i < p.nparts; i += kFitThreads) s += p.part[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    s = wave_sum(s);
     if (lane == 0) red[0][wave] = s;
     __syncthreads();
-    if (tid == 0) *p.loss = (((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) * p.inv;
+    if (tid == 0) *p.loss = sum4(red[0][0], red[0][1], red[0][2], red[0][3]) * p.inv;
 }
 
 __global__ __launch_bounds__(256) void adam_update_kernel(float* __restrict__ param, const float* __restrict__ grad,
@@ -291,12 +276,10 @@ __global__ __launch_bounds__(256) void adam_update_kernel(float* __restrict__ pa
     param[i] = w; m[i] = mm; v[i] = vv;
 }
 
-static size_t fit_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // workspace: G (rows_max, classes) fp32, then the loss partials of the finest tiling (16 x 16)
 static void fit_layout(long long rows, long long N, size_t* part_off, size_t* total) {
-    const size_t gb = fit_align((size_t)rows * N * 4);
-    const size_t pb = fit_align((size_t)((rows + 15) / 16) * ((N + 15) / 16) * 4);
+    const size_t gb = align_up((size_t)rows * N * 4);
+    const size_t pb = align_up((size_t)((rows + 15) / 16) * ((N + 15) / 16) * 4);
     *part_off = gb;
     *total = gb + pb;
 }
@@ -355,9 +338,7 @@ static int fit_check_call(const char* who, const FitCall& c, size_t* part_off) {
         ACX_FAIL(ACX_ERR_ARG, "%s: ld_target = %lld is shorter than %d classes", who, (long long)c.ld_y, c.classes);
     size_t need;
     fit_layout(c.rows, c.classes, part_off, &need);
-    if (c.ws_bytes < need) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, c.ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(c.ws) & 255) ACX_FAIL(ACX_ERR_WORKSPACE, "%s: workspace is not 256-byte aligned", who);
-    return ACX_OK;
+    return check_workspace_for(who, c.ws, c.ws_bytes, need);
 }
 
 // The two launches.  apply: W, b and the moments updated in place (u.a set); otherwise dW / db written.  The tile shape of each

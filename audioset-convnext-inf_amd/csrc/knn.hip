@@ -31,10 +31,10 @@
 #include <cmath>
 
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 
-typedef float knn_f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long knn_key;
 
 constexpr int kKnnThreads = 256;
@@ -118,8 +118,7 @@ __global__ __launch_bounds__(256) void knn_norm_kernel(const float* __restrict__
         bad |= !(fabsf(v.x) <= 3.4028234664e38f) || !(fabsf(v.y) <= 3.4028234664e38f) || !(fabsf(v.z) <= 3.4028234664e38f) ||
                !(fabsf(v.w) <= 3.4028234664e38f);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    s = wave_sum(s);
     if (__ballot(bad) && lane == 0) atomicOr(status, ACX_KNN_NONFINITE);
     if (lane == 0) inv_norm[row] = s > 0.f ? 1.0f / sqrtf(s) : 0.f;
 }
@@ -133,9 +132,6 @@ struct KnnSearchP {
     int* status;
     int slices; long long slice_rows;
 };
-
-// row of accumulator register i in the 32 x 32 MFMA tile, lane half h
-__device__ __forceinline__ int knn_acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 template <int QT, int R>
 __global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p) {
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p
     for (long long j0 = j_lo; j0 < j_hi; j0 += kKnnStepRows) {
         const long long jw = j0 + wave * 64;
         const bool active = jw < j_hi;               // wave-uniform
-        knn_f32x16 acc[QT][2];
+        F32Tile<32>::acc_t acc[QT][2];
         float rdv[2] = {1.f, 1.f};
         if (active) {
             const float* db[2];
@@ -192,7 +188,7 @@ __global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p
             const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #define KNN_MFMA(A, B, C)                                                                                      \
     _Pragma("unroll") for (int t = 0; t < QT; ++t) _Pragma("unroll") for (int u = 0; u < 2; ++u)               \
-        acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(A[t].C, B[u].C, acc[t][u], 0, 0, 0);
+        acc[t][u] = F32Tile<32>::mfma(A[t].C, B[u].C, acc[t][u]);
 #define KNN_GROUP                                                                               \
     KNN_MFMA(a0, b0, x) KNN_MFMA(a0, b0, y) KNN_MFMA(a0, b0, z) KNN_MFMA(a0, b0, w)             \
     KNN_MFMA(a1, b1, x) KNN_MFMA(a1, b1, y) KNN_MFMA(a1, b1, z) KNN_MFMA(a1, b1, w)
@@ -240,7 +236,7 @@ __global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p
                         for (int i = 0; i < 16; ++i) {
                             const int bit = (t * 2 + u) * 16 + i;
                             if ((pend >> bit) & 1ull) {
-                                const int ql = 32 * t + knn_acc_row(i, h);
+                                const int ql = 32 * t + F32Tile<32>::row(i, h);
                                 const long long j = jw + 32 * u + r32;
                                 bool keep = false;
                                 if (q0 + ql < p.nq && j < j_hi) {

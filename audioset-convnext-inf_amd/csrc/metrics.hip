@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 
@@ -214,10 +215,8 @@ __device__ void met_count(const T* pos, int P, const T* neg, int Nn, double* s_a
         a += (double)tp / (double)(tp + fp);
         u += (long long)lbn + ubn;
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        a += __shfl_xor(a, off);
-        u += __shfl_xor(u, off);
-    }
+    a = wave_sum(a);
+    u = wave_sum(u);
     const int w = threadIdx.x >> 6;
     if (__lane_id() == 0) { s_ap[w] = a; s_auc[w] = u; }
     __syncthreads();
@@ -291,11 +290,9 @@ __global__ __launch_bounds__(kMetThreads) void metrics_global_kernel(const unsig
     met_count((const unsigned*)g, P, (const unsigned*)(g + P), Nn, s_ap, s_auc, c, ap, auc, dprime);
 }
 
-static size_t met_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // keys, labels and (N > kMetLdsKeys) the global runs, each 256-byte aligned
 static void met_layout(long long n, long long C, size_t* keys_off, size_t* labs_off, size_t* runs_off, size_t* total) {
-    const size_t kb = met_align((size_t)n * C * 4), lb = met_align((size_t)n * C);
+    const size_t kb = align_up((size_t)n * C * 4), lb = align_up((size_t)n * C);
     *keys_off = 0;
     *labs_off = kb;
     *runs_off = kb + lb;
@@ -336,10 +333,7 @@ int acx_tagging_metrics(const float* scores, int64_t ld_scores, const void* targ
                  (long long)ld_target, classes);
     size_t koff, loff, roff, need;
     met_layout(n, classes, &koff, &loff, &roff, &need);
-    if (ws_bytes < need)
-        ACX_FAIL(ACX_ERR_WORKSPACE, "acx_tagging_metrics: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    if (reinterpret_cast<uintptr_t>(ws) & 255)
-        ACX_FAIL(ACX_ERR_WORKSPACE, "acx_tagging_metrics: workspace is not 256-byte aligned");
+    ACX_TRY(check_workspace_for("acx_tagging_metrics", ws, ws_bytes, need));
     const hipStream_t s = (hipStream_t)stream;
     char* w = static_cast<char*>(ws);
     unsigned* keys = reinterpret_cast<unsigned*>(w + koff);

@@ -1,14 +1,9 @@
 // K6 -- tail of forward_features + head (convnext.py:279-285, :321-325), and the NHWC->NCHW
 // transpose that gives forward_frame_embeddings its layout (convnext.py:276-277).
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // One workgroup of 768 threads per clip.  x NHWC (B,H3,7,768):
 //   mean over the 7 frequency columns (torch.mean(x, dim=3)), then max over time + mean over time,
@@ -35,14 +30,7 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
     const float* xb = x + row0 * 7 * 768 + 4 * cg;
     float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY), sm = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int h = ph; h < H3; h += 4) {
-        const float* r = xb + (long long)h * 7 * 768;
-        float4 v[7];
-#pragma unroll
-        for (int w = 0; w < 7; ++w) v[w] = *reinterpret_cast<const float4*>(r + w * 768);
-        float4 s = v[0];
-#pragma unroll
-        for (int w = 1; w < 7; ++w) { s.x += v[w].x; s.y += v[w].y; s.z += v[w].z; s.w += v[w].w; }
-        s.x *= (1.0f / 7.0f); s.y *= (1.0f / 7.0f); s.z *= (1.0f / 7.0f); s.w *= (1.0f / 7.0f);
+        const float4 s = freq_mean7(xb + (long long)h * 7 * 768);
         mx.x = fmaxf(mx.x, s.x); mx.y = fmaxf(mx.y, s.y); mx.z = fmaxf(mx.z, s.z); mx.w = fmaxf(mx.w, s.w);
         sm.x += s.x; sm.y += s.y; sm.z += s.z; sm.w += s.w;
     }
@@ -78,8 +66,8 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
 #pragma unroll
     for (int k = 0; k < 3; ++k) e[k] = *reinterpret_cast<const float4*>(&emb[4 * (lane + 64 * k)]);
     // four rows of the head per wave and pass: 12 independent 16-byte loads per lane in flight (one row at a time was a chain
-    // of 44 L2 round trips per wave).  The per-class arithmetic -- lane l's chunks l, l + 64, l + 128, 12 fmaf in chunk and
-    // then component order, wave_sum, + b[n], the sigmoid -- is head_tiled_kernel's as well: both give the same bits.
+    // of 44 L2 round trips per wave).  The per-class arithmetic is head_dot over lane l's chunks l, l + 64, l + 128, wave_sum,
+    // + b[n], head_sigmoid (device_common.h), the calls head_tiled_kernel makes as well: both give the same bits.
     for (int n0 = wave; n0 < N; n0 += 48) {
         float4 w4[4][3];
 #pragma unroll
@@ -91,18 +79,12 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                s = fmaf(e[k].x, w4[r][k].x, s); s = fmaf(e[k].y, w4[r][k].y, s);
-                s = fmaf(e[k].z, w4[r][k].z, s); s = fmaf(e[k].w, w4[r][k].w, s);
-            }
-            s = wave_sum(s);
+            const float s = wave_sum(head_dot(e, w4[r]));
             const int n = n0 + 12 * r;
             if (lane == 0 && n < N) {
                 const float z = s + hb[n];
                 if (logits) logits[b * N + n] = z;
-                if (probs) probs[b * N + n] = 1.0f / (1.0f + expf(-z));
+                if (probs) probs[b * N + n] = head_sigmoid(z);
             }
         }
     }
@@ -111,8 +93,8 @@ __global__ __launch_bounds__(768) void pool_head_kernel(const float* __restrict_
 // Class-tiled head for wide heads (kHeadTiledMin): logits / probs (B, N) from the scene rows (B, 768) that pool_head_kernel wrote.
 // pool_head_kernel reads the whole head once per clip (N = 16384: 48 MiB per clip, one busy CU per clip); here a workgroup holds
 // kHeadBt scene rows in LDS and applies the kHeadNt rows of its class tile to all of them, so the head is read ceil(B / kHeadBt)
-// times and the grid fills the chip.  Every (clip, class) value is pool_head_kernel's arithmetic: lane l holds chunks l, l + 64,
-// l + 128 of the row and of the embedding, 12 fmaf in chunk and then component order, wave_sum, + b[n], 1 / (1 + expf(-z)).
+// times and the grid fills the chip.  Every (clip, class) value is pool_head_kernel's arithmetic, by the same calls: lane l holds
+// chunks l, l + 64, l + 128 of the row and of the embedding, head_dot, wave_sum, + b[n], head_sigmoid (device_common.h).
 // Plain fp32 VALU, no MFMA: the bits stay, and the kernel is not CU-exclusive.
 // 4 waves; wave w takes classes w * 4 .. w * 4 + 3 of each group of 16, 4 rows in flight as in pool_head_kernel.  After the
 // wave_sums every lane holds each sum; lane r * 16 + i keeps (class r, clip i) of a pass of 16 clips, so that all 64 lanes add
@@ -156,13 +138,7 @@ __global__ __launch_bounds__(256) void head_tiled_kernel(const float* __restrict
                 for (int k = 0; k < 3; ++k) e[k] = *reinterpret_cast<const float4*>(&emb[i][4 * (lane + 64 * k)]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        s = fmaf(e[k].x, w4[r][k].x, s); s = fmaf(e[k].y, w4[r][k].y, s);
-                        s = fmaf(e[k].z, w4[r][k].z, s); s = fmaf(e[k].w, w4[r][k].w, s);
-                    }
-                    s = wave_sum(s);
+                    const float s = wave_sum(head_dot(e, w4[r]));
                     if (lane == r * 16 + (i - i0)) mine = s;
                 }
             }
@@ -171,7 +147,7 @@ __global__ __launch_bounds__(256) void head_tiled_kernel(const float* __restrict
                 const float z = mine + bias;
                 const long long o = (long long)(b0 + i) * N + n;
                 if (logits) logits[o] = z;
-                if (probs) probs[o] = 1.0f / (1.0f + expf(-z));
+                if (probs) probs[o] = head_sigmoid(z);
             }
         }
     }

@@ -19,23 +19,9 @@
 // LayerNorm statistics are computed in-kernel from the wave's own rows (two-pass, in registers).
 // HBM traffic per block: read y, read x, write x (3*C*H*W*4 B) -- the algorithmic minimum for this split.
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float gelu_erf_f(float v) {     // see gemm.hip: A&S 7.1.26 erf, 14 VALU
-    const float av = fabsf(v);
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678f, av, 1.0f));
-    float pl = fmaf(1.061405429f, t, -1.453152027f);
-    pl = fmaf(pl, t, 1.421413741f);
-    pl = fmaf(pl, t, -0.284496736f);
-    pl = fmaf(pl, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(v * v * -0.72134752f);
-    const float q = pl * t * e;
-    return fmaf(-0.5f * av, q, fmaxf(v, 0.0f));
-}
 
 template <int C>
 struct FusedCfg {
@@ -88,9 +74,7 @@ __global__ __launch_bounds__(FusedCfg<C>::kThreads) void mlp_fused_kernel(
     {                                                                                                           \
         const float* cb = wpack + (long long)(j) * (64 * C);                                                    \
         _Pragma("unroll") for (int k = 0; k < Cfg::kPieces; ++k)                                                \
-            __builtin_amdgcn_global_load_lds(                                                                   \
-                (const __attribute__((address_space(1))) void*)(cb + srcv[k]),                                  \
-                (__attribute__((address_space(3))) void*)((dstbase) + (wave * Cfg::kPieces + k) * 1024), 16, 0, 0); \
+            lds_dma16(cb + srcv[k], (dstbase) + (wave * Cfg::kPieces + k) * 1024);                              \
     }
     ACX_DMA(src1, 0, w1buf);
     ACX_DMA(src2, 0, w2buf);
@@ -158,10 +142,10 @@ __global__ __launch_bounds__(FusedCfg<C>::kThreads) void mlp_fused_kernel(
             const char* w1p = w1buf + ((j + 1) & 1) * Cfg::kHalfBytes;
             ACX_PHASE1(Xn, j + 1, w1p)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) X[r] = gelu_erf_f(X[r]);
+            for (int r = 0; r < 16; ++r) X[r] = gelu_erf(X[r]);
         } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { X[r] = gelu_erf_f(X[r]); Xn[r] = 0.f; }
+            for (int r = 0; r < 16; ++r) { X[r] = gelu_erf(X[r]); Xn[r] = 0.f; }
         }
         __builtin_amdgcn_sched_barrier(0);
         const char* w2p = w2buf + (j & 1) * Cfg::kHalfBytes + w2row;

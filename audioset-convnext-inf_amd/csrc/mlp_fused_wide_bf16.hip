@@ -18,9 +18,6 @@
 
 namespace acx {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 template <int C, int PT>
 struct WideBfCfg {
     static constexpr int kWaves = 4;
@@ -733,26 +730,15 @@ __global__ __launch_bounds__(512) void mlp_fused_stat_bf16_kernel(
 #undef ACX_LOAD_Y
 }
 
-// number of CUs of the current device (persistent launches), cached per device
-static int cu_count() {
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    int v = cached[dev & 63].load(std::memory_order_acquire);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cached[dev & 63].store(v, std::memory_order_release);
-    }
-    return v;
-}
-
 template <bool LNOUT, bool ABF>
 static int launch_stat_bf16(const BlockW& w, const void* y, void* x, long long M, void* ln_out, int ld_out, hipStream_t s) {
     static_assert(WideBfCfg<96, 1>::kSegs * WideBfCfg<96, 1>::kSegBytes + 5 * 96 * 4 <= kCuLdsBytes, "stream does not fit the LDS");
     static DeviceOnce once;
     ACX_TRY(set_max_dynamic_lds(once, &mlp_fused_stat_bf16_kernel<LNOUT, ABF>, kCuLdsBytes));
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));      // one persistent workgroup per CU
     const long long wgs_needed = ((M + 31) / 32 + 7) / 8;
-    const long long blocks = wgs_needed < cu_count() ? wgs_needed : cu_count();
+    const long long blocks = wgs_needed < cus ? wgs_needed : cus;
     launch_kernel(&mlp_fused_stat_bf16_kernel<LNOUT, ABF>, dim3((unsigned)blocks), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
         y, x, reinterpret_cast<const char*>(w.wstream_b), w.b1, w.b2, M, ld_out, reinterpret_cast<__bf16*>(ln_out));
     ACX_HIP(hipGetLastError());

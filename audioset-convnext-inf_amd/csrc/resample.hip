@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 

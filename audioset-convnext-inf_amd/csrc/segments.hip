@@ -16,21 +16,17 @@
 // 4 h .. 4 h + 3 and 8 + 4 h .. 8 + 4 h + 3, used alternately): the two tile shapes give the same bits, so the choice between
 // them -- by the size of the launch -- never shows in a result.  No atomics anywhere.
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
-
-__device__ __forceinline__ float seg_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 constexpr int kSegTs = 4;          // segments per workgroup of the pooling kernel
 
 // One workgroup of 192 threads per (clip, kSegTs consecutive segments); a thread owns four channels.  It walks the rows
 // t0 - pool / 2 .. t0 + kSegTs - 1 + pool / 2 that exist, one 7 x 16-byte load group per row, and folds each row's frequency
-// mean into the running (max, sum) of every segment of the tile whose window holds it: registers only.  The LayerNorm
-// statistics of the tile's rows are reduced as pool_head_kernel does (wave_sum, then the waves in order through LDS).
+// mean (freq_mean7, device_common.h: pool_head_kernel's call) into the running (max, sum) of every segment of the tile whose
+// window holds it: registers only.  The LayerNorm statistics of the tile's rows are reduced by wave_sum, then the three waves
+// in order through LDS.
 // VAR: clip b owns rows [roff3[b], roff3[b + 1]) of x and of emb.
 template <bool VAR>
 __global__ __launch_bounds__(192) void segment_pool_kernel(const float* __restrict__ x, int S_, int pool, int tiles,
@@ -55,14 +51,7 @@ __global__ __launch_bounds__(192) void segment_pool_kernel(const float* __restri
         sm[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (int s = s_lo; s <= s_hi; ++s) {
-        const float* r = xb + (long long)s * 7 * 768;
-        float4 v[7];
-#pragma unroll
-        for (int w = 0; w < 7; ++w) v[w] = *reinterpret_cast<const float4*>(r + w * 768);
-        float4 z = v[0];
-#pragma unroll
-        for (int w = 1; w < 7; ++w) { z.x += v[w].x; z.y += v[w].y; z.z += v[w].z; z.w += v[w].w; }
-        z.x *= (1.0f / 7.0f); z.y *= (1.0f / 7.0f); z.z *= (1.0f / 7.0f); z.w *= (1.0f / 7.0f);
+        const float4 z = freq_mean7(xb + (long long)s * 7 * 768);
 #pragma unroll
         for (int i = 0; i < kSegTs; ++i) {
             const int t = t0 + i;
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(192) void segment_pool_kernel(const float* __restri
     for (int i = 0; i < kSegTs; ++i) {
         p[i] = make_float4(mx[i].x + sm[i].x / fpool, mx[i].y + sm[i].y / fpool, mx[i].z + sm[i].z / fpool,
                            mx[i].w + sm[i].w / fpool);
-        part[i] = i < nt ? seg_wave_sum((p[i].x + p[i].y) + (p[i].z + p[i].w)) : 0.f;
+        part[i] = i < nt ? wave_sum((p[i].x + p[i].y) + (p[i].z + p[i].w)) : 0.f;
         if (lane == 0) red[0][wave][i] = part[i];
     }
     __syncthreads();
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(192) void segment_pool_kernel(const float* __restri
     for (int i = 0; i < kSegTs; ++i) {
         const float mean = ((red[0][0][i] + red[0][1][i]) + red[0][2][i]) * (1.0f / 768.0f);
         d[i] = make_float4(p[i].x - mean, p[i].y - mean, p[i].z - mean, p[i].w - mean);
-        part[i] = i < nt ? seg_wave_sum((d[i].x * d[i].x + d[i].y * d[i].y) + (d[i].z * d[i].z + d[i].w * d[i].w)) : 0.f;
+        part[i] = i < nt ? wave_sum((d[i].x * d[i].x + d[i].y * d[i].y) + (d[i].z * d[i].z + d[i].w * d[i].w)) : 0.f;
         if (lane == 0) red[1][wave][i] = part[i];
     }
     __syncthreads();
@@ -117,16 +106,10 @@ int launch_segment_pool(acx_ctx* c, const float* x, int B, int S, int pool, floa
 }
 
 // ---- the head ------------------------------------------------------------------------------------------------------------
-typedef float seg_f32x16 __attribute__((ext_vector_type(16)));
-typedef float seg_f32x4 __attribute__((ext_vector_type(4)));
-
+// F32Tile (device_common.h) + block(): one block of 16 inputs of the contraction
 template <int S> struct SegTile;
-template <> struct SegTile<32> {
-    typedef seg_f32x16 acc_t;
-    static constexpr int REGS = 16;
-    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-    // one block of 16 inputs: lane group h (0, 1) holds 4 h .. 4 h + 3 and 8 + 4 h .. 8 + 4 h + 3
+template <> struct SegTile<32> : F32Tile<32> {
+    // lane group h (0, 1) holds 4 h .. 4 h + 3 and 8 + 4 h .. 8 + 4 h + 3
     static __device__ __forceinline__ acc_t block(const float* a, const float* b, int h, acc_t c) {
         const float4 ap = *reinterpret_cast<const float4*>(a + 4 * h), aq = *reinterpret_cast<const float4*>(a + 8 + 4 * h);
         const float4 bp = *reinterpret_cast<const float4*>(b + 4 * h), bq = *reinterpret_cast<const float4*>(b + 8 + 4 * h);
@@ -137,11 +120,7 @@ template <> struct SegTile<32> {
         return c;
     }
 };
-template <> struct SegTile<16> {
-    typedef seg_f32x4 acc_t;
-    static constexpr int REGS = 4;
-    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int row(int i, int h) { return 4 * h + i; }
+template <> struct SegTile<16> : F32Tile<16> {
     // lane group h (0 .. 3) holds 4 h .. 4 h + 3
     static __device__ __forceinline__ acc_t block(const float* a, const float* b, int h, acc_t c) {
         const float4 av = *reinterpret_cast<const float4*>(a + 4 * h), bv = *reinterpret_cast<const float4*>(b + 4 * h);
@@ -187,8 +166,7 @@ __global__ __launch_bounds__(kSegThreads) void segment_head_kernel(SegHeadP p) {
         acc0 = T::block(ea + 32 * kb, wb + 32 * kb, h, acc0);
         acc1 = T::block(ea + 32 * kb + 16, wb + 32 * kb + 16, h, acc1);
     }
-#pragma unroll
-    for (int i = 0; i < T::REGS; ++i) red[wave][T::row(i, h) * S + r] = acc0[i] + acc1[i];
+    tile_spill<S>([&](int i) { return acc0[i] + acc1[i]; }, red[wave], r, h);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < S * S / kSegThreads; ++q) {
@@ -197,10 +175,10 @@ __global__ __launch_bounds__(kSegThreads) void segment_head_kernel(SegHeadP p) {
         const long long row = row0 + rr;
         const int c = c0 + cc;
         if (row < p.M && c < p.N) {
-            const float z = (((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]) + p.b[c];
+            const float z = tile_sum4(red, e) + p.b[c];
             const long long o = row * p.N + c;
             p.logits[o] = z;
-            p.probs[o] = 1.0f / (1.0f + expf(-z));
+            p.probs[o] = head_sigmoid(z);
         }
     }
 }

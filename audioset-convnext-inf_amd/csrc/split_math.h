@@ -1,14 +1,8 @@
-// Shared by the split-fp16 and bf16 kernels: vector types, LDS-DMA helpers, the GELU and the fp32 -> (fp16 hi, fp16 lo) split.
+// Shared by the split-fp16 and bf16 kernels: the inline-asm LDS-DMA forms, the GELU and the fp32 -> (fp16 hi, fp16 lo) split.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "device_common.h"
 
 namespace acx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 // One 1-KB LDS-DMA piece (global_load_lds_dwordx4: lane l's 16 bytes from gsrc land at lds_dst + 16 l) issued from inline
 // asm, so that hipcc does NOT know an LDS write is in flight: next to the builtin form it orders the next LDS read of the
@@ -103,7 +97,7 @@ __device__ __forceinline__ void acx_split_pair(const float x, const float y, uns
 //   for large |v|, E -> 0 without a clamp; E(0) = 1 exactly, so the relative accuracy near 0 is kept)
 //   gelu(v) = 0.5 v + 0.5 |v| (1 - E):  minimax fit of 0.5 |v| (E - erfc) over [0, 9] (tools/lab/fit_gelu.py):
 //   |gelu error| <= 5.4e-7 in exact arithmetic, <= 1e-6 as evaluated in fp32 (the fp32 rounding of a result near 4 is
-//   4.8e-7), against 2.1e-7 for A&S 7.1.26 (the native-fp32 path, gemm.hip) -- whose 1 / (1 + p |v|) and exp(-v^2 / 2) cost a second transcendental
+//   4.8e-7), against 2.1e-7 for A&S 7.1.26 (the native-fp32 path, device_common.h gelu_erf) -- whose 1 / (1 + p |v|) and exp(-v^2 / 2) cost a second transcendental
 //   (8 issue cycles each against 2-4 for an FMA, profiles/r03_c_valu_opcode_costs.txt) and four more instructions.
 // Unit: z = a (sinv 0.5 kH) = 0.5 kH v, the linear term of the result itself (one exact power-of-two multiply):
 //   g = gelu(v) kH = z + |z| (1 - E),   exp2 argument = |z| (K0 + K1 |z| + ... + K4 |z|^4),  Kj = -cj / (0.5 kH)^(j+1)

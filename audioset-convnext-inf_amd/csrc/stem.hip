@@ -16,6 +16,7 @@
 // xor-shuffles inside the 32-lane group.  A pixel leaves as one 384-byte run (12 bytes per lane; bf16: the even lane of a pair
 // stores both lanes' six channels).  0.90 MB in + 5.42 MB out per 10 s clip.
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 

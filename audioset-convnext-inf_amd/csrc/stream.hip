@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 
@@ -592,7 +593,7 @@ int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* 
         launch_kernel(&stream_table_kernel, dim3(1), dim3(kStrTable), 0, s, t, wstart + b0);
         ACX_HIP(hipGetLastError());
     }
-    const size_t head = ((size_t)count * 8 + 255) & ~(size_t)255;
+    const size_t head = align_up((size_t)count * 8);
     ACX_TRY(forward_uniform(st->ctx, st->ring, count, L, mode, out0, out1, (char*)workspace + head, s, wstart));
     if (st->timeline) {
         // window j of slot i -> history row i Hw + j mod Hw; slot i's windows are listed in order from its win_done on

@@ -85,8 +85,6 @@ __global__ __launch_bounds__(256) void varlen_tables_kernel(VarTabArgs a, VarTab
     }
 }
 
-static size_t var_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int varlen_geometry(const int64_t* lengths, int B, char* ws, VarGeom* vg, size_t* bytes) {
     if (B <= 0 || B > kVarMaxClips)
         ACX_FAIL(ACX_ERR_ARG, "variable-length batch of %d clips (expected 1 .. %d)", B, kVarMaxClips);
@@ -122,7 +120,7 @@ int varlen_geometry(const int64_t* lengths, int B, char* ws, VarGeom* vg, size_t
     }
     size_t off = 0;
     char* base = ws;
-    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += var_align(n); return p; };
+    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += align_up(n); return p; };
     g.soff = reinterpret_cast<const long long*>(take((size_t)(B + 1) * 8));
     g.foff = reinterpret_cast<const int*>(take((size_t)(B + 1) * 4));
     for (int s = 0; s < 4; ++s) g.roff[s] = reinterpret_cast<const int*>(take((size_t)(B + 1) * 4));

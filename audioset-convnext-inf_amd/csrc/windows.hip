@@ -7,6 +7,7 @@
 // gets the lengths BY VALUE, so the call stays free of host -> device copies, allocations and synchronisation (capturable),
 // as varlen_tables_kernel does for variable-length batches.
 #include "acx_internal.h"
+#include "device_common.h"
 
 namespace acx {
 
