@@ -51,6 +51,14 @@ class AcxEventParams(ctypes.Structure):
 
 _pevp, _pdbl = ctypes.POINTER(AcxEventParams), ctypes.POINTER(ctypes.c_double)
 
+
+class AcxOperatingSpec(ctypes.Structure):
+    """struct acx_operating_spec: the criterion of acx_operating_points."""
+    _fields_ = [("criterion", ctypes.c_int32), ("param", ctypes.c_double)]
+
+
+_pops = ctypes.POINTER(AcxOperatingSpec)
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -92,6 +100,10 @@ SIGNATURES = {
                                    _vp]),
     "acx_decode_events_varlen": (_c_int, [_vp, _c_i64, _pint, _pdbl, _c_int, _c_int, _pevp, _c_dbl, _vp, _c_i64, _vp, _vp, _vp,
                                           _c_sz, _vp]),
+    "acx_decode_events_classwise": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _pevp, _c_dbl, _c_dbl, _vp, _c_i64, _vp, _vp, _vp,
+                                             _c_sz, _vp, _vp, _vp]),
+    "acx_decode_events_varlen_classwise": (_c_int, [_vp, _c_i64, _pint, _pdbl, _c_int, _c_int, _pevp, _c_dbl, _vp, _c_i64, _vp, _vp,
+                                                    _vp, _c_sz, _vp, _vp, _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -124,6 +136,8 @@ SIGNATURES = {
     "acx_resample": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _vp, _vp]),
     "acx_metrics_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_tagging_metrics": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_operating_points": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _pops, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_threshold_counts": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp]),
     "acx_head_fit_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_head_fit_step": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _padam, _c_i64, _c_dbl, _vp, _vp, _vp, _c_sz, _vp]),
@@ -368,6 +382,8 @@ def window_count(lengths, window, hop):
 
 TARGET_F32, TARGET_U8 = 0, 1                 # enum acx_target_dtype
 METRICS_NONFINITE, METRICS_BAD_TARGET = 1, 2  # bits of acx_tagging_metrics' status word
+METRICS_BAD_THRESHOLD = 4                     # acx_threshold_counts: a NaN threshold
+OP_FBETA, OP_PRECISION, OP_RECALL = 0, 1, 2   # enum acx_operating_criterion
 
 
 def metrics_workspace_bytes(n, classes):
@@ -381,6 +397,20 @@ def tagging_metrics(scores, ld_scores, target, target_dtype, ld_target, n, class
     """acx_tagging_metrics on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
     check(lib().acx_tagging_metrics(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes), ap,
                                     auc, dprime, status, ws[0], int(ws[1]), stream))
+
+
+def operating_points(scores, ld_scores, target, target_dtype, ld_target, n, classes, criterion, param, thresholds, counts, status,
+                     ws, stream):
+    """acx_operating_points on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes) of metrics_workspace_bytes."""
+    spec = AcxOperatingSpec(int(criterion), float(param))
+    check(lib().acx_operating_points(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes),
+                                     ctypes.byref(spec), thresholds, counts, status, ws[0], int(ws[1]), stream))
+
+
+def threshold_counts(scores, ld_scores, target, target_dtype, ld_target, n, classes, thresholds, counts, status, stream):
+    """acx_threshold_counts on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_threshold_counts(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes),
+                                     thresholds, counts, status, stream))
 
 
 FIT_BAD_INDEX = 1                              # bit of the status word of acx_head_fit_step / acx_head_fit_grad
@@ -440,6 +470,7 @@ def knn_vote(indices, scores, nq, k, target, target_dtype, ld_target, n, classes
 
 MAX_EVENT_MEDIAN = 101                        # ACX_MAX_EVENT_MEDIAN
 EVENTS_NONFINITE, EVENTS_OVERFLOW = 1, 2      # bits of acx_decode_events' status word
+EVENTS_BAD_THRESHOLD = 4                      # the _classwise calls: a class with !(0 <= low <= threshold)
 EVENT_BYTES = ctypes.sizeof(AcxEvent)         # 32
 
 

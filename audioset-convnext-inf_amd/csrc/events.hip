@@ -32,7 +32,9 @@ struct EvArgs {
     long long ld;
     int steps;                 // uniform batches; varlen: tab_steps[clip]
     int N, G;                  // classes, units per clip = ceil(N / 64)
-    float thr, low;
+    float thr, low;            // every class's, unless thr_c / low_c give each class its own
+    const float* thr_c;        // [N] per-class threshold (null: thr)
+    const float* low_c;        // [N] per-class low (null: thr_c given ? the class's threshold : low)
     int median;
     double min_dur, gap, step, end;      // end: uniform batches (already resolved); varlen: tab_end[clip]
     const long long* tab_row0;           // varlen: first row of each clip (null: clip * steps)
@@ -102,6 +104,7 @@ struct EvColumn {
     int steps;
     double end;
     bool live;
+    float thr, low;          // this lane's class
     int clip, cls;
     long long base;          // EMIT: table index of this column's first event
     int n = 0;               // events so far
@@ -110,8 +113,9 @@ struct EvColumn {
     float rmax = 0.f, emax = 0.f, epeak = 0.f;
     double rsum = 0.0, esum = 0.0, esnap = 0.0;
 
-    __device__ __forceinline__ EvColumn(const EvArgs& a_, int steps_, double end_, bool live_, int clip_, int cls_, long long base_)
-        : a(a_), steps(steps_), end(end_), live(live_), clip(clip_), cls(cls_), base(base_) {}
+    __device__ __forceinline__ EvColumn(const EvArgs& a_, int steps_, double end_, bool live_, float thr_, float low_, int clip_,
+                                        int cls_, long long base_)
+        : a(a_), steps(steps_), end(end_), live(live_), thr(thr_), low(low_), clip(clip_), cls(cls_), base(base_) {}
     __device__ __forceinline__ double edge(int k) const { return k < steps ? (double)k * a.step : end; }
     __device__ __forceinline__ void finish_event() {
         if (!(edge(ee) - edge(eb) < a.min_dur)) {
@@ -143,14 +147,14 @@ struct EvColumn {
         }
     }
     __device__ __forceinline__ void step(int t, float p) {
-        const bool on = live && p >= a.low;
+        const bool on = live && p >= low;
         if (!on && in_run) end_run(t);
         if (have) { emax = fmaxf(emax, p); esum += (double)p; }
         if (on) {
             if (!in_run) { in_run = true; rb = t; rvalid = false; rmax = p; rsum = 0.0; }
             rmax = fmaxf(rmax, p);
             rsum += (double)p;
-            rvalid = rvalid || p >= a.thr;
+            rvalid = rvalid || p >= thr;
         }
     }
     __device__ __forceinline__ void finish() {
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(64) void events_kernel(EvArgs a) {
 
     long long base = 0;
     if constexpr (EMIT) {
-        if (*a.status & ACX_EVENTS_NONFINITE) return;
+        if (*a.status & (ACX_EVENTS_NONFINITE | ACX_EVENTS_BAD_THRESHOLD)) return;
         // exclusive prefix of the lanes' counts; a unit without events has nothing to write
         const int mine = a.counts[unit * 64 + lane];
         int incl = mine;
@@ -188,7 +192,11 @@ __global__ __launch_bounds__(64) void events_kernel(EvArgs a) {
     long long row0 = (long long)clip * a.steps;
     double end = a.end;
     if (a.tab_steps) { steps = a.tab_steps[clip]; row0 = a.tab_row0[clip]; end = a.tab_end[clip]; }
-    const float* x = a.probs + row0 * a.ld + (live ? cls : a.N - 1);     // idle lanes re-read the last class: in bounds
+    const int col_of = live ? cls : a.N - 1;                              // idle lanes re-read the last class: in bounds
+    const float* x = a.probs + row0 * a.ld + col_of;
+    // the lane's own two levels, loaded once
+    const float thr = a.thr_c ? a.thr_c[col_of] : a.thr;
+    const float low = a.low_c ? a.low_c[col_of] : a.thr_c ? thr : a.low;
     const int h = a.median / 2, last = steps - 1;
     auto row = [&](int r) { return x[(long long)(r < 0 ? 0 : r > last ? last : r) * a.ld]; };
 
@@ -209,7 +217,7 @@ __global__ __launch_bounds__(64) void events_kernel(EvArgs a) {
         win.r[0] = x0;
     }
 
-    EvColumn<EMIT> col(a, steps, end, live, clip, cls, base);
+    EvColumn<EMIT> col(a, steps, end, live, thr, low, clip, cls, base);
     // step t reads the window's median, then trades row t - h for row t + h + 1; both streams run kEvDepth rows ahead
     float cin[kEvDepth], cout[kEvDepth], nin[kEvDepth], nout[kEvDepth];
 #pragma unroll
@@ -242,7 +250,10 @@ __global__ __launch_bounds__(64) void events_kernel(EvArgs a) {
         a.counts[unit * 64 + lane] = col.n;
         const long long tot = wave_sum((long long)col.n);
         if (lane == 0) a.unit_off[unit] = tot;
-        if (__any(bad) && lane == 0) atomicOr(a.status, ACX_EVENTS_NONFINITE);     // an OR: no order to depend on
+        // per-class levels live on the device: checked here (the host has checked the scalar ones), NaN included
+        const bool bad_level = !(low >= 0.f && low <= thr);
+        const int bits = (__any(bad) ? ACX_EVENTS_NONFINITE : 0) | (__any(bad_level) ? ACX_EVENTS_BAD_THRESHOLD : 0);
+        if (bits && lane == 0) atomicOr(a.status, bits);                           // an OR: no order to depend on
     }
 }
 
@@ -276,7 +287,7 @@ __global__ __launch_bounds__(1024) void events_scan_kernel(long long* unit_off, 
     }
     if (tid == 0) {
         const int st = *status;
-        if (st & ACX_EVENTS_NONFINITE) {
+        if (st & (ACX_EVENTS_NONFINITE | ACX_EVENTS_BAD_THRESHOLD)) {
             *count = 0;
         } else {
             *count = total;
@@ -323,11 +334,15 @@ static int ev_units(const char* who, int64_t B, int N, long long* units) {
     return ACX_OK;
 }
 
-static int ev_check_params(const char* who, const acx_event_params* p, double step_seconds, int64_t capacity) {
+static int ev_check_params(const char* who, const acx_event_params* p, double step_seconds, int64_t capacity,
+                           const float* threshold = nullptr, const float* low = nullptr) {
     if (p->median < 1 || p->median > ACX_MAX_EVENT_MEDIAN || p->median % 2 == 0)
         ACX_FAIL(ACX_ERR_ARG, "%s: median %d (expected an odd width in 1 .. %d)", who, p->median, ACX_MAX_EVENT_MEDIAN);
-    if (!(p->low >= 0.f && p->low <= p->threshold))
+    // a per-class pointer replaces its scalar; what is left of the scalars is checked here, the rest on the device
+    if (!threshold && !low && !(p->low >= 0.f && p->low <= p->threshold))
         ACX_FAIL(ACX_ERR_ARG, "%s: low %g must be in [0, threshold = %g]", who, (double)p->low, (double)p->threshold);
+    if (!threshold && low && !(p->threshold >= 0.f))
+        ACX_FAIL(ACX_ERR_ARG, "%s: threshold %g must not be negative", who, (double)p->threshold);
     if (!(p->min_duration >= 0.0) || !(p->merge_gap >= 0.0))
         ACX_FAIL(ACX_ERR_ARG, "%s: min_duration %g and merge_gap %g must not be negative", who, p->min_duration, p->merge_gap);
     if (!(step_seconds > 0.0)) ACX_FAIL(ACX_ERR_ARG, "%s: step_seconds %g (expected > 0)", who, step_seconds);
@@ -360,27 +375,12 @@ static int ev_run(EvArgs a, long long units, long long* count, hipStream_t s) {
     return ACX_OK;
 }
 
-}  // namespace acx
-
-using namespace acx;
-
-extern "C" {
-
-int acx_events_workspace_bytes(int64_t B, int N, size_t* bytes) {
-    if (!bytes) ACX_FAIL(ACX_ERR_ARG, "acx_events_workspace_bytes: bytes is null");
-    long long units;
-    ACX_TRY(ev_units("acx_events_workspace_bytes", B, N, &units));
-    size_t c, r, e, st;
-    ev_layout(units, &c, &r, &e, &st, bytes);
-    return ACX_OK;
-}
-
-int acx_decode_events(const float* probs, int64_t ld, int64_t B, int steps, int N, const acx_event_params* p, double step_seconds,
-                      double end_seconds, acx_event* events, int64_t capacity, int64_t* count, int* status, void* ws,
-                      size_t ws_bytes, void* stream) {
-    const char* who = "acx_decode_events";
+// the uniform and the varlen call, with every class's levels in *p or one per class behind threshold / low
+static int ev_decode(const char* who, const float* probs, int64_t ld, int64_t B, int steps, int N, const acx_event_params* p,
+                     double step_seconds, double end_seconds, acx_event* events, int64_t capacity, int64_t* count, int* status,
+                     void* ws, size_t ws_bytes, void* stream, const float* threshold, const float* low) {
     if (!probs || !p || !events || !count || !status || !ws) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
-    ACX_TRY(ev_check_params(who, p, step_seconds, capacity));
+    ACX_TRY(ev_check_params(who, p, step_seconds, capacity, threshold, low));
     if (steps < 1 || steps > kEvMaxSteps) ACX_FAIL(ACX_ERR_SHAPE, "%s: %d steps (expected 1 .. 2^30)", who, steps);
     long long units;
     ACX_TRY(ev_units(who, B, N, &units));
@@ -391,7 +391,7 @@ int acx_decode_events(const float* probs, int64_t ld, int64_t B, int steps, int 
     char* w = static_cast<char*>(ws);
     EvArgs a{};
     a.probs = probs; a.ld = ld; a.steps = steps; a.N = N; a.G = (N + 63) / 64;
-    a.thr = p->threshold; a.low = p->low; a.median = p->median;
+    a.thr = p->threshold; a.low = p->low; a.thr_c = threshold; a.low_c = low; a.median = p->median;
     a.min_dur = p->min_duration; a.gap = p->merge_gap; a.step = step_seconds;
     a.end = end_seconds > 0.0 ? end_seconds : (double)steps * step_seconds;
     a.counts = reinterpret_cast<int*>(w + coff);
@@ -400,12 +400,12 @@ int acx_decode_events(const float* probs, int64_t ld, int64_t B, int steps, int 
     return ev_run(a, units, reinterpret_cast<long long*>(count), (hipStream_t)stream);
 }
 
-int acx_decode_events_varlen(const float* probs, int64_t ld, const int* steps, const double* end_seconds, int B, int N,
-                             const acx_event_params* p, double step_seconds, acx_event* events, int64_t capacity, int64_t* count,
-                             int* status, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "acx_decode_events_varlen";
+static int ev_decode_varlen(const char* who, const float* probs, int64_t ld, const int* steps, const double* end_seconds, int B,
+                            int N, const acx_event_params* p, double step_seconds, acx_event* events, int64_t capacity,
+                            int64_t* count, int* status, void* ws, size_t ws_bytes, void* stream, const float* threshold,
+                            const float* low) {
     if (!probs || !steps || !p || !events || !count || !status || !ws) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
-    ACX_TRY(ev_check_params(who, p, step_seconds, capacity));
+    ACX_TRY(ev_check_params(who, p, step_seconds, capacity, threshold, low));
     if (B < 1 || B > kVarMaxClips) ACX_FAIL(ACX_ERR_SHAPE, "%s: %d clips (expected 1 .. %d)", who, B, kVarMaxClips);
     for (int i = 0; i < B; ++i)
         if (steps[i] < 1 || steps[i] > kEvMaxSteps)
@@ -431,13 +431,57 @@ int acx_decode_events_varlen(const float* probs, int64_t ld, const int* steps, c
     ACX_HIP(hipGetLastError());
     EvArgs a{};
     a.probs = probs; a.ld = ld; a.steps = 0; a.N = N; a.G = (N + 63) / 64;
-    a.thr = p->threshold; a.low = p->low; a.median = p->median;
+    a.thr = p->threshold; a.low = p->low; a.thr_c = threshold; a.low_c = low; a.median = p->median;
     a.min_dur = p->min_duration; a.gap = p->merge_gap; a.step = step_seconds;
     a.tab_row0 = row0; a.tab_steps = stp; a.tab_end = end;
     a.counts = reinterpret_cast<int*>(w + coff);
     a.unit_off = reinterpret_cast<long long*>(w);
     a.status = status; a.events = events; a.capacity = capacity;
     return ev_run(a, units, reinterpret_cast<long long*>(count), s);
+}
+
+}  // namespace acx
+
+using namespace acx;
+
+extern "C" {
+
+int acx_events_workspace_bytes(int64_t B, int N, size_t* bytes) {
+    if (!bytes) ACX_FAIL(ACX_ERR_ARG, "acx_events_workspace_bytes: bytes is null");
+    long long units;
+    ACX_TRY(ev_units("acx_events_workspace_bytes", B, N, &units));
+    size_t c, r, e, st;
+    ev_layout(units, &c, &r, &e, &st, bytes);
+    return ACX_OK;
+}
+
+int acx_decode_events(const float* probs, int64_t ld, int64_t B, int steps, int N, const acx_event_params* p, double step_seconds,
+                      double end_seconds, acx_event* events, int64_t capacity, int64_t* count, int* status, void* ws,
+                      size_t ws_bytes, void* stream) {
+    return ev_decode("acx_decode_events", probs, ld, B, steps, N, p, step_seconds, end_seconds, events, capacity, count, status, ws,
+                     ws_bytes, stream, nullptr, nullptr);
+}
+
+int acx_decode_events_classwise(const float* probs, int64_t ld, int64_t B, int steps, int N, const acx_event_params* p,
+                                double step_seconds, double end_seconds, acx_event* events, int64_t capacity, int64_t* count,
+                                int* status, void* ws, size_t ws_bytes, void* stream, const float* threshold, const float* low) {
+    return ev_decode("acx_decode_events_classwise", probs, ld, B, steps, N, p, step_seconds, end_seconds, events, capacity, count,
+                     status, ws, ws_bytes, stream, threshold, low);
+}
+
+int acx_decode_events_varlen(const float* probs, int64_t ld, const int* steps, const double* end_seconds, int B, int N,
+                             const acx_event_params* p, double step_seconds, acx_event* events, int64_t capacity, int64_t* count,
+                             int* status, void* ws, size_t ws_bytes, void* stream) {
+    return ev_decode_varlen("acx_decode_events_varlen", probs, ld, steps, end_seconds, B, N, p, step_seconds, events, capacity,
+                            count, status, ws, ws_bytes, stream, nullptr, nullptr);
+}
+
+int acx_decode_events_varlen_classwise(const float* probs, int64_t ld, const int* steps, const double* end_seconds, int B, int N,
+                                       const acx_event_params* p, double step_seconds, acx_event* events, int64_t capacity,
+                                       int64_t* count, int* status, void* ws, size_t ws_bytes, void* stream, const float* threshold,
+                                       const float* low) {
+    return ev_decode_varlen("acx_decode_events_varlen_classwise", probs, ld, steps, end_seconds, B, N, p, step_seconds, events,
+                            capacity, count, status, ws, ws_bytes, stream, threshold, low);
 }
 
 }  // extern "C"

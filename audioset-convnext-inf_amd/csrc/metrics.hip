@@ -14,6 +14,11 @@
 // then splits its keys into a positives run and a negatives run, sorts both (bitonic network, in LDS up to kMetLdsKeys keys,
 // through the workspace beyond) and counts every positive against them by binary search.  Partial sums are reduced per wave and
 // combined in a fixed order: the results are the same bits on every call.
+//
+// Operating points (acx_operating_points): the same prep, split and sorts, then one sweep over the distinct positive scores --
+// the only thresholds worth choosing under the rule score >= threshold -- that keeps the best one under the criterion's total
+// order (op_better below); an argmax over distinct candidates, so the result does not depend on the order of the reduction.
+// acx_threshold_counts scores given thresholds on any split without a sort: integer sums per class, combined by integer atomics.
 #include <cmath>
 
 #include "acx_internal.h"
@@ -290,6 +295,195 @@ __global__ __launch_bounds__(kMetThreads) void metrics_global_kernel(const unsig
     met_count((const unsigned*)g, P, (const unsigned*)(g + P), Nn, s_ap, s_auc, c, ap, auc, dprime);
 }
 
+// ---- operating points -----------------------------------------------------------------------------------------------------
+
+struct OpSpec {
+    int crit;              // ACX_OP_*
+    double param;          // precision / recall: the level to reach
+    double b2, onepb2;     // F-beta: beta * beta and 1 + beta * beta, both rounded on the host
+};
+
+// A thread's best candidate.  The criterion's total order is (f, rank), larger is better: F-beta ranks by F, then by the key
+// (the highest threshold among equal F); precision and recall give every qualifying candidate f = 0 and rank by ~key (the lowest
+// threshold) and by the key (the highest).  f < 0: no candidate.  Keys of candidates are distinct, so the maximum is unique.
+struct OpBest {
+    double f;
+    unsigned rank;
+    int tp, fp;
+};
+
+__device__ __forceinline__ bool op_better(const OpBest& x, const OpBest& b) {
+    return x.f >= 0.0 && (x.f > b.f || (x.f == b.f && x.rank > b.rank));
+}
+
+// F-beta of a candidate.  The selection has to equal the host statement (pytorch/metrics.py operating_points_host) bit for bit,
+// and there every operation is rounded on its own: contraction into fused multiply-adds, which hipcc applies by default, is
+// switched off for this function.
+__device__ __forceinline__ double op_fbeta(const OpSpec& sp, int tp, int fn, int fp) {
+#pragma clang fp contract(off)
+    const double num = sp.onepb2 * (double)tp;
+    const double den = (num + sp.b2 * (double)fn) + (double)fp;
+    return num / den;
+}
+
+// every distinct positive score of the sorted runs pos[0, P) and neg[0, Nn) as a threshold; the class's threshold and its
+// (TP, FP, FN, TN) written by thread 0
+__device__ void met_operating(const unsigned* pos, int P, const unsigned* neg, int Nn, const OpSpec& sp, OpBest* s_best, int c,
+                              float* thresholds, long long* counts) {
+    OpBest b{-1.0, 0u, 0, 0};
+    for (int j = threadIdx.x; j < P; j += kMetThreads) {
+        const unsigned t = pos[j];
+        if (j > 0 && pos[j - 1] == t) continue;            // the first of equal positives: met_bound(pos, P, t, false) == j
+        OpBest x;
+        x.tp = P - j;
+        x.fp = Nn - met_bound(neg, Nn, t, false);
+        if (sp.crit == ACX_OP_FBETA) {
+            x.f = op_fbeta(sp, x.tp, P - x.tp, x.fp);
+            x.rank = t;
+        } else if (sp.crit == ACX_OP_PRECISION) {
+            x.f = (double)x.tp / (double)(x.tp + x.fp) >= sp.param ? 0.0 : -1.0;
+            x.rank = ~t;
+        } else {
+            x.f = (double)x.tp / (double)P >= sp.param ? 0.0 : -1.0;
+            x.rank = t;
+        }
+        if (op_better(x, b)) b = x;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        OpBest o;
+        o.f = __shfl_xor(b.f, d);
+        o.rank = __shfl_xor(b.rank, d);
+        o.tp = __shfl_xor(b.tp, d);
+        o.fp = __shfl_xor(b.fp, d);
+        if (op_better(o, b)) b = o;
+    }
+    if (__lane_id() == 0) s_best[threadIdx.x >> 6] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < kMetWaves; ++i)
+            if (op_better(s_best[i], b)) b = s_best[i];
+        long long* o = counts + (long long)c * 4;
+        if (b.f >= 0.0) {
+            const unsigned key = sp.crit == ACX_OP_PRECISION ? ~b.rank : b.rank;
+            thresholds[c] = __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);      // key 0x80000000 -> +0.0
+            o[0] = b.tp; o[1] = b.fp; o[2] = P - b.tp; o[3] = Nn - b.fp;
+        } else {                                            // no positives, or a precision no threshold reaches: never fires
+            thresholds[c] = INFINITY;
+            o[0] = 0; o[1] = 0; o[2] = P; o[3] = Nn;
+        }
+    }
+}
+
+__device__ __forceinline__ bool op_failed(const int* status, int c, float* thresholds, long long* counts) {
+    if (*status == 0) return false;
+    if (threadIdx.x < 4) counts[(long long)c * 4 + threadIdx.x] = -1;
+    if (threadIdx.x == 0) thresholds[c] = __builtin_nanf("");
+    return true;
+}
+
+// N <= kMetLdsKeys: both runs in LDS (dynamic, n keys)
+__global__ __launch_bounds__(kMetThreads) void operating_lds_kernel(const unsigned* __restrict__ keys,
+                                                                    const unsigned char* __restrict__ labs, int n,
+                                                                    const int* status, OpSpec sp, float* thresholds,
+                                                                    long long* counts) {
+    extern __shared__ unsigned s_k[];
+    __shared__ int s_cnt[2];
+    __shared__ OpBest s_best[kMetWaves];
+    const int c = blockIdx.x;
+    if (op_failed(status, c, thresholds, counts)) return;
+    const int P = met_split(keys + (long long)c * n, labs + (long long)c * n, n, s_k, s_cnt);
+    const int Nn = n - P;
+    // the positives, then the negatives, each through the network met_global_sort runs on a chunk (metrics_lds_kernel keeps its
+    // own loop over both runs at once, and with it its code)
+    if (P > 1) met_lds_network(s_k, P, 2, met_pow2(P));
+    if (Nn > 1) met_lds_network(s_k + P, Nn, 2, met_pow2(Nn));
+    met_operating(s_k, P, s_k + P, Nn, sp, s_best, c, thresholds, counts);
+}
+
+// N > kMetLdsKeys: the runs of class c in runs[c][0, n) of the workspace, as metrics_global_kernel sorts them
+__global__ __launch_bounds__(kMetThreads) void operating_global_kernel(const unsigned* __restrict__ keys,
+                                                                       const unsigned char* __restrict__ labs, int n,
+                                                                       unsigned* runs, const int* status, OpSpec sp,
+                                                                       float* thresholds, long long* counts) {
+    extern __shared__ unsigned s_k[];
+    __shared__ int s_cnt[2];
+    __shared__ OpBest s_best[kMetWaves];
+    const int c = blockIdx.x;
+    if (op_failed(status, c, thresholds, counts)) return;
+    unsigned* g = runs + (long long)c * n;
+    const int P = met_split(keys + (long long)c * n, labs + (long long)c * n, n, g, s_cnt);
+    const int Nn = n - P;
+    met_gsync();
+    met_global_sort(g, P, s_k);
+    met_global_sort(g + P, Nn, s_k);
+    met_operating(g, P, g + P, Nn, sp, s_best, c, thresholds, counts);
+}
+
+// ---- counts at given thresholds -------------------------------------------------------------------------------------------
+
+constexpr int kThrRows = 256;                     // rows per workgroup: 64 classes x 4 rows per pass, 256 threads
+
+// acc[c] = (TP, FP, P, -) of score >= thresholds[c] over the rows of this workgroup, added with integer atomics: any order gives
+// the same sums.  Rows are read as coalesced lines of 64 classes.  Invalid inputs are ORed into *status.
+__global__ __launch_bounds__(256) void threshold_counts_kernel(const float* __restrict__ scores, long long ld_s,
+                                                               const void* __restrict__ target, int u8, long long ld_t, int n,
+                                                               int C, const float* __restrict__ thresholds,
+                                                               unsigned long long* acc, int* status) {
+    __shared__ int s_part[4][3][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int c = blockIdx.y * 64 + tx;
+    const long long r0 = (long long)blockIdx.x * kThrRows;
+    const long long r1 = r0 + kThrRows < n ? r0 + kThrRows : n;
+    int bad = 0, tp = 0, fp = 0, p = 0;
+    if (c < C) {
+        const float th = thresholds[c];
+        if (th != th) bad |= ACX_METRICS_BAD_THRESHOLD;
+        for (long long r = r0 + ty; r < r1; r += 4) {
+            const float v = scores[r * ld_s + c];
+            if ((__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) bad |= ACX_METRICS_NONFINITE;
+            bool l;
+            if (u8) {
+                const unsigned char t = static_cast<const unsigned char*>(target)[r * ld_t + c];
+                if (t > 1) bad |= ACX_METRICS_BAD_TARGET;
+                l = t != 0;
+            } else {
+                const float t = static_cast<const float*>(target)[r * ld_t + c];
+                if (!(t == 0.0f || t == 1.0f)) bad |= ACX_METRICS_BAD_TARGET;
+                l = t == 1.0f;
+            }
+            const bool fire = v >= th;                     // float32 order: -0.0 == +0.0, nothing finite reaches +inf
+            tp += fire && l;
+            fp += fire && !l;
+            p += l;
+        }
+    }
+    s_part[ty][0][tx] = tp; s_part[ty][1][tx] = fp; s_part[ty][2][tx] = p;
+    __syncthreads();
+    if (ty < 3 && c < C) {                                 // wave ty adds quantity ty of its 64 classes
+        const int v = s_part[0][ty][tx] + s_part[1][ty][tx] + s_part[2][ty][tx] + s_part[3][ty][tx];
+        if (v) atomicAdd(&acc[(long long)c * 4 + ty], (unsigned long long)v);
+    }
+    const int bits = (__ballot(bad & ACX_METRICS_NONFINITE) ? ACX_METRICS_NONFINITE : 0) |
+                     (__ballot(bad & ACX_METRICS_BAD_TARGET) ? ACX_METRICS_BAD_TARGET : 0) |
+                     (__ballot(bad & ACX_METRICS_BAD_THRESHOLD) ? ACX_METRICS_BAD_THRESHOLD : 0);
+    if (__lane_id() == 0 && bits) atomicOr(status, bits);
+}
+
+// (TP, FP, P, -) -> (TP, FP, FN, TN), or four -1 on a data error
+__global__ __launch_bounds__(256) void threshold_finish_kernel(long long* counts, int n, int C, const int* status) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    long long* o = counts + (long long)c * 4;
+    if (*status) {
+        o[0] = -1; o[1] = -1; o[2] = -1; o[3] = -1;
+    } else {
+        const long long tp = o[0], fp = o[1], p = o[2];
+        o[2] = p - tp;
+        o[3] = ((long long)n - p) - fp;
+    }
+}
+
 // keys, labels and (N > kMetLdsKeys) the global runs, each 256-byte aligned
 static void met_layout(long long n, long long C, size_t* keys_off, size_t* labs_off, size_t* runs_off, size_t* total) {
     const size_t kb = align_up((size_t)n * C * 4), lb = align_up((size_t)n * C);
@@ -303,6 +497,45 @@ static int met_check_shape(int64_t n, int classes) {
     if (n < 1) ACX_FAIL(ACX_ERR_ARG, "tagging metrics: n = %lld (expected >= 1)", (long long)n);
     if (classes < 1) ACX_FAIL(ACX_ERR_ARG, "tagging metrics: %d classes (expected >= 1)", classes);
     if (n > kMetMaxN) ACX_FAIL(ACX_ERR_UNSUPPORTED, "tagging metrics: n = %lld (at most 2^30 rows)", (long long)n);
+    return ACX_OK;
+}
+
+// what the sorting calls share: the argument checks, the cleared status word and the keys / labels of the workspace
+struct MetPrep {
+    unsigned* keys;
+    unsigned char* labs;
+    unsigned* runs;
+};
+
+static int met_check_inputs(const char* who, const float* scores, int64_t ld_scores, const void* target, int target_dtype,
+                            int64_t ld_target, int64_t n, int classes, const int32_t* status) {
+    if (!scores || !target || !status) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    if (target_dtype != ACX_TARGET_F32 && target_dtype != ACX_TARGET_U8)
+        ACX_FAIL(ACX_ERR_ARG, "%s: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", who, target_dtype);
+    ACX_TRY(met_check_shape(n, classes));
+    if (ld_scores < classes || ld_target < classes)
+        ACX_FAIL(ACX_ERR_ARG, "%s: row strides %lld / %lld are shorter than %d classes", who, (long long)ld_scores,
+                 (long long)ld_target, classes);
+    return ACX_OK;
+}
+
+static int met_prepare(const char* who, const float* scores, int64_t ld_scores, const void* target, int target_dtype,
+                       int64_t ld_target, int64_t n, int classes, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s,
+                       MetPrep* m) {
+    if (!ws) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    ACX_TRY(met_check_inputs(who, scores, ld_scores, target, target_dtype, ld_target, n, classes, status));
+    size_t koff, loff, roff, need;
+    met_layout(n, classes, &koff, &loff, &roff, &need);
+    ACX_TRY(check_workspace_for(who, ws, ws_bytes, need));
+    char* w = static_cast<char*>(ws);
+    m->keys = reinterpret_cast<unsigned*>(w + koff);
+    m->labs = reinterpret_cast<unsigned char*>(w + loff);
+    m->runs = reinterpret_cast<unsigned*>(w + roff);
+    ACX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    const dim3 pgrid((unsigned)((n + kMetTile - 1) / kMetTile), (unsigned)((classes + kMetTile - 1) / kMetTile));
+    launch_kernel(&metrics_prep_kernel, pgrid, dim3(256), 0, s, scores, (long long)ld_scores, target,
+                  target_dtype == ACX_TARGET_U8 ? 1 : 0, (long long)ld_target, (int)n, classes, m->keys, m->labs, (int*)status);
+    ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
 
@@ -323,26 +556,13 @@ int acx_metrics_workspace_bytes(int64_t n, int classes, size_t* out_bytes) {
 int acx_tagging_metrics(const float* scores, int64_t ld_scores, const void* target, int target_dtype, int64_t ld_target,
                         int64_t n, int classes, double* ap, double* auc, double* dprime, int32_t* status, void* ws,
                         size_t ws_bytes, void* stream) {
-    if (!scores || !target || !ap || !auc || !dprime || !status || !ws)
-        ACX_FAIL(ACX_ERR_ARG, "acx_tagging_metrics: null argument");
-    if (target_dtype != ACX_TARGET_F32 && target_dtype != ACX_TARGET_U8)
-        ACX_FAIL(ACX_ERR_ARG, "acx_tagging_metrics: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", target_dtype);
-    ACX_TRY(met_check_shape(n, classes));
-    if (ld_scores < classes || ld_target < classes)
-        ACX_FAIL(ACX_ERR_ARG, "acx_tagging_metrics: row strides %lld / %lld are shorter than %d classes", (long long)ld_scores,
-                 (long long)ld_target, classes);
-    size_t koff, loff, roff, need;
-    met_layout(n, classes, &koff, &loff, &roff, &need);
-    ACX_TRY(check_workspace_for("acx_tagging_metrics", ws, ws_bytes, need));
+    if (!ap || !auc || !dprime) ACX_FAIL(ACX_ERR_ARG, "acx_tagging_metrics: null argument");
+    MetPrep m;
+    ACX_TRY(met_prepare("acx_tagging_metrics", scores, ld_scores, target, target_dtype, ld_target, n, classes, status, ws, ws_bytes,
+                        (hipStream_t)stream, &m));
     const hipStream_t s = (hipStream_t)stream;
-    char* w = static_cast<char*>(ws);
-    unsigned* keys = reinterpret_cast<unsigned*>(w + koff);
-    unsigned char* labs = reinterpret_cast<unsigned char*>(w + loff);
-    ACX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    const dim3 pgrid((unsigned)((n + kMetTile - 1) / kMetTile), (unsigned)((classes + kMetTile - 1) / kMetTile));
-    launch_kernel(&metrics_prep_kernel, pgrid, dim3(256), 0, s, scores, (long long)ld_scores, target,
-                  target_dtype == ACX_TARGET_U8 ? 1 : 0, (long long)ld_target, (int)n, classes, keys, labs, (int*)status);
-    ACX_HIP(hipGetLastError());
+    unsigned* keys = m.keys;
+    unsigned char* labs = m.labs;
     if (n <= kMetLdsKeys) {
         static DeviceOnce once;
         ACX_TRY(set_max_dynamic_lds(once, &metrics_lds_kernel, (size_t)kMetLdsKeys * 4));
@@ -352,9 +572,69 @@ int acx_tagging_metrics(const float* scores, int64_t ld_scores, const void* targ
         static DeviceOnce once;
         ACX_TRY(set_max_dynamic_lds(once, &metrics_global_kernel, (size_t)kMetLdsKeys * 4));
         launch_kernel(&metrics_global_kernel, dim3(classes), dim3(kMetThreads), (size_t)kMetLdsKeys * 4, s, (const unsigned*)keys,
-                      (const unsigned char*)labs, (int)n, reinterpret_cast<unsigned*>(w + roff), (const int*)status, ap, auc,
-                      dprime);
+                      (const unsigned char*)labs, (int)n, m.runs, (const int*)status, ap, auc, dprime);
     }
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int acx_operating_points(const float* scores, int64_t ld_scores, const void* target, int target_dtype, int64_t ld_target,
+                         int64_t n, int classes, const acx_operating_spec* spec, float* thresholds, int64_t* counts,
+                         int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "acx_operating_points";
+    if (!spec || !thresholds || !counts) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    const double v = spec->param;
+    if (spec->criterion == ACX_OP_FBETA) {
+        if (!(v > 0.0) || std::isinf(v)) ACX_FAIL(ACX_ERR_ARG, "%s: beta %g (expected a finite value > 0)", who, v);
+    } else if (spec->criterion == ACX_OP_PRECISION || spec->criterion == ACX_OP_RECALL) {
+        if (!(v > 0.0 && v <= 1.0)) ACX_FAIL(ACX_ERR_ARG, "%s: level %g (expected a value in (0, 1])", who, v);
+    } else {
+        ACX_FAIL(ACX_ERR_ARG, "%s: criterion %d (expected ACX_OP_FBETA, ACX_OP_PRECISION or ACX_OP_RECALL)", who, spec->criterion);
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    MetPrep m;
+    ACX_TRY(met_prepare(who, scores, ld_scores, target, target_dtype, ld_target, n, classes, status, ws, ws_bytes, s, &m));
+    OpSpec sp;
+    sp.crit = spec->criterion;
+    sp.param = v;
+    {
+#pragma clang fp contract(off)       // two roundings, as the host statement has them
+        sp.b2 = v * v;
+        sp.onepb2 = 1.0 + sp.b2;
+    }
+    if (n <= kMetLdsKeys) {
+        static DeviceOnce once;
+        ACX_TRY(set_max_dynamic_lds(once, &operating_lds_kernel, (size_t)kMetLdsKeys * 4));
+        launch_kernel(&operating_lds_kernel, dim3(classes), dim3(kMetThreads), (size_t)n * 4, s, (const unsigned*)m.keys,
+                      (const unsigned char*)m.labs, (int)n, (const int*)status, sp, thresholds,
+                      reinterpret_cast<long long*>(counts));
+    } else {
+        static DeviceOnce once;
+        ACX_TRY(set_max_dynamic_lds(once, &operating_global_kernel, (size_t)kMetLdsKeys * 4));
+        launch_kernel(&operating_global_kernel, dim3(classes), dim3(kMetThreads), (size_t)kMetLdsKeys * 4, s,
+                      (const unsigned*)m.keys, (const unsigned char*)m.labs, (int)n, m.runs, (const int*)status, sp, thresholds,
+                      reinterpret_cast<long long*>(counts));
+    }
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int acx_threshold_counts(const float* scores, int64_t ld_scores, const void* target, int target_dtype, int64_t ld_target,
+                         int64_t n, int classes, const float* thresholds, int64_t* counts, int32_t* status, void* stream) {
+    const char* who = "acx_threshold_counts";
+    if (!thresholds || !counts) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    ACX_TRY(met_check_inputs(who, scores, ld_scores, target, target_dtype, ld_target, n, classes, status));
+    if (classes > 65535 * 64) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: %d classes (at most %d)", who, classes, 65535 * 64);
+    const hipStream_t s = (hipStream_t)stream;
+    ACX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    ACX_HIP(hipMemsetAsync(counts, 0, (size_t)classes * 4 * sizeof(int64_t), s));
+    const dim3 grid((unsigned)((n + kThrRows - 1) / kThrRows), (unsigned)((classes + 63) / 64));
+    launch_kernel(&threshold_counts_kernel, grid, dim3(256), 0, s, scores, (long long)ld_scores, target,
+                  target_dtype == ACX_TARGET_U8 ? 1 : 0, (long long)ld_target, (int)n, classes, thresholds,
+                  reinterpret_cast<unsigned long long*>(counts), (int*)status);
+    ACX_HIP(hipGetLastError());
+    launch_kernel(&threshold_finish_kernel, dim3((classes + 255) / 256), dim3(256), 0, s, reinterpret_cast<long long*>(counts),
+                  (int)n, classes, (const int*)status);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

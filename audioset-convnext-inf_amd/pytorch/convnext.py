@@ -483,14 +483,34 @@ class ConvNeXt(nn.Module):
         table.  Returns forward_segments' dict (segment resolution) plus "events": an EventTable over the batch, decoded from
         "segmentwise_output" with the clip's "segment_edges" (pytorch/segments.py, decode_events_gpu).  decode_args: threshold,
         low, median, min_duration, merge_gap, capacity -- decode_events' arguments; they are checked before the forward runs.
+        threshold / low may hold one value per class (an array, or a CUDA tensor such as metrics.operating_points(...).threshold,
+        whose values are checked on the device when the table is first read).
         Nothing synchronises until the table is read (len(), .to_lists(labels), .check())."""
         if "step" in decode_args or "steps" in decode_args:
             raise TypeError("detect_events takes its boundaries from the clip: step / steps are not arguments")
         _seg.check_event_args(decode_args.get("threshold", 0.5), decode_args.get("low"), decode_args.get("median", 1),
-                              decode_args.get("min_duration", 0.0), decode_args.get("merge_gap", 0.0))
+                              decode_args.get("min_duration", 0.0), decode_args.get("merge_gap", 0.0), classes=self.num_classes)
         out = self.forward_segments(waveform, pool=pool, sample_rate=sample_rate)
         out["events"] = _seg.decode_events_gpu(out["segmentwise_output"], step=out["segment_edges"].numpy(), **decode_args)
         return out
+
+    def tag(self, waveform, threshold, sample_rate=None):
+        """Tags as decisions: one forward, then clipwise_output >= threshold.  threshold: one number, or one per class (an
+        array, or a CUDA tensor such as metrics.operating_points(...).threshold; +inf: the class never fires).  Returns
+        {"labels": bool (B, N), "clipwise_output", "clipwise_logits"}; nothing synchronises."""
+        if isinstance(threshold, torch.Tensor):
+            thr = threshold.detach()
+        else:
+            thr = torch.as_tensor(threshold, dtype=torch.float32)
+        N = self.num_classes
+        if thr.dim() > 1 or (thr.dim() == 1 and thr.shape[0] != N):
+            raise ValueError("threshold of shape %r for %d classes (expected a number or (%d,))" % (tuple(thr.shape), N, N))
+        if not thr.is_cuda and bool(torch.isnan(thr).any()):
+            raise ValueError("threshold holds a NaN")
+        out = self(waveform, sample_rate=sample_rate)
+        probs = out["clipwise_output"]
+        return {"labels": probs >= thr.to(device=probs.device, dtype=probs.dtype), "clipwise_output": probs,
+                "clipwise_logits": out["clipwise_logits"]}
 
     def forward_segment_embeddings(self, x, pool=3, sample_rate=None):
         """(B, L) -> (B, S, 768): the embedding of every 0.32 s segment -- forward_segments' rows in front of the head, i.e.

@@ -97,11 +97,51 @@ def median_filter(p, width):
     return np.median(np.stack([padded[i:i + p.shape[0]] for i in range(width)]), axis=0).astype(p.dtype)
 
 
+def _is_number(v):
+    return np.ndim(v) == 0 and not hasattr(v, "detach")
+
+
+def _host_level(v, p=None):
+    """A threshold / low argument on the host: None and numbers pass as they are; per-class values (array, list, tensor)
+    become a 1-D array in the precision of the probabilities p (float32 without p) -- what the device compares in."""
+    if v is None or _is_number(v):
+        return v
+    a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    if a.dtype == object or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("per-class threshold / low must hold numbers (got dtype %s)" % a.dtype)
+    if a.ndim != 1:
+        raise ValueError("per-class threshold / low must be one-dimensional (got shape %r)" % (a.shape,))
+    kind = p.dtype if p is not None and np.issubdtype(p.dtype, np.floating) else np.float32
+    return a.astype(kind)
+
+
+def _check_levels(threshold, low, classes=None):
+    """0 <= low <= threshold for numbers and host arrays (low already resolved), class by class, with decode_events' message;
+    an array must hold one value per class."""
+    for v in (threshold, low):
+        if np.ndim(v) == 1 and classes is not None and v.shape[0] != classes:
+            raise ValueError("%d per-class values for %d classes" % (v.shape[0], classes))
+    if np.ndim(threshold) == 0 and np.ndim(low) == 0:
+        if not 0.0 <= low <= threshold:
+            raise ValueError("low must be in [0, threshold] (got low=%r, threshold=%r)" % (low, threshold))
+        return
+    if np.ndim(threshold) == 1 and np.ndim(low) == 1 and threshold.shape != low.shape:
+        raise ValueError("%d thresholds and %d lows" % (threshold.shape[0], low.shape[0]))
+    with np.errstate(invalid="ignore"):
+        ok = (np.asarray(low) >= 0.0) & (np.asarray(low) <= np.asarray(threshold))           # a NaN fails both
+    if not np.all(ok):
+        c = int(np.nonzero(~np.broadcast_to(ok, np.broadcast(threshold, low).shape))[0][0])
+        raise ValueError("low must be in [0, threshold] (got low=%r, threshold=%r) in class %d"
+                         % (float(low if np.ndim(low) == 0 else low[c]), float(threshold if np.ndim(threshold) == 0 else threshold[c]), c))
+
+
 def decode_events(probs, threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=0.0, step=SEGMENT_SECONDS, labels=None):
     """Probabilities over time -> events.  probs: (steps, classes), a torch tensor or array -- "segmentwise_output" /
     "framewise_output" of one clip, or a forward_windows timeline.  Per class, after an optional odd `median` filter over time:
     an event is a maximal run of steps with p >= low that holds a value >= threshold (hysteresis; low=None: low = threshold);
     events of a class closer than `merge_gap` seconds are merged, then events shorter than `min_duration` seconds are dropped.
+    threshold / low: one number for every class, or one per class (an array or tensor of `classes` values, e.g.
+    metrics.operating_points(...).threshold; +inf: the class emits nothing), compared in the probabilities' own precision.
     step: seconds per row (0.32 for segments, 0.01 for frames), or the steps + 1 boundaries in seconds ("segment_edges").
     Returns [(class, onset_s, offset_s, peak, mean), ...] sorted by onset; class is labels[c] when labels are given, else c;
     peak / mean are taken over the event's rows of the filtered probabilities."""
@@ -110,9 +150,9 @@ def decode_events(probs, threshold=0.5, low=None, median=1, min_duration=0.0, me
     p = np.asarray(probs)
     if p.ndim != 2:
         raise ValueError("decode_events expects (steps, classes) probabilities, got shape %r" % (p.shape,))
+    threshold, low = _host_level(threshold, p), _host_level(low, p)
     low = threshold if low is None else low
-    if not 0.0 <= low <= threshold:
-        raise ValueError("low must be in [0, threshold] (got low=%r, threshold=%r)" % (low, threshold))
+    _check_levels(threshold, low, p.shape[1])
     if isinstance(median, bool) or not isinstance(median, int) or median < 1 or median % 2 == 0:
         raise ValueError("median must be an odd positive integer (got %r)" % (median,))
     if min_duration < 0 or merge_gap < 0:
@@ -134,10 +174,11 @@ def decode_events(probs, threshold=0.5, low=None, median=1, min_duration=0.0, me
     events = []
     for c in np.nonzero((p >= threshold).any(axis=0))[0]:
         col = p[:, c]
-        on = np.concatenate([[False], col >= low, [False]])
+        thr_c, low_c = (v if np.ndim(v) == 0 else v[c] for v in (threshold, low))
+        on = np.concatenate([[False], col >= low_c, [False]])
         begins = np.nonzero(on[1:] & ~on[:-1])[0]
         ends = np.nonzero(~on[1:] & on[:-1])[0]                 # exclusive
-        runs = [[b, e] for b, e in zip(begins, ends) if col[b:e].max() >= threshold]
+        runs = [[b, e] for b, e in zip(begins, ends) if col[b:e].max() >= thr_c]
         merged = []
         for b, e in runs:
             if merged and edges[b] - edges[merged[-1][1]] < merge_gap:
@@ -158,18 +199,33 @@ def decode_events(probs, threshold=0.5, low=None, median=1, min_duration=0.0, me
 _GPU_EDGES = "only uniform steps with a free last boundary run on the GPU (edges k * step for k < steps, then the clip's end)"
 
 
-def check_event_args(threshold, low, median, min_duration, merge_gap):
-    """decode_events' argument checks and messages, plus the device's cap on `median`.  Returns low with None resolved."""
+def _on_device(v):
+    return hasattr(v, "is_cuda") and v.is_cuda
+
+
+def check_event_args(threshold, low, median, min_duration, merge_gap, classes=None):
+    """decode_events' argument checks and messages, plus the device's cap on `median`.  Returns (threshold, low) with None
+    resolved and per-class host values as float32 arrays.  Per-class CUDA tensors pass unread: their values are checked on the
+    device (ACX_EVENTS_BAD_THRESHOLD, raised when the table is first read), only their length here."""
+    threshold = threshold if _on_device(threshold) else _host_level(threshold)
+    low = low if _on_device(low) else _host_level(low)
     low = threshold if low is None else low
-    if not 0.0 <= low <= threshold:
-        raise ValueError("low must be in [0, threshold] (got low=%r, threshold=%r)" % (low, threshold))
+    for v in (threshold, low):
+        if _on_device(v) and (v.dim() != 1 or (classes is not None and v.shape[0] != classes)):
+            raise ValueError("per-class threshold / low of shape %r for %s classes" % (tuple(v.shape), classes))
+    if not (_on_device(threshold) or _on_device(low)):
+        _check_levels(threshold, low, classes)
+    elif not _on_device(threshold):
+        _check_levels(threshold, 0.0, classes)                      # of a mixed pair, what the host can see: threshold >= 0
+    elif not _on_device(low):
+        _check_levels(low, low, classes)                            # low >= 0
     if isinstance(median, bool) or not isinstance(median, int) or median < 1 or median % 2 == 0:
         raise ValueError("median must be an odd positive integer (got %r)" % (median,))
     if median > _ffi.MAX_EVENT_MEDIAN:
         raise ValueError("median must be at most %d on the GPU (got %r)" % (_ffi.MAX_EVENT_MEDIAN, median))
     if min_duration < 0 or merge_gap < 0:
         raise ValueError("min_duration and merge_gap must not be negative")
-    return low
+    return threshold, low
 
 
 def _uniform_edges(edges, n):
@@ -212,12 +268,16 @@ class EventTable:
         return self.table.shape[0]
 
     def check(self):
-        """Waits for the decoding.  ValueError when the probabilities held a NaN or an infinity; a table that was too small is
-        decoded once more at the exact size.  Returns self."""
+        """Waits for the decoding.  ValueError when the probabilities held a NaN or an infinity, or a per-class threshold / low
+        on the device was not 0 <= low <= threshold; a table that was too small is decoded once more at the exact size (with
+        the same per-class values).  Returns self."""
         if self._n is None:
             n, st = int(self.count.cpu()), int(self.status.cpu())
             if st & _ffi.EVENTS_NONFINITE:
                 raise ValueError("the probabilities hold a NaN or an infinity")
+            if st & _ffi.EVENTS_BAD_THRESHOLD:
+                raise ValueError("low must be in [0, threshold] in every class (a per-class value on the device is out of "
+                                 "order, negative or NaN)")
             if st & _ffi.EVENTS_OVERFLOW or n > self.capacity:
                 if self._rerun is None:
                     raise ValueError("%d events for a table of %d rows" % (n, self.capacity))
@@ -265,9 +325,12 @@ def decode_events_gpu(probs, threshold=0.5, low=None, median=1, min_duration=0.0
     steps=[...].  step: seconds per row, or boundaries as segment_edges gives them ((steps + 1,), or one such array per clip):
     k * step for k < steps and any positive last one; other boundaries raise ValueError.  capacity: rows of the table
     (default max(1024, 16 * clips)); a table that turns out too small is decoded again at the exact size when it is first
-    read.  Runs on the current stream without synchronising.  Returns an EventTable."""
+    read.  threshold / low: numbers, or one value per class -- a host array (checked here, then copied) or a CUDA tensor (used
+    where it is, e.g. metrics.operating_points(...).threshold; checked on the device, ValueError when the table is first read).
+    Runs on the current stream without synchronising.  Returns an EventTable."""
     torch = _torch()
-    low = check_event_args(threshold, low, median, min_duration, merge_gap)
+    scalar_levels = _is_number(threshold) and (low is None or _is_number(low))
+    threshold, low = check_event_args(threshold, low, median, min_duration, merge_gap)
     if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0):
         raise ValueError("capacity must be a non-negative integer (got %r)" % (capacity,))
     # ---- the clips: uniform (B, S, N) or ragged (steps per clip over packed rows)
@@ -308,6 +371,9 @@ def decode_events_gpu(probs, threshold=0.5, low=None, median=1, min_duration=0.0
         raise ValueError("decode_events_gpu needs at least one step and one class per clip (steps %r, %d classes)"
                          % (clip_steps if len(clip_steps) <= 8 else clip_steps[:8] + ["..."], N))
     B = len(clip_steps)
+    for v in (threshold, low):
+        if not _is_number(v) and tuple(v.shape) != (N,):
+            raise ValueError("%d per-class values for %d classes" % (v.shape[0], N))
     # ---- the boundaries: one step and a last boundary per clip
     ends = None
     per_clip = isinstance(step, (list, tuple)) and len(step) > 0 and np.ndim(step[0]) == 1
@@ -363,7 +429,24 @@ def decode_events_gpu(probs, threshold=0.5, low=None, median=1, min_duration=0.0
         uniform_end = 0.0 if ends is None else ends[0]
     elif B > _ffi.MAX_VARLEN_CLIPS:
         raise ValueError("at most %d clips with boundaries of their own per call (got %d)" % (_ffi.MAX_VARLEN_CLIPS, B))
-    params = _ffi.event_params(threshold, low, median, min_duration, merge_gap)
+    if scalar_levels:
+        params = _ffi.event_params(threshold, low, median, min_duration, merge_gap)
+        thr_t = low_t = None
+    else:
+        # per class (acx_decode_events_classwise): a device pointer replaces the field of the same name
+        def level(v):
+            if _is_number(v):
+                return None
+            t = v.detach().to(device=dev, dtype=torch.float32).contiguous() if _on_device(v) else torch.from_numpy(v).to(dev)
+            if tuple(t.shape) != (N,):
+                raise ValueError("%d per-class values for %d classes" % (t.numel(), N))
+            return t
+        thr_t = level(threshold)
+        low_t = None if low is threshold else level(low)            # low=None: the class's own threshold
+        if low_t is None and thr_t is not None and low is not threshold:      # a number beside per-class thresholds
+            low_t = torch.full((N,), float(low), dtype=torch.float32, device=dev)
+        params = _ffi.event_params(threshold if thr_t is None else 0.0, low if _is_number(low) else 0.0, median, min_duration,
+                                   merge_gap)
     cap0 = max(1024, 16 * B) if capacity is None else capacity
 
     def run(cap):
@@ -372,17 +455,18 @@ def decode_events_gpu(probs, threshold=0.5, low=None, median=1, min_duration=0.0
             meta = torch.zeros(4, dtype=torch.int32, device=dev)
             count, status = meta[:2].view(torch.int64), meta[2:3]
             ws = torch.empty(_ffi.events_workspace_bytes(B, N), dtype=torch.uint8, device=dev)
+            tail = (table.data_ptr(), cap, count.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _ffi.stream_ptr(dev))
+            if not scalar_levels:               # (this closure keeps thr_t / low_t alive: the re-run reads them again)
+                tail += (None if thr_t is None else thr_t.data_ptr(), None if low_t is None else low_t.data_ptr())
+            which = "" if scalar_levels else "_classwise"
             if uniform_end is not None:
-                _ffi.check(_ffi.lib().acx_decode_events(x.data_ptr(), ld, B, clip_steps[0], N, ctypes.byref(params), step_s,
-                                                        uniform_end, table.data_ptr(), cap, count.data_ptr(), status.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), _ffi.stream_ptr(dev)))
+                _ffi.check(getattr(_ffi.lib(), "acx_decode_events" + which)(x.data_ptr(), ld, B, clip_steps[0], N,
+                                                                            ctypes.byref(params), step_s, uniform_end, *tail))
             else:
                 c_steps = (ctypes.c_int * B)(*clip_steps)
                 c_ends = None if ends is None else (ctypes.c_double * B)(*ends)
-                _ffi.check(_ffi.lib().acx_decode_events_varlen(x.data_ptr(), ld, c_steps, c_ends, B, N, ctypes.byref(params),
-                                                               step_s, table.data_ptr(), cap, count.data_ptr(),
-                                                               status.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                               _ffi.stream_ptr(dev)))
+                _ffi.check(getattr(_ffi.lib(), "acx_decode_events_varlen" + which)(x.data_ptr(), ld, c_steps, c_ends, B, N,
+                                                                                   ctypes.byref(params), step_s, *tail))
         return table, count, status
 
     return EventTable(*run(cap0), edges=edges, classes=N, rerun=run)

@@ -5,6 +5,7 @@ load / resample / pad a WAV, three forwards, labels above the 0.25 threshold).
     python demo_convnext.py --ckpt checkpoints/model.safetensors --wav clip.wav --labels metadata/class_labels_indices.csv
     python demo_convnext.py --synthetic-weights --wav clip.wav        # no checkpoint at hand: seeded weights
     python demo_convnext.py --wav clip.wav --sed --top 10              # sound event detection: WHEN the top classes happen
+    python demo_convnext.py --ckpt my_tagger/model.safetensors --wav clip.wav --thresholds my_tagger.thresholds.npy
 
 Prints the same lines as the reference (`# params`, sizes, predicted label indices, names, embedding shapes).
 """
@@ -33,6 +34,8 @@ def main():
     ap.add_argument("--wav", required=True)
     ap.add_argument("--labels", default=os.path.join(ROOT, "metadata", "class_labels_indices.csv"))
     ap.add_argument("--threshold", type=float, default=0.25)
+    ap.add_argument("--thresholds", help=".npy of one threshold per class (demo_finetune.py writes one, metrics.operating_points "
+                                         "computes them): used in place of --threshold for the labels and for --sed")
     ap.add_argument("--sed", action="store_true", help="also print the top classes by maximum framewise probability and their "
                                                        "events (the reference's sound_event_detection, inference.py:96-200)")
     ap.add_argument("--top", type=int, default=10, help="--sed: how many classes")
@@ -71,8 +74,17 @@ def main():
     print("logits size:", logits.size())
     print("probs size:", probs.size())
 
-    sample_labels = np.where(probs[0].clone().detach().cpu() > args.threshold)[0]
-    print("Predicted labels using activity threshold %.2f:\n" % args.threshold)
+    per_class = None
+    if args.thresholds:
+        per_class = np.load(args.thresholds).astype(np.float32)
+        if per_class.shape != (probs.shape[1],):
+            sys.exit("%s holds %s thresholds, the model has %d classes" % (args.thresholds, per_class.shape, probs.shape[1]))
+        with torch.no_grad():
+            sample_labels = np.where(model.tag(waveform, per_class)["labels"][0].cpu())[0]      # probs >= threshold, per class
+        print("Predicted labels using the per-class thresholds of %s:\n" % os.path.basename(args.thresholds))
+    else:
+        sample_labels = np.where(probs[0].clone().detach().cpu() > args.threshold)[0]
+        print("Predicted labels using activity threshold %.2f:\n" % args.threshold)
     print(sample_labels)
     # the reference reads metadata/class_labels_indices.csv (demo_convnext.py:29, utilities.py:195-216); without that file the
     # packaged copy of the same table names the classes.  A fine-tuned head (N != 527 classes) prints indices unless the table
@@ -98,7 +110,8 @@ def main():
         print("\nSound event detection, framewise_output shape:", framewise.shape)
         ranked = np.argsort(np.max(framewise, axis=0))[::-1][:args.top]              # inference.py:165-168
         name = lambda c: ix_to_lb[c] if ix_to_lb else "class %d" % c
-        events = segments.decode_events(sed["segmentwise_output"][0], threshold=args.threshold, step=sed["segment_edges"].numpy())
+        events = segments.decode_events(sed["segmentwise_output"][0], threshold=args.threshold if per_class is None else per_class,
+                                        step=sed["segment_edges"].numpy())
         for c in ranked:
             print("%s: max %.3f" % (name(c), framewise[:, c].max()))
             for _, on, off, peak, mean in [e for e in events if e[0] == c]:

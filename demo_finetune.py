@@ -8,13 +8,16 @@ as a checkpoint that ConvNeXt.from_pretrained loads as an N-class model.
     python demo_finetune.py --synthetic --out /tmp/tagger                      # seeded weights and clips, no files needed
 
 Writes <out>/model.safetensors, <out>/model.pth ({"model": state_dict}) and <out>/labels.txt (one class name per line, in head
-order).  16-bit PCM WAV files at any rate (resampled on the device)."""
+order).  With a validation split, one decision threshold per class is chosen on it (the largest F1, metrics.operating_points)
+and written next to <out> as <out>.thresholds.npy -- demo_convnext.py --thresholds takes it.  16-bit PCM WAV files at any rate
+(resampled on the device)."""
 import argparse
 import csv
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -121,6 +124,21 @@ def main():
     print("extraction %.2f s (%.0f clips/s), fit %.2f s (%d steps%s)" % (t1 - t0, len(waves) / (t1 - t0), t2 - t1, fit.loss.numel(),
                                                                            ", validation included" if n_val else ""))
 
+    thresholds = None
+    if n_val:
+        # one threshold per class, chosen where the labels are: the largest F1 on the validation split
+        import warnings
+        from audioset_convnext_inf_amd.pytorch.metrics import operating_points
+        head = model.head_audioset
+        with torch.no_grad():
+            probs = torch.sigmoid(torch.addmm(head.bias, emb[va], head.weight.t()))
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)          # classes the split holds no positive of: counted below
+            op = operating_points(target[va], probs, criterion="f1")
+        thresholds = op.threshold.cpu().numpy()
+        print("val F1 at per-class thresholds: macro %.3f  micro %.3f  (mAP %.3f; %d of %d classes without a positive never fire)"
+              % (op.macro()["f"], op.micro()["f"], fit.history[-1]["mAP"], int(np.isinf(thresholds).sum()), len(names)))
+
     os.makedirs(a.out, exist_ok=True)
     sd = {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}
     torch.save({"model": sd}, os.path.join(a.out, "model.pth"))
@@ -128,6 +146,10 @@ def main():
     save_file(sd, os.path.join(a.out, "model.safetensors"))
     with open(os.path.join(a.out, "labels.txt"), "w") as f:
         f.write("\n".join(names) + "\n")
+    if thresholds is not None:
+        thr_path = a.out.rstrip("/" + os.sep) + ".thresholds.npy"
+        np.save(thr_path, thresholds)
+        print("wrote %s: %d per-class thresholds (demo_convnext.py --thresholds)" % (thr_path, len(thresholds)))
     print("wrote %s: model.safetensors, model.pth, labels.txt -- ConvNeXt.from_pretrained(%r) loads it as a %d-class model"
           % (a.out, os.path.join(a.out, "model.safetensors"), len(names)))
 

@@ -305,6 +305,22 @@ ACX_API int acx_decode_events_varlen(const float* probs, int64_t ld, const int* 
                                      const double* end_seconds /* HOST, B, or NULL */, int B /* <= ACX_MAX_VARLEN_CLIPS */, int N,
                                      const acx_event_params* p, double step_seconds, acx_event* events, int64_t capacity,
                                      int64_t* count, int* status, void* ws, size_t ws_bytes, void* stream);
+/* The same two calls with one threshold and one low per class (the reference's pytorch/inference.py cuts every class at one
+ * fixed 0.5-style constant): threshold / low are DEVICE fp32 [N], e.g. acx_operating_points' output.  A pointer that is given
+ * replaces the field of the same name of *p, which is then ignored; low == NULL with threshold given means low = threshold per
+ * class; with both NULL the calls are acx_decode_events / _varlen.  Values on the device cannot be checked on the host: the
+ * count pass sets ACX_EVENTS_BAD_THRESHOLD in *status when any class has !(0 <= low <= threshold) (a NaN included; +inf is
+ * legal: the class emits nothing), and then *count = 0 and nothing is written, as with ACX_EVENTS_NONFINITE.  The scalar fields
+ * still in use are checked on the host as before. */
+#define ACX_EVENTS_BAD_THRESHOLD 4
+ACX_API int acx_decode_events_classwise(const float* probs, int64_t ld, int64_t B, int steps, int N, const acx_event_params* p,
+                                        double step_seconds, double end_seconds, acx_event* events, int64_t capacity,
+                                        int64_t* count, int* status, void* ws, size_t ws_bytes, void* stream,
+                                        const float* threshold /* device [N] or NULL */, const float* low /* device [N] or NULL */);
+ACX_API int acx_decode_events_varlen_classwise(const float* probs, int64_t ld, const int* steps, const double* end_seconds, int B,
+                                               int N, const acx_event_params* p, double step_seconds, acx_event* events,
+                                               int64_t capacity, int64_t* count, int* status, void* ws, size_t ws_bytes,
+                                               void* stream, const float* threshold, const float* low);
 
 /* ---- live streams: tagging recordings that arrive chunk by chunk ----------------------------------------------------------
  * No reference counterpart.  A handle has `slots`; each slot holds one recording at a time.  Samples pushed to a slot are
@@ -488,6 +504,41 @@ ACX_API int acx_metrics_workspace_bytes(int64_t n, int classes, size_t* out_byte
 ACX_API int acx_tagging_metrics(const float* scores, int64_t ld_scores, const void* target, int target_dtype,
                                 int64_t ld_target, int64_t n, int classes, double* ap, double* auc, double* dprime,
                                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- operating points: one decision threshold per class, chosen and scored on the device ------------------------------------
+ * The reference decides with fixed cut-offs (pytorch/inference.py thresholds its outputs with 0.5-style constants for every
+ * class); choosing a threshold per class on a labelled set is otherwise sklearn.metrics.precision_recall_curve looped over the
+ * classes on the host.  The decision rule everywhere is score >= threshold, float32, -0.0 == +0.0 (the decoder's p >= thr and
+ * the convention of sklearn's PR curve).  For class c with P positives and Nn negatives the CANDIDATES are the distinct scores
+ * of its positives -- any other threshold is dominated: raising it to the next positive score keeps TP and cannot raise FP --
+ * and for a candidate t:  TP = P - #pos(< t),  FP = Nn - #neg(< t),  FN = P - TP,  TN = Nn - FP.
+ *   ACX_OP_FBETA (param = beta > 0, finite): the candidate with the largest F, float64, every operation rounded on its own (no
+ *     fused multiply-add):  b2 = beta * beta;  num = (1 + b2) * TP;  den = (num + b2 * FN) + FP;  F = num / den.  Among equal F
+ *     the highest threshold.
+ *   ACX_OP_PRECISION (param = p in (0, 1]): the lowest candidate with (double)TP / (double)(TP + FP) >= p: the most recall at
+ *     that precision.
+ *   ACX_OP_RECALL (param = r in (0, 1]): the highest candidate with (double)TP / (double)P >= r.
+ *   No qualifying candidate (no positives, or a precision that no candidate reaches): threshold +inf, counts (0, 0, P, Nn) -- the
+ *   class never fires.  A zero threshold is returned as +0.0.
+ * pytorch/metrics.py::operating_points_host states the same in numpy float64; the device equals it bit for bit.
+ *   acx_operating_points: inputs, workspace (acx_metrics_workspace_bytes), argument errors, status bits and launch contract of
+ *     acx_tagging_metrics (a 4-byte clear and two kernels on `stream`, capturable, no context; the same bits on every call);
+ *     spec is read on the host; ACX_ERR_ARG for an unknown criterion or a param outside its range.  thresholds: device fp32
+ *     [classes]; counts: device int64 [classes][4] = TP, FP, FN, TN.  On a data error every threshold is NaN, every count -1.
+ *   acx_threshold_counts: TP, FP, FN, TN of score >= thresholds[c] (device fp32 [classes], +-inf allowed) on any (n, classes)
+ *     scores and targets -- thresholds picked on a validation split scored on a test split.  No workspace, no sort: two clears,
+ *     one counting kernel (integer sums combined by integer atomics: the same result in any order) and one finishing kernel on
+ *     `stream`, capturable.  A NaN threshold sets ACX_METRICS_BAD_THRESHOLD; on any data error every count is -1. */
+enum acx_operating_criterion { ACX_OP_FBETA = 0, ACX_OP_PRECISION = 1, ACX_OP_RECALL = 2 };
+typedef struct acx_operating_spec { int32_t criterion; double param; } acx_operating_spec;
+#define ACX_METRICS_BAD_THRESHOLD 4
+ACX_API int acx_operating_points(const float* scores, int64_t ld_scores, const void* target, int target_dtype,
+                                 int64_t ld_target, int64_t n, int classes, const acx_operating_spec* spec,
+                                 float* thresholds /* [classes] */, int64_t* counts /* [classes][4] = TP, FP, FN, TN */,
+                                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_threshold_counts(const float* scores, int64_t ld_scores, const void* target, int target_dtype,
+                                 int64_t ld_target, int64_t n, int classes, const float* thresholds /* device, [classes] */,
+                                 int64_t* counts /* [classes][4] */, int32_t* status, void* stream);
 
 /* ---- fitting a classifier head on frozen scene embeddings -----------------------------------------------------------------
  * The reference fine-tunes with the whole model in train mode (pytorch/finetune_audiocaps.py: base frozen, BCELoss on
