@@ -155,6 +155,8 @@ SIGNATURES = {
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
     "acx_test_fail_sub": (_c_int, [_vp, _c_int]),
+    "acx_test_stage_tail": (_c_int, [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_sz, _vp]),
+    "acx_test_stage_tail_scratch_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_profile_enable": (_c_int, [_vp, _c_int]),
     "acx_profile_read": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64)]),
 }

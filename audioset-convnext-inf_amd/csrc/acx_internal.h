@@ -465,6 +465,8 @@ inline BlockScratch carve_block_scratch(size_t pix, int C, size_t off) {
 // only the depthwise conv needs the per-clip tables
 int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, int B, int H, int Wd, hipStream_t st,
               void* ln_out = nullptr, const VarGeom* vg = nullptr);
+// the last block of stage s can write the downsample conv's operand rows (ln_out) instead of x
+bool block_can_emit_ln(const acx_ctx* c, int s);
 // have_ln: xnorm already holds the normalised S16 rows (written by the last block of the previous stage)
 // out_bf16: the result is the bf16 activation tensor of stage i (ACX_PREC_BF16_ACT inside acx_forward; the per-layer entry
 // point keeps fp32)

@@ -266,6 +266,55 @@ int acx_test_fail_sub(acx_ctx* c, int sub) {
     return ACX_OK;
 }
 
+// Scratch of acx_test_stage_tail: the block scratch of the stage, then a bf16 image of x and one of the downsample's output (the
+// storage types of ACX_PREC_BF16_ACT; sized whatever the precision: the size call has no context).
+struct TailScratch { BlockScratch blk; size_t xb, outb, end; };
+static TailScratch carve_tail_scratch(int stage, size_t B, size_t H, size_t Wd) {
+    TailScratch t;
+    const size_t pix = B * H * Wd;
+    t.blk = carve_block_scratch(pix, kDims[stage], 0);
+    size_t off = t.blk.end;
+    t.xb = off; off += align_up(pix * kDims[stage] * 2);
+    t.outb = off; off += align_up(B * (H / 2) * (Wd / 2) * kDims[stage + 1] * 2);
+    t.end = off;
+    return t;
+}
+
+int acx_test_stage_tail_scratch_bytes(int stage, int B, int H, int Wd, size_t* out_bytes) {
+    if (!out_bytes || stage < 0 || stage > 2 || B <= 0 || H <= 0 || Wd <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_stage_tail_scratch_bytes: bad argument");
+    *out_bytes = carve_tail_scratch(stage, (size_t)B, (size_t)H, (size_t)Wd).end;
+    return ACX_OK;
+}
+
+int acx_test_stage_tail(acx_ctx* c, int stage, float* x, float* out, int B, int H, int Wd, void* scratch, size_t scratch_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (stage < 0 || stage > 2) ACX_FAIL(ACX_ERR_ARG, "acx_test_stage_tail: stage %d (expected 0..2)", stage);
+    if (!x || !out || !scratch || B <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_stage_tail: bad argument");
+    if (Wd != (kStemW >> stage)) ACX_FAIL(ACX_ERR_SHAPE, "stage %d has width %d, got %d", stage, kStemW >> stage, Wd);
+    if (H < 2) ACX_FAIL(ACX_ERR_SHAPE, "acx_test_stage_tail: kernel size can't be greater than actual input size (%dx%d)", H, Wd);
+    const TailScratch t = carve_tail_scratch(stage, (size_t)B, (size_t)H, (size_t)Wd);
+    if (scratch_bytes < t.end || ((uintptr_t)scratch & 255)) ACX_FAIL(ACX_ERR_WORKSPACE, "acx_test_stage_tail: scratch too small (%zu < %zu) or misaligned", scratch_bytes, t.end);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)scratch;
+    float* y = (float*)(ws + t.blk.y);
+    float* hidden = (float*)(ws + t.blk.hidden);
+    float* stats = (float*)(ws + t.blk.stats);
+    const int last = kDepths[stage] - 1;
+    // as run_forward: the LayerNorm rows go to `hidden`; without them the downsample normalises x into y
+    const bool have_ln = block_can_emit_ln(c, stage);
+    float* xs = x;
+    if (act_bf16(c, stage)) {       // the stage's x as stored: bf16, in a region of its own (`hidden` takes the LayerNorm rows here)
+        xs = (float*)(ws + t.xb);
+        ACX_TRY(launch_convert_f32_to_bf16(x, xs, (long long)B * H * Wd * kDims[stage], st));
+    }
+    ACX_TRY(run_block(c, stage, last, xs, y, hidden, stats, B, H, Wd, st, have_ln ? (void*)hidden : nullptr));
+    const bool ob = act_bf16(c, stage + 1);
+    float* os = ob ? (float*)(ws + t.outb) : out;
+    ACX_TRY(run_downsample(c, stage + 1, xs, os, have_ln ? hidden : y, B, H, Wd, st, have_ln, ob));
+    if (ob) return launch_convert_bf16_to_f32(os, out, (long long)B * (H / 2) * (Wd / 2) * kDims[stage + 1], st);
+    return ACX_OK;
+}
+
 int acx_profile_enable(acx_ctx* c, int on) {
     if (!c) ACX_FAIL(ACX_ERR_ARG, "null context");
     c->prof.on = on != 0;

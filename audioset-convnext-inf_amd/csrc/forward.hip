@@ -112,7 +112,7 @@ static int run_mlp_split(acx_ctx* c, const BlockW& bw, int C, float* y, float* x
 
 // True when the last block of stage s hands the downsample conv its LayerNorm'ed operand rows (S16 / bf16) directly: the fused
 // MLP kernels of stages 0-2 in the 16-bit arithmetics (LNOUT epilogue).  x of that stage is then NOT updated by its last block.
-static bool block_can_emit_ln(const acx_ctx* c, int s) { return s < 3 && c->precision != ACX_PREC_F32; }
+bool block_can_emit_ln(const acx_ctx* c, int s) { return s < 3 && c->precision != ACX_PREC_F32; }
 
 int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, int B, int H, int Wd, hipStream_t st,
               void* ln_out, const VarGeom* vg) {

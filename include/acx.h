@@ -670,6 +670,14 @@ ACX_API int acx_tuning_refresh(void);
  * default; acx_finalize also resets it).  Per context (a process-global switch could poison every other user of the
  * library in the process), a call and not an environment variable.  No reference counterpart. */
 ACX_API int acx_test_fail_sub(acx_ctx* ctx, int sub);
+/* Test support: the tail of stage 0..2 exactly as the forwards queue it -- the stage's LAST block, which in the 16-bit arithmetics
+ * writes LayerNorm(x_new) as the downsample conv's operand rows instead of x (x is then NOT updated: do not read it afterwards),
+ * then downsample_layers[stage + 1] on those rows.  x NHWC (B,H,W,C_stage) fp32, out NHWC (B,H/2,W/2,C_{stage+1}) fp32 whatever
+ * the precision (ACX_PREC_BF16_ACT converts at the boundary, as acx_block does).  scratch >= acx_test_stage_tail_scratch_bytes,
+ * 256-byte aligned.  No other per-layer entry point reaches that epilogue.  No reference counterpart. */
+ACX_API int acx_test_stage_tail(acx_ctx* ctx, int stage, float* x, float* out, int B, int H, int W, void* scratch,
+                        size_t scratch_bytes, void* stream);
+ACX_API int acx_test_stage_tail_scratch_bytes(int stage, int B, int H, int W, size_t* out_bytes);
 
 /* ---- measurement: per-kernel-class device time, HIP events on the launch stream ------------ */
 ACX_API int acx_profile_enable(acx_ctx* ctx, int on);

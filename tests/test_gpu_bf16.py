@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from audioset_convnext_inf_amd import _ffi
 from audioset_convnext_inf_amd.pytorch.convnext import convnext_tiny
+import layer_ref
 import parity_floor
 
 pytestmark = pytest.mark.gpu
@@ -73,25 +74,36 @@ def ln_plain(x, C):
 @pytest.mark.parametrize("rows", [None, 3])
 @pytest.mark.parametrize("s", [0, 1, 2, 3])
 def test_block_bf16(ctx16, model16, taps, synth_sd, s, rows):
-    _block_check(ctx16, model16, taps, synth_sd, s, rows)
-
-
-def _block_check(ctx16, model16, taps, synth_sd, s, rows):
-    from oracle import ref_cpu
-    C = DIMS[s]
-    p = "stages.%d.0." % s
     x0 = taps["ds%d" % s]                                  # NCHW fp32
     if rows is not None:                                   # 3 x W pixels of one clip: not a multiple of any kernel's row tile
         x0 = x0[:1, :, :rows, :].contiguous()
-    x_in = x0
-    act = model16.precision == "bf16a" and s < 3           # stored tensors of this stage are bf16: x in, y, x out
+    _block_check(ctx16, model16, synth_sd, s, 0, x0, taps["s%d.b0.out" % s] if rows is None else None)
+
+
+# the block shapes of tests/test_gpu_layer_shapes.py (tests/layer_ref.py) -- pixel counts just below, at and just above the 64- / 128- / 256-row tiles --
+# without its (5, 263) cases: these kernels are not persistent across more tiles than CUs
+@pytest.mark.parametrize("s,B,H", [(s, B, H) for s in range(4) for B, H in layer_ref.BLOCK_SHAPES[s]])
+def test_block_bf16_tile_shapes(ctx16, model16, synth_sd, s, B, H):
+    """Block 1 of every stage on seeded inputs (first and last pixel constant) against the same emulation at the same bars."""
+    x0 = layer_ref.nchw(layer_ref.seeded_input(s, B, H, seed=700 + 100 * s + 7 * B + H))
+    _block_check(ctx16, model16, synth_sd, s, 1, x0)
+
+
+def _block_emulation(precision, synth_sd, s, j, x0, store=True, acc=torch.float64):
+    """Block j of stage s on x0 (NCHW fp32) in the arithmetic of the bf16 block kernels -> NHWC float64.  store=False: the block's
+    result BEFORE it is stored (the last block of a stage hands it to the LayerNorm-rows epilogue in registers).  acc: the type the
+    two matrix products accumulate in (float32: a stand-in for the device's accumulation, for sizing rounding-boundary flips)."""
+    from oracle import ref_cpu
+    C = DIMS[s]
+    p = "stages.%d.%d." % (s, j)
+    act = precision == "bf16a" and s < 3                   # stored tensors of this stage are bf16: x in, y, x out
     if act:
         x0 = x0.to(torch.bfloat16).float()                 # what the block reads
     sd_dw = synth_sd
     if act:                                                # the matrix-pipe depthwise kernel multiplies bf16 weights (dwconv_mfma.hip)
         sd_dw = dict(synth_sd)
         sd_dw[p + "dwconv.weight"] = synth_sd[p + "dwconv.weight"].to(torch.bfloat16).float()
-    y = ref_cpu.block_dwconv(sd_dw, s, 0, x0).permute(0, 2, 3, 1)
+    y = ref_cpu.block_dwconv(sd_dw, s, j, x0).permute(0, 2, 3, 1)
     if act:
         y = y.to(torch.bfloat16).float()                   # the depthwise conv's output as stored
     # the arithmetic of the bf16 block kernels (mlp_fused_wide_bf16.hip; stage 3: run_mlp_bf16 in api.hip): folds in
@@ -99,25 +111,34 @@ def _block_check(ctx16, model16, taps, synth_sd, s, rows):
     yn = bf(ln_plain(y, C))
     w1 = bf((synth_sd[p + "pwconv1.weight"].double() * synth_sd[p + "norm.weight"].double()[None, :]).float())
     b1 = synth_sd[p + "pwconv1.bias"].double() + synth_sd[p + "pwconv1.weight"].double() @ synth_sd[p + "norm.bias"].double()
-    h = bf(F.gelu((yn @ w1.T + b1).float()))
+    h = bf(F.gelu(((yn.to(acc) @ w1.T.to(acc)).double() + b1).float()))
     g = synth_sd[p + "gamma"].double()
     w2 = bf((g[:, None] * synth_sd[p + "pwconv2.weight"].double()).float())
-    ref = x0.permute(0, 2, 3, 1).double() + h @ w2.T + g * synth_sd[p + "pwconv2.bias"].double()
-    if act:
+    ref = x0.permute(0, 2, 3, 1).double() + (h.to(acc) @ w2.T.to(acc)).double() + g * synth_sd[p + "pwconv2.bias"].double()
+    if act and store:
         ref = ref.float().to(torch.bfloat16).double()      # ... and what it writes
+    return ref
+
+
+def _block_check(ctx16, model16, synth_sd, s, j, x0, tap_out=None):
+    """Block j of stage s on x0 (NCHW fp32) against the emulation; tap_out: the reference's fp32 output, for the drift."""
+    x_in = x0
+    act = model16.precision == "bf16a" and s < 3
+    ref = _block_emulation(model16.precision, synth_sd, s, j, x0)
 
     x = nhwc(x_in)
     B, H, W, _ = x.shape
     need = ctypes.c_size_t()
     _ffi.check(_ffi.lib().acx_block_scratch_bytes(s, B, H, W, ctypes.byref(need)))
     scratch = torch.empty(need.value, dtype=torch.uint8, device="cuda")
-    _ffi.check(_ffi.lib().acx_block(ctx16.handle, s, 0, _ffi.ptr(x), B, H, W, _ffi.ptr(scratch), need.value, sp()))
+    _ffi.check(_ffi.lib().acx_block(ctx16.handle, s, j, _ffi.ptr(x), B, H, W, _ffi.ptr(scratch), need.value, sp()))
     torch.cuda.synchronize()
+    assert bool(torch.isfinite(x).all())
     d_emu = maxdiff(x, ref)
     # bf16a: a stored value may round the other way when the fp32 sum sits at a rounding boundary -- one bf16 ulp of the result
     assert d_emu < (EMU_TOL if not act else max(EMU_TOL, 2.0 ** -7 * float(ref.abs().max())))
-    if rows is None:
-        d_f32 = maxdiff(x.permute(0, 3, 1, 2), taps["s%d.b0.out" % s])
+    if tap_out is not None:
+        d_f32 = maxdiff(x.permute(0, 3, 1, 2), tap_out)
         print("stage %d: vs bf16 emulation %.3g, vs fp32 tap %.3g" % (s, d_emu, d_f32))
         assert d_f32 < DRIFT_LAYER_TOL
 
@@ -187,14 +208,84 @@ def test_dwconv_matrix_kernel_segmentation_is_invisible(ctx16, model16):
 
 @pytest.mark.parametrize("i", [1, 2, 3])
 def test_downsample_bf16(ctx16, taps, synth_sd, i):
-    Ci, Co = DIMS[i - 1], DIMS[i]
+    out, d_emu = _downsample_check(ctx16, synth_sd, i, taps["stage%d" % (i - 1)])
+    d_f32 = maxdiff(out.permute(0, 3, 1, 2), taps["ds%d" % i])
+    print("downsample %d: vs bf16 emulation %.3g, vs fp32 tap %.3g" % (i, d_emu, d_f32))
+    assert d_f32 < DRIFT_LAYER_TOL
+
+
+@pytest.mark.parametrize("mi", ["2", "4"])
+@pytest.mark.parametrize("B,H", layer_ref.DOWN_SHAPES)
+@pytest.mark.parametrize("i", [1, 2, 3])
+def test_downsample_bf16_tile_shapes(ctx16, synth_sd, monkeypatch, i, B, H, mi):
+    """The downsample shapes of tests/test_gpu_layer_shapes.py (tests/layer_ref.py) (odd heights, 7 .. 1 036 output rows) under the 128- and the 256-row
+    tile of gemm_bf16_kernel (ACX_GEMM_MI = 2 | 4), against the same emulation at the same bar."""
+    x0 = layer_ref.nchw(layer_ref.seeded_input(i - 1, B, H, seed=800 + 100 * i + 7 * B + H))
+    refresh = _ffi.lib().acx_tuning_refresh
+    try:
+        monkeypatch.setenv("ACX_GEMM_MI", mi)
+        refresh()
+        _downsample_check(ctx16, synth_sd, i, x0)
+    finally:
+        monkeypatch.delenv("ACX_GEMM_MI", raising=False)
+        refresh()
+
+
+@pytest.mark.parametrize("B,H", [(1, 10), (3, 6), (2, 37)])
+@pytest.mark.parametrize("s", [0, 1, 2])
+def test_stage_tail_bf16(ctx16, model16, synth_sd, s, B, H):
+    """acx_test_stage_tail in the bf16 arithmetics: the stage's last block writes LayerNorm(x_new) as bf16 rows (row stride
+    pad64(C)) into the hidden scratch instead of x, the downsample GEMM reads them there; under "bf16a" x lives as bf16 in a region
+    of its own beside those rows and the downsample's output is stored as bf16 where the next stage keeps bf16 activations.
+    (i)  Against the emulation of the chain -- _block_emulation without its final store, then _downsample_emulation -- at EMU_TOL
+         once per layer: each layer is held to EMU_TOL on its own above, and what the first leaves (rounding-boundary flips of hidden
+         values) reaches the second through a LayerNorm that divides by a standard deviation of about 1 and a conv whose gain on
+         independent perturbations, sqrt(4C) x |w| with |w| about 0.03, is about 1.  Where the result is STORED as bf16, one bf16
+         step of it, as for the blocks.
+    (ii) Against float64 downsample(block(x)) at the file's drift bar, likewise once per layer."""
+    j = layer_ref.DEPTHS[s] - 1
+    x = layer_ref.seeded_input(s, B, H, seed=900 + 100 * s + 7 * B + H)
+    case = layer_ref.stage_tail_case(synth_sd, layer_ref.to64(synth_sd), s, layer_ref.nchw(x))
+    stored_bf16 = model16.precision == "bf16a" and s + 1 < 3
+    x_new = _block_emulation(model16.precision, synth_sd, s, j, layer_ref.nchw(x), store=False)
+    emu = _downsample_emulation(synth_sd, s + 1, x_new).permute(0, 2, 3, 1)
+    if stored_bf16:
+        emu = emu.float().to(torch.bfloat16).double()
+    W = 56 >> s
+    need = ctypes.c_size_t()
+    _ffi.check(_ffi.lib().acx_test_stage_tail_scratch_bytes(s, B, H, W, ctypes.byref(need)))
+    gx, xd = layer_ref.Guarded.tensor(x)
+    go, out = layer_ref.Guarded.filled((B, H // 2, W // 2, DIMS[s + 1]))
+    gs, scratch = layer_ref.Guarded.scratch(need.value)
+    _ffi.check(_ffi.lib().acx_test_stage_tail(ctx16.handle, s, _ffi.ptr(xd), _ffi.ptr(out), B, H, W, _ffi.ptr(scratch), need.value, sp()))
+    torch.cuda.synchronize()
+    layer_ref.assert_clean(out, gx, go, gs)
+    step = 2.0 ** -7 * float(emu.abs().max()) if stored_bf16 else 0.0
+    d_emu, d_f64 = maxdiff(out, emu), maxdiff(out, case.ref)
+    print("stage tail %d (%d,%d) %s: vs bf16 emulation %.3g (bar %.3g), vs float64 %.3g (bar %.3g)"
+          % (s, B, H, model16.precision, d_emu, max(2 * EMU_TOL, step), d_f64, 2 * DRIFT_LAYER_TOL + step))
+    assert d_emu < max(2 * EMU_TOL, step)
+    assert d_f64 < 2 * DRIFT_LAYER_TOL + step
+    if stored_bf16:
+        assert torch.equal(out, out.to(torch.bfloat16).float())            # what came back are bf16 values
+
+
+def _downsample_emulation(synth_sd, i, x, acc=torch.float64):
+    """downsample_layers[i] on x (NHWC) in the arithmetic of the bf16 kernels -> NCHW float64: LayerNorm in full precision, rows
+    and folded weights rounded to bf16, wide accumulation (acc as in _block_emulation)."""
+    Ci = DIMS[i - 1]
     p = "downsample_layers.%d." % i
-    x0 = taps["stage%d" % (i - 1)]
-    xn = bf(ln_plain(x0.permute(0, 2, 3, 1), Ci)).permute(0, 3, 1, 2)
+    xn = bf(ln_plain(x, Ci)).permute(0, 3, 1, 2)
     cw = synth_sd[p + "1.weight"].double()
     w = bf((cw * synth_sd[p + "0.weight"].double()[None, :, None, None]).float())
     b = synth_sd[p + "1.bias"].double() + (cw * synth_sd[p + "0.bias"].double()[None, :, None, None]).sum(dim=(1, 2, 3))
-    ref = F.conv2d(xn, w, b, stride=2)
+    return F.conv2d(xn.to(acc), w.to(acc), None, stride=2).double() + b[None, :, None, None]
+
+
+def _downsample_check(ctx16, synth_sd, i, x0):
+    """downsample_layers[i] on x0 (NCHW fp32) against the emulation -> (device output NHWC, deviation)."""
+    Co = DIMS[i]
+    ref = _downsample_emulation(synth_sd, i, x0.permute(0, 2, 3, 1))
 
     x = nhwc(x0)
     B, H, W, _ = x.shape
@@ -202,11 +293,10 @@ def test_downsample_bf16(ctx16, taps, synth_sd, i):
     scratch = torch.empty_like(x)
     _ffi.check(_ffi.lib().acx_downsample(ctx16.handle, i, _ffi.ptr(x), _ffi.ptr(out), _ffi.ptr(scratch), B, H, W, sp()))
     torch.cuda.synchronize()
+    assert bool(torch.isfinite(out).all())
     d_emu = maxdiff(out.permute(0, 3, 1, 2), ref)
-    d_f32 = maxdiff(out.permute(0, 3, 1, 2), taps["ds%d" % i])
-    print("downsample %d: vs bf16 emulation %.3g, vs fp32 tap %.3g" % (i, d_emu, d_f32))
-    assert d_emu < EMU_TOL
-    assert d_f32 < DRIFT_LAYER_TOL
+    assert d_emu < EMU_TOL, d_emu
+    return out, d_emu
 
 
 def test_e2e_bf16_drift_on_demo_clip(model16, golden_dir):

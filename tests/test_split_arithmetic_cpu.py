@@ -92,18 +92,8 @@ def test_three_term_product_matches_fp32_matmul_error(K, act_scale):
 
 
 # ---- the GELU of the fused kernels (csrc/split_math.h, third form; DESIGN.md 3a') -------------------------------------------
-def _gelu3_constants():
-    """The five coefficients as the kernels carry them (gelu_k3 in split_math.h): parsed from the source, so the test pins
-    what ships."""
-    import os
-    import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "audioset-convnext-inf_amd", "csrc",
-                            "split_math.h")).read()
-    body = src[src.index("GeluK3 gelu_k3("):]
-    body = body[:body.index("return k;")]
-    c = [float(m) for m in re.findall(r"k\.k[0-4] = (-?[0-9.]+)f \* s;", body)]
-    assert len(c) == 5
-    return c
+# (one restatement of the device form: tests/layer_ref.py, shared with the GPU layer tests)
+from layer_ref import GELU3_K, _gelu3_constants_in_source, _gelu3_fp32          # noqa: E402
 
 
 def _f32(x):
@@ -111,20 +101,10 @@ def _f32(x):
         return np.asarray(x, np.float64).astype(np.float32).astype(np.float64)
 
 
-def _gelu3_fp32(v, kh=1.0):
-    """gelu3_nano step by step, every instruction's result rounded to fp32 (an FMA = one rounding), in the unit z = 0.5 kh v."""
-    h = 0.5 * kh
-    k = [c / h ** (j + 1) for j, c in enumerate(_gelu3_constants())]       # exact: h is a power of two
-    assert all(abs(x) > 2.0 ** -126 and abs(x) < 2.0 ** 127 for x in k)
-    z = _f32(np.asarray(v, np.float64) * h)
-    a = np.abs(z)
-    q = _f32(a * k[4] + k[3])
-    q = _f32(q * a + k[2]); q = _f32(q * a + k[1]); q = _f32(q * a + k[0])
-    with np.errstate(over="ignore", under="ignore", invalid="raise"):
-        q = _f32(q * a)
-        e = _f32(np.exp2(q))
-    r = _f32(1.0 - e)
-    return _f32(a * r + z) / kh
+def test_shipped_gelu3_coefficients_are_the_pinned_ones():
+    """The restatement computes with literals of its own (layer_ref.GELU3_K), so that an edit of gelu_k3 does not move the reference
+    along with the kernel; the header must carry exactly those."""
+    assert _gelu3_constants_in_source() == GELU3_K
 
 
 def test_gelu_third_form_error_bound():
