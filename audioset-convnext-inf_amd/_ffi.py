@@ -138,6 +138,10 @@ SIGNATURES = {
     "acx_tagging_metrics": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_operating_points": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _pops, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_threshold_counts": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp]),
+    "acx_bootstrap_weights": (_c_int, [ctypes.c_uint64, ctypes.c_uint32, _c_int, _c_i64, _vp, _c_i64, _vp]),
+    "acx_weighted_metrics_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_weighted_metrics": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp,
+                                      _c_sz, _vp]),
     "acx_head_fit_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_head_fit_step": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _padam, _c_i64, _c_dbl, _vp, _vp, _vp, _c_sz, _vp]),
@@ -385,7 +389,9 @@ def window_count(lengths, window, hop):
 TARGET_F32, TARGET_U8 = 0, 1                 # enum acx_target_dtype
 METRICS_NONFINITE, METRICS_BAD_TARGET = 1, 2  # bits of acx_tagging_metrics' status word
 METRICS_BAD_THRESHOLD = 4                     # acx_threshold_counts: a NaN threshold
+METRICS_BAD_WEIGHT = 8                        # acx_weighted_metrics: a negative weight, or a weight vector summing above 2^30
 OP_FBETA, OP_PRECISION, OP_RECALL = 0, 1, 2   # enum acx_operating_criterion
+WEIGHTED_MAX_N = 32768                        # acx_weighted_metrics: rows per class (one LDS bucket each)
 
 
 def metrics_workspace_bytes(n, classes):
@@ -413,6 +419,25 @@ def threshold_counts(scores, ld_scores, target, target_dtype, ld_target, n, clas
     """acx_threshold_counts on raw device pointers (ctypes.c_void_p)."""
     check(lib().acx_threshold_counts(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes),
                                      thresholds, counts, status, stream))
+
+
+def bootstrap_weights(seed, first_replicate, replicates, n, weights, ld_w, stream):
+    """acx_bootstrap_weights on a raw device pointer (ctypes.c_void_p)."""
+    check(lib().acx_bootstrap_weights(int(seed), int(first_replicate), int(replicates), int(n), weights, int(ld_w), stream))
+
+
+def weighted_metrics_workspace_bytes(n, classes):
+    """Workspace of acx_weighted_metrics for n rows of `classes` scores (host only)."""
+    out = _c_sz()
+    check(lib().acx_weighted_metrics_workspace_bytes(int(n), int(classes), ctypes.byref(out)))
+    return out.value
+
+
+def weighted_metrics(scores, ld_scores, target, target_dtype, ld_target, n, classes, weights, ld_w, replicates, ap, auc, dprime,
+                     status, ws, stream):
+    """acx_weighted_metrics on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_weighted_metrics(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes),
+                                     weights, int(ld_w), int(replicates), ap, auc, dprime, status, ws[0], int(ws[1]), stream))
 
 
 FIT_BAD_INDEX = 1                              # bit of the status word of acx_head_fit_step / acx_head_fit_grad

@@ -378,10 +378,11 @@ class Evaluator(object):
         return calculate_statistics(out["target"], out["clipwise_output"])
 
 
-def evaluate_sharded(model, shard, batch_size=256, metrics="sklearn"):
+def evaluate_sharded(model, shard, batch_size=256, metrics="sklearn", keep=None):
     """Multi-GPU sweep: rank r scores batches r, r+W, ...; scores and targets are gathered ONCE
     at the end (all_gather of padded per-rank blocks), every rank then computes the same statistics -- on the host with
-    metrics="sklearn", on its own GPU with metrics="gpu" (the gathered blocks stay on the device)."""
+    metrics="sklearn", on its own GPU with metrics="gpu" (the gathered blocks stay on the device).  keep: a dict that receives
+    the gathered "target" and "clipwise_output" the statistics were computed from (for a bootstrap of the same sweep)."""
     _check_metrics(metrics)
     import torch.distributed as dist
     from ..utils.data_generator import evaluate_batches
@@ -410,11 +411,15 @@ def evaluate_sharded(model, shard, batch_size=256, metrics="sklearn"):
         if metrics == "gpu":
             s_all, t_all = s_all.view(world, per_rank, classes), t_all.view(world, per_rank, classes)
             rows = [int(counts[r]) for r in range(world)]
-            return gpu_statistics(torch.cat([t_all[r, : rows[r]] for r in range(world)]),
-                                  torch.cat([s_all[r, : rows[r]] for r in range(world)]), device=device)
+            target, scores = torch.cat([t_all[r, : rows[r]] for r in range(world)]), torch.cat([s_all[r, : rows[r]] for r in range(world)])
+            if keep is not None:
+                keep.update(target=target, clipwise_output=scores)
+            return gpu_statistics(target, scores, device=device)
         s_all, t_all = s_all.view(world, per_rank, classes).cpu().numpy(), t_all.view(world, per_rank, classes).cpu().numpy()
         scores = np.concatenate([s_all[r, : int(counts[r])] for r in range(world)])
         target = np.concatenate([t_all[r, : int(counts[r])] for r in range(world)])
-    elif metrics == "gpu":
+    if keep is not None:
+        keep.update(target=target, clipwise_output=scores)
+    if world == 1 and metrics == "gpu":
         return gpu_statistics(target, scores, device=next(model.parameters()).device)
     return calculate_statistics(target, scores)

@@ -300,3 +300,302 @@ def threshold_metrics(target, clipwise_output, threshold, device=None):
                               _ffi.stream_ptr(device))
     _raise_status(int(status.cpu()[0]))
     return OperatingPoints(thr, counts)
+
+
+# ---- bootstrap resamples and weighted statistics ---------------------------------------------------------------------------
+# The definitions of acx_bootstrap_weights and acx_weighted_metrics (include/acx.h) in plain numpy, and the calls that run them
+# on the GPU: a resample of the clips is a vector of integer weights over an order of each class's scores that never changes.
+
+_MIX1, _MIX2, _GOLDEN = np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB), np.uint64(0x9E3779B97F4A7C15)
+_STATS = ("average_precision", "auc", "d_prime")
+_SUMMARIES = (("mAP", "average_precision"), ("auc", "auc"), ("d_prime", "d_prime"))
+MAX_WEIGHT_SUM = 1 << 30
+
+
+def _mix(z):
+    """splitmix64's finaliser over a uint64 array (wrap-around arithmetic)."""
+    z = np.atleast_1d(np.asarray(z, dtype=np.uint64))
+    z = (z ^ (z >> np.uint64(30))) * _MIX1
+    z = (z ^ (z >> np.uint64(27))) * _MIX2
+    return z ^ (z >> np.uint64(31))
+
+
+def _check_draw_args(seed, first, replicates, n):
+    seed, first, replicates, n = int(seed), int(first), int(replicates), int(n)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be in [0, 2^64) (got %d)" % seed)
+    if replicates < 1:
+        raise ValueError("replicates must be >= 1 (got %d)" % replicates)
+    if first < 0 or first + replicates > 1 << 32:
+        raise ValueError("replicate numbers must be in [0, 2^32) (got %d .. %d)" % (first, first + replicates - 1))
+    if not 1 <= n <= 1 << 30:
+        raise ValueError("n must be in [1, 2^30] (got %d)" % n)
+    return seed, first, replicates, n
+
+
+def bootstrap_indices_host(seed, r, n, start=0, stop=None):
+    """The rows replicate r draws from n clips -- draws start .. stop - 1 (default: all n) as an int64 array:
+    x = mix(mix(seed) + 0x9E3779B97F4A7C15 * (((r << 32) | j) + 1)), idx = ((x >> 32) * n) >> 32, uint64 wrap-around arithmetic.
+    The multiply-shift is biased by at most n / 2^32."""
+    seed, r, _, n = _check_draw_args(seed, r, 1, n)
+    stop = n if stop is None else int(stop)
+    if not 0 <= int(start) <= stop <= n:
+        raise ValueError("draws %d .. %d of %d" % (start, stop, n))
+    j = np.arange(int(start), stop, dtype=np.uint64)
+    counter = ((np.uint64(r) << np.uint64(32)) | j) + np.uint64(1)
+    x = _mix(_mix(np.array([seed], dtype=np.uint64))[0] + _GOLDEN * counter)
+    return (((x >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def bootstrap_weights_host(seed, replicates, n, first=0):
+    """(replicates, n) int32: row k counts how often replicate first + k drew each clip; every row sums to n."""
+    seed, first, replicates, n = _check_draw_args(seed, first, replicates, n)
+    return np.stack([np.bincount(bootstrap_indices_host(seed, first + k, n), minlength=n) for k in range(replicates)]).astype(np.int32)
+
+
+def _host_weights(weights, n):
+    """-> (R, n) int64, checked: integers >= 0, every row summing to at most 2^30."""
+    w = np.asarray(weights.numpy() if isinstance(weights, torch.Tensor) else weights)
+    if w.dtype == np.bool_:
+        w = w.astype(np.int64)
+    if w.dtype == object or not np.issubdtype(w.dtype, np.integer):
+        raise ValueError("weights must hold integers (got dtype %s)" % w.dtype)
+    if w.ndim == 1:
+        w = w[None, :]
+    if w.ndim != 2 or w.shape[1] != n or w.shape[0] == 0:
+        raise ValueError("weights must have shape (R, %d) or (%d,); got %s" % (n, n, tuple(np.shape(weights))))
+    if w.dtype == np.uint64 and (w > np.uint64(MAX_WEIGHT_SUM)).any():
+        raise ValueError("the weights of a replicate sum above 2^30")
+    w = w.astype(np.int64)
+    if (w < 0).any():
+        raise ValueError("weights hold a negative value")
+    if (w.sum(axis=1) > MAX_WEIGHT_SUM).any():
+        raise ValueError("the weights of a replicate sum above 2^30")
+    return w
+
+
+def _erfinv(x):
+    return torch.special.erfinv(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))).numpy()
+
+
+def weighted_metrics_host(target, clipwise_output, weights):
+    """The definition of acx_weighted_metrics in numpy: {"average_precision", "auc", "d_prime"} as float64 (R, C) arrays for
+    (N, C) targets and scores and integer weights (R, N) or (N,) (R = 1), w >= 0.  Per class and weight vector, with Pw / Nw the
+    weight of the positives / negatives and, for each distinct positive score t whose positives weigh g > 0, TPw / FPw the weight
+    of the positives / negatives with score >= t:
+        AP = (1 / Pw) sum_t g * (TPw / (TPw + FPw));  AUC = sum_t g * (2 Nw(< t) + Nw(= t)) / (2 Pw Nw);  d' = 2 erfinv(2 AUC - 1)
+    Pw = 0: all three NaN (tagging_metrics has AP = 0 for a class without positives; a resample without one says nothing about
+    the class).  Nw = 0 < Pw: AP = 1, AUC and d' NaN.  These are sklearn's values on the rows repeated w times and with
+    sample_weight=w."""
+    _shape_check(target, clipwise_output)
+    s, y = _host_scores(clipwise_output), _host_target(target)
+    s = np.where(s == 0, np.float32(0.0), s)                        # -0.0 == +0.0
+    n, C = s.shape
+    w = _host_weights(weights, n)
+    R = w.shape[0]
+    ap, auc = np.full((R, C), np.nan), np.full((R, C), np.nan)
+    for c in range(C):
+        pos = y[:, c] == 1
+        op, on = np.argsort(s[pos, c], kind="stable"), np.argsort(s[~pos, c], kind="stable")
+        sp, sn = s[pos, c][op], s[~pos, c][on]
+        t, first = np.unique(sp, return_index=True)                 # the distinct positive scores, ascending
+        last = np.append(first[1:], len(sp))
+        lb, ub = np.searchsorted(sn, t, side="left"), np.searchsorted(sn, t, side="right")
+        for r in range(R):
+            cp = np.concatenate([[0], np.cumsum(w[r][pos][op])])
+            cn = np.concatenate([[0], np.cumsum(w[r][~pos][on])])
+            Pw, Nw = int(cp[-1]), int(cn[-1])
+            if Pw == 0:
+                continue
+            g = cp[last] - cp[first]
+            tpw, nlt, neq = Pw - cp[first], cn[lb], cn[ub] - cn[lb]
+            fpw = Nw - nlt
+            keep = g > 0
+            prec = tpw[keep].astype(np.float64) / (tpw[keep] + fpw[keep]).astype(np.float64)
+            ap[r, c] = float(np.sum(g[keep].astype(np.float64) * prec)) / float(Pw)
+            if Nw > 0:
+                auc[r, c] = np.float64(int(np.sum(g * (2 * nlt + neq)))) / np.float64(2 * Pw * Nw)
+    return {"average_precision": ap, "auc": auc, "d_prime": 2.0 * _erfinv(2.0 * auc - 1.0)}
+
+
+def _resolve_device(device):
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("bootstrap weights are drawn on a CUDA (HIP) device, not %s" % device)
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def bootstrap_weights(replicates, n, seed=0, first=0, device=None):
+    """bootstrap_weights_host on the GPU (acx_bootstrap_weights): an int32 device tensor (replicates, n), bit for bit the same."""
+    seed, first, replicates, n = _check_draw_args(seed, first, replicates, n)
+    device = _resolve_device(device)
+    w = torch.empty((replicates, n), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _ffi.bootstrap_weights(seed, first, replicates, n, ctypes.c_void_p(w.data_ptr()), n, _ffi.stream_ptr(device))
+    return w
+
+
+def _device_weights(weights, n, device):
+    """-> int32 device tensor (R, n), rows at a stride >= n: host weights are checked here, device weights by the kernel."""
+    if isinstance(weights, torch.Tensor) and weights.is_cuda:
+        w = weights.detach()
+        if w.dtype == torch.bool:
+            w = w.to(torch.int32)
+        if w.is_floating_point() or w.is_complex():
+            raise ValueError("weights must hold integers (got dtype %s)" % w.dtype)
+        if w.dim() == 1:
+            w = w.unsqueeze(0)
+        if w.dim() != 2 or w.shape[1] != n or w.shape[0] == 0:
+            raise ValueError("weights must have shape (R, %d) or (%d,); got %s" % (n, n, tuple(weights.shape)))
+        if w.dtype != torch.int32:
+            w = w.clamp(-1, MAX_WEIGHT_SUM + 1).to(torch.int32)     # what is invalid stays invalid
+        w = w.to(device)
+        if w.stride(1) != 1 or w.stride(0) < n:
+            w = w.contiguous()
+        return w
+    return torch.from_numpy(_host_weights(weights, n).astype(np.int32)).to(device)
+
+
+def _raise_weight_status(st):
+    _raise_status(st)
+    if st & _ffi.METRICS_BAD_WEIGHT:
+        raise ValueError("weights hold a negative value, or the weights of a replicate sum above 2^30")
+
+
+def _check_weighted_n(n, who):
+    if n > _ffi.WEIGHTED_MAX_N:
+        raise ValueError("%s: %d clips (at most %d: the weights of a class are recounted in LDS)" % (who, n, _ffi.WEIGHTED_MAX_N))
+
+
+class _WeightedRunner:
+    """acx_weighted_metrics on inputs that are already on the device, with one workspace for every call."""
+
+    def __init__(self, scores, tgt, dtype, device):
+        self.scores, self.tgt, self.dtype, self.device = scores, tgt, dtype, device
+        self.n, self.C = scores.shape
+        self.ws_bytes = _ffi.weighted_metrics_workspace_bytes(self.n, self.C)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+        self.status = torch.empty(1, dtype=torch.int32, device=device)
+
+    def __call__(self, w):
+        """w: int32 device tensor (R, n) -> float64 numpy (3, R, C); ValueError through the status word."""
+        R = w.shape[0]
+        out = torch.empty((3, R, self.C), dtype=torch.float64, device=self.device)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        s, t = self.scores, self.tgt
+        with torch.cuda.device(self.device):
+            _ffi.weighted_metrics(vp(s), s.stride(0), vp(t), self.dtype, t.stride(0), self.n, self.C, vp(w), w.stride(0), R,
+                                  vp(out[0]), vp(out[1]), vp(out[2]), vp(self.status), (vp(self.ws), self.ws_bytes),
+                                  _ffi.stream_ptr(self.device))
+        res = out.cpu().numpy()
+        _raise_weight_status(int(self.status.cpu()[0]))
+        return res
+
+
+def weighted_metrics(target, clipwise_output, weights, device=None):
+    """weighted_metrics_host on the GPU (acx_weighted_metrics): {"average_precision", "auc", "d_prime"} as float64 numpy arrays
+    (R, C).  target and clipwise_output as tagging_metrics takes them (N <= 32768); weights: integers >= 0 of shape (R, N) or
+    (N,) (R = 1), a host array or a device tensor, every row summing to at most 2^30.  A class whose positives all have weight
+    0 gets NaN in all three (no warning: under a resample that is an outcome, not a defect of the data).  ValueErrors as
+    tagging_metrics, and for weights that are not integers, negative or too large."""
+    _shape_check(target, clipwise_output)
+    _check_weighted_n(clipwise_output.shape[0], "weighted_metrics")
+    scores, tgt, dtype, device = _to_device(target, clipwise_output, device, "weighted_metrics")
+    res = _WeightedRunner(scores, tgt, dtype, device)(_device_weights(weights, scores.shape[0], device))
+    return {k: res[i].copy() for i, k in enumerate(_STATS)}
+
+
+def _mean_where(x, ok):
+    """Row means of x over the entries where ok, and how many those are; NaN for a row with none."""
+    count = ok.sum(axis=-1)
+    total = np.where(ok, x, 0.0).sum(axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(count > 0, total / count, np.nan), count
+
+
+def summarize_classes(stats):
+    """{"average_precision", "auc", "d_prime"} of shape (..., C) -> (values (..., 3), classes counted (..., 3)): mAP is the mean of
+    AP over the classes where it is not NaN, AUC likewise, d' over the classes where it is finite."""
+    ap, auc, dp = (np.asarray(stats[k], np.float64) for k in _STATS)
+    m = [_mean_where(ap, ~np.isnan(ap)), _mean_where(auc, ~np.isnan(auc)), _mean_where(dp, np.isfinite(dp))]
+    return np.stack([v for v, _ in m], axis=-1), np.stack([c for _, c in m], axis=-1).astype(np.int64)
+
+
+def _check_confidence(confidence):
+    confidence = float(confidence)
+    if not 0.0 < confidence < 1.0:
+        raise ValueError("confidence must be in (0, 1) (got %r)" % (confidence,))
+    return confidence
+
+
+def bootstrap_summary(estimate, replicates, confidence=0.95, per_class=False):
+    """The host arithmetic of bootstrap_metrics.  estimate: the three statistics of the full data, (C,) each, NaN where a class
+    is undefined (weighted_metrics' convention); replicates: the same per replicate, (R, C) each.  Percentile intervals:
+    np.quantile(values, [alpha / 2, 1 - alpha / 2]) with alpha = 1 - confidence, numpy's default interpolation, float64."""
+    confidence = _check_confidence(confidence)
+    q = [(1.0 - confidence) / 2.0, 1.0 - (1.0 - confidence) / 2.0]
+    point, _ = summarize_classes(estimate)
+    values, counted = summarize_classes(replicates)
+    out = {"confidence": confidence, "classes_counted": counted}
+    for i, (name, _) in enumerate(_SUMMARIES):
+        low, high = np.quantile(values[:, i], q)
+        out[name] = {"estimate": float(point[i]), "low": float(low), "high": float(high), "replicates": values[:, i].copy()}
+    if per_class:
+        out["per_class"] = {}
+        for k in _STATS:
+            v = np.asarray(replicates[k], np.float64)
+            ok = np.isfinite(v) if k == "d_prime" else ~np.isnan(v)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)      # a class no replicate defines: NaN bounds
+                low, high = np.nanquantile(np.where(ok, v, np.nan), q, axis=0)
+            out["per_class"][k] = {"estimate": np.asarray(estimate[k], np.float64).copy(), "low": low, "high": high,
+                                   "defined": ok.mean(axis=0)}
+    return out
+
+
+def bootstrap_metrics(target, clipwise_output, replicates=1000, seed=0, confidence=0.95, per_class=False, chunk=256, device=None):
+    """Clip-level bootstrap of mAP, macro AUC and macro d' on the GPU: `replicates` resamples of the N clips with replacement
+    (bootstrap_weights, seed), the per-class statistics of each (weighted_metrics) and percentile intervals.  Returns
+        {"mAP", "auc", "d_prime"}: each {"estimate", "low", "high", "replicates": (R,) float64},
+        "classes_counted": (R, 3) -- the classes that entered each replicate's three means --, "confidence",
+        and with per_class=True "per_class": {"average_precision", "auc", "d_prime"}: each {"estimate", "low", "high", "defined"}
+        of shape (C,), the bounds over the replicates that define the class and `defined` their fraction.
+    A replicate's mAP / AUC is the mean over the classes where the statistic is not NaN, its d' over those where it is finite;
+    the estimates apply the same rule to the statistics of the full data (all weights 1: tagging_metrics' values, a class
+    without positives left out instead of counted as AP = 0).  Replicates are processed `chunk` at a time -- the weights and
+    statistics of one chunk are all that is resident -- and the results do not depend on `chunk`."""
+    seed, _, replicates, _ = _check_draw_args(seed, 0, replicates, 1)
+    _check_confidence(confidence)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1 (got %d)" % chunk)
+    _shape_check(target, clipwise_output)
+    _check_weighted_n(clipwise_output.shape[0], "bootstrap_metrics")
+    scores, tgt, dtype, device = _to_device(target, clipwise_output, device, "bootstrap_metrics")
+    n, C = scores.shape
+    run = _WeightedRunner(scores, tgt, dtype, device)
+    full = run(torch.ones((1, n), dtype=torch.int32, device=device))
+    reps = np.empty((3, replicates, C), np.float64)
+    for first in range(0, replicates, chunk):
+        k = min(chunk, replicates - first)
+        reps[:, first:first + k] = run(bootstrap_weights(k, n, seed=seed, first=first, device=device))
+    out = bootstrap_summary({key: full[i, 0] for i, key in enumerate(_STATS)}, {key: reps[i] for i, key in enumerate(_STATS)},
+                            confidence=confidence, per_class=per_class)
+    out["seed"] = seed
+    return out
+
+
+def bootstrap_difference(target, scores_a, scores_b, replicates=1000, seed=0, confidence=0.95, chunk=256, device=None):
+    """Two models on the same clips and the same resamples (one seed): the percentile interval of a - b for mAP, AUC and d'.
+    Returns {"mAP", "auc", "d_prime"}: each {"estimate", "low", "high", "replicates": (R,) of a - b, "fraction_a_greater"}, and
+    "a" / "b": bootstrap_metrics of each model."""
+    a = bootstrap_metrics(target, scores_a, replicates, seed, confidence, False, chunk, device)
+    b = bootstrap_metrics(target, scores_b, replicates, seed, confidence, False, chunk, device)
+    alpha = 1.0 - a["confidence"]
+    out = {"confidence": a["confidence"], "seed": a["seed"], "a": a, "b": b}
+    for name, _ in _SUMMARIES:
+        d = a[name]["replicates"] - b[name]["replicates"]
+        low, high = np.quantile(d, [alpha / 2.0, 1.0 - alpha / 2.0])
+        out[name] = {"estimate": a[name]["estimate"] - b[name]["estimate"], "low": float(low), "high": float(high), "replicates": d,
+                     "fraction_a_greater": float(np.mean(d > 0))}
+    return out

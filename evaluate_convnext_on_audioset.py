@@ -5,7 +5,8 @@ evaluate_convnext_on_audioset.py: bs=256 sequential batches, mAP / AUC / d-prime
 gathered once at the end); a single process works too.
 
 Scores: --metrics gpu (default) computes the per-class statistics on each rank's GPU (pytorch/metrics.py, exact up to float64
-rounding); --metrics sklearn makes the reference's host calls.
+rounding); --metrics sklearn makes the reference's host calls.  --bootstrap R adds clip-level bootstrap confidence intervals
+(R resamples on the GPU, pytorch/metrics.py bootstrap_metrics) as one extra line per statistic; the sklearn path has none.
 
 Data: either the reference's packed HDF5 files (needs h5py) or .npy shards (int16 waveforms (N,320000) +
 targets (N,527)).  Without data, --synthetic N scores a seeded synthetic set (sanity check of the plumbing
@@ -71,7 +72,8 @@ def evaluate(args):
     for name, shard in sets:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        stats = evaluate_sharded(model, shard, batch_size=args.batch_size, metrics=args.metrics)
+        kept = {} if args.bootstrap > 0 else None
+        stats = evaluate_sharded(model, shard, batch_size=args.batch_size, metrics=args.metrics, keep=kept)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         if rank == 0:
@@ -80,6 +82,13 @@ def evaluate(args):
             print("Validate %s d-prime: %.3f" % (name, np.mean(stats["d_prime"])))
             print("(%d clips in %.2f s on %d GPU(s): %.1f clips/s incl. int16->fp32, H2D and metrics)"
                   % (len(shard), dt, world, len(shard) / dt))
+            if kept is not None:
+                from audioset_convnext_inf_amd.pytorch.metrics import bootstrap_metrics
+                ci = bootstrap_metrics(kept["target"], kept["clipwise_output"], replicates=args.bootstrap, seed=args.seed,
+                                       device=torch.device("cuda", local_rank))
+                for label, key in (("mAP", "mAP"), ("AUC", "auc"), ("d-prime", "d_prime")):
+                    print("Validate %s %s %d%% CI: [%.3f, %.3f] (%d resamples)"
+                          % (name, label, round(100 * ci["confidence"]), ci[key]["low"], ci[key]["high"], args.bootstrap))
 
 
 if __name__ == "__main__":
@@ -92,4 +101,13 @@ if __name__ == "__main__":
     p.add_argument("--batch_size", type=int, default=256)
     p.add_argument("--metrics", choices=("gpu", "sklearn"), default="gpu",
                    help="where mAP / AUC / d-prime are computed: on each rank's GPU (default) or by the reference's sklearn calls")
-    evaluate(p.parse_args())
+    p.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                   help="R > 0: also print 95%% percentile confidence intervals of mAP / AUC / d-prime from R clip-level bootstrap "
+                        "resamples computed on the GPU (default 0: off).  Needs --metrics gpu: the sklearn path has no bootstrap")
+    p.add_argument("--seed", type=int, default=0, help="seed of the bootstrap resamples")
+    args = p.parse_args()
+    if args.bootstrap < 0:
+        p.error("--bootstrap must be >= 0")
+    if args.bootstrap > 0 and args.metrics != "gpu":
+        p.error("--bootstrap needs --metrics gpu (the sklearn metrics path has no bootstrap)")
+    evaluate(args)

@@ -540,6 +540,48 @@ ACX_API int acx_threshold_counts(const float* scores, int64_t ld_scores, const v
                                  int64_t ld_target, int64_t n, int classes, const float* thresholds /* device, [classes] */,
                                  int64_t* counts /* [classes][4] */, int32_t* status, void* stream);
 
+/* ---- bootstrap resamples and weighted statistics: confidence intervals for mAP, AUC and d' ---------------------------------
+ * A clip-level bootstrap resamples the n clips with replacement and recomputes the statistics.  A resample changes no score, so
+ * it is a vector of integer weights (how often each clip was drawn) over an order that is computed once per class; the same
+ * call gives sklearn's `sample_weight` statistics for any non-negative integer weights (stratified or block resampling).
+ * DRAWS.  mix(z) is splitmix64's finaliser in uint64 wrap-around arithmetic:
+ *     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27; z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *   and draw j (0 <= j < n <= 2^30) of replicate r (0 <= r < 2^32) is
+ *     x = mix(mix(seed) + 0x9E3779B97F4A7C15 * (((r << 32) | j) + 1));   idx = ((x >> 32) * n) >> 32
+ *   Replicate r draws idx(r, 0 .. n-1); its weight vector is the count of each row among them, so it sums to n.  The
+ *   multiply-shift maps 2^32 values onto n rows: a row's probability differs from 1/n by at most 2^-32, a relative bias of at
+ *   most n / 2^32 (a contract, not a statistical claim).  pytorch/metrics.py::bootstrap_indices_host states the same in numpy.
+ * WEIGHTED STATISTICS of class c under one weight vector w (int32, >= 0), scores and labels as acx_tagging_metrics takes them:
+ *   Pw = sum of w over the positives, Nw = over the negatives; for each distinct positive score t whose positives have total
+ *   weight g > 0:  TPw = weight of positives with score >= t,  FPw = weight of negatives with score >= t
+ *   ap     = (1/Pw) sum_t g TPw / (TPw + FPw)                                   (float64)
+ *   auc    = sum_t g (2 Nw(< t) + Nw(= t)), an exact int64, divided once by 2 Pw Nw   (float64)
+ *   dprime = 2 erfinv(2 auc - 1)
+ *   Pw = 0: ap, auc and dprime are all NaN -- a resample that drew no positive says nothing about the class.  (This differs on
+ *   purpose from acx_tagging_metrics' ap = 0 for P = 0.)  Nw = 0 and Pw > 0: ap = 1, auc and dprime NaN.
+ *   With every weight 1 these are acx_tagging_metrics' values; with w the counts of a resample they are the statistics of the
+ *   resampled rows.  pytorch/metrics.py::weighted_metrics_host states them in numpy.
+ *   acx_bootstrap_weights: weights[k][0 .. n-1] (device int32, row stride ld_w >= n) = the weight vector of replicate
+ *     first_replicate + k, k < replicates -- a chunk computed alone equals the same rows of a larger call.  One clear and one
+ *     kernel on `stream` (integer atomics: the same counts in any order), capturable.  ACX_ERR_ARG for a null pointer, n < 1,
+ *     replicates < 1, ld_w < n or first_replicate + replicates > 2^32; n > 2^30 is ACX_ERR_UNSUPPORTED.
+ *   acx_weighted_metrics_workspace_bytes: workspace of acx_weighted_metrics for (n, classes) (host only).
+ *   acx_weighted_metrics: inputs, argument errors, status-word convention and launch contract of acx_tagging_metrics (a 4-byte
+ *     clear and four kernels on `stream`: no context, no allocation, no synchronisation, capturable; argument errors return
+ *     before anything touches the device; the same bits on every call whatever the workspace holds).  weights: device int32
+ *     (replicates, n) with row stride ld_w >= n; ap / auc / dprime: device float64 [replicates][classes].  replicates < 1 and
+ *     ld_w < n are ACX_ERR_ARG.  n > 32768 is ACX_ERR_UNSUPPORTED: the recount keeps one int32 weight bucket per row of a class
+ *     in LDS (128 KiB).  A negative weight, or a weight vector that sums to more than 2^30 (the bound under which the int32
+ *     buckets and the int64 AUC numerator cannot overflow), sets ACX_METRICS_BAD_WEIGHT; on any data error every output is NaN. */
+#define ACX_METRICS_BAD_WEIGHT 8
+ACX_API int acx_bootstrap_weights(uint64_t seed, uint32_t first_replicate, int replicates, int64_t n, int32_t* weights,
+                                  int64_t ld_w, void* stream);
+ACX_API int acx_weighted_metrics_workspace_bytes(int64_t n, int classes, size_t* out_bytes);
+ACX_API int acx_weighted_metrics(const float* scores, int64_t ld_scores, const void* target, int target_dtype,
+                                 int64_t ld_target, int64_t n, int classes, const int32_t* weights, int64_t ld_w, int replicates,
+                                 double* ap /* [replicates][classes] */, double* auc, double* dprime, int32_t* status, void* ws,
+                                 size_t ws_bytes, void* stream);
+
 /* ---- fitting a classifier head on frozen scene embeddings -----------------------------------------------------------------
  * The reference fine-tunes with the whole model in train mode (pytorch/finetune_audiocaps.py: base frozen, BCELoss on
  * clipwise_output, optim.Adam(amsgrad=True); pytorch/main.py:648 AdamW).  With the backbone frozen the head's input -- the scene
