@@ -59,6 +59,20 @@ class AcxOperatingSpec(ctypes.Structure):
 
 _pops = ctypes.POINTER(AcxOperatingSpec)
 
+
+class AcxRefEvent(ctypes.Structure):
+    """struct acx_ref_event: one row of the reference table of acx_score_events / acx_score_segments (24 bytes)."""
+    _fields_ = [("clip", ctypes.c_int32), ("cls", ctypes.c_int32), ("onset", ctypes.c_double), ("offset", ctypes.c_double)]
+
+
+class AcxEventCollar(ctypes.Structure):
+    """struct acx_event_collar: the matching settings of acx_score_events."""
+    _fields_ = [("t_collar", ctypes.c_double), ("percentage_of_length", ctypes.c_double), ("evaluate_onset", ctypes.c_int32),
+                ("evaluate_offset", ctypes.c_int32)]
+
+
+_pcol = ctypes.POINTER(AcxEventCollar)
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -104,6 +118,10 @@ SIGNATURES = {
                                              _c_sz, _vp, _vp, _vp]),
     "acx_decode_events_varlen_classwise": (_c_int, [_vp, _c_i64, _pint, _pdbl, _c_int, _c_int, _pevp, _c_dbl, _vp, _c_i64, _vp, _vp,
                                                     _vp, _c_sz, _vp, _vp, _vp]),
+    "acx_score_events": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _pcol, _vp, _vp, _vp, _vp,
+                                  _vp]),
+    "acx_score_segments": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _c_dbl, _vp, _vp, _vp,
+                                    _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -513,6 +531,16 @@ def events_workspace_bytes(B, N):
     out = _c_sz()
     check(lib().acx_events_workspace_bytes(int(B), int(N), ctypes.byref(out)))
     return out.value
+
+
+SCORE_BAD_TABLE = 1                           # bit of the status word of acx_score_events / acx_score_segments
+REF_EVENT_BYTES = ctypes.sizeof(AcxRefEvent)  # 24
+SCORE_TILE_SEGMENTS = 2048                    # ACX_SCORE_TILE_SEGMENTS
+
+
+def event_collar(t_collar=0.2, percentage_of_length=0.5, evaluate_onset=True, evaluate_offset=True):
+    """An acx_event_collar struct (sed_eval's defaults)."""
+    return AcxEventCollar(float(t_collar), float(percentage_of_length), 1 if evaluate_onset else 0, 1 if evaluate_offset else 0)
 
 
 def segment_count(L):

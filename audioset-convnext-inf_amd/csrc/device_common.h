@@ -156,6 +156,12 @@ __device__ __forceinline__ float win_reduce(Row row, long long j0, long long cnt
     return reduce ? acc : acc / (float)cnt;
 }
 
+// ---- event boundaries (events.hip, sed_score.hip) ---------------------------------------------------------------------------
+// Boundary k, in float64 seconds, of a clip of `steps` rows (include/acx.h "sound event decoding", 2.): k * step for k < steps,
+// the clip's last boundary `end` otherwise.  The decoder cuts events with it and the scorers read their onsets and offsets back
+// through it: one product, the same bits on both sides.
+__device__ __forceinline__ double event_edge(int k, int steps, double step, double end) { return k < steps ? (double)k * step : end; }
+
 // ---- resampling (resample.hip, stream.hip) ------------------------------------------------------------------------------
 // Output n = j nf + i of phase i: the fp32 FMA chain in ascending r over the band's count taps; xs = the staged input of the
 // band's first sample, h = tap 0 of phase i (tap r at h[r nf]).  Both resample kernels call this one chain.

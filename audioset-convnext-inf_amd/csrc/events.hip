@@ -116,7 +116,7 @@ struct EvColumn {
     __device__ __forceinline__ EvColumn(const EvArgs& a_, int steps_, double end_, bool live_, float thr_, float low_, int clip_,
                                         int cls_, long long base_)
         : a(a_), steps(steps_), end(end_), live(live_), thr(thr_), low(low_), clip(clip_), cls(cls_), base(base_) {}
-    __device__ __forceinline__ double edge(int k) const { return k < steps ? (double)k * a.step : end; }
+    __device__ __forceinline__ double edge(int k) const { return event_edge(k, steps, a.step, end); }
     __device__ __forceinline__ void finish_event() {
         if (!(edge(ee) - edge(eb) < a.min_dur)) {
             if constexpr (EMIT) {

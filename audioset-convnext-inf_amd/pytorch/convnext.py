@@ -23,6 +23,7 @@ from . import resample as _rs
 from . import windows as _win
 from . import stream as _stream
 from . import segments as _seg
+from . import sed_metrics as _sed
 
 HF_PYTORCH_WEIGHTS_NAME = "model.safetensors"     # convnext.py:29
 HF_CONFIG_NAME = "config.yaml"                    # convnext.py:31
@@ -492,6 +493,19 @@ class ConvNeXt(nn.Module):
                               decode_args.get("min_duration", 0.0), decode_args.get("merge_gap", 0.0), classes=self.num_classes)
         out = self.forward_segments(waveform, pool=pool, sample_rate=sample_rate)
         out["events"] = _seg.decode_events_gpu(out["segmentwise_output"], step=out["segment_edges"].numpy(), **decode_args)
+        return out
+
+    def score_events(self, waveform, reference, metric="event", **args):
+        """detect_events followed by the scoring of its table against annotated events, all on the GPU and on the same stream
+        (pytorch/sed_metrics.py).  reference: a ReferenceEvents on the model's device, one entry per clip of the batch;
+        metric: "event" (onset / offset collars) or "segment" (a fixed time grid).  args: detect_events' own (pool,
+        sample_rate, threshold, low, median, min_duration, merge_gap, capacity) and the scorer's (t_collar,
+        percentage_of_length, evaluate_onset, evaluate_offset / time_resolution).  Returns detect_events' dict plus "scores",
+        a SedScores; nothing synchronises until the table or the scores are read."""
+        args = dict(args)
+        score, score_args = _sed._scorer(metric, args)
+        out = self.detect_events(waveform, **args)
+        out["scores"] = score(reference, out["events"], **score_args)
         return out
 
     def tag(self, waveform, threshold, sample_rate=None):

@@ -322,6 +322,52 @@ ACX_API int acx_decode_events_varlen_classwise(const float* probs, int64_t ld, c
                                                int64_t capacity, int64_t* count, int* status, void* ws, size_t ws_bytes,
                                                void* stream, const float* threshold, const float* low);
 
+/* ---- sound event scoring: an event table against annotated events -> integer counts ------------------------------------------------
+ * The reference has no scoring of detected events at all (its pytorch/inference.py:156-200 stops at the thresholded plot); users
+ * of acx_decode_events pulled the table to the host and looped.  The definitions are the two host functions of this project,
+ * pytorch/sed_metrics.py::event_based_metrics_host and ::segment_based_metrics_host, written after sed_eval's published
+ * EventBasedMetrics (greedy matching) and SegmentBasedMetrics; every output is an integer and EQUALS theirs.
+ * ref: device table of n_ref reference events ordered by (clip, cls, onset, offset), 0 <= onset < offset finite, 0 <= clip < B,
+ * 0 <= cls < N; events of one class may overlap.  est / capacity / est_count / est_status: the table, capacity, *count and
+ * *status of acx_decode_events as they lie on the device -- the valid rows are the first min(*est_count, capacity), read on the
+ * device, so the call queues behind the decoder without a host synchronisation.  *est_status != 0 or *est_count > capacity (a
+ * table that overflowed, non-finite probabilities, bad per-class levels) sets ACX_SCORE_BAD_TABLE in *status and leaves every
+ * count zero and every match -1.  steps / end_seconds: DEVICE arrays of B values, the clips' row counts and last boundaries (no
+ * ACX_MAX_VARLEN_CLIPS limit: an evaluation set is one call).  An estimated event's onset / offset are edges[begin] / edges[end]
+ * of "sound event decoding", 2.
+ * acx_score_events (replaces: nothing in the reference; host loops over EventTable.to_lists()).  Per (clip, cls), the reference
+ *   events in order: each takes the first estimated row, in table order, not taken yet, with
+ *     |r_on - e_on| <= t_collar                                                  (unless evaluate_onset == 0) and
+ *     |r_off - e_off| <= max(t_collar, percentage_of_length * (r_off - r_on))    (unless evaluate_offset == 0), all in float64.
+ *   counts[cls] = TP (matched pairs), FP = rows - TP, FN = reference events - TP.  ref_match[i] = the estimated row matched to
+ *   reference event i or -1; est_match[j] = the reference row matched to estimated row j or -1 (all `capacity` entries are
+ *   written).  sed_eval's optimal (bipartite) matching and its cross-class substitutions are not offered.
+ * acx_score_segments (replaces: the same).  Clip i has ceil(end_i / time_resolution) segments (at most 2^31 - 2); an event is
+ *   active in segments [floor(onset / res), ceil(offset / res)) clipped to the clip, float64 with IEEE division.  Per segment and
+ *   class, ref / est activity is the union of the events.  counts[cls] = TP = sum(ref & est), FP = sum(est & ~ref), FN =
+ *   sum(ref & ~est) over all segments and clips.  Per segment, with fn / fp its totals over the classes: S = min(fn, fp),
+ *   D = max(0, fn - fp), I = max(0, fp - fn).  overall = TP, S, D, I, Nref, Nsys summed over segments and clips (Nref, Nsys: the
+ *   active (segment, class) cells).
+ * Launch contract: everything in order on `stream` (the clears of the outputs, one kernel), no allocation, no workspace, no
+ * synchronisation, capturable; counts meet only in 64-bit integer atomic adds, so every call gives the same bits.  n_ref == 0
+ * (ref, ref_match may be NULL) and an empty estimated table (capacity == 0: est, est_match may be NULL) are legal.
+ * Argument errors are returned before anything touches the device.  ACX_ERR_ARG: a null pointer; n_ref or capacity < 0;
+ * step_seconds <= 0; time_resolution not finite or <= 0; t_collar or percentage_of_length negative or not finite.  ACX_ERR_SHAPE:
+ * B < 1; N < 1 or N > ACX_MAX_CLASSES.  ACX_ERR_UNSUPPORTED: B * ceil(N / 64) beyond a launchable grid (2^31 - 1 workgroups). */
+typedef struct acx_ref_event { int32_t clip, cls; double onset, offset; } acx_ref_event;   /* 24 bytes */
+typedef struct acx_event_collar { double t_collar, percentage_of_length; int32_t evaluate_onset, evaluate_offset; } acx_event_collar;
+#define ACX_SCORE_BAD_TABLE 1
+#define ACX_SCORE_TILE_SEGMENTS 2048     /* segments one workgroup of acx_score_segments holds in LDS at a time */
+ACX_API int acx_score_events(const acx_ref_event* ref, int64_t n_ref, const acx_event* est, int64_t capacity,
+                             const int64_t* est_count, const int* est_status, int64_t B, int N, const int* steps /* device, B */,
+                             const double* end_seconds /* device, B */, double step_seconds, const acx_event_collar* c,
+                             int64_t* counts /* N*3 */, int64_t* ref_match /* n_ref */, int64_t* est_match /* capacity */,
+                             int* status, void* stream);
+ACX_API int acx_score_segments(const acx_ref_event* ref, int64_t n_ref, const acx_event* est, int64_t capacity,
+                               const int64_t* est_count, const int* est_status, int64_t B, int N, const int* steps /* device, B */,
+                               const double* end_seconds /* device, B */, double step_seconds, double time_resolution,
+                               int64_t* counts /* N*3 */, int64_t* overall /* 6 */, int* status, void* stream);
+
 /* ---- live streams: tagging recordings that arrive chunk by chunk ----------------------------------------------------------
  * No reference counterpart.  A handle has `slots`; each slot holds one recording at a time.  Samples pushed to a slot are
  * appended to its open recording; acx_stream_close ends it and the slot's next push starts a new one.  Window W, hop H, the
