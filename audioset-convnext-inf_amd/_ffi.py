@@ -166,6 +166,13 @@ SIGNATURES = {
     "acx_head_fit_grad": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _c_sz, _vp]),
     "acx_adam_update": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _padam, _c_i64, _c_dbl, _vp]),
+    "acx_head_fit_ce_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_head_fit_step_ce": (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_int, _c_dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _padam, _c_i64, _c_dbl, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_head_fit_grad_ce": (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_int, _c_dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _c_sz, _vp]),
+    "acx_softmax_topk": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp]),
+    "acx_classification_counts": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "acx_knn_row_norms": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp]),
     "acx_knn_workspace_bytes": (_c_int, [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_knn_slices": (_c_int, [_c_i64, _c_i64, _c_int, _pint]),
@@ -471,6 +478,40 @@ def head_fit_workspace_bytes(rows_max, classes):
     out = _c_sz()
     check(lib().acx_head_fit_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
     return out.value
+
+
+FIT_BAD_LABEL = 2                              # acx_head_fit_step_ce / acx_head_fit_grad_ce: a label outside [0, classes)
+
+
+def head_fit_ce_workspace_bytes(rows_max, classes):
+    """Workspace of acx_head_fit_step_ce / acx_head_fit_grad_ce for steps of up to rows_max rows (host only)."""
+    out = _c_sz()
+    check(lib().acx_head_fit_ce_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
+    return out.value
+
+
+CLASSIFY_MAX_K = 64                            # ACX_CLASSIFY_MAX_K
+CLASSIFY_NONFINITE, CLASSIFY_BAD_LABEL = 1, 2  # bits of the status words of acx_softmax_topk / acx_classification_counts
+CLASSIFY_MAX_CONFUSION = 4096                  # widest head acx_classification_counts fills a confusion matrix for
+SOFT_WAVE_MAX_N = 2048                         # rows up to this many classes are summed by one wave, wider ones by a workgroup
+
+
+def softmax_depth(classes):
+    """Depth of the fp32 row sum of the softmax kernels (include/acx.h): additions between an element and the sum."""
+    classes = int(classes)
+    return -(-classes // 64) + 6 if classes <= SOFT_WAVE_MAX_N else -(-classes // 256) + 9
+
+
+def softmax_topk(logits, ld, rows, classes, k, probs, ld_p, top_index, top_prob, status, stream):
+    """acx_softmax_topk on raw device pointers (ctypes.c_void_p); probs may be None."""
+    check(lib().acx_softmax_topk(logits, int(ld), int(rows), int(classes), int(k), probs, int(ld_p), top_index, top_prob, status,
+                                 stream))
+
+
+def classification_counts(logits, ld, labels, n, classes, k, per_class, hits, confusion, status, stream):
+    """acx_classification_counts on raw device pointers (ctypes.c_void_p); confusion may be None."""
+    check(lib().acx_classification_counts(logits, int(ld), labels, int(n), int(classes), int(k), per_class, hits, confusion,
+                                          status, stream))
 
 
 KNN_DOT, KNN_COSINE = 0, 1                    # enum acx_knn_metric

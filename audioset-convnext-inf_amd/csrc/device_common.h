@@ -70,6 +70,75 @@ __device__ __forceinline__ T wave_sum(T v) {
 // The partial results of a workgroup's four waves, added in wave order.
 __device__ __forceinline__ float sum4(float w0, float w1, float w2, float w3) { return ((w0 + w1) + w2) + w3; }
 
+// ---- one total order on (fp32 score, index) pairs (knn.hip, classify.hip) ---------------------------------------------------
+// ONE 64-bit key per pair: the order-preserving image of the score (-0.0 taken as +0.0) in the high word, the complemented
+// index in the low word.  Larger key = score descending, then index ascending; no two keys are equal.  Key 0 is "no
+// candidate" (no finite score and index < 2^30 maps to it).
+typedef unsigned long long knn_key;
+__device__ __forceinline__ knn_key knn_make_key(float s, long long idx) {
+    unsigned u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0u;                                   // -0.0 orders as +0.0
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((knn_key)u << 32) | (knn_key)(~(unsigned)idx);
+}
+__device__ __forceinline__ float knn_key_score(knn_key key) {
+    unsigned u = (unsigned)(key >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ int knn_key_index(knn_key key) { return (int)~(unsigned)key; }
+
+// ---- softmax of one row of logits (head_fit.hip: fit_ce_row_kernel; classify.hip) -------------------------------------------
+// A row of N logits belongs to a GROUP of W threads: W = 64, one wave (N <= kSoftWaveMaxN: the four waves of a workgroup
+// take four rows), or W = 256, the whole workgroup (wider rows).  Thread t of the group reads elements t, t + W, t + 2 W, ...
+// in ascending order; a row is read again from L2 on every pass instead of being kept in LDS (see head_fit.hip).  Group
+// results: the 64 lanes by the xor butterfly, then (W = 256) the four waves in wave order through `red` -- every thread of
+// the group ends with the same bits, and the order depends on N alone.  The sum of a row has depth
+// soft_depth(N) = ceil(N / W) + 6 (+ 3 for W = 256) additions.
+constexpr int kSoftWaveMaxN = 2048;
+template <int W> __device__ __forceinline__ int soft_thread() { return W == 64 ? (int)(threadIdx.x & 63) : (int)threadIdx.x; }
+template <int W>
+__device__ __forceinline__ float group_sum(float v, float* red) {
+    v = wave_sum(v);
+    if (W == 256) {
+        __syncthreads();                                           // the previous reduction's reads of red
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+        __syncthreads();
+        v = sum4(red[0], red[1], red[2], red[3]);
+    }
+    return v;
+}
+template <int W>
+__device__ __forceinline__ float group_max(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    if (W == 256) {
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+        __syncthreads();
+        v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    }
+    return v;
+}
+template <int W>
+__device__ __forceinline__ bool group_any(bool b) {
+    return W == 64 ? __ballot(b) != 0ull : __syncthreads_or(b) != 0;
+}
+// p_c of a row with maximum m and s = sum_c expf(z_c - m): the ONE evaluation behind G, probs and top_prob
+__device__ __forceinline__ float soft_prob(float z, float m, float s) { return expf(z - m) / s; }
+// m = max_c z_c and s = sum_c expf(z_c - m) of the group's row (NaN elements do not enter the maximum)
+template <int W>
+__device__ __forceinline__ void soft_row_stats(const float* z, int N, float* red, float& m, float& s) {
+    const int t = soft_thread<W>();
+    float mx = -INFINITY;
+    for (int c = t; c < N; c += W) mx = fmaxf(mx, z[c]);
+    mx = group_max<W>(mx, red);
+    float sm = 0.f;
+    for (int c = t; c < N; c += W) sm += expf(z[c] - mx);
+    m = mx;
+    s = group_sum<W>(sm, red);
+}
+
 // ---- S x S tiles on the f32-input matrix cores (head_fit.hip, segments.hip, knn.hip) ---------------------------------------
 // Lane = (column r = lane % S, lane group h = lane / S); accumulator register i of lane group h holds row row(i, h).
 template <int S> struct F32Tile;

@@ -14,6 +14,23 @@
 //                     the gradient kernel's reads.
 // The batch rows are gathered through idx in both kernels: no shuffled copy of the data set exists.
 //
+// Cross-entropy (acx_head_fit_step_ce / acx_head_fit_grad_ce: a single-label head, integer labels, F.cross_entropy with
+// label_smoothing, reduction mean) is three launches:
+//   fit_logits_kernel  the tile body of fit_grad_kernel with the loss taken out (fit_grad_tile<S, kLossCe>): z -> workspace.
+//   fit_ce_row_kernel  per row: m = max z, s = sum expf(z - m), G = (expf(z - m) / s - q) / rows with q = (1 - eps) [c = y] +
+//                      eps / N, and the row's loss log s + sum_c q_c (m - z_c) (= m + log s - sum_c q_c z_c, written so
+//                      that every term is >= 0 and a one-class row gives 0 exactly) -> part[row].
+//                      Which shape runs when: N <= 2048 (kSoftWaveMaxN): one WAVE per row, four rows per workgroup, so a
+//                      50-class head with 64 rows is 16 full workgroups; wider rows: one WORKGROUP per row.  Either way a
+//                      thread adds its elements in ascending order, then the lanes by the xor butterfly, then (workgroup
+//                      shape) the four waves in order: depth D = ceil(N / 64) + 6, or ceil(N / 256) + 9, a function of N alone.
+//                      The row is NOT staged in LDS: it is read three times (max, sum, G); the first pass brings it into
+//                      the XCD's L2 (4 MiB; a 32 768-class row is 128 KiB, a 527-class one 2 KiB and stays in L1), the other
+//                      two hit there.  Holding a wide row in LDS would cost 128 of a CU's 160 KiB -- one workgroup per CU and
+//                      no latency hiding -- to save L2 hits.  No atomics on floats; a row's G (at equal rows) depends on that row's z
+//                      and label alone, and so do the row's z bits: the logits launch picks its tile shape from N, not rows.
+//   fit_update_kernel  exactly as for BCE: it consumes G, adds part[0 .. rows) in index order and scales by 1 / rows.
+//
 // Arithmetic: fp32 products, fp32 accumulation on the f32-input matrix cores (v_mfma_f32_32x32x2_f32 when the launch has
 // at least one 32 x 32 tile per CU, v_mfma_f32_16x16x4_f32 otherwise, so that a 50-class head with 64 rows still spreads over
 // 16 + 192 workgroups) -- bit-equal to an fmaf chain.  The four waves of a workgroup split the contraction (K = 768 or the rows)
@@ -93,8 +110,12 @@ struct FitGradP {
     int* status; float inv; int tiles_n;
 };
 
-template <int S>
-__global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) {
+enum { kLossBce = 0, kLossCe = 1 };
+
+// The tile body of the gradient pass.  LOSS = kLossBce: the whole of fit_grad_kernel.  LOSS = kLossCe: the logits alone go
+// to p.z (the softmax needs whole rows: fit_ce_row_kernel); Y, G, part and inv are not read.
+template <int S, int LOSS>
+__device__ __forceinline__ void fit_grad_tile(FitGradP p) {
     using T = FitTile<S>;
     constexpr int KB = (64 / S) * 4;               // k per block of four MFMAs: lane group h holds k = 4 h .. 4 h + 3
     constexpr int KW = kFitK / 4;                  // k per wave
@@ -143,6 +164,10 @@ __global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) {
         const int row = row0 + rr, c = c0 + cc;
         if (row < p.rows && c < p.N) {
             const float zz = tile_sum4(red, e) + p.b[c];
+            if (LOSS == kLossCe) {
+                p.z[(long long)row * p.N + c] = zz;
+                continue;
+            }
             const long long yo = s_idx[rr] * p.ld_y + c;
             const float y = p.y_u8 ? (static_cast<const unsigned char*>(p.Y)[yo] ? 1.f : 0.f) : static_cast<const float*>(p.Y)[yo];
             // sigmoid and both logarithms from e = exp(-|z|): log p = min(z, 0) - log1p(e), log(1 - p) = min(-z, 0) - log1p(e)
@@ -157,10 +182,54 @@ __global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) {
             if (p.z) p.z[o] = zz;
         }
     }
+    if (LOSS == kLossCe) return;
     lsum = wave_sum(lsum);
     if (lane == 0) s_loss[wave] = lsum;
     __syncthreads();
     if (tid == 0) p.part[blockIdx.x] = sum4(s_loss[0], s_loss[1], s_loss[2], s_loss[3]);
+}
+
+template <int S>
+__global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) { fit_grad_tile<S, kLossBce>(p); }
+template <int S>
+__global__ __launch_bounds__(kFitThreads) void fit_logits_kernel(FitGradP p) { fit_grad_tile<S, kLossCe>(p); }
+
+// The row pass of the cross-entropy step: G and the row's loss from the logits z (rows, N), one group of W threads per row
+// (device_common.h, "softmax of one row").  label = labels[idx[r]], both clamped into their ranges.
+struct FitCeRowP {
+    const float* z; const long long* labels; const long long* idx; long long n_total; int rows; int N;
+    float q_hit, q_miss, ome;      // fp32 roundings of (1 - eps) + eps / N, eps / N and 1 - eps
+    float inv;                     // 1 / rows
+    float* G; float* part; int* status;
+};
+
+template <int W>
+__global__ __launch_bounds__(kFitThreads) void fit_ce_row_kernel(FitCeRowP p) {
+    __shared__ float red[4];
+    const int t = soft_thread<W>();
+    const int row = W == 64 ? (int)(blockIdx.x * 4 + (threadIdx.x >> 6)) : (int)blockIdx.x;
+    if (row >= p.rows) return;                                     // W = 64 only: a whole wave, and no barrier follows
+    long long src = p.idx[row];
+    src = src < 0 ? 0 : src >= p.n_total ? p.n_total - 1 : src;    // flagged by the logits kernel
+    long long y = p.labels[src];
+    if (y < 0 || y >= p.N) {
+        if (t == 0) atomicOr(p.status, ACX_FIT_BAD_LABEL);
+        y = y < 0 ? 0 : p.N - 1;
+    }
+    const float* z = p.z + (long long)row * p.N;
+    float* g = p.G + (long long)row * p.N;
+    float m, s;
+    soft_row_stats<W>(z, p.N, red, m, s);
+    // sum_c q_c (m - z_c) = q_miss sum_c (m - z_c) + (1 - eps) (m - z_y): with sum_c q_c = 1 this is m - sum_c q_c z_c, every
+    // term >= 0, and a one-class row gives 0 exactly
+    float d = 0.f;
+    for (int c = t; c < p.N; c += W) {
+        const float zc = z[c];
+        d += m - zc;
+        g[c] = (soft_prob(zc, m, s) - (c == (int)y ? p.q_hit : p.q_miss)) * p.inv;
+    }
+    d = group_sum<W>(d, red);
+    if (t == 0) p.part[row] = logf(s) + (p.q_miss * d + p.ome * (m - z[y]));
 }
 
 struct FitUpdP {
@@ -284,6 +353,14 @@ static void fit_layout(long long rows, long long N, size_t* part_off, size_t* to
     *total = gb + pb;
 }
 
+// cross-entropy workspace: G, z (rows_max, classes) fp32 each, then one loss partial per row
+static void fit_ce_layout(long long rows, long long N, size_t* z_off, size_t* part_off, size_t* total) {
+    const size_t gb = align_up((size_t)rows * N * 4);
+    *z_off = gb;
+    *part_off = 2 * gb;
+    *total = 2 * gb + align_up((size_t)rows * 4);
+}
+
 static int fit_check_shape(const char* who, int64_t rows, int classes) {
     if (rows < 1) ACX_FAIL(ACX_ERR_ARG, "%s: rows = %lld (expected >= 1)", who, (long long)rows);
     if (classes < 1 || classes > ACX_MAX_CLASSES)
@@ -341,6 +418,23 @@ static int fit_check_call(const char* who, const FitCall& c, size_t* part_off) {
     return check_workspace_for(who, c.ws, c.ws_bytes, need);
 }
 
+// The update launch both losses share: u complete except for its tile count.
+static int fit_launch_update(FitUpdP u, int N, int cus, bool apply, hipStream_t s) {
+    const bool u32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
+    const int us = u32 ? 32 : 16;
+    u.tiles = ((N + us - 1) / us) * (kFitK / us);
+    const dim3 grid(u.tiles + (N + kFitDbCols - 1) / kFitDbCols + 1);
+    if (apply) {
+        if (u32) launch_kernel(&fit_update_kernel<32, true>, grid, dim3(kFitThreads), 0, s, u);
+        else launch_kernel(&fit_update_kernel<16, true>, grid, dim3(kFitThreads), 0, s, u);
+    } else {
+        if (u32) launch_kernel(&fit_update_kernel<32, false>, grid, dim3(kFitThreads), 0, s, u);
+        else launch_kernel(&fit_update_kernel<16, false>, grid, dim3(kFitThreads), 0, s, u);
+    }
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
 // The two launches.  apply: W, b and the moments updated in place (u.a set); otherwise dW / db written.  The tile shape of each
 // launch depends on (rows, classes, CUs) alone, so the step and its component form run the same kernels.
 static int fit_launch(const FitCall& c, float* z, float* G, float* part, FitUpdP u, bool apply, float* loss, hipStream_t s) {
@@ -363,19 +457,64 @@ static int fit_launch(const FitCall& c, float* z, float* G, float* part, FitUpdP
 
     u.E = c.E; u.ld_e = c.ld_e; u.n_total = c.n_total; u.idx = g.idx; u.rows = rows; u.N = N;
     u.G = G; u.part = part; u.nparts = gtiles; u.loss = loss; u.inv = inv;
-    const bool u32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
-    const int us = u32 ? 32 : 16;
-    u.tiles = ((N + us - 1) / us) * (kFitK / us);
-    const dim3 grid(u.tiles + (N + kFitDbCols - 1) / kFitDbCols + 1);
-    if (apply) {
-        if (u32) launch_kernel(&fit_update_kernel<32, true>, grid, dim3(kFitThreads), 0, s, u);
-        else launch_kernel(&fit_update_kernel<16, true>, grid, dim3(kFitThreads), 0, s, u);
-    } else {
-        if (u32) launch_kernel(&fit_update_kernel<32, false>, grid, dim3(kFitThreads), 0, s, u);
-        else launch_kernel(&fit_update_kernel<16, false>, grid, dim3(kFitThreads), 0, s, u);
-    }
+    return fit_launch_update(u, N, cus, apply, s);
+}
+
+struct FitCeCall {      // the arguments the cross-entropy step and its component form share
+    const float* E; int64_t ld_e; int64_t n_total; const int64_t* labels; const int64_t* idx; int64_t rows; int classes;
+    double eps; const float* W; const float* b; int32_t* status; void* ws; size_t ws_bytes;
+};
+
+static int fit_ce_check_call(const char* who, const FitCeCall& c, size_t* z_off, size_t* part_off) {
+    if (!c.E) ACX_FAIL(ACX_ERR_ARG, "%s: E is null", who);
+    if (!c.labels) ACX_FAIL(ACX_ERR_ARG, "%s: labels is null", who);
+    if (!c.idx) ACX_FAIL(ACX_ERR_ARG, "%s: idx is null", who);
+    if (!c.W) ACX_FAIL(ACX_ERR_ARG, "%s: W is null", who);
+    if (!c.b) ACX_FAIL(ACX_ERR_ARG, "%s: b is null", who);
+    if (!c.status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    if (!c.ws) ACX_FAIL(ACX_ERR_ARG, "%s: workspace is null", who);
+    if (!(c.eps >= 0.0 && c.eps < 1.0)) ACX_FAIL(ACX_ERR_ARG, "%s: label_smoothing = %g (expected 0 <= label_smoothing < 1)", who, c.eps);
+    ACX_TRY(fit_check_shape(who, c.rows, c.classes));
+    if (c.n_total < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n_rows_total = %lld (expected >= 1)", who, (long long)c.n_total);
+    if (c.ld_e < kFitK) ACX_FAIL(ACX_ERR_ARG, "%s: ld_e = %lld is shorter than a row of %d", who, (long long)c.ld_e, kFitK);
+    if ((c.ld_e & 3) || (reinterpret_cast<uintptr_t>(c.E) & 15) || (reinterpret_cast<uintptr_t>(c.W) & 15))
+        ACX_FAIL(ACX_ERR_ARG, "%s: E and W must be 16-byte aligned and ld_e a multiple of 4 (ld_e = %lld)", who, (long long)c.ld_e);
+    size_t need;
+    fit_ce_layout(c.rows, c.classes, z_off, part_off, &need);
+    return check_workspace_for(who, c.ws, c.ws_bytes, need);
+}
+
+// The three launches.  BOTH matrix launches take the update kernel's tile rule, a function of (classes, CUs) alone: the logits
+// of a row then have the same bits in every batch, whatever `rows` is (the two tile shapes add the 768 products in different
+// orders, so a rule that looked at `rows`, as fit_launch's does for BCE, would let the short last batch of an epoch change them).
+static int fit_ce_launch(const FitCeCall& c, float* z, float* G, float* part, FitUpdP u, bool apply, float* loss, hipStream_t s) {
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    const int rows = (int)c.rows, N = c.classes;
+    const float inv = (float)(1.0 / (double)rows);
+    FitGradP g{};
+    g.E = c.E; g.ld_e = c.ld_e; g.n_total = c.n_total;
+    g.idx = reinterpret_cast<const long long*>(c.idx); g.rows = rows; g.N = N;
+    g.W = c.W; g.b = c.b; g.z = z; g.status = (int*)c.status;
+    const bool g32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
+    const int gs = g32 ? 32 : 16;
+    g.tiles_n = (N + gs - 1) / gs;
+    const int gtiles = ((rows + gs - 1) / gs) * g.tiles_n;
+    if (g32) launch_kernel(&fit_logits_kernel<32>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
+    else launch_kernel(&fit_logits_kernel<16>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
     ACX_HIP(hipGetLastError());
-    return ACX_OK;
+
+    FitCeRowP r;
+    r.z = z; r.labels = reinterpret_cast<const long long*>(c.labels); r.idx = g.idx; r.n_total = c.n_total; r.rows = rows; r.N = N;
+    r.q_hit = (float)((1.0 - c.eps) + c.eps / N); r.q_miss = (float)(c.eps / N); r.ome = (float)(1.0 - c.eps);
+    r.inv = inv; r.G = G; r.part = part; r.status = (int*)c.status;
+    if (N <= kSoftWaveMaxN) launch_kernel(&fit_ce_row_kernel<64>, dim3((rows + 3) / 4), dim3(kFitThreads), 0, s, r);
+    else launch_kernel(&fit_ce_row_kernel<256>, dim3(rows), dim3(kFitThreads), 0, s, r);
+    ACX_HIP(hipGetLastError());
+
+    u.E = c.E; u.ld_e = c.ld_e; u.n_total = c.n_total; u.idx = g.idx; u.rows = rows; u.N = N;
+    u.G = G; u.part = part; u.nparts = rows; u.loss = loss; u.inv = inv;
+    return fit_launch_update(u, N, cus, apply, s);
 }
 
 }  // namespace acx
@@ -423,6 +562,47 @@ int acx_head_fit_grad(const float* E, int64_t ld_e, int64_t n_rows_total, const 
     FitUpdP u{};
     u.dW = dW; u.db = db;
     return fit_launch(c, z, G, reinterpret_cast<float*>(static_cast<char*>(ws) + part_off), u, false, loss, (hipStream_t)stream);
+}
+
+int acx_head_fit_ce_workspace_bytes(int64_t rows_max, int classes, size_t* out_bytes) {
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "acx_head_fit_ce_workspace_bytes: out_bytes is null");
+    ACX_TRY(fit_check_shape("acx_head_fit_ce_workspace_bytes", rows_max, classes));
+    size_t zo, po;
+    fit_ce_layout(rows_max, classes, &zo, &po, out_bytes);
+    return ACX_OK;
+}
+
+int acx_head_fit_step_ce(const float* E, int64_t ld_e, int64_t n_rows_total, const int64_t* labels, const int64_t* idx,
+                         int64_t rows, int classes, double label_smoothing, float* W, float* b, float* mW, float* vW, float* vmaxW,
+                         float* mb, float* vb, float* vmaxb, const acx_adam* hp, int64_t step_t, double lr, float* loss_out,
+                         int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "acx_head_fit_step_ce";
+    const FitCeCall c{E, ld_e, n_rows_total, labels, idx, rows, classes, label_smoothing, W, b, status, ws, ws_bytes};
+    size_t z_off, part_off;
+    ACX_TRY(fit_ce_check_call(who, c, &z_off, &part_off));
+    if (!mW || !vW || !mb || !vb) ACX_FAIL(ACX_ERR_ARG, "%s: a moment buffer (mW, vW, mb, vb) is null", who);
+    if (!loss_out) ACX_FAIL(ACX_ERR_ARG, "%s: loss_out is null", who);
+    FitUpdP u{};
+    ACX_TRY(adam_scalars(who, hp, step_t, lr, &u.a));
+    if (hp->amsgrad && (!vmaxW || !vmaxb)) ACX_FAIL(ACX_ERR_ARG, "%s: vmaxW / vmaxb is null with hp->amsgrad set", who);
+    u.W = W; u.mW = mW; u.vW = vW; u.vmaxW = vmaxW;
+    u.b = b; u.mb = mb; u.vb = vb; u.vmaxb = vmaxb;
+    char* w = static_cast<char*>(ws);
+    return fit_ce_launch(c, reinterpret_cast<float*>(w + z_off), reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + part_off),
+                         u, true, loss_out, (hipStream_t)stream);
+}
+
+int acx_head_fit_grad_ce(const float* E, int64_t ld_e, int64_t n_rows_total, const int64_t* labels, const int64_t* idx,
+                         int64_t rows, int classes, double label_smoothing, const float* W, const float* b, float* z, float* G,
+                         float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "acx_head_fit_grad_ce";
+    const FitCeCall c{E, ld_e, n_rows_total, labels, idx, rows, classes, label_smoothing, W, b, status, ws, ws_bytes};
+    size_t z_off, part_off;
+    ACX_TRY(fit_ce_check_call(who, c, &z_off, &part_off));
+    if (!z || !G || !dW || !db || !loss) ACX_FAIL(ACX_ERR_ARG, "%s: an output (z, G, dW, db, loss) is null", who);
+    FitUpdP u{};
+    u.dW = dW; u.db = db;
+    return fit_ce_launch(c, z, G, reinterpret_cast<float*>(static_cast<char*>(ws) + part_off), u, false, loss, (hipStream_t)stream);
 }
 
 int acx_adam_update(float* param, const float* grad, float* m, float* v, float* vmax, int64_t n, const acx_adam* hp,

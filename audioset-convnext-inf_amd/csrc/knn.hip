@@ -35,26 +35,13 @@
 
 namespace acx {
 
-typedef unsigned long long knn_key;
-
 constexpr int kKnnThreads = 256;
 constexpr int kKnnStepRows = 256;            // database rows per step of a workgroup: four waves x 64
 constexpr int kKnnTargetWgs = 512;           // the slice count aims at this many workgroups: two per CU of an MI355X
 constexpr int kKnnMaxSlices = 1024;
 constexpr long long kKnnMaxRows = 1LL << 30;
 
-__device__ __forceinline__ knn_key knn_make_key(float s, long long idx) {
-    unsigned u = __float_as_uint(s);
-    if (u == 0x80000000u) u = 0u;                                   // -0.0 orders as +0.0
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((knn_key)u << 32) | (knn_key)(~(unsigned)idx);
-}
-__device__ __forceinline__ float knn_key_score(knn_key key) {
-    unsigned u = (unsigned)(key >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return __uint_as_float(u);
-}
-__device__ __forceinline__ int knn_key_index(knn_key key) { return (int)~(unsigned)key; }
+// knn_key, knn_make_key, knn_key_score, knn_key_index: device_common.h (classify.hip orders classes by the same keys)
 
 // Element e = lane + 64 r of a wave's 64 R keys, sorted descending (bitonic network: strides under 64 by lane shuffles, the
 // others between the lane's own registers).

@@ -526,6 +526,17 @@ class ConvNeXt(nn.Module):
         return {"labels": probs >= thr.to(device=probs.device, dtype=probs.dtype), "clipwise_output": probs,
                 "clipwise_logits": out["clipwise_logits"]}
 
+    def classify(self, waveform, k=5, sample_rate=None):
+        """A single-label head (fit_head(..., loss="ce")) read with softmax: one forward, then classify.softmax_topk on the same
+        stream; nothing synchronises.  Returns {"probabilities" (B, N), "labels" (B,) int64 = the top-1 class, "top_indices"
+        (B, k) int32, "top_probabilities" (B, k), "clipwise_logits"}; k is cut to N.  model(x) itself keeps returning the sigmoid
+        clipwise_output (INTEGRATION.md, "Single-label heads")."""
+        from . import classify as _cl
+        logits = self(waveform, sample_rate=sample_rate)["clipwise_logits"]
+        probs, top_prob, top_index = _cl.softmax_topk(logits, k=min(int(k), int(logits.shape[1])))
+        return {"probabilities": probs, "labels": top_index[:, 0].to(torch.int64), "top_indices": top_index,
+                "top_probabilities": top_prob, "clipwise_logits": logits}
+
     def forward_segment_embeddings(self, x, pool=3, sample_rate=None):
         """(B, L) -> (B, S, 768): the embedding of every 0.32 s segment -- forward_segments' rows in front of the head, i.e.
         forward_scene_embeddings' recipe (convnext.py:279-285) with the pooling over `pool` segments instead of the clip.  The
@@ -750,7 +761,8 @@ class ConvNeXt(nn.Module):
     def fit_head(self, data, target, sample_rate=None, **kw):
         """Train a new classifier head on this (frozen) backbone and install it (pytorch/finetune.py, fit_head): `data` is an
         (n, 768) tensor of scene embeddings, or a list of waveforms at `sample_rate`, whose scene embeddings are extracted
-        first (extract(..., what="scene", pack=True)); target: (n, N) bool / uint8 / float labels; **kw: fit_head's settings.
+        first (extract(..., what="scene", pack=True)); target: (n, N) bool / uint8 / float labels; **kw: fit_head's settings
+        (loss="ce", classes=N with (n,) integer labels trains a single-label head; read it with classify()).
         Afterwards head_audioset is an nn.Linear(768, N) with the fitted weights on the model's device -- the next forward
         runs it, state_dict() saves a checkpoint that from_pretrained loads as a fine-tuned model.  The model stays in eval
         mode.  Returns the HeadFit."""

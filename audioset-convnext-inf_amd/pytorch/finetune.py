@@ -10,6 +10,13 @@ Adam / AdamW, two launches per step:
     fit.weight, fit.bias, fit.loss                                     # (N, 768), (N,), (steps,) on the device
     fit.history                                                        # per epoch: mean loss and, with val=, mAP / AUC / d'
 
+A single-label head (one class per clip: ESC-50, "one folder per class") is trained with softmax cross-entropy instead:
+
+    fit = fit_head(emb, labels, classes=50, loss="ce", label_smoothing=0.1)        # labels (n,) integers, or (n, N) one-hot rows
+
+(acx_head_fit_step_ce: three launches per step), read with pytorch/classify.py softmax_topk and judged with
+classification_metrics.  loss="bce" (the default) is the path above, bit for bit.
+
 The epoch order is part of the contract: torch.randperm(n, generator=g) drawn once per epoch from ONE CPU generator
 g = torch.Generator().manual_seed(seed) (shuffle=False: arange); the last batch of an epoch is short unless drop_last.  The
 initial weights (init=None) come from a second generator seeded with `seed` too: trunc_normal_(std=0.02) weight, zero bias
@@ -83,14 +90,7 @@ def _lr_schedule(lr, steps):
 
 def _check_pair(emb, target, name="emb", tname="target"):
     """Shapes, dtypes, devices and values of one (embeddings, targets) pair; -> (emb, target tensor for the kernel, dtype code)."""
-    if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
-        raise ValueError("%s must be a (n, %d) tensor (got %s)" % (name, EMBED_DIM, getattr(emb, "shape", type(emb))))
-    if emb.dtype != torch.float32:
-        raise ValueError("%s must be float32 (got %s)" % (name, emb.dtype))
-    if not emb.is_cuda:
-        raise ValueError("%s must be a CUDA (HIP) tensor: fit_head runs on the GPU only (got device %s)" % (name, emb.device))
-    if emb.shape[0] < 1:
-        raise ValueError("%s holds no rows" % name)
+    emb = _check_emb(emb, name)
     if not isinstance(target, torch.Tensor) or target.dim() != 2 or target.shape[0] != emb.shape[0]:
         raise ValueError("%s must be a (%d, N) tensor (got %s)" % (tname, emb.shape[0], getattr(target, "shape", type(target))))
     if target.device != emb.device:
@@ -112,13 +112,71 @@ def _check_pair(emb, target, name="emb", tname="target"):
         raise ValueError("%s must be bool, an integer type or floating point (got %s)" % (tname, target.dtype))
     if t.stride(1) != 1 or t.stride(0) < N:
         t = t.contiguous()
+    return emb, t, (_ffi.TARGET_U8 if t.dtype == torch.uint8 else _ffi.TARGET_F32)
+
+
+def _check_emb(emb, name="emb", device=True):
+    """Shape, dtype and (device=True) device of the embeddings; -> emb in a layout the kernels take (unit column stride, 16-byte
+    aligned rows)."""
+    if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
+        raise ValueError("%s must be a (n, %d) tensor (got %s)" % (name, EMBED_DIM, getattr(emb, "shape", type(emb))))
+    if emb.dtype != torch.float32:
+        raise ValueError("%s must be float32 (got %s)" % (name, emb.dtype))
+    if emb.shape[0] < 1:
+        raise ValueError("%s holds no rows" % name)
+    if not device:
+        return emb
+    if not emb.is_cuda:
+        raise ValueError("%s must be a CUDA (HIP) tensor: fit_head runs on the GPU only (got device %s)" % (name, emb.device))
     if emb.stride(1) != 1 or emb.stride(0) < EMBED_DIM or emb.stride(0) % 4 or emb.data_ptr() % 16:
         emb = emb.contiguous()
-    return emb, t, (_ffi.TARGET_U8 if t.dtype == torch.uint8 else _ffi.TARGET_F32)
+    return emb
+
+
+def labels_of(target, n, classes=None, tname="target"):
+    """The (n,) int64 labels and the class count N of a loss="ce" target: (n,) integer class numbers (classes= required, every
+    label in [0, classes)), or (n, N) rows holding exactly one 1 and zeros otherwise.  Validates on the target's device (one
+    synchronisation) and raises ValueError; -> (labels, N)."""
+    if not isinstance(target, torch.Tensor):
+        target = torch.as_tensor(np.asarray(target))
+    if target.dim() == 1:
+        if target.shape[0] != n:
+            raise ValueError("%s must hold %d labels (got %s)" % (tname, n, tuple(target.shape)))
+        if target.dtype == torch.bool or target.dtype.is_floating_point or target.dtype.is_complex:
+            raise ValueError("%s of shape (n,) must be an integer tensor of class numbers (got %s)" % (tname, target.dtype))
+        if classes is None:
+            raise ValueError("classes= is required with (n,) integer labels")
+        N = int(classes)
+        if not 1 <= N <= _ffi.MAX_CLASSES:
+            raise ValueError("classes = %d (expected 1 .. %d)" % (N, _ffi.MAX_CLASSES))
+        lab = target.to(torch.int64)
+        if n and not bool(((lab >= 0) & (lab < N)).all()):
+            raise ValueError("%s holds labels outside [0, %d)" % (tname, N))
+        return lab.contiguous(), N
+    if target.dim() != 2 or target.shape[0] != n:
+        raise ValueError("%s must be (%d,) labels or (%d, N) one-hot rows (got %s)" % (tname, n, n, tuple(target.shape)))
+    N = int(target.shape[1])
+    if not 1 <= N <= _ffi.MAX_CLASSES:
+        raise ValueError("%s has N = %d classes (expected 1 .. %d)" % (tname, N, _ffi.MAX_CLASSES))
+    if classes is not None and int(classes) != N:
+        raise ValueError("classes = %d, but %s has %d columns" % (int(classes), tname, N))
+    t = target.to(torch.float32)
+    if not bool(((t == 0) | (t == 1)).all()):
+        raise ValueError("%s holds values other than 0 and 1" % tname)
+    if not bool((t.sum(dim=1) == 1).all()):
+        raise ValueError("%s must hold exactly one 1 per row for loss=\"ce\" (a row with none or several was found)" % tname)
+    return t.argmax(dim=1).to(torch.int64).contiguous(), N
 
 
 def _vp(t):
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _validate_ce(weight, bias, emb_val, labels_val):
+    from .classify import classification_metrics
+    N = int(weight.shape[0])
+    m = classification_metrics(labels_val, torch.addmm(bias, emb_val, weight.t()), k=min(5, N), confusion=False)
+    return {"accuracy": m.accuracy, "topk_accuracy": m.topk_accuracy, "macro_f1": m.macro_f1}
 
 
 def _validate(weight, bias, emb_val, target_val):
@@ -130,23 +188,50 @@ def _validate(weight, bias, emb_val, target_val):
 
 
 def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=True,
-             decoupled=False, init=None, seed=0, shuffle=True, drop_last=False, val=None):
+             decoupled=False, init=None, seed=0, shuffle=True, drop_last=False, val=None, loss="bce", label_smoothing=0.0,
+             classes=None):
     """Train an nn.Linear(768, N) head on (n, 768) scene embeddings with binary cross-entropy and Adam (decoupled=True: AdamW);
     the defaults are the reference's fine-tuning settings.  lr: a float, or one value per step.  init: None (seeded
     trunc_normal(std=0.02) weight, zero bias) or (weight, bias) to continue from a head; the moments always start at zero.
     val: (emb_val, target_val) -> per-epoch tagging_metrics in the history (this synchronises once per epoch).
+    loss="ce": softmax cross-entropy for a single-label head (F.cross_entropy with label_smoothing in [0, 1)); target is (n,)
+    integer labels with classes=N, or (n, N) one-hot rows (labels_of); val=(emb_val, labels_val) puts accuracy, topk_accuracy
+    (k = min(5, N)) and macro_f1 into the history.
     Returns HeadFit(weight, bias, loss, history): device tensors and a list of one dict per epoch, whose "loss" is a 0-d
     device tensor (the mean of the epoch's step losses)."""
+    if loss not in ("bce", "ce"):
+        raise ValueError("loss must be \"bce\" or \"ce\" (got %r)" % (loss,))
+    label_smoothing = float(label_smoothing)
+    ce = loss == "ce"
+    if not ce and label_smoothing != 0.0:
+        raise ValueError("label_smoothing belongs to loss=\"ce\"; binary cross-entropy takes soft targets instead")
+    if not ce and classes is not None:
+        raise ValueError("classes= belongs to loss=\"ce\"; with loss=\"bce\" the class count is the target's width")
+    if ce and not 0.0 <= label_smoothing < 1.0:
+        raise ValueError("label_smoothing must be in [0, 1) (got %r)" % (label_smoothing,))
     _check_hyper(epochs, batch_size, betas, eps, weight_decay)
-    emb, tgt, tdtype = _check_pair(emb, target)
-    n, N = int(emb.shape[0]), int(tgt.shape[1])
+    if ce:
+        _check_emb(emb, device=False)
+        tgt, N = labels_of(target, int(emb.shape[0]), classes)     # the target's own errors come before the GPU-only one
+        emb = _check_emb(emb)
+        if isinstance(target, torch.Tensor) and target.device != emb.device:
+            raise ValueError("target is on %s, emb on %s" % (target.device, emb.device))
+        tgt = tgt.to(emb.device)
+        n = int(emb.shape[0])
+    else:
+        emb, tgt, tdtype = _check_pair(emb, target)
+        n, N = int(emb.shape[0]), int(tgt.shape[1])
     device = emb.device
     if val is not None:
         if len(val) != 2:
             raise ValueError("val must be (emb_val, target_val)")
-        emb_val, target_val, _ = _check_pair(val[0], val[1], "emb_val", "target_val")
-        if target_val.shape[1] != N:
-            raise ValueError("target_val has %d classes, target %d" % (target_val.shape[1], N))
+        if ce:
+            emb_val = _check_emb(val[0], "emb_val")
+            target_val = labels_of(val[1], int(emb_val.shape[0]), N, "labels_val")[0].to(device)
+        else:
+            emb_val, target_val, _ = _check_pair(val[0], val[1], "emb_val", "target_val")
+            if target_val.shape[1] != N:
+                raise ValueError("target_val has %d classes, target %d" % (target_val.shape[1], N))
         if emb_val.device != device:
             raise ValueError("emb_val is on %s, emb on %s" % (emb_val.device, device))
     if init is None:
@@ -173,14 +258,20 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
         mom = torch.zeros((3, N, EMBED_DIM), dtype=torch.float32, device=device)
         momb = torch.zeros((3, N), dtype=torch.float32, device=device)
         status = torch.zeros(1, dtype=torch.int32, device=device)
-        ws_bytes = _ffi.head_fit_workspace_bytes(min(batch_size, n), N)
+        if ce:
+            ws_bytes = _ffi.head_fit_ce_workspace_bytes(min(batch_size, n), N)
+            step_fn = _ffi.lib().acx_head_fit_step_ce
+            fixed_a = (_vp(emb), emb.stride(0), n, _vp(tgt))
+        else:
+            ws_bytes = _ffi.head_fit_workspace_bytes(min(batch_size, n), N)
+            step_fn = _ffi.lib().acx_head_fit_step
+            fixed_a = (_vp(emb), emb.stride(0), n, _vp(tgt), tdtype, tgt.stride(0))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         hp = _ffi.adam(betas[0], betas[1], eps, weight_decay, amsgrad, decoupled)
-        step_fn = _ffi.lib().acx_head_fit_step
         stream = _ffi.stream_ptr(device)
-        fixed_a = (_vp(emb), emb.stride(0), n, _vp(tgt), tdtype, tgt.stride(0))
-        fixed_b = (N, _vp(W), _vp(b), _vp(mom[0]), _vp(mom[1]), _vp(mom[2]) if amsgrad else None, _vp(momb[0]), _vp(momb[1]),
-                   _vp(momb[2]) if amsgrad else None, ctypes.byref(hp))
+        fixed_b = ((N, label_smoothing) if ce else (N,)) + (
+            _vp(W), _vp(b), _vp(mom[0]), _vp(mom[1]), _vp(mom[2]) if amsgrad else None, _vp(momb[0]), _vp(momb[1]),
+            _vp(momb[2]) if amsgrad else None, ctypes.byref(hp))
         tail = (_vp(status), _vp(ws), ws_bytes, stream)
         order_ptr, loss_ptr = order.data_ptr(), loss.data_ptr()
         t = 0
@@ -193,6 +284,6 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
                 t += 1
             rec = {"epoch": e, "loss": loss[e * len(batches):(e + 1) * len(batches)].mean()}
             if val is not None:
-                rec.update(_validate(W, b, emb_val, target_val))
+                rec.update(_validate_ce(W, b, emb_val, target_val) if ce else _validate(W, b, emb_val, target_val))
             history.append(rec)
     return HeadFit(W, b, loss, history)

@@ -6,6 +6,7 @@ load / resample / pad a WAV, three forwards, labels above the 0.25 threshold).
     python demo_convnext.py --synthetic-weights --wav clip.wav        # no checkpoint at hand: seeded weights
     python demo_convnext.py --wav clip.wav --sed --top 10              # sound event detection: WHEN the top classes happen
     python demo_convnext.py --ckpt my_tagger/model.safetensors --wav clip.wav --thresholds my_tagger.thresholds.npy
+    python demo_convnext.py --ckpt my_classifier/model.safetensors --wav clip.wav --softmax --top 5     # a single-label head
 
 Prints the same lines as the reference (`# params`, sizes, predicted label indices, names, embedding shapes).
 """
@@ -38,7 +39,9 @@ def main():
                                          "computes them): used in place of --threshold for the labels and for --sed")
     ap.add_argument("--sed", action="store_true", help="also print the top classes by maximum framewise probability and their "
                                                        "events (the reference's sound_event_detection, inference.py:96-200)")
-    ap.add_argument("--top", type=int, default=10, help="--sed: how many classes")
+    ap.add_argument("--softmax", action="store_true", help="a single-label head (demo_finetune.py --loss ce): print the --top "
+                                                           "classes by softmax probability (ConvNeXt.classify)")
+    ap.add_argument("--top", type=int, default=10, help="--sed / --softmax: how many classes")
     args = ap.parse_args()
 
     if args.synthetic_weights:
@@ -94,6 +97,13 @@ def main():
         print(why)
     for l in sample_labels:
         print("%s: %.3f" % (ix_to_lb[l] if ix_to_lb else "class %d" % l, probs[0, l]))
+
+    if args.softmax:
+        with torch.no_grad():
+            res = model.classify(waveform, k=min(args.top, 64))
+        print("\nTop classes by softmax:\n")
+        for c, p in zip(res["top_indices"][0].tolist(), res["top_probabilities"][0].tolist()):
+            print("%s: %.3f" % (ix_to_lb[c] if ix_to_lb else "class %d" % c, p))
 
     with torch.no_grad():
         scene = model.forward_scene_embeddings(waveform)

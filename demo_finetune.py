@@ -6,11 +6,14 @@ as a checkpoint that ConvNeXt.from_pretrained loads as an N-class model.
     python demo_finetune.py --ckpt checkpoints/model.safetensors --data sounds/ --out my_tagger/        # sounds/<class>/*.wav
     python demo_finetune.py --ckpt ... --csv clips.csv --out my_tagger/        # lines: path.wav,label[;label...]
     python demo_finetune.py --synthetic --out /tmp/tagger                      # seeded weights and clips, no files needed
+    python demo_finetune.py --ckpt ... --data sounds/ --loss ce --out my_classifier/    # one class per clip: softmax cross-entropy
 
 Writes <out>/model.safetensors, <out>/model.pth ({"model": state_dict}) and <out>/labels.txt (one class name per line, in head
 order).  With a validation split, one decision threshold per class is chosen on it (the largest F1, metrics.operating_points)
 and written next to <out> as <out>.thresholds.npy -- demo_convnext.py --thresholds takes it.  16-bit PCM WAV files at any rate
-(resampled on the device)."""
+(resampled on the device).  --loss ce trains a single-label head (every clip needs exactly one label): it prints validation
+accuracy, top-5 accuracy and the five largest confusions, and writes no thresholds file -- read the model with
+ConvNeXt.classify / demo_convnext.py --softmax."""
 import argparse
 import csv
 import os
@@ -71,6 +74,8 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--weight-decay", type=float, default=0.0)
     ap.add_argument("--adamw", action="store_true")
+    ap.add_argument("--loss", choices=("bce", "ce"), default="bce", help="ce: softmax cross-entropy for one label per clip")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="--loss ce only")
     ap.add_argument("--val-fraction", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
@@ -114,18 +119,40 @@ def main():
     order = torch.randperm(len(waves), generator=torch.Generator().manual_seed(a.seed)).cuda()
     tr, va = order[n_val:], order[:n_val]
     target = target.cuda()
+    ce = a.loss == "ce"
+    if ce and not bool((target.sum(dim=1) == 1).all()):
+        sys.exit("--loss ce needs exactly one label per clip")
+    extra = dict(loss="ce", label_smoothing=a.label_smoothing) if ce else {}
     fit = model.fit_head(emb[tr], target[tr], epochs=a.epochs, batch_size=a.batch_size, lr=a.lr, weight_decay=a.weight_decay,
-                         decoupled=a.adamw, seed=a.seed, val=(emb[va], target[va]) if n_val else None)
+                         decoupled=a.adamw, seed=a.seed, val=(emb[va], target[va]) if n_val else None, **extra)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     for rec in fit.history:
-        print("epoch %2d  loss %.4f%s" % (rec["epoch"], float(rec["loss"]),
-                                          "  val mAP %.3f  AUC %.3f" % (rec["mAP"], rec["mAUC"]) if n_val else ""))
+        if ce:
+            val = "  val accuracy %.3f  top-5 %.3f  macro F1 %.3f" % (rec["accuracy"], rec["topk_accuracy"], rec["macro_f1"]) if n_val else ""
+        else:
+            val = "  val mAP %.3f  AUC %.3f" % (rec["mAP"], rec["mAUC"]) if n_val else ""
+        print("epoch %2d  loss %.4f%s" % (rec["epoch"], float(rec["loss"]), val))
     print("extraction %.2f s (%.0f clips/s), fit %.2f s (%d steps%s)" % (t1 - t0, len(waves) / (t1 - t0), t2 - t1, fit.loss.numel(),
                                                                            ", validation included" if n_val else ""))
 
     thresholds = None
-    if n_val:
+    if n_val and ce:
+        from audioset_convnext_inf_amd.pytorch.classify import classification_metrics
+        head = model.head_audioset
+        with torch.no_grad():
+            m = classification_metrics(target[va].int().argmax(dim=1), torch.addmm(head.bias, emb[va], head.weight.t()),
+                                       k=5, confusion=len(names) <= 4096)
+        print("val accuracy %.3f  top-%d accuracy %.3f  balanced accuracy %.3f  macro F1 %.3f  (%d clips)"
+              % (m.accuracy, m.k, m.topk_accuracy, m.balanced_accuracy, m.macro_f1, m.counted))
+        if m.confusion is not None:
+            conf = m.confusion.cpu().numpy().copy()
+            np.fill_diagonal(conf, 0)
+            for flat in np.argsort(conf, axis=None)[::-1][:5]:
+                t, p = divmod(int(flat), len(names))
+                if conf[t, p]:
+                    print("    %d x %s taken for %s" % (conf[t, p], names[t], names[p]))
+    elif n_val:
         # one threshold per class, chosen where the labels are: the largest F1 on the validation split
         import warnings
         from audioset_convnext_inf_amd.pytorch.metrics import operating_points

@@ -676,6 +676,53 @@ ACX_API int acx_head_fit_grad(const float* E, int64_t ld_e, int64_t n_rows_total
 ACX_API int acx_adam_update(float* param, const float* grad, float* m, float* v, float* vmax, int64_t n, const acx_adam* hp,
                             int64_t step_t, double lr, void* stream);
 
+/* Single-label heads: softmax cross-entropy instead of BCE.  labels: n_rows_total int64 class numbers (the label of batch row r
+ * is labels[idx[r]]); everything else as above.  One step with q_c = (1 - label_smoothing) [c = label] + label_smoothing /
+ * classes, per row m = max_c z_c, s = sum_c expf(z_c - m), p_c = expf(z_c - m) / s:
+ *   G = (p - q) / rows;   *loss_out = mean over rows of (m + log s) - sum_c q_c z_c
+ * -- F.cross_entropy(z, labels, label_smoothing=...), reduction mean -- then the update above.  Three launches: the logits to
+ * the workspace, the row pass, the update kernel of acx_head_fit_step.  Row sums run in a fixed order that depends on
+ * `classes` alone (depth ceil(classes / 64) + 6 up to 2048 classes, ceil(classes / 256) + 9 beyond); a row's z bits depend
+ * on that row alone -- not on `rows`, the other rows of the batch or the row's place in it (the logits launch picks its tile shape
+ * from `classes`) -- and so does its G up to the one factor 1 / rows: equal G bits at equal `rows`.  classes = 1 gives G = 0 and loss = 0 exactly.
+ *   acx_head_fit_ce_workspace_bytes: G + z + one loss partial per row.  acx_head_fit_step_ce / acx_head_fit_grad_ce: the
+ *   counterparts of acx_head_fit_step / acx_head_fit_grad, with the same contract (acx_head_fit_grad_ce, then acx_adam_update on
+ *   (W, dW) and (b, db), leaves the bits of acx_head_fit_step_ce).  label_smoothing outside [0, 1) is ACX_ERR_ARG.  A label
+ *   outside [0, classes) is a DATA error: it is clamped into the range and ACX_FIT_BAD_LABEL is ORed into *status. */
+#define ACX_FIT_BAD_LABEL 2
+ACX_API int acx_head_fit_ce_workspace_bytes(int64_t rows_max, int classes, size_t* out_bytes);
+ACX_API int acx_head_fit_step_ce(const float* E, int64_t ld_e, int64_t n_rows_total, const int64_t* labels, const int64_t* idx,
+                                 int64_t rows, int classes, double label_smoothing, float* W, float* b, float* mW, float* vW,
+                                 float* vmaxW, float* mb, float* vb, float* vmaxb, const acx_adam* hp, int64_t step_t, double lr,
+                                 float* loss_out, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_head_fit_grad_ce(const float* E, int64_t ld_e, int64_t n_rows_total, const int64_t* labels, const int64_t* idx,
+                                 int64_t rows, int classes, double label_smoothing, const float* W, const float* b, float* z,
+                                 float* G, float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes,
+                                 void* stream);
+
+/* ---- reading and judging a single-label head: softmax top-k, accuracy, confusion matrix ---------------------------------------
+ * Stateless, no workspace; logits (rows, classes) fp32 on the device with row stride ld >= classes.  Both calls clear *status
+ * (4 bytes) on `stream` first, then run one kernel; capturable.
+ *   acx_softmax_topk: probs[r][c] = expf(z_c - m) / s with m and s as above (probs may be NULL; row stride ld_p), and the k
+ *     best classes of each row ordered by logit descending, then class index ascending, -0.0 equal to +0.0 (the order of
+ *     acx_knn_search) -- decided on the logits, so exact.  top_prob[r][j] has the bits of probs[r][top_index[r][j]].  A row
+ *     holding a NaN or an infinity gets NaN probabilities and -1 indices and sets ACX_CLASSIFY_NONFINITE.  A row's outputs do
+ *     not depend on rows, its position or ld.  1 <= k <= min(classes, ACX_CLASSIFY_MAX_K), else ACX_ERR_ARG.
+ *   acx_classification_counts: over n rows with int64 labels: per_class[c] = {support, predicted, correct}, hits = {top-1,
+ *     top-k}, confusion[true][predicted] (may be NULL).  The prediction is the first index of the row maximum; the rank of the
+ *     true class y is #{c : z_c > z_y, or z_c = z_y and c < y}; a top-k hit is rank < k.  The outputs are cleared on `stream`
+ *     first and counted with integer atomics: the same counts in any order.  A row with a non-finite logit or a label outside
+ *     [0, classes) is counted nowhere and flagged.  confusion != NULL with classes > 4096 is ACX_ERR_UNSUPPORTED.
+ * ARGUMENT errors (before any launch, acx_last_error naming the argument): a null pointer, rows / n < 1, classes outside
+ * 1 .. ACX_MAX_CLASSES, ld < classes, ld_p < classes, k out of range; rows / n > 2^30 is ACX_ERR_UNSUPPORTED. */
+#define ACX_CLASSIFY_MAX_K 64
+#define ACX_CLASSIFY_NONFINITE 1
+#define ACX_CLASSIFY_BAD_LABEL 2
+ACX_API int acx_softmax_topk(const float* logits, int64_t ld, int64_t rows, int classes, int k, float* probs, int64_t ld_p,
+                             int32_t* top_index, float* top_prob, int32_t* status, void* stream);
+ACX_API int acx_classification_counts(const float* logits, int64_t ld, const int64_t* labels, int64_t n, int classes, int k,
+                                      int64_t* per_class, int64_t* hits, int64_t* confusion, int32_t* status, void* stream);
+
 /* ---- nearest-neighbour search over embeddings: top-k by dot product or cosine, and kNN tagging ----------------------------------
  * The reference's checkpoint is "for audio tagging and embedding extraction"; this is what the embeddings are extracted for:
  * query by example, and the kNN probe of a frozen representation.  Stateless: the caller owns every buffer (all on the device).
