@@ -230,6 +230,19 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def vp(t):
+    """Raw pointer of a torch tensor or None, whatever its strides.  ptr() is for calls that take no stride and so need a
+    contiguous tensor; vp() is for the analysis calls, which pass the row stride along and read views where they lie."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _query(fn, ctype, *args):
+    """The value a host-only query writes through its last parameter: fn(*args, &out) checked, -> out."""
+    out = ctype()
+    check(fn(*args, ctypes.byref(out)))
+    return out.value
+
+
 def stream_ptr(device):
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
@@ -286,18 +299,14 @@ class Context:
 
     def num_classes(self):
         """N, the class count of the finalized head (acx_num_classes)."""
-        out = _c_int()
-        check(lib().acx_num_classes(self._h, ctypes.byref(out)))
-        return out.value
+        return _query(lib().acx_num_classes, _c_int, self._h)
 
     def _workspace_bytes(self, geometry, kind, *args):
         """acx_workspace_bytes<geometry> for an output kind: a key of MODES (or the acx_mode value itself), or a key of
         SEG_WHAT, which goes to the _segments form of the call."""
         seg = kind in SEG_WHAT
         fn = getattr(lib(), "acx_workspace_bytes" + ("_segments" if seg else "") + geometry)
-        out = _c_sz()
-        check(fn(self._h, *args, SEG_WHAT[kind] if seg else int(MODES.get(kind, kind)), ctypes.byref(out)))
-        return out.value
+        return _query(fn, _c_sz, self._h, *args, SEG_WHAT[kind] if seg else int(MODES.get(kind, kind)))
 
     def workspace_bytes(self, B, L, kind):
         return self._workspace_bytes("", kind, int(B), int(L))
@@ -311,9 +320,7 @@ class Context:
 
     def sub_batches(self, B):
         """How many sub-batches (on separate streams) a forward of B clips runs as (acx_sub_batches)."""
-        out = _c_int()
-        check(lib().acx_sub_batches(self._h, int(B), ctypes.byref(out)))
-        return out.value
+        return _query(lib().acx_sub_batches, _c_int, self._h, int(B))
 
     # ---- the C ABI's own collective (include/acx.h): RCCL all-gather without torch.distributed ----
     @staticmethod
@@ -398,17 +405,13 @@ def resample_taps(orig_hz, new_hz):
 
 
 def resampled_length(orig_hz, new_hz, L):
-    out = _c_i64()
-    check(lib().acx_resampled_length(int(orig_hz), int(new_hz), int(L), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_resampled_length, _c_i64, int(orig_hz), int(new_hz), int(L))
 
 
 def window_count(lengths, window, hop):
     """Windows of `window` samples every `hop` samples over recordings of `lengths` samples (acx_window_count; host only)."""
     lens = (_c_i64 * max(1, len(lengths)))(*[int(n) for n in lengths])
-    out = _c_i64()
-    check(lib().acx_window_count(lens, len(lengths), int(window), int(hop), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_window_count, _c_i64, lens, len(lengths), int(window), int(hop))
 
 
 TARGET_F32, TARGET_U8 = 0, 1                 # enum acx_target_dtype
@@ -421,9 +424,7 @@ WEIGHTED_MAX_N = 32768                        # acx_weighted_metrics: rows per c
 
 def metrics_workspace_bytes(n, classes):
     """Workspace of acx_tagging_metrics for n rows of `classes` scores (host only)."""
-    out = _c_sz()
-    check(lib().acx_metrics_workspace_bytes(int(n), int(classes), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_metrics_workspace_bytes, _c_sz, int(n), int(classes))
 
 
 def tagging_metrics(scores, ld_scores, target, target_dtype, ld_target, n, classes, ap, auc, dprime, status, ws, stream):
@@ -453,9 +454,7 @@ def bootstrap_weights(seed, first_replicate, replicates, n, weights, ld_w, strea
 
 def weighted_metrics_workspace_bytes(n, classes):
     """Workspace of acx_weighted_metrics for n rows of `classes` scores (host only)."""
-    out = _c_sz()
-    check(lib().acx_weighted_metrics_workspace_bytes(int(n), int(classes), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_weighted_metrics_workspace_bytes, _c_sz, int(n), int(classes))
 
 
 def weighted_metrics(scores, ld_scores, target, target_dtype, ld_target, n, classes, weights, ld_w, replicates, ap, auc, dprime,
@@ -475,9 +474,7 @@ def adam(beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, amsgrad=True, decou
 
 def head_fit_workspace_bytes(rows_max, classes):
     """Workspace of acx_head_fit_step / acx_head_fit_grad for steps of up to rows_max rows (host only)."""
-    out = _c_sz()
-    check(lib().acx_head_fit_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_head_fit_workspace_bytes, _c_sz, int(rows_max), int(classes))
 
 
 FIT_BAD_LABEL = 2                              # acx_head_fit_step_ce / acx_head_fit_grad_ce: a label outside [0, classes)
@@ -485,9 +482,7 @@ FIT_BAD_LABEL = 2                              # acx_head_fit_step_ce / acx_head
 
 def head_fit_ce_workspace_bytes(rows_max, classes):
     """Workspace of acx_head_fit_step_ce / acx_head_fit_grad_ce for steps of up to rows_max rows (host only)."""
-    out = _c_sz()
-    check(lib().acx_head_fit_ce_workspace_bytes(int(rows_max), int(classes), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_head_fit_ce_workspace_bytes, _c_sz, int(rows_max), int(classes))
 
 
 CLASSIFY_MAX_K = 64                            # ACX_CLASSIFY_MAX_K
@@ -524,16 +519,12 @@ KNN_WEIGHTS = {"uniform": KNN_UNIFORM, "similarity": KNN_SIMILARITY}
 
 def knn_workspace_bytes(nq, n, k):
     """Workspace of acx_knn_search for nq queries, n database rows and k neighbours (host only)."""
-    out = _c_sz()
-    check(lib().acx_knn_workspace_bytes(int(nq), int(n), int(k), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_knn_workspace_bytes, _c_sz, int(nq), int(n), int(k))
 
 
 def knn_slices(nq, n, k):
     """Slices of the database rows a search of this shape runs as (acx_knn_slices; host only)."""
-    out = _c_int()
-    check(lib().acx_knn_slices(int(nq), int(n), int(k), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_knn_slices, _c_int, int(nq), int(n), int(k))
 
 
 def knn_row_norms(x, ld, n, dim, inv_norm, status, stream):
@@ -569,9 +560,7 @@ def event_params(threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=
 
 def events_workspace_bytes(B, N):
     """Workspace of acx_decode_events / acx_decode_events_varlen for B clips of N classes (host only)."""
-    out = _c_sz()
-    check(lib().acx_events_workspace_bytes(int(B), int(N), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_events_workspace_bytes, _c_sz, int(B), int(N))
 
 
 SCORE_BAD_TABLE = 1                           # bit of the status word of acx_score_events / acx_score_segments
@@ -586,9 +575,7 @@ def event_collar(t_collar=0.2, percentage_of_length=0.5, evaluate_onset=True, ev
 
 def segment_count(L):
     """S, the segments of a clip of L samples (acx_segment_count; host only)."""
-    out = _c_int()
-    check(lib().acx_segment_count(int(L), ctypes.byref(out)))
-    return out.value
+    return _query(lib().acx_segment_count, _c_int, int(L))
 
 
 def stage_hw(L, stage):
@@ -598,9 +585,7 @@ def stage_hw(L, stage):
 
 
 def num_frames(L):
-    t = _c_int()
-    check(lib().acx_num_frames(int(L), ctypes.byref(t)))
-    return t.value
+    return _query(lib().acx_num_frames, _c_int, int(L))
 
 
 def stream_schedule(window, hop, orig_hz, pushed, closed):

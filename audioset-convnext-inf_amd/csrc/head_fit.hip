@@ -391,26 +391,40 @@ static int adam_scalars(const char* who, const acx_adam* hp, int64_t t, double l
     return ACX_OK;
 }
 
-struct FitCall {        // the arguments the step and its component form share
-    const float* E; int64_t ld_e; int64_t n_total; const void* Y; int y_dtype; int64_t ld_y; const int64_t* idx; int64_t rows;
-    int classes; const float* W; const float* b; int32_t* status; void* ws; size_t ws_bytes;
+struct FitCall {        // the arguments a step and its component form share, for either loss
+    const float* E; int64_t ld_e; int64_t n_total;
+    const void* Y; const char* y_name;      // target (BCE) or labels (cross-entropy), and the name its null message prints
+    int y_dtype; int64_t ld_y;              // BCE only
+    double eps;                             // cross-entropy only: label_smoothing
+    const int64_t* idx; int64_t rows; int classes; const float* W; const float* b; int32_t* status; void* ws; size_t ws_bytes;
 };
 
-static int fit_check_call(const char* who, const FitCall& c, size_t* part_off) {
+// The checks of both losses, in two pieces: a loss has checks of its own between them, and its workspace check after them.
+static int fit_check_pointers(const char* who, const FitCall& c) {
     if (!c.E) ACX_FAIL(ACX_ERR_ARG, "%s: E is null", who);
-    if (!c.Y) ACX_FAIL(ACX_ERR_ARG, "%s: target is null", who);
+    if (!c.Y) ACX_FAIL(ACX_ERR_ARG, "%s: %s is null", who, c.y_name);
     if (!c.idx) ACX_FAIL(ACX_ERR_ARG, "%s: idx is null", who);
     if (!c.W) ACX_FAIL(ACX_ERR_ARG, "%s: W is null", who);
     if (!c.b) ACX_FAIL(ACX_ERR_ARG, "%s: b is null", who);
     if (!c.status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
     if (!c.ws) ACX_FAIL(ACX_ERR_ARG, "%s: workspace is null", who);
-    if (c.y_dtype != ACX_TARGET_F32 && c.y_dtype != ACX_TARGET_U8)
-        ACX_FAIL(ACX_ERR_ARG, "%s: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", who, c.y_dtype);
+    return ACX_OK;
+}
+
+static int fit_check_rows(const char* who, const FitCall& c) {
     ACX_TRY(fit_check_shape(who, c.rows, c.classes));
     if (c.n_total < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n_rows_total = %lld (expected >= 1)", who, (long long)c.n_total);
     if (c.ld_e < kFitK) ACX_FAIL(ACX_ERR_ARG, "%s: ld_e = %lld is shorter than a row of %d", who, (long long)c.ld_e, kFitK);
     if ((c.ld_e & 3) || (reinterpret_cast<uintptr_t>(c.E) & 15) || (reinterpret_cast<uintptr_t>(c.W) & 15))
         ACX_FAIL(ACX_ERR_ARG, "%s: E and W must be 16-byte aligned and ld_e a multiple of 4 (ld_e = %lld)", who, (long long)c.ld_e);
+    return ACX_OK;
+}
+
+static int fit_check_call(const char* who, const FitCall& c, size_t* part_off) {
+    ACX_TRY(fit_check_pointers(who, c));
+    if (c.y_dtype != ACX_TARGET_F32 && c.y_dtype != ACX_TARGET_U8)
+        ACX_FAIL(ACX_ERR_ARG, "%s: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", who, c.y_dtype);
+    ACX_TRY(fit_check_rows(who, c));
     if (c.ld_y < c.classes)
         ACX_FAIL(ACX_ERR_ARG, "%s: ld_target = %lld is shorter than %d classes", who, (long long)c.ld_y, c.classes);
     size_t need;
@@ -418,8 +432,49 @@ static int fit_check_call(const char* who, const FitCall& c, size_t* part_off) {
     return check_workspace_for(who, c.ws, c.ws_bytes, need);
 }
 
-// The update launch both losses share: u complete except for its tile count.
-static int fit_launch_update(FitUpdP u, int N, int cus, bool apply, hipStream_t s) {
+static int fit_ce_check_call(const char* who, const FitCall& c, size_t* z_off, size_t* part_off) {
+    ACX_TRY(fit_check_pointers(who, c));
+    if (!(c.eps >= 0.0 && c.eps < 1.0)) ACX_FAIL(ACX_ERR_ARG, "%s: label_smoothing = %g (expected 0 <= label_smoothing < 1)", who, c.eps);
+    ACX_TRY(fit_check_rows(who, c));
+    size_t need;
+    fit_ce_layout(c.rows, c.classes, z_off, part_off, &need);
+    return check_workspace_for(who, c.ws, c.ws_bytes, need);
+}
+
+// What the two _step entries check after the call itself, and the APPLY half of the update's arguments.
+static int fit_step_args(const char* who, float* W, float* b, float* mW, float* vW, float* vmaxW, float* mb, float* vb, float* vmaxb,
+                         const acx_adam* hp, int64_t step_t, double lr, const float* loss_out, FitUpdP* u) {
+    if (!mW || !vW || !mb || !vb) ACX_FAIL(ACX_ERR_ARG, "%s: a moment buffer (mW, vW, mb, vb) is null", who);
+    if (!loss_out) ACX_FAIL(ACX_ERR_ARG, "%s: loss_out is null", who);
+    ACX_TRY(adam_scalars(who, hp, step_t, lr, &u->a));
+    if (hp->amsgrad && (!vmaxW || !vmaxb)) ACX_FAIL(ACX_ERR_ARG, "%s: vmaxW / vmaxb is null with hp->amsgrad set", who);
+    u->W = W; u->mW = mW; u->vW = vW; u->vmaxW = vmaxW;
+    u->b = b; u->mb = mb; u->vb = vb; u->vmaxb = vmaxb;
+    return ACX_OK;
+}
+
+// The same for the two _grad entries: the !APPLY half.
+static int fit_grad_args(const char* who, const float* z, const float* G, float* dW, float* db, const float* loss, FitUpdP* u) {
+    if (!z || !G || !dW || !db || !loss) ACX_FAIL(ACX_ERR_ARG, "%s: an output (z, G, dW, db, loss) is null", who);
+    u->dW = dW; u->db = db;
+    return ACX_OK;
+}
+
+// The arguments of the first matrix launch that both losses set; BCE adds its targets, G, part and inv.
+static FitGradP fit_grad_params(const FitCall& c, float* z) {
+    FitGradP g{};
+    g.E = c.E; g.ld_e = c.ld_e; g.n_total = c.n_total;
+    g.idx = reinterpret_cast<const long long*>(c.idx); g.rows = (int)c.rows; g.N = c.classes;
+    g.W = c.W; g.b = c.b; g.z = z; g.status = (int*)c.status;
+    return g;
+}
+
+// The update launch both losses share: u holds its APPLY or !APPLY half (fit_step_args / fit_grad_args).
+static int fit_launch_update(FitUpdP u, const FitCall& c, const float* G, const float* part, int nparts, float* loss, float inv,
+                             int cus, bool apply, hipStream_t s) {
+    const int N = c.classes;
+    u.E = c.E; u.ld_e = c.ld_e; u.n_total = c.n_total; u.idx = reinterpret_cast<const long long*>(c.idx); u.rows = (int)c.rows;
+    u.N = N; u.G = G; u.part = part; u.nparts = nparts; u.loss = loss; u.inv = inv;
     const bool u32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
     const int us = u32 ? 32 : 16;
     u.tiles = ((N + us - 1) / us) * (kFitK / us);
@@ -437,16 +492,14 @@ static int fit_launch_update(FitUpdP u, int N, int cus, bool apply, hipStream_t 
 
 // The two launches.  apply: W, b and the moments updated in place (u.a set); otherwise dW / db written.  The tile shape of each
 // launch depends on (rows, classes, CUs) alone, so the step and its component form run the same kernels.
-static int fit_launch(const FitCall& c, float* z, float* G, float* part, FitUpdP u, bool apply, float* loss, hipStream_t s) {
+static int fit_launch(const FitCall& c, float* z, float* G, float* part, const FitUpdP& u, bool apply, float* loss, hipStream_t s) {
     int cus = 0;
     ACX_TRY(cu_count_of_current_device(&cus));
     const int rows = (int)c.rows, N = c.classes;
     const float inv = (float)(1.0 / ((double)rows * (double)N));
-    FitGradP g;
-    g.E = c.E; g.ld_e = c.ld_e; g.n_total = c.n_total;
+    FitGradP g = fit_grad_params(c, z);
     g.Y = c.Y; g.y_u8 = c.y_dtype == ACX_TARGET_U8; g.ld_y = c.ld_y;
-    g.idx = reinterpret_cast<const long long*>(c.idx); g.rows = rows; g.N = N;
-    g.W = c.W; g.b = c.b; g.z = z; g.G = G; g.part = part; g.status = (int*)c.status; g.inv = inv;
+    g.G = G; g.part = part; g.inv = inv;
     const bool g32 = (long long)((rows + 31) / 32) * ((N + 31) / 32) >= cus;
     const int gs = g32 ? 32 : 16;
     g.tiles_n = (N + gs - 1) / gs;
@@ -454,48 +507,18 @@ static int fit_launch(const FitCall& c, float* z, float* G, float* part, FitUpdP
     if (g32) launch_kernel(&fit_grad_kernel<32>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
     else launch_kernel(&fit_grad_kernel<16>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
     ACX_HIP(hipGetLastError());
-
-    u.E = c.E; u.ld_e = c.ld_e; u.n_total = c.n_total; u.idx = g.idx; u.rows = rows; u.N = N;
-    u.G = G; u.part = part; u.nparts = gtiles; u.loss = loss; u.inv = inv;
-    return fit_launch_update(u, N, cus, apply, s);
-}
-
-struct FitCeCall {      // the arguments the cross-entropy step and its component form share
-    const float* E; int64_t ld_e; int64_t n_total; const int64_t* labels; const int64_t* idx; int64_t rows; int classes;
-    double eps; const float* W; const float* b; int32_t* status; void* ws; size_t ws_bytes;
-};
-
-static int fit_ce_check_call(const char* who, const FitCeCall& c, size_t* z_off, size_t* part_off) {
-    if (!c.E) ACX_FAIL(ACX_ERR_ARG, "%s: E is null", who);
-    if (!c.labels) ACX_FAIL(ACX_ERR_ARG, "%s: labels is null", who);
-    if (!c.idx) ACX_FAIL(ACX_ERR_ARG, "%s: idx is null", who);
-    if (!c.W) ACX_FAIL(ACX_ERR_ARG, "%s: W is null", who);
-    if (!c.b) ACX_FAIL(ACX_ERR_ARG, "%s: b is null", who);
-    if (!c.status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
-    if (!c.ws) ACX_FAIL(ACX_ERR_ARG, "%s: workspace is null", who);
-    if (!(c.eps >= 0.0 && c.eps < 1.0)) ACX_FAIL(ACX_ERR_ARG, "%s: label_smoothing = %g (expected 0 <= label_smoothing < 1)", who, c.eps);
-    ACX_TRY(fit_check_shape(who, c.rows, c.classes));
-    if (c.n_total < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n_rows_total = %lld (expected >= 1)", who, (long long)c.n_total);
-    if (c.ld_e < kFitK) ACX_FAIL(ACX_ERR_ARG, "%s: ld_e = %lld is shorter than a row of %d", who, (long long)c.ld_e, kFitK);
-    if ((c.ld_e & 3) || (reinterpret_cast<uintptr_t>(c.E) & 15) || (reinterpret_cast<uintptr_t>(c.W) & 15))
-        ACX_FAIL(ACX_ERR_ARG, "%s: E and W must be 16-byte aligned and ld_e a multiple of 4 (ld_e = %lld)", who, (long long)c.ld_e);
-    size_t need;
-    fit_ce_layout(c.rows, c.classes, z_off, part_off, &need);
-    return check_workspace_for(who, c.ws, c.ws_bytes, need);
+    return fit_launch_update(u, c, G, part, gtiles, loss, inv, cus, apply, s);
 }
 
 // The three launches.  BOTH matrix launches take the update kernel's tile rule, a function of (classes, CUs) alone: the logits
 // of a row then have the same bits in every batch, whatever `rows` is (the two tile shapes add the 768 products in different
 // orders, so a rule that looked at `rows`, as fit_launch's does for BCE, would let the short last batch of an epoch change them).
-static int fit_ce_launch(const FitCeCall& c, float* z, float* G, float* part, FitUpdP u, bool apply, float* loss, hipStream_t s) {
+static int fit_ce_launch(const FitCall& c, float* z, float* G, float* part, const FitUpdP& u, bool apply, float* loss, hipStream_t s) {
     int cus = 0;
     ACX_TRY(cu_count_of_current_device(&cus));
     const int rows = (int)c.rows, N = c.classes;
     const float inv = (float)(1.0 / (double)rows);
-    FitGradP g{};
-    g.E = c.E; g.ld_e = c.ld_e; g.n_total = c.n_total;
-    g.idx = reinterpret_cast<const long long*>(c.idx); g.rows = rows; g.N = N;
-    g.W = c.W; g.b = c.b; g.z = z; g.status = (int*)c.status;
+    FitGradP g = fit_grad_params(c, z);
     const bool g32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
     const int gs = g32 ? 32 : 16;
     g.tiles_n = (N + gs - 1) / gs;
@@ -505,16 +528,13 @@ static int fit_ce_launch(const FitCeCall& c, float* z, float* G, float* part, Fi
     ACX_HIP(hipGetLastError());
 
     FitCeRowP r;
-    r.z = z; r.labels = reinterpret_cast<const long long*>(c.labels); r.idx = g.idx; r.n_total = c.n_total; r.rows = rows; r.N = N;
+    r.z = z; r.labels = static_cast<const long long*>(c.Y); r.idx = g.idx; r.n_total = c.n_total; r.rows = rows; r.N = N;
     r.q_hit = (float)((1.0 - c.eps) + c.eps / N); r.q_miss = (float)(c.eps / N); r.ome = (float)(1.0 - c.eps);
     r.inv = inv; r.G = G; r.part = part; r.status = (int*)c.status;
     if (N <= kSoftWaveMaxN) launch_kernel(&fit_ce_row_kernel<64>, dim3((rows + 3) / 4), dim3(kFitThreads), 0, s, r);
     else launch_kernel(&fit_ce_row_kernel<256>, dim3(rows), dim3(kFitThreads), 0, s, r);
     ACX_HIP(hipGetLastError());
-
-    u.E = c.E; u.ld_e = c.ld_e; u.n_total = c.n_total; u.idx = g.idx; u.rows = rows; u.N = N;
-    u.G = G; u.part = part; u.nparts = rows; u.loss = loss; u.inv = inv;
-    return fit_launch_update(u, N, cus, apply, s);
+    return fit_launch_update(u, c, G, part, rows, loss, inv, cus, apply, s);
 }
 
 }  // namespace acx
@@ -536,16 +556,12 @@ int acx_head_fit_step(const float* E, int64_t ld_e, int64_t n_rows_total, const 
                       float* vmaxW, float* mb, float* vb, float* vmaxb, const acx_adam* hp, int64_t step_t, double lr,
                       float* loss_out, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
     static const char* who = "acx_head_fit_step";
-    const FitCall c{E, ld_e, n_rows_total, target, target_dtype, ld_target, idx, rows, classes, W, b, status, ws, ws_bytes};
+    const FitCall c{E, ld_e, n_rows_total, target, "target", target_dtype, ld_target, 0.0, idx, rows, classes, W, b, status, ws,
+                    ws_bytes};
     size_t part_off;
     ACX_TRY(fit_check_call(who, c, &part_off));
-    if (!mW || !vW || !mb || !vb) ACX_FAIL(ACX_ERR_ARG, "%s: a moment buffer (mW, vW, mb, vb) is null", who);
-    if (!loss_out) ACX_FAIL(ACX_ERR_ARG, "%s: loss_out is null", who);
     FitUpdP u{};
-    ACX_TRY(adam_scalars(who, hp, step_t, lr, &u.a));
-    if (hp->amsgrad && (!vmaxW || !vmaxb)) ACX_FAIL(ACX_ERR_ARG, "%s: vmaxW / vmaxb is null with hp->amsgrad set", who);
-    u.W = W; u.mW = mW; u.vW = vW; u.vmaxW = vmaxW;
-    u.b = b; u.mb = mb; u.vb = vb; u.vmaxb = vmaxb;
+    ACX_TRY(fit_step_args(who, W, b, mW, vW, vmaxW, mb, vb, vmaxb, hp, step_t, lr, loss_out, &u));
     char* w = static_cast<char*>(ws);
     return fit_launch(c, nullptr, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + part_off), u, true, loss_out,
                       (hipStream_t)stream);
@@ -555,12 +571,12 @@ int acx_head_fit_grad(const float* E, int64_t ld_e, int64_t n_rows_total, const 
                       int64_t ld_target, const int64_t* idx, int64_t rows, int classes, const float* W, const float* b, float* z,
                       float* G, float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
     static const char* who = "acx_head_fit_grad";
-    const FitCall c{E, ld_e, n_rows_total, target, target_dtype, ld_target, idx, rows, classes, W, b, status, ws, ws_bytes};
+    const FitCall c{E, ld_e, n_rows_total, target, "target", target_dtype, ld_target, 0.0, idx, rows, classes, W, b, status, ws,
+                    ws_bytes};
     size_t part_off;
     ACX_TRY(fit_check_call(who, c, &part_off));
-    if (!z || !G || !dW || !db || !loss) ACX_FAIL(ACX_ERR_ARG, "%s: an output (z, G, dW, db, loss) is null", who);
     FitUpdP u{};
-    u.dW = dW; u.db = db;
+    ACX_TRY(fit_grad_args(who, z, G, dW, db, loss, &u));
     return fit_launch(c, z, G, reinterpret_cast<float*>(static_cast<char*>(ws) + part_off), u, false, loss, (hipStream_t)stream);
 }
 
@@ -577,16 +593,11 @@ int acx_head_fit_step_ce(const float* E, int64_t ld_e, int64_t n_rows_total, con
                          float* mb, float* vb, float* vmaxb, const acx_adam* hp, int64_t step_t, double lr, float* loss_out,
                          int32_t* status, void* ws, size_t ws_bytes, void* stream) {
     static const char* who = "acx_head_fit_step_ce";
-    const FitCeCall c{E, ld_e, n_rows_total, labels, idx, rows, classes, label_smoothing, W, b, status, ws, ws_bytes};
+    const FitCall c{E, ld_e, n_rows_total, labels, "labels", 0, 0, label_smoothing, idx, rows, classes, W, b, status, ws, ws_bytes};
     size_t z_off, part_off;
     ACX_TRY(fit_ce_check_call(who, c, &z_off, &part_off));
-    if (!mW || !vW || !mb || !vb) ACX_FAIL(ACX_ERR_ARG, "%s: a moment buffer (mW, vW, mb, vb) is null", who);
-    if (!loss_out) ACX_FAIL(ACX_ERR_ARG, "%s: loss_out is null", who);
     FitUpdP u{};
-    ACX_TRY(adam_scalars(who, hp, step_t, lr, &u.a));
-    if (hp->amsgrad && (!vmaxW || !vmaxb)) ACX_FAIL(ACX_ERR_ARG, "%s: vmaxW / vmaxb is null with hp->amsgrad set", who);
-    u.W = W; u.mW = mW; u.vW = vW; u.vmaxW = vmaxW;
-    u.b = b; u.mb = mb; u.vb = vb; u.vmaxb = vmaxb;
+    ACX_TRY(fit_step_args(who, W, b, mW, vW, vmaxW, mb, vb, vmaxb, hp, step_t, lr, loss_out, &u));
     char* w = static_cast<char*>(ws);
     return fit_ce_launch(c, reinterpret_cast<float*>(w + z_off), reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + part_off),
                          u, true, loss_out, (hipStream_t)stream);
@@ -596,12 +607,11 @@ int acx_head_fit_grad_ce(const float* E, int64_t ld_e, int64_t n_rows_total, con
                          int64_t rows, int classes, double label_smoothing, const float* W, const float* b, float* z, float* G,
                          float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
     static const char* who = "acx_head_fit_grad_ce";
-    const FitCeCall c{E, ld_e, n_rows_total, labels, idx, rows, classes, label_smoothing, W, b, status, ws, ws_bytes};
+    const FitCall c{E, ld_e, n_rows_total, labels, "labels", 0, 0, label_smoothing, idx, rows, classes, W, b, status, ws, ws_bytes};
     size_t z_off, part_off;
     ACX_TRY(fit_ce_check_call(who, c, &z_off, &part_off));
-    if (!z || !G || !dW || !db || !loss) ACX_FAIL(ACX_ERR_ARG, "%s: an output (z, G, dW, db, loss) is null", who);
     FitUpdP u{};
-    u.dW = dW; u.db = db;
+    ACX_TRY(fit_grad_args(who, z, G, dW, db, loss, &u));
     return fit_ce_launch(c, z, G, reinterpret_cast<float*>(static_cast<char*>(ws) + part_off), u, false, loss, (hipStream_t)stream);
 }
 

@@ -17,16 +17,13 @@ Definitions (the *_host functions below are their float64 / exact evaluation in 
                  support, precision = correct / predicted (0 for a class never predicted), F1 = 2 correct / (support + predicted).
   balanced_accuracy, macro_f1   means of recall / F1 over the classes WITH support, as sklearn's balanced_accuracy_score.
 A row holding a NaN or an infinity, or a label outside [0, N), is counted nowhere; check() raises for them."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _ffi
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from .._ffi import vp
+from . import _inputs
+from .metrics import _ratio
 
 
 def _check_logits(logits, name="logits"):
@@ -41,9 +38,7 @@ def _check_logits(logits, name="logits"):
         raise ValueError("%s holds no rows" % name)
     if not 1 <= N <= _ffi.MAX_CLASSES:
         raise ValueError("%s has N = %d classes (expected 1 .. %d)" % (name, N, _ffi.MAX_CLASSES))
-    if logits.stride(1) != 1 or logits.stride(0) < N:
-        logits = logits.contiguous()
-    return logits, rows, N
+    return _inputs.rows(logits), rows, N
 
 
 def _check_k(k, N):
@@ -67,14 +62,9 @@ def softmax_topk(logits, k=5, probabilities=True, status=None):
         top_index = torch.empty((rows, k), dtype=torch.int32, device=dev)
         if status is None:
             status = torch.empty(1, dtype=torch.int32, device=dev)
-        _ffi.softmax_topk(_vp(logits), logits.stride(0), rows, N, k, _vp(probs), N, _vp(top_index), _vp(top_prob), _vp(status),
+        _ffi.softmax_topk(vp(logits), logits.stride(0), rows, N, k, vp(probs), N, vp(top_index), vp(top_prob), vp(status),
                           _ffi.stream_ptr(dev))
     return probs, top_prob, top_index
-
-
-def _ratio(num, den):
-    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
-    return np.divide(num, den, out=np.zeros_like(num), where=den > 0)
 
 
 class _Summary:
@@ -175,8 +165,8 @@ def classification_metrics(labels, logits, k=5, confusion=True):
         hits = torch.empty(2, dtype=torch.int64, device=dev)
         conf = torch.empty((N, N), dtype=torch.int64, device=dev) if confusion else None
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        _ffi.classification_counts(_vp(logits), logits.stride(0), _vp(lab), n, N, k, _vp(per_class), _vp(hits), _vp(conf),
-                                   _vp(status), _ffi.stream_ptr(dev))
+        _ffi.classification_counts(vp(logits), logits.stride(0), vp(lab), n, N, k, vp(per_class), vp(hits), vp(conf),
+                                   vp(status), _ffi.stream_ptr(dev))
     return ClassificationMetrics(per_class, hits, conf, status, n, k)
 
 

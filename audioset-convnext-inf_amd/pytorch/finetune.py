@@ -28,6 +28,8 @@ import numpy as np
 import torch
 
 from .. import _ffi
+from .._ffi import vp
+from . import _inputs
 
 EMBED_DIM = 768
 HeadFit = namedtuple("HeadFit", ["weight", "bias", "loss", "history"])
@@ -110,9 +112,8 @@ def _check_pair(emb, target, name="emb", tname="target"):
         t = target if target.dtype == torch.uint8 else target.to(torch.uint8)
     else:
         raise ValueError("%s must be bool, an integer type or floating point (got %s)" % (tname, target.dtype))
-    if t.stride(1) != 1 or t.stride(0) < N:
-        t = t.contiguous()
-    return emb, t, (_ffi.TARGET_U8 if t.dtype == torch.uint8 else _ffi.TARGET_F32)
+    t = _inputs.rows(t)
+    return emb, t, _inputs.target_code(t)
 
 
 def _check_emb(emb, name="emb", device=True):
@@ -128,9 +129,7 @@ def _check_emb(emb, name="emb", device=True):
         return emb
     if not emb.is_cuda:
         raise ValueError("%s must be a CUDA (HIP) tensor: fit_head runs on the GPU only (got device %s)" % (name, emb.device))
-    if emb.stride(1) != 1 or emb.stride(0) < EMBED_DIM or emb.stride(0) % 4 or emb.data_ptr() % 16:
-        emb = emb.contiguous()
-    return emb
+    return _inputs.rows(emb, align4=True)
 
 
 def labels_of(target, n, classes=None, tname="target"):
@@ -168,10 +167,6 @@ def labels_of(target, n, classes=None, tname="target"):
     return t.argmax(dim=1).to(torch.int64).contiguous(), N
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _validate_ce(weight, bias, emb_val, labels_val):
     from .classify import classification_metrics
     N = int(weight.shape[0])
@@ -185,6 +180,23 @@ def _validate(weight, bias, emb_val, target_val):
     stats = tagging_metrics(target_val, probs)
     return {"average_precision": stats["average_precision"], "auc": stats["auc"], "d_prime": stats["d_prime"],
             "mAP": float(np.mean(stats["average_precision"])), "mAUC": float(np.nanmean(stats["auc"]))}
+
+
+def _check_val_ce(val, N, device):
+    emb_val = _check_emb(val[0], "emb_val")
+    return emb_val, labels_of(val[1], int(emb_val.shape[0]), N, "labels_val")[0].to(device)
+
+
+def _check_val(val, N, device):
+    emb_val, target_val, _ = _check_pair(val[0], val[1], "emb_val", "target_val")
+    if target_val.shape[1] != N:
+        raise ValueError("target_val has %d classes, target %d" % (target_val.shape[1], N))
+    return emb_val, target_val
+
+
+# What differs between the two losses of fit_head, picked once: the workspace query, the name of the step entry, its arguments
+# between n_rows_total and idx (the kernel's target) and between rows and W, and how val= is checked and scored.
+_Loss = namedtuple("_Loss", ["workspace_bytes", "step", "target_args", "class_args", "check_val", "validate"])
 
 
 def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=True,
@@ -217,21 +229,17 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
         if isinstance(target, torch.Tensor) and target.device != emb.device:
             raise ValueError("target is on %s, emb on %s" % (target.device, emb.device))
         tgt = tgt.to(emb.device)
-        n = int(emb.shape[0])
+        how = _Loss(_ffi.head_fit_ce_workspace_bytes, "acx_head_fit_step_ce", (vp(tgt),), (N, label_smoothing), _check_val_ce,
+                    _validate_ce)
     else:
         emb, tgt, tdtype = _check_pair(emb, target)
-        n, N = int(emb.shape[0]), int(tgt.shape[1])
-    device = emb.device
+        N = int(tgt.shape[1])
+        how = _Loss(_ffi.head_fit_workspace_bytes, "acx_head_fit_step", (vp(tgt), tdtype, tgt.stride(0)), (N,), _check_val, _validate)
+    n, device = int(emb.shape[0]), emb.device
     if val is not None:
         if len(val) != 2:
             raise ValueError("val must be (emb_val, target_val)")
-        if ce:
-            emb_val = _check_emb(val[0], "emb_val")
-            target_val = labels_of(val[1], int(emb_val.shape[0]), N, "labels_val")[0].to(device)
-        else:
-            emb_val, target_val, _ = _check_pair(val[0], val[1], "emb_val", "target_val")
-            if target_val.shape[1] != N:
-                raise ValueError("target_val has %d classes, target %d" % (target_val.shape[1], N))
+        emb_val, target_val = how.check_val(val, N, device)
         if emb_val.device != device:
             raise ValueError("emb_val is on %s, emb on %s" % (emb_val.device, device))
     if init is None:
@@ -258,21 +266,16 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
         mom = torch.zeros((3, N, EMBED_DIM), dtype=torch.float32, device=device)
         momb = torch.zeros((3, N), dtype=torch.float32, device=device)
         status = torch.zeros(1, dtype=torch.int32, device=device)
-        if ce:
-            ws_bytes = _ffi.head_fit_ce_workspace_bytes(min(batch_size, n), N)
-            step_fn = _ffi.lib().acx_head_fit_step_ce
-            fixed_a = (_vp(emb), emb.stride(0), n, _vp(tgt))
-        else:
-            ws_bytes = _ffi.head_fit_workspace_bytes(min(batch_size, n), N)
-            step_fn = _ffi.lib().acx_head_fit_step
-            fixed_a = (_vp(emb), emb.stride(0), n, _vp(tgt), tdtype, tgt.stride(0))
+        ws_bytes = how.workspace_bytes(min(batch_size, n), N)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        step_fn = getattr(_ffi.lib(), how.step)
         hp = _ffi.adam(betas[0], betas[1], eps, weight_decay, amsgrad, decoupled)
         stream = _ffi.stream_ptr(device)
-        fixed_b = ((N, label_smoothing) if ce else (N,)) + (
-            _vp(W), _vp(b), _vp(mom[0]), _vp(mom[1]), _vp(mom[2]) if amsgrad else None, _vp(momb[0]), _vp(momb[1]),
-            _vp(momb[2]) if amsgrad else None, ctypes.byref(hp))
-        tail = (_vp(status), _vp(ws), ws_bytes, stream)
+        fixed_a = (vp(emb), emb.stride(0), n) + how.target_args
+        fixed_b = how.class_args + (
+            vp(W), vp(b), vp(mom[0]), vp(mom[1]), vp(mom[2]) if amsgrad else None, vp(momb[0]), vp(momb[1]),
+            vp(momb[2]) if amsgrad else None, ctypes.byref(hp))
+        tail = (vp(status), vp(ws), ws_bytes, stream)
         order_ptr, loss_ptr = order.data_ptr(), loss.data_ptr()
         t = 0
         for e in range(epochs):
@@ -284,6 +287,6 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
                 t += 1
             rec = {"epoch": e, "loss": loss[e * len(batches):(e + 1) * len(batches)].mean()}
             if val is not None:
-                rec.update(_validate_ce(W, b, emb_val, target_val) if ce else _validate(W, b, emb_val, target_val))
+                rec.update(how.validate(W, b, emb_val, target_val))
             history.append(rec)
     return HeadFit(W, b, loss, history)

@@ -8,13 +8,14 @@ sqrt(2) * scipy.stats.norm.ppf(auc) -- up to float64 rounding, from scores taken
 CUDA tensors are read where they are, on the current stream (a column slice of a wider tensor too); numpy arrays and CPU tensors
 are checked on the host, then copied to `device` (default: the current CUDA device), the targets as uint8.  A class with no
 positive or no negative target gets AP 0 / 1 and NaN AUC and d', with one UserWarning, as sklearn does."""
-import ctypes
 import warnings
 
 import numpy as np
 import torch
 
 from .. import _ffi
+from .._ffi import vp
+from . import _inputs
 
 
 def _shape_check(target, scores):
@@ -52,25 +53,6 @@ def _host_target(x):
     return np.ascontiguousarray(t.astype(np.uint8))
 
 
-def _device_scores(s):
-    if s.dtype != torch.float32:
-        s = s.to(torch.float32)
-    if s.stride(1) != 1 or s.stride(0) < s.shape[1]:
-        s = s.contiguous()
-    return s
-
-
-def _device_target(t):
-    """-> (tensor, ACX_TARGET_*): float32 and uint8 / bool are read as they are, anything else travels as float32."""
-    if t.dtype == torch.bool:
-        t = t.view(torch.uint8)
-    if t.dtype not in (torch.uint8, torch.float32):
-        t = t.to(torch.float32)
-    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        t = t.contiguous()
-    return t, (_ffi.TARGET_U8 if t.dtype == torch.uint8 else _ffi.TARGET_F32)
-
-
 def _to_device(target, clipwise_output, device, who):
     """The checks and copies every call here starts with -> (scores, targets, ACX_TARGET_*, device): host inputs are checked
     before any copy or device call, CUDA tensors are taken where they are."""
@@ -81,17 +63,10 @@ def _to_device(target, clipwise_output, device, who):
     scores = _host_scores(clipwise_output) if not s_dev else None
     tgt = _host_target(target) if not t_dev else None
     if device is None:
-        device = clipwise_output.device if s_dev else target.device if t_dev else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise ValueError("%s runs on a CUDA (HIP) device, not %s" % (who, device))
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    scores = _device_scores(clipwise_output.to(device)) if s_dev else torch.from_numpy(scores).to(device)
-    if t_dev:
-        tgt, dtype = _device_target(target.to(device))
-    else:
-        tgt, dtype = torch.from_numpy(tgt).to(device), _ffi.TARGET_U8
+        device = clipwise_output.device if s_dev else target.device if t_dev else None
+    device = _inputs.cuda_device(device, who + " runs on")
+    scores = _inputs.rows(clipwise_output.to(device=device, dtype=torch.float32)) if s_dev else torch.from_numpy(scores).to(device)
+    tgt, dtype = _inputs.kernel_target(target.to(device) if t_dev else torch.from_numpy(tgt).to(device))
     return scores, tgt, dtype, device
 
 
@@ -114,9 +89,9 @@ def tagging_metrics(target, clipwise_output, device=None):
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     out = torch.empty((3, C), dtype=torch.float64, device=device)
     status = torch.empty(1, dtype=torch.int32, device=device)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    _ffi.tagging_metrics(vp(scores), scores.stride(0), vp(tgt), dtype, tgt.stride(0), n, C, vp(out[0]), vp(out[1]), vp(out[2]),
-                         vp(status), (vp(ws), ws_bytes), _ffi.stream_ptr(device))
+    with torch.cuda.device(device):
+        _ffi.tagging_metrics(vp(scores), scores.stride(0), vp(tgt), dtype, tgt.stride(0), n, C, vp(out[0]), vp(out[1]), vp(out[2]),
+                             vp(status), (vp(ws), ws_bytes), _ffi.stream_ptr(device))
     res = out.cpu().numpy()
     _raise_status(int(status.cpu()[0]))
     ap, auc, dp = res[0].copy(), res[1].copy(), res[2].copy()
@@ -259,7 +234,6 @@ def operating_points(target, clipwise_output, criterion="f1", device=None):
     thr = torch.empty(C, dtype=torch.float32, device=device)
     counts = torch.empty((C, 4), dtype=torch.int64, device=device)
     status = torch.empty(1, dtype=torch.int32, device=device)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
     with torch.cuda.device(device):
         _ffi.operating_points(vp(scores), scores.stride(0), vp(tgt), dtype, tgt.stride(0), n, C, code, value, vp(thr), vp(counts),
                               vp(status), (vp(ws), ws_bytes), _ffi.stream_ptr(device))
@@ -294,7 +268,6 @@ def threshold_metrics(target, clipwise_output, threshold, device=None):
         raise ValueError("threshold has shape %s for %d classes (expected (%d,))" % (tuple(thr.shape), C, C))
     counts = torch.empty((C, 4), dtype=torch.int64, device=device)
     status = torch.empty(1, dtype=torch.int32, device=device)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())
     with torch.cuda.device(device):
         _ffi.threshold_counts(vp(scores), scores.stride(0), vp(tgt), dtype, tgt.stride(0), n, C, vp(thr), vp(counts), vp(status),
                               _ffi.stream_ptr(device))
@@ -418,20 +391,13 @@ def weighted_metrics_host(target, clipwise_output, weights):
     return {"average_precision": ap, "auc": auc, "d_prime": 2.0 * _erfinv(2.0 * auc - 1.0)}
 
 
-def _resolve_device(device):
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise ValueError("bootstrap weights are drawn on a CUDA (HIP) device, not %s" % device)
-    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def bootstrap_weights(replicates, n, seed=0, first=0, device=None):
     """bootstrap_weights_host on the GPU (acx_bootstrap_weights): an int32 device tensor (replicates, n), bit for bit the same."""
     seed, first, replicates, n = _check_draw_args(seed, first, replicates, n)
-    device = _resolve_device(device)
+    device = _inputs.cuda_device(device, "bootstrap weights are drawn on")
     w = torch.empty((replicates, n), dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _ffi.bootstrap_weights(seed, first, replicates, n, ctypes.c_void_p(w.data_ptr()), n, _ffi.stream_ptr(device))
+        _ffi.bootstrap_weights(seed, first, replicates, n, vp(w), n, _ffi.stream_ptr(device))
     return w
 
 
@@ -449,10 +415,7 @@ def _device_weights(weights, n, device):
             raise ValueError("weights must have shape (R, %d) or (%d,); got %s" % (n, n, tuple(weights.shape)))
         if w.dtype != torch.int32:
             w = w.clamp(-1, MAX_WEIGHT_SUM + 1).to(torch.int32)     # what is invalid stays invalid
-        w = w.to(device)
-        if w.stride(1) != 1 or w.stride(0) < n:
-            w = w.contiguous()
-        return w
+        return _inputs.rows(w.to(device))
     return torch.from_numpy(_host_weights(weights, n).astype(np.int32)).to(device)
 
 
@@ -481,7 +444,6 @@ class _WeightedRunner:
         """w: int32 device tensor (R, n) -> float64 numpy (3, R, C); ValueError through the status word."""
         R = w.shape[0]
         out = torch.empty((3, R, self.C), dtype=torch.float64, device=self.device)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
         s, t = self.scores, self.tgt
         with torch.cuda.device(self.device):
             _ffi.weighted_metrics(vp(s), s.stride(0), vp(t), self.dtype, t.stride(0), self.n, self.C, vp(w), w.stride(0), R,

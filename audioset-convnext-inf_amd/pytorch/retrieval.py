@@ -20,22 +20,18 @@ or classify since the last check.
 
 `search_host` / `vote_host` are the documented host equivalents in numpy float64 (the tests' reference), as
 `segments.decode_events` is for the event decoder."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _ffi
+from .._ffi import vp
+from . import _inputs
 
 METRICS = tuple(_ffi.KNN_METRICS)
 WEIGHTS = tuple(_ffi.KNN_WEIGHTS)
 MAX_K = _ffi.KNN_MAX_K
 MAX_DIM = _ffi.KNN_MAX_DIM
 WORKSPACE_LIMIT = 256 << 20          # bytes of search workspace per chunk of queries
-
-
-def _vp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _check_metric(metric):
@@ -110,25 +106,9 @@ def vote_host(indices, scores, target, weights="uniform", temperature=0.07):
 
 
 # ---- the device path -------------------------------------------------------------------------------------------------------
-def _device_of(device):
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise ValueError("the search runs on a CUDA (HIP) device, not %s" % device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
-
-
-def _readable(x):
-    """True if the kernels can read the rows of x where they are: unit column stride, a row stride that is a multiple of 4 and
-    no shorter than the row, 16-byte aligned."""
-    return (x.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]
-            and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0)
-
-
 def _rows(x, device, dim=None, name="embeddings"):
-    """x (rows, dim) -> an fp32 tensor on `device` the kernels can read, zero-padded to a multiple of 4 columns.  A CUDA tensor
-    that is already readable -- a column slice of a wider tensor too -- is returned as it is."""
+    """x (rows, dim) -> an fp32 tensor on `device` the kernels can read (_inputs.rows with align4), zero-padded to a multiple
+    of 4 columns.  A CUDA tensor that is already readable -- a column slice of a wider tensor too -- is returned as it is."""
     shape = _check_2d(x, name)
     if dim is not None and shape[1] != dim:
         raise ValueError("%s have dim %d, the index dim %d" % (name, shape[1], dim))
@@ -139,13 +119,11 @@ def _rows(x, device, dim=None, name="embeddings"):
     x = x.detach().to(device=device, dtype=torch.float32)
     if x.shape[1] % 4:
         x = torch.nn.functional.pad(x, (0, 4 - x.shape[1] % 4))
-    if x.shape[0] and not _readable(x):
-        x = x.contiguous()
-    return x
+    return _inputs.rows(x, align4=True) if x.shape[0] else x
 
 
 def _target(t, rows, device):
-    """-> a (rows, C) uint8 or fp32 device tensor with unit column stride."""
+    """-> (a (rows, C) uint8 or fp32 device tensor with unit column stride, ACX_TARGET_*)."""
     shape = _check_2d(t, "target")
     if shape[0] != rows:
         raise ValueError("target has %d rows, the embeddings %d" % (shape[0], rows))
@@ -153,14 +131,7 @@ def _target(t, rows, device):
         raise ValueError("target has %d classes (expected 1 .. %d)" % (shape[1], _ffi.MAX_CLASSES))
     if not isinstance(t, torch.Tensor):
         t = torch.from_numpy(np.ascontiguousarray(t))
-    t = t.detach().to(device)
-    if t.dtype == torch.bool:
-        t = t.view(torch.uint8)
-    if t.dtype not in (torch.uint8, torch.float32):
-        t = t.to(torch.float32)
-    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        t = t.contiguous()
-    return t
+    return _inputs.kernel_target(t.detach().to(device))
 
 
 def row_norms(x, status=None):
@@ -169,7 +140,7 @@ def row_norms(x, status=None):
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        _ffi.knn_row_norms(_vp(x), x.stride(0), x.shape[0], x.shape[1], _vp(out), _vp(status), _ffi.stream_ptr(x.device))
+        _ffi.knn_row_norms(vp(x), x.stride(0), x.shape[0], x.shape[1], vp(out), vp(status), _ffi.stream_ptr(x.device))
     return out
 
 
@@ -184,7 +155,7 @@ def vote(indices, scores, target, weights="uniform", temperature=0.07, status=No
     if k < 1 or k > MAX_K:
         raise ValueError("k = %d (expected 1 .. %d)" % (k, MAX_K))
     dev = indices.device
-    target = _target(target, target.shape[0], dev)
+    target, code = _target(target, target.shape[0], dev)
     idx32 = indices.to(torch.int32).contiguous()
     sc = None if scores is None else scores.to(torch.float32).contiguous()
     if weights == "similarity" and sc is None:
@@ -192,9 +163,8 @@ def vote(indices, scores, target, weights="uniform", temperature=0.07, status=No
     out = torch.empty((q, target.shape[1]), dtype=torch.float32, device=dev)
     word = torch.empty(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _ffi.knn_vote(_vp(idx32), _vp(sc), q, k, _vp(target), _ffi.TARGET_U8 if target.dtype == torch.uint8 else _ffi.TARGET_F32,
-                      target.stride(0), target.shape[0], target.shape[1], _ffi.KNN_WEIGHTS[weights], temperature, _vp(out),
-                      out.stride(0), _vp(word), _ffi.stream_ptr(dev))
+        _ffi.knn_vote(vp(idx32), vp(sc), q, k, vp(target), code, target.stride(0), target.shape[0], target.shape[1],
+                      _ffi.KNN_WEIGHTS[weights], temperature, vp(out), out.stride(0), vp(word), _ffi.stream_ptr(dev))
     if status is not None:
         status.bitwise_or_(word)
     return out
@@ -213,7 +183,7 @@ class EmbeddingIndex:
         shape = _check_2d(emb, "embeddings")
         if isinstance(emb, torch.Tensor) and emb.is_cuda and device is None:
             device = emb.device
-        self.device = _device_of(device)
+        self.device = _inputs.cuda_device(device, "the search runs on")
         self.metric = metric
         self.dim = int(shape[1])
         self.workspace_limit = int(workspace_limit)
@@ -257,7 +227,7 @@ class EmbeddingIndex:
                              % ("with" if self._has_target else "without"))
         if m == 0:
             return self
-        t = _target(target, m, self.device) if target is not None else None
+        t = _target(target, m, self.device)[0] if target is not None else None
         if t is not None and self._tgt is not None and (t.shape[1] != self._tgt.shape[1] or t.dtype != self._tgt.dtype):
             raise ValueError("target rows of %d classes (%s) added to an index of %d classes (%s)"
                              % (t.shape[1], t.dtype, self._tgt.shape[1], self._tgt.dtype))
@@ -340,10 +310,10 @@ class EmbeddingIndex:
             stream = _ffi.stream_ptr(dev)
             for i, a in enumerate(range(0, nq, chunk)):
                 b = min(nq, a + chunk)
-                _ffi.knn_search(_vp(q[a:b]), q.stride(0), _vp(rq[a:b]) if cosine else None, b - a, _vp(d), d.stride(0),
-                                _vp(self._inv) if cosine else None, self._n, q.shape[1], _ffi.KNN_METRICS[self.metric], k,
-                                _vp(exclude[a:b]) if exclude is not None else None, _vp(indices[a:b]), _vp(scores[a:b]),
-                                _vp(words[i:]), (_vp(ws), ws_bytes), stream)
+                _ffi.knn_search(vp(q[a:b]), q.stride(0), vp(rq[a:b]) if cosine else None, b - a, vp(d), d.stride(0),
+                                vp(self._inv) if cosine else None, self._n, q.shape[1], _ffi.KNN_METRICS[self.metric], k,
+                                vp(exclude[a:b]) if exclude is not None else None, vp(indices[a:b]), vp(scores[a:b]),
+                                vp(words[i:]), (vp(ws), ws_bytes), stream)
             self._status.bitwise_or_(words if words.numel() == 1 else words.amax())      # each word is 0 or ACX_KNN_NONFINITE
         return scores, indices.to(torch.int64)
 

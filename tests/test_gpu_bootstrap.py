@@ -4,7 +4,6 @@ resamples that draw no positive, at every size class of the kernels, as the loop
 AudioSet eval set's shape, on strided and differently typed inputs, through the status word, captured into a graph, and through
 bootstrap_metrics / bootstrap_difference and the evaluation script.  Tolerances as test_gpu_metrics.py: AP and AUC within 1e-12,
 d' to rtol 1e-10 where finite, NaN and infinity patterns equal exactly."""
-import ctypes
 import os
 import re
 import subprocess
@@ -17,6 +16,7 @@ import torch
 from sklearn import metrics as skm
 
 from audioset_convnext_inf_amd import _ffi
+from audioset_convnext_inf_amd._ffi import vp
 from audioset_convnext_inf_amd.pytorch import metrics as M
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +75,7 @@ def test_weights_equal_the_host_bit_for_bit(n):
     assert np.array_equal(M.bootstrap_weights(2, n, seed=7, first=3).cpu().numpy(), host[3:])      # a chunk computed alone
     # raw ABI, rows at a stride: what lies between the rows is left alone
     wide = torch.full((5, n + 3), 0x7f7f7f7f, dtype=torch.int32, device="cuda")
-    _ffi.bootstrap_weights(7, 0, 5, n, ctypes.c_void_p(wide.data_ptr()), n + 3, _ffi.stream_ptr(wide.device))
+    _ffi.bootstrap_weights(7, 0, 5, n, vp(wide), n + 3, _ffi.stream_ptr(wide.device))
     w = wide.cpu().numpy()
     assert np.array_equal(w[:, :n], host) and (w[:, n:] == 0x7f7f7f7f).all()
 
@@ -287,7 +287,6 @@ def test_bad_data_raises_through_the_status_word():
     ws = torch.empty(n_ws, dtype=torch.uint8, device="cuda")
     out = torch.zeros((3, 3, C), dtype=torch.float64, device="cuda")
     st = torch.zeros(1, dtype=torch.int32, device="cuda")
-    vp = lambda x: ctypes.c_void_p(x.data_ptr())
     _ffi.weighted_metrics(vp(s), C, vp(t), _ffi.TARGET_U8, C, N, C, vp(w2), N, 3, vp(out[0]), vp(out[1]), vp(out[2]), vp(st),
                           (vp(ws), n_ws), _ffi.stream_ptr(s.device))
     assert int(st.cpu()[0]) == _ffi.METRICS_BAD_WEIGHT and torch.isnan(out).all()
@@ -354,7 +353,6 @@ def test_capture_and_replay_equals_eager(small):
     out = torch.full((3, R, C), 7.0, dtype=torch.float64, device="cuda")
     st = torch.full((1,), -1, dtype=torch.int32, device="cuda")
     wcap = torch.zeros_like(w)
-    vp = lambda x: ctypes.c_void_p(x.data_ptr())
     g = torch.cuda.CUDAGraph()
     torch.cuda.synchronize()
     with torch.cuda.graph(g):                             # a linear graph: two clears and five kernels in a row

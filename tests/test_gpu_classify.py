@@ -17,6 +17,7 @@ from audioset_convnext_inf_amd.pytorch import classify as cl
 from audioset_convnext_inf_amd.pytorch.convnext import ConvNeXt, convnext_tiny
 from audioset_convnext_inf_amd.pytorch.extract_embeddings import extract
 from audioset_convnext_inf_amd.pytorch.finetune import fit_head
+from fit_calls import call_update, fresh_state, init, last_error, vp
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -33,14 +34,6 @@ def data(n, N, seed=0):
     return F.layer_norm(x, (768,)), y
 
 
-def init(N):
-    return torch.randn(N, 768, generator=torch.Generator().manual_seed(1)) * 0.02, torch.zeros(N)
-
-
-def vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def workspace(rows, N):
     nbytes = _ffi.head_fit_ce_workspace_bytes(rows, N)
     return torch.empty(nbytes, dtype=torch.uint8, device=DEV), nbytes
@@ -48,10 +41,6 @@ def workspace(rows, N):
 
 def stream():
     return _ffi.stream_ptr(torch.device(DEV))
-
-
-def last_error():
-    return _ffi.lib().acx_last_error().decode()
 
 
 def call_grad(E, y, idx, W, b, eps=0.0, ws=None, over=None):
@@ -80,17 +69,6 @@ def call_step(E, y, idx, st, hp, t, lr, loss, status, ws, eps=0.0, over=None):
     return _ffi.lib().acx_head_fit_step_ce(a["E"], a["ld_e"], a["n_total"], a["y"], a["idx"], a["rows"], a["N"], a["eps"], a["W"],
                                            a["b"], a["mW"], a["vW"], a["xW"], a["mb"], a["vb"], a["xb"], a["hp"], a["t"], a["lr"],
                                            a["loss"], a["status"], a["ws"], a["ws_bytes"], stream())
-
-
-def call_update(p, g, m, v, x, hp, t, lr):
-    return _ffi.lib().acx_adam_update(vp(p), vp(g), vp(m), vp(v), vp(x), p.numel(), ctypes.byref(hp), t, lr, stream())
-
-
-def fresh_state(W0, b0):
-    st = {"W": W0.to(DEV).clone(), "b": b0.to(DEV).clone()}
-    for k, ref in (("mW", "W"), ("vW", "W"), ("xW", "W"), ("mb", "b"), ("vb", "b"), ("xb", "b")):
-        st[k] = torch.zeros_like(st[ref])
-    return st
 
 
 def p_bound(z64, delta, N):

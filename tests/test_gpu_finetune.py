@@ -19,8 +19,10 @@ import torch.nn.functional as F
 from audioset_convnext_inf_amd import _ffi, synth
 from audioset_convnext_inf_amd.pytorch.convnext import ConvNeXt, convnext_tiny
 from audioset_convnext_inf_amd.pytorch.extract_embeddings import extract
+from audioset_convnext_inf_amd.pytorch._inputs import target_code
 from audioset_convnext_inf_amd.pytorch.finetune import fit_head
 from audioset_convnext_inf_amd.pytorch.metrics import tagging_metrics
+from fit_calls import call_update, fresh_state, init, last_error, vp
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -35,10 +37,6 @@ def data(n, N, seed=0):
     y[torch.arange(n), torch.randint(0, N, (n,), generator=g)] = True
     x = y.float() @ proto * 0.7 + torch.randn(n, 768, generator=g)
     return F.layer_norm(x, (768,)), y.float()
-
-
-def init(N):
-    return torch.randn(N, 768, generator=torch.Generator().manual_seed(1)) * 0.02, torch.zeros(N)
 
 
 def oracle(E, Y, W0, b0, batch, epochs, lr, dtype, seed=2, adamw=False, wd=0.0, amsgrad=True):
@@ -67,10 +65,6 @@ def oracle(E, Y, W0, b0, batch, epochs, lr, dtype, seed=2, adamw=False, wd=0.0, 
     return W.detach(), b.detach(), torch.stack(losses), zmax
 
 
-def vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def workspace(rows, N):
     nbytes = _ffi.head_fit_workspace_bytes(rows, N)
     return torch.empty(nbytes, dtype=torch.uint8, device=DEV), nbytes
@@ -86,7 +80,7 @@ def call_grad(E, Y, idx, W, b, n_total=None, rows=None, N=None, ws=None, over=No
     loss, status = torch.full((1,), float("nan"), device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
     wsb, nbytes = workspace(max(rows, 1), W.shape[0]) if ws is None else ws
     a = dict(E=vp(E), ld_e=E.stride(0), n_total=E.shape[0] if n_total is None else n_total, Y=vp(Y),
-             dtype=_ffi.TARGET_U8 if Y.dtype == torch.uint8 else _ffi.TARGET_F32, ld_y=Y.stride(0), idx=vp(idx), rows=rows, N=N,
+             dtype=target_code(Y), ld_y=Y.stride(0), idx=vp(idx), rows=rows, N=N,
              W=vp(W), b=vp(b), z=vp(z), G=vp(G), dW=vp(dW), db=vp(db), loss=vp(loss), status=vp(status), ws=vp(wsb),
              ws_bytes=nbytes)
     a.update(over or {})
@@ -99,7 +93,7 @@ def call_grad(E, Y, idx, W, b, n_total=None, rows=None, N=None, ws=None, over=No
 def call_step(E, Y, idx, st, hp, t, lr, loss, status, ws, stream=None, over=None):
     """acx_head_fit_step; st: dict of W b mW vW xW mb vb xb device tensors."""
     a = dict(E=vp(E), ld_e=E.stride(0), n_total=E.shape[0], Y=vp(Y),
-             dtype=_ffi.TARGET_U8 if Y.dtype == torch.uint8 else _ffi.TARGET_F32, ld_y=Y.stride(0), idx=vp(idx), rows=idx.numel(),
+             dtype=target_code(Y), ld_y=Y.stride(0), idx=vp(idx), rows=idx.numel(),
              N=st["W"].shape[0], hp=ctypes.byref(hp) if hp is not None else None, t=t, lr=lr, loss=vp(loss), status=vp(status),
              ws=vp(ws[0]), ws_bytes=ws[1])
     a.update({k: vp(v) for k, v in st.items()})
@@ -108,25 +102,6 @@ def call_step(E, Y, idx, st, hp, t, lr, loss, status, ws, stream=None, over=None
                                         a["W"], a["b"], a["mW"], a["vW"], a["xW"], a["mb"], a["vb"], a["xb"], a["hp"], a["t"],
                                         a["lr"], a["loss"], a["status"], a["ws"], a["ws_bytes"],
                                         stream if stream is not None else _ffi.stream_ptr(torch.device(DEV)))
-
-
-def call_update(p, g, m, v, x, hp, t, lr, over=None):
-    a = dict(p=vp(p), g=vp(g), m=vp(m), v=vp(v), x=vp(x), n=p.numel(), hp=ctypes.byref(hp) if hp is not None else None, t=t,
-             lr=lr)
-    a.update(over or {})
-    return _ffi.lib().acx_adam_update(a["p"], a["g"], a["m"], a["v"], a["x"], a["n"], a["hp"], a["t"], a["lr"],
-                                      _ffi.stream_ptr(torch.device(DEV)))
-
-
-def fresh_state(W0, b0):
-    st = {"W": W0.to(DEV).clone(), "b": b0.to(DEV).clone()}
-    for k, ref in (("mW", "W"), ("vW", "W"), ("xW", "W"), ("mb", "b"), ("vb", "b"), ("xb", "b")):
-        st[k] = torch.zeros_like(st[ref])
-    return st
-
-
-def last_error():
-    return _ffi.lib().acx_last_error().decode()
 
 
 # ---- 1. the gradient pass against float64 ----------------------------------------------------------------------------------

@@ -2,7 +2,6 @@
 scipy computed live -- at the AudioSet eval set's shape, on ties, signed zeros, denormals and degenerate classes, through the
 global-memory path (N > 32768), on strided and differently typed inputs, through the status word, on the model's own output and
 through the evaluation harness and script."""
-import ctypes
 import os
 import re
 import subprocess
@@ -16,6 +15,7 @@ from scipy.stats import norm
 from sklearn import metrics as skm
 
 from audioset_convnext_inf_amd import _ffi
+from audioset_convnext_inf_amd._ffi import vp
 from audioset_convnext_inf_amd.pytorch import evaluate as ev
 from audioset_convnext_inf_amd.pytorch.metrics import tagging_metrics
 
@@ -142,7 +142,6 @@ def test_strided_dtypes_workspace_and_repeat():
     ws = torch.full((n_ws,), 0xFF, dtype=torch.uint8, device="cuda")
     out = torch.full((3, C), 7.0, dtype=torch.float64, device="cuda")
     st = torch.full((1,), -1, dtype=torch.int32, device="cuda")
-    vp = lambda x: ctypes.c_void_p(x.data_ptr())
     args = [vp(sc), C, vp(tg), _ffi.TARGET_U8, C, N, C, vp(out[0]), vp(out[1]), vp(out[2]), vp(st)]
     _ffi.check(_ffi.lib().acx_tagging_metrics(*args, vp(ws), n_ws, _ffi.stream_ptr(sc.device)))
     assert int(st.cpu()[0]) == 0
@@ -175,13 +174,27 @@ def test_bad_device_data_raises_through_status():
     ws = torch.empty(n_ws, dtype=torch.uint8, device="cuda")
     out = torch.zeros((3, 9), dtype=torch.float64, device="cuda")
     st = torch.zeros(1, dtype=torch.int32, device="cuda")
-    vp = lambda x: ctypes.c_void_p(x.data_ptr())
     s2 = s.clone()
     s2[0, 0] = float("nan")
     _ffi.check(_ffi.lib().acx_tagging_metrics(vp(s2), 9, vp(t2), _ffi.TARGET_F32, 9, 300, 9, vp(out[0]), vp(out[1]), vp(out[2]),
                                               vp(st), vp(ws), n_ws, _ffi.stream_ptr(s.device)))
     assert int(st.cpu()[0]) == _ffi.METRICS_NONFINITE | _ffi.METRICS_BAD_TARGET
     assert torch.isnan(out).all()
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="a call on a device that is not the current one needs two GPUs")
+def test_runs_on_the_device_it_is_given_while_another_is_current():
+    rs = np.random.RandomState(11)
+    N, C = 64, 3
+    s = rs.uniform(size=(N, C)).astype(np.float32)
+    t = rs.uniform(size=(N, C)) < 0.4
+    t[0], t[1] = True, False
+    with torch.cuda.device(0):
+        host_in = gpu(t, s, device="cuda:1")
+        dev_in = gpu(torch.from_numpy(t).to("cuda:1"), torch.from_numpy(s).to("cuda:1"))
+        assert torch.cuda.current_device() == 0
+    assert_matches(host_in, sk(t, s))
+    assert_matches(dev_in, sk(t, s))
 
 
 @pytest.fixture(scope="module")

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from audioset_convnext_inf_amd import _ffi, synth
+from audioset_convnext_inf_amd._ffi import vp
 from audioset_convnext_inf_amd.pytorch import segments as seg
 from audioset_convnext_inf_amd.pytorch.metrics import (operating_points, operating_points_host, tagging_metrics,
                                                        threshold_metrics)
@@ -172,7 +173,6 @@ def test_strided_dtypes_workspace_and_repeat():
     thr = torch.full((C,), 7.0, dtype=torch.float32, device="cuda")
     cnt = torch.full((C, 4), 7, dtype=torch.int64, device="cuda")
     st = torch.full((1,), -1, dtype=torch.int32, device="cuda")
-    vp = lambda x: ctypes.c_void_p(x.data_ptr())
     spec = _ffi.AcxOperatingSpec(_ffi.OP_FBETA, 1.0)
     args = [vp(sc), C, vp(tg), _ffi.TARGET_U8, C, N, C, ctypes.byref(spec), vp(thr), vp(cnt), vp(st)]
     _ffi.check(_ffi.lib().acx_operating_points(*args, vp(ws), n_ws, _ffi.stream_ptr(sc.device)))
@@ -210,7 +210,6 @@ def test_bad_device_data_raises_through_status():
     out = torch.zeros(9, dtype=torch.float32, device="cuda")
     cnt = torch.zeros((9, 4), dtype=torch.int64, device="cuda")
     st = torch.zeros(1, dtype=torch.int32, device="cuda")
-    vp = lambda x: ctypes.c_void_p(x.data_ptr())
     _ffi.operating_points(vp(s2), 9, vp(t2), _ffi.TARGET_U8, 9, 300, 9, _ffi.OP_RECALL, 0.5, vp(out), vp(cnt), vp(st), (vp(ws), n_ws),
                           _ffi.stream_ptr(s.device))
     assert int(st.cpu()[0]) == _ffi.METRICS_NONFINITE | _ffi.METRICS_BAD_TARGET

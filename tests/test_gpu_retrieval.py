@@ -5,13 +5,13 @@ so fp32 is exact in any order) and must EQUAL the float64 host reference `search
 (standard-normal data) are checked for validity under the derived rounding bound of an fp32 dot product,
 b = (dim + 8) 2^-24 sum_i |q_i x_i| (divided by the norms for cosine): returned scores within b of the float64 score, rows
 sorted by the one total order, and no row left out whose float64 score could not have lost to the k-th returned one."""
-import ctypes
 
 import numpy as np
 import pytest
 import torch
 
 from audioset_convnext_inf_amd import _ffi, synth
+from audioset_convnext_inf_amd._ffi import vp
 from audioset_convnext_inf_amd.pytorch import retrieval
 from audioset_convnext_inf_amd.pytorch.convnext import convnext_tiny
 from audioset_convnext_inf_amd.pytorch.extract_embeddings import extract
@@ -20,10 +20,6 @@ from audioset_convnext_inf_amd.pytorch.retrieval import EmbeddingIndex, search_h
 pytestmark = pytest.mark.gpu
 MAX_K = _ffi.KNN_MAX_K
 DIM = 768
-
-
-def vp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def raw_search(q, d, k, metric="dot", exclude=None, ws=None):

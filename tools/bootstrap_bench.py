@@ -15,7 +15,6 @@ one GPU with the inputs resident, medians of five runs after a warm-up -- nothin
 
     python tools/bootstrap_bench.py [--parent-lib PATH] [--replicates 1000] > profiles/rNN_bootstrap_bench.txt"""
 import argparse
-import ctypes
 import json
 import os
 import subprocess
@@ -32,7 +31,7 @@ from audioset_convnext_inf_amd import _ffi                                      
 from audioset_convnext_inf_amd.pytorch import metrics as M                                         # noqa: E402
 
 CHUNK = 256
-vp = lambda x: ctypes.c_void_p(x.data_ptr())
+vp = _ffi.vp
 
 
 def inputs(N, C, seed=0, device="cuda"):

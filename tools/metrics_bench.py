@@ -12,7 +12,6 @@ Targets (ISSUE, estimates set before measuring): 1. <= 2 ms; 2. >= 100x faster t
 
     python tools/metrics_bench.py [--skip-script] [--script-n N] > profiles/rNN_metrics_bench.txt
 (the script's synthetic set is generated in float64 on the host: 20 371 clips take about 100 GB of host memory at the peak)"""
-import ctypes
 import os
 import re
 import subprocess
@@ -46,7 +45,7 @@ def device_ms(N, reps):
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
     out = torch.empty((3, C), dtype=torch.float64, device="cuda")
     st = torch.empty(1, dtype=torch.int32, device="cuda")
-    vp = lambda x: ctypes.c_void_p(x.data_ptr())
+    vp = _ffi.vp
     stream = _ffi.stream_ptr(s.device)
 
     def call():

@@ -15,7 +15,6 @@ decoder with per-class levels (acx_decode_events_classwise), measured -- nothing
 
     python tools/operating_bench.py [--parent-lib PATH] [--skip-model] > profiles/rNN_operating_bench.txt"""
 import argparse
-import ctypes
 import json
 import os
 import subprocess
@@ -34,7 +33,7 @@ from audioset_convnext_inf_amd.pytorch.metrics import operating_points, operatin
 N, C = 20371, 527
 CRITERIA = [("f1", _ffi.OP_FBETA, 1.0), ("fbeta 2", _ffi.OP_FBETA, 2.0), ("precision 0.9", _ffi.OP_PRECISION, 0.9),
             ("recall 0.8", _ffi.OP_RECALL, 0.8)]
-vp = lambda x: ctypes.c_void_p(x.data_ptr())
+vp = _ffi.vp
 
 
 def inputs(seed=0, device="cuda"):
