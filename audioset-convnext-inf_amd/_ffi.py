@@ -173,6 +173,14 @@ SIGNATURES = {
                                       _vp, _c_sz, _vp]),
     "acx_softmax_topk": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp]),
     "acx_classification_counts": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
+    "acx_reliability_counts": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "acx_reliability_toplabel": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_platt_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_platt_fit": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_platt_apply": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
+    "acx_temperature_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_temperature_fit": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_temperature_apply": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
     "acx_knn_row_norms": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp]),
     "acx_knn_workspace_bytes": (_c_int, [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_knn_slices": (_c_int, [_c_i64, _c_i64, _c_int, _pint]),
@@ -507,6 +515,56 @@ def classification_counts(logits, ld, labels, n, classes, k, per_class, hits, co
     """acx_classification_counts on raw device pointers (ctypes.c_void_p); confusion may be None."""
     check(lib().acx_classification_counts(logits, int(ld), labels, int(n), int(classes), int(k), per_class, hits, confusion,
                                           status, stream))
+
+
+CAL_MAX_BINS, CAL_MAX_EVALUATIONS = 64, 64     # ACX_CAL_MAX_BINS, ACX_CAL_MAX_EVALUATIONS
+CAL_NONFINITE, CAL_BAD_TARGET, CAL_BAD_PROBABILITY, CAL_BAD_LABEL = 1, 2, 4, 8   # bits of the calibration calls' status words
+CAL_DEGENERATE, CAL_NOT_CONVERGED, CAL_AT_BOUND = -1, -2, -3                     # negative values of their info words
+
+
+def reliability_counts(probs, ld, target, target_dtype, ld_t, n, classes, bins, count, positive, conf_sum, brier_sum, status,
+                       stream):
+    """acx_reliability_counts on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_reliability_counts(probs, int(ld), target, int(target_dtype), int(ld_t), int(n), int(classes), int(bins),
+                                       count, positive, conf_sum, brier_sum, status, stream))
+
+
+def reliability_toplabel(logits, ld, labels, n, classes, beta, bins, count, correct, conf_sum, nll_sum, status, ws, stream):
+    """acx_reliability_toplabel on raw device pointers; beta may be None; ws: (pointer, bytes) of temperature_workspace_bytes."""
+    check(lib().acx_reliability_toplabel(logits, int(ld), labels, int(n), int(classes), beta, int(bins), count, correct, conf_sum,
+                                         nll_sum, status, ws[0], int(ws[1]), stream))
+
+
+def platt_workspace_bytes(n, classes):
+    """Workspace of acx_platt_fit for n rows of `classes` logits (host only)."""
+    return _query(lib().acx_platt_workspace_bytes, _c_sz, int(n), int(classes))
+
+
+def platt_fit(logits, ld, target, target_dtype, ld_t, n, classes, smooth, ab, info, status, ws, stream):
+    """acx_platt_fit on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_platt_fit(logits, int(ld), target, int(target_dtype), int(ld_t), int(n), int(classes), 1 if smooth else 0, ab,
+                              info, status, ws[0], int(ws[1]), stream))
+
+
+def platt_apply(logits, ld, rows, classes, ab, probs, ld_p, stream):
+    """acx_platt_apply on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_platt_apply(logits, int(ld), int(rows), int(classes), ab, probs, int(ld_p), stream))
+
+
+def temperature_workspace_bytes(n, classes):
+    """Workspace of acx_temperature_fit and acx_reliability_toplabel for n rows of `classes` logits (host only)."""
+    return _query(lib().acx_temperature_workspace_bytes, _c_sz, int(n), int(classes))
+
+
+def temperature_fit(logits, ld, labels, n, classes, evaluations, beta, info, status, ws, stream):
+    """acx_temperature_fit on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_temperature_fit(logits, int(ld), labels, int(n), int(classes), int(evaluations), beta, info, status, ws[0],
+                                    int(ws[1]), stream))
+
+
+def temperature_apply(logits, ld, rows, classes, beta, out, ld_o, stream):
+    """acx_temperature_apply on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_temperature_apply(logits, int(ld), int(rows), int(classes), beta, out, int(ld_o), stream))
 
 
 KNN_DOT, KNN_COSINE = 0, 1                    # enum acx_knn_metric

@@ -508,10 +508,11 @@ class ConvNeXt(nn.Module):
         out["scores"] = score(reference, out["events"], **score_args)
         return out
 
-    def tag(self, waveform, threshold, sample_rate=None):
+    def tag(self, waveform, threshold, sample_rate=None, calibration=None):
         """Tags as decisions: one forward, then clipwise_output >= threshold.  threshold: one number, or one per class (an
-        array, or a CUDA tensor such as metrics.operating_points(...).threshold; +inf: the class never fires).  Returns
-        {"labels": bool (B, N), "clipwise_output", "clipwise_logits"}; nothing synchronises."""
+        array, or a CUDA tensor such as metrics.operating_points(...).threshold; +inf: the class never fires).  calibration: a
+        calibration.PlattScaling -- its probabilities of the logits take the place of clipwise_output, in the comparison and in
+        the result.  Returns {"labels": bool (B, N), "clipwise_output", "clipwise_logits"}; nothing synchronises."""
         if isinstance(threshold, torch.Tensor):
             thr = threshold.detach()
         else:
@@ -523,17 +524,29 @@ class ConvNeXt(nn.Module):
             raise ValueError("threshold holds a NaN")
         out = self(waveform, sample_rate=sample_rate)
         probs = out["clipwise_output"]
+        if calibration is not None:
+            from . import calibration as _cal
+            if not isinstance(calibration, _cal.PlattScaling):
+                raise ValueError("tag(calibration=) takes a PlattScaling (got %s)" % type(calibration).__name__)
+            probs = calibration.apply(out["clipwise_logits"])
         return {"labels": probs >= thr.to(device=probs.device, dtype=probs.dtype), "clipwise_output": probs,
                 "clipwise_logits": out["clipwise_logits"]}
 
-    def classify(self, waveform, k=5, sample_rate=None):
+    def classify(self, waveform, k=5, sample_rate=None, calibration=None):
         """A single-label head (fit_head(..., loss="ce")) read with softmax: one forward, then classify.softmax_topk on the same
-        stream; nothing synchronises.  Returns {"probabilities" (B, N), "labels" (B,) int64 = the top-1 class, "top_indices"
+        stream; nothing synchronises.  calibration: a calibration.TemperatureScaling -- the softmax is taken of its scaled
+        logits; clipwise_logits stay raw.  Returns {"probabilities" (B, N), "labels" (B,) int64 = the top-1 class, "top_indices"
         (B, k) int32, "top_probabilities" (B, k), "clipwise_logits"}; k is cut to N.  model(x) itself keeps returning the sigmoid
         clipwise_output (INTEGRATION.md, "Single-label heads")."""
         from . import classify as _cl
         logits = self(waveform, sample_rate=sample_rate)["clipwise_logits"]
-        probs, top_prob, top_index = _cl.softmax_topk(logits, k=min(int(k), int(logits.shape[1])))
+        scaled = logits
+        if calibration is not None:
+            from . import calibration as _cal
+            if not isinstance(calibration, _cal.TemperatureScaling):
+                raise ValueError("classify(calibration=) takes a TemperatureScaling (got %s)" % type(calibration).__name__)
+            scaled = calibration.apply(logits)
+        probs, top_prob, top_index = _cl.softmax_topk(scaled, k=min(int(k), int(logits.shape[1])))
         return {"probabilities": probs, "labels": top_index[:, 0].to(torch.int64), "top_indices": top_index,
                 "top_probabilities": top_prob, "clipwise_logits": logits}
 
@@ -783,6 +796,27 @@ class ConvNeXt(nn.Module):
         head.train(self.training)
         self.head_audioset = head
         return fit
+
+    def calibrate(self, data, target, method="platt", sample_rate=None, **kw):
+        """Fit a calibration map for this model's head on a validation split (pytorch/calibration.py): `data` is an (n, N)
+        tensor of clipwise_logits, or a list of waveforms at `sample_rate`, whose logits are extracted first
+        (extract(..., what="logits", pack=True), as fit_head extracts embeddings).  method="platt": target (n, N) 0 / 1 labels
+        -> PlattScaling (tag(calibration=)); method="temperature": target (n,) class numbers -> TemperatureScaling
+        (classify(calibration=)).  **kw: smooth= / evaluations=.  Nothing is installed in the model."""
+        from . import calibration as _cal
+        from .extract_embeddings import extract
+        if method not in ("platt", "temperature"):
+            raise ValueError("method must be \"platt\" or \"temperature\" (got %r)" % (method,))
+        dev = self.head_audioset.weight.device
+        if isinstance(data, torch.Tensor) and data.dim() == 2:
+            logits = data.to(dev)
+        else:
+            logits = torch.stack(extract(self, list(data), what="logits", pack=True, sample_rate=sample_rate)).to(dev)
+        if isinstance(target, torch.Tensor) and target.device != logits.device:
+            target = target.to(logits.device)
+        if method == "platt":
+            return _cal.fit_platt(target, logits, **kw)
+        return _cal.fit_temperature(target, logits, **kw)
 
     def build_index(self, data, target=None, sample_rate=None, metric="cosine"):
         """An EmbeddingIndex (pytorch/retrieval.py) over scene embeddings on the model's device: `data` is an (n, 768) tensor

@@ -7,6 +7,7 @@ load / resample / pad a WAV, three forwards, labels above the 0.25 threshold).
     python demo_convnext.py --wav clip.wav --sed --top 10              # sound event detection: WHEN the top classes happen
     python demo_convnext.py --ckpt my_tagger/model.safetensors --wav clip.wav --thresholds my_tagger.thresholds.npy
     python demo_convnext.py --ckpt my_classifier/model.safetensors --wav clip.wav --softmax --top 5     # a single-label head
+    python demo_convnext.py --ckpt my_tagger/model.safetensors --wav clip.wav --calibration my_tagger.calibration.npz
 
 Prints the same lines as the reference (`# params`, sizes, predicted label indices, names, embedding shapes).
 """
@@ -42,6 +43,8 @@ def main():
     ap.add_argument("--softmax", action="store_true", help="a single-label head (demo_finetune.py --loss ce): print the --top "
                                                            "classes by softmax probability (ConvNeXt.classify)")
     ap.add_argument("--top", type=int, default=10, help="--sed / --softmax: how many classes")
+    ap.add_argument("--calibration", help=".npz written by demo_finetune.py (pytorch/calibration.py): Platt scaling replaces the "
+                                          "sigmoid probabilities of the labels, temperature scaling those of --softmax")
     args = ap.parse_args()
 
     if args.synthetic_weights:
@@ -77,13 +80,28 @@ def main():
     print("logits size:", logits.size())
     print("probs size:", probs.size())
 
+    calibration = platt = temperature = None
+    if args.calibration:
+        from audioset_convnext_inf_amd.pytorch import calibration as cal
+        calibration = cal.load_calibration(args.calibration, device)
+        if isinstance(calibration, cal.PlattScaling):
+            platt = calibration
+            if platt.ab.shape[0] != probs.shape[1]:
+                sys.exit("%s holds %d classes, the model has %d" % (args.calibration, platt.ab.shape[0], probs.shape[1]))
+            probs = platt.apply(logits)
+            print("Calibration: per-class Platt scaling of %s applied to the probabilities" % os.path.basename(args.calibration))
+        else:
+            temperature = calibration
+            print("Calibration: temperature T = %.3f of %s (applies to --softmax)"
+                  % (temperature.temperature, os.path.basename(args.calibration)))
+
     per_class = None
     if args.thresholds:
         per_class = np.load(args.thresholds).astype(np.float32)
         if per_class.shape != (probs.shape[1],):
             sys.exit("%s holds %s thresholds, the model has %d classes" % (args.thresholds, per_class.shape, probs.shape[1]))
         with torch.no_grad():
-            sample_labels = np.where(model.tag(waveform, per_class)["labels"][0].cpu())[0]      # probs >= threshold, per class
+            sample_labels = np.where(model.tag(waveform, per_class, calibration=platt)["labels"][0].cpu())[0]   # probs >= threshold
         print("Predicted labels using the per-class thresholds of %s:\n" % os.path.basename(args.thresholds))
     else:
         sample_labels = np.where(probs[0].clone().detach().cpu() > args.threshold)[0]
@@ -100,7 +118,7 @@ def main():
 
     if args.softmax:
         with torch.no_grad():
-            res = model.classify(waveform, k=min(args.top, 64))
+            res = model.classify(waveform, k=min(args.top, 64), calibration=temperature)
         print("\nTop classes by softmax:\n")
         for c, p in zip(res["top_indices"][0].tolist(), res["top_probabilities"][0].tolist()):
             print("%s: %.3f" % (ix_to_lb[c] if ix_to_lb else "class %d" % c, p))

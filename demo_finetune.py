@@ -13,7 +13,9 @@ order).  With a validation split, one decision threshold per class is chosen on 
 and written next to <out> as <out>.thresholds.npy -- demo_convnext.py --thresholds takes it.  16-bit PCM WAV files at any rate
 (resampled on the device).  --loss ce trains a single-label head (every clip needs exactly one label): it prints validation
 accuracy, top-5 accuracy and the five largest confusions, and writes no thresholds file -- read the model with
-ConvNeXt.classify / demo_convnext.py --softmax."""
+ConvNeXt.classify / demo_convnext.py --softmax.  With a validation split the head's probabilities are also calibrated on it
+(pytorch/calibration.py: per-class Platt scaling for --loss bce, temperature scaling for --loss ce): the ECE before and after is
+printed and the map written as <out>.calibration.npz -- demo_convnext.py --calibration takes it."""
 import argparse
 import csv
 import os
@@ -137,12 +139,21 @@ def main():
                                                                            ", validation included" if n_val else ""))
 
     thresholds = None
+    calibration = None
     if n_val and ce:
+        from audioset_convnext_inf_amd.pytorch import calibration as cal
         from audioset_convnext_inf_amd.pytorch.classify import classification_metrics
         head = model.head_audioset
         with torch.no_grad():
-            m = classification_metrics(target[va].int().argmax(dim=1), torch.addmm(head.bias, emb[va], head.weight.t()),
-                                       k=5, confusion=len(names) <= 4096)
+            val_labels = target[va].int().argmax(dim=1)
+            val_logits = torch.addmm(head.bias, emb[va], head.weight.t())
+            m = classification_metrics(val_labels, val_logits, k=5, confusion=len(names) <= 4096)
+            calibration = cal.fit_temperature(val_labels, val_logits)
+            before = cal.reliability_toplabel(val_labels, val_logits)
+            after = cal.reliability_toplabel(val_labels, val_logits, calibration=calibration)
+        note = {cal.NOT_CONVERGED: " (not converged)", cal.AT_BOUND: " (at a bound)", cal.DEGENERATE: " (constant rows)"}
+        print("temperature scaling: T = %.3f%s  top-label ECE before %.4f  after %.4f  (NLL %.4f -> %.4f)"
+              % (calibration.temperature, note.get(int(calibration.info.item()), ""), before.ece, after.ece, before.nll, after.nll))
         print("val accuracy %.3f  top-%d accuracy %.3f  balanced accuracy %.3f  macro F1 %.3f  (%d clips)"
               % (m.accuracy, m.k, m.topk_accuracy, m.balanced_accuracy, m.macro_f1, m.counted))
         if m.confusion is not None:
@@ -157,8 +168,17 @@ def main():
         import warnings
         from audioset_convnext_inf_amd.pytorch.metrics import operating_points
         head = model.head_audioset
+        from audioset_convnext_inf_amd.pytorch import calibration as cal
         with torch.no_grad():
-            probs = torch.sigmoid(torch.addmm(head.bias, emb[va], head.weight.t()))
+            val_logits = torch.addmm(head.bias, emb[va], head.weight.t())
+            probs = torch.sigmoid(val_logits)
+            calibration = cal.fit_platt(target[va], val_logits)
+            before = cal.reliability(target[va], probs)
+            after = cal.reliability(target[va], calibration.apply(val_logits))
+        info = calibration.info.cpu().numpy()
+        print("Platt scaling: class-wise ECE before %.4f  after %.4f  (Brier %.4f -> %.4f; %d of %d classes kept the identity, "
+              "%d did not converge)" % (before.classwise_ece, after.classwise_ece, before.brier.mean(), after.brier.mean(),
+                                        int((info == cal.DEGENERATE).sum()), len(names), int((info == cal.NOT_CONVERGED).sum())))
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", UserWarning)          # classes the split holds no positive of: counted below
             op = operating_points(target[va], probs, criterion="f1")
@@ -177,6 +197,11 @@ def main():
         thr_path = a.out.rstrip("/" + os.sep) + ".thresholds.npy"
         np.save(thr_path, thresholds)
         print("wrote %s: %d per-class thresholds (demo_convnext.py --thresholds)" % (thr_path, len(thresholds)))
+    if calibration is not None:
+        cal_path = a.out.rstrip("/" + os.sep) + ".calibration.npz"
+        calibration.save(cal_path)
+        print("wrote %s: the %s map fitted on the validation split (demo_convnext.py --calibration)"
+              % (cal_path, "temperature" if ce else "Platt"))
     print("wrote %s: model.safetensors, model.pth, labels.txt -- ConvNeXt.from_pretrained(%r) loads it as a %d-class model"
           % (a.out, os.path.join(a.out, "model.safetensors"), len(names)))
 

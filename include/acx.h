@@ -723,6 +723,72 @@ ACX_API int acx_softmax_topk(const float* logits, int64_t ld, int64_t rows, int 
 ACX_API int acx_classification_counts(const float* logits, int64_t ld, const int64_t* labels, int64_t n, int classes, int k,
                                       int64_t* per_class, int64_t* hits, int64_t* confusion, int32_t* status, void* stream);
 
+/* ---- calibration: reliability (ECE / MCE / Brier), per-class Platt scaling, temperature scaling ---------------------------------
+ * What the probabilities of a head mean, measured and repaired on the device.  Stateless: no context, the caller owns every
+ * buffer (all on the device), everything runs on `stream`, nothing allocates or synchronises; capturable.  Each call clears
+ * *status (4 bytes) on `stream` first and writes every element of its outputs.  The definitions are the float64 numpy
+ * functions of pytorch/calibration.py (reliability_host, reliability_toplabel_host, fit_platt_host, fit_temperature_host,
+ * platt_apply_host): Platt 1999 with the Newton / backtracking solver of Lin, Lin & Weng 2007; temperature scaling and ECE as
+ * in Guo et al. 2017.  With a non-zero status the outputs are not to be read.
+ *   bin of a probability p with `bins` bins (1 .. ACX_CAL_MAX_BINS): min(bins - 1, (int)(p * (float)bins)), the product in
+ *     float32: p = 1 falls into the last bin, an edge k / bins belongs to bin k.
+ *   acx_reliability_counts: probs (n, classes) fp32 with row stride ld against targets as acx_threshold_counts takes them.
+ *     count / positive [classes][bins] int64: rows per bin and the positives among them (exact); conf_sum [classes][bins]
+ *     double: the sum of p per bin; brier_sum [classes] double: the sum of (p - y)^2.  The float64 sums have ONE order: a
+ *     (class, bin) sum runs over ascending rows, brier_sum adds the bins' partials by a fixed tree -- the same call gives the
+ *     same bits.  p outside [0, 1] sets ACX_CAL_BAD_PROBABILITY, a NaN or infinity ACX_CAL_NONFINITE, a target other than 0 / 1
+ *     ACX_CAL_BAD_TARGET.
+ *   acx_reliability_toplabel: logits (n, classes) fp32, int64 labels, *beta a DEVICE double (NULL: 1).  The scaled logit is
+ *     (float)beta * z (one rounding); the confidence is the top-1 softmax probability of the scaled row with the bits of
+ *     acx_softmax_topk's top_prob[:, 0] on the scaled logits; the prediction is the first index of the row maximum.  count /
+ *     correct [bins] int64, conf_sum [bins] double, nll_sum [1] double = sum of log s + (m - z_y) over the counted rows, in one
+ *     fixed order.  A row holding a NaN or an infinity, or a label outside [0, classes), is counted nowhere and sets
+ *     ACX_CAL_NONFINITE / ACX_CAL_BAD_LABEL.  workspace: acx_temperature_workspace_bytes(n, classes) bytes.
+ *   acx_platt_fit: per class c the minimiser (a, b) of F = - sum_i [t_i log p_i + (1 - t_i) log(1 - p_i)], p_i = sigmoid(a z_ic +
+ *     b); smooth != 0: Platt's targets t+ = (P + 1) / (P + 2), t- = 1 / (Nn + 2), else t = y.  ab [classes][2] double; info
+ *     [classes] int32: the Newton iterations used, ACX_CAL_DEGENERATE (no positive, no negative or a constant column: the
+ *     identity a = 1, b = 0 is returned) or ACX_CAL_NOT_CONVERGED (100 iterations; e.g. smooth = 0 on a separable class).  One
+ *     launch fits all classes, the whole iteration on the device.  Status bits as acx_reliability_counts.
+ *   acx_platt_apply: probs[r][c] = sigmoid_f32(fmaf((float)a_c, z, (float)b_c)) with the forward's sigmoid: a = 1, b = 0 gives
+ *     the bits of clipwise_output.  rows x classes, row strides ld / ld_p.
+ *   acx_temperature_fit: the minimiser over beta = 1 / T in [1e-4, 1e4] of F = sum_i [logsumexp_c(beta z_ic) - beta z_i,y_i],
+ *     Newton with step halving from beta = 1.  The call queues `evaluations` (1 .. ACX_CAL_MAX_EVALUATIONS) launches, one pass
+ *     over the logits each; the decision stays in device memory and launches after the stop return at once.  beta [1] double
+ *     and info [1] int32 ON THE DEVICE: info = the evaluations used, ACX_CAL_DEGENERATE (every row constant: beta = 1),
+ *     ACX_CAL_NOT_CONVERGED (evaluations used up; beta = the last accepted value) or ACX_CAL_AT_BOUND (the iteration stopped
+ *     against 1e-4 or 1e4).  Rows flagged as in acx_reliability_toplabel enter no sum.
+ *   acx_temperature_apply: out[r][c] = (float)beta * z (the input of acx_softmax_topk); row strides ld / ld_o.
+ * ARGUMENT errors (before any launch): a null pointer, n / rows < 1, classes outside 1 .. ACX_MAX_CLASSES, a row stride shorter
+ * than its row, bins or evaluations out of range, a bad target_dtype; n > 2^30 is ACX_ERR_UNSUPPORTED; a workspace too small
+ * or not 256-byte aligned is ACX_ERR_WORKSPACE. */
+#define ACX_CAL_MAX_BINS 64
+#define ACX_CAL_MAX_EVALUATIONS 64
+#define ACX_CAL_NONFINITE 1
+#define ACX_CAL_BAD_TARGET 2
+#define ACX_CAL_BAD_PROBABILITY 4
+#define ACX_CAL_BAD_LABEL 8
+#define ACX_CAL_DEGENERATE (-1)
+#define ACX_CAL_NOT_CONVERGED (-2)
+#define ACX_CAL_AT_BOUND (-3)
+ACX_API int acx_reliability_counts(const float* probs, int64_t ld, const void* target, int target_dtype, int64_t ld_t, int64_t n,
+                                   int classes, int bins, int64_t* count, int64_t* positive, double* conf_sum, double* brier_sum,
+                                   int32_t* status, void* stream);
+ACX_API int acx_reliability_toplabel(const float* logits, int64_t ld, const int64_t* labels, int64_t n, int classes,
+                                     const double* beta, int bins, int64_t* count, int64_t* correct, double* conf_sum,
+                                     double* nll_sum, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+ACX_API int acx_platt_workspace_bytes(int64_t n, int classes, size_t* out_bytes);                              /* host only */
+ACX_API int acx_platt_fit(const float* logits, int64_t ld, const void* target, int target_dtype, int64_t ld_t, int64_t n,
+                          int classes, int smooth, double* ab, int32_t* info, int32_t* status, void* workspace,
+                          size_t workspace_bytes, void* stream);
+ACX_API int acx_platt_apply(const float* logits, int64_t ld, int64_t rows, int classes, const double* ab, float* probs,
+                            int64_t ld_p, void* stream);
+ACX_API int acx_temperature_workspace_bytes(int64_t n, int classes, size_t* out_bytes);                        /* host only */
+ACX_API int acx_temperature_fit(const float* logits, int64_t ld, const int64_t* labels, int64_t n, int classes, int evaluations,
+                                double* beta, int32_t* info, int32_t* status, void* workspace, size_t workspace_bytes,
+                                void* stream);
+ACX_API int acx_temperature_apply(const float* logits, int64_t ld, int64_t rows, int classes, const double* beta, float* out,
+                                  int64_t ld_o, void* stream);
+
 /* ---- nearest-neighbour search over embeddings: top-k by dot product or cosine, and kNN tagging ----------------------------------
  * The reference's checkpoint is "for audio tagging and embedding extraction"; this is what the embeddings are extracted for:
  * query by example, and the kNN probe of a frozen representation.  Stateless: the caller owns every buffer (all on the device).
