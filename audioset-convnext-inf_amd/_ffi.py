@@ -118,6 +118,14 @@ SIGNATURES = {
                                              _c_sz, _vp, _vp, _vp]),
     "acx_decode_events_varlen_classwise": (_c_int, [_vp, _c_i64, _pint, _pdbl, _c_int, _c_int, _pevp, _c_dbl, _vp, _c_i64, _vp, _vp,
                                                     _vp, _c_sz, _vp, _vp, _vp]),
+    "acx_event_stream_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_event_stream_create": (_c_int, [_c_int, _c_int, _pevp, _c_dbl, _vp, _vp, ctypes.POINTER(_vp)]),
+    "acx_event_stream_destroy": (None, [_vp]),
+    "acx_event_stream_push": (_c_int, [_vp, _vp, _c_i64, _pint, _pint, _c_int, _vp, _c_i64, _vp, _vp, _vp]),
+    "acx_event_stream_close": (_c_int, [_vp, _pint, _pdbl, _c_int, _vp, _c_i64, _vp, _vp, _vp]),
+    "acx_event_stream_open": (_c_int, [_vp, _pint, _c_int, _vp, _vp]),
+    "acx_event_stream_steps": (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64)]),
+    "acx_event_stream_undo": (_c_int, [_vp, _pint, _c_int]),
     "acx_score_events": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _pcol, _vp, _vp, _vp, _vp,
                                   _vp]),
     "acx_score_segments": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _c_dbl, _vp, _vp, _vp,
@@ -619,6 +627,11 @@ def event_params(threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=
 def events_workspace_bytes(B, N):
     """Workspace of acx_decode_events / acx_decode_events_varlen for B clips of N classes (host only)."""
     return _query(lib().acx_events_workspace_bytes, _c_sz, int(B), int(N))
+
+
+def event_stream_bytes(slots, N, median):
+    """Device state of an acx_event_stream handle of `slots` recordings of N classes (host only)."""
+    return _query(lib().acx_event_stream_bytes, _c_sz, int(slots), int(N), int(median))
 
 
 SCORE_BAD_TABLE = 1                           # bit of the status word of acx_score_events / acx_score_segments

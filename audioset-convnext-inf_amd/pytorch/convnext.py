@@ -757,7 +757,7 @@ class ConvNeXt(nn.Module):
         return results[0] if single else results
 
     def stream(self, slots=256, window=10.0, hop=1.0, what="logits", sample_rate=None, timeline="mean", max_push=2.0,
-               max_batch=64):
+               max_batch=64, events=None, event_source="windows"):
         """A live-stream handle (pytorch/stream.py): `slots` recordings pushed chunk by chunk, each tagged window by window as
         soon as a window is complete, with the bits of forward_windows over the whole recording for any chunking.
         st.push(chunks) -- a list of `slots` 1-D CUDA tensors or None, or {slot: tensor} -- and st.close(slots=None) return
@@ -767,9 +767,20 @@ class ConvNeXt(nn.Module):
         length and emitted nothing.  window / hop: seconds, whole samples at 32 kHz; sample_rate: the input rate of every
         slot; max_push: the longest chunk the device state is sized for, in seconds -- a longer one is pushed in pieces;
         max_batch: windows per forward.  Segment outputs (forward_segments) are not part of live streams: run
-        forward_windows(what="segment") on the finished recording."""
+        forward_windows(what="segment") on the finished recording.
+        events: a dict of decode_events' threshold / low / median / min_duration / merge_gap (what="logits" only) -- the
+        handle then decodes sound events live, one step per hop, with an online decoder whose state lives on the device
+        (segments.EventStream): every push() / close() dict gains "events", the EventTable (clip = slot, begin / end in hops
+        of the slot's recording) of the events this call made final, each handed out once, and "events_open", (n, N) int32
+        per slot touched (ascending) and class the step at which the event the class is inside of began, or -1.
+        event_source="windows": row j is window j's "clipwise_output"; detection lags the audio by one window plus
+        median // 2 hops plus merge_gap -- the low-latency form.  "timeline": the rows are the timeline's (needs timeline=)
+        and inherit its trail; the last boundary is the end of the audio.  Over all calls a recording's events are
+        decode_events_gpu of forward_windows' rows of the whole recording, byte for byte.  close() reads the last push's event
+        count before it ends the recordings (one small synchronisation)."""
         return _stream.Stream(self, slots=slots, window=window, hop=hop, what=what, sample_rate=sample_rate,
-                              timeline=timeline, max_push=max_push, max_batch=max_batch)
+                              timeline=timeline, max_push=max_push, max_batch=max_batch, events=events,
+                              event_source=event_source)
 
     def fit_head(self, data, target, sample_rate=None, **kw):
         """Train a new classifier head on this (frozen) backbone and install it (pytorch/finetune.py, fit_head): `data` is an

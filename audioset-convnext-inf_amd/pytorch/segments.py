@@ -1,7 +1,8 @@
 """Sound event detection on the host side (ConvNeXt.forward_segments / forward_segment_embeddings, include/acx.h "sound event
 detection"): the geometry of segments, frames and the segment timeline -- one definition shared with the C ABI -- and the
 decoding of probabilities over time into events: decode_events on the host -- nothing down to it touches the GPU -- and
-decode_events_gpu / EventTable, the same decoding for whole batches on the device (acx_decode_events).
+decode_events_gpu / EventTable, the same decoding for whole batches on the device (acx_decode_events), and for rows that arrive
+chunk by chunk OnlineEventDecoderHost, the definition, and EventStream, its device form (acx_event_stream_*).
 
 The trunk halves time four times after a stride-4 stem on hop-320 frames, so one row of the stage-3 map -- one SEGMENT -- stands
 for 32 STFT frames = 10240 samples = 0.32 s at 32 kHz.  A clip of L samples has T = L // 320 + 1 frames and
@@ -192,6 +193,141 @@ def decode_events(probs, threshold=0.5, low=None, median=1, min_duration=0.0, me
                            float(col[b:e].max()), float(col[b:e].mean())))
     events.sort(key=lambda ev: (ev[1], ev[2], str(ev[0])))
     return events
+
+
+class OnlineEventDecoderHost:
+    """decode_events for ONE recording whose rows arrive chunk by chunk: the definition of the online decoder (include/acx.h
+    "online event decoding", csrc/events_online.hip), the per-column state machine of csrc/events_common.h restated step by
+    step on the host, every class at once.  push(rows) takes (r, classes) rows, r >= 0, and returns the events this call makes
+    final; close(end_seconds=None) flushes and returns the rest (the decoder then stands ready for a new recording).  Events
+    are rows (cls, begin, end, peak, mean) in (cls, begin) order, begin / end in absolute steps of the recording; over all
+    calls they are decode_events of the concatenated rows, each exactly once, for any chunking (mean: the float64 sum in
+    ascending time over [begin, end) divided by the count; decode_events takes numpy's float32 mean).
+
+    Filtered row t exists once raw row t + median // 2 has been pushed (the front repeats row 0; close repeats the last row).
+    After filtered row t a pending event [eb, ee) is final -- and emitted, if edge(ee) - edge(eb) is no shorter than
+    min_duration -- when a run is open that began at rb and not edge(rb) - edge(ee) < merge_gap, or when no run is open and
+    not edge(t + 1) - edge(ee) < merge_gap, with edge(k) = float64(k) * step: k * step never decreases in k, so no later run
+    could have merged.  A run still open is part of no emitted event.  The free last boundary enters only in close().
+    open_begin()[c]: the step at which the event that class c is inside of began -- the pending event's begin when the open
+    run will merge with it, else the run's -- once the open run has reached `threshold`; -1 otherwise."""
+
+    def __init__(self, classes, threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=0.0, step=SEGMENT_SECONDS):
+        if isinstance(classes, bool) or not isinstance(classes, (int, np.integer)) or classes < 1:
+            raise ValueError("classes must be a positive integer (got %r)" % (classes,))
+        threshold, low = _host_level(threshold), _host_level(low)
+        low = threshold if low is None else low
+        _check_levels(threshold, low, classes)
+        if isinstance(median, bool) or not isinstance(median, int) or median < 1 or median % 2 == 0:
+            raise ValueError("median must be an odd positive integer (got %r)" % (median,))
+        if min_duration < 0 or merge_gap < 0:
+            raise ValueError("min_duration and merge_gap must not be negative")
+        if np.ndim(step) != 0 or not step > 0:
+            raise ValueError("step must be a positive number of seconds (got %r)" % (step,))
+        N = self.classes = int(classes)
+        self.thr = np.broadcast_to(np.asarray(threshold, dtype=np.float32), (N,))
+        self.low = np.broadcast_to(np.asarray(low, dtype=np.float32), (N,))
+        self.median, self.h = median, median // 2
+        self.min_duration, self.merge_gap, self.step = float(min_duration), float(merge_gap), float(step)
+        self._reset()
+
+    def _reset(self):
+        N = self.classes
+        self.steps = 0                       # raw rows of the open recording
+        self.t = 0                           # filtered rows consumed
+        self._raw = {}                       # raw row i, for the rows a filtered row still to come reads
+        self._end = None                     # close(): (steps, end_seconds) of edge()
+        self.in_run, self.rvalid, self.have = (np.zeros(N, dtype=bool) for _ in range(3))
+        self.rb, self.eb, self.ee = (np.zeros(N, dtype=np.int64) for _ in range(3))
+        self.rmax, self.emax, self.epeak = (np.zeros(N, dtype=np.float32) for _ in range(3))
+        self.rsum, self.esum, self.esnap = (np.zeros(N, dtype=np.float64) for _ in range(3))
+
+    def _edge(self, k):
+        e = np.asarray(k, dtype=np.float64) * self.step
+        if self._end is not None:
+            e = np.where(np.asarray(k) < self._end[0], e, self._end[1])
+        return e
+
+    def _finish_event(self, m, out):
+        keep = m & ~(self._edge(self.ee) - self._edge(self.eb) < self.min_duration)
+        for c in np.nonzero(keep)[0]:
+            b, e = int(self.eb[c]), int(self.ee[c])
+            out.append((int(c), b, e, float(self.epeak[c]), float(self.esnap[c] / np.float64(e - b))))
+
+    def _end_run(self, t, m, out):
+        self.in_run[m] = False
+        m = m & self.rvalid
+        merge = m & self.have & (self._edge(self.rb) - self._edge(self.ee) < self.merge_gap)
+        self.ee[merge] = t
+        self.epeak[merge] = self.emax[merge]
+        self.esnap[merge] = self.esum[merge]
+        new = m & ~merge
+        self._finish_event(new & self.have, out)
+        self.have[new] = True
+        self.eb[new] = self.rb[new]
+        self.ee[new] = t
+        self.epeak[new] = self.emax[new] = self.rmax[new]
+        self.esnap[new] = self.esum[new] = self.rsum[new]
+
+    def _step(self, t, p, out):
+        on = p >= self.low
+        self._end_run(t, ~on & self.in_run, out)
+        hv = self.have
+        self.emax[hv] = np.maximum(self.emax[hv], p[hv])
+        self.esum[hv] += p[hv].astype(np.float64)
+        start = on & ~self.in_run
+        self.in_run[start] = True
+        self.rb[start] = t
+        self.rvalid[start] = False
+        self.rmax[start] = p[start]
+        self.rsum[start] = 0.0
+        self.rmax[on] = np.maximum(self.rmax[on], p[on])
+        self.rsum[on] += p[on].astype(np.float64)
+        self.rvalid[on] |= p[on] >= self.thr[on]
+        # early emission: the pending event is final once nothing still to come can merge with it
+        since = np.where(self.in_run, self.rb, t + 1)
+        final = self.have & ~(self._edge(since) - self._edge(self.ee) < self.merge_gap)
+        self._finish_event(final, out)
+        self.have[final] = False
+
+    def _consume(self, upto, last, out):
+        """filtered rows t .. upto - 1; raw rows past `last` repeat row `last`"""
+        h = self.h
+        while self.t < upto:
+            t = self.t
+            win = np.stack([self._raw[min(max(t + j, 0), last)] for j in range(-h, h + 1)])
+            self._step(t, np.median(win, axis=0).astype(np.float32), out)
+            self.t = t + 1
+
+    def push(self, rows):
+        rows = np.asarray(rows.detach().cpu().numpy() if hasattr(rows, "detach") else rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.classes:
+            raise ValueError("push expects (rows, %d) probabilities, got shape %r" % (self.classes, rows.shape))
+        if not np.isfinite(rows).all():
+            raise ValueError("the probabilities hold a NaN or an infinity")
+        for r in rows:
+            self._raw[self.steps] = r
+            self.steps += 1
+        out = []
+        self._consume(self.steps - self.h, self.steps - 1, out)
+        for i in [i for i in self._raw if i < self.t - self.h]:     # what no filtered row still to come reads
+            del self._raw[i]
+        return sorted(out, key=lambda e: (e[0], e[1]))
+
+    def close(self, end_seconds=None):
+        out = []
+        n = self.steps
+        if n:
+            self._consume(n, n - 1, out)
+            self._end = (n, float(end_seconds) if end_seconds is not None and end_seconds > 0 else float(n) * self.step)
+            self._end_run(n, self.in_run.copy(), out)
+            self._finish_event(self.have, out)
+        self._reset()
+        return sorted(out, key=lambda e: (e[0], e[1]))
+
+    def open_begin(self):
+        merges = self.have & (self._edge(self.rb) - self._edge(self.ee) < self.merge_gap)
+        return np.where(self.in_run & self.rvalid, np.where(merges, self.eb, self.rb), -1).astype(np.int64)
 
 
 # ---- the same decoding on the device (include/acx.h "sound event decoding", csrc/events.hip) ---------------------------------
@@ -470,3 +606,369 @@ def decode_events_gpu(probs, threshold=0.5, low=None, median=1, min_duration=0.0
         return table, count, status
 
     return EventTable(*run(cap0), edges=edges, classes=N, rerun=run)
+
+
+# ---- the online decoder on the device (include/acx.h "online event decoding", csrc/events_online.hip) -------------------------
+
+class _StreamEvents(EventTable):
+    """The EventTable of one EventStream call: `clip` is the slot, begin / end are steps of the slot's recording.  A call over
+    more than 256 slots (and a ConvNeXt.stream call that pushes and closes) is several device calls: their tables are joined
+    -- in call order, each ordered (slot, cls, begin) -- when the table is first read, so `table`, `count`, `status` and the
+    column views then wait for the decoding like len() does.  to_lists() returns {slot: events} over the slots of the call."""
+
+    def __init__(self, owner, parts):
+        self._owner, self._parts = owner, parts
+        self.classes = owner.classes
+        self.edges = None
+        self._rerun = None
+        self._n = None
+        if len(parts) == 1:
+            self._set(parts[0]["table"], parts[0]["count"], parts[0]["status"])
+
+    def __getattr__(self, name):
+        # a joined table exists once its parts have been read
+        if name in ("table", "count", "status", "clip", "cls", "begin", "end", "peak", "mean") and self._n is None:
+            self.check()
+            return getattr(self, name)
+        raise AttributeError(name)
+
+    def check(self):
+        """Waits for the decoding.  A part whose table was too small is issued once more at the exact size -- the device state
+        is untouched by a void call -- and a part whose rows held a NaN or an infinity raises ValueError: its slots have
+        consumed nothing (reading again gives the events of the other parts)."""
+        if self._n is not None:
+            return self
+        own = self._owner
+        if own is not None and own._pending is self:
+            own._pending = None
+        torch = _torch()
+        parts = self._parts
+        refused = []
+        for p in parts:
+            p["done"].synchronize()
+            m = p["seen"]
+            n, st = int(m[:2].view(torch.int64)), int(m[2])
+            if st & _ffi.EVENTS_NONFINITE:
+                own._undo(p["slots"])
+                refused.append(p)
+                continue
+            if st & _ffi.EVENTS_OVERFLOW or n > p["table"].shape[0]:
+                own._undo(p["slots"])
+                p.update(p["issue"](n))
+                p["done"].synchronize()
+                m = p["seen"]
+                n2, st = int(m[:2].view(torch.int64)), int(m[2])
+                if st or n2 != n:
+                    raise RuntimeError("event stream: status %d, %d events for %d rows after the second pass" % (st, n2, n))
+            p["n"] = n
+        if refused:
+            self._parts = [p for p in parts if p not in refused]
+            raise ValueError("the probabilities hold a NaN or an infinity (slots %s: their rows were not consumed)"
+                             % sorted(s for p in refused for s in p["slots"]))
+        if len(parts) == 1:
+            self._set(parts[0]["table"], parts[0]["count"], parts[0]["status"])
+        else:
+            dev = own.device
+            rows = [p["table"][:p["n"]] for p in parts if p["n"]]
+            total = sum(p["n"] for p in parts)
+            self._set(torch.cat(rows) if rows else torch.zeros((1, _ffi.EVENT_BYTES // 4), dtype=torch.int32, device=dev),
+                      torch.tensor([total], dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        self._n = sum(p["n"] for p in parts)
+        return self
+
+    def to_lists(self, labels=None):
+        """{slot: [(class, onset_s, offset_s, peak, mean), ...]} over the slots of the call, each list sorted like
+        decode_events' output; onset / offset are k * step, and the recording's own last boundary where close() gave one."""
+        if labels is not None and len(labels) != self.classes:
+            raise ValueError("%d labels for %d classes" % (len(labels), self.classes))
+        n = len(self)
+        step = self._owner.step
+        ends = {}
+        out = {}
+        for p in self._parts:
+            for s in p["slots"]:
+                out.setdefault(s, [])
+            ends.update(p.get("ends") or {})
+        rows = self.table[:n].cpu().contiguous().numpy()
+        clip, cls, begin, end = (rows[:, i].tolist() for i in range(4))
+        peak = rows.view(np.float32)[:, 4].tolist()
+        mean = rows.view(np.float64)[:, 3].tolist()
+        for i in range(n):
+            last = ends.get(clip[i])
+            off = last[1] if last is not None and end[i] >= last[0] else float(np.float64(end[i]) * step)
+            c = cls[i]
+            out[clip[i]].append((labels[c] if labels is not None else c, float(np.float64(begin[i]) * step), off, peak[i], mean[i]))
+        for events in out.values():
+            events.sort(key=lambda ev: (ev[1], ev[2], str(ev[0])))
+        return out
+
+
+class EventStream:
+    """decode_events_gpu for recordings whose rows arrive chunk by chunk (acx_event_stream_*): `slots` recordings at a time,
+    each column's state carried across calls on the device.  Every event is handed out exactly once, as soon as nothing still
+    to come can change it (OnlineEventDecoderHost is the definition), and the rows of all calls of a recording, sorted by
+    (cls, begin), are the rows of decode_events_gpu over the whole matrix byte for byte, for any chunking.  Arguments as
+    decode_events_gpu's; step is the seconds per row (the recording's last boundary is close()'s end_seconds).  Per-class
+    threshold / low (host arrays or CUDA tensors) are copied and checked here: a bad level raises ValueError at once.
+
+    push() and close() run on the current stream without synchronising and return an EventTable with clip = slot.  A table
+    that turns out too small is decoded again at the exact size when it is first read: a void call leaves the device state
+    untouched.  For that to hold, while a table of the handle is unchecked a further push() or close() on the handle checks
+    it first -- one read of its count / status, which waits for that earlier call alone (the two words were copied to pinned
+    memory behind it), not for work queued since."""
+
+    def __init__(self, slots, classes, threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=0.0, step=SEGMENT_SECONDS,
+                 device=None):
+        torch = _torch()
+        if isinstance(slots, bool) or not isinstance(slots, int) or not 1 <= slots <= (1 << 20):
+            raise ValueError("slots must be an integer in [1, 2^20] (got %r)" % (slots,))
+        if isinstance(classes, bool) or not isinstance(classes, int) or not 1 <= classes <= _ffi.MAX_CLASSES:
+            raise ValueError("classes must be an integer in [1, %d] (got %r)" % (_ffi.MAX_CLASSES, classes))
+        scalar_levels = _is_number(threshold) and (low is None or _is_number(low))
+        threshold, low = check_event_args(threshold, low, median, min_duration, merge_gap, classes)
+        if np.ndim(step) != 0 or not step > 0:
+            raise ValueError("step must be a positive number of seconds (got %r)" % (step,))
+        self._h = None
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("an EventStream lives on a CUDA device (got %s)" % (self.device,))
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.slots, self.classes, self.step, self.median = slots, classes, float(step), median
+        dev = self.device
+
+        def level(v):
+            if v is None or _is_number(v):
+                return None
+            return (v.detach().to(device=dev, dtype=torch.float32) if _on_device(v) else torch.from_numpy(v).to(dev)).contiguous()
+        thr_t = None if scalar_levels else level(threshold)
+        low_t = None if scalar_levels or low is threshold else level(low)
+        if not scalar_levels and low_t is None and thr_t is not None and low is not threshold:
+            low_t = torch.full((classes,), float(low), dtype=torch.float32, device=dev)
+        params = _ffi.event_params(threshold if thr_t is None else 0.0, low if _is_number(low) else 0.0, median, min_duration,
+                                   merge_gap)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(dev):
+            torch.cuda.current_stream(dev).synchronize()               # the levels are read now
+            try:
+                _ffi.check(_ffi.lib().acx_event_stream_create(slots, classes, ctypes.byref(params), self.step, _ffi.vp(thr_t),
+                                                              _ffi.vp(low_t), ctypes.byref(h)))
+            except _ffi.AcxError as e:
+                if "must be in [0, threshold" in str(e):
+                    raise ValueError("low must be in [0, threshold] in every class (%s)" % e) from None
+                raise
+        self._h = h
+        self._pending = None
+        self._last = None
+        self._open = set()              # slots pushed to since their last close
+
+    def close_handle(self):
+        if self._h is not None and self._h.value:
+            _ffi.lib().acx_event_stream_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close_handle()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------------------------------------------------- helpers
+    def _slot(self, s):
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s < self.slots:
+            raise ValueError("slot %r out of range (the stream has %d slots)" % (s, self.slots))
+        return int(s)
+
+    def _enter(self):
+        """The handle's calls run in order: the table still unchecked is checked, a new current stream waits for the last."""
+        torch = _torch()
+        if self._pending is not None:
+            self._pending.check()
+        cur = torch.cuda.current_stream(self.device)
+        if self._last is not None and self._last != cur:
+            ev = torch.cuda.Event()
+            ev.record(self._last)
+            cur.wait_event(ev)
+        self._last = cur
+
+    def _undo(self, slots):
+        arr = (ctypes.c_int * len(slots))(*slots)
+        _ffi.check(_ffi.lib().acx_event_stream_undo(self._h, arr, len(slots)))
+
+    def _part(self, slots, cap, call, ends=None):
+        """One device call -> a part of a _StreamEvents; call(table, cap, count, status) issues it."""
+        torch = _torch()
+        dev = self.device
+
+        def issue(c):
+            with torch.cuda.device(dev):
+                table = torch.zeros((max(c, 1), _ffi.EVENT_BYTES // 4), dtype=torch.int32, device=dev)
+                meta = torch.zeros(4, dtype=torch.int32, device=dev)
+                count, status = meta[:2].view(torch.int64), meta[2:3]
+                call(table.data_ptr(), c, count.data_ptr(), status.data_ptr(), _ffi.stream_ptr(dev))
+                # count / status travel to pinned memory behind the call: reading them later waits for this call alone,
+                # not for whatever the stream has been given since
+                seen = torch.empty(4, dtype=torch.int32, pin_memory=True)
+                seen.copy_(meta, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(torch.cuda.current_stream(dev))
+            return dict(table=table, meta=meta, count=count, status=status, seen=seen, done=done)
+        p = dict(slots=slots, issue=issue, ends=ends)
+        p.update(issue(cap))
+        return p
+
+    def _capacity(self, capacity, n):
+        if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0):
+            raise ValueError("capacity must be a non-negative integer (got %r)" % (capacity,))
+        return max(1024, 16 * n) if capacity is None else capacity
+
+    def _result(self, parts):
+        t = _StreamEvents(self, parts)
+        self._pending = t
+        return t
+
+    # ------------------------------------------------------------------------------------------------------------- calls
+    def push(self, probs, slots=None, steps=None, capacity=None):
+        """probs: a (r, N) fp32 CUDA tensor for one slot (slots=the slot, default 0), a {slot: (r_i, N)} dict, or one packed
+        (sum(steps), N) tensor with slots=[...] and steps=[...] (r_i >= 0).  More than 256 slots are split into several device
+        calls; capacity (default max(1024, 16 * slots of the call)) is each call's.  Returns the events this call makes final."""
+        torch = _torch()
+        packed = None
+        if isinstance(probs, dict):
+            if slots is not None or steps is not None:
+                raise ValueError("slots= / steps= go with a tensor, not with a dict")
+            items = [(self._slot(s), t) for s, t in probs.items()]
+        elif steps is not None:
+            if slots is None or not isinstance(probs, torch.Tensor) or probs.dim() != 2:
+                raise ValueError("steps= goes with one packed (rows, classes) tensor and slots=")
+            slots, steps = [self._slot(s) for s in slots], [int(n) for n in steps]
+            if len(slots) != len(steps) or min(steps, default=0) < 0 or sum(steps) != probs.shape[0]:
+                raise ValueError("steps=%r of %d slots do not add up to the %d packed rows" % (steps[:8], len(slots), probs.shape[0]))
+            at, items = 0, []
+            for s, n in zip(slots, steps):
+                items.append((s, probs[at:at + n]))
+                at += n
+            if all(a < b for a, b in zip(slots, slots[1:])):
+                packed = probs
+        else:
+            items = [(self._slot(0 if slots is None else slots), probs)]
+        if not items:
+            raise ValueError("push expects at least one slot")
+        if len({s for s, _ in items}) != len(items):
+            raise ValueError("a slot is listed twice")
+        for _, t in items:
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != self.classes:
+                raise ValueError("push expects (rows, %d) probabilities, got %r" % (self.classes, getattr(t, "shape", type(t))))
+            if not t.is_cuda or t.device != self.device:
+                raise ValueError("push expects CUDA tensors on %s (got a tensor on %s)" % (self.device, t.device))
+            if t.dtype != torch.float32:
+                raise ValueError("push expects float32 probabilities (got %s)" % (t.dtype,))
+        items.sort(key=lambda e: e[0])
+        cap = self._capacity(capacity, min(len(items), _ffi.MAX_VARLEN_CLIPS))
+        self._enter()
+        if packed is not None and packed.stride(1) != 1 and self.classes > 1:
+            packed = None
+        parts, at = [], 0
+        for b0 in range(0, len(items), _ffi.MAX_VARLEN_CLIPS):
+            batch = items[b0:b0 + _ffi.MAX_VARLEN_CLIPS]
+            rows = [int(t.shape[0]) for _, t in batch]
+            total = sum(rows)
+            if packed is not None:
+                x = packed[at:at + total].detach()
+                at += total
+            else:
+                full = [t.detach() for _, t in batch if t.shape[0]]
+                x = None if not full else full[0] if len(full) == 1 else torch.cat(full)
+            ld = self.classes
+            if x is not None and total:
+                if (x.stride(1) != 1 and self.classes > 1) or (total > 1 and x.stride(0) < self.classes):
+                    x = x.contiguous()
+                ld = x.stride(0) if total > 1 else self.classes
+            c_slot = (ctypes.c_int * len(batch))(*[s for s, _ in batch])
+            c_rows = (ctypes.c_int * len(batch))(*rows)
+
+            def call(table, c, count, status, stream, x=x, ld=ld, c_slot=c_slot, c_rows=c_rows, n=len(batch)):
+                _ffi.check(_ffi.lib().acx_event_stream_push(self._h, None if x is None else x.data_ptr(), ld, c_slot, c_rows, n,
+                                                            table, c, count, status, stream))
+            parts.append(self._part([s for s, _ in batch], cap, call))
+            self._open.update(s for s, _ in batch)
+        return self._result(parts)
+
+    def close(self, slots=None, end_seconds=None, capacity=None):
+        """Ends the recordings of `slots` (default: every slot pushed to since its last close) and returns what is left of their events.
+        end_seconds: the recordings' last boundaries -- a number, a list beside slots, or {slot: seconds}; None or <= 0: rows
+        * step.  The slots are clean for their next recordings."""
+        torch = _torch()
+        self._enter()
+        if slots is None:
+            slots = sorted(self._open)
+        elif isinstance(slots, (int, np.integer)) and not isinstance(slots, bool):
+            slots = [slots]
+        slots = [self._slot(s) for s in slots]
+        if len(set(slots)) != len(slots):
+            raise ValueError("a slot is listed twice")
+        if isinstance(end_seconds, dict):
+            end_of = {self._slot(s): float(v) for s, v in end_seconds.items()}
+        elif end_seconds is None or np.ndim(end_seconds) == 0:
+            end_of = {s: 0.0 if end_seconds is None else float(end_seconds) for s in slots}
+        else:
+            if len(end_seconds) != len(slots):
+                raise ValueError("%d end_seconds for %d slots" % (len(end_seconds), len(slots)))
+            end_of = {s: float(v) for s, v in zip(slots, end_seconds)}
+        slots = sorted(slots)
+        cap = self._capacity(capacity, min(max(len(slots), 1), _ffi.MAX_VARLEN_CLIPS))
+        parts = []
+        for b0 in range(0, len(slots), _ffi.MAX_VARLEN_CLIPS):
+            batch = slots[b0:b0 + _ffi.MAX_VARLEN_CLIPS]
+            c_slot = (ctypes.c_int * len(batch))(*batch)
+            c_end = (ctypes.c_double * len(batch))(*[end_of.get(s, 0.0) for s in batch])
+            ends = {}
+            for s in batch:
+                n = self.steps(s)
+                e = end_of.get(s, 0.0)
+                ends[s] = (n, e if e > 0.0 else float(np.float64(n) * self.step))
+
+            def call(table, c, count, status, stream, c_slot=c_slot, c_end=c_end, n=len(batch)):
+                _ffi.check(_ffi.lib().acx_event_stream_close(self._h, c_slot, c_end, n, table, c, count, status, stream))
+            parts.append(self._part(batch, cap, call, ends))
+            self._open.difference_update(batch)
+        if not parts:
+            dev = self.device
+            meta = torch.zeros(4, dtype=torch.int32, device=dev)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+            parts = [dict(slots=[], issue=None, ends=None, table=torch.zeros((1, _ffi.EVENT_BYTES // 4), dtype=torch.int32, device=dev),
+                          meta=meta, count=meta[:2].view(torch.int64), status=meta[2:3], seen=torch.zeros(4, dtype=torch.int32),
+                          done=done)]
+        return self._result(parts)
+
+    def open_begin(self, slots=None):
+        """(n, N) int32 on the device: per slot (default: all) and class the step at which the event the class is inside of
+        began -- an open run that has reached `threshold` -- or -1.  Runs on the current stream without synchronising."""
+        torch = _torch()
+        slots = list(range(self.slots)) if slots is None else [self._slot(s) for s in slots]
+        self._enter()
+        out = torch.empty((len(slots), self.classes), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            for b0 in range(0, len(slots), _ffi.MAX_VARLEN_CLIPS):
+                batch = slots[b0:b0 + _ffi.MAX_VARLEN_CLIPS]
+                arr = (ctypes.c_int * len(batch))(*batch)
+                _ffi.check(_ffi.lib().acx_event_stream_open(self._h, arr, len(batch), out[b0:b0 + len(batch)].data_ptr(),
+                                                            _ffi.stream_ptr(self.device)))
+        return out
+
+    def steps(self, slot):
+        """Raw rows of the slot's open recording (host only)."""
+        n = ctypes.c_int64()
+        _ffi.check(_ffi.lib().acx_event_stream_steps(self._h, self._slot(slot), ctypes.byref(n)))
+        return n.value
+
+
+def join_event_tables(tables):
+    """One table of several calls of one EventStream, in the order given (each part stays ordered (slot, cls, begin))."""
+    tables = list(tables)
+    owner = tables[0]._owner
+    joined = _StreamEvents(owner, [p for t in tables for p in t._parts])
+    if owner._pending in tables:
+        owner._pending = joined
+    return joined

@@ -7,13 +7,19 @@ ConvNeXt.forward_windows of the whole recording -- window starts, per-window out
 for bit, for any chunking.  When things are emitted is the schedule of include/acx.h (schedule() below gives it for one slot):
 window j once its last sample is final; timeline row k once no window still to come can cover its midpoint, which trails the
 newest window by about one window length; the rest at close.  A recording shorter than the model's minimum emits nothing and is
-listed under "short" instead of raising, so one short stream does not cost the results of the others."""
+listed under "short" instead of raising, so one short stream does not cost the results of the others.
+
+With events= the handle also says what started and stopped when: the rows it emits -- one per window, or the timeline rows --
+go through an online event decoder (pytorch/segments.py EventStream, acx_event_stream_*) that carries its state across calls
+and hands out each event once, as soon as nothing still to come can change it; over a recording's calls the events are those
+of decode_events_gpu over forward_windows' rows of the whole recording, byte for byte."""
 import ctypes
 
 import torch
 
 from .. import _ffi
 from . import resample as _rs
+from . import segments as _seg
 from . import windows as _win
 
 
@@ -27,10 +33,13 @@ def schedule(window, hop, sample_rate, pushed, closed):
 class Stream:
     """One acx_stream handle on the model's device (see ConvNeXt.stream).  Clip-level outputs per window only: the segment-wise /
     frame-wise outputs of ConvNeXt.forward_segments are not part of live streams (run forward_windows(what="segment") on the
-    finished recording)."""
+    finished recording).  events=dict(threshold=..., low=..., median=..., min_duration=..., merge_gap=...) decodes events
+    live from the clip-level rows, one step per hop: event_source="windows" takes row j from window j's "clipwise_output"
+    (detection lags the audio by one window plus median // 2 hops plus merge_gap), "timeline" takes the handle's timeline
+    rows (and inherits their trail)."""
 
     def __init__(self, model, slots=256, window=10.0, hop=1.0, what="logits", sample_rate=None, timeline="mean", max_push=2.0,
-                 max_batch=64):
+                 max_batch=64, events=None, event_source="windows"):
         if what not in _ffi.MODES:
             raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
         if timeline not in ("mean", "max", None):
@@ -61,6 +70,20 @@ class Stream:
         self.classes = ctx.classes  # N of the model's head at create: the handle's rows are this wide
         self._pushed = {}           # slot -> input samples of its open recording
         self._last = None           # the torch stream of the previous call
+        self._ev = None             # the online event decoder over the rows this handle emits
+        if events is not None:
+            if what != "logits":
+                raise ValueError("events= needs what='logits' (got %r)" % (what,))
+            if event_source not in ("windows", "timeline"):
+                raise ValueError("event_source must be 'windows' or 'timeline' (got %r)" % (event_source,))
+            if event_source == "timeline" and not self.timeline:
+                raise ValueError("event_source='timeline' needs a timeline (got timeline=None)")
+            extra = set(events) - {"threshold", "low", "median", "min_duration", "merge_gap"}
+            if extra:
+                raise TypeError("events= takes decode_events' threshold, low, median, min_duration and merge_gap (got %s)"
+                                % sorted(extra))
+            self.event_source = event_source
+            self._ev = _seg.EventStream(slots, self.classes, step=self.hop / _rs.MODEL_RATE, device=self.device, **events)
 
     def close_handle(self):
         if self._h is not None and self._h.value:
@@ -102,7 +125,12 @@ class Stream:
                 for (s, _), n in zip(batch, lens):
                     self._pushed[s] = self._pushed.get(s, 0) + n
                 self._drain(out)
-        return out.result()
+        d = out.result()
+        if self._ev is not None:
+            touched = [s for s, _ in entries]
+            d["events"] = self._decode(d, touched)
+            d["events_open"] = self._ev.open_begin(touched)
+        return d
 
     def close(self, slots=None):
         """End the recordings of `slots` (default: every slot pushed to since its last close); emits what the ends make final.
@@ -115,6 +143,7 @@ class Stream:
                 raise ValueError("a slot is listed twice")
         out = _Result(self)
         self._enter()
+        seconds = {s: self._pushed.get(s, 0) / self.rate for s in slots}       # of the original audio
         for b0 in range(0, len(slots), _ffi.MAX_VARLEN_CLIPS):
             batch = slots[b0:b0 + _ffi.MAX_VARLEN_CLIPS]
             arr = (ctypes.c_int * len(batch))(*batch)
@@ -125,7 +154,15 @@ class Stream:
                 if L < _ffi.MIN_SAMPLES:
                     out.short.append(s)
             self._drain(out)
-        return out.result()
+        d = out.result()
+        if self._ev is not None:
+            # the rows the ends made final, then the recordings' ends: the timeline's last boundary is the end of the audio,
+            # the windows' the last hop's (a short recording closes an empty event recording)
+            last = self._decode(d, slots).check()
+            ends = seconds if self.event_source == "timeline" else None
+            d["events"] = _seg.join_event_tables([last, self._ev.close(slots, ends)])
+            d["events_open"] = self._ev.open_begin(slots)
+        return d
 
     # ------------------------------------------------------------------------------------------------------------- helpers
     def _slot(self, s):
@@ -153,6 +190,18 @@ class Stream:
                 raise RuntimeError("chunk for slot %d on %s but the model is on %s" % (s, t.device, self.device))
             out.append((s, t.detach()))
         return out
+
+    def _decode(self, d, touched):
+        """The event table of one call's rows: d's window rows or timeline rows, which lie in (slot, step) order; the slots
+        touched without a row push zero rows."""
+        rows, of = (d["clipwise_output"], d["slot"]) if self.event_source == "windows" else (d["timeline"], d["timeline_slot"])
+        count = {s: 0 for s in touched}
+        for s in of.tolist():
+            count[s] = count.get(s, 0) + 1
+        slots = sorted(count)
+        if not slots:
+            return self._ev.close([])
+        return self._ev.push(rows, slots=slots, steps=[count[s] for s in slots])
 
     def _enter(self):
         """All work of the handle runs in order: a new current stream first waits for the previous one (no synchronisation)."""

@@ -322,6 +322,62 @@ ACX_API int acx_decode_events_varlen_classwise(const float* probs, int64_t ld, c
                                                int64_t capacity, int64_t* count, int* status, void* ws, size_t ws_bytes,
                                                void* stream, const float* threshold, const float* low);
 
+/* ---- online event decoding: the same events from rows that arrive chunk by chunk ---------------------------------------------------
+ * The reference decodes nothing, and acx_decode_events needs the whole (steps, N) matrix of a finished recording.  A handle
+ * holds `slots` recordings at a time and carries each column's state machine across calls (csrc/events_common.h; the
+ * definition is pytorch/segments.py::OnlineEventDecoderHost): every event is handed out exactly once, as soon as nothing still
+ * to come can change it, and the rows of all calls of one recording, sorted by (cls, begin), are the rows of acx_decode_events
+ * over the concatenated matrix BYTE FOR BYTE, `mean` included, for any chunking.  Rules 1-6 of "sound event decoding" hold
+ * unchanged; edges[k] = (double)k * step_seconds for every k but the recording's last boundary, which is free and enters only
+ * in acx_event_stream_close.
+ *   filtered rows: filtered row t exists once raw row t + median / 2 has been pushed; the front repeats row 0, close supplies
+ *     the tail by repeating the last raw row.  A recording of fewer rows than median / 2, or of none, is legal; an empty one
+ *     emits nothing.
+ *   early emission: after filtered row t a pending event [eb, ee) is final -- and is emitted by this call if it passes the
+ *     minimum duration -- when a run is open that began at rb and !(edges[rb] - edges[ee] < merge_gap), or when no run is open
+ *     and !(edges[t + 1] - edges[ee] < merge_gap): k * step never decreases in k, so no later run could have merged.  A run
+ *     still open is part of no emitted event.
+ * acx_event_stream_create allocates the device state on the current device (acx_event_stream_bytes of it: per (slot, class)
+ * the state machine's fields and the last `median` raw rows), copies the per-class levels -- device fp32 [N] as in the
+ * _classwise calls, NULL: the field of *p -- and CHECKS them: !(0 <= low <= threshold) in any class is ACX_ERR_ARG (a NaN
+ * included; +inf is legal), so ACX_EVENTS_BAD_THRESHOLD never appears in a handle's status.  It synchronises the device.
+ * After create there is no allocation and no synchronisation: push / close / open launch on `stream` only (a 4-byte clear,
+ * a count pass, the scan of acx_decode_events and an emit pass; close one small kernel more) and are capturable.  Slots and
+ * row counts travel by value.  The calls of one handle must reach the device in order (one stream, or an event between two).
+ * acx_event_stream_push: probs holds rows[0] rows of slot[0], then rows[1] rows of slot[1], ... (row stride ld >= N; may be
+ *   NULL when every rows[i] is 0).  The table is ordered by (position in slot[], cls, begin) with clip = the slot and begin /
+ *   end in steps of the slot's recording, the same bits on every call.
+ * acx_event_stream_close: ends the recordings (last boundary end_seconds[i], <= 0 or end_seconds == NULL: steps * step_seconds),
+ *   emits what is left; the slots are clean for their next recordings.
+ * A VOID CALL CHANGES NOTHING: when the events of a call exceed `capacity`, ACX_EVENTS_OVERFLOW is set and *count = the total;
+ *   a NaN or +-inf in a pushed row sets ACX_EVENTS_NONFINITE and *count = 0.  In both cases the table is not to be used and
+ *   the device state of every slot of the call is exactly as before (only the emit pass stores state, and it reads the status
+ *   first): repeat the call with a larger table, or with other rows.  The host-side row counters cannot see the device's
+ *   status: a caller that finds a call void tells the handle with acx_event_stream_undo (host only: takes back what the
+ *   last push or close of each listed slot did to its counter) before the next call to those slots.  Should a recording pass
+ *   2^30 rows unseen by the host counters all the same, the device voids the call with ACX_EVENTS_NONFINITE.
+ * acx_event_stream_open: begin[i][c] = the step at which the event that class c of slot[i] is inside of began -- the pending
+ *   event's begin when the open run will merge with it, else the run's -- once the open run has reached threshold; else -1.
+ * acx_event_stream_steps (host only): the raw rows of the slot's open recording.
+ * Argument errors are returned before anything touches the device, with acx_decode_events' codes; in addition ACX_ERR_ARG:
+ * n outside 1 .. ACX_MAX_VARLEN_CLIPS, a slot out of range or listed twice, rows[i] < 0; ACX_ERR_SHAPE: slots outside
+ * 1 .. 2^20, a push that would take a recording past 2^30 rows; ACX_ERR_UNSUPPORTED: a state beyond 2^40 bytes. */
+typedef struct acx_event_stream acx_event_stream;
+ACX_API int acx_event_stream_bytes(int slots, int N, int median, size_t* bytes);                            /* host only */
+ACX_API int acx_event_stream_create(int slots, int N, const acx_event_params* p, double step_seconds,
+                                    const float* threshold /* device [N] or NULL */, const float* low /* device [N] or NULL */,
+                                    acx_event_stream** out);
+ACX_API void acx_event_stream_destroy(acx_event_stream* s);
+ACX_API int acx_event_stream_push(acx_event_stream* s, const float* probs, int64_t ld, const int* slot /* HOST, n, distinct */,
+                                  const int* rows /* HOST, n, >= 0 */, int n, acx_event* events, int64_t capacity, int64_t* count,
+                                  int* status, void* stream);
+ACX_API int acx_event_stream_close(acx_event_stream* s, const int* slot /* HOST, n */, const double* end_seconds /* HOST, n, or NULL */,
+                                   int n, acx_event* events, int64_t capacity, int64_t* count, int* status, void* stream);
+ACX_API int acx_event_stream_open(const acx_event_stream* s, const int* slot /* HOST, n */, int n, int32_t* begin /* device (n, N) */,
+                                  void* stream);
+ACX_API int acx_event_stream_steps(const acx_event_stream* s, int slot, int64_t* steps);                    /* host only */
+ACX_API int acx_event_stream_undo(acx_event_stream* s, const int* slot /* HOST, n */, int n);               /* host only */
+
 /* ---- sound event scoring: an event table against annotated events -> integer counts ------------------------------------------------
  * The reference has no scoring of detected events at all (its pytorch/inference.py:156-200 stops at the thresholded plot); users
  * of acx_decode_events pulled the table to the host and looped.  The definitions are the two host functions of this project,
