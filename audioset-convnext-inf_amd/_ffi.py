@@ -196,6 +196,15 @@ SIGNATURES = {
                                 _c_sz, _vp]),
     "acx_knn_vote": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, ctypes.c_float, _vp, _c_i64,
                               _vp, _vp]),
+    "acx_kmeans_workspace_bytes": (_c_int, [_c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_kmeans_assign": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "acx_kmeans_update": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz,
+                                   _vp]),
+    "acx_kmeans_fit": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _c_sz, _vp]),
+    "acx_kmeans_min_distance": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
+    "acx_kmeans_sample": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_kmeans_seed": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
     "acx_frontend_info": (_c_int, [_vp, _pint, ctypes.POINTER(ctypes.c_float), _pint]),
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
@@ -609,6 +618,64 @@ def knn_vote(indices, scores, nq, k, target, target_dtype, ld_target, n, classes
     """acx_knn_vote on raw device pointers (ctypes.c_void_p)."""
     check(lib().acx_knn_vote(indices, scores, int(nq), int(k), target, int(target_dtype), int(ld_target), int(n), int(classes),
                              int(weighting), float(temperature), out, int(ld_out), status, stream))
+
+
+KMEANS_EUCLIDEAN, KMEANS_COSINE = 0, 1         # enum acx_kmeans_metric
+KMEANS_METRICS = {"euclidean": KMEANS_EUCLIDEAN, "cosine": KMEANS_COSINE}
+KMEANS_MAX_CLUSTERS, KMEANS_MAX_ITER = 4096, 1000      # ACX_KMEANS_MAX_CLUSTERS, ACX_KMEANS_MAX_ITER
+KMEANS_NONFINITE, KMEANS_DEGENERATE, KMEANS_BAD_LABEL = 1, 2, 4    # bits of the status words of the acx_kmeans_* calls
+KMEANS_SAMPLE_WORKSPACE = 8192                 # bytes of workspace acx_kmeans_sample needs
+
+
+class AcxKmeansState(ctypes.Structure):
+    """struct acx_kmeans_state: the device-side state of acx_kmeans_fit (32 bytes)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("done", ctypes.c_int32), ("changed", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("shift", ctypes.c_double), ("inertia", ctypes.c_double)]
+
+
+KMEANS_STATE_BYTES = ctypes.sizeof(AcxKmeansState)     # 32
+
+
+def kmeans_workspace_bytes(n, dim, clusters):
+    """Workspace of acx_kmeans_fit / acx_kmeans_update / acx_kmeans_seed (host only)."""
+    return _query(lib().acx_kmeans_workspace_bytes, _c_sz, int(n), int(dim), int(clusters))
+
+
+def kmeans_assign(x, ld_x, x_inv_norm, n, centers, ld_c, clusters, dim, metric, prev_labels, labels, scores, changed, status,
+                  stream):
+    """acx_kmeans_assign on raw device pointers (ctypes.c_void_p); prev_labels may be None."""
+    check(lib().acx_kmeans_assign(x, int(ld_x), x_inv_norm, int(n), centers, int(ld_c), int(clusters), int(dim), int(metric),
+                                  prev_labels, labels, scores, changed, status, stream))
+
+
+def kmeans_update(x, ld_x, x_inv_norm, n, dim, metric, labels, clusters, centers, ld_c, counts, shift, status, ws, stream):
+    """acx_kmeans_update on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_kmeans_update(x, int(ld_x), x_inv_norm, int(n), int(dim), int(metric), labels, int(clusters), centers,
+                                  int(ld_c), counts, shift, status, ws[0], int(ws[1]), stream))
+
+
+def kmeans_fit(x, ld_x, x_inv_norm, n, dim, metric, centers, ld_c, clusters, max_iter, tol_abs, labels, counts, state, status, ws,
+               stream):
+    """acx_kmeans_fit on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_kmeans_fit(x, int(ld_x), x_inv_norm, int(n), int(dim), int(metric), centers, int(ld_c), int(clusters),
+                               int(max_iter), tol_abs, labels, counts, state, status, ws[0], int(ws[1]), stream))
+
+
+def kmeans_min_distance(x, ld_x, x_inv_norm, n, dim, metric, center, first, d, d_max, status, stream):
+    """acx_kmeans_min_distance on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_kmeans_min_distance(x, int(ld_x), x_inv_norm, int(n), int(dim), int(metric), center, 1 if first else 0, d,
+                                        d_max, status, stream))
+
+
+def kmeans_sample(d, n, d_max, u, picked, status, ws, stream):
+    """acx_kmeans_sample on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_kmeans_sample(d, int(n), d_max, u, picked, status, ws[0], int(ws[1]), stream))
+
+
+def kmeans_seed(x, ld_x, x_inv_norm, n, dim, metric, clusters, u, picked, centers, ld_c, status, ws, stream):
+    """acx_kmeans_seed on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_kmeans_seed(x, int(ld_x), x_inv_norm, int(n), int(dim), int(metric), int(clusters), u, picked, centers,
+                                int(ld_c), status, ws[0], int(ws[1]), stream))
 
 
 MAX_EVENT_MEDIAN = 101                        # ACX_MAX_EVENT_MEDIAN

@@ -842,6 +842,19 @@ class ConvNeXt(nn.Module):
             emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
         return EmbeddingIndex(emb, metric=metric, target=target, device=dev)
 
+    def cluster(self, data, clusters, sample_rate=None, **kw):
+        """K-means (pytorch/clustering.py: kmeans) over scene embeddings on the model's device: `data` is an (n, 768) tensor of
+        embeddings, or a list of waveforms at `sample_rate`, extracted as build_index does; kw: metric, init, n_init, max_iter,
+        tol, seed.  -> clustering.KMeans."""
+        from .clustering import kmeans
+        from .extract_embeddings import extract
+        dev = self.head_audioset.weight.device
+        if getattr(data, "ndim", None) == 2:
+            emb = data
+        else:
+            emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
+        return kmeans(emb, clusters, device=dev, **kw)
+
     def search(self, index, waveform, k=10, sample_rate=None):
         """Query by example: {"scores" (B, k) fp32, "indices" (B, k) int64, "scene" (B, 768)} of a (B, L) waveform batch --
         forward_scene_embeddings, then index.search, on one stream with no host synchronisation (capturable as a whole).

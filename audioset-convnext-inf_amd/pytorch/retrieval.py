@@ -8,6 +8,7 @@ the kNN probe of a frozen representation, next to the linear probe of `finetune.
     scores, indices = idx.search(None, k=10)                   # self-search: every row against the others
     probs = idx.classify(queries, k=10, weights="uniform")     # (q, C) fp32: kNN tagging, needs target=
     idx.check()                                                # synchronises; ValueError if a search met a NaN or inf
+    km = idx.cluster(50)                                       # k-means over the stored rows (pytorch/clustering.py)
 
 Order: score descending, then database index ascending, -0.0 as +0.0 -- one total order, so the result does not depend on how
 the kernel got there.  A (query, row) pair has the same score bits whatever the batch, the index size, k or the chunking.
@@ -326,6 +327,18 @@ class EmbeddingIndex:
             raise ValueError("weights must be one of %s, got %r" % (WEIGHTS, weights))
         scores, indices = self.search(queries, k)
         return vote(indices, scores, self.target, weights, temperature, status=self._status)
+
+    def cluster(self, clusters, **kw):
+        """K-means over the stored rows (pytorch/clustering.py: kmeans) with the index's own metric -- "cosine": cosine,
+        "dot": euclidean -- reusing the index's inverse norms; kw: init, n_init, max_iter, tol, seed.  -> clustering.KMeans."""
+        from . import clustering
+        if self._n == 0:
+            raise ValueError("the index is empty")
+        metric = "cosine" if self.metric == "cosine" else "euclidean"
+        clustering._check_fit_args((self._n, self.dim), clusters, metric, kw.get("init", "k-means++"), kw.get("n_init", 1),
+                                   kw.get("max_iter", 100), kw.get("tol", 1e-4))
+        return clustering._fit_rows(self._buf[:self._n], self.dim, self.inverse_norms if metric == "cosine" else None, clusters,
+                                    metric, **kw)
 
     def check(self):
         """Synchronise and raise ValueError if a search or classify since the last check met bad data."""

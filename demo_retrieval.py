@@ -5,6 +5,7 @@ ConvNeXt.search).
 
     python demo_retrieval.py --ckpt checkpoints/model.safetensors --data sounds/ --query dog.wav      # sounds/<class>/*.wav
     python demo_retrieval.py --synthetic                       # seeded weights and clips, no files needed
+    python demo_retrieval.py --synthetic --clusters 8          # also k-means over the corpus: sizes, the clip nearest each centre
 
 16-bit PCM WAV files at any rate (resampled on the device)."""
 import argparse
@@ -62,6 +63,7 @@ def main():
     ap.add_argument("-k", type=int, default=5)
     ap.add_argument("--metric", default="cosine", choices=("cosine", "dot"))
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--clusters", type=int, default=0, help="also cluster the corpus into this many clusters (k-means on the GPU)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("this build runs on an MI355X; no GPU is visible")
@@ -116,6 +118,17 @@ def main():
             print("%s (%s): %s" % (paths[r], names[int(label[r])],
                                    ", ".join("%s %.3f (%s)" % (paths[j], s, names[int(label[j])])
                                              for s, j in zip(scores[r].tolist(), indices[r].tolist()))))
+
+    if a.clusters:
+        # no labels needed: k-means over the stored rows with the index's metric, and the stored clip nearest to each centre
+        km = index.cluster(a.clusters, seed=a.seed)
+        _, nearest = index.search(km.centers, 1)
+        km.check()
+        index.check()
+        print("k-means, %d clusters, %d iterations, inertia %.4g; sizes %s" % (a.clusters, int(km.n_iter), float(km.inertia),
+                                                                           km.counts.tolist()))
+        for c, j in enumerate(nearest[:, 0].tolist()):
+            print("    cluster %d (%d clips): nearest %s (%s)" % (c, int(km.counts[c]), paths[j], names[int(label[j])]))
 
     # the kNN probe: each clip labelled by its neighbours (itself left out), scored like any tagger
     from audioset_convnext_inf_amd.pytorch.retrieval import vote

@@ -895,6 +895,74 @@ ACX_API int acx_knn_vote(const int32_t* indices, const float* scores, int64_t nq
                          int64_t ld_target, int64_t n, int classes, int weighting, float temperature, float* out,
                          int64_t ld_out, int32_t* status, void* stream);
 
+/* ---- k-means over embeddings: Lloyd iterations with k-means++ seeding, all decisions on the device --------------------------------
+ * Clustering for embeddings without labels (no reference counterpart).  Stateless; every buffer is the caller's, on the device.
+ *   x (n, dim) and centers (clusters, dim) fp32 with row strides ld_x / ld_c, the layout rules of acx_knn_search: 16-byte
+ *   aligned, strides multiples of 4, dim a multiple of 4 in 4 .. ACX_KNN_MAX_DIM (pad with zero columns);
+ *   1 <= clusters <= ACX_KMEANS_MAX_CLUSTERS, n <= 2^30, and clusters <= n for acx_kmeans_fit / acx_kmeans_seed.
+ * SCORE of (row i, centre k): fma(-2, dot(x_i, c_k), cc_k) in fp32 -- the squared distance less the row's own sum x_i^2, which
+ * cannot change the arg-min -- with the dot product on the f32 matrix instructions in ONE fixed order per pair (that of
+ * acx_knn_search) and cc_k = sum c_k^2 in one fixed order.  ACX_KMEANS_COSINE: -dot(x_i, c_k) with the RAW row (its positive
+ * inverse norm cannot change the arg-min either); the centres are unit rows.  A pair's score has the SAME BITS whatever n,
+ * clusters or the position of the row or the centre.  ONE TOTAL ORDER: the label of a row is the first centre by score
+ * ascending, then centre index ascending, -0.0 counting as +0.0.  The (n, clusters) scores are never written.
+ *   acx_kmeans_assign: clears *status and *changed; labels[i] int32, scores[i] = the winner's score, *changed = rows whose label
+ *     differs from prev_labels[i] (prev_labels NULL: n; it may alias labels).  A row with a non-finite winner score (a NaN or
+ *     +-inf in x or centers, or an overflow) gets label -1 and sets ACX_KMEANS_NONFINITE.
+ *   acx_kmeans_update: one mean step from given labels.  The row indices are partitioned STABLY by label, each (cluster, column)
+ *     is summed in float64 in an order that depends on (n, dim, labels) alone, and c_k = (float)(sum / count).  COSINE: the rows
+ *     are weighted by x_inv_norm (acx_knn_row_norms) and c_k = (float)(sum / |sum|), the norm in float64.  AN EMPTY CLUSTER KEEPS
+ *     ITS CENTRE and reports count 0 (scikit-learn moves it to a far row instead).  counts (clusters) int32; *shift =
+ *     sum_k |c_new - c_old|^2 in float64.  Labels outside [0, clusters) are left out and set ACX_KMEANS_BAD_LABEL.  No float
+ *     atomics: the same inputs give the same bits on every call.
+ *   acx_kmeans_fit: centers holds the initial centres and receives the final ones.  max_iter iterations (assign, update,
+ *     decide) are QUEUED; after each the device sets state->done when no label changed or shift <= *tol_abs (a float64 on the
+ *     device), and every kernel of a later iteration returns at once.  One closing assignment runs only if the last update moved a
+ *     centre, so labels, counts and state->inertia always belong to the returned centres.  inertia = sum_i max(sum x_i^2 +
+ *     score_i, 0) in float64 in a fixed order (COSINE: sum_i 1 + score_i x_inv_norm[i]).  state->iterations counts the
+ *     iterations that ran, state->changed / shift are those of the last one.  ACX_KMEANS_NONFINITE stops the fit and leaves every
+ *     label -1.
+ *   k-means++ (D^2 sampling):
+ *   acx_kmeans_min_distance: d[i] <- min(d[i], dist(x_i, center)) (first != 0: d[i] <- dist), dist = sum (x - c)^2 in fp32 by one
+ *     wave per row in a fixed order, COSINE: max(0, 2 - 2 cos) with cos = (dot * x_inv_norm[i]) / |center|; *d_max = max_i d[i].
+ *   acx_kmeans_sample: integer weights q_i = floor(d_i 2^(30 - e)), e = floor(log2 *d_max), summed exactly in uint64;
+ *     *picked = the smallest i whose inclusive prefix sum exceeds t = min(floor(*u total), total - 1), the product one rounded
+ *     float64 multiply.  Integer arithmetic after the quantisation: the pick does not depend on any order of summation.
+ *     total == 0: *picked = -1 and ACX_KMEANS_DEGENERATE.  ws: at least 8192 bytes.
+ *   acx_kmeans_seed: picked[0] = floor(u[0] n); round r = 1 .. clusters - 1 runs min_distance against row picked[r - 1] and
+ *     sample with u[r]; a round with total == 0 (fewer distinct rows than clusters) takes the lowest row index not yet picked and
+ *     sets ACX_KMEANS_DEGENERATE.  centers[k] = row picked[k] (COSINE: times its inverse norm).  u: clusters doubles in [0, 1).
+ *   acx_kmeans_workspace_bytes: the workspace of fit, update and seed; non-decreasing in each argument (host only).
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable.  ARGUMENT errors
+ * return a negative status before any launch, as for acx_knn_search. */
+enum acx_kmeans_metric { ACX_KMEANS_EUCLIDEAN = 0, ACX_KMEANS_COSINE = 1 };
+#define ACX_KMEANS_MAX_CLUSTERS 4096
+#define ACX_KMEANS_MAX_ITER 1000
+#define ACX_KMEANS_NONFINITE 1
+#define ACX_KMEANS_DEGENERATE 2
+#define ACX_KMEANS_BAD_LABEL 4
+typedef struct acx_kmeans_state {
+    int32_t iterations, done, changed, reserved;
+    double shift, inertia;
+} acx_kmeans_state;
+ACX_API int acx_kmeans_workspace_bytes(int64_t n, int dim, int clusters, size_t* out_bytes);
+ACX_API int acx_kmeans_assign(const float* x, int64_t ld_x, const float* x_inv_norm, int64_t n, const float* centers, int64_t ld_c,
+                              int clusters, int dim, int metric, const int32_t* prev_labels, int32_t* labels, float* scores,
+                              int32_t* changed, int32_t* status, void* stream);
+ACX_API int acx_kmeans_update(const float* x, int64_t ld_x, const float* x_inv_norm, int64_t n, int dim, int metric,
+                              const int32_t* labels, int clusters, float* centers, int64_t ld_c, int32_t* counts, double* shift,
+                              int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_kmeans_fit(const float* x, int64_t ld_x, const float* x_inv_norm, int64_t n, int dim, int metric, float* centers,
+                           int64_t ld_c, int clusters, int max_iter, const double* tol_abs, int32_t* labels, int32_t* counts,
+                           acx_kmeans_state* state, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_kmeans_min_distance(const float* x, int64_t ld_x, const float* x_inv_norm, int64_t n, int dim, int metric,
+                                    const float* center, int first, float* d, float* d_max, int32_t* status, void* stream);
+ACX_API int acx_kmeans_sample(const float* d, int64_t n, const float* d_max, const double* u, int32_t* picked, int32_t* status,
+                              void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_kmeans_seed(const float* x, int64_t ld_x, const float* x_inv_norm, int64_t n, int dim, int metric, int clusters,
+                            const double* u, int32_t* picked, float* centers, int64_t ld_c, int32_t* status, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* Which evaluation of the STFT the frontend uses (round 6).  ACX_FRONTEND_AUTO (default): the FFT kernel when the stored buffers are
  * window x DFT, the dense contraction otherwise (acx_finalize above).  ACX_FRONTEND_DENSE: ALWAYS the dense contraction with the
  * stored `conv_real` / `conv_imag` weights -- the reference's own formulation (two Conv1d, convnext.py:179-187,298) -- 2.1 GFLOP
