@@ -37,6 +37,11 @@ class AcxAdam(ctypes.Structure):
 _padam, _c_dbl = ctypes.POINTER(AcxAdam), ctypes.c_double
 
 
+class AcxFitJob(ctypes.Structure):
+    """struct acx_fit_job: the device pointers of one job of acx_head_fit_group_step (80 bytes)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("idx", "W", "b", "mW", "vW", "vmaxW", "mb", "vb", "vmaxb", "loss")]
+
+
 class AcxEvent(ctypes.Structure):
     """struct acx_event: one row of the event table of acx_decode_events (32 bytes)."""
     _fields_ = [("clip", ctypes.c_int32), ("cls", ctypes.c_int32), ("begin", ctypes.c_int32), ("end", ctypes.c_int32),
@@ -179,6 +184,13 @@ SIGNATURES = {
                                       _padam, _c_i64, _c_dbl, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_head_fit_grad_ce": (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_int, _c_dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _c_sz, _vp]),
+    "acx_head_fit_group_workspace_bytes": (_c_int, [_c_int, _c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_head_fit_plan_bytes": (_c_int, [_c_int, _c_i64, ctypes.POINTER(_c_sz)]),
+    "acx_head_fit_plan_fill": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _padam, _vp, _vp, _c_sz]),
+    "acx_head_fit_group_step": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _c_int, _c_i64, _c_int, _vp, _vp, _c_i64, _c_i64,
+                                         _vp, _vp, _c_sz, _vp]),
+    "acx_head_fit_group_step_ce": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _c_int, _c_dbl, _vp, _vp, _c_i64, _c_i64, _vp,
+                                            _vp, _c_sz, _vp]),
     "acx_softmax_topk": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp]),
     "acx_classification_counts": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "acx_reliability_counts": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -508,6 +520,31 @@ FIT_BAD_LABEL = 2                              # acx_head_fit_step_ce / acx_head
 def head_fit_ce_workspace_bytes(rows_max, classes):
     """Workspace of acx_head_fit_step_ce / acx_head_fit_grad_ce for steps of up to rows_max rows (host only)."""
     return _query(lib().acx_head_fit_ce_workspace_bytes, _c_sz, int(rows_max), int(classes))
+
+
+FIT_MAX_JOBS = 256                             # ACX_FIT_MAX_JOBS: jobs of one acx_head_fit_group_step
+FIT_LOSS_BCE, FIT_LOSS_CE = 0, 1               # enum acx_fit_loss
+
+
+def head_fit_group_workspace_bytes(jobs, rows_max, classes, loss):
+    """Workspace of acx_head_fit_group_step / _step_ce for `jobs` jobs of up to rows_max rows a step (host only)."""
+    return _query(lib().acx_head_fit_group_workspace_bytes, _c_sz, int(jobs), int(rows_max), int(classes), int(loss))
+
+
+def head_fit_plan(rows, idx_offset, lr, hps, rows_max, classes, loss):
+    """The plan of a group fit (acx_head_fit_plan_fill, host only): rows / idx_offset / lr are (steps, jobs) arrays, hps one
+    AcxAdam per job.  -> a uint8 numpy array to upload once."""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    steps, jobs = rows.shape
+    idx_offset = np.ascontiguousarray(idx_offset, dtype=np.int64)
+    lr = np.ascontiguousarray(lr, dtype=np.float64)
+    if idx_offset.shape != rows.shape or lr.shape != rows.shape or len(hps) != jobs:
+        raise ValueError("rows, idx_offset and lr must share one (steps, jobs) shape, with one hp per job")
+    plan = np.zeros(_query(lib().acx_head_fit_plan_bytes, _c_sz, jobs, steps), dtype=np.uint8)
+    check(lib().acx_head_fit_plan_fill(jobs, steps, int(rows_max), int(classes), int(loss), rows.ctypes.data, idx_offset.ctypes.data,
+                                       (AcxAdam * jobs)(*hps), lr.ctypes.data, plan.ctypes.data, plan.nbytes))
+    return plan
 
 
 CLASSIFY_MAX_K = 64                            # ACX_CLASSIFY_MAX_K

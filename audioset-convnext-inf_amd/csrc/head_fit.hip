@@ -31,6 +31,11 @@
 //                      and label alone, and so do the row's z bits: the logits launch picks its tile shape from N, not rows.
 //   fit_update_kernel  exactly as for BCE: it consumes G, adds part[0 .. rows) in index order and scales by 1 / rows.
 //
+// Groups (acx_head_fit_group_step / _step_ce): up to ACX_FIT_MAX_JOBS independent fits over the same E advance per launch.  The
+// bodies above are device functions that take the tile (or row) number as an argument; the single-call kernels pass blockIdx.x,
+// the group kernels resolve (tile, job) = (blockIdx.x, blockIdx.y) first and build the same parameter struct from the job table
+// and the step's plan row, so a job's bits are its single call's (see "groups" below).
+//
 // Arithmetic: fp32 products, fp32 accumulation on the f32-input matrix cores (v_mfma_f32_32x32x2_f32 when the launch has
 // at least one 32 x 32 tile per CU, v_mfma_f32_16x16x4_f32 otherwise, so that a 50-class head with 64 rows still spreads over
 // 16 + 192 workgroups) -- bit-equal to an fmaf chain.  The four waves of a workgroup split the contraction (K = 768 or the rows)
@@ -47,6 +52,7 @@
 // eps sits outside the root, after the bias correction.  What depends only on the hyper-parameters and t is evaluated on the
 // host in double and rounded to fp32 once (adam_scalars); the decay and the step are applied to p in ONE fused multiply-add.
 #include <cmath>
+#include <vector>
 
 #include "acx_internal.h"
 #include "device_common.h"
@@ -57,6 +63,13 @@ constexpr int kFitK = 768;                        // inputs of the head (convnex
 constexpr int kFitThreads = 256;                  // four waves: the contraction is split four ways
 constexpr int kFitDbCols = 64;                    // classes per db block
 constexpr long long kFitMaxRows = 1LL << 22;
+
+// The tile form of a matrix launch: 32 x 32 where that still leaves every CU a tile, 16 x 16 otherwise.  The BCE gradient pass
+// asks fit_rows_wide, the cross-entropy logits and every update pass fit_classes_wide (fit_ce_launch says why).  The two forms add
+// the products in different orders, so these are part of the bit contract: the single calls evaluate them on the host, the group
+// kernels per job on the device.
+__host__ __device__ inline bool fit_rows_wide(int rows, int N, int cus) { return (long long)((rows + 31) / 32) * ((N + 31) / 32) >= cus; }
+__host__ __device__ inline bool fit_classes_wide(int N, int cus) { return ((N + 31) / 32) * (kFitK / 32) >= cus; }
 
 struct AdamK {          // fp32 roundings of the host's double evaluations
     float beta1, omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt;
@@ -113,9 +126,10 @@ struct FitGradP {
 enum { kLossBce = 0, kLossCe = 1 };
 
 // The tile body of the gradient pass.  LOSS = kLossBce: the whole of fit_grad_kernel.  LOSS = kLossCe: the logits alone go
-// to p.z (the softmax needs whole rows: fit_ce_row_kernel); Y, G, part and inv are not read.
+// to p.z (the softmax needs whole rows: fit_ce_row_kernel); Y, G, part and inv are not read.  bid: the tile's number in p's own
+// tiling (blockIdx.x in a single call; a group's block resolves its job first).
 template <int S, int LOSS>
-__device__ __forceinline__ void fit_grad_tile(FitGradP p) {
+__device__ __forceinline__ void fit_grad_tile(const FitGradP& p, unsigned bid) {
     using T = FitTile<S>;
     constexpr int KB = (64 / S) * 4;               // k per block of four MFMAs: lane group h holds k = 4 h .. 4 h + 3
     constexpr int KW = kFitK / 4;                  // k per wave
@@ -125,7 +139,7 @@ __device__ __forceinline__ void fit_grad_tile(FitGradP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane % S, h = lane / S;
-    const int tile_c = blockIdx.x % p.tiles_n, tile_r = blockIdx.x / p.tiles_n;
+    const int tile_c = bid % p.tiles_n, tile_r = bid / p.tiles_n;
     const int row0 = tile_r * S, c0 = tile_c * S;
 
     // rows past the batch and classes past N repeat the last valid one: loads stay inside the buffers, results are dropped
@@ -186,13 +200,13 @@ __device__ __forceinline__ void fit_grad_tile(FitGradP p) {
     lsum = wave_sum(lsum);
     if (lane == 0) s_loss[wave] = lsum;
     __syncthreads();
-    if (tid == 0) p.part[blockIdx.x] = sum4(s_loss[0], s_loss[1], s_loss[2], s_loss[3]);
+    if (tid == 0) p.part[bid] = sum4(s_loss[0], s_loss[1], s_loss[2], s_loss[3]);
 }
 
 template <int S>
-__global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) { fit_grad_tile<S, kLossBce>(p); }
+__global__ __launch_bounds__(kFitThreads) void fit_grad_kernel(FitGradP p) { fit_grad_tile<S, kLossBce>(p, blockIdx.x); }
 template <int S>
-__global__ __launch_bounds__(kFitThreads) void fit_logits_kernel(FitGradP p) { fit_grad_tile<S, kLossCe>(p); }
+__global__ __launch_bounds__(kFitThreads) void fit_logits_kernel(FitGradP p) { fit_grad_tile<S, kLossCe>(p, blockIdx.x); }
 
 // The row pass of the cross-entropy step: G and the row's loss from the logits z (rows, N), one group of W threads per row
 // (device_common.h, "softmax of one row").  label = labels[idx[r]], both clamped into their ranges.
@@ -204,10 +218,10 @@ struct FitCeRowP {
 };
 
 template <int W>
-__global__ __launch_bounds__(kFitThreads) void fit_ce_row_kernel(FitCeRowP p) {
+__device__ __forceinline__ void fit_ce_row_body(const FitCeRowP& p, int bid) {
     __shared__ float red[4];
     const int t = soft_thread<W>();
-    const int row = W == 64 ? (int)(blockIdx.x * 4 + (threadIdx.x >> 6)) : (int)blockIdx.x;
+    const int row = W == 64 ? (int)(bid * 4 + (threadIdx.x >> 6)) : bid;
     if (row >= p.rows) return;                                     // W = 64 only: a whole wave, and no barrier follows
     long long src = p.idx[row];
     src = src < 0 ? 0 : src >= p.n_total ? p.n_total - 1 : src;    // flagged by the logits kernel
@@ -232,6 +246,9 @@ __global__ __launch_bounds__(kFitThreads) void fit_ce_row_kernel(FitCeRowP p) {
     if (t == 0) p.part[row] = logf(s) + (p.q_miss * d + p.ome * (m - z[y]));
 }
 
+template <int W>
+__global__ __launch_bounds__(kFitThreads) void fit_ce_row_kernel(FitCeRowP p) { fit_ce_row_body<W>(p, blockIdx.x); }
+
 struct FitUpdP {
     const float* E; long long ld_e; long long n_total;
     const long long* idx; int rows; int N;
@@ -245,14 +262,13 @@ struct FitUpdP {
 };
 
 template <int S, bool APPLY>
-__global__ __launch_bounds__(kFitThreads) void fit_update_kernel(FitUpdP p) {
+__device__ __forceinline__ void fit_update_body(const FitUpdP& p, int bid) {
     using T = FitTile<S>;
     constexpr int KB = (64 / S) * 4;               // batch rows per block of four MFMAs
     constexpr int TK = kFitK / S;
     __shared__ float red[4][S * S];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bid = blockIdx.x;
 
     if (bid < p.tiles) {
         const int r = lane % S, h = lane / S;
@@ -335,6 +351,9 @@ __global__ __launch_bounds__(kFitThreads) void fit_update_kernel(FitUpdP p) {
     if (tid == 0) *p.loss = sum4(red[0][0], red[0][1], red[0][2], red[0][3]) * p.inv;
 }
 
+template <int S, bool APPLY>
+__global__ __launch_bounds__(kFitThreads) void fit_update_kernel(FitUpdP p) { fit_update_body<S, APPLY>(p, blockIdx.x); }
+
 __global__ __launch_bounds__(256) void adam_update_kernel(float* __restrict__ param, const float* __restrict__ grad,
                                                           float* __restrict__ m, float* __restrict__ v, float* vmax,
                                                           long long n, AdamK a) {
@@ -343,6 +362,99 @@ __global__ __launch_bounds__(256) void adam_update_kernel(float* __restrict__ pa
     float w = param[i], mm = m[i], vv = v[i];
     adam_elem(w, grad[i], mm, vv, a.amsgrad ? vmax + i : nullptr, a);
     param[i] = w; m[i] = mm; v[i] = vv;
+}
+
+// ---- groups: J independent fits over the same embeddings, one launch per stage for all of them (acx_head_fit_group_step) -----
+// A block is (tile, job) = (blockIdx.x, blockIdx.y): it reads the job's pointers (acx_fit_job) and its entry of the step's plan row
+// (rows, idx offset, loss slot, 1 / count and the AdamK scalars, all evaluated on the host by acx_head_fit_plan_fill with the
+// single call's own code), builds the single call's parameter struct and runs the single call's body.  The grid is sized for
+// rows_max; blocks past the job's own tiling, blocks of a job that sits the step out (rows = 0) and -- BCE gradient pass, where the
+// form depends on the job's rows -- blocks of the other tile form return before the first barrier.  Nothing of an idle job is
+// written.  Each job owns a slice of the workspace laid out as the single call's.
+struct FitPlanE {       // one (step, job) entry of the plan
+    long long idx_off;  // the batch is idx[idx_off .. idx_off + rows) of the job's index array
+    int rows;           // 0: the job sits this step out
+    int loss_slot;      // the job's step count before this step (t - 1): loss[loss_slot] receives the step's loss
+    float inv;          // 1 / (rows classes) (BCE) or 1 / rows (cross-entropy), from double
+    int pad;
+    AdamK a;
+};
+static_assert(sizeof(FitPlanE) == 64, "plan entries are 64 bytes: acx_head_fit_plan_bytes");
+
+struct FitGroupP {
+    const float* E; long long ld_e; long long n_total;
+    const void* Y; int y_u8; long long ld_y;           // the targets (BCE) or the int64 labels (cross-entropy)
+    const acx_fit_job* jobs; const FitPlanE* plan;     // plan: the step's row of J entries
+    int N, rows_max, cus, loss;
+    char* ws; size_t ws_job, z_off, part_off;          // job j's slice starts at ws + j ws_job: G, then z (CE), then the partials
+    int* status;                                       // [J]
+    float q_hit, q_miss, ome;                          // cross-entropy: FitCeRowP's
+};
+
+template <int S, int LOSS>
+__global__ __launch_bounds__(kFitThreads) void fit_group_grad_kernel(FitGroupP q) {
+    const int j = blockIdx.y;
+    const FitPlanE e = q.plan[j];
+    const int rows = min(e.rows, q.rows_max);
+    if (rows <= 0) return;
+    if (LOSS == kLossBce && fit_rows_wide(rows, q.N, q.cus) != (S == 32)) return;
+    const int tiles_n = (q.N + S - 1) / S;
+    if ((int)blockIdx.x >= ((rows + S - 1) / S) * tiles_n) return;
+    const acx_fit_job jb = q.jobs[j];
+    char* w = q.ws + j * q.ws_job;
+    FitGradP p;
+    p.E = q.E; p.ld_e = q.ld_e; p.n_total = q.n_total;
+    p.Y = q.Y; p.y_u8 = q.y_u8; p.ld_y = q.ld_y;
+    p.idx = reinterpret_cast<const long long*>(jb.idx) + e.idx_off; p.rows = rows; p.N = q.N;
+    p.W = jb.W; p.b = jb.b;
+    p.z = LOSS == kLossCe ? reinterpret_cast<float*>(w + q.z_off) : nullptr;
+    p.G = reinterpret_cast<float*>(w);
+    p.part = reinterpret_cast<float*>(w + q.part_off);
+    p.status = q.status + j; p.inv = e.inv; p.tiles_n = tiles_n;
+    fit_grad_tile<S, LOSS>(p, blockIdx.x);
+}
+
+template <int W>
+__global__ __launch_bounds__(kFitThreads) void fit_group_ce_row_kernel(FitGroupP q) {
+    const int j = blockIdx.y;
+    const FitPlanE e = q.plan[j];
+    const int rows = min(e.rows, q.rows_max);
+    if ((int)blockIdx.x * (W == 64 ? 4 : 1) >= rows) return;
+    const acx_fit_job jb = q.jobs[j];
+    char* w = q.ws + j * q.ws_job;
+    FitCeRowP p;
+    p.z = reinterpret_cast<const float*>(w + q.z_off); p.labels = static_cast<const long long*>(q.Y);
+    p.idx = reinterpret_cast<const long long*>(jb.idx) + e.idx_off; p.n_total = q.n_total; p.rows = rows; p.N = q.N;
+    p.q_hit = q.q_hit; p.q_miss = q.q_miss; p.ome = q.ome; p.inv = e.inv;
+    p.G = reinterpret_cast<float*>(w); p.part = reinterpret_cast<float*>(w + q.part_off); p.status = q.status + j;
+    fit_ce_row_body<W>(p, blockIdx.x);
+}
+
+template <int S>
+__global__ __launch_bounds__(kFitThreads) void fit_group_update_kernel(FitGroupP q) {
+    const int j = blockIdx.y;
+    const FitPlanE e = q.plan[j];
+    const int rows = min(e.rows, q.rows_max);
+    if (rows <= 0) return;
+    const acx_fit_job jb = q.jobs[j];
+    char* w = q.ws + j * q.ws_job;
+    FitUpdP p;
+    p.E = q.E; p.ld_e = q.ld_e; p.n_total = q.n_total;
+    p.idx = reinterpret_cast<const long long*>(jb.idx) + e.idx_off; p.rows = rows; p.N = q.N;
+    p.G = reinterpret_cast<const float*>(w);
+    p.W = jb.W; p.mW = jb.mW; p.vW = jb.vW; p.vmaxW = jb.vmaxW;
+    p.b = jb.b; p.mb = jb.mb; p.vb = jb.vb; p.vmaxb = jb.vmaxb;
+    p.dW = nullptr; p.db = nullptr;
+    p.part = reinterpret_cast<const float*>(w + q.part_off);
+    if (q.loss == kLossCe) {
+        p.nparts = rows;                               // one partial per row
+    } else {                                           // one per tile of the form the job's gradient pass took
+        const int gs = fit_rows_wide(rows, q.N, q.cus) ? 32 : 16;
+        p.nparts = ((rows + gs - 1) / gs) * ((q.N + gs - 1) / gs);
+    }
+    p.loss = jb.loss + e.loss_slot; p.inv = e.inv; p.a = e.a;
+    p.tiles = ((q.N + S - 1) / S) * (kFitK / S);
+    fit_update_body<S, true>(p, blockIdx.x);
 }
 
 // workspace: G (rows_max, classes) fp32, then the loss partials of the finest tiling (16 x 16)
@@ -475,7 +587,7 @@ static int fit_launch_update(FitUpdP u, const FitCall& c, const float* G, const 
     const int N = c.classes;
     u.E = c.E; u.ld_e = c.ld_e; u.n_total = c.n_total; u.idx = reinterpret_cast<const long long*>(c.idx); u.rows = (int)c.rows;
     u.N = N; u.G = G; u.part = part; u.nparts = nparts; u.loss = loss; u.inv = inv;
-    const bool u32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
+    const bool u32 = fit_classes_wide(N, cus);
     const int us = u32 ? 32 : 16;
     u.tiles = ((N + us - 1) / us) * (kFitK / us);
     const dim3 grid(u.tiles + (N + kFitDbCols - 1) / kFitDbCols + 1);
@@ -500,7 +612,7 @@ static int fit_launch(const FitCall& c, float* z, float* G, float* part, const F
     FitGradP g = fit_grad_params(c, z);
     g.Y = c.Y; g.y_u8 = c.y_dtype == ACX_TARGET_U8; g.ld_y = c.ld_y;
     g.G = G; g.part = part; g.inv = inv;
-    const bool g32 = (long long)((rows + 31) / 32) * ((N + 31) / 32) >= cus;
+    const bool g32 = fit_rows_wide(rows, N, cus);
     const int gs = g32 ? 32 : 16;
     g.tiles_n = (N + gs - 1) / gs;
     const int gtiles = ((rows + gs - 1) / gs) * g.tiles_n;
@@ -519,7 +631,7 @@ static int fit_ce_launch(const FitCall& c, float* z, float* G, float* part, cons
     const int rows = (int)c.rows, N = c.classes;
     const float inv = (float)(1.0 / (double)rows);
     FitGradP g = fit_grad_params(c, z);
-    const bool g32 = ((N + 31) / 32) * (kFitK / 32) >= cus;
+    const bool g32 = fit_classes_wide(N, cus);
     const int gs = g32 ? 32 : 16;
     g.tiles_n = (N + gs - 1) / gs;
     const int gtiles = ((rows + gs - 1) / gs) * g.tiles_n;
@@ -535,6 +647,88 @@ static int fit_ce_launch(const FitCall& c, float* z, float* G, float* part, cons
     else launch_kernel(&fit_ce_row_kernel<256>, dim3(rows), dim3(kFitThreads), 0, s, r);
     ACX_HIP(hipGetLastError());
     return fit_launch_update(u, c, G, part, rows, loss, inv, cus, apply, s);
+}
+
+// A job's slice of the group workspace: the single call's layout of its loss (z_off is unused for BCE).
+static void fit_group_layout(int loss, long long rows, long long N, size_t* z_off, size_t* part_off, size_t* per_job) {
+    *z_off = 0;
+    if (loss == kLossCe) fit_ce_layout(rows, N, z_off, part_off, per_job);
+    else fit_layout(rows, N, part_off, per_job);
+}
+
+static int fit_group_check_shape(const char* who, int jobs, int64_t rows_max, int classes, int loss) {
+    if (jobs < 1 || jobs > ACX_FIT_MAX_JOBS) ACX_FAIL(ACX_ERR_ARG, "%s: jobs = %d (expected 1 .. %d)", who, jobs, ACX_FIT_MAX_JOBS);
+    if (loss != ACX_FIT_LOSS_BCE && loss != ACX_FIT_LOSS_CE)
+        ACX_FAIL(ACX_ERR_ARG, "%s: loss %d (expected ACX_FIT_LOSS_BCE or ACX_FIT_LOSS_CE)", who, loss);
+    return fit_check_shape(who, rows_max, classes);
+}
+
+struct FitGroupCall {
+    int loss; double eps; int jobs; const acx_fit_job* job_table; const void* plan; int64_t steps, step;
+};
+
+// One group step: each stage once for all jobs.  c holds the shared arguments as a single call's would (rows = rows_max, no W / b).
+static int fit_group_step(const char* who, const FitCall& c, const FitGroupCall& gc, hipStream_t s) {
+    if (!c.E) ACX_FAIL(ACX_ERR_ARG, "%s: E is null", who);
+    if (!c.Y) ACX_FAIL(ACX_ERR_ARG, "%s: %s is null", who, c.y_name);
+    if (!gc.job_table) ACX_FAIL(ACX_ERR_ARG, "%s: jobs is null", who);
+    if (!gc.plan) ACX_FAIL(ACX_ERR_ARG, "%s: plan is null", who);
+    if (!c.status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    if (!c.ws) ACX_FAIL(ACX_ERR_ARG, "%s: workspace is null", who);
+    ACX_TRY(fit_group_check_shape(who, gc.jobs, c.rows, c.classes, gc.loss));
+    if (gc.steps < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n_steps = %lld (expected >= 1)", who, (long long)gc.steps);
+    if (gc.step < 0 || gc.step >= gc.steps)
+        ACX_FAIL(ACX_ERR_ARG, "%s: step = %lld (expected 0 .. %lld)", who, (long long)gc.step, (long long)gc.steps - 1);
+    if (gc.loss == kLossCe) {
+        if (!(gc.eps >= 0.0 && gc.eps < 1.0))
+            ACX_FAIL(ACX_ERR_ARG, "%s: label_smoothing = %g (expected 0 <= label_smoothing < 1)", who, gc.eps);
+    } else if (c.y_dtype != ACX_TARGET_F32 && c.y_dtype != ACX_TARGET_U8) {
+        ACX_FAIL(ACX_ERR_ARG, "%s: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", who, c.y_dtype);
+    }
+    ACX_TRY(fit_check_rows(who, c));                               // W and b live in the job table, on the device
+    if (gc.loss == kLossBce && c.ld_y < c.classes)
+        ACX_FAIL(ACX_ERR_ARG, "%s: ld_target = %lld is shorter than %d classes", who, (long long)c.ld_y, c.classes);
+    FitGroupP q{};
+    size_t per_job;
+    fit_group_layout(gc.loss, c.rows, c.classes, &q.z_off, &q.part_off, &per_job);
+    ACX_TRY(check_workspace_for(who, c.ws, c.ws_bytes, per_job * (size_t)gc.jobs));
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+
+    const int J = gc.jobs, rows = (int)c.rows, N = c.classes;
+    q.E = c.E; q.ld_e = c.ld_e; q.n_total = c.n_total;
+    q.Y = c.Y; q.y_u8 = c.y_dtype == ACX_TARGET_U8; q.ld_y = c.ld_y;
+    q.jobs = gc.job_table; q.plan = static_cast<const FitPlanE*>(gc.plan) + gc.step * J;
+    q.N = N; q.rows_max = rows; q.cus = cus; q.loss = gc.loss;
+    q.ws = static_cast<char*>(c.ws); q.ws_job = per_job; q.status = (int*)c.status;
+    const auto tiles = [&](int S) { return (unsigned)(((rows + S - 1) / S) * ((N + S - 1) / S)); };
+    const bool u32 = fit_classes_wide(N, cus);
+    if (gc.loss == kLossCe) {
+        q.q_hit = (float)((1.0 - gc.eps) + gc.eps / N); q.q_miss = (float)(gc.eps / N); q.ome = (float)(1.0 - gc.eps);
+        if (u32) launch_kernel(&fit_group_grad_kernel<32, kLossCe>, dim3(tiles(32), J), dim3(kFitThreads), 0, s, q);
+        else launch_kernel(&fit_group_grad_kernel<16, kLossCe>, dim3(tiles(16), J), dim3(kFitThreads), 0, s, q);
+        ACX_HIP(hipGetLastError());
+        if (N <= kSoftWaveMaxN) launch_kernel(&fit_group_ce_row_kernel<64>, dim3((rows + 3) / 4, J), dim3(kFitThreads), 0, s, q);
+        else launch_kernel(&fit_group_ce_row_kernel<256>, dim3(rows, J), dim3(kFitThreads), 0, s, q);
+        ACX_HIP(hipGetLastError());
+    } else {
+        // fit_rows_wide never falls as rows grow: a job of 1 .. rows_max rows can need the wide form only if rows_max does, the
+        // narrow one only if a single row does.  One launch per form that can occur; a block of the other form returns at once.
+        if (fit_rows_wide(rows, N, cus)) {
+            launch_kernel(&fit_group_grad_kernel<32, kLossBce>, dim3(tiles(32), J), dim3(kFitThreads), 0, s, q);
+            ACX_HIP(hipGetLastError());
+        }
+        if (!fit_rows_wide(1, N, cus)) {
+            launch_kernel(&fit_group_grad_kernel<16, kLossBce>, dim3(tiles(16), J), dim3(kFitThreads), 0, s, q);
+            ACX_HIP(hipGetLastError());
+        }
+    }
+    const int us = u32 ? 32 : 16;
+    const dim3 ugrid(((N + us - 1) / us) * (kFitK / us) + (N + kFitDbCols - 1) / kFitDbCols + 1, J);
+    if (u32) launch_kernel(&fit_group_update_kernel<32>, ugrid, dim3(kFitThreads), 0, s, q);
+    else launch_kernel(&fit_group_update_kernel<16>, ugrid, dim3(kFitThreads), 0, s, q);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
 }
 
 }  // namespace acx
@@ -627,6 +821,76 @@ int acx_adam_update(float* param, const float* grad, float* m, float* v, float* 
                   vmax, (long long)n, a);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
+}
+
+int acx_head_fit_group_workspace_bytes(int jobs, int64_t rows_max, int classes, int loss, size_t* out_bytes) {
+    static const char* who = "acx_head_fit_group_workspace_bytes";
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "%s: out_bytes is null", who);
+    ACX_TRY(fit_group_check_shape(who, jobs, rows_max, classes, loss));
+    size_t zo, po, per_job;
+    fit_group_layout(loss, rows_max, classes, &zo, &po, &per_job);
+    *out_bytes = per_job * (size_t)jobs;
+    return ACX_OK;
+}
+
+int acx_head_fit_plan_bytes(int jobs, int64_t n_steps, size_t* out_bytes) {
+    static const char* who = "acx_head_fit_plan_bytes";
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "%s: out_bytes is null", who);
+    if (jobs < 1 || jobs > ACX_FIT_MAX_JOBS) ACX_FAIL(ACX_ERR_ARG, "%s: jobs = %d (expected 1 .. %d)", who, jobs, ACX_FIT_MAX_JOBS);
+    if (n_steps < 1 || n_steps > (1LL << 40) / ACX_FIT_MAX_JOBS) ACX_FAIL(ACX_ERR_ARG, "%s: n_steps = %lld (expected >= 1)", who, (long long)n_steps);
+    *out_bytes = sizeof(FitPlanE) * (size_t)jobs * (size_t)n_steps;
+    return ACX_OK;
+}
+
+int acx_head_fit_plan_fill(int jobs, int64_t n_steps, int64_t rows_max, int classes, int loss, const int32_t* rows,
+                           const int64_t* idx_offset, const acx_adam* hp, const double* lr, void* plan, size_t plan_bytes) {
+    static const char* who = "acx_head_fit_plan_fill";
+    size_t need;
+    ACX_TRY(acx_head_fit_plan_bytes(jobs, n_steps, &need));
+    ACX_TRY(fit_group_check_shape(who, jobs, rows_max, classes, loss));
+    if (!rows || !idx_offset || !hp || !lr || !plan) ACX_FAIL(ACX_ERR_ARG, "%s: rows, idx_offset, hp, lr or plan is null", who);
+    if (plan_bytes < need) ACX_FAIL(ACX_ERR_ARG, "%s: plan of %zu bytes, %zu needed", who, plan_bytes, need);
+    for (int j = 1; j < jobs; ++j)
+        if (!hp[j].amsgrad != !hp[0].amsgrad || !hp[j].decoupled != !hp[0].decoupled)
+            ACX_FAIL(ACX_ERR_ARG, "%s: hp[%d] differs from hp[0] in amsgrad / decoupled (a group shares them)", who, j);
+    FitPlanE* out = static_cast<FitPlanE*>(plan);
+    std::vector<int64_t> t((size_t)jobs, 0);
+    for (int64_t s = 0; s < n_steps; ++s)
+        for (int j = 0; j < jobs; ++j) {
+            const size_t i = (size_t)s * jobs + j;
+            FitPlanE e{};
+            if (rows[i] < 0 || rows[i] > rows_max)
+                ACX_FAIL(ACX_ERR_ARG, "%s: rows[%lld][%d] = %d (expected 0 .. rows_max = %lld)", who, (long long)s, j, rows[i], (long long)rows_max);
+            if (rows[i] > 0) {
+                if (idx_offset[i] < 0) ACX_FAIL(ACX_ERR_ARG, "%s: idx_offset[%lld][%d] = %lld (expected >= 0)", who, (long long)s, j, (long long)idx_offset[i]);
+                e.idx_off = idx_offset[i];
+                e.rows = rows[i];
+                e.loss_slot = (int)t[j];
+                e.inv = loss == kLossCe ? (float)(1.0 / (double)rows[i]) : (float)(1.0 / ((double)rows[i] * (double)classes));
+                ACX_TRY(adam_scalars(who, &hp[j], ++t[j], lr[i], &e.a));      // the job's own step count: idle steps do not advance it
+            }
+            out[i] = e;
+        }
+    return ACX_OK;
+}
+
+int acx_head_fit_group_step(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                            int64_t ld_target, int jobs, int64_t rows_max, int classes, const acx_fit_job* job_table,
+                            const void* plan, int64_t n_steps, int64_t step, int32_t* status, void* ws, size_t ws_bytes,
+                            void* stream) {
+    const FitCall c{E, ld_e, n_rows_total, target, "target", target_dtype, ld_target, 0.0, nullptr, rows_max, classes, nullptr,
+                    nullptr, status, ws, ws_bytes};
+    return fit_group_step("acx_head_fit_group_step", c, FitGroupCall{kLossBce, 0.0, jobs, job_table, plan, n_steps, step},
+                          (hipStream_t)stream);
+}
+
+int acx_head_fit_group_step_ce(const float* E, int64_t ld_e, int64_t n_rows_total, const int64_t* labels, int jobs, int64_t rows_max,
+                               int classes, double label_smoothing, const acx_fit_job* job_table, const void* plan, int64_t n_steps,
+                               int64_t step, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    const FitCall c{E, ld_e, n_rows_total, labels, "labels", 0, 0, label_smoothing, nullptr, rows_max, classes, nullptr, nullptr,
+                    status, ws, ws_bytes};
+    return fit_group_step("acx_head_fit_group_step_ce", c,
+                          FitGroupCall{kLossCe, label_smoothing, jobs, job_table, plan, n_steps, step}, (hipStream_t)stream);
 }
 
 }  // extern "C"

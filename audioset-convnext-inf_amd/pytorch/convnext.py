@@ -791,6 +791,24 @@ class ConvNeXt(nn.Module):
         runs it, state_dict() saves a checkpoint that from_pretrained loads as a fine-tuned model.  The model stays in eval
         mode.  Returns the HeadFit."""
         from . import finetune as _ft
+        emb, target = self._fit_inputs(data, target, sample_rate)
+        fit = _ft.fit_head(emb, target, **kw)
+        self._install_fit(fit)
+        return fit
+
+    def cross_validate_head(self, data, target, sample_rate=None, install=True, **kw):
+        """k-fold cross-validation of a new head over a grid of settings (pytorch/finetune.py, cross_validate_head): data and
+        target exactly as fit_head takes them; **kw: folds=, grid=, fold_ids=, stratify=, metric=, refit= and fit_head's
+        settings.  install=True installs cv.final -- the best setting refitted on all rows -- as fit_head installs its fit
+        (nothing is installed with refit=False).  Returns the CrossValidation."""
+        from . import finetune as _ft
+        emb, target = self._fit_inputs(data, target, sample_rate)
+        cv = _ft.cross_validate_head(emb, target, **kw)
+        if install and cv.final is not None:
+            self._install_fit(cv.final)
+        return cv
+
+    def _fit_inputs(self, data, target, sample_rate):
         from .extract_embeddings import extract
         dev = self.head_audioset.weight.device
         if isinstance(data, torch.Tensor) and data.dim() == 2:
@@ -799,14 +817,17 @@ class ConvNeXt(nn.Module):
             emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
         if isinstance(target, torch.Tensor) and target.device != emb.device:
             target = target.to(emb.device)
-        fit = _ft.fit_head(emb, target, **kw)
+        return emb, target
+
+    def _install_fit(self, fit):
+        from . import finetune as _ft
+        dev = self.head_audioset.weight.device
         head = nn.Linear(_ft.EMBED_DIM, fit.weight.shape[0]).to(dev)
         with torch.no_grad():
             head.weight.copy_(fit.weight)
             head.bias.copy_(fit.bias)
         head.train(self.training)
         self.head_audioset = head
-        return fit
 
     def calibrate(self, data, target, method="platt", sample_rate=None, **kw):
         """Fit a calibration map for this model's head on a validation split (pytorch/calibration.py): `data` is an (n, N)

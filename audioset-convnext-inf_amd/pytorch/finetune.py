@@ -17,6 +17,12 @@ A single-label head (one class per clip: ESC-50, "one folder per class") is trai
 (acx_head_fit_step_ce: three launches per step), read with pytorch/classify.py softmax_topk and judged with
 classification_metrics.  loss="bce" (the default) is the path above, bit for bit.
 
+Many fits over the same embeddings -- the folds of a cross-validation, the settings of a grid -- advance together, each stage one
+launch for all of them (acx_head_fit_group_step), every head bit-equal to its fit_head call:
+
+    fits = fit_heads(emb, target, [dict(rows=train_rows, val=held_rows, lr=1e-3), ...], epochs=20)
+    cv = cross_validate_head(emb, labels, folds=5, grid={"lr": [1e-4, 1e-3]}, loss="ce", classes=50)   # cv.scores, cv.best, cv.final
+
 The epoch order is part of the contract: torch.randperm(n, generator=g) drawn once per epoch from ONE CPU generator
 g = torch.Generator().manual_seed(seed) (shuffle=False: arange); the last batch of an epoch is short unless drop_last.  The
 initial weights (init=None) come from a second generator seeded with `seed` too: trunc_normal_(std=0.02) weight, zero bias
@@ -199,18 +205,8 @@ def _check_val(val, N, device):
 _Loss = namedtuple("_Loss", ["workspace_bytes", "step", "target_args", "class_args", "check_val", "validate"])
 
 
-def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=True,
-             decoupled=False, init=None, seed=0, shuffle=True, drop_last=False, val=None, loss="bce", label_smoothing=0.0,
-             classes=None):
-    """Train an nn.Linear(768, N) head on (n, 768) scene embeddings with binary cross-entropy and Adam (decoupled=True: AdamW);
-    the defaults are the reference's fine-tuning settings.  lr: a float, or one value per step.  init: None (seeded
-    trunc_normal(std=0.02) weight, zero bias) or (weight, bias) to continue from a head; the moments always start at zero.
-    val: (emb_val, target_val) -> per-epoch tagging_metrics in the history (this synchronises once per epoch).
-    loss="ce": softmax cross-entropy for a single-label head (F.cross_entropy with label_smoothing in [0, 1)); target is (n,)
-    integer labels with classes=N, or (n, N) one-hot rows (labels_of); val=(emb_val, labels_val) puts accuracy, topk_accuracy
-    (k = min(5, N)) and macro_f1 into the history.
-    Returns HeadFit(weight, bias, loss, history): device tensors and a list of one dict per epoch, whose "loss" is a 0-d
-    device tensor (the mean of the epoch's step losses)."""
+def _check_loss(loss, label_smoothing, classes):
+    """The loss settings of fit_head / fit_heads; -> (ce, label_smoothing as a float)."""
     if loss not in ("bce", "ce"):
         raise ValueError("loss must be \"bce\" or \"ce\" (got %r)" % (loss,))
     label_smoothing = float(label_smoothing)
@@ -221,7 +217,11 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
         raise ValueError("classes= belongs to loss=\"ce\"; with loss=\"bce\" the class count is the target's width")
     if ce and not 0.0 <= label_smoothing < 1.0:
         raise ValueError("label_smoothing must be in [0, 1) (got %r)" % (label_smoothing,))
-    _check_hyper(epochs, batch_size, betas, eps, weight_decay)
+    return ce, label_smoothing
+
+
+def _check_data(emb, target, ce, label_smoothing, classes):
+    """The (embeddings, targets) of a fit, checked; -> (emb, the kernel's target tensor, N, the loss's _Loss)."""
     if ce:
         _check_emb(emb, device=False)
         tgt, N = labels_of(target, int(emb.shape[0]), classes)     # the target's own errors come before the GPU-only one
@@ -235,6 +235,34 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
         emb, tgt, tdtype = _check_pair(emb, target)
         N = int(tgt.shape[1])
         how = _Loss(_ffi.head_fit_workspace_bytes, "acx_head_fit_step", (vp(tgt), tdtype, tgt.stride(0)), (N,), _check_val, _validate)
+    return emb, tgt, N, how
+
+
+def _check_init(init, N):
+    if len(init) != 2:
+        raise ValueError("init must be (weight, bias)")
+    w0, b0 = init
+    if tuple(w0.shape) != (N, EMBED_DIM) or tuple(b0.shape) != (N,):
+        raise ValueError("init must be a (%d, %d) weight and a (%d,) bias (got %s and %s)"
+                         % (N, EMBED_DIM, N, tuple(w0.shape), tuple(b0.shape)))
+    return w0, b0
+
+
+def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=True,
+             decoupled=False, init=None, seed=0, shuffle=True, drop_last=False, val=None, loss="bce", label_smoothing=0.0,
+             classes=None):
+    """Train an nn.Linear(768, N) head on (n, 768) scene embeddings with binary cross-entropy and Adam (decoupled=True: AdamW);
+    the defaults are the reference's fine-tuning settings.  lr: a float, or one value per step.  init: None (seeded
+    trunc_normal(std=0.02) weight, zero bias) or (weight, bias) to continue from a head; the moments always start at zero.
+    val: (emb_val, target_val) -> per-epoch tagging_metrics in the history (this synchronises once per epoch).
+    loss="ce": softmax cross-entropy for a single-label head (F.cross_entropy with label_smoothing in [0, 1)); target is (n,)
+    integer labels with classes=N, or (n, N) one-hot rows (labels_of); val=(emb_val, labels_val) puts accuracy, topk_accuracy
+    (k = min(5, N)) and macro_f1 into the history.
+    Returns HeadFit(weight, bias, loss, history): device tensors and a list of one dict per epoch, whose "loss" is a 0-d
+    device tensor (the mean of the epoch's step losses)."""
+    ce, label_smoothing = _check_loss(loss, label_smoothing, classes)
+    _check_hyper(epochs, batch_size, betas, eps, weight_decay)
+    emb, tgt, N, how = _check_data(emb, target, ce, label_smoothing, classes)
     n, device = int(emb.shape[0]), emb.device
     if val is not None:
         if len(val) != 2:
@@ -245,12 +273,7 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
     if init is None:
         w0, b0 = init_head(N, seed)
     else:
-        if len(init) != 2:
-            raise ValueError("init must be (weight, bias)")
-        w0, b0 = init
-        if tuple(w0.shape) != (N, EMBED_DIM) or tuple(b0.shape) != (N,):
-            raise ValueError("init must be a (%d, %d) weight and a (%d,) bias (got %s and %s)"
-                             % (N, EMBED_DIM, N, tuple(w0.shape), tuple(b0.shape)))
+        w0, b0 = _check_init(init, N)
     batches = epoch_batches(n, batch_size, drop_last)
     steps = epochs * len(batches)
     lrs = _lr_schedule(lr, steps)
@@ -290,3 +313,294 @@ def fit_head(emb, target, epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999),
                 rec.update(how.validate(W, b, emb_val, target_val))
             history.append(rec)
     return HeadFit(W, b, loss, history)
+
+
+# ---- many heads at once: groups of fits, k-fold cross-validation, grids ---------------------------------------------------------
+# A small fit is bound by launch latency: a step of (n 2 000, N 50, batch 64) occupies 16 + 192 workgroups of a 256-CU part.
+# fit_heads advances up to FIT_MAX_JOBS independent fits over the SAME embeddings per launch (acx_head_fit_group_step); every
+# head has the bits of the fit_head call it replaces.
+
+_JOB_DEFAULTS = {"rows": None, "lr": 1e-4, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.0, "seed": 0, "init": None,
+                 "val": None}
+GRID_JOB_KEYS = ("lr", "weight_decay", "betas", "eps", "seed")                   # what the jobs of one group may differ in
+GRID_SHARED_KEYS = ("epochs", "batch_size", "label_smoothing", "amsgrad", "decoupled", "shuffle", "drop_last")
+CrossValidation = namedtuple("CrossValidation", ["configs", "fold_ids", "metric", "scores", "mean", "std", "best", "fits", "final"])
+
+
+def group_schedule(sizes, epochs, batch_size, drop_last=False):
+    """(steps, J) int32 numpy array: the rows job j (a training set of sizes[j] rows) has in each step of a group fit.  An epoch
+    of the group takes as many steps as its longest job's epoch; job j runs its own epoch_batches(sizes[j], ...) in the first
+    steps of each epoch and sits the rest out (0 rows)."""
+    per = [epoch_batches(m, batch_size, drop_last) for m in sizes]
+    spe = max([len(b) for b in per], default=0)
+    rows = np.zeros((int(epochs) * spe, len(per)), dtype=np.int32)
+    for j, b in enumerate(per):
+        for k, (_, r) in enumerate(b):
+            rows[k::spe, j] = r
+    return rows
+
+
+def _check_index(rows, n, name, device):
+    """A (m,) int64 tensor of row numbers in [0, n), on the CPU or on `device`; -> its CPU copy."""
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.dtype != torch.int64:
+        raise ValueError("%s must be a (m,) int64 tensor of row numbers (got %s)"
+                         % (name, getattr(rows, "dtype", type(rows))))
+    if rows.shape[0] < 1:
+        raise ValueError("%s holds no rows" % name)
+    if rows.device.type != "cpu" and rows.device != device:
+        raise ValueError("%s is on %s, emb on %s" % (name, rows.device, device))
+    r = rows.cpu()
+    if int(r.min()) < 0 or int(r.max()) >= n:
+        raise ValueError("%s holds row numbers outside [0, %d)" % (name, n))
+    return r
+
+
+def _check_jobs(jobs, n, device, epochs, batch_size, drop_last):
+    """The job list of fit_heads with the defaults filled in, rows / val as CPU tensors (None: all rows / no validation) and
+    lr as the list of the job's steps."""
+    if not isinstance(jobs, (list, tuple)) or len(jobs) == 0:
+        raise ValueError("jobs must be a non-empty list of dicts")
+    out = []
+    for j, job in enumerate(jobs):
+        if not isinstance(job, dict) or set(job) - set(_JOB_DEFAULTS):
+            raise ValueError("jobs[%d] must be a dict with keys among %s (got %r)" % (j, sorted(_JOB_DEFAULTS), job))
+        job = dict(_JOB_DEFAULTS, **job)
+        _check_hyper(epochs, batch_size, job["betas"], job["eps"], job["weight_decay"])
+        if job["rows"] is not None:
+            job["rows"] = _check_index(job["rows"], n, "jobs[%d][\"rows\"]" % j, device)
+        if job["val"] is not None:
+            job["val"] = _check_index(job["val"], n, "jobs[%d][\"val\"]" % j, device)
+        job["size"] = n if job["rows"] is None else int(job["rows"].shape[0])
+        job["steps"] = epochs * len(epoch_batches(job["size"], batch_size, drop_last))
+        job["lr"] = _lr_schedule(job["lr"], job["steps"])
+        out.append(job)
+    return out
+
+
+def fit_heads(emb, target, jobs, epochs=20, batch_size=64, loss="bce", label_smoothing=0.0, classes=None, amsgrad=True,
+              decoupled=False, shuffle=True, drop_last=False):
+    """Train many heads over the same embeddings at once.  jobs: a list of dicts, each with any of
+        rows=None | (m,) int64 row numbers of emb (the job's training set), lr (a float or one value per step OF THAT JOB), betas,
+        eps, weight_decay, seed, init (fit_head's), val=None | (v,) int64 row numbers (held out: the metrics of fit_head's val=
+        after the last epoch, in the last record of the history)
+    -> [HeadFit] in job order.  fits[j].weight / .bias / .loss equal, bit for bit, fit_head(emb[rows], target[rows], ...) with
+    the job's settings and the shared ones: job j visits rows[epoch_orders(len(rows), epochs, seed)[e]] in epoch e, gathered
+    through the batch indices -- no copy of a subset is made for training.  Every step of a group advances all its jobs (each
+    stage is one launch); jobs whose epoch has fewer batches sit the last steps of each epoch out (group_schedule).  More than
+    FIT_MAX_JOBS jobs run as several groups.  Nothing synchronises per step or per epoch."""
+    ce, label_smoothing = _check_loss(loss, label_smoothing, classes)
+    _check_emb(emb, device=False)
+    n = int(emb.shape[0])
+    jobs = _check_jobs(jobs, n, emb.device, epochs, batch_size, drop_last)      # the jobs' own errors come before the GPU-only one
+    emb, tgt, N, how = _check_data(emb, target, ce, label_smoothing, classes)
+    inits = [init_head(N, job["seed"]) if job["init"] is None else _check_init(job["init"], N) for job in jobs]
+    fits = []
+    for lo in range(0, len(jobs), _ffi.FIT_MAX_JOBS):
+        fits += _fit_group(emb, tgt, N, how, ce, label_smoothing, jobs[lo:lo + _ffi.FIT_MAX_JOBS], inits[lo:lo + _ffi.FIT_MAX_JOBS],
+                           epochs, batch_size, amsgrad, decoupled, shuffle, drop_last)
+    return fits
+
+
+def _fit_group(emb, tgt, N, how, ce, label_smoothing, jobs, inits, epochs, batch_size, amsgrad, decoupled, shuffle, drop_last):
+    n, device, J = int(emb.shape[0]), emb.device, len(jobs)
+    sizes = [job["size"] for job in jobs]
+    rows = group_schedule(sizes, epochs, batch_size, drop_last)
+    steps = rows.shape[0]
+    spe = steps // epochs if epochs else 0
+    with torch.no_grad(), torch.cuda.device(device):
+        W = torch.stack([w.detach().to(device=device, dtype=torch.float32) for w, _ in inits]).contiguous()
+        b = torch.stack([v.detach().to(device=device, dtype=torch.float32) for _, v in inits]).contiguous()
+        max_steps = max(job["steps"] for job in jobs)
+        loss = torch.zeros((J, max_steps), dtype=torch.float32, device=device)
+        if steps:
+            # job j's batches of all epochs, one after the other: rows_j[order of epoch e]; the plan holds each step's offset
+            orders, starts, at = [], [], 0
+            for job in jobs:
+                o = epoch_orders(job["size"], epochs, job["seed"], shuffle)
+                orders.append((o if job["rows"] is None else job["rows"][o]).reshape(-1))
+                starts.append(at)
+                at += orders[-1].numel()
+            idx = torch.cat(orders).to(device)
+            idx_off = np.zeros((epochs, spe, J), dtype=np.int64)
+            lrs = np.zeros((epochs, spe, J), dtype=np.float64)
+            for j, job in enumerate(jobs):
+                first = np.array([start for start, _ in epoch_batches(sizes[j], batch_size, drop_last)], dtype=np.int64)
+                idx_off[:, :len(first), j] = np.arange(epochs, dtype=np.int64)[:, None] * sizes[j] + first[None, :]
+                lrs[:, :len(first), j] = np.asarray(job["lr"], dtype=np.float64).reshape(epochs, len(first))
+            idx_off, lrs = idx_off.reshape(steps, J), lrs.reshape(steps, J)
+            hps = [_ffi.adam(job["betas"][0], job["betas"][1], job["eps"], job["weight_decay"], amsgrad, decoupled) for job in jobs]
+            code = _ffi.FIT_LOSS_CE if ce else _ffi.FIT_LOSS_BCE
+            rows_max = min(batch_size, max(sizes))
+            plan = torch.from_numpy(_ffi.head_fit_plan(rows, idx_off, lrs, hps, rows_max, N, code)).to(device)
+            mom = torch.zeros((J, 3, N, EMBED_DIM), dtype=torch.float32, device=device)
+            momb = torch.zeros((J, 3, N), dtype=torch.float32, device=device)
+            table = (_ffi.AcxFitJob * J)()
+            for j in range(J):
+                t = table[j]
+                t.idx, t.W, t.b, t.loss = idx.data_ptr() + 8 * starts[j], W[j].data_ptr(), b[j].data_ptr(), loss[j].data_ptr()
+                t.mW, t.vW, t.mb, t.vb = mom[j, 0].data_ptr(), mom[j, 1].data_ptr(), momb[j, 0].data_ptr(), momb[j, 1].data_ptr()
+                t.vmaxW, t.vmaxb = (mom[j, 2].data_ptr(), momb[j, 2].data_ptr()) if amsgrad else (None, None)
+            table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+            status = torch.zeros(J, dtype=torch.int32, device=device)
+            ws_bytes = _ffi.head_fit_group_workspace_bytes(J, rows_max, N, code)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+            step_fn = getattr(_ffi.lib(), "acx_head_fit_group_step_ce" if ce else "acx_head_fit_group_step")
+            head = (vp(emb), emb.stride(0), n) + how.target_args + (J, rows_max) + how.class_args + (vp(table), vp(plan), steps)
+            tail = (vp(status), vp(ws), ws_bytes, _ffi.stream_ptr(device))
+            for s in range(steps):
+                rc = step_fn(*head, s, *tail)
+                if rc != _ffi.OK:
+                    _ffi.check(rc)
+        fits = []
+        for j, job in enumerate(jobs):
+            lj = loss[j, :job["steps"]]
+            means = lj.view(epochs, -1).mean(dim=1) if job["steps"] else None
+            history = [{"epoch": e, "loss": means[e]} for e in range(epochs)] if job["steps"] else []
+            if job["val"] is not None and history:
+                v = job["val"].to(device)
+                history[-1].update(how.validate(W[j], b[j], emb[v], tgt[v]))
+            fits.append(HeadFit(W[j], b[j], lj, history))
+    return fits
+
+
+def kfold_ids(n, folds, seed=0, labels=None):
+    """(n,) int64 CPU tensor of fold numbers in [0, folds).  perm = torch.randperm(n, generator=Generator().manual_seed(seed));
+    plain: row perm[i] goes to fold i % folds.  labels ((n,) integers): the rows of perm are first sorted stably by label and
+    then dealt round-robin WITHOUT restarting at class boundaries, so every class's counts, and the fold sizes, differ by at
+    most one between folds."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("n must be an integer >= 1 (got %r)" % (n,))
+    if isinstance(folds, bool) or not isinstance(folds, int) or not 2 <= folds <= n:
+        raise ValueError("folds must be an integer in 2 .. n = %d (got %r)" % (n, folds))
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.as_tensor(np.asarray(labels))
+        if labels.dim() != 1 or labels.shape[0] != n:
+            raise ValueError("stratified folds need (n,) class numbers: multi-label targets cannot be stratified (got shape %s)"
+                             % (tuple(labels.shape),))
+        if labels.dtype == torch.bool or labels.dtype.is_floating_point or labels.dtype.is_complex:
+            raise ValueError("labels must be an integer tensor of class numbers (got %s)" % labels.dtype)
+        perm = perm[torch.sort(labels.cpu().to(torch.int64)[perm], stable=True).indices]
+    ids = torch.empty(n, dtype=torch.int64)
+    ids[perm] = torch.arange(n) % folds
+    return ids
+
+
+def expand_grid(grid):
+    """The configs of a grid, as a list of dicts: None -> [{}]; a dict of lists -> their product in key order (the first key
+    varies slowest); a list of dicts -> itself.  Keys: GRID_JOB_KEYS and GRID_SHARED_KEYS."""
+    if grid is None:
+        return [{}]
+    if isinstance(grid, dict):
+        if not grid:
+            return [{}]
+        keys = list(grid)
+        for k in keys:
+            if isinstance(grid[k], (str, bytes)) or not hasattr(grid[k], "__len__") or len(grid[k]) == 0:
+                raise ValueError("grid[%r] must be a non-empty list of values" % (k,))
+        configs = [{}]
+        for k in keys:
+            configs = [dict(c, **{k: v}) for c in configs for v in grid[k]]
+    elif isinstance(grid, (list, tuple)) and len(grid) and all(isinstance(c, dict) for c in grid):
+        configs = [dict(c) for c in grid]
+    else:
+        raise ValueError("grid must be None, a dict of lists or a non-empty list of dicts")
+    for c in configs:
+        bad = set(c) - set(GRID_JOB_KEYS) - set(GRID_SHARED_KEYS)
+        if bad:
+            raise ValueError("grid key %r is not one of %s" % (sorted(bad)[0], GRID_JOB_KEYS + GRID_SHARED_KEYS))
+    return configs
+
+
+def partition_configs(configs):
+    """[(shared settings dict, [config numbers])]: the configs that agree in every GRID_SHARED_KEYS value they set can run in
+    one group; the partitions come in order of first appearance."""
+    parts = {}
+    for i, c in enumerate(configs):
+        key = tuple((k, c[k]) for k in GRID_SHARED_KEYS if k in c)
+        parts.setdefault(key, []).append(i)
+    return [(dict(key), members) for key, members in parts.items()]
+
+
+def select_best(mean):
+    """The index of the highest mean: ties go to the lowest index, a NaN mean is never best (all NaN: None)."""
+    best = None
+    for i, m in enumerate(mean):
+        if not np.isnan(m) and (best is None or m > mean[best]):
+            best = i
+    return best
+
+
+def cross_validate_head(emb, target, folds=5, grid=None, fold_ids=None, stratify=None, seed=0, refit=True, metric=None,
+                        keep_fits=True, **settings):
+    """k-fold cross-validation of a head over a grid of settings, all fits advanced together (fit_heads).
+    grid: expand_grid's; a config overrides `settings` (fit_head's keywords except init / val; `seed` also seeds every fit
+    unless the grid sets it).  Jobs are (config, fold): trained on the other folds, validated on the fold; configs that differ
+    in a shared setting (GRID_SHARED_KEYS) run as separate groups.  fold_ids: (n,) fold numbers in [0, folds), or None for
+    kfold_ids(n, folds, seed, labels) -- stratified by default for loss="ce" (stratify=True with multi-label targets is
+    refused).  metric: a key of the validation record (default "mAP" for bce, "accuracy" for ce).
+    -> CrossValidation(configs, fold_ids, metric, scores (configs, folds) float64, mean, std, best, fits, final): best =
+    select_best(mean); fits[c][f] the HeadFit of (config, fold), None with keep_fits=False; final = fit_head on all rows with
+    configs[best] when refit (else None) -- the head to use."""
+    loss = settings.get("loss", "bce")
+    bad = set(settings) - {"epochs", "batch_size", "lr", "betas", "eps", "weight_decay", "amsgrad", "decoupled", "shuffle",
+                           "drop_last", "loss", "label_smoothing", "classes"}
+    if bad:
+        raise ValueError("cross_validate_head takes no setting %r" % (sorted(bad)[0],))
+    ce, _ = _check_loss(loss, settings.get("label_smoothing", 0.0), settings.get("classes"))
+    _check_emb(emb, device=False)
+    n = int(emb.shape[0])
+    configs = []
+    for c in expand_grid(grid):
+        full = {"seed": seed}
+        full.update(settings)
+        full.update(c)
+        configs.append(full)
+    if metric is None:
+        metric = "accuracy" if ce else "mAP"
+    if stratify is None:
+        stratify = ce
+    if fold_ids is None:
+        labels = None
+        if stratify:
+            if not ce:
+                raise ValueError("stratify=True needs single-label targets (loss=\"ce\"): multi-label rows have no one class")
+            labels = labels_of(target, n, settings.get("classes"))[0]
+        fold_ids = kfold_ids(n, folds, seed, labels)
+    else:
+        fold_ids = torch.as_tensor(fold_ids).cpu()
+        if fold_ids.dim() != 1 or fold_ids.shape[0] != n or fold_ids.dtype.is_floating_point:
+            raise ValueError("fold_ids must be (%d,) integers" % n)
+        fold_ids = fold_ids.to(torch.int64)
+        if isinstance(folds, bool) or not isinstance(folds, int) or folds < 2:
+            raise ValueError("folds must be an integer >= 2 (got %r)" % (folds,))
+        if int(fold_ids.min()) < 0 or int(fold_ids.max()) >= folds:
+            raise ValueError("fold_ids holds values outside [0, %d)" % folds)
+        if len(torch.unique(fold_ids)) != folds:
+            raise ValueError("fold_ids leaves a fold empty")
+    held = [torch.nonzero(fold_ids == f).reshape(-1) for f in range(folds)]
+    train = [torch.nonzero(fold_ids != f).reshape(-1) for f in range(folds)]
+
+    shared_names = ("epochs", "batch_size", "loss", "label_smoothing", "classes", "amsgrad", "decoupled", "shuffle", "drop_last")
+    fits = [None] * len(configs)
+    for _, members in partition_configs(configs):
+        shared = {k: configs[members[0]][k] for k in shared_names if k in configs[members[0]]}
+        jobs = [dict({k: configs[c][k] for k in GRID_JOB_KEYS if k in configs[c]}, rows=train[f], val=held[f])
+                for c in members for f in range(folds)]
+        got = fit_heads(emb, target, jobs, **shared)
+        for i, c in enumerate(members):
+            fits[c] = got[i * folds:(i + 1) * folds]
+    scores = np.full((len(configs), folds), np.nan, dtype=np.float64)
+    for c, per_fold in enumerate(fits):
+        for f, fit in enumerate(per_fold):
+            rec = fit.history[-1] if fit.history else {}
+            if metric not in rec:
+                raise ValueError("metric %r is not in the validation record (%s)" % (metric, sorted(set(rec) - {"epoch", "loss"})))
+            scores[c, f] = float(rec[metric])
+    mean, std = scores.mean(axis=1), scores.std(axis=1)
+    best = select_best(mean)
+    final = None
+    if refit and best is not None:
+        final = fit_head(emb, target, **configs[best])
+    return CrossValidation(configs, fold_ids, metric, scores, mean, std, best, fits if keep_fits else None, final)

@@ -7,6 +7,7 @@ as a checkpoint that ConvNeXt.from_pretrained loads as an N-class model.
     python demo_finetune.py --ckpt ... --csv clips.csv --out my_tagger/        # lines: path.wav,label[;label...]
     python demo_finetune.py --synthetic --out /tmp/tagger                      # seeded weights and clips, no files needed
     python demo_finetune.py --ckpt ... --data sounds/ --loss ce --out my_classifier/    # one class per clip: softmax cross-entropy
+    python demo_finetune.py --ckpt ... --data sounds/ --loss ce --folds 5 --grid-lr 1e-4,3e-4,1e-3 --out my_classifier/
 
 Writes <out>/model.safetensors, <out>/model.pth ({"model": state_dict}) and <out>/labels.txt (one class name per line, in head
 order).  With a validation split, one decision threshold per class is chosen on it (the largest F1, metrics.operating_points)
@@ -15,7 +16,10 @@ and written next to <out> as <out>.thresholds.npy -- demo_convnext.py --threshol
 accuracy, top-5 accuracy and the five largest confusions, and writes no thresholds file -- read the model with
 ConvNeXt.classify / demo_convnext.py --softmax.  With a validation split the head's probabilities are also calibrated on it
 (pytorch/calibration.py: per-class Platt scaling for --loss bce, temperature scaling for --loss ce): the ECE before and after is
-printed and the map written as <out>.calibration.npz -- demo_convnext.py --calibration takes it."""
+printed and the map written as <out>.calibration.npz -- demo_convnext.py --calibration takes it.
+--folds K cross-validates the settings of --grid-lr x --grid-weight-decay (default: the one --lr / --weight-decay pair) on the
+training split first, all K x settings fits advanced together on the GPU (ConvNeXt.cross_validate_head): one line per setting,
+the best marked; the run then continues as above with the best setting."""
 import argparse
 import csv
 import os
@@ -80,6 +84,9 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=0.0, help="--loss ce only")
     ap.add_argument("--val-fraction", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--folds", type=int, default=0, help="K-fold cross-validation of the grid on the training split first")
+    ap.add_argument("--grid-lr", help="comma-separated learning rates for --folds (default: --lr)")
+    ap.add_argument("--grid-weight-decay", help="comma-separated weight decays for --folds (default: --weight-decay)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("this build runs on an MI355X; no GPU is visible")
@@ -125,6 +132,22 @@ def main():
     if ce and not bool((target.sum(dim=1) == 1).all()):
         sys.exit("--loss ce needs exactly one label per clip")
     extra = dict(loss="ce", label_smoothing=a.label_smoothing) if ce else {}
+    if a.folds:
+        grid = {"lr": [float(v) for v in a.grid_lr.split(",")] if a.grid_lr else [a.lr],
+                "weight_decay": [float(v) for v in a.grid_weight_decay.split(",")] if a.grid_weight_decay else [a.weight_decay]}
+        cv = model.cross_validate_head(emb[tr], target[tr], folds=a.folds, grid=grid, seed=a.seed, refit=False, install=False,
+                                       keep_fits=False, epochs=a.epochs, batch_size=a.batch_size, decoupled=a.adamw, **extra)
+        torch.cuda.synchronize()
+        for c, cfg in enumerate(cv.configs):
+            print("%s lr %-8g weight decay %-8g  %s %.3f +- %.3f  (%s)" % (
+                "*" if c == cv.best else " ", cfg["lr"], cfg["weight_decay"], cv.metric, cv.mean[c], cv.std[c],
+                " ".join("%.3f" % v for v in cv.scores[c])))
+        if cv.best is None:
+            sys.exit("every setting's %s is NaN: no best setting" % cv.metric)
+        a.lr, a.weight_decay = cv.configs[cv.best]["lr"], cv.configs[cv.best]["weight_decay"]
+        print("cross-validation %.2f s (%d folds x %d settings); continuing with lr %g, weight decay %g"
+              % (time.perf_counter() - t1, a.folds, len(cv.configs), a.lr, a.weight_decay))
+        t1 = time.perf_counter()
     fit = model.fit_head(emb[tr], target[tr], epochs=a.epochs, batch_size=a.batch_size, lr=a.lr, weight_decay=a.weight_decay,
                          decoupled=a.adamw, seed=a.seed, val=(emb[va], target[va]) if n_val else None, **extra)
     torch.cuda.synchronize()

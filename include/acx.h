@@ -756,6 +756,49 @@ ACX_API int acx_head_fit_grad_ce(const float* E, int64_t ld_e, int64_t n_rows_to
                                  float* G, float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* Groups: `jobs` independent fits (1 .. ACX_FIT_MAX_JOBS: the folds of a cross-validation, the settings of a grid) over the SAME
+ * E and target / labels, advanced together: one group step launches each stage ONCE for all jobs (BCE: the gradient pass, once
+ * per tile form that can occur, and the update; cross-entropy: logits, row pass, update).  The jobs share classes, the loss,
+ * label_smoothing, rows_max (the batch size) and hp->amsgrad / hp->decoupled; each has its own batch (so its own training subset
+ * and epoch order), its own row count per step -- 0: the job sits the step out and NOTHING of it is written -- and its own W, b,
+ * moments, optimiser scalars, step count, loss outputs and status word.
+ *   Every job's W, b, loss outputs and status have the bits of the acx_head_fit_step / _step_ce calls it replaces: each job runs
+ *   the tile form its own single call would (decided per job on the device by the single call's rule) and the same orders of
+ *   addition; its step count t advances only in the steps in which it has rows.
+ * acx_fit_job: a job's DEVICE pointers; the table of `jobs` of them lives on the device.  idx: the job's batches of all steps
+ * (int64 rows of E, as acx_head_fit_step's idx); loss: one float per step in which the job has rows, in order; the rest as
+ * acx_head_fit_step's (W 16-byte aligned; vmaxW / vmaxb may be NULL unless amsgrad).  The host cannot check these.
+ * The plan: what changes from step to step -- (row count, offset of the batch in the job's idx, 1 / count, the optimiser scalars
+ * of the job's step t with that step's lr) per (step, job) -- evaluated on the HOST by the single calls' own code, once, before
+ * the first step.  acx_head_fit_plan_bytes: 64 bytes per entry.  acx_head_fit_plan_fill (host only, no device needed): rows,
+ * idx_offset and lr are [n_steps][jobs] (idx_offset and lr are not read where rows is 0), hp is [jobs]; writes plan_bytes of HOST
+ * memory, which the caller copies to the device once.  Its layout is private.  ACX_ERR_ARG: what acx_head_fit_step refuses in hp
+ * and lr, rows outside 0 .. rows_max, a negative offset, jobs that differ in amsgrad / decoupled, a plan buffer too small.
+ * acx_head_fit_group_step / _step_ce: step `step` (0 .. n_steps - 1) of the plan at DEVICE pointer `plan`; status: `jobs`
+ * int32 words (ACX_FIT_BAD_INDEX / ACX_FIT_BAD_LABEL, ORed into the offending job's word only).  Workspace:
+ * acx_head_fit_group_workspace_bytes(jobs, rows_max, classes, loss) (host only).  The launch contract of acx_head_fit_step: in
+ * order on `stream`, no copy, no allocation, no synchronisation, capturable (a captured step replays that step of the plan);
+ * argument errors return before any launch. */
+#define ACX_FIT_MAX_JOBS 256
+enum acx_fit_loss { ACX_FIT_LOSS_BCE = 0, ACX_FIT_LOSS_CE = 1 };
+typedef struct acx_fit_job {
+    const int64_t* idx;
+    float *W, *b, *mW, *vW, *vmaxW, *mb, *vb, *vmaxb;
+    float* loss;
+} acx_fit_job;
+ACX_API int acx_head_fit_group_workspace_bytes(int jobs, int64_t rows_max, int classes, int loss, size_t* out_bytes);
+ACX_API int acx_head_fit_plan_bytes(int jobs, int64_t n_steps, size_t* out_bytes);
+ACX_API int acx_head_fit_plan_fill(int jobs, int64_t n_steps, int64_t rows_max, int classes, int loss, const int32_t* rows,
+                                   const int64_t* idx_offset, const acx_adam* hp, const double* lr, void* plan, size_t plan_bytes);
+ACX_API int acx_head_fit_group_step(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                                    int64_t ld_target, int jobs, int64_t rows_max, int classes, const acx_fit_job* job_table,
+                                    const void* plan, int64_t n_steps, int64_t step, int32_t* status, void* ws, size_t ws_bytes,
+                                    void* stream);
+ACX_API int acx_head_fit_group_step_ce(const float* E, int64_t ld_e, int64_t n_rows_total, const int64_t* labels, int jobs,
+                                       int64_t rows_max, int classes, double label_smoothing, const acx_fit_job* job_table,
+                                       const void* plan, int64_t n_steps, int64_t step, int32_t* status, void* ws,
+                                       size_t ws_bytes, void* stream);
+
 /* ---- reading and judging a single-label head: softmax top-k, accuracy, confusion matrix ---------------------------------------
  * Stateless, no workspace; logits (rows, classes) fp32 on the device with row stride ld >= classes.  Both calls clear *status
  * (4 bytes) on `stream` first, then run one kernel; capturable.
