@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/acx.h"
+#include "packed.h"
 
 struct acx_resampler {
     int device, orig, target, of, nf, width, max_band, per_thread;
@@ -262,7 +263,6 @@ __host__ __device__ inline int stage_h0(int T) { return (T + 8 - 4) / 4 + 1; }
 // [roff[s][i], roff[s][i+1]) (H_s,i = T_i ... as the uniform geometry).  The depthwise kernels see the stage as one tall image of
 // VIRTUAL rows: clip i starts at virtual row roff[s][i] + 3 i, and the three virtual rows after each clip are zero rows that
 // exist in no memory.  All tables live in the head of the forward's workspace and are written by one kernel per call.
-constexpr int kVarMaxClips = ACX_MAX_VARLEN_CLIPS;
 struct VarGeom {
     const long long* soff;        // [B+1] sample offsets
     const int* foff;              // [B+1] frame offsets
@@ -409,16 +409,7 @@ int launch_window_table(const int64_t* lengths, int R, int64_t window, int64_t h
 int launch_window_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
                            int reduce, float* out, hipStream_t s);
 
-// The window definition (include/acx.h), shared by windows.hip and stream.hip: windows of a recording of L samples, the start of
-// window j and the timeline steps.
-__host__ __device__ __forceinline__ long long win_count(long long L, long long W, long long H) {
-    return L <= W ? 1 : 1 + (L - W + H - 1) / H;
-}
-__host__ __device__ __forceinline__ long long win_start(long long j, long long L, long long W, long long H) {
-    const long long last = L > W ? L - W : 0;
-    return j * H < last ? j * H : last;
-}
-__host__ __device__ __forceinline__ long long win_steps(long long L, long long H) { return (L + H - 1) / H; }
+// (the window definition itself -- win_count, win_start, win_steps, win_mid, win_cover -- is packed.h's)
 
 // ---- sound event detection (segments.hip; the segment timeline in windows.hip) ---------------------------------------------
 constexpr int kSegSamples = ACX_SEGMENT_SAMPLES;

@@ -1,5 +1,7 @@
 // Device primitives shared by the libacx kernels (gfx950 only).  Every "same bits" promise between two kernels
-// rests on ONE function of this file that both sides call; acx_internal.h holds the host declarations and the launchers.
+// rests on ONE function that both sides call: the arithmetic ones are in this file, the indexing of packed batches (prefix sums,
+// owner search, window cover) is in packed.h, which the host and the CPU tests compile too.  acx_internal.h holds the host
+// declarations and the launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -233,11 +235,42 @@ __device__ __forceinline__ double event_edge(int k, int steps, double step, doub
 
 // ---- resampling (resample.hip, stream.hip) ------------------------------------------------------------------------------
 // Output n = j nf + i of phase i: the fp32 FMA chain in ascending r over the band's count taps; xs = the staged input of the
-// band's first sample, h = tap 0 of phase i (tap r at h[r nf]).  Both resample kernels call this one chain.
+// band's first sample, h = tap 0 of phase i (tap r at h[r nf]).
 __device__ __forceinline__ float res_chain(const float* xs, const float* h, int nf, int count) {
     float acc = 0.0f;
     for (int r = 0; r < count; ++r) acc = __builtin_fmaf(h[(long long)r * nf], xs[r], acc);
     return acc;
+}
+// One tile of a workgroup of kResThreads: outputs nb .. nb + nt - 1 of one clip or slot, nt <= kResThreads * per_thread.
+// load(m) is input sample m of that clip (zero outside it or past what was pushed); the tile's input span is staged through it
+// into s_in, then lane d computes output nb + d from the span and phase i's band and hands it to store(d, value).  Both resample
+// kernels form every output here: acx_resample and a stream's ring hold the same bits.
+constexpr int kResThreads = 256;
+struct ResGeom {
+    int of, nf, width, per_thread;
+};
+template <class Load, class Store>
+__device__ __forceinline__ void res_tile(const ResGeom& g, long long nb, int nt, float* s_in, const int2* __restrict__ band,
+                                         const float* __restrict__ taps, Load load, Store store) {
+    const int tid = threadIdx.x;
+    const long long jb = nb / g.nf;
+    const int ib = (int)(nb - jb * g.nf);
+    const long long lo = nb * g.of / g.nf - g.width - 1;
+    const int span = (int)((nb + nt - 1) * g.of / g.nf - lo + g.width + 2);
+    const int base_off = (int)(jb * g.of - lo);
+    for (int e = tid; e < span; e += kResThreads) s_in[e] = load(lo + e);
+    __syncthreads();
+    for (int q = 0; q < g.per_thread; ++q) {
+        const int d = q * kResThreads + tid;
+        if (d < nt) {
+            const unsigned ii = (unsigned)(ib + d);
+            const unsigned jj = ii / (unsigned)g.nf;
+            const int i = (int)(ii - jj * (unsigned)g.nf);
+            const int2 bc = band[i];
+            store(d, res_chain(s_in + (int)jj * g.of + bc.x + base_off, taps + i, g.nf, bc.y));
+        }
+    }
+    __syncthreads();
 }
 
 }  // namespace acx

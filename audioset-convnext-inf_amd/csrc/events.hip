@@ -158,19 +158,19 @@ __global__ __launch_bounds__(1024) void events_scan_kernel(long long* unit_off, 
 
 // varlen: the clips' first rows, step counts and last boundaries, from the values passed by value
 struct EvTabArgs {
-    int steps[kVarMaxClips];
+    PackedLens steps;
     double end[kVarMaxClips];      // <= 0: steps * step
-    int B;
     double step;
 };
 __global__ __launch_bounds__(kVarMaxClips) void events_table_kernel(EvTabArgs t, long long* row0, int* steps, double* end) {
+    __shared__ long long s_row0[kVarMaxClips + 1];
     const int i = threadIdx.x;
-    if (i >= t.B) return;
-    long long r = 0;
-    for (int j = 0; j < i; ++j) r += t.steps[j];
-    row0[i] = r;
-    steps[i] = t.steps[i];
-    end[i] = t.end[i] > 0.0 ? t.end[i] : (double)t.steps[i] * t.step;
+    if (i == 0) packed_prefix(t.steps.n, s_row0, [&t](int j) { return (long long)t.steps.len[j]; });
+    __syncthreads();
+    if (i >= t.steps.n) return;
+    row0[i] = s_row0[i];
+    steps[i] = t.steps.len[i];
+    end[i] = t.end[i] > 0.0 ? t.end[i] : (double)t.steps.len[i] * t.step;
 }
 
 // workspace: unit_off [units] int64 | counts [units][64] int32 | row0 [256] int64 | end [256] double | steps [256] int32
@@ -256,11 +256,9 @@ static int ev_decode_varlen(const char* who, const float* probs, int64_t ld, con
     const hipStream_t s = (hipStream_t)stream;
     char* w = static_cast<char*>(ws);
     EvTabArgs t{};
-    t.B = B; t.step = step_seconds;
-    for (int i = 0; i < B; ++i) {
-        t.steps[i] = steps[i];
-        t.end[i] = end_seconds ? end_seconds[i] : 0.0;
-    }
+    t.steps = packed_lens(steps, B);
+    t.step = step_seconds;
+    for (int i = 0; i < B; ++i) t.end[i] = end_seconds ? end_seconds[i] : 0.0;
     long long* row0 = reinterpret_cast<long long*>(w + roff);
     double* end = reinterpret_cast<double*>(w + eoff);
     int* stp = reinterpret_cast<int*>(w + soff);

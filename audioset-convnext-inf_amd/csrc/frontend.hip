@@ -39,14 +39,6 @@ struct FrontLds {
 // WIN: windows of acx_forward_windows -- frame f = frame f % T of window b = f / T, as UNIFORM, but window b's L samples start
 // at soff[b] (the window table, windows.hip) instead of b L: windows overlap and need not be evenly spaced.
 enum FrontForm : int { kFrontUniform = 0, kFrontVar = 1, kFrontWin = 2 };
-__device__ __forceinline__ int var_frame_clip(const int* __restrict__ foff, int B, long long f) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (foff[mid] <= f) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 template <FrontForm F>
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ wav, long long L, int T,
@@ -126,7 +118,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
         int t;
         const float* x;
         if (F == kFrontVar) {
-            b = var_frame_clip(foff, B, valid ? f : 0);
+            b = packed_find(foff, B, valid ? f : 0);
             t = valid ? (int)(f - foff[b]) : 0;
             x = wav + soff[b];
             Lc = soff[b + 1] - soff[b];
@@ -232,7 +224,7 @@ __global__ __launch_bounds__(256) void frames_kernel(const float* __restrict__ w
         int t;
         const float* x;
         if (F == kFrontVar) {
-            b = var_frame_clip(foff, B, f);
+            b = packed_find(foff, B, f);
             t = (int)(f - foff[b]);
             x = wav + soff[b];
             L = soff[b + 1] - soff[b];

@@ -16,7 +16,6 @@
 
 namespace acx {
 
-constexpr int kResThreads = 256;
 constexpr int kResMaxRate = 768000;
 constexpr long long kResMaxTable = 1LL << 22;           // nf * max_band floats
 constexpr size_t kResMaxLds = 56 * 1024;                // the staged input span (the prefix tables take 6 KiB more)
@@ -89,25 +88,17 @@ static float res_tap(const ResPlan& p, int i, long long k) {
 
 static long long res_out_len(const ResPlan& p, long long L) { return (p.nf * L + p.of - 1) / p.of; }
 
-struct ResClips {
-    int B;
-    int len[kVarMaxClips];
-};
-struct ResGeom {
-    int of, nf, width, per_thread;
-};
-
-// One workgroup per tile of 256 * per_thread consecutive outputs of one clip (grid-strided over every tile of the call).
-// The tile's input span, zero outside the clip, is staged in LDS; lane d of the tile computes output nb + d from it and
-// phase i's band.  Offsets of clips and tiles are prefix sums over the lengths passed by value.
-__global__ __launch_bounds__(kResThreads) void resample_kernel(ResClips a, ResGeom g, const float* __restrict__ in,
+// One workgroup per tile of 256 * per_thread consecutive outputs of one clip (grid-strided over every tile of the call), each
+// formed by res_tile from the clip's own samples.  Offsets of clips and tiles are prefix sums over the lengths passed by value.
+__global__ __launch_bounds__(kResThreads) void resample_kernel(PackedLens a, ResGeom g, const float* __restrict__ in,
                                                               float* __restrict__ out, const int2* __restrict__ band,
                                                               const float* __restrict__ taps) {
     extern __shared__ float s_in[];
     __shared__ long long s_soff[kVarMaxClips + 1], s_ooff[kVarMaxClips + 1], s_toff[kVarMaxClips + 1];
-    const int tid = threadIdx.x, B = a.B;
+    const int tid = threadIdx.x, B = a.n;
     const int T = kResThreads * g.per_thread;
-    {   // inclusive scan of (samples, outputs, tiles) per clip; slot c + 1 ends clip c
+    {   // inclusive scan of (samples, outputs, tiles) per clip; slot c + 1 ends clip c.  Every workgroup of a large launch runs
+        // this prologue, so it stays a parallel scan where the other packed calls take packed_prefix
         long long L = 0, N = 0, nt = 0;
         if (tid < B) {
             L = a.len[tid];
@@ -127,40 +118,14 @@ __global__ __launch_bounds__(kResThreads) void resample_kernel(ResClips a, ResGe
     }
     const long long tiles = s_toff[B];
     for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        int lo_c = 0, hi_c = B - 1;                      // the clip whose tiles hold t: largest c with toff[c] <= t
-        while (lo_c < hi_c) {
-            const int mid = (lo_c + hi_c + 1) >> 1;
-            if (s_toff[mid] <= t) lo_c = mid; else hi_c = mid - 1;
-        }
-        const int c = lo_c;
+        const int c = packed_find(s_toff, B, t);         // the clip whose tiles hold t
         const long long L = a.len[c];
         const long long N = s_ooff[c + 1] - s_ooff[c];
         const long long nb = (t - s_toff[c]) * T;
-        const int nt = (int)min((long long)T, N - nb);
-        const long long jb = nb / g.nf;
-        const int ib = (int)(nb - jb * g.nf);
-        const long long lo = nb * g.of / g.nf - g.width - 1;
-        const int span = (int)((nb + nt - 1) * g.of / g.nf - lo + g.width + 2);
-        const int base_off = (int)(jb * g.of - lo);
         const float* x = in + s_soff[c];
-        for (int e = tid; e < span; e += kResThreads) {
-            const long long m = lo + e;
-            s_in[e] = (m >= 0 && m < L) ? x[m] : 0.0f;
-        }
-        __syncthreads();
         float* y = out + s_ooff[c] + nb;
-        for (int q = 0; q < g.per_thread; ++q) {
-            const int d = q * kResThreads + tid;
-            if (d < nt) {
-                const unsigned ii = (unsigned)(ib + d);
-                const unsigned jj = ii / (unsigned)g.nf;
-                const int i = (int)(ii - jj * (unsigned)g.nf);
-                const int2 bc = band[i];
-                const float* xs = s_in + (int)jj * g.of + bc.x + base_off;
-                y[d] = res_chain(xs, taps + i, g.nf, bc.y);
-            }
-        }
-        __syncthreads();
+        res_tile(g, nb, (int)min((long long)T, N - nb), s_in, band, taps,
+                 [x, L](long long m) { return (m >= 0 && m < L) ? x[m] : 0.0f; }, [y](int d, float v) { y[d] = v; });
     }
 }
 
@@ -255,8 +220,6 @@ void acx_resampler_destroy(acx_resampler* rs) {
 int acx_resample(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, void* stream) {
     if (!rs || !lengths || !out) ACX_FAIL(ACX_ERR_ARG, "acx_resample: null argument");
     if (B <= 0 || B > kVarMaxClips) ACX_FAIL(ACX_ERR_ARG, "acx_resample: %d clips (expected 1 .. %d)", B, kVarMaxClips);
-    ResClips a{};
-    a.B = B;
     long long tiles = 0, samples = 0;
     const long long T = (long long)kResThreads * rs->per_thread;
     ResPlan p;
@@ -265,7 +228,6 @@ int acx_resample(const acx_resampler* rs, const float* in, const int64_t* length
     for (int i = 0; i < B; ++i) {
         if (lengths[i] < 0 || lengths[i] > 0x7fffffffLL)
             ACX_FAIL(ACX_ERR_SHAPE, "acx_resample: clip %d has %lld samples (expected 0 .. 2^31 - 1)", i, (long long)lengths[i]);
-        a.len[i] = (int)lengths[i];
         samples += lengths[i];
         tiles += (res_out_len(p, lengths[i]) + T - 1) / T;
     }
@@ -273,8 +235,8 @@ int acx_resample(const acx_resampler* rs, const float* in, const int64_t* length
     if (tiles == 0) return ACX_OK;
     const ResGeom g{rs->of, rs->nf, rs->width, rs->per_thread};
     const unsigned grid = (unsigned)std::min(tiles, 4096LL);
-    launch_kernel(&resample_kernel, dim3(grid), dim3(kResThreads), rs->lds_bytes, (hipStream_t)stream, a, g, in, out,
-                  (const int2*)rs->band, (const float*)rs->taps);
+    launch_kernel(&resample_kernel, dim3(grid), dim3(kResThreads), rs->lds_bytes, (hipStream_t)stream, packed_lens(lengths, B), g,
+                  in, out, (const int2*)rs->band, (const float*)rs->taps);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

@@ -232,45 +232,26 @@ int launch_segment_clipmax(const float* probs, int B, int S, int N, float* clip,
 // The output is one flat array of (frames x N) floats; a thread writes four consecutive ones with one 16-byte store (the array
 // starts 16-byte aligned; rows of N floats need not).  It finds (clip, frame, class) of its first element once and steps from
 // there.  VAR: packed clips, lengths by value; the frame / segment offsets of the clips are a serial prefix by one thread.
-struct SegLens {
-    int B;
-    int len[kVarMaxClips];
-};
 struct SegOffs {
     long long foff[kVarMaxClips + 1];       // first frame of clip b
     long long roff[kVarMaxClips + 1];       // first segment of clip b
 };
 
 template <bool VAR>
-__global__ __launch_bounds__(256) void segment_expand_kernel(SegLens a, const float* __restrict__ probs, int S_, int N, int T_,
+__global__ __launch_bounds__(256) void segment_expand_kernel(PackedLens a, const float* __restrict__ probs, int S_, int N, int T_,
                                                              long long total, float* __restrict__ out) {
     __shared__ SegOffs o;
     if (VAR) {
         if (threadIdx.x == 0) {
-            long long f = 0, r = 0;
-            for (int b = 0; b < a.B; ++b) {
-                o.foff[b] = f; o.roff[b] = r;
-                f += a.len[b] / kHop + 1;
-                r += seg_count(a.len[b]);
-            }
-            o.foff[a.B] = f; o.roff[a.B] = r;
+            packed_prefix(a.n, o.foff, [&a](int b) { return (long long)(a.len[b] / kHop + 1); });
+            packed_prefix(a.n, o.roff, [&a](int b) { return (long long)seg_count(a.len[b]); });
         }
         __syncthreads();
     }
     for (long long g = (blockIdx.x * 256ll + threadIdx.x) * 4; g < total; g += (long long)gridDim.x * 256 * 4) {
         const long long uf = g / N;                 // frame, counted over all clips
         int n = (int)(g - uf * N);
-        long long b;
-        if (VAR) {
-            int lo = 0, hi = a.B - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (o.foff[mid] <= uf) lo = mid; else hi = mid - 1;
-            }
-            b = lo;
-        } else {
-            b = uf / T_;
-        }
+        long long b = VAR ? packed_find(o.foff, a.n, uf) : uf / T_;
         int T = VAR ? (int)(o.foff[b + 1] - o.foff[b]) : T_;
         int S = VAR ? (int)(o.roff[b + 1] - o.roff[b]) : S_;
         long long row0 = VAR ? o.roff[b] : b * (long long)S;
@@ -287,7 +268,7 @@ __global__ __launch_bounds__(256) void segment_expand_kernel(SegLens a, const fl
                     if (++u == T) {
                         u = 0; ++b;
                         if (VAR) {
-                            if (b < a.B) { T = (int)(o.foff[b + 1] - o.foff[b]); S = (int)(o.roff[b + 1] - o.roff[b]); row0 = o.roff[b]; }
+                            if (b < a.n) { T = (int)(o.foff[b + 1] - o.foff[b]); S = (int)(o.roff[b + 1] - o.roff[b]); row0 = o.roff[b]; }
                         } else {
                             row0 += S;
                         }
@@ -303,7 +284,7 @@ __global__ __launch_bounds__(256) void segment_expand_kernel(SegLens a, const fl
     }
 }
 
-static int expand_launch(bool var, const SegLens& a, const float* probs, int S, int N, int T, long long total, float* frame,
+static int expand_launch(bool var, const PackedLens& a, const float* probs, int S, int N, int T, long long total, float* frame,
                          hipStream_t s) {
     if (reinterpret_cast<uintptr_t>(frame) & 15) ACX_FAIL(ACX_ERR_ARG, "acx_segment_expand: frame must be 16-byte aligned");
     long long blocks = (total / 4 + 255) / 256;
@@ -316,20 +297,13 @@ static int expand_launch(bool var, const SegLens& a, const float* probs, int S, 
 }
 
 int launch_segment_expand(const float* probs, int B, int S, int N, int T, float* frame, hipStream_t s) {
-    SegLens a{};
-    a.B = B;
-    return expand_launch(false, a, probs, S, N, T, (long long)B * T * N, frame, s);
+    return expand_launch(false, PackedLens{}, probs, S, N, T, (long long)B * T * N, frame, s);
 }
 
 int launch_segment_expand_varlen(const float* probs, const int64_t* lengths, int B, int N, float* frame, hipStream_t s) {
-    SegLens a{};
-    a.B = B;
-    long long frames = 0;
-    for (int b = 0; b < B; ++b) {
-        a.len[b] = (int)lengths[b];
-        frames += lengths[b] / kHop + 1;
-    }
-    return expand_launch(true, a, probs, 0, N, 0, frames * N, frame, s);
+    long long foff[kVarMaxClips + 1];
+    const long long frames = packed_prefix(B, foff, [lengths](int b) { return (long long)(lengths[b] / kHop + 1); });
+    return expand_launch(true, packed_lens(lengths, B), probs, 0, N, 0, frames * N, frame, s);
 }
 
 }  // namespace acx

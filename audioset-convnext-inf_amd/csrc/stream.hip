@@ -4,10 +4,10 @@
 // Each slot owns a mirrored 32 kHz ring of C samples: sample p sits at both p mod C and C + (p mod C) of the slot's 2C
 // region, so any span of up to C samples is contiguous at slot 2C + (s mod C) and a window goes through the unchanged uniform
 // forward by its table offset (forward_uniform with wstart, the acx_forward_windows path).  At an input rate other than
-// 32 kHz, pushes land in a per-slot input history and the outputs that became final are resampled into the ring with the
-// chain of resample_kernel (res_chain).  With a timeline, the probabilities of each forwarded window are kept in a per-slot
-// history of Hw windows, and the rows that became final are reduced from it with win_reduce, the reduction of
-// window_timeline_kernel.
+// 32 kHz, pushes land in a per-slot input history and the outputs that became final are resampled into the ring by res_tile,
+// the tile body resample_kernel calls.  With a timeline, the probabilities of each forwarded window are kept in a per-slot
+// history of Hw windows, and the rows that became final are reduced from it by the calls window_timeline_kernel makes: win_mid,
+// win_cover and win_reduce.
 //
 // The host owns every position and count (the schedule below).  Launches take them BY VALUE, in blocks of at most
 // kStrBatch slots (about 1 KiB), so a call copies nothing from the host and allocates and synchronises nothing.
@@ -144,60 +144,32 @@ struct StrRes {
     int slot[kStrBatch], nout[kStrBatch];
     long long out0[kStrBatch], in1[kStrBatch];
 };
-struct StrResGeom {
-    int of, nf, width, per_thread;
-    long long C, Ch;
-};
-
-// Outputs out0 .. out0 + nout - 1 of each entry's slot, tile by tile as resample_kernel forms them: the tile's input span,
-// zero below sample 0 and from in1 (the samples pushed) on, staged from the slot's input history; then res_chain per output,
-// written mirrored into the 32 kHz ring.
-__global__ __launch_bounds__(kStrThreads) void stream_resample_kernel(StrRes a, StrResGeom g, const float* __restrict__ hin,
-                                                                     float* __restrict__ ring, const int2* __restrict__ band,
-                                                                     const float* __restrict__ taps) {
+// Outputs out0 .. out0 + nout - 1 of each entry's slot, tile by tile through res_tile: the input comes from the slot's input
+// history of Ch samples, zero below sample 0 and from in1 (the samples pushed) on, and every output is written mirrored into
+// the slot's 32 kHz ring of C samples.
+static_assert(kStrThreads == kResThreads, "res_tile strides by kResThreads");
+__global__ __launch_bounds__(kStrThreads) void stream_resample_kernel(StrRes a, ResGeom g, long long C, long long Ch,
+                                                                     const float* __restrict__ hin, float* __restrict__ ring,
+                                                                     const int2* __restrict__ band, const float* __restrict__ taps) {
     extern __shared__ float s_in[];
     __shared__ long long s_toff[kStrBatch + 1];
-    const int tid = threadIdx.x;
     const int T = kStrThreads * g.per_thread;
-    if (tid == 0) {
-        long long t = 0;
-        for (int e = 0; e < a.n; ++e) { s_toff[e] = t; t += (a.nout[e] + T - 1) / T; }
-        s_toff[a.n] = t;
-    }
+    if (threadIdx.x == 0) packed_prefix(a.n, s_toff, [&a, T](int e) { return (long long)((a.nout[e] + T - 1) / T); });
     __syncthreads();
     const long long tiles = s_toff[a.n];
     for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        int e = 0;
-        while (e + 1 < a.n && s_toff[e + 1] <= t) ++e;
+        const int e = packed_find(s_toff, a.n, t);
         const long long nb = a.out0[e] + (t - s_toff[e]) * T;
-        const int nt = (int)min((long long)T, a.out0[e] + a.nout[e] - nb);
-        const long long jb = nb / g.nf;
-        const int ib = (int)(nb - jb * g.nf);
-        const long long lo = nb * g.of / g.nf - g.width - 1;
-        const int span = (int)((nb + nt - 1) * g.of / g.nf - lo + g.width + 2);
-        const int base_off = (int)(jb * g.of - lo);
-        const float* x = hin + (long long)a.slot[e] * g.Ch;
+        const float* x = hin + (long long)a.slot[e] * Ch;
         const long long in1 = a.in1[e];
-        for (int k = tid; k < span; k += kStrThreads) {
-            const long long m = lo + k;
-            s_in[k] = (m >= 0 && m < in1) ? x[m % g.Ch] : 0.0f;
-        }
-        __syncthreads();
-        float* y = ring + (long long)a.slot[e] * 2 * g.C;
-        for (int q = 0; q < g.per_thread; ++q) {
-            const int d = q * kStrThreads + tid;
-            if (d < nt) {
-                const unsigned ii = (unsigned)(ib + d);
-                const unsigned jj = ii / (unsigned)g.nf;
-                const int i = (int)(ii - jj * (unsigned)g.nf);
-                const int2 bc = band[i];
-                const float v = res_chain(s_in + (int)jj * g.of + bc.x + base_off, taps + i, g.nf, bc.y);
-                const long long p = (nb + d) % g.C;
-                y[p] = v;
-                y[g.C + p] = v;
-            }
-        }
-        __syncthreads();
+        float* y = ring + (long long)a.slot[e] * 2 * C;
+        res_tile(g, nb, (int)min((long long)T, a.out0[e] + a.nout[e] - nb), s_in, band, taps,
+                 [x, in1, Ch](long long m) { return (m >= 0 && m < in1) ? x[m % Ch] : 0.0f; },
+                 [y, nb, C](int d, float v) {
+                     const long long p = (nb + d) % C;
+                     y[p] = v;
+                     y[C + p] = v;
+                 });
     }
 }
 
@@ -227,27 +199,19 @@ struct StrRows {
     int slot[kStrBatch], rows[kStrBatch];
     long long k0[kStrBatch], L[kStrBatch];
 };
-// One workgroup per row (grid-stride), threads striding over the N classes: row k of entry e's slot, as window_timeline_kernel forms it,
-// over the slot's window history (window j at row j mod Hw).  L = kStrOpen while the recording is open.
+// One workgroup per row (grid-stride), threads striding over the N classes: row k of entry e's slot is reduced over the windows
+// that win_cover names, read from the slot's window history (window j at row j mod Hw).  L = kStrOpen while the recording is open.
 __global__ __launch_bounds__(kStrThreads) void stream_timeline_kernel(StrRows a, const float* __restrict__ hist, int N,
                                                                      int reduce, float* __restrict__ out) {
     __shared__ long long s_roff[kStrBatch + 1];
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int e = 0; e < a.n; ++e) { s_roff[e] = t; t += a.rows[e]; }
-        s_roff[a.n] = t;
-    }
+    if (threadIdx.x == 0) packed_prefix(a.n, s_roff, [&a](int e) { return (long long)a.rows[e]; });
     __syncthreads();
     const long long total = s_roff[a.n];
     for (long long row = blockIdx.x; row < total; row += gridDim.x) {
-        int e = 0;
-        while (e + 1 < a.n && s_roff[e + 1] <= row) ++e;
-        const long long L = a.L[e], k = a.k0[e] + (row - s_roff[e]), n = win_count(L, a.W, a.H);
-        long long m = k * a.H + a.H / 2;
-        if (m > L - 1) m = L - 1;
-        const long long j0 = m >= a.W ? (m - a.W) / a.H + 1 : 0;
-        long long j1 = j0;
-        while (j1 < n && win_start(j1, L, a.W, a.H) <= m) ++j1;
+        const int e = packed_find(s_roff, a.n, row);
+        const long long L = a.L[e];
+        long long j0, j1;
+        win_cover(win_mid(a.k0[e] + (row - s_roff[e]), a.H, L), L, a.W, a.H, &j0, &j1);
         const float* hs = hist + (long long)a.slot[e] * a.Hw * N;
         const long long Hw = a.Hw;
         for (int c = threadIdx.x; c < N; c += kStrThreads)
@@ -328,14 +292,14 @@ int check_slots(const acx_stream* st, const int* slot, int n, const char* who) {
 int launch_stream_resample(acx_stream* st, const std::vector<int>& slot, const std::vector<long long>& out0,
                            const std::vector<long long>& out1, const std::vector<long long>& in1, hipStream_t s) {
     const StrGeom& g = st->g;
-    const StrResGeom rg{g.of, g.nf, g.width, st->rs->per_thread, st->C, st->Ch};
+    const ResGeom rg{g.of, g.nf, g.width, st->rs->per_thread};
     const long long T = (long long)kStrThreads * st->rs->per_thread;
     StrRes a{};
     long long tiles = 0;
     auto flush = [&]() -> int {
         if (a.n == 0) return ACX_OK;
         launch_kernel(&stream_resample_kernel, dim3((unsigned)std::min(tiles, 4096LL)), dim3(kStrThreads), st->rs->lds_bytes, s,
-                      a, rg, (const float*)st->hin, st->ring, (const int2*)st->rs->band, (const float*)st->rs->taps);
+                      a, rg, st->C, st->Ch, (const float*)st->hin, st->ring, (const int2*)st->rs->band, (const float*)st->rs->taps);
         ACX_HIP(hipGetLastError());
         a = StrRes{};
         tiles = 0;

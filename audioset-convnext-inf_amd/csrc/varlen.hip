@@ -6,79 +6,49 @@
 
 namespace acx {
 
-struct VarTabArgs {
-    int B;
-    int len[kVarMaxClips];
-};
-
 struct VarTabOut {
     long long* soff; int* foff; int* roff[4]; int* vclip[4]; unsigned* vbits[4]; int* rclip0; int* irow[4];
     int rows[4], vrows[4], vwords[4];
 };
 
-// largest i in [0, B) with off[i] + step * i <= v (off ascending, off[0] = 0, v >= 0)
-__device__ __forceinline__ int var_find(const int* off, int step, int B, int v) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] + step * mid <= v) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(256) void varlen_tables_kernel(VarTabArgs a, VarTabOut o) {
+__global__ __launch_bounds__(256) void varlen_tables_kernel(PackedLens a, VarTabOut o) {
+    __shared__ long long s_soff[kVarMaxClips + 1];
     __shared__ int s_foff[kVarMaxClips + 1];
     __shared__ int s_roff[4][kVarMaxClips + 1];
-    __shared__ int s_len[kVarMaxClips];
-    const int B = a.B, tid = threadIdx.x;
-    for (int i = tid; i < B; i += 256) s_len[i] = a.len[i];
-    __syncthreads();
-    if (tid == 0) {                                  // B <= 256: a serial prefix is a few microseconds at most
-        int f = 0, r[4] = {0, 0, 0, 0};
-        for (int i = 0; i < B; ++i) {
-            s_foff[i] = f;
-            const int T = s_len[i] / kHop + 1;
-            f += T;
-            int h = stage_h0(T);
-            for (int s = 0; s < 4; ++s) {
-                s_roff[s][i] = r[s];
-                r[s] += h;
-                h /= 2;
-            }
-        }
-        s_foff[B] = f;
-        for (int s = 0; s < 4; ++s) s_roff[s][B] = r[s];
+    const int B = a.n, tid = threadIdx.x;
+    if (tid == 0) {                                  // B <= 256: serial prefixes are a few microseconds at most
+        packed_prefix(B, s_soff, [&a](int i) { return (long long)a.len[i]; });
+        packed_prefix(B, s_foff, [&a](int i) { return a.len[i] / kHop + 1; });
+        for (int s = 0; s < 4; ++s) packed_prefix(B, s_roff[s], [&a, s](int i) { return stage_h0(a.len[i] / kHop + 1) >> s; });
     }
     __syncthreads();
     const long long gtid = (long long)blockIdx.x * 256 + tid, gstride = (long long)gridDim.x * 256;
     if (blockIdx.x == 0) {
         for (int i = tid; i <= B; i += 256) {
-            long long so = 0;
-            for (int k = 0; k < i; ++k) so += s_len[k];
-            o.soff[i] = so;
+            o.soff[i] = s_soff[i];
             o.foff[i] = s_foff[i];
             for (int s = 0; s < 4; ++s) o.roff[s][i] = s_roff[s][i];
         }
     }
     for (int s = 0; s < 4; ++s) {
         const int* ro = s_roff[s];
-        for (long long v = gtid; v < o.vrows[s]; v += gstride) o.vclip[s][v] = var_find(ro, 3, B, (int)v);
+        for (long long v = gtid; v < o.vrows[s]; v += gstride) o.vclip[s][v] = packed_find(ro, B, v, 3);
         for (long long w = gtid; w < o.vwords[s]; w += gstride) {
             unsigned bits = 0;
             for (int j = 0; j < 32; ++j) {
                 const long long v = 32 * w + j - 32;
                 if (v < 0 || v >= o.vrows[s]) continue;
-                const int c = var_find(ro, 3, B, (int)v);
+                const int c = packed_find(ro, B, v, 3);
                 if (v - (ro[c] + 3 * c) < ro[c + 1] - ro[c]) bits |= 1u << j;
             }
             o.vbits[s][w] = bits;
         }
         if (s == 0) {
-            for (long long r = gtid; r < o.rows[0]; r += gstride) o.rclip0[r] = var_find(ro, 0, B, (int)r);
+            for (long long r = gtid; r < o.rows[0]; r += gstride) o.rclip0[r] = packed_find(ro, B, r);
         } else {
             const int* rp = s_roff[s - 1];
             for (long long r = gtid; r < o.rows[s]; r += gstride) {
-                const int c = var_find(ro, 0, B, (int)r);
+                const int c = packed_find(ro, B, r);
                 o.irow[s][r] = rp[c] + 2 * ((int)r - ro[c]);
             }
         }
@@ -135,9 +105,6 @@ int varlen_geometry(const int64_t* lengths, int B, char* ws, VarGeom* vg, size_t
 }
 
 int launch_varlen_tables(const int64_t* lengths, const VarGeom& g, hipStream_t s) {
-    VarTabArgs a{};
-    a.B = g.B;
-    for (int i = 0; i < g.B; ++i) a.len[i] = (int)lengths[i];
     VarTabOut o{};
     o.soff = const_cast<long long*>(g.soff);
     o.foff = const_cast<int*>(g.foff);
@@ -152,7 +119,7 @@ int launch_varlen_tables(const int64_t* lengths, const VarGeom& g, hipStream_t s
     long long blocks = ((long long)g.vrows[0] + 255) / 256;
     if (blocks > 256) blocks = 256;
     if (blocks < 1) blocks = 1;
-    launch_kernel(&varlen_tables_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, o);
+    launch_kernel(&varlen_tables_kernel, dim3((unsigned)blocks), dim3(256), 0, s, packed_lens(lengths, g.B), o);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

@@ -11,69 +11,42 @@
 
 namespace acx {
 
-struct WinArgs {
-    int R;
-    long long W, H;
-    int len[kVarMaxClips];
-};
-
-// largest i in [0, R) with off[i] <= v (off ascending, off[0] = 0 <= v)
-__device__ __forceinline__ int win_find(const long long* off, int R, long long v) {
-    int lo = 0, hi = R - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= v) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// Per recording: first sample, first window and (timeline) first step -- a serial prefix over R <= 256 by one thread.
-struct WinPrefix {
-    long long soff[kVarMaxClips], woff[kVarMaxClips], toff[kVarMaxClips + 1];
-};
-__device__ void win_prefix(const WinArgs& a, WinPrefix& p) {
-    if (threadIdx.x == 0) {
-        long long s = 0, w = 0, t = 0;
-        for (int r = 0; r < a.R; ++r) {
-            p.soff[r] = s; p.woff[r] = w; p.toff[r] = t;
-            s += a.len[r];
-            w += win_count(a.len[r], a.W, a.H);
-            t += win_steps(a.len[r], a.H);
-        }
-        p.toff[a.R] = t;
-    }
-    __syncthreads();
-}
+// Per recording, each kernel takes the offsets it needs -- first sample, first window (or probs row), first timeline row -- as
+// serial prefixes over R <= 256 by thread 0 (packed.h).
 
 // wstart[i] = absolute sample offset of window first + i, i < count
-__global__ __launch_bounds__(256) void window_table_kernel(WinArgs a, long long first, int count, long long* __restrict__ wstart) {
-    __shared__ WinPrefix p;
-    win_prefix(a, p);
+__global__ __launch_bounds__(256) void window_table_kernel(PackedLens a, long long W, long long H, long long first, int count,
+                                                           long long* __restrict__ wstart) {
+    __shared__ long long soff[kVarMaxClips + 1], woff[kVarMaxClips + 1];
+    if (threadIdx.x == 0) {
+        packed_prefix(a.n, soff, [&a](int r) { return (long long)a.len[r]; });
+        packed_prefix(a.n, woff, [&a, W, H](int r) { return win_count(a.len[r], W, H); });
+    }
+    __syncthreads();
     for (int i = blockIdx.x * 256 + threadIdx.x; i < count; i += gridDim.x * 256) {
         const long long g = first + i;
-        const int r = win_find(p.woff, a.R, g);
-        wstart[i] = p.soff[r] + win_start(g - p.woff[r], a.len[r], a.W, a.H);
+        const int r = packed_find(woff, a.n, g);
+        wstart[i] = soff[r] + win_start(g - woff[r], a.len[r], W, H);
     }
 }
 
 // One workgroup per timeline row (grid-stride), threads striding over the row's N classes.  Row k of recording r has the
-// midpoint m = min(k H + H / 2, L_r - 1); the windows with s_j <= m < s_j + W are a run of consecutive j: those with j H > m - W
-// (an earlier window ends at or before m) up to the last with s_j <= m (s_j does not decrease).  mean: an fp32 sum in ascending
-// j, then one division by the count; max: the largest value.
-__global__ __launch_bounds__(256) void window_timeline_kernel(WinArgs a, const float* __restrict__ probs, int N, int reduce,
-                                                              float* __restrict__ out) {
-    __shared__ WinPrefix p;
-    win_prefix(a, p);
-    const long long rows = p.toff[a.R];
+// midpoint m = win_mid(k, H, L_r) and is reduced over the windows that cover it (win_cover).  mean: an fp32 sum in ascending
+// j, then one division by the count; max: the largest value (win_reduce).
+__global__ __launch_bounds__(256) void window_timeline_kernel(PackedLens a, long long W, long long H, const float* __restrict__ probs,
+                                                              int N, int reduce, float* __restrict__ out) {
+    __shared__ long long woff[kVarMaxClips + 1], toff[kVarMaxClips + 1];
+    // every workgroup waits for its prefixes before its first row: the two run side by side, on the first lanes of two waves
+    if (threadIdx.x == 0) packed_prefix(a.n, woff, [&a, W, H](int r) { return win_count(a.len[r], W, H); });
+    if (threadIdx.x == 64) packed_prefix(a.n, toff, [&a, H](int r) { return win_steps(a.len[r], H); });
+    __syncthreads();
+    const long long rows = toff[a.n];
     for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int r = win_find(p.toff, a.R, row);
-        const long long L = a.len[r], k = row - p.toff[r], n = win_count(L, a.W, a.H);
-        long long m = k * a.H + a.H / 2;
-        if (m > L - 1) m = L - 1;
-        const long long j0 = m >= a.W ? (m - a.W) / a.H + 1 : 0;
-        long long j1 = j0;                                 // at least one window qualifies (j0 itself: j0 H <= m - W + H <= m)
-        while (j1 < n && win_start(j1, L, a.W, a.H) <= m) ++j1;
-        const float* pr = probs + p.woff[r] * N;
+        const int r = packed_find(toff, a.n, row);
+        const long long L = a.len[r];
+        long long j0, j1;
+        win_cover(win_mid(row - toff[r], H, L), L, W, H, &j0, &j1);
+        const float* pr = probs + woff[r] * N;
         for (int c = threadIdx.x; c < N; c += 256)
             out[row * N + c] = win_reduce([pr, N](long long j) { return pr + j * N; }, j0, j1 - j0, c, reduce);
     }
@@ -81,37 +54,27 @@ __global__ __launch_bounds__(256) void window_timeline_kernel(WinArgs a, const f
 
 // The timeline at segment resolution (acx_segment_timeline).  Window j of recording r holds min(W, L_r) samples and
 // S_r = seg_count(min(W, L_r)) segments of 10240 samples, the last one reaching to the window's end; probs holds the windows'
-// (S_r, N) blocks in window order.  Row k of recording r has the midpoint m = min(10240 k + 5120, L_r - 1); the windows that
-// cover it are the run of window_timeline_kernel, and each contributes the one segment min((m - s_j) / 10240, S_r - 1).
-struct SegWinPrefix {
-    long long poff[kVarMaxClips], toff[kVarMaxClips + 1];       // first probs row / first timeline row of recording r
-};
-__global__ __launch_bounds__(256) void segment_timeline_kernel(WinArgs a, const float* __restrict__ probs, int N, int reduce,
-                                                               float* __restrict__ out) {
-    __shared__ SegWinPrefix p;
-    if (threadIdx.x == 0) {
-        long long w = 0, t = 0;
-        for (int r = 0; r < a.R; ++r) {
+// (S_r, N) blocks in window order.  Row k of recording r has the midpoint m = win_mid(k, 10240, L_r); each window that covers
+// it contributes the one segment min((m - s_j) / 10240, S_r - 1).
+__host__ __device__ __forceinline__ long long seg_steps(long long L) { return (L + kSegSamples - 1) / kSegSamples; }
+__global__ __launch_bounds__(256) void segment_timeline_kernel(PackedLens a, long long W, long long H, const float* __restrict__ probs,
+                                                               int N, int reduce, float* __restrict__ out) {
+    __shared__ long long woff[kVarMaxClips + 1], toff[kVarMaxClips + 1];       // woff: the first probs row of recording r
+    if (threadIdx.x == 0)                                       // side by side, as in window_timeline_kernel
+        packed_prefix(a.n, woff, [&a, W, H](int r) {
             const long long L = a.len[r];
-            p.poff[r] = w; p.toff[r] = t;
-            w += win_count(L, a.W, a.H) * seg_count(L < a.W ? L : a.W);
-            t += (L + kSegSamples - 1) / kSegSamples;
-        }
-        p.toff[a.R] = t;
-    }
+            return win_count(L, W, H) * seg_count(L < W ? L : W);
+        });
+    if (threadIdx.x == 64) packed_prefix(a.n, toff, [&a](int r) { return seg_steps(a.len[r]); });
     __syncthreads();
-    const long long rows = p.toff[a.R];
+    const long long rows = toff[a.n];
     for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
-        const int r = win_find(p.toff, a.R, row);
-        const long long L = a.len[r], k = row - p.toff[r], n = win_count(L, a.W, a.H);
-        const int Sr = seg_count(L < a.W ? L : a.W);
-        long long m = k * kSegSamples + kSegSamples / 2;
-        if (m > L - 1) m = L - 1;
-        const long long j0 = m >= a.W ? (m - a.W) / a.H + 1 : 0;
-        long long j1 = j0;
-        while (j1 < n && win_start(j1, L, a.W, a.H) <= m) ++j1;
-        const float* pr = probs + p.poff[r] * N;
-        const long long W = a.W, H = a.H;
+        const int r = packed_find(toff, a.n, row);
+        const long long L = a.len[r], m = win_mid(row - toff[r], kSegSamples, L);
+        const int Sr = seg_count(L < W ? L : W);
+        long long j0, j1;
+        win_cover(m, L, W, H, &j0, &j1);
+        const float* pr = probs + woff[r] * N;
         auto seg_row = [pr, N, Sr, m, L, W, H](long long j) {
             long long i = (m - win_start(j, L, W, H)) / kSegSamples;
             if (i > Sr - 1) i = Sr - 1;
@@ -142,44 +105,39 @@ int window_check(const int64_t* lengths, int R, int64_t window, int64_t hop, int
     return ACX_OK;
 }
 
-static WinArgs win_args(const int64_t* lengths, int R, int64_t window, int64_t hop) {
-    WinArgs a{};
-    a.R = R; a.W = window; a.H = hop;
-    for (int r = 0; r < R; ++r) a.len[r] = (int)lengths[r];
-    return a;
-}
-
 int launch_window_table(const int64_t* lengths, int R, int64_t window, int64_t hop, int64_t first, int count, long long* wstart,
                         hipStream_t s) {
     const unsigned blocks = (unsigned)((count + 255) / 256);
-    launch_kernel(&window_table_kernel, dim3(blocks), dim3(256), 0, s, win_args(lengths, R, window, hop), (long long)first,
-                  count, wstart);
+    launch_kernel(&window_table_kernel, dim3(blocks), dim3(256), 0, s, packed_lens(lengths, R), (long long)window, (long long)hop,
+                  (long long)first, count, wstart);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+// one workgroup per timeline row, 4096 at most; `steps`: the rows of a recording of L samples
+template <class Kernel, class Steps>
+static int timeline_launch(Kernel kernel, Steps steps, const float* probs, int classes, const int64_t* lengths, int R,
+                           int64_t window, int64_t hop, int reduce, float* out, hipStream_t s) {
+    long long toff[kVarMaxClips + 1];
+    const long long rows = packed_prefix(R, toff, [&](int r) { return steps(lengths[r]); });
+    if (rows == 0) return ACX_OK;
+    const unsigned blocks = (unsigned)(rows < 4096 ? rows : 4096);
+    launch_kernel(kernel, dim3(blocks), dim3(256), 0, s, packed_lens(lengths, R), (long long)window, (long long)hop, probs, classes,
+                  reduce, out);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
 
 int launch_window_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
                            int reduce, float* out, hipStream_t s) {
-    long long rows = 0;
-    for (int r = 0; r < R; ++r) rows += win_steps(lengths[r], hop);
-    if (rows == 0) return ACX_OK;
-    const unsigned blocks = (unsigned)(rows < 4096 ? rows : 4096);
-    launch_kernel(&window_timeline_kernel, dim3(blocks), dim3(256), 0, s, win_args(lengths, R, window, hop), probs, classes, reduce,
-                  out);
-    ACX_HIP(hipGetLastError());
-    return ACX_OK;
+    return timeline_launch(&window_timeline_kernel, [hop](long long L) { return win_steps(L, hop); }, probs, classes, lengths, R,
+                           window, hop, reduce, out, s);
 }
 
 int launch_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
                             int reduce, float* out, hipStream_t s) {
-    long long rows = 0;
-    for (int r = 0; r < R; ++r) rows += (lengths[r] + kSegSamples - 1) / kSegSamples;
-    if (rows == 0) return ACX_OK;
-    const unsigned blocks = (unsigned)(rows < 4096 ? rows : 4096);
-    launch_kernel(&segment_timeline_kernel, dim3(blocks), dim3(256), 0, s, win_args(lengths, R, window, hop), probs, classes,
-                  reduce, out);
-    ACX_HIP(hipGetLastError());
-    return ACX_OK;
+    return timeline_launch(&segment_timeline_kernel, [](long long L) { return seg_steps(L); }, probs, classes, lengths, R, window,
+                           hop, reduce, out, s);
 }
 
 }  // namespace acx

@@ -287,17 +287,19 @@ def test_derived_outputs(model, L):
 
 
 def test_expand_varlen_through_the_c_abi(model):
-    lengths = [SR, 112000, 7360, 104960]
-    N = 37
-    g = torch.Generator().manual_seed(5)
-    blocks = [torch.rand(seg.segment_count(n), N, generator=g) for n in lengths]
-    probs = torch.cat(blocks).cuda()
-    frames = sum(n // 320 + 1 for n in lengths)
-    out = torch.full((frames, N), -1.0, device="cuda")
-    lens = (ctypes.c_int64 * len(lengths))(*lengths)
-    _ffi.check(_ffi.lib().acx_segment_expand_varlen(_ffi.ptr(probs), lens, len(lengths), N, _ffi.ptr(out), _ffi.stream_ptr(out.device)))
-    want = torch.cat([b[torch.from_numpy(seg.frame_to_segment(n // 320 + 1, b.shape[0]))] for b, n in zip(blocks, lengths)])
-    assert torch.equal(out.cpu(), want)
+    # the second case: a full table of 256 clips of the smallest legal lengths and one of 102080, rows that are no multiple of
+    # the 16-byte store
+    for lengths, N in (([SR, 112000, 7360, 104960], 37), ([102080 if b == 100 else 7360 + 319 * (b % 3) for b in range(256)], 3)):
+        g = torch.Generator().manual_seed(5)
+        blocks = [torch.rand(seg.segment_count(n), N, generator=g) for n in lengths]
+        probs = torch.cat(blocks).cuda()
+        frames = sum(n // 320 + 1 for n in lengths)
+        out = torch.full((frames, N), -1.0, device="cuda")
+        lens = (ctypes.c_int64 * len(lengths))(*lengths)
+        _ffi.check(_ffi.lib().acx_segment_expand_varlen(_ffi.ptr(probs), lens, len(lengths), N, _ffi.ptr(out),
+                                                        _ffi.stream_ptr(out.device)))
+        want = torch.cat([b[torch.from_numpy(seg.frame_to_segment(n // 320 + 1, b.shape[0]))] for b, n in zip(blocks, lengths)])
+        assert torch.equal(out.cpu(), want), (len(lengths), N)
 
 
 def test_sample_rate_equals_resampled_input(model):
@@ -315,6 +317,21 @@ def test_sample_rate_equals_resampled_input(model):
 
 
 # ---- 6. timeline ------------------------------------------------------------------------------------------------------------
+def timeline_want(probs, cover, reduce):
+    """The rows of seg.segment_timeline_cover reduced over probs (numpy, rows of N) as the definition says."""
+    want = np.empty((len(cover), probs.shape[1]), dtype=np.float32)
+    for k, row in enumerate(cover):
+        rows = [probs[pr] for _, _, _, pr in row]
+        if reduce == "max":
+            want[k] = np.max(np.stack(rows), axis=0)
+        else:
+            acc = np.zeros(probs.shape[1], dtype=np.float32)
+            for v in rows:                                    # fp32 sum in ascending window order
+                acc = (acc + v).astype(np.float32)
+            want[k] = acc / np.float32(len(rows))             # one fp32 division by the count
+    return want
+
+
 @pytest.mark.parametrize("hop", [L_BITS, 70000, 30720])
 def test_segment_timeline(model, hop):
     W = L_BITS
@@ -327,21 +344,34 @@ def test_segment_timeline(model, hop):
         probs = torch.cat([r["segmentwise_output"].reshape(-1, 527) for r in res]).cpu().numpy()
         got = torch.cat([r["timeline"] for r in res]).cpu().numpy()
         assert got.shape == (len(cover), 527) == (sum(-(-n // 10240) for n in lengths), 527)
-        want = np.empty_like(got)
-        for k, row in enumerate(cover):
-            rows = [probs[pr] for _, _, _, pr in row]
-            if reduce == "max":
-                want[k] = np.max(np.stack(rows), axis=0)
-            else:
-                acc = np.zeros(527, dtype=np.float32)
-                for v in rows:                                    # fp32 sum in ascending window order
-                    acc = (acc + v).astype(np.float32)
-                want[k] = acc / np.float32(len(rows))             # one fp32 division by the count
-        assert np.array_equal(got, want), (hop, reduce)
+        assert np.array_equal(got, timeline_want(probs, cover, reduce)), (hop, reduce)
     with torch.no_grad():
         none = model.forward_windows(recs, window=W / SR, hop=hop / SR, what="segment", timeline=None)
     assert all("timeline" not in r for r in none)
     assert res[1]["segmentwise_output"].shape == (1, seg.segment_count(40000), 527)
+    if hop != L_BITS:
+        return
+    # the C call on its own, over random probabilities: lengths around the window, a zero-length recording (no segment and no
+    # row: it shares both offsets with its successor) and R = 256, the most recordings one call takes.  Recordings of 1 and
+    # 7359 samples are shorter than a clip: the call refuses them, so they leave the cycle of lengths.
+    lib, W, cycle = _ffi.lib(), 7360, (0, 7360, 7361, 11040, 22097)
+    one = torch.zeros((1, 3), device="cuda")
+    for short in (1, 7359):
+        rc = lib.acx_segment_timeline(_ffi.ptr(one), 3, (ctypes.c_int64 * 2)(7360, short), 2, W, W, 0, _ffi.ptr(one), None)
+        assert rc == -4 and "recording 1" in lib.acx_last_error().decode()
+    for N in (3, 527):
+        for H in (3680, 7360):
+            for R in (1, 256):
+                lengths = [cycle[r % len(cycle)] for r in range(R)]
+                cover = seg.segment_timeline_cover(lengths, W, H)
+                blocks = sum(len(win.window_starts([n], W, H)) * seg.window_segments(n, W) for n in lengths if n)
+                probs = torch.rand((max(blocks, 1), N), generator=torch.Generator().manual_seed(N + H + R))
+                out = torch.full((max(len(cover), 1), N), -1.0, device="cuda")
+                lens = (ctypes.c_int64 * R)(*lengths)
+                for reduce in ("max", "mean"):
+                    _ffi.check(lib.acx_segment_timeline(_ffi.ptr(probs.cuda()), N, lens, R, W, H, int(reduce == "max"),
+                                                        _ffi.ptr(out), _ffi.stream_ptr(out.device)))
+                    assert np.array_equal(out[:len(cover)].cpu().numpy(), timeline_want(probs.numpy(), cover, reduce)), (N, H, R)
 
 
 # ---- 7. graph capture -------------------------------------------------------------------------------------------------------

@@ -39,10 +39,11 @@ def chunk_sizes(L, rng, max_push):
     return out
 
 
-def run_stream(st, recs, rng, max_push, close=True):
+def run_stream(st, recs, rng, max_push, close=True, lead=()):
     """Push every recording (slot i = recording i) in random chunks, all slots interleaved, then close; returns the calls'
-    dicts."""
-    plans = [chunk_sizes(r.numel(), rng, max_push) for r in recs]
+    dicts.  lead: chunk sizes per slot of the first calls, ahead of the random ones."""
+    heads = [[step[i] for step in lead] for i in range(len(recs))]
+    plans = [h + chunk_sizes(r.numel() - sum(h), rng, max_push) for h, r in zip(heads, recs)]
     offs = [0] * len(recs)
     results = []
     for step in range(max(len(p) for p in plans)):
@@ -120,7 +121,9 @@ def test_stream_resampled(sd, rate, lengths):
     model = make_model(sd)
     recs = [synth.synth_waveforms(1, L, seed=31 + i)[0].cuda() for i, L in enumerate(lengths)]
     st = model.stream(slots=len(recs), window=W / SR, hop=H / SR, sample_rate=rate, max_push=4.0)
-    results = run_stream(st, recs, random.Random(rate), 4 * rate)
+    # after one second everywhere, slot 0 is pushed a single sample while the others get a normal chunk in the same call
+    lead = [[rate] * len(recs), [1] + [rate // 2 + 7] * (len(recs) - 1)]
+    results = run_stream(st, recs, random.Random(rate), 4 * rate, lead=lead)
     check_equal(model, recs, results, rate=rate)
 
 

@@ -36,7 +36,7 @@ def timeline_ref(probs, L, W, H, reduce):
         if reduce == "max":
             rows.append(probs[js].max(dim=0).values)
         else:
-            acc = torch.zeros(527, dtype=torch.float32, device=probs.device)
+            acc = torch.zeros(probs.shape[1], dtype=torch.float32, device=probs.device)
             for j in js:
                 acc = acc + probs[j]
             rows.append(acc / torch.tensor(float(len(js)), dtype=torch.float32, device=probs.device))
@@ -150,6 +150,24 @@ def test_timeline_matches_definition(synth_sd, reduce):
             ref = timeline_ref(out[r]["clipwise_output"], L, W, H, reduce)
             assert torch.equal(out[r]["timeline"], ref), (W, H, L)
     assert "timeline" not in model.forward_windows(recs, window=0.5, timeline=None)[0]
+    # the C call on its own, over random probabilities: a zero-length recording (one window, no row: it shares its row offset
+    # with its successor), lengths around the window, and R = 256, the most recordings one call takes
+    W, cycle = 7360, (0, 1, 7359, 7360, 7361, 11040, 22097)
+    for N in (3, 527):
+        for H in (3680, 7360):
+            for R in (1, 256):
+                lengths = [cycle[r % len(cycle)] for r in range(R)]
+                counts = [len(win.window_starts([L], W, H)) for L in lengths]
+                probs = torch.rand((sum(counts), N), generator=torch.Generator().manual_seed(N + H + R))
+                rows = len(win.timeline_steps(lengths, W, H))
+                out = torch.full((max(rows, 1), N), -1.0, device="cuda")
+                lens = (ctypes.c_int64 * R)(*lengths)
+                _ffi.check(_ffi.lib().acx_window_timeline_classes(_ffi.ptr(probs.cuda()), N, lens, R, W, H, int(reduce == "max"),
+                                                                  _ffi.ptr(out), _ffi.stream_ptr(out.device)))
+                blocks = probs.split(counts)
+                ref = [timeline_ref(blocks[r], L, W, H, reduce) for r, L in enumerate(lengths) if L > 0]
+                ref = torch.cat(ref) if ref else torch.empty((0, N))
+                assert ref.shape == (rows, N) and torch.equal(out[:rows].cpu(), ref), (N, H, R)
 
 
 def test_sample_rate_equals_resample_then_windows(synth_sd):
