@@ -427,6 +427,13 @@ int launch_segment_expand_varlen(const float* probs, const int64_t* lengths, int
 int launch_segment_timeline(const float* probs, int classes, const int64_t* lengths, int R, int64_t window, int64_t hop,
                             int reduce, float* out, hipStream_t s);
 
+// ---- rows of fp32 vectors: the search and the clustering (knn.hip, kmeans.hip) ---------------------------------------------
+inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+// at most this many rows or queries per call
+constexpr long long kF32MaxRows = 1LL << 30;
+// x non-null and 16-byte aligned, dim a multiple of 4 in 4 .. ACX_KNN_MAX_DIM, ld a multiple of 4 and at least dim (knn.hip)
+int check_f32_rows(const char* who, const char* name, const float* x, int64_t ld, int dim);
+
 // ---- host code shared by api.hip, weights.hip, forward.hip and stream.hip ------------------------------------------------
 // bf16 activations in HBM for the stages that keep them (ACX_PREC_BF16_ACT, stages 0-2)
 inline bool act_bf16(const acx_ctx* c, int stage) { return c->precision == ACX_PREC_BF16_ACT && stage >= 0 && stage < 3; }

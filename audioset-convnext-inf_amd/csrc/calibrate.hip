@@ -180,7 +180,7 @@ __global__ __launch_bounds__(kRowThreads) void toplabel_row_kernel(TopRowP p) {
     for (int c = t; c < p.N; c += W) {                             // thread t touches zs[t + k W] only, here and below
         const float v = bf * z[c];
         zs[c] = v;
-        bad |= !(fabsf(v) <= 3.4028234664e38f);
+        bad |= acx_nonfinite(v);
         const knn_key key = knn_make_key(v, c);
         best = key > best ? key : best;
     }
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(kRowThreads) void temperature_eval_kernel(TempEvalP
         float mx = -INFINITY, mn = INFINITY;
         for (int c = t; c < p.N; c += W) {
             const float v = z[c];
-            bad |= !(fabsf(v) <= 3.4028234664e38f);
+            bad |= acx_nonfinite(v);
             mx = fmaxf(mx, v);
             mn = fminf(mn, v);
         }

@@ -54,7 +54,6 @@ __device__ __forceinline__ int group_sum_int(int v, int* red) {
     }
     return v;
 }
-__device__ __forceinline__ bool cls_nonfinite(float v) { return !(fabsf(v) <= 3.4028234664e38f); }
 
 struct SoftTopkP {
     const float* z; long long ld; long long rows; int N; int k;
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(kClsThreads) void softmax_topk_kernel(SoftTopkP p) 
     int* ti = p.top_index + row * p.k;
     float* tp = p.top_prob + row * p.k;
     bool bad = false;
-    for (int c = t; c < p.N; c += W) bad |= cls_nonfinite(z[c]);
+    for (int c = t; c < p.N; c += W) bad |= acx_nonfinite(z[c]);
     if (group_any<W>(bad)) {                                       // the same answer in every thread of the group
         const float nan = __uint_as_float(0x7fc00000u);
         if (pr)
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(kClsThreads) void class_counts_kernel(ClassCountsP 
         int rank = 0;
         for (int c = t; c < p.N; c += W) {
             const float v = z[c];
-            bad |= cls_nonfinite(v);
+            bad |= acx_nonfinite(v);
             const knn_key key = knn_make_key(v, c);
             best = key > best ? key : best;
             rank += (v > zy || (v == zy && c < y)) ? 1 : 0;

@@ -72,7 +72,12 @@ __device__ __forceinline__ T wave_sum(T v) {
 // The partial results of a workgroup's four waves, added in wave order.
 __device__ __forceinline__ float sum4(float w0, float w1, float w2, float w3) { return ((w0 + w1) + w2) + w3; }
 
-// ---- one total order on (fp32 score, index) pairs (knn.hip, classify.hip) ---------------------------------------------------
+// ---- finite or not ----------------------------------------------------------------------------------------------------------
+// NaN or an infinity (the largest finite float is the only bound: no fast-math assumption can fold the comparison away)
+constexpr float kF32Max = 3.4028234664e38f;
+__device__ __forceinline__ bool acx_nonfinite(float v) { return !(fabsf(v) <= kF32Max); }
+
+// ---- one total order on (fp32 score, index) pairs (knn.hip, classify.hip, kmeans.hip) ---------------------------------------
 // ONE 64-bit key per pair: the order-preserving image of the score (-0.0 taken as +0.0) in the high word, the complemented
 // index in the low word.  Larger key = score descending, then index ascending; no two keys are equal.  Key 0 is "no
 // candidate" (no finite score and index < 2^30 maps to it).
@@ -141,7 +146,7 @@ __device__ __forceinline__ void soft_row_stats(const float* z, int N, float* red
     s = group_sum<W>(sm, red);
 }
 
-// ---- S x S tiles on the f32-input matrix cores (head_fit.hip, segments.hip, knn.hip) ---------------------------------------
+// ---- S x S tiles on the f32-input matrix cores (head_fit.hip, segments.hip, knn.hip, kmeans.hip) ----------------------------
 // Lane = (column r = lane % S, lane group h = lane / S); accumulator register i of lane group h holds row row(i, h).
 template <int S> struct F32Tile;
 template <> struct F32Tile<32> {
@@ -169,6 +174,74 @@ template <int N>
 __device__ __forceinline__ float tile_sum4(const float (&red)[4][N], int e) {
     return sum4(red[0][e], red[1][e], red[2][e], red[3][e]);
 }
+
+// ---- the fp32 dot-product tile of the search and the clustering (knn.hip, kmeans.hip) --------------------------------------
+// The fp32 dot products of 32 QT rows a with 64 rows b, whole in one wave: acc[t][u] <- the 32 x 32 tile of rows a[t] against
+// rows b[u] (knn_search_kernel: queries x database rows; kmeans_assign_kernel: rows x centres).  Lane (r, h) passes ITS rows'
+// first elements; rows of `dim` floats, dim a multiple of 4, 16-byte aligned.
+// The bit contract: the contraction runs over `dim` in groups of 16 columns, eight MFMAs per operand pair each, lane half h
+// taking columns 8 h .. 8 h + 7 of the group in ascending order; the last group of a dim that is no multiple of 16 loads zeros
+// past dim.  The order is a function of `dim` alone -- not of the pair's place in its tile, of QT, or of the caller -- so one
+// (a row, b row) pair has the same bits in every kernel that calls this, whatever the shapes of the call.
+// each_b(b0, b1) sees a group's b operand registers (b0[u], b1[u]: columns 8 h .. + 3 and 8 h + 4 .. + 7 of row b[u]) before
+// the group's MFMAs: k-means sums the centres' squares there.
+__device__ __forceinline__ float4 dot_load4(const float* p, bool on) {
+    return on ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+template <int QT, class EachB>
+__device__ __forceinline__ void dot_tile(F32Tile<32>::acc_t (&acc)[QT][2], const float* const (&a)[QT], const float* const (&b)[2],
+                                         int dim, int h, EachB each_b) {
+#pragma unroll
+    for (int t = 0; t < QT; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) acc[t][u] = F32Tile<32>::acc_t(0.f);
+    auto group = [&](int col, bool on0, bool on1) {          // col: the group's first column
+        float4 a0[QT], a1[QT], b0[2], b1[2];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            a0[t] = dot_load4(a[t] + 8 * h + col, on0);
+            a1[t] = dot_load4(a[t] + 8 * h + col + 4, on1);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            b0[u] = dot_load4(b[u] + 8 * h + col, on0);
+            b1[u] = dot_load4(b[u] + 8 * h + col + 4, on1);
+        }
+        each_b(b0, b1);
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+#pragma unroll
+            for (int t = 0; t < QT; ++t)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    acc[t][u] = F32Tile<32>::mfma(c < 4 ? a0[t][c] : a1[t][c - 4], c < 4 ? b0[u][c] : b1[u][c - 4], acc[t][u]);
+    };
+    const int full = dim >> 4, rem = dim & 15;
+    for (int kb = 0; kb < full; ++kb) group(kb * 16, true, true);
+    if (rem) group(full * 16, rem >= 4 + 8 * h, rem >= 8 + 8 * h);      // the last 4, 8 or 12 columns
+}
+// A cosine score from a raw dot product and the two inverse norms: two roundings, in this order, never contracted
+__device__ __forceinline__ float cos_scale(float acc, float ra, float rb) {
+#pragma clang fp contract(off)
+    return (acc * ra) * rb;
+}
+// This lane's share of sum x^2 of a row of `dim` floats: its 16-byte chunks lane, lane + 64, ... by four FMAs each in component
+// order; wave_sum of it is the row's sum.  each(v) sees every chunk the lane loaded.
+template <class Each>
+__device__ __forceinline__ float row_sumsq(const float* x, int dim, int lane, Each each) {
+    float s = 0.f;
+    for (int k = lane * 4; k < dim; k += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(x + k);
+        s = __builtin_fmaf(v.x, v.x, s);
+        s = __builtin_fmaf(v.y, v.y, s);
+        s = __builtin_fmaf(v.z, v.z, s);
+        s = __builtin_fmaf(v.w, v.w, s);
+        each(v);
+    }
+    return s;
+}
+// 1 / |x| from sum x^2; 0 for a zero row
+__device__ __forceinline__ float inv_norm_of(float sumsq) { return sumsq > 0.f ? 1.0f / sqrtf(sumsq) : 0.f; }
 
 // ---- the head (misc.hip: pool_head_kernel, head_tiled_kernel; segments.hip) ------------------------------------------------
 // One lane's share of a head row's dot product with an embedding: lane l holds chunks l, l + 64, l + 128 of both, 12 fmaf in

@@ -1,12 +1,12 @@
 // K-means over embeddings (acx_kmeans_* in include/acx.h): Lloyd iterations with k-means++ seeding, everything on the device.
 //
 //   kmeans_assign_kernel    a workgroup owns 64 rows and streams all K centres, 256 per step: each of the four waves forms the
-//                           64 x 64 tile of dot products of its 64 centres on the f32 matrix cores (v_mfma_f32_32x32x2_f32, the
-//                           contraction order of knn_search_kernel: 16 columns per group of eight MFMAs, the lane halves on
-//                           columns 0-7 and 8-15, zeros past dim in the tail group) and sums c^2 of its centres from the same
-//                           operand registers.  score = fma(-2, dot, cc) (cosine: -dot).  Every accumulator register keeps ONE
-//                           running key knn_make_key(-score, k): lowest score, then lowest centre index, -0.0 as +0.0.  The keys
-//                           of a row are joined by lane shuffles and through LDS by max -- a total order, so the label does not
+//                           64 x 64 tile of dot products of its 64 centres on the f32 matrix cores by dot_tile
+//                           (device_common.h, which states the bit contract: the function knn_search_kernel calls, so a
+//                           pair's dot product has the search's bits) and sums c^2 of its centres from the same operand
+//                           registers.  score = fma(-2, dot, cc) (cosine: -dot).  Every accumulator register keeps ONE running
+//                           key knn_make_key(-score, k): lowest score, then lowest centre index, -0.0 as +0.0.  The keys of a
+//                           row are joined by lane shuffles and through LDS by max -- a total order, so the label does not
 //                           depend on how the centres arrived.  The n x K scores never go to memory.
 //   kmeans_hist / scan / scatter   the stable partition of the row indices by label: histograms per block of rows, exclusive
 //                           sums, and a scatter by one wave per block that keeps ascending row order inside a cluster.
@@ -31,11 +31,9 @@ namespace acx {
 constexpr int kKmThreads = 256;
 constexpr int kKmTileRows = 64;              // rows per workgroup of the assignment
 constexpr int kKmStepCentres = 256;          // centres per step: four waves x 64
-constexpr long long kKmMaxRows = 1LL << 30;
 constexpr int kKmMaxBlocks = 1024;           // row blocks of the partition and of the sampler
 constexpr int kKmBlockRows = 1024;           // their least height
 constexpr int kKmDistRows = 16;              // rows per wave of the seeding distance pass
-constexpr float kKmFltMax = 3.4028234664e38f;
 
 enum { KM_ALWAYS = 0, KM_UNLESS_DONE = 1, KM_IF_MOVED = 2 };
 
@@ -81,9 +79,7 @@ __global__ __launch_bounds__(kKmThreads, 2) void kmeans_assign_kernel(KmAssignP 
     // rows past n / centres past K repeat the last valid one: loads stay inside the buffers, results are dropped
     const float* xa[QT];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) xa[t] = p.x + min(i0 + 32 * t + r32, p.n - 1) * p.ld_x + 8 * h;
-    const int full = p.dim >> 4, rem = p.dim & 15;
-    const bool tail0 = rem >= 4 + 8 * h, tail1 = rem >= 8 + 8 * h;
+    for (int t = 0; t < QT; ++t) xa[t] = p.x + min(i0 + 32 * t + r32, p.n - 1) * p.ld_x;
     bool bad = false;
     knn_key best[QT][16];
 #pragma unroll
@@ -96,65 +92,21 @@ __global__ __launch_bounds__(kKmThreads, 2) void kmeans_assign_kernel(KmAssignP 
         if (kw >= p.K) break;                        // wave-uniform; no barrier inside the loop
         const float* cb[2];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) cb[u] = p.c + (long long)min(kw + 32 * u + r32, p.K - 1) * p.ld_c + 8 * h;
+        for (int u = 0; u < 2; ++u) cb[u] = p.c + (long long)min(kw + 32 * u + r32, p.K - 1) * p.ld_c;
         F32Tile<32>::acc_t acc[QT][2];
-#pragma unroll
-        for (int t = 0; t < QT; ++t)
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[t][u][i] = 0.f;
-        float cs0 = 0.f, cs1 = 0.f;                  // this lane half's share of sum c^2 of its two centres, in column order
-        const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#define KM_MFMA(A, B, C)                                                                                       \
-    _Pragma("unroll") for (int t = 0; t < QT; ++t) _Pragma("unroll") for (int u = 0; u < 2; ++u)               \
-        acc[t][u] = F32Tile<32>::mfma(A[t].C, B[u].C, acc[t][u]);
-#define KM_GROUP                                                                            \
-    KM_MFMA(a0, b0, x) KM_MFMA(a0, b0, y) KM_MFMA(a0, b0, z) KM_MFMA(a0, b0, w)             \
-    KM_MFMA(a1, b1, x) KM_MFMA(a1, b1, y) KM_MFMA(a1, b1, z) KM_MFMA(a1, b1, w)
-#define KM_SQ1(S, U)                                                                                              \
-    S = __builtin_fmaf(b0[U].x, b0[U].x, S); S = __builtin_fmaf(b0[U].y, b0[U].y, S);                             \
-    S = __builtin_fmaf(b0[U].z, b0[U].z, S); S = __builtin_fmaf(b0[U].w, b0[U].w, S);                             \
-    S = __builtin_fmaf(b1[U].x, b1[U].x, S); S = __builtin_fmaf(b1[U].y, b1[U].y, S);                             \
-    S = __builtin_fmaf(b1[U].z, b1[U].z, S); S = __builtin_fmaf(b1[U].w, b1[U].w, S);
-#define KM_SQUARES KM_SQ1(cs0, 0) KM_SQ1(cs1, 1)
-        float4 a0[QT], a1[QT], b0[2], b1[2];
-        for (int kb = 0; kb < full; ++kb) {
-#pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                a0[t] = *reinterpret_cast<const float4*>(xa[t] + kb * 16);
-                a1[t] = *reinterpret_cast<const float4*>(xa[t] + kb * 16 + 4);
-            }
+        float cs[2] = {0.f, 0.f};                    // this lane half's share of sum c^2 of its two centres, in column order
+        dot_tile<QT>(acc, xa, cb, p.dim, h, [&](const float4 (&b0)[2], const float4 (&b1)[2]) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                b0[u] = *reinterpret_cast<const float4*>(cb[u] + kb * 16);
-                b1[u] = *reinterpret_cast<const float4*>(cb[u] + kb * 16 + 4);
-            }
-            KM_SQUARES
-            KM_GROUP
-        }
-        if (rem) {                                   // the last 4, 8 or 12 columns: the lane halves past dim contribute zeros
 #pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                a0[t] = tail0 ? *reinterpret_cast<const float4*>(xa[t] + full * 16) : zero4;
-                a1[t] = tail1 ? *reinterpret_cast<const float4*>(xa[t] + full * 16 + 4) : zero4;
-            }
+                for (int c = 0; c < 4; ++c) cs[u] = __builtin_fmaf(b0[u][c], b0[u][c], cs[u]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                b0[u] = tail0 ? *reinterpret_cast<const float4*>(cb[u] + full * 16) : zero4;
-                b1[u] = tail1 ? *reinterpret_cast<const float4*>(cb[u] + full * 16 + 4) : zero4;
+                for (int c = 0; c < 4; ++c) cs[u] = __builtin_fmaf(b1[u][c], b1[u][c], cs[u]);
             }
-            KM_SQUARES
-            KM_GROUP
-        }
-#undef KM_SQUARES
-#undef KM_SQ1
-#undef KM_GROUP
-#undef KM_MFMA
+        });
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const float ch = u ? cs1 : cs0;
-            const float cc = ch + __shfl_xor(ch, 32);            // the two halves of the centre's row: a + b = b + a
+            const float cc = cs[u] + __shfl_xor(cs[u], 32);           // the two halves of the centre's row: a + b = b + a
             const int k = kw + 32 * u + r32;
             if (k < p.K) {
 #pragma unroll
@@ -163,7 +115,7 @@ __global__ __launch_bounds__(kKmThreads, 2) void kmeans_assign_kernel(KmAssignP 
                     for (int i = 0; i < 16; ++i) {
                         const float a = acc[t][u][i];
                         const float s = p.cosine ? -a : __builtin_fmaf(-2.f, a, cc);
-                        if (i0 + 32 * t + F32Tile<32>::row(i, h) < p.n && !(fabsf(s) <= kKmFltMax)) bad = true;
+                        if (i0 + 32 * t + F32Tile<32>::row(i, h) < p.n && acx_nonfinite(s)) bad = true;
                         const knn_key key = knn_make_key(-s, k);
                         best[t][i] = key > best[t][i] ? key : best[t][i];
                     }
@@ -193,8 +145,7 @@ __global__ __launch_bounds__(kKmThreads, 2) void kmeans_assign_kernel(KmAssignP 
 #pragma unroll
             for (int w = 1; w < 4; ++w) v = s_best[w][tid] > v ? s_best[w][tid] : v;
             const float score = 0.f - knn_key_score(v);          // -0.0 never leaves
-            const bool fin = fabsf(score) <= kKmFltMax;
-            const int label = fin ? knn_key_index(v) : -1;
+            const int label = acx_nonfinite(score) ? -1 : knn_key_index(v);
             chg = p.prev ? (p.prev[row] != label) : 1;
             p.labels[row] = label;
             p.scores[row] = score;
@@ -245,13 +196,12 @@ __global__ __launch_bounds__(256) void kmeans_poison_kernel(int* labels, long lo
 
 // ---- the centre update -----------------------------------------------------------------------------------------------------
 struct KmPart { int nb; long long rpb; };
-static long long km_cdiv(long long a, long long b) { return (a + b - 1) / b; }
-static int km_max_blocks(long long n) { return (int)std::min<long long>(kKmMaxBlocks, km_cdiv(n, kKmBlockRows)); }
+static int km_max_blocks(long long n) { return (int)std::min<long long>(kKmMaxBlocks, cdiv(n, kKmBlockRows)); }
 // row blocks of n rows: at most km_max_blocks(n) blocks of rpb rows
 static KmPart km_part(long long n) {
     KmPart pt;
-    pt.rpb = km_cdiv(n, km_max_blocks(n));
-    pt.nb = (int)km_cdiv(n, pt.rpb);
+    pt.rpb = cdiv(n, km_max_blocks(n));
+    pt.nb = (int)cdiv(n, pt.rpb);
     return pt;
 }
 
@@ -451,21 +401,20 @@ __global__ __launch_bounds__(256) void kmeans_mindist_kernel(const float* __rest
     const int lane = threadIdx.x & 63;
     const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pick) c = x + (long long)min(max(*pick, 0), (int)(n - 1)) * ld;
+    const float rc = cosine ? inv_norm_of(wave_sum(row_sumsq(c, dim, lane, [](const float4&) {}))) : 0.f;
     float mx = 0.f;
     bool bad = false;
     for (int r = 0; r < kKmDistRows; ++r) {
         const long long row = wv * kKmDistRows + r;
         if (row >= n) break;
         const float* xr = x + row * ld;
-        float s = 0.f, q = 0.f;
+        float s = 0.f;
         for (int k = lane * 4; k < dim; k += 256) {
             const float4 v = *reinterpret_cast<const float4*>(xr + k);
             const float4 w = *reinterpret_cast<const float4*>(c + k);
             if (cosine) {
                 s = __builtin_fmaf(v.x, w.x, s); s = __builtin_fmaf(v.y, w.y, s);
                 s = __builtin_fmaf(v.z, w.z, s); s = __builtin_fmaf(v.w, w.w, s);
-                q = __builtin_fmaf(w.x, w.x, q); q = __builtin_fmaf(w.y, w.y, q);
-                q = __builtin_fmaf(w.z, w.z, q); q = __builtin_fmaf(w.w, w.w, q);
             } else {
                 const float t0 = v.x - w.x, t1 = v.y - w.y, t2 = v.z - w.z, t3 = v.w - w.w;
                 s = __builtin_fmaf(t0, t0, s); s = __builtin_fmaf(t1, t1, s);
@@ -474,17 +423,8 @@ __global__ __launch_bounds__(256) void kmeans_mindist_kernel(const float* __rest
         }
         s = wave_sum(s);
         float dist = s;
-        if (cosine) {
-            q = wave_sum(q);
-            const float rc = q > 0.f ? 1.0f / sqrtf(q) : 0.f;
-            float cs;
-            {
-#pragma clang fp contract(off)
-                cs = (s * rx[row]) * rc;
-            }
-            dist = fmaxf(__builtin_fmaf(-2.f, cs, 2.f), 0.f);
-        }
-        if (!(dist <= kKmFltMax)) bad = true;
+        if (cosine) dist = fmaxf(__builtin_fmaf(-2.f, cos_scale(s, rx[row], rc), 2.f), 0.f);
+        if (!(dist <= kF32Max)) bad = true;
         const float nd = first ? dist : fminf(d[row], dist);
         if (lane == 0) d[row] = nd;
         mx = fmaxf(mx, nd);
@@ -500,7 +440,7 @@ __device__ __forceinline__ unsigned long long km_quant(float d, int sh) {
 }
 __device__ __forceinline__ int km_shift_of(unsigned dmax_bits) {
     const float m = __uint_as_float(dmax_bits);
-    return (m > 0.f && m <= kKmFltMax) ? 30 - ilogbf(m) : 0;
+    return (m > 0.f && m <= kF32Max) ? 30 - ilogbf(m) : 0;
 }
 
 __global__ __launch_bounds__(256) void kmeans_bsum_kernel(const float* __restrict__ d, long long n, long long rpb,
@@ -598,21 +538,11 @@ __global__ __launch_bounds__(256) void kmeans_gather_kernel(const float* __restr
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-static int km_check_rows(const char* who, const char* name, const float* x, int64_t ld, int dim) {
-    if (!x) ACX_FAIL(ACX_ERR_ARG, "%s: %s is null", who, name);
-    if (dim < 4 || dim > ACX_KNN_MAX_DIM || (dim & 3))
-        ACX_FAIL(ACX_ERR_ARG, "%s: dim = %d (expected a multiple of 4 in 4 .. %d)", who, dim, ACX_KNN_MAX_DIM);
-    if (ld < dim || (ld & 3))
-        ACX_FAIL(ACX_ERR_ARG, "%s: row stride of %s = %lld (expected a multiple of 4, at least dim = %d)", who, name, (long long)ld, dim);
-    if (reinterpret_cast<uintptr_t>(x) & 15) ACX_FAIL(ACX_ERR_ARG, "%s: %s is not 16-byte aligned", who, name);
-    return ACX_OK;
-}
-
 static int km_check_shape(const char* who, int64_t n, int clusters, bool need_k_le_n = true) {
     if (n < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n = %lld (expected >= 1)", who, (long long)n);
     if (clusters < 1 || clusters > ACX_KMEANS_MAX_CLUSTERS)
         ACX_FAIL(ACX_ERR_ARG, "%s: clusters = %d (expected 1 .. %d)", who, clusters, ACX_KMEANS_MAX_CLUSTERS);
-    if (n > kKmMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
+    if (n > kF32MaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
     if (need_k_le_n && clusters > n) ACX_FAIL(ACX_ERR_ARG, "%s: clusters = %d exceeds the %lld rows", who, clusters, (long long)n);
     return ACX_OK;
 }
@@ -654,7 +584,7 @@ static void km_launch_assign(const KmData& v, const int* prev, int* labels, floa
     KmAssignP p;
     p.x = v.x; p.ld_x = v.ld_x; p.n = v.n; p.c = v.c; p.ld_c = v.ld_c; p.K = v.K; p.dim = v.dim; p.cosine = v.cosine;
     p.prev = prev; p.labels = labels; p.scores = scores; p.changed = changed; p.status = status; p.st = st; p.gate = gate;
-    launch_kernel(&kmeans_assign_kernel, dim3((unsigned)km_cdiv(v.n, kKmTileRows)), dim3(kKmThreads), 0, s, p);
+    launch_kernel(&kmeans_assign_kernel, dim3((unsigned)cdiv(v.n, kKmTileRows)), dim3(kKmThreads), 0, s, p);
 }
 
 static int km_bits(int K) {
@@ -685,7 +615,7 @@ static void km_launch_update(const KmData& v, const int* labels, int* counts, ch
 
 static void km_launch_mindist(const KmData& v, const float* c, const int* pick, int first, float* d, unsigned* dmax, int* status,
                               hipStream_t s) {
-    launch_kernel(&kmeans_mindist_kernel, dim3((unsigned)km_cdiv(v.n, 4 * kKmDistRows)), dim3(256), 0, s, v.x, v.ld_x, v.rx, v.n, v.dim,
+    launch_kernel(&kmeans_mindist_kernel, dim3((unsigned)cdiv(v.n, 4 * kKmDistRows)), dim3(256), 0, s, v.x, v.ld_x, v.rx, v.n, v.dim,
                   v.cosine, c, pick, first, d, dmax, status);
 }
 
@@ -719,8 +649,8 @@ int acx_kmeans_assign(const float* x, int64_t ld_x, const float* x_inv_norm, int
     static const char* who = "acx_kmeans_assign";
     ACX_TRY(km_check_shape(who, n, clusters, false));
     ACX_TRY(km_check_metric(who, metric, x_inv_norm));
-    ACX_TRY(km_check_rows(who, "x", x, ld_x, dim));
-    ACX_TRY(km_check_rows(who, "centers", centers, ld_c, dim));
+    ACX_TRY(check_f32_rows(who, "x", x, ld_x, dim));
+    ACX_TRY(check_f32_rows(who, "centers", centers, ld_c, dim));
     if (!labels || !scores) ACX_FAIL(ACX_ERR_ARG, "%s: labels / scores is null", who);
     if (!changed) ACX_FAIL(ACX_ERR_ARG, "%s: changed is null", who);
     if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
@@ -739,8 +669,8 @@ int acx_kmeans_update(const float* x, int64_t ld_x, const float* x_inv_norm, int
     static const char* who = "acx_kmeans_update";
     ACX_TRY(km_check_shape(who, n, clusters, false));
     ACX_TRY(km_check_metric(who, metric, x_inv_norm));
-    ACX_TRY(km_check_rows(who, "x", x, ld_x, dim));
-    ACX_TRY(km_check_rows(who, "centers", centers, ld_c, dim));
+    ACX_TRY(check_f32_rows(who, "x", x, ld_x, dim));
+    ACX_TRY(check_f32_rows(who, "centers", centers, ld_c, dim));
     if (!labels) ACX_FAIL(ACX_ERR_ARG, "%s: labels is null", who);
     if (!counts || !shift) ACX_FAIL(ACX_ERR_ARG, "%s: counts / shift is null", who);
     if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
@@ -763,8 +693,8 @@ int acx_kmeans_fit(const float* x, int64_t ld_x, const float* x_inv_norm, int64_
     static const char* who = "acx_kmeans_fit";
     ACX_TRY(km_check_shape(who, n, clusters));
     ACX_TRY(km_check_metric(who, metric, x_inv_norm));
-    ACX_TRY(km_check_rows(who, "x", x, ld_x, dim));
-    ACX_TRY(km_check_rows(who, "centers", centers, ld_c, dim));
+    ACX_TRY(check_f32_rows(who, "x", x, ld_x, dim));
+    ACX_TRY(check_f32_rows(who, "centers", centers, ld_c, dim));
     if (max_iter < 1 || max_iter > ACX_KMEANS_MAX_ITER)
         ACX_FAIL(ACX_ERR_ARG, "%s: max_iter = %d (expected 1 .. %d)", who, max_iter, ACX_KMEANS_MAX_ITER);
     if (!tol_abs) ACX_FAIL(ACX_ERR_ARG, "%s: tol_abs is null", who);
@@ -787,7 +717,7 @@ int acx_kmeans_fit(const float* x, int64_t ld_x, const float* x_inv_norm, int64_
     ACX_HIP(hipMemsetAsync(state, 0, sizeof(acx_kmeans_state), s));
     ACX_HIP(hipMemsetAsync(changed, 0, 2 * sizeof(int), s));
     ACX_HIP(hipMemsetAsync(labels, 0xff, (size_t)n * sizeof(int32_t), s));       // every row counts as changed in iteration 1
-    if (!cosine) launch_kernel(&kmeans_rowsq_kernel, dim3((unsigned)km_cdiv(n, 4)), dim3(256), 0, s, x, (long long)ld_x, (long long)n, dim, xx);
+    if (!cosine) launch_kernel(&kmeans_rowsq_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, s, x, (long long)ld_x, (long long)n, dim, xx);
     for (int it = 0; it < max_iter; ++it) {
         km_launch_assign(v, (const int*)labels, (int*)labels, scores, changed, (int*)status, state, KM_UNLESS_DONE, s);
         km_launch_update(v, (const int*)labels, (int*)counts, base, w, (int*)status, 0, true, state, KM_UNLESS_DONE, s);
@@ -795,7 +725,7 @@ int acx_kmeans_fit(const float* x, int64_t ld_x, const float* x_inv_norm, int64_
     }
     // labels, counts and inertia belong to the returned centres: one more assignment if the last update moved a centre
     km_launch_assign(v, (const int*)labels, (int*)labels, scores, changed + 1, (int*)status, state, KM_IF_MOVED, s);
-    launch_kernel(&kmeans_poison_kernel, dim3((unsigned)std::min<long long>(km_cdiv(n, 256), 1024)), dim3(256), 0, s, (int*)labels,
+    launch_kernel(&kmeans_poison_kernel, dim3((unsigned)std::min<long long>(cdiv(n, 256), 1024)), dim3(256), 0, s, (int*)labels,
                   (long long)n, (const int*)status);
     km_launch_update(v, (const int*)labels, (int*)counts, base, w, (int*)status, 0, false, nullptr, KM_ALWAYS, s);
     launch_kernel(&kmeans_inertia_kernel, dim3(1), dim3(1024), 0, s, (const float*)scores, (const double*)xx, x_inv_norm, (long long)n,
@@ -809,8 +739,8 @@ int acx_kmeans_min_distance(const float* x, int64_t ld_x, const float* x_inv_nor
     static const char* who = "acx_kmeans_min_distance";
     ACX_TRY(km_check_shape(who, n, 1));
     ACX_TRY(km_check_metric(who, metric, x_inv_norm));
-    ACX_TRY(km_check_rows(who, "x", x, ld_x, dim));
-    ACX_TRY(km_check_rows(who, "center", center, dim, dim));
+    ACX_TRY(check_f32_rows(who, "x", x, ld_x, dim));
+    ACX_TRY(check_f32_rows(who, "center", center, dim, dim));
     if (!d || !d_max) ACX_FAIL(ACX_ERR_ARG, "%s: d / d_max is null", who);
     if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
     hipStream_t s = (hipStream_t)stream;
@@ -847,8 +777,8 @@ int acx_kmeans_seed(const float* x, int64_t ld_x, const float* x_inv_norm, int64
     static const char* who = "acx_kmeans_seed";
     ACX_TRY(km_check_shape(who, n, clusters));
     ACX_TRY(km_check_metric(who, metric, x_inv_norm));
-    ACX_TRY(km_check_rows(who, "x", x, ld_x, dim));
-    ACX_TRY(km_check_rows(who, "centers", centers, ld_c, dim));
+    ACX_TRY(check_f32_rows(who, "x", x, ld_x, dim));
+    ACX_TRY(check_f32_rows(who, "centers", centers, ld_c, dim));
     if (!u) ACX_FAIL(ACX_ERR_ARG, "%s: u is null", who);
     if (reinterpret_cast<uintptr_t>(u) & 7) ACX_FAIL(ACX_ERR_ARG, "%s: u is not 8-byte aligned", who);
     if (!picked) ACX_FAIL(ACX_ERR_ARG, "%s: picked is null", who);

@@ -23,11 +23,11 @@
 // the threshold soon rejects almost everything and trims are rare; on adversarial data (every score beats the last) there is
 // one trim per CAP - k rows, and the result is the same.
 //
-// Bits.  The contraction of a (query, row) pair runs over the whole of `dim` inside one wave, in one fixed order (16 columns
-// per group of eight MFMAs, the lane halves taking columns 0-7 and 8-15 of the group), whatever the pair's position in its
-// tile, the tile's in the grid, nq, n, k or the number of slices: the same pair has the same score bits everywhere.  Cosine
-// scores are (acc * rq[i]) * rd[j], two roundings.  A non-finite accumulator (a NaN or inf in Q or D always gives one, as every
-// query meets every row) sets ACX_KNN_NONFINITE, and the merge then writes index -1 / score NaN everywhere.
+// Bits.  The contraction of a (query, row) pair is dot_tile's (device_common.h, which states the contract): the whole of `dim`
+// inside one wave, in an order that depends on `dim` alone, whatever the pair's position in its tile, the tile's in the grid,
+// nq, n, k or the number of slices: the same pair has the same score bits everywhere, and in kmeans_assign_kernel too.  Cosine
+// scores are cos_scale(acc, rq[i], rd[j]), two roundings.  A non-finite accumulator (a NaN or inf in Q or D always gives one,
+// as every query meets every row) sets ACX_KNN_NONFINITE, and the merge then writes index -1 / score NaN everywhere.
 #include <cmath>
 
 #include "acx_internal.h"
@@ -39,7 +39,6 @@ constexpr int kKnnThreads = 256;
 constexpr int kKnnStepRows = 256;            // database rows per step of a workgroup: four waves x 64
 constexpr int kKnnTargetWgs = 512;           // the slice count aims at this many workgroups: two per CU of an MI355X
 constexpr int kKnnMaxSlices = 1024;
-constexpr long long kKnnMaxRows = 1LL << 30;
 
 // knn_key, knn_make_key, knn_key_score, knn_key_index: device_common.h (classify.hip orders classes by the same keys)
 
@@ -94,20 +93,12 @@ __global__ __launch_bounds__(256) void knn_norm_kernel(const float* __restrict__
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
     const float* xr = x + row * ld;
-    float s = 0.f;
     bool bad = false;
-    for (int k = lane * 4; k < dim; k += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(xr + k);
-        s = __builtin_fmaf(v.x, v.x, s);
-        s = __builtin_fmaf(v.y, v.y, s);
-        s = __builtin_fmaf(v.z, v.z, s);
-        s = __builtin_fmaf(v.w, v.w, s);
-        bad |= !(fabsf(v.x) <= 3.4028234664e38f) || !(fabsf(v.y) <= 3.4028234664e38f) || !(fabsf(v.z) <= 3.4028234664e38f) ||
-               !(fabsf(v.w) <= 3.4028234664e38f);
-    }
-    s = wave_sum(s);
+    const float s = wave_sum(row_sumsq(xr, dim, lane, [&](const float4& v) {
+        bad |= acx_nonfinite(v.x) || acx_nonfinite(v.y) || acx_nonfinite(v.z) || acx_nonfinite(v.w);
+    }));
     if (__ballot(bad) && lane == 0) atomicOr(status, ACX_KNN_NONFINITE);
-    if (lane == 0) inv_norm[row] = s > 0.f ? 1.0f / sqrtf(s) : 0.f;
+    if (lane == 0) inv_norm[row] = inv_norm_of(s);
 }
 
 struct KnnSearchP {
@@ -148,9 +139,7 @@ __global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p
     // rows past nq / the slice repeat the last valid one: loads stay inside the buffers, results are dropped
     const float* qa[QT];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) qa[t] = p.q + min(q0 + 32 * t + r32, p.nq - 1) * p.ld_q + 8 * h;
-    const int full = p.dim >> 4, rem = p.dim & 15;
-    const bool tail0 = rem >= 4 + 8 * h, tail1 = rem >= 8 + 8 * h;
+    for (int t = 0; t < QT; ++t) qa[t] = p.q + min(q0 + 32 * t + r32, p.nq - 1) * p.ld_q;
     bool bad = false;
 
     for (long long j0 = j_lo; j0 < j_hi; j0 += kKnnStepRows) {
@@ -163,51 +152,10 @@ __global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const long long j = min(jw + 32 * u + r32, j_hi - 1);
-                db[u] = p.d + j * p.ld_d + 8 * h;
+                db[u] = p.d + j * p.ld_d;
                 if (cosine) rdv[u] = p.rd[j];
             }
-#pragma unroll
-            for (int t = 0; t < QT; ++t)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[t][u][i] = 0.f;
-            const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#define KNN_MFMA(A, B, C)                                                                                      \
-    _Pragma("unroll") for (int t = 0; t < QT; ++t) _Pragma("unroll") for (int u = 0; u < 2; ++u)               \
-        acc[t][u] = F32Tile<32>::mfma(A[t].C, B[u].C, acc[t][u]);
-#define KNN_GROUP                                                                               \
-    KNN_MFMA(a0, b0, x) KNN_MFMA(a0, b0, y) KNN_MFMA(a0, b0, z) KNN_MFMA(a0, b0, w)             \
-    KNN_MFMA(a1, b1, x) KNN_MFMA(a1, b1, y) KNN_MFMA(a1, b1, z) KNN_MFMA(a1, b1, w)
-            float4 a0[QT], a1[QT], b0[2], b1[2];
-            for (int kb = 0; kb < full; ++kb) {
-#pragma unroll
-                for (int t = 0; t < QT; ++t) {
-                    a0[t] = *reinterpret_cast<const float4*>(qa[t] + kb * 16);
-                    a1[t] = *reinterpret_cast<const float4*>(qa[t] + kb * 16 + 4);
-                }
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    b0[u] = *reinterpret_cast<const float4*>(db[u] + kb * 16);
-                    b1[u] = *reinterpret_cast<const float4*>(db[u] + kb * 16 + 4);
-                }
-                KNN_GROUP
-            }
-            if (rem) {                               // the last 4, 8 or 12 columns: the lane halves past dim contribute zeros
-#pragma unroll
-                for (int t = 0; t < QT; ++t) {
-                    a0[t] = tail0 ? *reinterpret_cast<const float4*>(qa[t] + full * 16) : zero4;
-                    a1[t] = tail1 ? *reinterpret_cast<const float4*>(qa[t] + full * 16 + 4) : zero4;
-                }
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    b0[u] = tail0 ? *reinterpret_cast<const float4*>(db[u] + full * 16) : zero4;
-                    b1[u] = tail1 ? *reinterpret_cast<const float4*>(db[u] + full * 16 + 4) : zero4;
-                }
-                KNN_GROUP
-            }
-#undef KNN_GROUP
-#undef KNN_MFMA
+            dot_tile<QT>(acc, qa, db, p.dim, h, [](const float4 (&)[2], const float4 (&)[2]) {});
         }
 
         // filter the tile into the candidate buffers; lanes left without a slot try again after the trim
@@ -228,12 +176,9 @@ __global__ __launch_bounds__(kKnnThreads, 2) void knn_search_kernel(KnnSearchP p
                                 bool keep = false;
                                 if (q0 + ql < p.nq && j < j_hi) {
                                     float s = acc[t][u][i];
-                                    if (!(fabsf(s) <= 3.4028234664e38f)) bad = true;
+                                    if (acx_nonfinite(s)) bad = true;
                                     if (j != (long long)s_excl[ql]) {
-                                        if (cosine) {
-#pragma clang fp contract(off)
-                                            s = (s * s_rq[ql]) * rdv[u];
-                                        }
+                                        if (cosine) s = cos_scale(s, s_rq[ql], rdv[u]);
                                         const knn_key key = knn_make_key(s, j);
                                         if (key > s_thr[ql]) {
                                             const int slot = atomicAdd(&s_cnt[ql], 1);
@@ -360,24 +305,22 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(KnnVoteP p) {
 // ---- host ------------------------------------------------------------------------------------------------------------------
 struct KnnPlan { int qt, r, slices; long long slice_rows; };
 
-static long long knn_cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
 // The launch shape of a search: a function of (nq, n, k) and ACX_KNN_SLICE_ROWS alone.
 static KnnPlan knn_plan(long long nq, long long n, int k) {
     KnnPlan pl;
     pl.qt = nq <= 32 ? 1 : 2;
     pl.r = k <= 32 ? 1 : k <= 64 ? 2 : 4;
-    const long long qtiles = knn_cdiv(nq, 32 * pl.qt);
+    const long long qtiles = cdiv(nq, 32 * pl.qt);
     const int forced = tuning().knn_slice_rows.load(std::memory_order_relaxed);
     long long rows, slices;
     if (forced > 0) {
         rows = forced;
-        if (knn_cdiv(n, rows) > kKnnMaxSlices) rows = knn_cdiv(n, kKnnMaxSlices);
+        if (cdiv(n, rows) > kKnnMaxSlices) rows = cdiv(n, kKnnMaxSlices);
     } else {
-        slices = std::min(std::max(knn_cdiv(kKnnTargetWgs, qtiles), 1LL), knn_cdiv(n, kKnnStepRows));
-        rows = knn_cdiv(knn_cdiv(n, slices), kKnnStepRows) * kKnnStepRows;
+        slices = std::min(std::max(cdiv(kKnnTargetWgs, qtiles), 1LL), cdiv(n, kKnnStepRows));
+        rows = cdiv(cdiv(n, slices), kKnnStepRows) * kKnnStepRows;
     }
-    slices = knn_cdiv(n, rows);
+    slices = cdiv(n, rows);
     pl.slices = (int)slices;
     pl.slice_rows = rows;
     return pl;
@@ -388,8 +331,8 @@ static KnnPlan knn_plan(long long nq, long long n, int k) {
 static size_t knn_ws_bytes(long long nq, long long n, int k) {
     const int forced = tuning().knn_slice_rows.load(std::memory_order_relaxed);
     long long cells;
-    if (forced > 0) cells = nq * std::min<long long>(kKnnMaxSlices, knn_cdiv(n, forced));
-    else cells = std::min(nq * knn_cdiv(n, kKnnStepRows), 64LL * kKnnTargetWgs + nq);
+    if (forced > 0) cells = nq * std::min<long long>(kKnnMaxSlices, cdiv(n, forced));
+    else cells = std::min(nq * cdiv(n, kKnnStepRows), 64LL * kKnnTargetWgs + nq);
     return align_up((size_t)cells * (size_t)k * sizeof(knn_key));
 }
 
@@ -397,12 +340,12 @@ static int knn_check_shape(const char* who, int64_t nq, int64_t n, int k) {
     if (nq < 1) ACX_FAIL(ACX_ERR_ARG, "%s: nq = %lld (expected >= 1)", who, (long long)nq);
     if (n < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n = %lld (expected >= 1)", who, (long long)n);
     if (k < 1 || k > ACX_KNN_MAX_K) ACX_FAIL(ACX_ERR_ARG, "%s: k = %d (expected 1 .. %d)", who, k, ACX_KNN_MAX_K);
-    if (n > kKnnMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
-    if (nq > kKnnMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: nq = %lld (at most 2^30 queries per call)", who, (long long)nq);
+    if (n > kF32MaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
+    if (nq > kF32MaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: nq = %lld (at most 2^30 queries per call)", who, (long long)nq);
     return ACX_OK;
 }
 
-static int knn_check_rows(const char* who, const char* name, const float* x, int64_t ld, int dim) {
+int check_f32_rows(const char* who, const char* name, const float* x, int64_t ld, int dim) {
     if (!x) ACX_FAIL(ACX_ERR_ARG, "%s: %s is null", who, name);
     if (dim < 4 || dim > ACX_KNN_MAX_DIM || (dim & 3))
         ACX_FAIL(ACX_ERR_ARG, "%s: dim = %d (expected a multiple of 4 in 4 .. %d)", who, dim, ACX_KNN_MAX_DIM);
@@ -432,8 +375,8 @@ extern "C" {
 int acx_knn_row_norms(const float* x, int64_t ld, int64_t n, int dim, float* inv_norm, int32_t* status, void* stream) {
     static const char* who = "acx_knn_row_norms";
     if (n < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n = %lld (expected >= 1)", who, (long long)n);
-    if (n > kKnnMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
-    ACX_TRY(knn_check_rows(who, "x", x, ld, dim));
+    if (n > kF32MaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
+    ACX_TRY(check_f32_rows(who, "x", x, ld, dim));
     if (!inv_norm) ACX_FAIL(ACX_ERR_ARG, "%s: inv_norm is null", who);
     if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
     launch_kernel(&knn_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (long long)ld, (long long)n,
@@ -463,8 +406,8 @@ int acx_knn_search(const float* q, int64_t ld_q, const float* q_inv_norm, int64_
     ACX_TRY(knn_check_shape(who, nq, n, k));
     if (metric != ACX_KNN_DOT && metric != ACX_KNN_COSINE)
         ACX_FAIL(ACX_ERR_ARG, "%s: metric %d (expected ACX_KNN_DOT or ACX_KNN_COSINE)", who, metric);
-    ACX_TRY(knn_check_rows(who, "q", q, ld_q, dim));
-    ACX_TRY(knn_check_rows(who, "d", d, ld_d, dim));
+    ACX_TRY(check_f32_rows(who, "q", q, ld_q, dim));
+    ACX_TRY(check_f32_rows(who, "d", d, ld_d, dim));
     if (metric == ACX_KNN_COSINE && (!q_inv_norm || !d_inv_norm))
         ACX_FAIL(ACX_ERR_ARG, "%s: q_inv_norm / d_inv_norm is null with ACX_KNN_COSINE", who);
     if (!indices || !scores) ACX_FAIL(ACX_ERR_ARG, "%s: indices / scores is null", who);
@@ -482,7 +425,7 @@ int acx_knn_search(const float* q, int64_t ld_q, const float* q_inv_norm, int64_
     p.dim = dim; p.k = k; p.exclude = exclude; p.ws = static_cast<knn_key*>(ws); p.status = (int*)status;
     p.slices = pl.slices; p.slice_rows = pl.slice_rows;
     ACX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    const long long qtiles = knn_cdiv(nq, 32 * pl.qt);
+    const long long qtiles = cdiv(nq, 32 * pl.qt);
     const int ri = pl.r == 1 ? 0 : pl.r == 2 ? 1 : 2;
     DeviceOnce& once = g_knn_lds[pl.qt - 1][ri];
     int rc;

@@ -128,6 +128,27 @@ def test_score_bits_do_not_depend_on_the_shape():
         np.testing.assert_array_equal(s1.view(np.uint32), sc[rows[::-1]].view(np.uint32))
 
 
+@pytest.mark.parametrize("dim", [4, 8, 12, 16, 20, 24, 28, 772])
+def test_dot_products_are_the_search_s(dim):
+    """kmeans_assign_kernel and knn_search_kernel form a (row, centre) dot product by ONE function (dot_tile, device_common.h).
+    The cosine assignment scores a row as minus its largest raw dot product with a centre, and a k = 1 "dot" search over the
+    centres returns that largest dot product: labels = indices and scores = -scores, no tolerance, on normal float32 data whose
+    bits show the summation order.  dim: rem 4 / 8 / 12 / 0 of the 16-column groups without and with full groups; n: the search
+    takes 32-query and 64-query tiles while the assignment always takes 64 rows; K: one centre, a partial second wave, a second
+    step.  (Values are compared, not bit patterns: the search returns +0.0 where the assignment returns 0 - (+0.0).)"""
+    rng = np.random.default_rng(7700 + dim)
+    for n in (31, 65):
+        for K in (1, 65, 257):
+            xd = dev_rows(rng.standard_normal((n, dim)))
+            cd = dev_rows(rng.standard_normal((K, dim)))
+            lab, sc, _, status = dev_assign(xd, cd, "cosine")
+            index = retrieval.EmbeddingIndex(cd, metric="dot")
+            s, i = index.search(xd, k=1)
+            assert status == 0 and int(index._status.cpu()[0]) == 0, (n, K)
+            np.testing.assert_array_equal(lab, i.cpu().numpy()[:, 0], err_msg="n %d K %d" % (n, K))
+            np.testing.assert_array_equal(sc, -s.cpu().numpy()[:, 0], err_msg="n %d K %d" % (n, K))
+
+
 # ---- (3) the centre update -------------------------------------------------------------------------------------------------------
 def dev_update(x, labels, c_old, metric="euclidean"):
     n, dim = x.shape
