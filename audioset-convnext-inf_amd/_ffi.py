@@ -66,7 +66,7 @@ _pops = ctypes.POINTER(AcxOperatingSpec)
 
 
 class AcxRefEvent(ctypes.Structure):
-    """struct acx_ref_event: one row of the reference table of acx_score_events / acx_score_segments (24 bytes)."""
+    """struct acx_ref_event: one row of the reference table of acx_score_events / acx_score_segments / acx_score_intersection (24 bytes)."""
     _fields_ = [("clip", ctypes.c_int32), ("cls", ctypes.c_int32), ("onset", ctypes.c_double), ("offset", ctypes.c_double)]
 
 
@@ -77,6 +77,15 @@ class AcxEventCollar(ctypes.Structure):
 
 
 _pcol = ctypes.POINTER(AcxEventCollar)
+
+
+class AcxIntersectionCriteria(ctypes.Structure):
+    """struct acx_intersection_criteria: the three ratios of acx_score_intersection."""
+    _fields_ = [("dtc", ctypes.c_double), ("gtc", ctypes.c_double), ("cttc", ctypes.c_double), ("cross_triggers", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+_pcrit = ctypes.POINTER(AcxIntersectionCriteria)
 
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
@@ -135,6 +144,9 @@ SIGNATURES = {
                                   _vp]),
     "acx_score_segments": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _c_dbl, _vp, _vp, _vp,
                                     _vp]),
+    "acx_score_intersection": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _pcrit, _vp, _vp, _vp,
+                                        _vp, _vp, _vp]),
+    "acx_cross_trigger_rate": (_c_int, [_vp, _vp, _c_int, _vp, _vp]),
     "acx_logmel_bn0": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _c_int, _vp]),
     "acx_stem_ln": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
     "acx_dwconv7": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
@@ -738,7 +750,7 @@ def event_stream_bytes(slots, N, median):
     return _query(lib().acx_event_stream_bytes, _c_sz, int(slots), int(N), int(median))
 
 
-SCORE_BAD_TABLE = 1                           # bit of the status word of acx_score_events / acx_score_segments
+SCORE_BAD_TABLE = 1                           # bit of the status word of acx_score_events / acx_score_segments / acx_score_intersection
 REF_EVENT_BYTES = ctypes.sizeof(AcxRefEvent)  # 24
 SCORE_TILE_SEGMENTS = 2048                    # ACX_SCORE_TILE_SEGMENTS
 
@@ -746,6 +758,12 @@ SCORE_TILE_SEGMENTS = 2048                    # ACX_SCORE_TILE_SEGMENTS
 def event_collar(t_collar=0.2, percentage_of_length=0.5, evaluate_onset=True, evaluate_offset=True):
     """An acx_event_collar struct (sed_eval's defaults)."""
     return AcxEventCollar(float(t_collar), float(percentage_of_length), 1 if evaluate_onset else 0, 1 if evaluate_offset else 0)
+
+
+def intersection_criteria(dtc_threshold=0.7, gtc_threshold=0.7, cttc_threshold=None):
+    """An acx_intersection_criteria struct; cttc_threshold None: no cross-trigger matrix."""
+    return AcxIntersectionCriteria(float(dtc_threshold), float(gtc_threshold), 0.0 if cttc_threshold is None else float(cttc_threshold),
+                                   0 if cttc_threshold is None else 1, 0)
 
 
 def segment_count(L):

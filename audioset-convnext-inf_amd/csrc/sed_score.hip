@@ -12,10 +12,15 @@
 //                           and of the estimated intervals, intersected by two pointers; the runs of misses and false alarms are
 //                           +1 / -1 interval adds into two per-segment LDS difference arrays, which the workgroup then scans for
 //                           the substitutions, deletions and insertions of every segment.
+//   sed_intersection_kernel one WAVE per (clip, 64 classes), a lane per class: the intersection criteria of PSDS (detection
+//                           tolerance, ground-truth intersection, cross-trigger tolerance), all three by one walk, sc_cover_row.
+//   cross_trigger_rate_kernel  a thread per detected class: its row of a cross-trigger matrix as one weighted mean, summed in
+//                           ascending class order (the fixed order psds_host states).
 //
 // float64 throughout, as the host definitions: onsets and offsets come from event_edge (device_common.h), the decoder's own
 // function.  The expressions compared -- |r_on - e_on| <= t_collar, |r_off - e_off| <= max(t_collar, pct * (r_off - r_on)),
-// floor(t / res), ceil(t / res) -- hold subtractions, one product, one IEEE division and comparisons.  NOTHING here may be
+// floor(t / res), ceil(t / res), cover >= rho * (b - a) -- hold subtractions, one product, one IEEE division, sums in a stated
+// order and comparisons.  NOTHING here may be
 // contracted into an FMA or reassociated, or a difference exactly on a collar would fall on the other side than on the host:
 // this file is built with -ffp-contract=off and without fast-math (csrc/Makefile), and says so again below.  Like events.hip it
 // may run beside a forward on another stream: -fno-slp-vectorize, no packed-FP32 instructions.
@@ -287,6 +292,115 @@ __global__ __launch_bounds__(1024) void sed_segment_kernel(ScArgs a, double res,
     }
 }
 
+// ---- intersection-based: the criteria of PSDS ---------------------------------------------------------------------------------
+// One row of the cover walk of pytorch/sed_metrics.py::_cover: [a, b) is the interval measured, `covered` starts at a and `total`
+// at 0.0, the rows (on, off) come ascending in on.  false: this row begins at or behind b, and so does every later one.
+__device__ __forceinline__ bool sc_cover_row(double on, double off, double b, double& covered, double& total) {
+    if (on >= b) return false;
+    const double lo = fmax(on, covered), hi = fmin(off, b);
+    if (hi > lo) { total += hi - lo; covered = hi; }
+    return true;
+}
+
+// rows [lo, hi) of the reference table that belong to `clip`, every class: two lower bounds stepped together
+__device__ __forceinline__ void sc_clip_range(const ScArgs& a, int clip, long long& lo, long long& hi) {
+    ScBound s[2] = {{reinterpret_cast<const char*>(a.ref), (long long)sizeof(acx_ref_event), 0, a.n_ref, (long long)clip << 32},
+                    {reinterpret_cast<const char*>(a.ref), (long long)sizeof(acx_ref_event), 0, a.n_ref, ((long long)clip + 1) << 32}};
+    while (s[0].open() || s[1].open()) {
+        s[0].step();
+        s[1].step();
+    }
+    lo = s[0].lo; hi = s[1].lo;
+}
+
+// A lane's three passes over its column.  Detections of a column ascend in onset and do not overlap; reference events ascend in
+// onset and may overlap.  A row that ends at or before the interval's beginning adds nothing to its cover (hi <= a <= covered
+// <= lo), nor to that of any later interval of the column, whose beginning is no smaller: `low` passes such rows once, from
+// the front only, so that a long column costs its length and not its square.  est_rel is written in the first pass and read
+// in the third by the lane that wrote it.
+__global__ __launch_bounds__(64) void sed_intersection_kernel(ScArgs a, acx_intersection_criteria c, long long* ct,
+                                                              long long* ref_hit, long long* est_rel) {
+    const int lane = threadIdx.x;
+    const long long unit = blockIdx.x;
+    const int clip = (int)(unit / a.G), cls = (int)(unit - (long long)clip * a.G) * 64 + lane;
+    const long long n_est = sc_est_rows(a);
+    if (n_est < 0) {
+        if (unit == 0 && lane == 0) atomicOr(a.status, ACX_SCORE_BAD_TABLE);
+        return;
+    }
+    if (cls >= a.N) return;
+    long long rlo, rhi, elo, ehi, clo = 0, chi = 0;
+    sc_ranges(a, n_est, clip, cls, rlo, rhi, elo, ehi);
+    const bool cross = c.cross_triggers != 0 && ct != nullptr;
+    if (cross && ehi > elo) sc_clip_range(a, clip, clo, chi);
+    const int steps = a.steps[clip];
+    const double end = a.end[clip];
+
+    // 1. detection tolerance: a detection is relevant when the annotations of its column cover dtc of its length
+    long long low = rlo, fp = 0;
+    for (long long j = elo; j < ehi; ++j) {
+        const int2 be = *reinterpret_cast<const int2*>(&a.est[j].begin);
+        const double d_on = event_edge(be.x, steps, a.step, end), d_off = event_edge(be.y, steps, a.step, end);
+        while (low < rhi && a.ref[low].offset <= d_on) ++low;
+        double covered = d_on, total = 0.0;
+        for (long long r = low; r < rhi; ++r)
+            if (!sc_cover_row(a.ref[r].onset, a.ref[r].offset, d_off, covered, total)) break;
+        const bool relevant = total >= c.dtc * (d_off - d_on);                      // one product, not contracted
+        est_rel[j] = relevant ? 1 : 0;
+        if (relevant) continue;
+        ++fp;
+        if (!cross) continue;
+        // 2. cross triggers of a false positive: the clip's annotations, class group by class group
+        for (long long i = clo; i < chi;) {
+            const int k = a.ref[i].cls;
+            if (k == cls) { i = rhi; continue; }                                    // its own column is [rlo, rhi)
+            double cov = d_on, sum = 0.0;
+            bool more = true;
+            for (; i < chi && a.ref[i].cls == k; ++i)
+                if (more) more = sc_cover_row(a.ref[i].onset, a.ref[i].offset, d_off, cov, sum);
+            if ((unsigned)k < (unsigned)a.N && sum >= c.cttc * (d_off - d_on)) sc_add(ct + (long long)cls * a.N + k, 1);
+        }
+    }
+
+    // 3. ground-truth intersection: an annotation is found when the relevant detections of its column cover gtc of its length
+    long long tp = 0;
+    low = elo;
+    for (long long r = rlo; r < rhi; ++r) {
+        const double g_on = a.ref[r].onset, g_off = a.ref[r].offset;
+        while (low < ehi && event_edge(a.est[low].end, steps, a.step, end) <= g_on) ++low;
+        double covered = g_on, total = 0.0;
+        for (long long j = low; j < ehi; ++j) {
+            const int2 be = *reinterpret_cast<const int2*>(&a.est[j].begin);
+            const double d_on = event_edge(be.x, steps, a.step, end);
+            if (d_on >= g_off) break;                                               // what sc_cover_row would answer
+            if (est_rel[j] == 0) continue;
+            sc_cover_row(d_on, event_edge(be.y, steps, a.step, end), g_off, covered, total);
+        }
+        const bool hit = total >= c.gtc * (g_off - g_on);
+        ref_hit[r] = hit ? 1 : 0;
+        tp += hit ? 1 : 0;
+    }
+    sc_add(a.counts + (long long)cls * 3 + 0, tp);
+    sc_add(a.counts + (long long)cls * 3 + 1, fp);
+    sc_add(a.counts + (long long)cls * 3 + 2, (rhi - rlo) - tp);
+}
+
+// rate[c] = the mean over k != c with weight[k] > 0 of ct[c][k] * weight[k]: one thread's sum in ascending k, then one division
+__global__ __launch_bounds__(256) void cross_trigger_rate_kernel(const long long* ct, const double* weight, int N, double* rate) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const long long* row = ct + (long long)c * N;
+    double acc = 0.0;
+    int n = 0;
+    for (int k = 0; k < N; ++k) {
+        const double w = weight[k];
+        if (k == c || !(w > 0.0)) continue;
+        acc += (double)row[k] * w;                                                  // a product, then a sum: not contracted
+        ++n;
+    }
+    rate[c] = n > 0 ? acc / (double)n : 0.0;
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 static int sc_check(const char* who, const acx_ref_event* ref, int64_t n_ref, const acx_event* est, int64_t capacity,
                     const int64_t* est_count, const int* est_status, int64_t B, int N, const int* steps, const double* end_seconds,
@@ -363,6 +477,45 @@ int acx_score_segments(const acx_ref_event* ref, int64_t n_ref, const acx_event*
     const long long workers = (1024 + B - 1) / B;
     const dim3 grid((unsigned)B, (unsigned)(workers < 1 ? 1 : workers > kScMaxTileWorkers ? kScMaxTileWorkers : workers));
     launch_kernel(&sed_segment_kernel, grid, dim3(threads), 0, s, a, time_resolution, reinterpret_cast<long long*>(overall));
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int acx_score_intersection(const acx_ref_event* ref, int64_t n_ref, const acx_event* est, int64_t capacity, const int64_t* est_count,
+                           const int* est_status, int64_t B, int N, const int* steps, const double* end_seconds, double step_seconds,
+                           const acx_intersection_criteria* c, int64_t* counts, int64_t* cross_triggers, int64_t* ref_hit,
+                           int64_t* est_relevant, int* status, void* stream) {
+    const char* who = "acx_score_intersection";
+    if (!c || (n_ref > 0 && !ref_hit) || (capacity > 0 && !est_relevant)) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    ACX_TRY(sc_check(who, ref, n_ref, est, capacity, est_count, est_status, B, N, steps, end_seconds, step_seconds, counts, status));
+    const double rho[3] = {c->dtc, c->gtc, c->cttc};
+    const char* const name[3] = {"dtc", "gtc", "cttc"};
+    for (int i = 0; i < (c->cross_triggers ? 3 : 2); ++i)
+        if (!(rho[i] > 0.0 && rho[i] <= 1.0))
+            ACX_FAIL(ACX_ERR_ARG, "%s: %s %g (expected a threshold in (0, 1])", who, name[i], rho[i]);
+    if (c->cross_triggers && !cross_triggers)
+        ACX_FAIL(ACX_ERR_ARG, "%s: cross_triggers is set and the matrix is null", who);
+    const hipStream_t s = (hipStream_t)stream;
+    const bool cross = c->cross_triggers != 0;
+    ACX_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
+    ACX_HIP(hipMemsetAsync(counts, 0, (size_t)N * 3 * sizeof(int64_t), s));
+    if (cross) ACX_HIP(hipMemsetAsync(cross_triggers, 0, (size_t)N * N * sizeof(int64_t), s));
+    if (n_ref > 0) ACX_HIP(hipMemsetAsync(ref_hit, 0, (size_t)n_ref * sizeof(int64_t), s));
+    if (capacity > 0) ACX_HIP(hipMemsetAsync(est_relevant, 0xff, (size_t)capacity * sizeof(int64_t), s));   // -1
+    const ScArgs a = sc_args(ref, n_ref, est, capacity, est_count, est_status, N, steps, end_seconds, step_seconds, counts, status);
+    launch_kernel(&sed_intersection_kernel, dim3((unsigned)(B * a.G)), dim3(64), 0, s, a, *c,
+                  cross ? reinterpret_cast<long long*>(cross_triggers) : nullptr, reinterpret_cast<long long*>(ref_hit),
+                  reinterpret_cast<long long*>(est_relevant));
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int acx_cross_trigger_rate(const int64_t* cross_triggers, const double* weight, int N, double* rate, void* stream) {
+    const char* who = "acx_cross_trigger_rate";
+    if (!cross_triggers || !weight || !rate) ACX_FAIL(ACX_ERR_ARG, "%s: null argument", who);
+    if (N < 1 || N > ACX_MAX_CLASSES) ACX_FAIL(ACX_ERR_SHAPE, "%s: %d classes (expected 1 .. %d)", who, N, ACX_MAX_CLASSES);
+    launch_kernel(&cross_trigger_rate_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                  reinterpret_cast<const long long*>(cross_triggers), weight, N, rate);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

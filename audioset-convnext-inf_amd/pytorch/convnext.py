@@ -498,14 +498,33 @@ class ConvNeXt(nn.Module):
     def score_events(self, waveform, reference, metric="event", **args):
         """detect_events followed by the scoring of its table against annotated events, all on the GPU and on the same stream
         (pytorch/sed_metrics.py).  reference: a ReferenceEvents on the model's device, one entry per clip of the batch;
-        metric: "event" (onset / offset collars) or "segment" (a fixed time grid).  args: detect_events' own (pool,
-        sample_rate, threshold, low, median, min_duration, merge_gap, capacity) and the scorer's (t_collar,
-        percentage_of_length, evaluate_onset, evaluate_offset / time_resolution).  Returns detect_events' dict plus "scores",
+        metric: "event" (onset / offset collars), "segment" (a fixed time grid) or "intersection" (the criteria of PSDS).
+        args: detect_events' own (pool, sample_rate, threshold, low, median, min_duration, merge_gap, capacity) and the
+        scorer's (t_collar, percentage_of_length, evaluate_onset, evaluate_offset / time_resolution / dtc_threshold,
+        gtc_threshold, cttc_threshold).  Returns detect_events' dict plus "scores",
         a SedScores; nothing synchronises until the table or the scores are read."""
         args = dict(args)
         score, score_args = _sed._scorer(metric, args)
         out = self.detect_events(waveform, **args)
         out["scores"] = score(reference, out["events"], **score_args)
+        return out
+
+    def psds(self, waveform, reference, pool=3, sample_rate=None, **psds_args):
+        """forward_segments followed by sed_metrics.psds on "segmentwise_output" with the clips' own "segment_edges": the
+        polyphonic sound detection score of the batch against a ReferenceEvents on the model's device, one forward and a
+        sweep of thresholds decoded and scored on the GPU.  psds_args: thresholds, scenario ("dcase_1" / "dcase_2"),
+        dtc_threshold, gtc_threshold, cttc_threshold, alpha_ct, alpha_st, max_efpr, unit_seconds and the decoder's (low, median,
+        min_duration, merge_gap, capacity); psds' own are checked before the forward runs.  Returns forward_segments' dict
+        plus "psds", a sed_metrics.PsdsResult."""
+        if "step" in psds_args or "steps" in psds_args:
+            raise TypeError("psds takes its boundaries from the clip: step / steps are not arguments")
+        if "threshold" in psds_args:
+            raise TypeError("psds sets threshold itself")
+        own = ("thresholds", "scenario", "dtc_threshold", "gtc_threshold", "cttc_threshold", "alpha_ct", "alpha_st", "max_efpr",
+               "unit_seconds")
+        _sed.check_psds_args(**{k: psds_args[k] for k in own if k in psds_args})
+        out = self.forward_segments(waveform, pool=pool, sample_rate=sample_rate)
+        out["psds"] = _sed.psds(out["segmentwise_output"], reference, step=out["segment_edges"].numpy(), **psds_args)
         return out
 
     def tag(self, waveform, threshold, sample_rate=None, calibration=None):

@@ -424,6 +424,45 @@ ACX_API int acx_score_segments(const acx_ref_event* ref, int64_t n_ref, const ac
                                const double* end_seconds /* device, B */, double step_seconds, double time_resolution,
                                int64_t* counts /* N*3 */, int64_t* overall /* 6 */, int* status, void* stream);
 
+/* ---- sound event scoring, intersection criteria: the counts that PSDS integrates ----------------------------------------------
+ * The third scoring family (replaces: nothing in the reference; host loops over EventTable.to_lists() per threshold).  The
+ * definitions are this project's own host functions, pytorch/sed_metrics.py::intersection_based_metrics_host and ::psds_host,
+ * written after the polyphonic sound detection score of Bilen et al. (ICASSP 2020); psds_eval is not a dependency and nothing
+ * claims equality with it.  Every output of acx_score_intersection is an integer and EQUALS the host definition's.
+ * Tables, est_count / est_status, steps / end_seconds / step_seconds: as in "sound event scoring" above.
+ * cover(a, b, rows) = the length of [a, b) that the union of rows (on, off), ascending in on, covers: with covered = a and
+ *   total = 0.0, for each row until the first with on >= b:  lo = max(on, covered), hi = min(off, b);  if hi > lo: total += hi - lo,
+ *   covered = hi.  A criterion with ratio rho holds when cover(...) >= rho * (b - a): float64, one product, not contracted.
+ * Per (clip, class c) column:
+ *   DTC   detection d is relevant when cover(d, the reference rows of (clip, c)) >= dtc * len(d); one that is not is an FP of c.
+ *   GTC   reference event g is a TP when cover(g, the RELEVANT detections of (clip, c), in table order) >= gtc * len(g), else
+ *         an FN.  A relevant detection whose annotation fails GTC is neither a TP nor an FP.
+ *   CTTC  (cross_triggers != 0) for each FP d of class c and each class k != c with annotations in the clip:
+ *         cover(d, the reference rows of (clip, k)) >= cttc * len(d) adds 1 to cross_triggers[c * N + k].  The diagonal stays 0.
+ * counts[cls] = TP, FP, FN.  est_relevant[j] = 1 / 0 for the valid rows and -1 behind them (all `capacity` entries are
+ * written); ref_hit[i] = 1 / 0.  An unusable estimated table sets ACX_SCORE_BAD_TABLE and leaves the outputs cleared: counts,
+ * matrix and ref_hit 0, est_relevant -1.
+ * Launch contract: the clears of the outputs, then one kernel (one wave per (clip, 64 classes), a lane per class), in order on
+ * `stream`; no allocation, no workspace, no synchronisation, capturable; counts meet only in 64-bit integer atomic adds, so every
+ * call gives the same bits.  n_ref == 0 (ref, ref_hit may be NULL) and capacity == 0 (est, est_relevant may be NULL) are legal;
+ * cross_triggers (the matrix) may be NULL when c->cross_triggers == 0, and is not touched then.
+ * Argument errors are returned before anything touches the device, with the codes of "sound event scoring"; in addition
+ * ACX_ERR_ARG: dtc or gtc -- and cttc when c->cross_triggers != 0 -- not finite or outside (0, 1]; c->cross_triggers != 0 with a
+ * NULL matrix.
+ * acx_cross_trigger_rate: rate[c] = (sum over k != c with weight[k] > 0, ascending in k, of (double)cross_triggers[c * N + k] *
+ *   weight[k]) / (the number of such k), 0 when there is none: one thread's sequential float64 sum per class, the order
+ *   psds_host states, so a threshold sweep keeps one matrix and T rows of rates.  All three arrays on the device; one launch on
+ *   `stream`, capturable.  ACX_ERR_ARG: a null pointer; ACX_ERR_SHAPE: N < 1 or N > ACX_MAX_CLASSES. */
+typedef struct acx_intersection_criteria { double dtc, gtc, cttc; int32_t cross_triggers, reserved; } acx_intersection_criteria;
+ACX_API int acx_score_intersection(const acx_ref_event* ref, int64_t n_ref, const acx_event* est, int64_t capacity,
+                                   const int64_t* est_count, const int* est_status, int64_t B, int N,
+                                   const int* steps /* device, B */, const double* end_seconds /* device, B */,
+                                   double step_seconds, const acx_intersection_criteria* c, int64_t* counts /* N*3 */,
+                                   int64_t* cross_triggers /* N*N or NULL */, int64_t* ref_hit /* n_ref */,
+                                   int64_t* est_relevant /* capacity */, int* status, void* stream);
+ACX_API int acx_cross_trigger_rate(const int64_t* cross_triggers /* N*N */, const double* weight /* N */, int N,
+                                   double* rate /* N */, void* stream);
+
 /* ---- live streams: tagging recordings that arrive chunk by chunk ----------------------------------------------------------
  * No reference counterpart.  A handle has `slots`; each slot holds one recording at a time.  Samples pushed to a slot are
  * appended to its open recording; acx_stream_close ends it and the slot's next push starts a new one.  Window W, hop H, the
