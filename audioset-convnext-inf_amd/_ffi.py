@@ -87,6 +87,19 @@ class AcxIntersectionCriteria(ctypes.Structure):
 
 _pcrit = ctypes.POINTER(AcxIntersectionCriteria)
 
+AUG_MAX_STRIPES = 4                  # ACX_AUG_MAX_STRIPES
+
+
+class AcxWaveAug(ctypes.Structure):
+    """struct acx_wave_aug: one clip's waveform plan of acx_augment_wave (40 bytes)."""
+    _fields_ = [("step", ctypes.c_double), ("n_out", ctypes.c_int64), ("shift", ctypes.c_int64), ("roll", ctypes.c_int64),
+                ("gain", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+class AcxSpecAug(ctypes.Structure):
+    """struct acx_spec_aug: one clip's stripes of acx_augment_spec (64 bytes)."""
+    _fields_ = [(k, ctypes.c_int32 * AUG_MAX_STRIPES) for k in ("t_bgn", "t_len", "f_bgn", "f_len")]
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -177,6 +190,12 @@ SIGNATURES = {
     "acx_resampler_create": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_vp)]),
     "acx_resampler_destroy": (None, [_vp]),
     "acx_resample": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _vp, _vp]),
+    "acx_augment_plan_check": (_c_int, [_c_int, _c_i64, _vp, _vp]),
+    "acx_augment_wave": (_c_int, [_vp, _c_int, _c_i64, _vp, _vp, _vp]),
+    "acx_augment_spec": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "acx_forward_features": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_workspace_bytes_augmented": (_c_int, [_vp, _c_int, _c_i64, _c_int, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_forward_augmented": (_c_int, [_vp, _vp, _c_int, _c_i64, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_metrics_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_tagging_metrics": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_operating_points": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _pops, _vp, _vp, _vp, _vp, _c_sz, _vp]),
@@ -359,6 +378,10 @@ class Context:
 
     def workspace_bytes(self, B, L, kind):
         return self._workspace_bytes("", kind, int(B), int(L))
+
+    def workspace_bytes_augmented(self, B, L, has_wave_plan, has_lambda, kind):
+        return _query(lib().acx_workspace_bytes_augmented, _c_sz, self._h, int(B), int(L), 1 if has_wave_plan else 0,
+                      1 if has_lambda else 0, int(MODES.get(kind, kind)))
 
     def workspace_bytes_varlen(self, lengths, kind):
         lens = (_c_i64 * max(1, len(lengths)))(*[int(n) for n in lengths])

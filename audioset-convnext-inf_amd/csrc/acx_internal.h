@@ -475,9 +475,13 @@ int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, 
 // The uniform forward of B clips of L samples with the batch split (acx_forward; arguments checked by the caller).  wstart: the
 // window table of acx_forward_windows / acx_stream_forward, written on `st` by the caller -- clip b's samples start at
 // wav + wstart[b], sub-batch i gets its slice of the table and the whole of wav.  seg: the segment tail instead of `mode`'s.
+// feat_in: the (B, T, 224) bn0'd log-mel rows of the batch, given by the caller (acx_forward_features; wav is null then): the
+// frontend launch is skipped and sub-batch i's stem reads its slice of them.
 struct SegTail;
 int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws, hipStream_t st,
-                    const long long* wstart, const SegTail* seg = nullptr);
+                    const long long* wstart, const SegTail* seg = nullptr, const float* feat_in = nullptr);
+// null pointers / mode / logits-needs-out1, in the entry points' words (forward.hip)
+int check_forward_args(const char* who, const void* wav, const float* out0, const float* out1, const void* ws, int mode);
 
 // number of CUs of the current device (one persistent workgroup each), cached per device
 inline int cu_count_of_current_device(int* out) {

@@ -304,8 +304,10 @@ static int run_segment_tail(acx_ctx* c, const SegTail& sg, const float* x3, int 
 // The forward of one (sub-)batch on one stream: frontend, stem, the four stages, then the tail -- seg's, or `mode`'s.  Where the
 // uniform and the variable-length kernels differ (frontend, stem, depthwise conv, downsample gather, pooling, transpose), p.g.vg
 // picks the launcher; the pointwise stages of a variable-length batch run as B = 1, H = the stage's total rows.
+// feat_in (uniform batches only): the batch's bn0'd log-mel rows, (B, T, 224), given by the caller (acx_forward_features) -- no
+// frontend launch, the stem reads them where they lie; `feat` of the workspace stays the tail's scratch.
 static int run_forward(acx_ctx* c, const float* wav, const Plan& p, int mode, float* out0, float* out1, char* ws, hipStream_t st,
-                       const SegTail* seg) {
+                       const SegTail* seg, const float* feat_in = nullptr) {
     const Geom& g = p.g;
     const VarGeom* vg = g.vg;
     float* feat = (float*)(ws + p.off_feat);
@@ -323,8 +325,8 @@ static int run_forward(acx_ctx* c, const float* wav, const Plan& p, int mode, fl
         ACX_TRY(launch_logmel_varlen(c, wav, *vg, feat, st, hidden, y));
         ACX_TRY(launch_stem_varlen(c, feat, *vg, x[0], st, act_bf16(c, 0)));
     } else {
-        ACX_TRY(launch_logmel(c, wav, g.B, g.L, g.T, feat, true, st, hidden, y, g.wstart));
-        ACX_TRY(launch_stem(c, feat, g.B, g.T, g.Hs[0], x[0], st, act_bf16(c, 0)));
+        if (!feat_in) ACX_TRY(launch_logmel(c, wav, g.B, g.L, g.T, feat, true, st, hidden, y, g.wstart));
+        ACX_TRY(launch_stem(c, feat_in ? feat_in : feat, g.B, g.T, g.Hs[0], x[0], st, act_bf16(c, 0)));
     }
     for (int s = 0; s < 4; ++s) {
         const int Wd = kStemW >> s;
@@ -363,7 +365,7 @@ static int run_forward(acx_ctx* c, const float* wav, const Plan& p, int mode, fl
 }
 
 int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws, hipStream_t st,
-                    const long long* wstart, const SegTail* seg) {
+                    const long long* wstart, const SegTail* seg, const float* feat_in) {
     // Clips are independent: a large batch runs as sub-batches on separate streams (fork/join with events, so the call
     // still looks like one unit of work on `stream` and stays graph-capturable).  Per-kernel event profiling runs
     // un-split to keep launch durations clean.  The kernels of the 16-bit arithmetics are CU-exclusive -- nothing
@@ -401,8 +403,9 @@ int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, fl
                 forked = i;
             }
             pi.g.wstart = wstart ? wstart + b_off : nullptr;
-            rc = run_forward(c, wstart ? wav : wav + (size_t)b_off * L, pi, mode, out0 + b_off * per_clip,
-                             out1 ? out1 + b_off * per_clip : nullptr, ws + ws_off, si, seg ? &sgi : nullptr);
+            rc = run_forward(c, (wstart || !wav) ? wav : wav + (size_t)b_off * L, pi, mode, out0 + b_off * per_clip,
+                             out1 ? out1 + b_off * per_clip : nullptr, ws + ws_off, si, seg ? &sgi : nullptr,
+                             feat_in ? feat_in + (size_t)b_off * pi.g.T * kMels : nullptr);
             ws_off += pi.total;
             b_off += Bi;
             if (rc == ACX_OK && c->fail_sub.load(std::memory_order_relaxed) == i) {
@@ -422,11 +425,11 @@ int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, fl
     Plan p;
     ACX_TRY(make_plan(B, L, &p));
     p.g.wstart = wstart;
-    return run_forward(c, wav, p, mode, out0, out1, ws, st, seg);
+    return run_forward(c, wav, p, mode, out0, out1, ws, st, seg, feat_in);
 }
 
 // ---- argument checks shared by the entry points (who: the entry point's name, which its messages start with) ---------------
-static int check_forward_args(const char* who, const void* wav, const float* out0, const float* out1, const void* ws, int mode) {
+int check_forward_args(const char* who, const void* wav, const float* out0, const float* out1, const void* ws, int mode) {
     if (!wav || !out0 || !ws) ACX_FAIL(ACX_ERR_ARG, "%s: null pointer", who);
     if (mode < 0 || mode > 2) ACX_FAIL(ACX_ERR_ARG, "%s: bad mode %d", who, mode);
     if (mode == ACX_MODE_LOGITS && !out1) ACX_FAIL(ACX_ERR_ARG, "%s: logits mode needs out1 (probs)", who);
@@ -529,6 +532,17 @@ int acx_forward(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float*
     ACX_TRY(acx_workspace_bytes(c, B, L, mode, &need));
     ACX_TRY(check_workspace(workspace, workspace_bytes, need));
     return forward_uniform(c, wav, B, L, mode, out0, out1, (char*)workspace, (hipStream_t)stream, nullptr);
+}
+
+int acx_forward_features(acx_ctx* c, const float* feat, int B, int64_t L, int mode, float* out0, float* out1, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    ACX_TRY(check_forward_args("acx_forward_features", feat, out0, out1, workspace, mode));
+    if ((uintptr_t)feat & 15) ACX_FAIL(ACX_ERR_ARG, "acx_forward_features: feat must be 16-byte aligned");
+    size_t need = 0;
+    ACX_TRY(acx_workspace_bytes(c, B, L, mode, &need));
+    ACX_TRY(check_workspace(workspace, workspace_bytes, need));
+    return forward_uniform(c, nullptr, B, L, mode, out0, out1, (char*)workspace, (hipStream_t)stream, nullptr, nullptr, feat);
 }
 
 // ---- sliding windows -----------------------------------------------------------------------------------------------------

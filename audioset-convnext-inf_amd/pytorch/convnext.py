@@ -801,35 +801,50 @@ class ConvNeXt(nn.Module):
                               timeline=timeline, max_push=max_push, max_batch=max_batch, events=events,
                               event_source=event_source)
 
-    def fit_head(self, data, target, sample_rate=None, **kw):
+    def fit_head(self, data, target, sample_rate=None, augment=None, views=1, mixup_alpha=None, **kw):
         """Train a new classifier head on this (frozen) backbone and install it (pytorch/finetune.py, fit_head): `data` is an
         (n, 768) tensor of scene embeddings, or a list of waveforms at `sample_rate`, whose scene embeddings are extracted
         first (extract(..., what="scene", pack=True)); target: (n, N) bool / uint8 / float labels; **kw: fit_head's settings
         (loss="ce", classes=N with (n,) integer labels trains a single-label head; read it with classify()).
         Afterwards head_audioset is an nn.Linear(768, N) with the fitted weights on the model's device -- the next forward
         runs it, state_dict() saves a checkpoint that from_pretrained loads as a fine-tuned model.  The model stays in eval
-        mode.  Returns the HeadFit."""
+        mode.  Returns the HeadFit.
+        augment: an augment.AugmentPolicy -- the head is then fitted on `views` augmented passes over the clips
+        (augment.augmented_embeddings with seed = the fit's `seed`, mixup_alpha mixing clips and label rows pairwise), as the
+        reference fine-tunes; `data` must be waveforms of one length.  The fit itself is the same fit_head on those rows."""
         from . import finetune as _ft
-        emb, target = self._fit_inputs(data, target, sample_rate)
+        emb, target = self._fit_inputs(data, target, sample_rate, augment, views, mixup_alpha, kw.get("seed", 0))
         fit = _ft.fit_head(emb, target, **kw)
         self._install_fit(fit)
         return fit
 
-    def cross_validate_head(self, data, target, sample_rate=None, install=True, **kw):
+    def cross_validate_head(self, data, target, sample_rate=None, install=True, augment=None, views=1, mixup_alpha=None, **kw):
         """k-fold cross-validation of a new head over a grid of settings (pytorch/finetune.py, cross_validate_head): data and
         target exactly as fit_head takes them; **kw: folds=, grid=, fold_ids=, stratify=, metric=, refit= and fit_head's
         settings.  install=True installs cv.final -- the best setting refitted on all rows -- as fit_head installs its fit
-        (nothing is installed with refit=False).  Returns the CrossValidation."""
+        (nothing is installed with refit=False).  augment / views / mixup_alpha: as fit_head takes them; the folds are cut over
+        the augmented rows.  Returns the CrossValidation."""
         from . import finetune as _ft
-        emb, target = self._fit_inputs(data, target, sample_rate)
+        emb, target = self._fit_inputs(data, target, sample_rate, augment, views, mixup_alpha, kw.get("seed", 0))
         cv = _ft.cross_validate_head(emb, target, **kw)
         if install and cv.final is not None:
             self._install_fit(cv.final)
         return cv
 
-    def _fit_inputs(self, data, target, sample_rate):
+    def _fit_inputs(self, data, target, sample_rate, augment=None, views=1, mixup_alpha=None, seed=0):
         from .extract_embeddings import extract
         dev = self.head_audioset.weight.device
+        if augment is None and (views != 1 or mixup_alpha is not None):
+            raise ValueError("views= and mixup_alpha= go with augment= (an AugmentPolicy; AugmentPolicy.identity() for mixup alone)")
+        if augment is not None:
+            from . import augment as _aug
+            if isinstance(data, torch.Tensor) and data.dim() == 2 and data.shape[1] == 768:
+                raise ValueError("augment= needs waveform input: the augmentations act on the audio and its log-mel, and an "
+                                 "(n, 768) embedding tensor has neither")
+            if not isinstance(target, torch.Tensor):
+                target = torch.as_tensor(target)
+            return _aug.augmented_embeddings(self, data, target.to(dev), augment, views=views, mixup_alpha=mixup_alpha, seed=seed,
+                                             sample_rate=sample_rate)
         if isinstance(data, torch.Tensor) and data.dim() == 2:
             emb = data
         else:
@@ -919,6 +934,57 @@ class ConvNeXt(nn.Module):
     def forward_frame_embeddings(self, x, mixup_lambda=None, sample_rate=None):
         """(B, L) -> NCHW (B, 768, T', 7) (convnext.py:369-402)."""
         return self._run(self._resampled(x, sample_rate), "frame")[0]
+
+    def forward_augmented(self, x, policy=None, plan=None, mixup_lambda=None, what="logits", generator=None, sample_rate=None):
+        """One forward with the reference's TRAINING-mode input transforms, the model in eval mode -- the backbone is frozen, the
+        transforms are what a fine-tuning epoch of the reference sees (pytorch/augment.py has the definitions): gain, roll and
+        speed perturbation of the waveform (convnext.py:288-295), SpecAugment stripes on the bn0'd log-mel (:308-309), mixup of
+        clips 2b and 2b + 1 (:312-313).  All of it runs on x's stream (acx_forward_augmented), nothing synchronises after the
+        plan's upload.
+        policy: an augment.AugmentPolicy (None: AugmentPolicy.reference(), SpecAugment only), drawn with `generator` (a torch
+        CPU generator; None: the global one); or plan: an augment.AugmentPlan drawn earlier (policy and generator unused).
+        mixup_lambda: B values (the reference's argument; B even) -- the outputs then have B / 2 rows.
+        what: "logits" -> {"clipwise_output", "clipwise_logits"}; "scene" -> {"scene": (rows, 768)}; "frame" -> {"frame":
+        (rows, 768, T', 7)}; each dict also has "plan", the AugmentPlan that was applied.  With AugmentPolicy.identity() and
+        no lambdas the outputs equal model(x) / forward_scene_embeddings / forward_frame_embeddings bit for bit."""
+        from . import augment as _aug
+        if what in _ffi.SEG_WHAT:
+            raise ValueError("forward_augmented has no segment outputs (what=%r): the augmented forwards are logits, scene and "
+                             "frame" % (what,))
+        if what not in _ffi.MODES:
+            raise ValueError("what must be 'logits', 'scene' or 'frame' (got %r)" % (what,))
+        x = self._resampled(x, sample_rate)
+        self._check_batch(x)
+        self._check_run(x.device)
+        x = x.detach().to(torch.float32).contiguous()
+        B, L = x.shape
+        if L < _ffi.MIN_SAMPLES:
+            raise RuntimeError("clip of %d samples is too short: kernel size can't be greater than actual input size "
+                               "(minimum is %d samples)" % (L, _ffi.MIN_SAMPLES))
+        if plan is None:
+            plan = _aug.draw_plan(_aug.AugmentPolicy.reference() if policy is None else policy, B, L, generator)
+        elif not isinstance(plan, _aug.AugmentPlan) or (plan.B, plan.L) != (B, L):
+            raise ValueError("plan must be an AugmentPlan of this batch (%d clips of %d samples)" % (B, L))
+        dev = x.device
+        lam = None
+        if mixup_lambda is not None:
+            lam = torch.as_tensor(mixup_lambda).detach().to(torch.float32).reshape(-1).contiguous()
+            lam = (lam if lam.is_cuda else lam.pin_memory()).to(dev, non_blocking=True)
+            if B % 2 or lam.numel() != B:
+                raise ValueError("mixup pairs clips 2b and 2b + 1: %d clips with %d lambdas (expected an even batch and one "
+                                 "lambda per clip)" % (B, lam.numel()))
+        rows = B // 2 if lam is not None else B
+        dplan = plan.to(dev)
+        with torch.cuda.device(dev):
+            ctx = self.native_context(dev)
+            ws = self._workspace(dev, ctx.workspace_bytes_augmented(B, L, dplan.wave_dev is not None, lam is not None, what))
+            out0, out1, _ = self._outputs(what, (rows,), ctx.classes, L, dev)
+            _ffi.check(_ffi.lib().acx_forward_augmented(ctx.handle, _ffi.ptr(x), B, L, _ffi.ptr(dplan.wave_dev),
+                                                        _ffi.ptr(dplan.spec_dev), _ffi.ptr(lam), _ffi.MODES[what], _ffi.ptr(out0),
+                                                        _ffi.ptr(out1), _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr(dev)))
+        if what == "logits":
+            return {"clipwise_output": out1, "clipwise_logits": out0, "plan": plan}
+        return {what: out0, "plan": plan}
 
     @classmethod
     def from_pretrained(cls, pretrained_checkpoint_path, map_location=None, use_auth_token=None):

@@ -19,7 +19,13 @@ ConvNeXt.classify / demo_convnext.py --softmax.  With a validation split the hea
 printed and the map written as <out>.calibration.npz -- demo_convnext.py --calibration takes it.
 --folds K cross-validates the settings of --grid-lr x --grid-weight-decay (default: the one --lr / --weight-decay pair) on the
 training split first, all K x settings fits advanced together on the GPU (ConvNeXt.cross_validate_head): one line per setting,
-the best marked; the run then continues as above with the best setting."""
+the best marked; the run then continues as above with the best setting.
+--augment reference fits the head as the reference fine-tunes -- on augmented views of the training clips instead of their
+plain embeddings (ConvNeXt.forward_augmented: SpecAugment stripes; "full" adds gain, roll and speed perturbation), --views K
+passes over them, --mixup-alpha A mixing clips and label rows pairwise (--loss bce).  The clips must share one length; validation,
+thresholds and calibration stay on the plain embeddings.
+
+    python demo_finetune.py --synthetic --augment reference --views 4 --mixup-alpha 0.5 --out /tmp/tagger"""
 import argparse
 import csv
 import os
@@ -87,6 +93,9 @@ def main():
     ap.add_argument("--folds", type=int, default=0, help="K-fold cross-validation of the grid on the training split first")
     ap.add_argument("--grid-lr", help="comma-separated learning rates for --folds (default: --lr)")
     ap.add_argument("--grid-weight-decay", help="comma-separated weight decays for --folds (default: --weight-decay)")
+    ap.add_argument("--augment", choices=("reference", "full"), help="fit on augmented views of the training clips")
+    ap.add_argument("--views", type=int, default=1, help="augmented passes over the training clips (--augment)")
+    ap.add_argument("--mixup-alpha", type=float, help="mixup of clip pairs and their label rows (--augment, --loss bce)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("this build runs on an MI355X; no GPU is visible")
@@ -132,10 +141,29 @@ def main():
     if ce and not bool((target.sum(dim=1) == 1).all()):
         sys.exit("--loss ce needs exactly one label per clip")
     extra = dict(loss="ce", label_smoothing=a.label_smoothing) if ce else {}
+    train_emb, train_target = emb[tr], target[tr]
+    if a.augment:
+        from audioset_convnext_inf_amd.pytorch import augment
+        if ce and a.mixup_alpha is not None:
+            sys.exit("--mixup-alpha gives soft label rows: use it with --loss bce")
+        rows = tr.tolist()
+        if a.mixup_alpha is not None and len(rows) % 2:
+            rows = rows[:-1]                    # mixup pairs clips
+        try:
+            train_emb, train_target = augment.augmented_embeddings(
+                model, [waves[i].cuda() for i in rows], target[torch.tensor(rows, device="cuda")], augment.policy_of(a.augment),
+                views=a.views, mixup_alpha=a.mixup_alpha, seed=a.seed, sample_rate=rate)
+        except ValueError as e:
+            sys.exit("--augment: %s" % e)
+        torch.cuda.synchronize()
+        print("augmented views: %d rows from %d clips (%s, %d views%s) in %.2f s" % (
+            train_emb.shape[0], len(rows), a.augment, a.views,
+            "" if a.mixup_alpha is None else ", mixup alpha %g" % a.mixup_alpha, time.perf_counter() - t1))
+        t1 = time.perf_counter()
     if a.folds:
         grid = {"lr": [float(v) for v in a.grid_lr.split(",")] if a.grid_lr else [a.lr],
                 "weight_decay": [float(v) for v in a.grid_weight_decay.split(",")] if a.grid_weight_decay else [a.weight_decay]}
-        cv = model.cross_validate_head(emb[tr], target[tr], folds=a.folds, grid=grid, seed=a.seed, refit=False, install=False,
+        cv = model.cross_validate_head(train_emb, train_target, folds=a.folds, grid=grid, seed=a.seed, refit=False, install=False,
                                        keep_fits=False, epochs=a.epochs, batch_size=a.batch_size, decoupled=a.adamw, **extra)
         torch.cuda.synchronize()
         for c, cfg in enumerate(cv.configs):
@@ -148,7 +176,7 @@ def main():
         print("cross-validation %.2f s (%d folds x %d settings); continuing with lr %g, weight decay %g"
               % (time.perf_counter() - t1, a.folds, len(cv.configs), a.lr, a.weight_decay))
         t1 = time.perf_counter()
-    fit = model.fit_head(emb[tr], target[tr], epochs=a.epochs, batch_size=a.batch_size, lr=a.lr, weight_decay=a.weight_decay,
+    fit = model.fit_head(train_emb, train_target, epochs=a.epochs, batch_size=a.batch_size, lr=a.lr, weight_decay=a.weight_decay,
                          decoupled=a.adamw, seed=a.seed, val=(emb[va], target[va]) if n_val else None, **extra)
     torch.cuda.synchronize()
     t2 = time.perf_counter()

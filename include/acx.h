@@ -558,6 +558,61 @@ ACX_API int acx_resampler_create(int hip_device, int orig_hz, int new_hz, acx_re
 ACX_API void acx_resampler_destroy(acx_resampler* rs);
 ACX_API int acx_resample(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, void* stream);
 
+/* ---- augmented forwards: the reference's training-mode input transforms with the backbone frozen ---------------------------
+ * The reference fine-tunes with the model in train mode (finetune_audiocaps.py): every forward then sees, in this order,
+ * pydub_augment, roll_augment and SpeedPerturbation on the waveform (augmentations.py:266-351, convnext.py:288-295),
+ * SpecAugmentation on the bn0'd log-mel (convnext.py:205-210, 308-309) and do_mixup (pytorch_utils.py:20-36, convnext.py:312-313).
+ * Here they are two kernels driven by PLANS -- per-clip structs the caller draws on the host (pytorch/augment.py: draw_plan) and
+ * keeps in device memory -- so that the calls allocate nothing, synchronise nothing and are capturable.  The definitions the
+ * kernels equal bit for bit are augment_wave_host / augment_spec_host of pytorch/augment.py.
+ *
+ * acx_wave_aug (40 bytes), one per clip of L samples: the composite of gain, roll, nearest-neighbour stretch and pad / crop,
+ *     out[i] = gain * in[(src(i + shift) - roll) mod L]   if 0 <= i + shift < n_out, else +0
+ *     src(j) = min(L - 1, rint(j * step))                 evaluated in FLOAT64, ties to even
+ *   step = 1 / rate; n_out = ceil(L / step), the stretched length (Resample.resample_nearest); shift = the crop's start
+ *   (n_out > L: 0 .. n_out - L) or minus the left padding (n_out < L: n_out - L .. 0); roll reduced to 0 <= roll < L
+ *   (x.roll(r): out[i] = in[(i - r) mod L]); gain = float32 of 10 ** (dB / 20).  The reference forms src with a float32
+ *   torch.arange whose values depend on torch's CPU vectoriser and thread count; where the step is exact in binary every scheme
+ *   agrees, and that is where this definition is pinned to it.
+ * acx_spec_aug (64 bytes), one per clip of T = acx_num_frames(L) frames: up to ACX_AUG_MAX_STRIPES stripes per axis, frames
+ *   [t_bgn, t_bgn + t_len) and mel bins [f_bgn, f_bgn + f_len) become +0.0 (DropStripes zeroes AFTER bn0); a stripe of length
+ *   0 is legal and is how unused slots are filled.
+ * lambda: B float32 values on the device; output row b = fl(mask(row 2b) * lambda[2b]) + fl(mask(row 2b + 1) * lambda[2b + 1]),
+ *   two rounded products and one rounded sum, each row masked with its own stripes first.  B must be even.
+ *
+ * acx_augment_plan_check: HOST arrays (either may be null) -- stripe bounds, 0 <= roll < L, n_out == ceil(L / step) in
+ *   1 .. 2^31 - 1, shift in its range; call it before uploading a plan.  No device is touched.
+ * acx_augment_wave: wav, out (B, L) device, out != wav.  acx_augment_spec: feat (B, T, 224), 16-byte aligned; lambda == null: the
+ *   masks are written IN PLACE (out == feat, only the masked elements are stored, plan non-null); lambda != null: out is a second
+ *   (B / 2, T, 224) buffer, feat is left untouched, plan may be null.  One kernel each on `stream`.
+ * acx_forward_features: acx_forward from the stem on -- feat = (B, T, 224) bn0'd log-mel rows (acx_logmel_bn0's output, or the
+ *   caller's own features), 16-byte aligned, T = acx_num_frames(L).  Same sub-batch split, same workspace (acx_workspace_bytes),
+ *   same outputs as acx_forward; acx_forward_features(acx_logmel_bn0(wav)) equals acx_forward(wav) bit for bit.
+ * acx_forward_augmented: wave kernel (wave_plan non-null), the frontend over all B clips, spec kernel (spec_plan or lambda
+ *   non-null), then acx_forward_features over B clips -- B / 2 with lambda, as the reference's output has.  Its extra buffers are
+ *   carved from its own workspace, acx_workspace_bytes_augmented(ctx, B, L, wave_plan != null, lambda != null, mode);
+ *   acx_workspace_bytes does not change.  With all three null it equals acx_forward bit for bit. */
+#define ACX_AUG_MAX_STRIPES 4
+typedef struct acx_wave_aug {
+    double step;
+    int64_t n_out, shift, roll;
+    float gain;
+    int32_t reserved;
+} acx_wave_aug;
+typedef struct acx_spec_aug {
+    int32_t t_bgn[ACX_AUG_MAX_STRIPES], t_len[ACX_AUG_MAX_STRIPES], f_bgn[ACX_AUG_MAX_STRIPES], f_len[ACX_AUG_MAX_STRIPES];
+} acx_spec_aug;
+ACX_API int acx_augment_plan_check(int B, int64_t L, const acx_wave_aug* wave, const acx_spec_aug* spec);
+ACX_API int acx_augment_wave(const float* wav, int B, int64_t L, const acx_wave_aug* plan, float* out, void* stream);
+ACX_API int acx_augment_spec(float* feat, int B, int T, const acx_spec_aug* plan, const float* lambda, float* out, void* stream);
+ACX_API int acx_forward_features(acx_ctx* ctx, const float* feat, int B, int64_t L, int mode, float* out0, float* out1,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+ACX_API int acx_workspace_bytes_augmented(const acx_ctx* ctx, int B, int64_t L, int has_wave_plan, int has_lambda, int mode,
+                                          size_t* out_bytes);
+ACX_API int acx_forward_augmented(acx_ctx* ctx, const float* wav, int B, int64_t L, const acx_wave_aug* wave_plan,
+                                  const acx_spec_aug* spec_plan, const float* lambda, int mode, float* out0, float* out1,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU: the one collective of the path -----------------------------------------------------------------
  * One process per GPU, full weight replica, clips sharded; logits / probabilities / scene rows are all-gathered over xGMI by
  * RCCL (ncclAllGather), frame embeddings stay sharded.  The reference has no inference-time collective (training DDP only,
