@@ -215,6 +215,12 @@ SIGNATURES = {
                                       _padam, _c_i64, _c_dbl, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_head_fit_grad_ce": (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_int, _c_dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _c_sz, _vp]),
+    "acx_head_fit_mil_workspace_bytes": (_c_int, [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_head_fit_step_mil": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _c_int,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _padam, _c_i64, _c_dbl, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_head_fit_grad_mil": (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_int, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_int, _c_int,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_segment_pool": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _vp, _vp]),
     "acx_head_fit_group_workspace_bytes": (_c_int, [_c_int, _c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_head_fit_plan_bytes": (_c_int, [_c_int, _c_i64, ctypes.POINTER(_c_sz)]),
     "acx_head_fit_plan_fill": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _padam, _vp, _vp, _c_sz]),
@@ -555,6 +561,21 @@ FIT_BAD_LABEL = 2                              # acx_head_fit_step_ce / acx_head
 def head_fit_ce_workspace_bytes(rows_max, classes):
     """Workspace of acx_head_fit_step_ce / acx_head_fit_grad_ce for steps of up to rows_max rows (host only)."""
     return _query(lib().acx_head_fit_ce_workspace_bytes, _c_sz, int(rows_max), int(classes))
+
+
+FIT_BAD_BAG = 4                                # acx_head_fit_step_mil / acx_head_fit_grad_mil / acx_segment_pool: a bad bag_off entry
+FIT_MAX_ROWS = 1 << 22                         # rows (segment rows, bags) of one step
+MIL_MAX, MIL_MEAN, MIL_LINEAR, MIL_EXP = 0, 1, 2, 3     # enum acx_mil_pool
+
+
+def head_fit_mil_workspace_bytes(seg_rows_max, bags_max, classes):
+    """Workspace of acx_head_fit_step_mil / acx_head_fit_grad_mil for steps of up to seg_rows_max rows in bags_max bags (host only)."""
+    return _query(lib().acx_head_fit_mil_workspace_bytes, _c_sz, int(seg_rows_max), int(bags_max), int(classes))
+
+
+def segment_pool(logits, ld, bag_off, bags, classes, pool, out, status, stream):
+    """acx_segment_pool on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_segment_pool(logits, int(ld), bag_off, int(bags), int(classes), int(pool), out, status, stream))
 
 
 FIT_MAX_JOBS = 256                             # ACX_FIT_MAX_JOBS: jobs of one acx_head_fit_group_step

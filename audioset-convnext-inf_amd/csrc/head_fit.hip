@@ -125,6 +125,9 @@ struct FitGradP {
 
 enum { kLossBce = 0, kLossCe = 1 };
 
+// sigmoid(z) from ex = exp(-|z|): 1 / (1 + ex) or ex / (1 + ex), never an overflow (the gradient pass and the bag pass)
+__device__ __forceinline__ float fit_sigmoid(float zz, float ex) { return (zz >= 0.f ? 1.f : ex) / (1.f + ex); }
+
 // The tile body of the gradient pass.  LOSS = kLossBce: the whole of fit_grad_kernel.  LOSS = kLossCe: the logits alone go
 // to p.z (the softmax needs whole rows: fit_ce_row_kernel); Y, G, part and inv are not read.  bid: the tile's number in p's own
 // tiling (blockIdx.x in a single call; a group's block resolves its job first).
@@ -186,8 +189,7 @@ __device__ __forceinline__ void fit_grad_tile(const FitGradP& p, unsigned bid) {
             const float y = p.y_u8 ? (static_cast<const unsigned char*>(p.Y)[yo] ? 1.f : 0.f) : static_cast<const float*>(p.Y)[yo];
             // sigmoid and both logarithms from e = exp(-|z|): log p = min(z, 0) - log1p(e), log(1 - p) = min(-z, 0) - log1p(e)
             const float ex = expf(-fabsf(zz));
-            const float den = 1.f + ex;
-            const float pr = (zz >= 0.f ? 1.f : ex) / den;
+            const float pr = fit_sigmoid(zz, ex);
             const float l1 = log1pf(ex);
             const float lp = fmaxf(fminf(zz, 0.f) - l1, -100.f), lq = fmaxf(fminf(-zz, 0.f) - l1, -100.f);
             lsum -= y * lp + (1.f - y) * lq;
@@ -362,6 +364,161 @@ __global__ __launch_bounds__(256) void adam_update_kernel(float* __restrict__ pa
     float w = param[i], mm = m[i], vv = v[i];
     adam_elem(w, grad[i], mm, vv, a.amsgrad ? vmax + i : nullptr, a);
     param[i] = w; m[i] = mm; v[i] = vv;
+}
+
+// ---- weak labels: the bag pass of acx_head_fit_step_mil / acx_head_fit_grad_mil, and acx_segment_pool ----------------------------
+// A clip is a bag of S segments and only the clip has a label (include/acx.h, "sound event detection heads from clip-level
+// labels").  Between the logits launch (fit_logits_kernel on idx = seg_idx) and the update launch (fit_update_kernel on the same
+// rows) this pass turns z (seg_rows, N) into G (seg_rows, N), the pooled P (bags, N) and one loss partial per item.
+// An item is (bag, chunk of 64 consecutive classes), owned by ONE WAVE, four items per workgroup: lane l walks the column of class
+// 64 chunk + l over the bag's rows twice -- statistics, then G -- in ascending t.  A row's read is one coalesced 256-byte line per
+// wave; a lane's sums depend on its own column alone: no LDS, no barrier, no atomics on floats, the same bits on every run.  The
+// column is not staged in LDS, because S has no bound (an hour-long recording is 11 250 segments).  The second walk re-reads what
+// the first one brought in: a 64-bag step of 31 segments and 527 classes is 4 MiB of z in all, an XCD's L2; the columns of an
+// hour-long bag (2.8 MiB per chunk, eight chunks in flight) come back from the Infinity Cache instead.  With 576 waves for such a
+// step occupancy is no concern (24 .. 32 VGPRs, no scratch); what hides the latency of the walks is kMilAhead independent row
+// loads in flight per lane, while the arithmetic stays in t order.  "max" needs no second read: one row of a column has a gradient.
+// GRAD = false is the forward alone (acx_segment_pool): the same functions, the same P.
+constexpr int kMilAhead = 8;
+enum { kMilMax = ACX_MIL_MAX, kMilMean = ACX_MIL_MEAN, kMilLinear = ACX_MIL_LINEAR, kMilExp = ACX_MIL_EXP };
+
+struct FitMilP {
+    const float* z; long long ld_z;                    // (seg_rows, classes) logits
+    const int* bag_off; int bags; int seg_rows;        // bag i: rows [bag_off[i], bag_off[i + 1]); seg_rows: the bound of the clamp
+    int N; int chunks;                                 // chunks = ceil(N / 64)
+    float* P; long long ld_p;                          // (bags, classes)
+    // GRAD only
+    const void* Y; int y_u8; long long ld_y; long long n_bags; const long long* bag_idx;
+    float* G; float* part; float inv;
+    int* status;
+};
+
+// Row t of a lane's column joins its running statistics (a, b, ts): MAX: a = the maximum so far and ts the FIRST row that attains
+// it; MEAN: a = sum q; LINEAR: a = sum q, b = sum q q; EXP: a = sum e^q, b = sum q e^q.  Every product is rounded before it is added.
+template <int POOL>
+__device__ __forceinline__ void mil_accumulate(float zt, int t, float& a, float& b, int& ts) {
+#pragma clang fp contract(off)
+    if (POOL == kMilMax) {
+        if (zt > a) { a = zt; ts = t; }
+        return;
+    }
+    const float q = fit_sigmoid(zt, expf(-fabsf(zt)));
+    if (POOL == kMilMean) {
+        a += q;
+    } else if (POOL == kMilLinear) {
+        a += q;
+        b += q * q;
+    } else {
+        const float e = expf(q);
+        a += e;
+        b += q * e;
+    }
+}
+
+// The pooled probability of a bag of S rows from its statistics.  Termwise q q <= q and q e^q <= e^q and both sums run in the
+// same order, so b <= a and P <= 1 in fp32 as well.
+template <int POOL>
+__device__ __forceinline__ float mil_pooled(float a, float b, int S) {
+    if (S == 0) return 0.f;
+    if (POOL == kMilMax) return fit_sigmoid(a, expf(-fabsf(a)));
+    if (POOL == kMilMean) return a / (float)S;
+    return a == 0.f ? 0.f : b / a;                     // LINEAR: every q underflowed; EXP: a >= S
+}
+
+// G of row t: dL/dP dP/dq_t q_t (1 - q_t) inv, the products taken from the left.
+template <int POOL>
+__device__ __forceinline__ float mil_grad_elem(float zt, float a, float P, float dLdP, float invS, float inv) {
+#pragma clang fp contract(off)
+    const float q = fit_sigmoid(zt, expf(-fabsf(zt)));
+    float d;
+    if (POOL == kMilMax) {
+        d = 1.f;
+    } else if (POOL == kMilMean) {
+        d = invS;
+    } else if (POOL == kMilLinear) {
+        d = a == 0.f ? 0.f : (2.f * q - P) / a;
+    } else {
+        d = expf(q) * ((1.f + q) - P) / a;
+    }
+    return ((dLdP * d) * (q * (1.f - q))) * inv;
+}
+
+template <int POOL, bool GRAD>
+__global__ __launch_bounds__(kFitThreads) void fit_mil_bag_kernel(FitMilP p) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long item = (long long)blockIdx.x * 4 + wave;
+    if (item >= (long long)p.bags * p.chunks) return;              // a whole wave, and no barrier follows
+    const int bag = (int)(item / p.chunks), chunk = (int)(item % p.chunks);
+    const int c = chunk * 64 + lane;
+    const bool live = c < p.N;
+    const int cc = live ? c : p.N - 1;                             // lanes past N repeat the last class: loads stay inside z
+
+    // the bag's rows, held inside [0, seg_rows] and in order; a gradient pass covers every row of G whatever bag_off holds: the
+    // first bag starts at 0, the last one ends at seg_rows
+    int lo = p.bag_off[bag], hi = p.bag_off[bag + 1];
+    bool bad = lo < 0 || lo > p.seg_rows || hi < lo || hi > p.seg_rows;
+    lo = min(max(lo, 0), p.seg_rows);
+    hi = min(max(hi, lo), p.seg_rows);
+    if (GRAD) {
+        if (bag == 0 && lo != 0) { bad = true; lo = 0; }
+        if (bag == p.bags - 1 && hi != p.seg_rows) { bad = true; hi = p.seg_rows; }
+    }
+    if (bad && chunk == 0 && lane == 0) atomicOr(p.status, ACX_FIT_BAD_BAG);
+    const int S = hi - lo;
+
+    const float* __restrict__ zc = p.z + cc;
+    float a = POOL == kMilMax ? -__builtin_inff() : 0.f, b = 0.f;
+    int ts = lo;
+    int t = lo;
+    // groups of kMilAhead rows: every load is issued (rows past the bag repeat its last one) before the first is used; the rows
+    // past the bag are left out of the arithmetic by a wave-uniform test, so a short last group costs one round trip, not one per row
+    for (; t < hi; t += kMilAhead) {
+        float v[kMilAhead];
+#pragma unroll
+        for (int j = 0; j < kMilAhead; ++j) v[j] = zc[(long long)min(t + j, hi - 1) * p.ld_z];
+#pragma unroll
+        for (int j = 0; j < kMilAhead; ++j)
+            if (t + j < hi) mil_accumulate<POOL>(v[j], t + j, a, b, ts);
+    }
+    const float P = mil_pooled<POOL>(a, b, S);
+    if (live) p.P[(long long)bag * p.ld_p + c] = P;
+    if (!GRAD) return;
+
+    long long yb = p.bag_idx[bag];
+    if (yb < 0 || yb >= p.n_bags) {
+        if (chunk == 0 && lane == 0) atomicOr(p.status, ACX_FIT_BAD_INDEX);
+        yb = yb < 0 ? 0 : p.n_bags - 1;
+    }
+    const long long yo = yb * p.ld_y + cc;
+    const float y = p.y_u8 ? (static_cast<const unsigned char*>(p.Y)[yo] ? 1.f : 0.f) : static_cast<const float*>(p.Y)[yo];
+    // torch's binary_cross_entropy on a probability, and its backward: both logarithms held at -100, P (1 - P) at 1e-12
+    const float lp = fmaxf(logf(P), -100.f), lq = fmaxf(log1pf(-P), -100.f);
+    float l = live ? -(y * lp + (1.f - y) * lq) : 0.f;
+    l = wave_sum(l);
+    if (lane == 0) p.part[item] = l;
+    const float dLdP = (P - y) / fmaxf(P * (1.f - P), 1e-12f);
+    const float invS = 1.f / (float)max(S, 1);
+
+    float* __restrict__ gc = p.G + c;
+    if (POOL == kMilMax) {                                         // one row of the column has a gradient: no second read
+        const float g = S ? mil_grad_elem<POOL>(a, a, P, dLdP, invS, p.inv) : 0.f;
+        if (live)
+            for (t = lo; t < hi; ++t) gc[(long long)t * p.N] = t == ts ? g : 0.f;
+        return;
+    }
+    t = lo;
+    for (; t < hi; t += kMilAhead) {
+        float v[kMilAhead];
+#pragma unroll
+        for (int j = 0; j < kMilAhead; ++j) v[j] = zc[(long long)min(t + j, hi - 1) * p.ld_z];
+#pragma unroll
+        for (int j = 0; j < kMilAhead; ++j) {
+            const float g = mil_grad_elem<POOL>(v[j], a, P, dLdP, invS, p.inv);
+            if (live && t + j < hi) gc[(long long)(t + j) * p.N] = g;
+        }
+    }
 }
 
 // ---- groups: J independent fits over the same embeddings, one launch per stage for all of them (acx_head_fit_group_step) -----
@@ -625,11 +782,8 @@ static int fit_launch(const FitCall& c, float* z, float* G, float* part, const F
 // The three launches.  BOTH matrix launches take the update kernel's tile rule, a function of (classes, CUs) alone: the logits
 // of a row then have the same bits in every batch, whatever `rows` is (the two tile shapes add the 768 products in different
 // orders, so a rule that looked at `rows`, as fit_launch's does for BCE, would let the short last batch of an epoch change them).
-static int fit_ce_launch(const FitCall& c, float* z, float* G, float* part, const FitUpdP& u, bool apply, float* loss, hipStream_t s) {
-    int cus = 0;
-    ACX_TRY(cu_count_of_current_device(&cus));
+static int fit_launch_logits(const FitCall& c, float* z, int cus, hipStream_t s) {
     const int rows = (int)c.rows, N = c.classes;
-    const float inv = (float)(1.0 / (double)rows);
     FitGradP g = fit_grad_params(c, z);
     const bool g32 = fit_classes_wide(N, cus);
     const int gs = g32 ? 32 : 16;
@@ -638,15 +792,112 @@ static int fit_ce_launch(const FitCall& c, float* z, float* G, float* part, cons
     if (g32) launch_kernel(&fit_logits_kernel<32>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
     else launch_kernel(&fit_logits_kernel<16>, dim3(gtiles), dim3(kFitThreads), 0, s, g);
     ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+static int fit_ce_launch(const FitCall& c, float* z, float* G, float* part, const FitUpdP& u, bool apply, float* loss, hipStream_t s) {
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    const int rows = (int)c.rows, N = c.classes;
+    const float inv = (float)(1.0 / (double)rows);
+    ACX_TRY(fit_launch_logits(c, z, cus, s));
 
     FitCeRowP r;
-    r.z = z; r.labels = static_cast<const long long*>(c.Y); r.idx = g.idx; r.n_total = c.n_total; r.rows = rows; r.N = N;
+    r.z = z; r.labels = static_cast<const long long*>(c.Y); r.idx = reinterpret_cast<const long long*>(c.idx); r.n_total = c.n_total; r.rows = rows; r.N = N;
     r.q_hit = (float)((1.0 - c.eps) + c.eps / N); r.q_miss = (float)(c.eps / N); r.ome = (float)(1.0 - c.eps);
     r.inv = inv; r.G = G; r.part = part; r.status = (int*)c.status;
     if (N <= kSoftWaveMaxN) launch_kernel(&fit_ce_row_kernel<64>, dim3((rows + 3) / 4), dim3(kFitThreads), 0, s, r);
     else launch_kernel(&fit_ce_row_kernel<256>, dim3(rows), dim3(kFitThreads), 0, s, r);
     ACX_HIP(hipGetLastError());
     return fit_launch_update(u, c, G, part, rows, loss, inv, cus, apply, s);
+}
+
+// ---- weak labels: host side -------------------------------------------------------------------------------------------------
+// workspace: G, z (seg_rows_max, classes), P (bags_max, classes) fp32, then one loss partial per (bag, chunk of 64 classes)
+struct MilLayout { size_t z, P, part, total; };
+static MilLayout fit_mil_layout(long long seg_rows, long long bags, long long N) {
+    MilLayout l;
+    const size_t gb = align_up((size_t)seg_rows * N * 4);
+    l.z = gb;
+    l.P = 2 * gb;
+    l.part = l.P + align_up((size_t)bags * N * 4);
+    l.total = l.part + align_up((size_t)bags * ((N + 63) / 64) * 4);
+    return l;
+}
+
+static int fit_mil_check_pool(const char* who, int pool) {
+    if (pool != ACX_MIL_MAX && pool != ACX_MIL_MEAN && pool != ACX_MIL_LINEAR && pool != ACX_MIL_EXP)
+        ACX_FAIL(ACX_ERR_ARG, "%s: pool %d (expected ACX_MIL_MAX, ACX_MIL_MEAN, ACX_MIL_LINEAR or ACX_MIL_EXP)", who, pool);
+    return ACX_OK;
+}
+
+static int fit_mil_check_shape(const char* who, int64_t seg_rows, int64_t bags, int classes) {
+    if (bags < 1) ACX_FAIL(ACX_ERR_ARG, "%s: bags = %lld (expected >= 1)", who, (long long)bags);
+    if (seg_rows < 1) ACX_FAIL(ACX_ERR_ARG, "%s: seg_rows = %lld (expected >= 1)", who, (long long)seg_rows);
+    if (classes < 1 || classes > ACX_MAX_CLASSES)
+        ACX_FAIL(ACX_ERR_ARG, "%s: classes = %d (expected 1 .. %d)", who, classes, ACX_MAX_CLASSES);
+    if (seg_rows > kFitMaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: seg_rows = %lld (at most 2^22 per step)", who, (long long)seg_rows);
+    if (bags > kFitMaxRows || bags * ((classes + 63) / 64) > (1LL << 30))
+        ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: bags = %lld (at most 2^22 per step, and 2^30 chunks of 64 classes)", who, (long long)bags);
+    return ACX_OK;
+}
+
+struct MilCall {        // what a weak-label step has beside FitCall (whose idx / rows are seg_idx / seg_rows)
+    int64_t n_bags; const int32_t* bag_off; const int64_t* bag_idx; int64_t bags; int pool;
+};
+
+static int fit_mil_check_call(const char* who, const FitCall& c, const MilCall& m, MilLayout* lay) {
+    if (!c.E) ACX_FAIL(ACX_ERR_ARG, "%s: E is null", who);
+    if (!c.Y) ACX_FAIL(ACX_ERR_ARG, "%s: target is null", who);
+    if (!c.idx) ACX_FAIL(ACX_ERR_ARG, "%s: seg_idx is null", who);
+    if (!m.bag_off) ACX_FAIL(ACX_ERR_ARG, "%s: bag_off is null", who);
+    if (!m.bag_idx) ACX_FAIL(ACX_ERR_ARG, "%s: bag_idx is null", who);
+    if (!c.W) ACX_FAIL(ACX_ERR_ARG, "%s: W is null", who);
+    if (!c.b) ACX_FAIL(ACX_ERR_ARG, "%s: b is null", who);
+    if (!c.status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    if (!c.ws) ACX_FAIL(ACX_ERR_ARG, "%s: workspace is null", who);
+    if (c.y_dtype != ACX_TARGET_F32 && c.y_dtype != ACX_TARGET_U8)
+        ACX_FAIL(ACX_ERR_ARG, "%s: target_dtype %d (expected ACX_TARGET_F32 or ACX_TARGET_U8)", who, c.y_dtype);
+    ACX_TRY(fit_mil_check_shape(who, c.rows, m.bags, c.classes));
+    ACX_TRY(fit_mil_check_pool(who, m.pool));
+    if (m.n_bags < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n_bags_total = %lld (expected >= 1)", who, (long long)m.n_bags);
+    ACX_TRY(fit_check_rows(who, c));
+    if (c.ld_y < c.classes)
+        ACX_FAIL(ACX_ERR_ARG, "%s: ld_target = %lld is shorter than %d classes", who, (long long)c.ld_y, c.classes);
+    *lay = fit_mil_layout(c.rows, m.bags, c.classes);
+    return check_workspace_for(who, c.ws, c.ws_bytes, lay->total);
+}
+
+template <bool GRAD>
+static int fit_mil_launch_bag(const FitMilP& p, int pool, hipStream_t s) {
+    const dim3 grid((unsigned)(((long long)p.bags * p.chunks + 3) / 4)), block(kFitThreads);
+    switch (pool) {
+        case ACX_MIL_MAX: launch_kernel(&fit_mil_bag_kernel<kMilMax, GRAD>, grid, block, 0, s, p); break;
+        case ACX_MIL_MEAN: launch_kernel(&fit_mil_bag_kernel<kMilMean, GRAD>, grid, block, 0, s, p); break;
+        case ACX_MIL_LINEAR: launch_kernel(&fit_mil_bag_kernel<kMilLinear, GRAD>, grid, block, 0, s, p); break;
+        default: launch_kernel(&fit_mil_bag_kernel<kMilExp, GRAD>, grid, block, 0, s, p); break;
+    }
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+// The three launches: the logits of the segment rows (the cross-entropy step's launch: a row's z bits are acx_head_fit_grad_ce's),
+// the bag pass, and the update over the segment rows with 1 / (bags classes) on the loss.
+static int fit_mil_launch(const FitCall& c, const MilCall& m, float* z, float* P, float* G, float* part, const FitUpdP& u, bool apply,
+                          float* loss, hipStream_t s) {
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    const int N = c.classes, bags = (int)m.bags;
+    const float inv = (float)(1.0 / ((double)bags * (double)N));
+    ACX_TRY(fit_launch_logits(c, z, cus, s));
+    FitMilP p{};
+    p.z = z; p.ld_z = N; p.bag_off = m.bag_off; p.bags = bags; p.seg_rows = (int)c.rows; p.N = N; p.chunks = (N + 63) / 64;
+    p.P = P; p.ld_p = N;
+    p.Y = c.Y; p.y_u8 = c.y_dtype == ACX_TARGET_U8; p.ld_y = c.ld_y; p.n_bags = m.n_bags;
+    p.bag_idx = reinterpret_cast<const long long*>(m.bag_idx);
+    p.G = G; p.part = part; p.inv = inv; p.status = (int*)c.status;
+    ACX_TRY(fit_mil_launch_bag<true>(p, m.pool, s));
+    return fit_launch_update(u, c, G, part, bags * p.chunks, loss, inv, cus, apply, s);
 }
 
 // A job's slice of the group workspace: the single call's layout of its loss (z_off is unused for BCE).
@@ -807,6 +1058,66 @@ int acx_head_fit_grad_ce(const float* E, int64_t ld_e, int64_t n_rows_total, con
     FitUpdP u{};
     ACX_TRY(fit_grad_args(who, z, G, dW, db, loss, &u));
     return fit_ce_launch(c, z, G, reinterpret_cast<float*>(static_cast<char*>(ws) + part_off), u, false, loss, (hipStream_t)stream);
+}
+
+int acx_head_fit_mil_workspace_bytes(int64_t seg_rows_max, int64_t bags_max, int classes, size_t* out_bytes) {
+    static const char* who = "acx_head_fit_mil_workspace_bytes";
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "%s: out_bytes is null", who);
+    ACX_TRY(fit_mil_check_shape(who, seg_rows_max, bags_max, classes));
+    *out_bytes = fit_mil_layout(seg_rows_max, bags_max, classes).total;
+    return ACX_OK;
+}
+
+int acx_head_fit_step_mil(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                          int64_t ld_target, int64_t n_bags_total, const int64_t* seg_idx, int64_t seg_rows, const int32_t* bag_off,
+                          const int64_t* bag_idx, int64_t bags, int classes, int pool, float* W, float* b, float* mW, float* vW,
+                          float* vmaxW, float* mb, float* vb, float* vmaxb, const acx_adam* hp, int64_t step_t, double lr,
+                          float* loss_out, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    static const char* who = "acx_head_fit_step_mil";
+    const FitCall c{E, ld_e, n_rows_total, target, "target", target_dtype, ld_target, 0.0, seg_idx, seg_rows, classes, W, b, status,
+                    ws, ws_bytes};
+    const MilCall m{n_bags_total, bag_off, bag_idx, bags, pool};
+    MilLayout lay;
+    ACX_TRY(fit_mil_check_call(who, c, m, &lay));
+    FitUpdP u{};
+    ACX_TRY(fit_step_args(who, W, b, mW, vW, vmaxW, mb, vb, vmaxb, hp, step_t, lr, loss_out, &u));
+    char* w = static_cast<char*>(ws);
+    return fit_mil_launch(c, m, reinterpret_cast<float*>(w + lay.z), reinterpret_cast<float*>(w + lay.P), reinterpret_cast<float*>(w),
+                          reinterpret_cast<float*>(w + lay.part), u, true, loss_out, (hipStream_t)stream);
+}
+
+int acx_head_fit_grad_mil(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                          int64_t ld_target, int64_t n_bags_total, const int64_t* seg_idx, int64_t seg_rows, const int32_t* bag_off,
+                          const int64_t* bag_idx, int64_t bags, int classes, int pool, const float* W, const float* b, float* z,
+                          float* P, float* G, float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes,
+                          void* stream) {
+    static const char* who = "acx_head_fit_grad_mil";
+    const FitCall c{E, ld_e, n_rows_total, target, "target", target_dtype, ld_target, 0.0, seg_idx, seg_rows, classes, W, b, status,
+                    ws, ws_bytes};
+    const MilCall m{n_bags_total, bag_off, bag_idx, bags, pool};
+    MilLayout lay;
+    ACX_TRY(fit_mil_check_call(who, c, m, &lay));
+    if (!P) ACX_FAIL(ACX_ERR_ARG, "%s: an output (z, P, G, dW, db, loss) is null", who);
+    FitUpdP u{};
+    ACX_TRY(fit_grad_args(who, z, G, dW, db, loss, &u));
+    return fit_mil_launch(c, m, z, P, G, reinterpret_cast<float*>(static_cast<char*>(ws) + lay.part), u, false, loss,
+                          (hipStream_t)stream);
+}
+
+int acx_segment_pool(const float* logits, int64_t ld, const int32_t* bag_off, int64_t bags, int classes, int pool, float* out,
+                     int32_t* status, void* stream) {
+    static const char* who = "acx_segment_pool";
+    if (!logits) ACX_FAIL(ACX_ERR_ARG, "%s: logits is null", who);
+    if (!bag_off) ACX_FAIL(ACX_ERR_ARG, "%s: bag_off is null", who);
+    if (!out) ACX_FAIL(ACX_ERR_ARG, "%s: out is null", who);
+    if (!status) ACX_FAIL(ACX_ERR_ARG, "%s: status is null", who);
+    ACX_TRY(fit_mil_check_shape(who, 1, bags, classes));
+    ACX_TRY(fit_mil_check_pool(who, pool));
+    if (ld < classes) ACX_FAIL(ACX_ERR_ARG, "%s: ld = %lld is shorter than %d classes", who, (long long)ld, classes);
+    FitMilP p{};
+    p.z = logits; p.ld_z = ld; p.bag_off = bag_off; p.bags = (int)bags; p.seg_rows = 0x7ffffff0;     // the caller owns the rows
+    p.N = classes; p.chunks = (classes + 63) / 64; p.P = out; p.ld_p = classes; p.status = (int*)status;
+    return fit_mil_launch_bag<false>(p, pool, (hipStream_t)stream);
 }
 
 int acx_adam_update(float* param, const float* grad, float* m, float* v, float* vmax, int64_t n, const acx_adam* hp,

@@ -818,6 +818,41 @@ class ConvNeXt(nn.Module):
         self._install_fit(fit)
         return fit
 
+    def fit_sed_head(self, data, target, pooling="max", pool=3, sample_rate=None, **kw):
+        """Train a sound event detection head from CLIP-level labels on this (frozen) backbone and install it
+        (pytorch/finetune.py, fit_sed_head): the head sees every 0.32 s segment embedding, the segment probabilities are pooled
+        over the clip (`pooling`: "max" -- what forward_segments' "clipwise_output" and detect_events read --, "mean", "linear",
+        "exp") and the loss is taken on the pooled probability: the path detect_events / psds take at inference, which a
+        fit_head on scene embeddings never sees.  data: waveforms at `sample_rate` -- a (B, L) tensor or a list of 1-D clips of
+        any lengths, whose segment embeddings are computed with the `pool` that detection will use (forward_segment_embeddings /
+        forward_varlen(what="segment_embeddings")) -- or segment embeddings as finetune.fit_sed_head takes them ((B, S, 768), a
+        list of (S_i, 768), (packed, lengths)); target: (clips, N); **kw: fit_sed_head's settings.  The head is installed as
+        fit_head installs its own; the model stays in eval mode.  Returns the HeadFit."""
+        from . import finetune as _ft
+        _ft.check_pooling(pooling)
+        dev = self.head_audioset.weight.device
+        is_emb = ((isinstance(data, torch.Tensor) and data.dim() == 3)
+                  or (isinstance(data, tuple) and len(data) == 2 and isinstance(data[0], torch.Tensor) and data[0].dim() == 2
+                      and data[0].shape[1] == _ft.EMBED_DIM and not (isinstance(data[1], torch.Tensor) and data[1].dim() == 2))
+                  or (isinstance(data, (list, tuple)) and len(data) > 0
+                      and all(isinstance(d, torch.Tensor) and d.dim() == 2 for d in data)))
+        if is_emb:
+            segments = data
+        else:
+            self._check_segment_call(pool)
+            with torch.no_grad():
+                if isinstance(data, torch.Tensor):
+                    segments = self.forward_segment_embeddings(data.to(dev), pool=pool, sample_rate=sample_rate)
+                else:
+                    clips = [torch.as_tensor(c, dtype=torch.float32).to(dev) for c in data]
+                    segments = [s.clone() for s in self.forward_varlen(clips, what="segment_embeddings", sample_rate=sample_rate,
+                                                                       pool=pool)]
+        if isinstance(target, torch.Tensor) and target.device != dev:
+            target = target.to(dev)
+        fit = _ft.fit_sed_head(segments, target, pooling=pooling, **kw)
+        self._install_fit(fit)
+        return fit
+
     def cross_validate_head(self, data, target, sample_rate=None, install=True, augment=None, views=1, mixup_alpha=None, **kw):
         """k-fold cross-validation of a new head over a grid of settings (pytorch/finetune.py, cross_validate_head): data and
         target exactly as fit_head takes them; **kw: folds=, grid=, fold_ids=, stratify=, metric=, refit= and fit_head's

@@ -99,10 +99,16 @@ def _lr_schedule(lr, steps):
 def _check_pair(emb, target, name="emb", tname="target"):
     """Shapes, dtypes, devices and values of one (embeddings, targets) pair; -> (emb, target tensor for the kernel, dtype code)."""
     emb = _check_emb(emb, name)
-    if not isinstance(target, torch.Tensor) or target.dim() != 2 or target.shape[0] != emb.shape[0]:
-        raise ValueError("%s must be a (%d, N) tensor (got %s)" % (tname, emb.shape[0], getattr(target, "shape", type(target))))
-    if target.device != emb.device:
-        raise ValueError("%s is on %s, %s on %s" % (tname, target.device, name, emb.device))
+    t = _check_target(target, int(emb.shape[0]), emb.device, name, tname)
+    return emb, t, _inputs.target_code(t)
+
+
+def _check_target(target, n, device, name="emb", tname="target"):
+    """(n, N) multi-label targets on `device`, checked; -> the tensor the kernels read (uint8 or float32, rows in place)."""
+    if not isinstance(target, torch.Tensor) or target.dim() != 2 or target.shape[0] != n:
+        raise ValueError("%s must be a (%d, N) tensor (got %s)" % (tname, n, getattr(target, "shape", type(target))))
+    if target.device != device:
+        raise ValueError("%s is on %s, %s on %s" % (tname, target.device, name, device))
     N = int(target.shape[1])
     if not 1 <= N <= _ffi.MAX_CLASSES:
         raise ValueError("%s has N = %d classes (expected 1 .. %d)" % (tname, N, _ffi.MAX_CLASSES))
@@ -118,8 +124,7 @@ def _check_pair(emb, target, name="emb", tname="target"):
         t = target if target.dtype == torch.uint8 else target.to(torch.uint8)
     else:
         raise ValueError("%s must be bool, an integer type or floating point (got %s)" % (tname, target.dtype))
-    t = _inputs.rows(t)
-    return emb, t, _inputs.target_code(t)
+    return _inputs.rows(t)
 
 
 def _check_emb(emb, name="emb", device=True):
@@ -604,3 +609,298 @@ def cross_validate_head(emb, target, folds=5, grid=None, fold_ids=None, stratify
     if refit and best is not None:
         final = fit_head(emb, target, **configs[best])
     return CrossValidation(configs, fold_ids, metric, scores, mean, std, best, fits if keep_fits else None, final)
+
+
+# ---- sound event detection heads from clip-level labels: multiple-instance learning over segments -----------------------------
+# fit_head trains on scene embeddings (the mean over the clip, then LayerNorm); detect_events reads the head on every 0.32 s
+# segment embedding and pools over time.  fit_sed_head trains along the path inference takes -- the reference's decision-level
+# recipe (pytorch/models.py:5757-5771: head per segment, sigmoid, pooling over time; losses.py clip_bce: F.binary_cross_entropy on
+# the pooled clip probability): a clip is a bag, its segments are the instances, the label belongs to the bag
+# (acx_head_fit_step_mil in include/acx.h: logits, bag pass, update -- three launches per step).
+MIL_POOLS = {"max": 0, "mean": 1, "linear": 2, "exp": 3}                   # enum acx_mil_pool
+SedSchedule = namedtuple("SedSchedule", ["bag_idx", "bag_off", "seg_idx", "steps"])
+MilGrad = namedtuple("MilGrad", ["P", "G", "loss", "terms", "tstar"])
+
+
+def check_pooling(pooling):
+    if pooling not in MIL_POOLS:
+        raise ValueError("pooling must be one of %s (got %r)" % (", ".join("\"%s\"" % k for k in MIL_POOLS), pooling))
+    return MIL_POOLS[pooling]
+
+
+def _check_lengths(lengths, rows, name="segments"):
+    lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lens) < 1:
+        raise ValueError("%s holds no clips" % name)
+    if any(v < 1 for v in lens):
+        raise ValueError("%s: every clip needs at least one segment (clip %d has %d)"
+                         % (name, next(i for i, v in enumerate(lens) if v < 1), min(lens)))
+    if sum(lens) != rows:
+        raise ValueError("%s: lengths sum to %d rows but the packed tensor holds %d" % (name, sum(lens), rows))
+    return lens
+
+
+def check_segments(segments, name="segments", device=True):
+    """The segment embeddings of a weak-label fit in any of their three forms -- a (B, S, 768) tensor, a list of (S_i, 768)
+    tensors, or (packed (M, 768), lengths) -- as (packed (M, 768) in a layout the kernels take, [S_0, S_1, ...]).  The rules
+    of the rows are fit_head's (_check_emb): float32, 768 wide and, with device=True, on the GPU."""
+    if isinstance(segments, torch.Tensor):
+        if segments.dim() != 3 or segments.shape[2] != EMBED_DIM:
+            raise ValueError("%s must be a (B, S, %d) tensor, a list of (S_i, %d) tensors or (packed, lengths) (got shape %s)"
+                             % (name, EMBED_DIM, EMBED_DIM, tuple(segments.shape)))
+        if segments.shape[0] < 1 or segments.shape[1] < 1:
+            raise ValueError("%s holds no rows" % name)
+        lens = [int(segments.shape[1])] * int(segments.shape[0])
+        packed = segments.reshape(-1, EMBED_DIM)
+    elif (isinstance(segments, tuple) and len(segments) == 2 and isinstance(segments[0], torch.Tensor)
+          and not (isinstance(segments[1], torch.Tensor) and segments[1].dim() == 2)):
+        packed = segments[0]
+        if packed.dim() != 2:
+            raise ValueError("%s: the packed tensor must be (M, %d) (got shape %s)" % (name, EMBED_DIM, tuple(packed.shape)))
+        lens = _check_lengths(segments[1], int(packed.shape[0]), name)
+    elif isinstance(segments, (list, tuple)) and len(segments) and all(isinstance(s, torch.Tensor) for s in segments):
+        for i, s in enumerate(segments):
+            if s.dim() != 2 or s.shape[1] != EMBED_DIM or s.dtype != segments[0].dtype or s.device != segments[0].device:
+                raise ValueError("%s[%d] must be a (S_i, %d) tensor of the dtype and device of %s[0] (got %s, %s, %s)"
+                                 % (name, i, EMBED_DIM, name, tuple(s.shape), s.dtype, s.device))
+        lens = _check_lengths([s.shape[0] for s in segments], sum(int(s.shape[0]) for s in segments), name)
+        packed = torch.cat(list(segments))
+    else:
+        raise ValueError("%s must be a (B, S, %d) tensor, a list of (S_i, %d) tensors or (packed, lengths) (got %s)"
+                         % (name, EMBED_DIM, EMBED_DIM, type(segments).__name__))
+    return _check_emb(packed, name, device), lens
+
+
+def sed_schedule(lengths, epochs, batch_size, seed=0, shuffle=True, drop_last=False):
+    """The index arrays of every step of a weak-label fit, built once (acx_head_fit_step_mil's bag_idx / bag_off / seg_idx):
+    clip i owns the rows [sum(lengths[:i]), sum(lengths[:i + 1])) of the packed embeddings; epoch e visits the clips in
+    epoch_orders(n, epochs, seed, shuffle)[e], cut into epoch_batches(n, batch_size, drop_last).  -> SedSchedule of three numpy
+    arrays, each the steps' own arrays laid back to back -- bag_idx int64 (the clips of the batch), bag_off int32 (bags + 1
+    entries per step, from 0 to the step's seg_rows), seg_idx int64 (the rows of the batch's segments, in bag order) -- and
+    steps: one (bag_start, bags, off_start, seg_start, seg_rows) per step, the places of its slices in them."""
+    lens = np.asarray(lengths, dtype=np.int64)
+    n = int(lens.shape[0])
+    first = np.concatenate([[0], np.cumsum(lens)])[:-1]
+    order = epoch_orders(n, epochs, seed, shuffle).numpy()
+    batches = epoch_batches(n, batch_size, drop_last)
+    used = sum(rows for _, rows in batches)
+    bag_idx, bag_off, seg_idx, steps = [], [], [], []
+    nb = no = ns = 0
+    for e in range(int(epochs)):                                   # an epoch at a time: its steps are slices of these arrays
+        b = order[e, :used]
+        l = lens[b]
+        cum = np.concatenate([[0], np.cumsum(l)])
+        bag_idx.append(b)
+        seg_idx.append(np.repeat(first[b] - cum[:-1], l) + np.arange(cum[-1], dtype=np.int64))
+        for start, rows in batches:
+            bag_off.append(cum[start:start + rows + 1] - cum[start])
+            seg_rows = int(cum[start + rows] - cum[start])
+            steps.append((nb, rows, no, ns, seg_rows))
+            nb, no, ns = nb + rows, no + rows + 1, ns + seg_rows
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.zeros(0, dtype=dt)       # noqa: E731
+    return SedSchedule(cat(bag_idx, np.int64), cat(bag_off, np.int32), cat(seg_idx, np.int64), steps)
+
+
+def _padded_bags(z, bag_off):
+    """z (rows, N) with bag i in rows [bag_off[i], bag_off[i + 1]) -> (zb (bags, Smax, N), mask (bags, Smax), lens (bags,))."""
+    off = torch.as_tensor(np.asarray(bag_off, dtype=np.int64))
+    if off.dim() != 1 or off.shape[0] < 2 or int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()) or int(off[-1]) != z.shape[0]:
+        raise ValueError("bag_off must run from 0 to the %d rows of z without decreasing" % z.shape[0])
+    lens = off[1:] - off[:-1]
+    smax = max(int(lens.max()), 1)
+    ar = torch.arange(smax)
+    mask = ar[None, :] < lens[:, None]
+    rows = (off[:-1, None] + ar[None, :]).clamp(max=max(z.shape[0] - 1, 0))
+    zb = z[rows] if z.shape[0] else z.new_zeros((lens.shape[0], smax, z.shape[1]))
+    return torch.where(mask[:, :, None], zb, torch.zeros_like(zb)), mask, lens
+
+
+def mil_forward_host(z, bag_off, pooling):
+    """The pooled clip probabilities of segment logits, in torch ops of z's dtype (float64 for the definition), differentiable:
+    q = sigmoid(z) per segment, then over the S rows of a bag
+        "max"     P = q at t*, the LOWEST t that attains max_t z_t (taken on the logits)
+        "mean"    P = sum q / S
+        "linear"  P = sum q^2 / sum q   (sum q = 0: P = 0)
+        "exp"     P = sum q e^q / sum e^q
+    and P = 0 for an empty bag.  -> (P (bags, N), tstar (bags, N) int64: t* within the bag, for "max"; else None)."""
+    check_pooling(pooling)
+    zb, mask, lens = _padded_bags(z, bag_off)
+    m3 = mask[:, :, None]
+    some = (lens > 0)[:, None]
+    q = torch.sigmoid(zb)
+    zero = torch.zeros((), dtype=z.dtype)
+    tstar = None
+    if pooling == "max":
+        zm = torch.where(m3, zb.detach(), torch.full_like(zb, float("-inf")))
+        top = zm.max(dim=1).values
+        ar = torch.arange(zb.shape[1])[None, :, None].expand_as(zm)
+        tstar = torch.where((zm == top[:, None, :]) & m3, ar, torch.full_like(ar, zb.shape[1] - 1)).min(dim=1).values
+        P = torch.where(some, q.gather(1, tstar[:, None, :]).squeeze(1), zero)
+    elif pooling == "mean":
+        P = torch.where(m3, q, zero).sum(dim=1) / lens.clamp(min=1)[:, None].to(z.dtype)
+    elif pooling == "linear":
+        qm = torch.where(m3, q, zero)
+        s1 = qm.sum(dim=1)
+        P = (qm * qm).sum(dim=1) / torch.where(s1 == 0, torch.ones_like(s1), s1)
+    else:
+        e = torch.where(m3, torch.exp(q), zero)
+        P = (q * e).sum(dim=1) / torch.where(some, e.sum(dim=1), torch.ones((), dtype=z.dtype))
+    return P, tstar
+
+
+def mil_grad_host(z, bag_off, y, pooling, dtype=torch.float64):
+    """One bag pass in float64 (or `dtype`), in closed form: z (rows, N) segment logits, bag i in rows [bag_off[i], bag_off[i + 1]), y
+    (bags, N) clip labels in [0, 1].  P = mil_forward_host(z); per (bag, class)
+        term  = -[y max(log P, -100) + (1 - y) max(log1p(-P), -100)],  loss = mean(term)
+        dL/dP = (P - y) / max(P (1 - P), 1e-12)                          -- F.binary_cross_entropy and its backward
+        dP/dq = [t = t*] | 1 / S | (2 q - P) / sum q | e^q (1 + q - P) / sum e^q   ("linear" with sum q = 0: 0)
+        G[t]  = dL/dP dP/dq_t q_t (1 - q_t) / (bags N)
+    -> MilGrad(P, G (rows, N), loss, terms (bags, N), tstar).  Autograd through mil_forward_host and F.binary_cross_entropy
+    gives the same G (tests/test_sed_fit_cpu.py)."""
+    z = torch.as_tensor(z).detach().to(dtype)
+    y = torch.as_tensor(y).detach().to(dtype)
+    P, tstar = mil_forward_host(z, bag_off, pooling)
+    zb, mask, lens = _padded_bags(z, bag_off)
+    if tuple(y.shape) != tuple(P.shape):
+        raise ValueError("y must be (%d, %d) (got %s)" % (P.shape[0], P.shape[1], tuple(y.shape)))
+    m3 = mask[:, :, None]
+    q = torch.sigmoid(zb)
+    terms = -(y * torch.log(P).clamp(min=-100) + (1 - y) * torch.log1p(-P).clamp(min=-100))
+    dLdP = ((P - y) / (P * (1 - P)).clamp(min=1e-12))[:, None, :]
+    P3 = P[:, None, :]
+    if pooling == "max":
+        d = (torch.arange(zb.shape[1])[None, :, None] == tstar[:, None, :]).to(dtype)
+    elif pooling == "mean":
+        d = (1.0 / lens.clamp(min=1).to(dtype))[:, None, None].expand_as(q)
+    elif pooling == "linear":
+        s1 = torch.where(m3, q, torch.zeros_like(q)).sum(dim=1, keepdim=True)
+        d = torch.where(s1 == 0, torch.zeros_like(q), (2 * q - P3) / torch.where(s1 == 0, torch.ones_like(s1), s1))
+    else:
+        e = torch.exp(q)
+        s1 = torch.where(m3, e, torch.zeros_like(e)).sum(dim=1, keepdim=True)
+        d = e * (1 + q - P3) / torch.where(s1 == 0, torch.ones_like(s1), s1)
+    G = dLdP * d * (q * (1 - q)) / (P.shape[0] * P.shape[1])
+    return MilGrad(P, G[mask], terms.mean(), terms, tstar)
+
+
+def fit_sed_head_host(segments, target, pooling="max", epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
+                      weight_decay=0.0, amsgrad=True, decoupled=False, init=None, seed=0, shuffle=True, drop_last=False,
+                      dtype=torch.float64, on_step=None, closed_form=False):
+    """fit_sed_head's definition on the CPU: the same schedule (sed_schedule), the same initial head, then per step autograd
+    through sigmoid -> mil_forward_host -> F.binary_cross_entropy and torch.optim.Adam / AdamW, in `dtype`.
+    closed_form: the gradients come from mil_grad_host in `dtype` (G, then G^T E and its column sums) instead of autograd -- the
+    same definition, evaluated in another order.  on_step(t, z, bag_off, E[seg_idx], W, b): called with every step's logits and inputs before the update (tests read margins).
+    -> HeadFit(weight, bias, loss (steps,), [])."""
+    check_pooling(pooling)
+    _check_hyper(epochs, batch_size, betas, eps, weight_decay)
+    packed, lens = check_segments(segments, device=False)
+    target = torch.as_tensor(target)
+    if target.dim() != 2 or target.shape[0] != len(lens):
+        raise ValueError("target must be a (%d, N) tensor (got %s)" % (len(lens), tuple(target.shape)))
+    N = int(target.shape[1])
+    w0, b0 = init_head(N, seed) if init is None else _check_init(init, N)
+    E, Y = packed.detach().cpu().to(dtype), target.detach().cpu().to(dtype)
+    W = w0.detach().cpu().to(dtype).clone().requires_grad_()
+    b = b0.detach().cpu().to(dtype).clone().requires_grad_()
+    sched = sed_schedule(lens, epochs, batch_size, seed, shuffle, drop_last)
+    lrs = _lr_schedule(lr, len(sched.steps))
+    opt = (torch.optim.AdamW if decoupled else torch.optim.Adam)([W, b], lr=lrs[0] if lrs else 0.0, betas=tuple(betas), eps=eps,
+                                                                  weight_decay=weight_decay, amsgrad=amsgrad)
+    losses = []
+    for t, (nb, bags, no, ns, rows) in enumerate(sched.steps):
+        opt.param_groups[0]["lr"] = lrs[t]
+        e = E[torch.from_numpy(sched.seg_idx[ns:ns + rows])]
+        z = e @ W.T + b
+        if on_step is not None:
+            on_step(t, z.detach(), sched.bag_off[no:no + bags + 1].tolist(), e, W.detach().clone(), b.detach().clone())
+        yb = Y[torch.from_numpy(sched.bag_idx[nb:nb + bags])]
+        if closed_form:
+            g = mil_grad_host(z, sched.bag_off[no:no + bags + 1], yb, pooling, dtype=dtype)
+            loss, W.grad, b.grad = g.loss, g.G.T @ e, g.G.sum(dim=0)
+        else:
+            P, _ = mil_forward_host(z, sched.bag_off[no:no + bags + 1], pooling)
+            loss = torch.nn.functional.binary_cross_entropy(P, yb)
+            opt.zero_grad()
+            loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+    return HeadFit(W.detach(), b.detach(), torch.stack(losses) if losses else torch.zeros(0, dtype=dtype), [])
+
+
+def _validate_sed(weight, bias, seg_val, lens_val, target_val, pooling):
+    from .metrics import tagging_metrics
+    from .segments import pool_segments
+    probs = pool_segments(torch.addmm(bias, seg_val, weight.t()), pooling, steps=lens_val)
+    stats = tagging_metrics(target_val, probs)
+    return {"average_precision": stats["average_precision"], "auc": stats["auc"], "d_prime": stats["d_prime"],
+            "mAP": float(np.mean(stats["average_precision"])), "mAUC": float(np.nanmean(stats["auc"]))}
+
+
+def fit_sed_head(segments, target, pooling="max", epochs=20, batch_size=64, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 amsgrad=True, decoupled=False, init=None, seed=0, shuffle=True, drop_last=False, val=None):
+    """Train an nn.Linear(768, N) sound event detection head from CLIP-level labels: the head is applied to every segment
+    embedding of a clip, the segment probabilities are pooled over time (`pooling`: "max", the pooling forward_segments'
+    "clipwise_output" and detect_events use; "mean", "linear" or "exp", read at inference with segments.pool_segments) and
+    F.binary_cross_entropy is taken on the pooled clip probability -- multiple-instance learning, on the GPU
+    (acx_head_fit_step_mil: three launches per step, nothing synchronises).
+    segments: (B, S, 768), a list of (S_i, 768), or (packed (M, 768), lengths) -- forward_segment_embeddings /
+    extract(what="segment_embeddings") outputs; target: (clips, N) bool / uint8 / float, fit_head's rules; batch_size counts
+    clips.  The other settings, the epoch order and the initial head are fit_head's.  val=(segments_val, target_val):
+    per-epoch tagging_metrics of the POOLED clip probabilities in the history (one synchronisation per epoch).
+    Returns HeadFit(weight, bias, loss, history)."""
+    pool = check_pooling(pooling)
+    _check_hyper(epochs, batch_size, betas, eps, weight_decay)
+    emb, lens = check_segments(segments)
+    n, device, rows_total = len(lens), emb.device, int(emb.shape[0])
+    tgt = _check_target(target, n, device, "segments")
+    N = int(tgt.shape[1])
+    if val is not None:
+        if len(val) != 2:
+            raise ValueError("val must be (segments_val, target_val)")
+        seg_val, lens_val = check_segments(val[0], "segments_val")
+        if seg_val.device != device:
+            raise ValueError("segments_val is on %s, segments on %s" % (seg_val.device, device))
+        target_val = _check_target(val[1], len(lens_val), device, "segments_val", "target_val")
+        if target_val.shape[1] != N:
+            raise ValueError("target_val has %d classes, target %d" % (target_val.shape[1], N))
+    w0, b0 = init_head(N, seed) if init is None else _check_init(init, N)
+    sched = sed_schedule(lens, epochs, batch_size, seed, shuffle, drop_last)
+    steps = len(sched.steps)
+    lrs = _lr_schedule(lr, steps)
+    seg_max = max((s[4] for s in sched.steps), default=1)
+    if seg_max > _ffi.FIT_MAX_ROWS:
+        raise ValueError("a batch of %d clips holds %d segments (at most 2^22 per step): lower batch_size" % (batch_size, seg_max))
+
+    with torch.no_grad(), torch.cuda.device(device):
+        W = w0.detach().to(device=device, dtype=torch.float32, copy=True).contiguous()
+        b = b0.detach().to(device=device, dtype=torch.float32, copy=True).contiguous()
+        loss = torch.zeros(steps, dtype=torch.float32, device=device)
+        history = []
+        if steps == 0:
+            return HeadFit(W, b, loss, history)
+        bag_idx, bag_off, seg_idx = (torch.from_numpy(a).to(device) for a in (sched.bag_idx, sched.bag_off, sched.seg_idx))
+        mom = torch.zeros((3, N, EMBED_DIM), dtype=torch.float32, device=device)
+        momb = torch.zeros((3, N), dtype=torch.float32, device=device)
+        status = torch.zeros(1, dtype=torch.int32, device=device)
+        ws_bytes = _ffi.head_fit_mil_workspace_bytes(seg_max, min(batch_size, n), N)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        step_fn = _ffi.lib().acx_head_fit_step_mil
+        hp = _ffi.adam(betas[0], betas[1], eps, weight_decay, amsgrad, decoupled)
+        fixed_a = (vp(emb), emb.stride(0), rows_total, vp(tgt), _inputs.target_code(tgt), tgt.stride(0), n)
+        fixed_b = (N, pool, vp(W), vp(b), vp(mom[0]), vp(mom[1]), vp(mom[2]) if amsgrad else None, vp(momb[0]), vp(momb[1]),
+                   vp(momb[2]) if amsgrad else None, ctypes.byref(hp))
+        tail = (vp(status), vp(ws), ws_bytes, _ffi.stream_ptr(device))
+        bi, bo, si, loss_ptr = bag_idx.data_ptr(), bag_off.data_ptr(), seg_idx.data_ptr(), loss.data_ptr()
+        per = steps // epochs
+        for t, (nb, bags, no, ns, rows) in enumerate(sched.steps):
+            rc = step_fn(*fixed_a, ctypes.c_void_p(si + 8 * ns), rows, ctypes.c_void_p(bo + 4 * no), ctypes.c_void_p(bi + 8 * nb),
+                         bags, *fixed_b, t + 1, lrs[t], ctypes.c_void_p(loss_ptr + 4 * t), *tail)
+            if rc != _ffi.OK:
+                _ffi.check(rc)
+            if (t + 1) % per == 0:
+                e = t // per
+                rec = {"epoch": e, "loss": loss[e * per:(e + 1) * per].mean()}
+                if val is not None:
+                    rec.update(_validate_sed(W, b, seg_val, lens_val, target_val, pooling))
+                history.append(rec)
+    return HeadFit(W, b, loss, history)

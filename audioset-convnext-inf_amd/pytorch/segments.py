@@ -972,3 +972,56 @@ def join_event_tables(tables):
     if owner._pending in tables:
         owner._pending = joined
     return joined
+
+
+# ---- pooling segment logits into clip probabilities (acx_segment_pool) ---------------------------------------------------------
+def _pool_clips(logits, steps):
+    """The (rows, N) view of segment logits and the rows per clip: logits (B, S, N) or (S, N) with steps=None, or packed
+    (sum(steps), N) rows with one count per clip."""
+    torch = _torch()
+    if not isinstance(logits, torch.Tensor) or logits.dim() not in (2, 3) or logits.shape[-1] < 1:
+        raise ValueError("pool_segments expects (B, S, N) or (rows, N) logits (got %s)" % (getattr(logits, "shape", type(logits)),))
+    if steps is None:
+        if logits.dim() == 2:
+            logits = logits[None]
+        lens = [int(logits.shape[1])] * int(logits.shape[0])
+        logits = logits.reshape(-1, logits.shape[-1])
+    else:
+        lens = [int(n) for n in (steps.tolist() if hasattr(steps, "tolist") else steps)]
+        if logits.dim() != 2 or not lens or min(lens) < 0 or sum(lens) != logits.shape[0]:
+            raise ValueError("steps=%r do not add up to the %r packed rows" % (lens, tuple(logits.shape)))
+    if not lens or not 1 <= logits.shape[1] <= _ffi.MAX_CLASSES:
+        raise ValueError("pool_segments needs at least one clip and 1 .. %d classes" % _ffi.MAX_CLASSES)
+    return logits, lens
+
+
+def pool_segments(logits, pooling="max", steps=None):
+    """Segment logits -> clip probabilities (clips, N) on the GPU, as finetune.fit_sed_head pools them while it trains
+    (acx_segment_pool: the bits of the training pass): sigmoid per segment, then over a clip's segments "max", "mean", "linear"
+    (sum q^2 / sum q) or "exp" (sum q e^q / sum e^q).  logits: fp32 CUDA, (B, S, N) / (S, N), or packed (rows, N) with steps=
+    the segments per clip (forward_varlen's and forward_windows' outputs); a clip without segments gives 0.  "max" equals
+    forward_segments' "clipwise_output".  Runs on the current stream without synchronising."""
+    torch = _torch()
+    from . import _inputs
+    from .finetune import check_pooling
+    pool = check_pooling(pooling)
+    logits, lens = _pool_clips(logits, steps)
+    if not logits.is_cuda or logits.dtype != torch.float32:
+        raise ValueError("pool_segments runs on fp32 CUDA (HIP) tensors (got %s on %s); pool_segments_host takes any"
+                         % (logits.dtype, logits.device))
+    logits = _inputs.rows(logits)
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)).to(logits.device)
+    out = torch.empty((len(lens), logits.shape[1]), dtype=torch.float32, device=logits.device)
+    status = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        _ffi.segment_pool(_ffi.vp(logits), logits.stride(0), _ffi.vp(off), len(lens), logits.shape[1], pool, _ffi.vp(out),
+                          _ffi.vp(status), _ffi.stream_ptr(logits.device))
+    return out
+
+
+def pool_segments_host(logits, pooling="max", steps=None):
+    """pool_segments' definition in float64 torch on the CPU (finetune.mil_forward_host) -> (clips, N) float64."""
+    torch = _torch()
+    from .finetune import mil_forward_host
+    logits, lens = _pool_clips(torch.as_tensor(logits), steps)
+    return mil_forward_host(logits.detach().cpu().to(torch.float64), np.concatenate([[0], np.cumsum(lens)]), pooling)[0]

@@ -25,7 +25,13 @@ plain embeddings (ConvNeXt.forward_augmented: SpecAugment stripes; "full" adds g
 passes over them, --mixup-alpha A mixing clips and label rows pairwise (--loss bce).  The clips must share one length; validation,
 thresholds and calibration stay on the plain embeddings.
 
-    python demo_finetune.py --synthetic --augment reference --views 4 --mixup-alpha 0.5 --out /tmp/tagger"""
+    python demo_finetune.py --synthetic --augment reference --views 4 --mixup-alpha 0.5 --out /tmp/tagger
+
+--sed-pooling max|mean|linear|exp fits a sound event detection head from the same clip labels instead (ConvNeXt.fit_sed_head):
+the head is trained on every clip's 0.32 s segment embeddings through that pooling over time -- the path detect_events and
+psds read it on -- and the validation mAP is taken of the pooled clip probabilities.  Without the flag nothing changes.
+
+    python demo_finetune.py --synthetic --sed-pooling linear --lr 1e-3 --out /tmp/detector"""
 import argparse
 import csv
 import os
@@ -72,6 +78,47 @@ def synthetic_items(clips, classes, seconds, seed=0):
     return waves, target, ["tone_%d" % c for c in range(classes)]
 
 
+def sed_fit(model, waves, target, names, rate, a):
+    """--sed-pooling: the weak-label SED fit.  Segment embeddings of every clip, the head trained through the pooling over time
+    on the clip labels (the path detect_events takes), validation mAP of the pooled clip probabilities per epoch."""
+    if a.loss != "bce" or a.folds or a.augment:
+        sys.exit("--sed-pooling fits with binary cross-entropy on the clips as they are: no --loss ce, --folds or --augment")
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        segs = []
+        for s in range(0, len(waves), 256):
+            part = model.forward_varlen([torch.as_tensor(w, dtype=torch.float32).cuda() for w in waves[s:s + 256]],
+                                        what="segment_embeddings", sample_rate=rate)
+            segs += [p.clone() for p in part]
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    n_val = int(len(waves) * a.val_fraction) if len(waves) >= 20 else 0
+    order = torch.randperm(len(waves), generator=torch.Generator().manual_seed(a.seed)).tolist()
+    tr, va = order[n_val:], order[:n_val]
+    target = target.cuda()
+    pick = lambda rows: ([segs[i] for i in rows], target[torch.tensor(rows, device="cuda")])       # noqa: E731
+    fit = model.fit_sed_head(*pick(tr), pooling=a.sed_pooling, epochs=a.epochs, batch_size=a.batch_size, lr=a.lr,
+                             weight_decay=a.weight_decay, decoupled=a.adamw, seed=a.seed, val=pick(va) if n_val else None)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    for rec in fit.history:
+        print("epoch %2d  loss %.4f%s" % (rec["epoch"], float(rec["loss"]),
+                                          "  val mAP %.3f  AUC %.3f (clip probabilities pooled with %s)" % (rec["mAP"], rec["mAUC"], a.sed_pooling)
+                                          if n_val else ""))
+    print("segment embeddings %.2f s (%d segments of %d clips), fit %.2f s (%d steps%s)"
+          % (t1 - t0, sum(s.shape[0] for s in segs), len(waves), t2 - t1, fit.loss.numel(), ", validation included" if n_val else ""))
+    os.makedirs(a.out, exist_ok=True)
+    sd = {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}
+    torch.save({"model": sd}, os.path.join(a.out, "model.pth"))
+    from safetensors.torch import save_file
+    save_file(sd, os.path.join(a.out, "model.safetensors"))
+    with open(os.path.join(a.out, "labels.txt"), "w") as f:
+        f.write("\n".join(names) + "\n")
+    print("wrote %s: model.safetensors, model.pth, labels.txt -- a %d-class head for detect_events / psds%s"
+          % (a.out, len(names), "" if a.sed_pooling == "max" else
+             "; clip probabilities: segments.pool_segments(segmentwise_logits, %r)" % a.sed_pooling))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", default="topel/ConvNeXt-Tiny-AT", help="local .safetensors/.pth, Zenodo URL or HF model id")
@@ -96,6 +143,9 @@ def main():
     ap.add_argument("--augment", choices=("reference", "full"), help="fit on augmented views of the training clips")
     ap.add_argument("--views", type=int, default=1, help="augmented passes over the training clips (--augment)")
     ap.add_argument("--mixup-alpha", type=float, help="mixup of clip pairs and their label rows (--augment, --loss bce)")
+    ap.add_argument("--sed-pooling", choices=("max", "mean", "linear", "exp"),
+                    help="fit a sound event detection head from the clip labels instead (ConvNeXt.fit_sed_head): the head is trained "
+                         "on segment embeddings through this pooling over time")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("this build runs on an MI355X; no GPU is visible")
@@ -128,6 +178,8 @@ def main():
             target[i, [col[l] for l in labels]] = True
     model = model.to("cuda").eval()
     print("%d clips, %d classes" % (len(waves), len(names)))
+    if a.sed_pooling:
+        return sed_fit(model, waves, target, names, rate, a)
 
     t0 = time.perf_counter()
     emb = torch.stack(extract(model, waves, what="scene", pack=True, sample_rate=rate)).cuda()

@@ -850,6 +850,56 @@ ACX_API int acx_head_fit_grad_ce(const float* E, int64_t ld_e, int64_t n_rows_to
                                  float* G, float* dW, float* db, float* loss, int32_t* status, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* Sound event detection heads from clip-level labels: multiple-instance learning.  acx_head_fit_step trains on scene embeddings;
+ * detection applies the head to every 0.32 s segment embedding and pools over time ("sound event detection" above).  These calls
+ * train along that path -- the reference's decision-level recipe, pytorch/models.py:5757-5771 (head per segment, sigmoid, pooling
+ * over time) with pytorch/losses.py clip_bce (F.binary_cross_entropy on the pooled clip probability): a clip is a BAG, its
+ * segments are the instances, only the bag has a label.
+ *   E (n_rows_total, 768): the segment embeddings of all clips back to back (acx_head_fit_step's layout rules);
+ *   target (n_bags_total, classes): one row per clip, of target_dtype, row stride ld_target.
+ * A step takes `bags` clips: bag_idx (`bags` int64 target rows; repeats allowed), bag_off (`bags` + 1 int32: bag i owns the rows
+ * [bag_off[i], bag_off[i + 1]) of the step; bag_off[0] = 0, non-decreasing, bag_off[bags] = seg_rows) and seg_idx (seg_rows int64
+ * rows of E, in bag order), all on the device; seg_rows and bags travel by value.  With z = E[seg_idx] W^T + b -- the bits
+ * acx_head_fit_grad_ce writes for those rows -- and q_t = sigmoid(z_t) over the S rows of a bag, per class:
+ *   ACX_MIL_MAX     P = sigmoid(z_t*), t* the LOWEST t that attains max_t z_t         dP/dq_t = [t = t*]
+ *   ACX_MIL_MEAN    P = (sum q_t) / S                                                 dP/dq_t = 1 / S
+ *   ACX_MIL_LINEAR  P = sum q_t^2 / sum q_t   (sum q_t = 0: P = 0, no gradient)       dP/dq_t = (2 q_t - P) / sum q_t
+ *   ACX_MIL_EXP     P = sum q_t e^q_t / sum e^q_t                                     dP/dq_t = e^q_t (1 + q_t - P) / sum e^q_t
+ *   loss term -[y max(log P, -100) + (1 - y) max(log1p(-P), -100)],  dL/dP = (P - y) / max(P (1 - P), 1e-12)
+ *   G[t] = dL/dP dP/dq_t q_t (1 - q_t) / (bags classes);  *loss_out = the mean of the terms over (bags, classes)
+ * -- torch's binary_cross_entropy on a probability and its backward -- then acx_head_fit_step's update with g = G^T E[seg_idx],
+ * sum_rows G.  An empty bag has P = 0, no gradient, and its loss term.  All fp32, every sum in ascending t per (bag, class), the
+ * loss terms added in a fixed order: the same inputs give the same bits on every call.  Three launches.
+ *   acx_head_fit_mil_workspace_bytes: for steps of up to seg_rows_max rows and bags_max bags; non-decreasing (host only).
+ *   acx_head_fit_step_mil: the step.  acx_head_fit_grad_mil: the same pass without the update -- z, G (seg_rows, classes), P
+ *     (bags, classes), dW, db and *loss to caller buffers; followed by acx_adam_update on (W, dW) and (b, db) it leaves the bits
+ *     of acx_head_fit_step_mil.
+ *   acx_segment_pool: the forward half alone, the same device function and so the same bits as P: logits (rows, classes) with
+ *     row stride ld, bag_off as above (bag_off[bags] rows are read), out (bags, classes).  How a head trained with MEAN / LINEAR /
+ *     EXP gets its clip probability at inference; acx_forward_segments' clipwise output stays the maximum.
+ * The launch contract and the ARGUMENT errors of acx_head_fit_step; also bags < 1, seg_rows < 1, a pool that is no acx_mil_pool
+ * (ACX_ERR_ARG); seg_rows or bags > 2^22 (ACX_ERR_UNSUPPORTED).  DATA errors: a seg_idx or bag_idx entry out of range is clamped
+ * and ORs ACX_FIT_BAD_INDEX into *status; a bag_off entry below its predecessor (the bag is then empty), below 0 or beyond
+ * seg_rows, a first entry other than 0 or a last one other than seg_rows is clamped -- nothing outside the buffers is touched,
+ * every row of G is written -- and ORs ACX_FIT_BAD_BAG.  acx_segment_pool knows no seg_rows: it flags negative and decreasing
+ * entries only. */
+#define ACX_FIT_BAD_BAG 4
+enum acx_mil_pool { ACX_MIL_MAX = 0, ACX_MIL_MEAN = 1, ACX_MIL_LINEAR = 2, ACX_MIL_EXP = 3 };
+ACX_API int acx_head_fit_mil_workspace_bytes(int64_t seg_rows_max, int64_t bags_max, int classes, size_t* out_bytes);
+ACX_API int acx_head_fit_step_mil(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                                  int64_t ld_target, int64_t n_bags_total, const int64_t* seg_idx, int64_t seg_rows,
+                                  const int32_t* bag_off, const int64_t* bag_idx, int64_t bags, int classes, int pool, float* W,
+                                  float* b, float* mW, float* vW, float* vmaxW, float* mb, float* vb, float* vmaxb,
+                                  const acx_adam* hp, int64_t step_t, double lr, float* loss_out, int32_t* status, void* ws,
+                                  size_t ws_bytes, void* stream);
+ACX_API int acx_head_fit_grad_mil(const float* E, int64_t ld_e, int64_t n_rows_total, const void* target, int target_dtype,
+                                  int64_t ld_target, int64_t n_bags_total, const int64_t* seg_idx, int64_t seg_rows,
+                                  const int32_t* bag_off, const int64_t* bag_idx, int64_t bags, int classes, int pool,
+                                  const float* W, const float* b, float* z, float* P, float* G, float* dW, float* db, float* loss,
+                                  int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_segment_pool(const float* logits, int64_t ld, const int32_t* bag_off, int64_t bags, int classes, int pool,
+                             float* out /* (bags, classes) */, int32_t* status, void* stream);
+
 /* Groups: `jobs` independent fits (1 .. ACX_FIT_MAX_JOBS: the folds of a cross-validation, the settings of a grid) over the SAME
  * E and target / labels, advanced together: one group step launches each stage ONCE for all jobs (BCE: the gradient pass, once
  * per tile form that can occur, and the update; cross-entropy: logits, row pass, update).  The jobs share classes, the loss,
