@@ -245,6 +245,11 @@ SIGNATURES = {
                                 _c_sz, _vp]),
     "acx_knn_vote": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, ctypes.c_float, _vp, _c_i64,
                               _vp, _vp]),
+    "acx_knn_quantize_i8": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp]),
+    "acx_knn_search_i8": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz,
+                                   _vp]),
+    "acx_knn_rescore": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_i64, _c_int, _c_int, _vp,
+                                 _vp, _vp, _vp]),
     "acx_kmeans_workspace_bytes": (_c_int, [_c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_kmeans_assign": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "acx_kmeans_update": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz,
@@ -711,6 +716,26 @@ def knn_vote(indices, scores, nq, k, target, target_dtype, ld_target, n, classes
     """acx_knn_vote on raw device pointers (ctypes.c_void_p)."""
     check(lib().acx_knn_vote(indices, scores, int(nq), int(k), target, int(target_dtype), int(ld_target), int(n), int(classes),
                              int(weighting), float(temperature), out, int(ld_out), status, stream))
+
+
+KNN_I8_K = 32                                 # ACX_KNN_I8_K: int8 code rows are padded to a multiple
+
+
+def knn_quantize_i8(x, ld, inv_norm, n, dim, codes, ld_c, scale, status, stream):
+    """acx_knn_quantize_i8 on raw device pointers (ctypes.c_void_p); inv_norm None: the dot metric."""
+    check(lib().acx_knn_quantize_i8(x, int(ld), inv_norm, int(n), int(dim), codes, int(ld_c), scale, status, stream))
+
+
+def knn_search_i8(cq, ld_cq, sq, nq, cd, ld_cd, sd, n, dim, k, exclude, indices, scores, status, ws, stream):
+    """acx_knn_search_i8 on raw device pointers (ctypes.c_void_p); dim: the padded code width; ws: (pointer, bytes)."""
+    check(lib().acx_knn_search_i8(cq, int(ld_cq), sq, int(nq), cd, int(ld_cd), sd, int(n), int(dim), int(k), exclude, indices, scores,
+                                  status, ws[0], int(ws[1]), stream))
+
+
+def knn_rescore(q, ld_q, q_inv_norm, nq, d, ld_d, d_inv_norm, n, dim, metric, cand, ld_cand, kc, k, indices, scores, status, stream):
+    """acx_knn_rescore on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_knn_rescore(q, int(ld_q), q_inv_norm, int(nq), d, int(ld_d), d_inv_norm, int(n), int(dim), int(metric), cand,
+                                int(ld_cand), int(kc), int(k), indices, scores, status, stream))
 
 
 KMEANS_EUCLIDEAN, KMEANS_COSINE = 0, 1         # enum acx_kmeans_metric

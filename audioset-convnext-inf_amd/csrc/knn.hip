@@ -32,60 +32,13 @@
 
 #include "acx_internal.h"
 #include "device_common.h"
+#include "knn_common.h"
 
 namespace acx {
 
-constexpr int kKnnThreads = 256;
-constexpr int kKnnStepRows = 256;            // database rows per step of a workgroup: four waves x 64
-constexpr int kKnnTargetWgs = 512;           // the slice count aims at this many workgroups: two per CU of an MI355X
-constexpr int kKnnMaxSlices = 1024;
-
+// kKnn* constants, knn_sort_desc, knn_load_sorted and the launch plan: knn_common.h (knn_i8.hip searches with the same machinery;
+// its kernel takes the slot / trim / slice-list steps below from there as functions)
 // knn_key, knn_make_key, knn_key_score, knn_key_index: device_common.h (classify.hip orders classes by the same keys)
-
-// Element e = lane + 64 r of a wave's 64 R keys, sorted descending (bitonic network: strides under 64 by lane shuffles, the
-// others between the lane's own registers).
-template <int R>
-__device__ __forceinline__ void knn_sort_desc(knn_key (&v)[R], int lane) {
-#pragma unroll
-    for (int size = 2; size <= 64 * R; size <<= 1) {
-#pragma unroll
-        for (int j = size >> 1; j >= 1; j >>= 1) {
-            if (j >= 64) {
-                const int jr = j >> 6;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    if ((r & jr) == 0) {
-                        const bool desc = ((r << 6) & size) == 0;
-                        const knn_key a = v[r], b = v[r | jr];
-                        const bool sw = desc ? (a < b) : (a > b);
-                        v[r] = sw ? b : a;
-                        v[r | jr] = sw ? a : b;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const bool desc = ((lane + (r << 6)) & size) == 0;
-                    const bool lower = (lane & j) == 0;
-                    const knn_key o = __shfl_xor(v[r], j);
-                    const knn_key hi = v[r] > o ? v[r] : o, lo = v[r] > o ? o : v[r];
-                    v[r] = (lower == desc) ? hi : lo;
-                }
-            }
-        }
-    }
-}
-
-// v[] <- the cnt keys of buf (the other elements 0), sorted descending.  One wave.
-template <int R>
-__device__ __forceinline__ void knn_load_sorted(const knn_key* buf, int cnt, knn_key (&v)[R], int lane) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = lane + 64 * r;
-        v[r] = e < cnt ? buf[e] : 0ull;
-    }
-    knn_sort_desc<R>(v, lane);
-}
 
 __global__ __launch_bounds__(256) void knn_norm_kernel(const float* __restrict__ x, long long ld, long long n, int dim,
                                                        float* __restrict__ inv_norm, int* status) {
@@ -303,48 +256,6 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(KnnVoteP p) {
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-struct KnnPlan { int qt, r, slices; long long slice_rows; };
-
-// The launch shape of a search: a function of (nq, n, k) and ACX_KNN_SLICE_ROWS alone.
-static KnnPlan knn_plan(long long nq, long long n, int k) {
-    KnnPlan pl;
-    pl.qt = nq <= 32 ? 1 : 2;
-    pl.r = k <= 32 ? 1 : k <= 64 ? 2 : 4;
-    const long long qtiles = cdiv(nq, 32 * pl.qt);
-    const int forced = tuning().knn_slice_rows.load(std::memory_order_relaxed);
-    long long rows, slices;
-    if (forced > 0) {
-        rows = forced;
-        if (cdiv(n, rows) > kKnnMaxSlices) rows = cdiv(n, kKnnMaxSlices);
-    } else {
-        slices = std::min(std::max(cdiv(kKnnTargetWgs, qtiles), 1LL), cdiv(n, kKnnStepRows));
-        rows = cdiv(cdiv(n, slices), kKnnStepRows) * kKnnStepRows;
-    }
-    slices = cdiv(n, rows);
-    pl.slices = (int)slices;
-    pl.slice_rows = rows;
-    return pl;
-}
-
-// Workspace: nq * slices lists of k keys.  The bound below covers every plan and is non-decreasing in nq, n and k:
-// nq * slices <= nq * ceil(n / 256), and <= 64 * 512 + nq because slices <= ceil(512 / qtiles) and nq <= 64 qtiles.
-static size_t knn_ws_bytes(long long nq, long long n, int k) {
-    const int forced = tuning().knn_slice_rows.load(std::memory_order_relaxed);
-    long long cells;
-    if (forced > 0) cells = nq * std::min<long long>(kKnnMaxSlices, cdiv(n, forced));
-    else cells = std::min(nq * cdiv(n, kKnnStepRows), 64LL * kKnnTargetWgs + nq);
-    return align_up((size_t)cells * (size_t)k * sizeof(knn_key));
-}
-
-static int knn_check_shape(const char* who, int64_t nq, int64_t n, int k) {
-    if (nq < 1) ACX_FAIL(ACX_ERR_ARG, "%s: nq = %lld (expected >= 1)", who, (long long)nq);
-    if (n < 1) ACX_FAIL(ACX_ERR_ARG, "%s: n = %lld (expected >= 1)", who, (long long)n);
-    if (k < 1 || k > ACX_KNN_MAX_K) ACX_FAIL(ACX_ERR_ARG, "%s: k = %d (expected 1 .. %d)", who, k, ACX_KNN_MAX_K);
-    if (n > kF32MaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: n = %lld (at most 2^30 rows)", who, (long long)n);
-    if (nq > kF32MaxRows) ACX_FAIL(ACX_ERR_UNSUPPORTED, "%s: nq = %lld (at most 2^30 queries per call)", who, (long long)nq);
-    return ACX_OK;
-}
-
 int check_f32_rows(const char* who, const char* name, const float* x, int64_t ld, int dim) {
     if (!x) ACX_FAIL(ACX_ERR_ARG, "%s: %s is null", who, name);
     if (dim < 4 || dim > ACX_KNN_MAX_DIM || (dim & 3))
@@ -362,6 +273,16 @@ static int knn_launch_search(const KnnSearchP& p, long long qtiles, DeviceOnce& 
     const size_t lds = (size_t)32 * QT * 64 * R * sizeof(knn_key);
     ACX_TRY(set_max_dynamic_lds(once, &knn_search_kernel<QT, R>, lds));
     launch_kernel(&knn_search_kernel<QT, R>, dim3((unsigned)qtiles, (unsigned)p.slices), dim3(kKnnThreads), lds, s, p);
+    ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int knn_launch_merge(const knn_key* ws, long long nq, int slices, int k, int r, int* indices, float* scores, const int* status,
+                     hipStream_t s) {
+    const dim3 mgrid((unsigned)((nq + 3) / 4));
+    if (r == 1) launch_kernel(&knn_merge_kernel<1>, mgrid, dim3(kKnnThreads), 0, s, ws, nq, slices, k, indices, scores, status);
+    else if (r == 2) launch_kernel(&knn_merge_kernel<2>, mgrid, dim3(kKnnThreads), 0, s, ws, nq, slices, k, indices, scores, status);
+    else launch_kernel(&knn_merge_kernel<4>, mgrid, dim3(kKnnThreads), 0, s, ws, nq, slices, k, indices, scores, status);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }
@@ -434,12 +355,7 @@ int acx_knn_search(const float* q, int64_t ld_q, const float* q_inv_norm, int64_
     else rc = ri == 0 ? knn_launch_search<2, 1>(p, qtiles, once, s) : ri == 1 ? knn_launch_search<2, 2>(p, qtiles, once, s)
                                                                               : knn_launch_search<2, 4>(p, qtiles, once, s);
     ACX_TRY(rc);
-    const dim3 mgrid((unsigned)((nq + 3) / 4));
-    if (ri == 0) launch_kernel(&knn_merge_kernel<1>, mgrid, dim3(kKnnThreads), 0, s, (const knn_key*)p.ws, (long long)nq, pl.slices, k, (int*)indices, scores, (const int*)status);
-    else if (ri == 1) launch_kernel(&knn_merge_kernel<2>, mgrid, dim3(kKnnThreads), 0, s, (const knn_key*)p.ws, (long long)nq, pl.slices, k, (int*)indices, scores, (const int*)status);
-    else launch_kernel(&knn_merge_kernel<4>, mgrid, dim3(kKnnThreads), 0, s, (const knn_key*)p.ws, (long long)nq, pl.slices, k, (int*)indices, scores, (const int*)status);
-    ACX_HIP(hipGetLastError());
-    return ACX_OK;
+    return knn_launch_merge(p.ws, nq, pl.slices, k, pl.r, (int*)indices, scores, (const int*)status, s);
 }
 
 int acx_knn_vote(const int32_t* indices, const float* scores, int64_t nq, int k, const void* target, int target_dtype,

@@ -919,17 +919,23 @@ class ConvNeXt(nn.Module):
             return _cal.fit_platt(target, logits, **kw)
         return _cal.fit_temperature(target, logits, **kw)
 
-    def build_index(self, data, target=None, sample_rate=None, metric="cosine"):
+    def build_index(self, data, target=None, sample_rate=None, metric="cosine", quantize=None, rerank=True, oversample=4):
         """An EmbeddingIndex (pytorch/retrieval.py) over scene embeddings on the model's device: `data` is an (n, 768) tensor
         of embeddings, or a list of waveforms at `sample_rate`, whose scene embeddings are extracted first
-        (extract(..., what="scene", pack=True), as fit_head does); target: optional (n, C) labels for idx.classify."""
+        (extract(..., what="scene", pack=True), as fit_head does); target: optional (n, C) labels for idx.classify.
+        quantize="int8": a QuantizedIndex instead -- the coarse search on int8 codes, with rerank=True followed by the exact
+        fp32 scores of k * oversample candidates."""
         from .extract_embeddings import extract
-        from .retrieval import EmbeddingIndex
+        from .retrieval import EmbeddingIndex, QuantizedIndex
+        if quantize not in (None, "int8"):
+            raise ValueError("quantize must be None or \"int8\", got %r" % (quantize,))
         dev = self.head_audioset.weight.device
         if getattr(data, "ndim", None) == 2:
             emb = data
         else:
             emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
+        if quantize == "int8":
+            return QuantizedIndex(emb, metric=metric, target=target, device=dev, rerank=rerank, oversample=oversample)
         return EmbeddingIndex(emb, metric=metric, target=target, device=dev)
 
     def cluster(self, data, clusters, sample_rate=None, **kw):

@@ -6,6 +6,7 @@ ConvNeXt.search).
     python demo_retrieval.py --ckpt checkpoints/model.safetensors --data sounds/ --query dog.wav      # sounds/<class>/*.wav
     python demo_retrieval.py --synthetic                       # seeded weights and clips, no files needed
     python demo_retrieval.py --synthetic --clusters 8          # also k-means over the corpus: sizes, the clip nearest each centre
+    python demo_retrieval.py --synthetic --int8 [--oversample 4] [--no-rerank]     # int8 index: coarse search, exact fp32 rerank
 
 16-bit PCM WAV files at any rate (resampled on the device)."""
 import argparse
@@ -63,6 +64,9 @@ def main():
     ap.add_argument("-k", type=int, default=5)
     ap.add_argument("--metric", default="cosine", choices=("cosine", "dot"))
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--int8", action="store_true", help="an int8 index: coarse search on int8 codes, then the exact fp32 rerank")
+    ap.add_argument("--oversample", type=int, default=4, help="--int8: coarse candidates per neighbour asked for")
+    ap.add_argument("--no-rerank", action="store_true", help="--int8: keep codes only and return the coarse scores")
     ap.add_argument("--clusters", type=int, default=0, help="also cluster the corpus into this many clusters (k-means on the GPU)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -99,9 +103,11 @@ def main():
     print("%d clips, %d classes" % (len(waves), len(names)))
 
     t0 = time.perf_counter()
-    index = model.build_index(waves, target=target, sample_rate=rate, metric=a.metric)
+    index = model.build_index(waves, target=target, sample_rate=rate, metric=a.metric, quantize="int8" if a.int8 else None,
+                              rerank=not a.no_rerank, oversample=a.oversample)
     torch.cuda.synchronize()
-    print("index of %d x %d built in %.2f s" % (len(index), index.dim, time.perf_counter() - t0))
+    print("%sindex of %d x %d built in %.2f s" % ("int8 " + ("" if index.rerank else "codes-only ") if a.int8 else "", len(index),
+                                                  index.dim, time.perf_counter() - t0))
     label = target.float().argmax(1)
     k = min(a.k, len(index) - 1)
 
@@ -119,7 +125,9 @@ def main():
                                    ", ".join("%s %.3f (%s)" % (paths[j], s, names[int(label[j])])
                                              for s, j in zip(scores[r].tolist(), indices[r].tolist()))))
 
-    if a.clusters:
+    if a.clusters and a.int8 and a.no_rerank:
+        print("--clusters needs the fp32 rows: skipped with --no-rerank")
+    elif a.clusters:
         # no labels needed: k-means over the stored rows with the index's metric, and the stored clip nearest to each centre
         km = index.cluster(a.clusters, seed=a.seed)
         _, nearest = index.search(km.centers, 1)

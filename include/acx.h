@@ -1082,6 +1082,46 @@ ACX_API int acx_knn_vote(const int32_t* indices, const float* scores, int64_t nq
                          int64_t ld_target, int64_t n, int classes, int weighting, float temperature, float* out,
                          int64_t ld_out, int32_t* status, void* stream);
 
+/* ---- int8 embedding index: coarse search on int8 codes (i8 matrix instructions), exact fp32 rerank -----------------------------
+ * The two-stage design of a retrieval library over the search above (no reference counterpart, as for the search itself): a
+ * coarse search on per-row symmetric int8 codes, 1 byte per column instead of 4, then the exact fp32 scores of a short candidate
+ * list.  Stateless; every buffer is the caller's, on the device.
+ *   acx_knn_quantize_i8: per row i of x (n, dim) fp32 (the layout rules of acx_knn_search), all in fp32 and each operation
+ *     rounded on its own: y = x * inv_norm[i] (inv_norm NULL, the dot metric: y = x), amax = max |y|, g = 127.0f / amax,
+ *     code = (int8) clamp(rintf(y * g), -127, 127) (round half to even), scale[i] = amax / 127.0f.  A zero row gives zero
+ *     codes and scale 0.  A row with a NaN or +-inf among its y gives zero codes and scale NaN and ORs ACX_KNN_NONFINITE into
+ *     *status (never clears).  codes (n, ld_c) int8, 16-byte aligned, ld_c a multiple of 16 and >= dim rounded up to
+ *     ACX_KNN_I8_K; the columns from dim up to that multiple are written as zeros.
+ *   acx_knn_search_i8: cq (nq, dim) / cd (n, dim) int8 codes with row strides ld_cq / ld_cd (16-byte aligned, multiples of 16,
+ *     >= dim) and their scales sq / sd; dim is the PADDED code width, a multiple of ACX_KNN_I8_K in ACX_KNN_I8_K ..
+ *     ACX_KNN_MAX_DIM.  t = sum_c cq[i][c] cd[j][c] is exact in int32 (|t| <= 4096 * 127^2 = 66 064 384), and the score is
+ *     ((float)t * sq[i]) * sd[j]: one int -> float conversion (round to nearest even) and two rounded products.  Order,
+ *     exclude, output shapes, workspace (acx_knn_workspace_bytes), slicing (acx_knn_slices, ACX_KNN_SLICE_ROWS) and launch
+ *     sequence (4-byte clear of *status, search kernel, merge) are acx_knn_search's; where ws_bytes leaves room behind the
+ *     slices' lists (nq * slices * k keys), a search of 16 or more slices merges them in two levels -- the result is the same.  A NaN or infinite scale sets
+ *     ACX_KNN_NONFINITE: every index is then -1 and every score NaN.  The search kernel runs dense i8 matrix instructions and
+ *     is launched as workgroups that hold a whole compute unit, like the 16-bit kernels of a forward.
+ *   acx_knn_rescore: for each query the exact fp32 scores of its kc <= ACX_KNN_MAX_K candidate rows cand (nq, kc) int32 with row
+ *     stride ld_cand, with the SAME BITS acx_knn_search gives that (query, row) pair, and the first k <= kc of the one total
+ *     order into indices (nq, k) / scores (nq, k).  A candidate -1 is skipped; an index outside [0, n) is skipped and sets
+ *     ACX_KNN_BAD_INDEX; outputs beyond the valid candidates are -1 / NaN.  A non-finite exact dot product sets
+ *     ACX_KNN_NONFINITE and makes that query's row -1 / NaN.  A row listed twice is returned twice.  Clears *status first.
+ *     No workspace.
+ * acx_forward's launch contract, as above.  ARGUMENT errors return a negative status before any launch: a null pointer
+ * (inv_norm may be NULL; the inverse norms of acx_knn_rescore for ACX_KNN_DOT), a size < 1, k or kc > ACX_KNN_MAX_K, k > kc,
+ * k > n (n - 1 with exclude), a code width that is no multiple of ACX_KNN_I8_K or outside its range, a code stride that is no
+ * multiple of 16 or too short, ld_cand < kc, an unaligned pointer, the fp32 layout errors and workspace errors of acx_knn_search;
+ * n > 2^30 is ACX_ERR_UNSUPPORTED. */
+#define ACX_KNN_I8_K 32        /* contraction width of one i8 matrix instruction: code rows are padded to a multiple */
+ACX_API int acx_knn_quantize_i8(const float* x, int64_t ld, const float* inv_norm, int64_t n, int dim, int8_t* codes, int64_t ld_c,
+                                float* scale, int32_t* status, void* stream);
+ACX_API int acx_knn_search_i8(const int8_t* cq, int64_t ld_cq, const float* sq, int64_t nq, const int8_t* cd, int64_t ld_cd,
+                              const float* sd, int64_t n, int dim, int k, const int32_t* exclude, int32_t* indices, float* scores,
+                              int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_knn_rescore(const float* q, int64_t ld_q, const float* q_inv_norm, int64_t nq, const float* d, int64_t ld_d,
+                            const float* d_inv_norm, int64_t n, int dim, int metric, const int32_t* cand, int64_t ld_cand, int kc,
+                            int k, int32_t* indices, float* scores, int32_t* status, void* stream);
+
 /* ---- k-means over embeddings: Lloyd iterations with k-means++ seeding, all decisions on the device --------------------------------
  * Clustering for embeddings without labels (no reference counterpart).  Stateless; every buffer is the caller's, on the device.
  *   x (n, dim) and centers (clusters, dim) fp32 with row strides ld_x / ld_c, the layout rules of acx_knn_search: 16-byte

@@ -17,9 +17,9 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = os.environ.get("ACX_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
-# kernels (namespace acx) that run dense 16-bit MFMA on live data
+# kernels (namespace acx) that run dense 16-bit MFMA on live data, and the dense i8 MFMA of the int8 search (treated as that class)
 EXCLUSIVE = ("gemm_split16_kernel", "mlp_fused_split_kernel", "mlp_fused_wide_kernel", "mlp_fused_wide_bf16_kernel",
-             "mlp_fused_stat_bf16_kernel", "gemm_bf16_kernel", "dwconv7_mfma_kernel")
+             "mlp_fused_stat_bf16_kernel", "gemm_bf16_kernel", "dwconv7_mfma_kernel", "knn_search_i8_kernel")
 
 
 def kernels_of(lib):
