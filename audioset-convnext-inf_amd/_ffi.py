@@ -259,6 +259,13 @@ SIGNATURES = {
     "acx_kmeans_min_distance": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
     "acx_kmeans_sample": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_kmeans_seed": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
+    "acx_moments_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_moments": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
+    "acx_gram_f64": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp]),
+    "acx_eigh_workspace_bytes": (_c_int, [_c_int, ctypes.POINTER(_c_sz)]),
+    "acx_eigh": (_c_int, [_vp, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_pca_transform": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
+    "acx_pca_inverse": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
     "acx_frontend_info": (_c_int, [_vp, _pint, ctypes.POINTER(ctypes.c_float), _pint]),
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
@@ -800,6 +807,53 @@ MAX_EVENT_MEDIAN = 101                        # ACX_MAX_EVENT_MEDIAN
 EVENTS_NONFINITE, EVENTS_OVERFLOW = 1, 2      # bits of acx_decode_events' status word
 EVENTS_BAD_THRESHOLD = 4                      # the _classwise calls: a class with !(0 <= low <= threshold)
 EVENT_BYTES = ctypes.sizeof(AcxEvent)         # 32
+
+
+# ---- embedding statistics (acx_moments, acx_gram_f64, acx_eigh, acx_pca_*) ---------------------------------------------------
+STATS_MAX_DIM = 1024                           # ACX_STATS_MAX_DIM
+EIGH_MAX_SWEEPS = 64                           # ACX_EIGH_MAX_SWEEPS
+STATS_NONFINITE, STATS_NOT_CONVERGED, STATS_DEGENERATE = 1, 2, 4    # bits of the status words of acx_moments / acx_eigh
+
+
+class AcxEighState(ctypes.Structure):
+    """struct acx_eigh_state: the device-side state of acx_eigh (16 bytes)."""
+    _fields_ = [("sweeps", ctypes.c_int32), ("done", ctypes.c_int32), ("rotations", ctypes.c_int64)]
+
+
+def moments_workspace_bytes(n, dim):
+    """Workspace of acx_moments (host only; a function of n, dim and ACX_MOMENTS_SLICE_ROWS)."""
+    return _query(lib().acx_moments_workspace_bytes, _c_sz, int(n), int(dim))
+
+
+def moments(x, ld_x, n, dim, ddof, mean, cov, ld_c, status, ws, stream):
+    """acx_moments on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_moments(x, int(ld_x), int(n), int(dim), int(ddof), mean, cov, int(ld_c), status, ws[0], int(ws[1]), stream))
+
+
+def gram_f64(a, ld_a, b, ld_b, rows, m, n, out, ld_o, stream):
+    """acx_gram_f64 on raw device pointers (ctypes.c_void_p): out (m, n) = a^T b."""
+    check(lib().acx_gram_f64(a, int(ld_a), b, int(ld_b), int(rows), int(m), int(n), out, int(ld_o), stream))
+
+
+def eigh_workspace_bytes(dim):
+    """Workspace of acx_eigh (host only)."""
+    return _query(lib().acx_eigh_workspace_bytes, _c_sz, int(dim))
+
+
+def eigh(a, ld_a, dim, max_sweeps, values, vectors, ld_v, state, status, ws, stream):
+    """acx_eigh on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_eigh(a, int(ld_a), int(dim), int(max_sweeps), values, vectors, int(ld_v), state, status, ws[0], int(ws[1]),
+                         stream))
+
+
+def pca_transform(x, ld_x, n, dim, mean, w, ld_w, k, scale, out, ld_o, stream):
+    """acx_pca_transform on raw device pointers (ctypes.c_void_p); scale may be None."""
+    check(lib().acx_pca_transform(x, int(ld_x), int(n), int(dim), mean, w, int(ld_w), int(k), scale, out, int(ld_o), stream))
+
+
+def pca_inverse(z, ld_z, n, k, scale, w, ld_w, dim, mean, out, ld_o, stream):
+    """acx_pca_inverse on raw device pointers (ctypes.c_void_p); scale may be None."""
+    check(lib().acx_pca_inverse(z, int(ld_z), int(n), int(k), scale, w, int(ld_w), int(dim), mean, out, int(ld_o), stream))
 
 
 def event_params(threshold=0.5, low=None, median=1, min_duration=0.0, merge_gap=0.0):

@@ -232,6 +232,7 @@ struct Tuning {
     std::atomic<int> dw_stream{-1};    // ACX_DW_STREAM = 0 | 1: forces the tile / column-streaming depthwise kernels (-1: by launch size)
     std::atomic<int> head_path{0};     // ACX_HEAD_PATH = 1 | 2: forces the fused / class-tiled head in the forwards (0: by N, kHeadTiledMin)
     std::atomic<int> knn_slice_rows{0}; // ACX_KNN_SLICE_ROWS = 16 .. 2^30: database rows per slice of acx_knn_search (0: by launch size; tests run many slices on small inputs)
+    std::atomic<int> moments_slice_rows{0}; // ACX_MOMENTS_SLICE_ROWS = 16 .. 2^30: rows per slice of acx_moments (0: by n; tests run many slices on small inputs)
 };
 Tuning& tuning();
 void tuning_reload();

@@ -31,6 +31,9 @@ void tuning_reload() {
     const char* sr = std::getenv("ACX_KNN_SLICE_ROWS");
     const long srv = sr && sr[0] ? std::strtol(sr, nullptr, 10) : 0;
     t.knn_slice_rows.store(srv >= 16 && srv <= (1L << 30) ? (int)srv : 0, std::memory_order_relaxed);
+    const char* mr = std::getenv("ACX_MOMENTS_SLICE_ROWS");
+    const long mrv = mr && mr[0] ? std::strtol(mr, nullptr, 10) : 0;
+    t.moments_slice_rows.store(mrv >= 16 && mrv <= (1L << 30) ? (int)mrv : 0, std::memory_order_relaxed);
 }
 
 void set_error(const char* fmt, ...) {

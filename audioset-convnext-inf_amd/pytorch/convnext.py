@@ -951,6 +951,29 @@ class ConvNeXt(nn.Module):
             emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
         return kmeans(emb, clusters, device=dev, **kw)
 
+    def _scene_rows(self, data, sample_rate):
+        """`data` as build_index takes it -> (n, 768) scene embeddings: a 2-D tensor of embeddings as it is, a list of waveforms
+        at `sample_rate` extracted first (extract(..., what="scene", pack=True))."""
+        from .extract_embeddings import extract
+        if getattr(data, "ndim", None) == 2:
+            return data
+        return torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(self.head_audioset.weight.device)
+
+    def frechet_distance(self, data_a, data_b, sample_rate=None, **kw):
+        """The Frechet (audio) distance between two sets on the model's device (pytorch/statistics.py: frechet_distance): each
+        of data_a / data_b is an (n, 768) tensor of scene embeddings, or a list of waveforms at `sample_rate`, extracted as
+        build_index does; kw: max_sweeps.  -> statistics.FrechetDistance (0-d device tensors; float() / check() synchronise)."""
+        from .statistics import frechet_distance
+        a, b = self._scene_rows(data_a, sample_rate), self._scene_rows(data_b, sample_rate)
+        return frechet_distance(a, b, device=self.head_audioset.weight.device, **kw)
+
+    def fit_pca(self, data, components=None, whiten=False, sample_rate=None, **kw):
+        """PCA (pytorch/statistics.py: PCA.fit) of scene embeddings on the model's device: `data` is an (n, 768) tensor of
+        embeddings, or a list of waveforms at `sample_rate`; components: None, an integer, or a float in (0, 1) = the share of
+        the variance to keep; kw: max_sweeps, eps.  -> statistics.PCA."""
+        from .statistics import PCA
+        return PCA.fit(self._scene_rows(data, sample_rate), components, whiten, device=self.head_audioset.weight.device, **kw)
+
     def search(self, index, waveform, k=10, sample_rate=None):
         """Query by example: {"scores" (B, k) fp32, "indices" (B, k) int64, "scene" (B, 768)} of a (B, L) waveform batch --
         forward_scene_embeddings, then index.search, on one stream with no host synchronisation (capturable as a whole).

@@ -481,6 +481,24 @@ class EmbeddingIndex:
         return clustering._fit_rows(self._buf[:self._n], self.dim, self.inverse_norms if metric == "cosine" else None, clusters,
                                     metric, **kw)
 
+    def moments(self, ddof=1):
+        """Mean and covariance of the stored rows in float64 (pytorch/statistics.py: moments) -> statistics.Moments."""
+        from . import statistics
+        if self._n == 0:
+            raise ValueError("the index is empty")
+        return statistics.moments(self.embeddings, ddof, self.device)
+
+    def pca(self, components=None, whiten=False, **kw):
+        """PCA of the stored rows (pytorch/statistics.py: PCA.fit) -> (the fitted statistics.PCA, a new EmbeddingIndex over
+        PCA.transform of the rows, with this index's metric and targets); kw: max_sweeps, eps."""
+        from . import statistics
+        if self._n == 0:
+            raise ValueError("the index is empty")
+        fit = statistics.PCA.fit(self.embeddings, components, whiten, device=self.device, **kw)
+        reduced = EmbeddingIndex(fit.transform(self.embeddings), metric=self.metric, target=self.target, device=self.device,
+                                 workspace_limit=self.workspace_limit)
+        return fit, reduced
+
     def quantize(self, rerank=True, oversample=4):
         """-> a QuantizedIndex over the stored rows.  rerank=True: it SHARES this index (the fp32 rows are not copied; rows
         added to either later are seen by both); rerank=False: int8 codes, scales and a copy of the targets only."""

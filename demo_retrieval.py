@@ -6,6 +6,7 @@ ConvNeXt.search).
     python demo_retrieval.py --ckpt checkpoints/model.safetensors --data sounds/ --query dog.wav      # sounds/<class>/*.wav
     python demo_retrieval.py --synthetic                       # seeded weights and clips, no files needed
     python demo_retrieval.py --synthetic --clusters 8          # also k-means over the corpus: sizes, the clip nearest each centre
+    python demo_retrieval.py --synthetic --pca 16 [--whiten]   # also search a PCA-reduced copy of the index, against the full one
     python demo_retrieval.py --synthetic --int8 [--oversample 4] [--no-rerank]     # int8 index: coarse search, exact fp32 rerank
 
 16-bit PCM WAV files at any rate (resampled on the device)."""
@@ -68,6 +69,8 @@ def main():
     ap.add_argument("--oversample", type=int, default=4, help="--int8: coarse candidates per neighbour asked for")
     ap.add_argument("--no-rerank", action="store_true", help="--int8: keep codes only and return the coarse scores")
     ap.add_argument("--clusters", type=int, default=0, help="also cluster the corpus into this many clusters (k-means on the GPU)")
+    ap.add_argument("--pca", type=int, default=0, help="also reduce the index to this many principal components (PCA on the GPU)")
+    ap.add_argument("--whiten", action="store_true", help="--pca: whiten the reduced rows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("this build runs on an MI355X; no GPU is visible")
@@ -137,6 +140,18 @@ def main():
                                                                            km.counts.tolist()))
         for c, j in enumerate(nearest[:, 0].tolist()):
             print("    cluster %d (%d clips): nearest %s (%s)" % (c, int(km.counts[c]), paths[j], names[int(label[j])]))
+
+    if a.pca and a.int8:
+        print("--pca reduces the fp32 index: skipped with --int8")
+    elif a.pca:
+        # covariance, eigenvectors and projection on the device; the reduced index keeps the metric and the targets
+        pca, small = index.pca(min(a.pca, index.dim, len(index)), whiten=a.whiten)
+        pca.check()
+        _, full_nn = index.search(None, 1)
+        _, small_nn = small.search(None, 1)
+        same = float((full_nn[:, 0] == small_nn[:, 0]).float().mean())
+        print("PCA %d -> %d%s: %.1f %% of the variance kept; the nearest neighbour is the full index's for %.1f %% of the clips"
+              % (index.dim, small.dim, " (whitened)" if a.whiten else "", 100 * float(pca.explained_variance_ratio_.sum()), 100 * same))
 
     # the kNN probe: each clip labelled by its neighbours (itself left out), scored like any tagger
     from audioset_convnext_inf_amd.pytorch.retrieval import vote

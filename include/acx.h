@@ -1190,6 +1190,71 @@ ACX_API int acx_kmeans_seed(const float* x, int64_t ld_x, const float* x_inv_nor
                             const double* u, int32_t* picked, float* centers, int64_t ld_c, int32_t* status, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- embedding statistics: float64 moments, Gram products, a symmetric eigensolver, PCA projection ------------------------------
+ * Second-order statistics of a set of embeddings (no reference counterpart): what covariance, PCA / whitening, Mahalanobis
+ * scores and the Frechet distance rest on.  Stateless; every buffer is the caller's, on the device.  1 <= dim <=
+ * ACX_STATS_MAX_DIM; dim need NOT be a multiple of 4 and no pointer needs more than its element's alignment: tails are
+ * predicated.  Row strides ld >= the row's width.  n <= 2^30 rows.
+ *   acx_moments: x (n, dim) fp32 -> mean (dim) and cov (dim, dim) float64, ddof in {0, 1}.
+ *     mean[j] = (sum_i (double)x[i][j]) / n: the n rows are cut into slices of R rows; inside a slice row i goes to partial
+ *     i mod 4, each partial is summed in ascending i, the four are added as ((p0 + p1) + p2) + p3, the slices' sums are added
+ *     in ascending slice order and the total is divided ONCE by n.
+ *     cov[a][b] = (sum_i fl(x_ia - mean_a) fl(x_ib - mean_b)) / (n - ddof): the rows are centred ON LOAD in float64 (one
+ *     rounded subtraction per element), the products and sums run on v_mfma_f64_16x16x4_f64, four rows per instruction in
+ *     ascending row order inside a slice; the slices' partial tiles are summed in ascending slice order by a second pass and
+ *     divided once.  Only the 64 x 64 tiles with b >= a are computed; the result is mirrored, so cov is exactly symmetric.
+ *     No float atomics: the same input gives the same bits on every run.  R = ACX_MOMENTS_SLICE_ROWS (16 .. 2^30, rounded up
+ *     to a multiple of 4; read at the first acx_create and by acx_tuning_refresh) or, without it, max(1024, ceil(n / 16))
+ *     rounded up to a multiple of 4.  A NaN or infinite element sets ACX_STATS_NONFINITE (the outputs are written all the
+ *     same, non-finite where the arithmetic makes them so); n - ddof == 0 sets ACX_STATS_DEGENERATE and writes a zero cov.
+ *   acx_gram_f64: out (m, n) = A^T B for float64 A (rows, m) and B (rows, n), m, n <= ACX_STATS_MAX_DIM, on the same tile body:
+ *     out[a][b] = sum_i A[i][a] B[i][b], four rows per instruction in ascending row order, ONE slice.  No workspace, no status.
+ *   acx_eigh: a (dim, dim) float64 symmetric (the upper triangle is read) -> values (dim) descending (ties by the original
+ *     column index) and vectors (dim, dim): ROW k is the k-th eigenvector, signed so that its entry of the largest magnitude
+ *     (lowest index on ties) is positive.  Cyclic Jacobi with the round-robin ordering: with m = dim rounded up to even, a sweep
+ *     is m - 1 rounds; in round r index m - 1 pairs with r and every other i with (2 r - i) mod (m - 1) (pairs with the padding
+ *     index of an odd dim are idle).  A pair p < q is rotated where |a_pq| > 2^-53 max_i |a_ii| of the INPUT, by
+ *     theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(1 + theta^2)), c = 1 / sqrt(1 + t^2), s = t c;
+ *     a_pp <- a_pp - t a_pq, a_qq <- a_qq + t a_pq, a_pq <- 0, and every other new element from the four old ones
+ *     A[{i, pi(i)}][{j, pi(j)}] (for i <= j, mirrored: the matrix stays exactly symmetric).  One launch per round reads one
+ *     copy of the matrix (and of the accumulated vectors) and writes the other; every workgroup recomputes the rotations of
+ *     its rows and columns from the old elements, so nothing inside a launch waits on another workgroup.  Each round adds the
+ *     rotations it applied to a counter of its sweep; the first round of a sweep sets state->done when the sweep before applied
+ *     none, and every later launch returns at once: max_sweeps (1 .. ACX_EIGH_MAX_SWEEPS) sweeps are QUEUED and the host reads
+ *     nothing.  state->sweeps = sweeps that ran (the closing one that applied no rotation included), state->rotations = rotations
+ *     applied.  ACX_STATS_NOT_CONVERGED when the last queued sweep still rotated; ACX_STATS_NONFINITE for a NaN or infinite
+ *     input (nothing is rotated then).
+ *   acx_pca_transform: out[i][c] = scale[c] * sum_j fl32(x[i][j] - mean[j]) W[c][j], x (n, dim), W (k, dim), mean (dim), scale (k)
+ *     or NULL, all fp32, k <= dim, on the f32 matrix instructions (v_mfma_f32_32x32x2_f32).  The sum runs over groups of 16
+ *     columns in ascending order; inside a group instruction e = 0 .. 7 adds columns e and 8 + e of the group, zeros past dim.
+ *   acx_pca_inverse: out[i][j] = mean[j] + sum_c (z[i][c] * scale[c]) W[c][j], z (n, k); components in ascending pairs (2 e,
+ *     2 e + 1), one instruction per pair, zero past k.  scale NULL: 1.
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable.  ARGUMENT errors
+ * (a null pointer, a size < 1 or over its limit, ld too short, ddof outside {0, 1}, max_sweeps outside its range, an unaligned
+ * state or float64 pointer, workspace errors) return a negative status before any launch; n > 2^30 is ACX_ERR_UNSUPPORTED.  The
+ * data calls clear *status first. */
+#define ACX_STATS_MAX_DIM 1024
+#define ACX_EIGH_MAX_SWEEPS 64
+#define ACX_STATS_NONFINITE 1
+#define ACX_STATS_NOT_CONVERGED 2
+#define ACX_STATS_DEGENERATE 4
+typedef struct acx_eigh_state {
+    int32_t sweeps, done;
+    int64_t rotations;
+} acx_eigh_state;
+ACX_API int acx_moments_workspace_bytes(int64_t n, int dim, size_t* out_bytes);
+ACX_API int acx_moments(const float* x, int64_t ld_x, int64_t n, int dim, int ddof, double* mean, double* cov, int64_t ld_c,
+                        int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_gram_f64(const double* a, int64_t ld_a, const double* b, int64_t ld_b, int64_t rows, int m, int n, double* out,
+                         int64_t ld_o, void* stream);
+ACX_API int acx_eigh_workspace_bytes(int dim, size_t* out_bytes);
+ACX_API int acx_eigh(const double* a, int64_t ld_a, int dim, int max_sweeps, double* values, double* vectors, int64_t ld_v,
+                     acx_eigh_state* state, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_pca_transform(const float* x, int64_t ld_x, int64_t n, int dim, const float* mean, const float* w, int64_t ld_w,
+                              int k, const float* scale, float* out, int64_t ld_o, void* stream);
+ACX_API int acx_pca_inverse(const float* z, int64_t ld_z, int64_t n, int k, const float* scale, const float* w, int64_t ld_w,
+                            int dim, const float* mean, float* out, int64_t ld_o, void* stream);
+
 /* Which evaluation of the STFT the frontend uses (round 6).  ACX_FRONTEND_AUTO (default): the FFT kernel when the stored buffers are
  * window x DFT, the dense contraction otherwise (acx_finalize above).  ACX_FRONTEND_DENSE: ALWAYS the dense contraction with the
  * stored `conv_real` / `conv_imag` weights -- the reference's own formulation (two Conv1d, convnext.py:179-187,298) -- 2.1 GFLOP
@@ -1213,7 +1278,8 @@ ACX_API int acx_frontend_info(const acx_ctx* ctx, int* dense_dft, float* stft_de
 
 /* Diagnostics.  The tile-shape A/B switches ACX_GEMM_MI, ACX_WIDE_NPB, ACX_WIDE_PERSIST, ACX_DW_STREAM and ACX_DWM_WAVES, and
  * ACX_HEAD_PATH (1: the fused head kernel, 2: the class-tiled one, whatever N), and ACX_KNN_SLICE_ROWS (database rows per slice of
- * acx_knn_search, 16 .. 2^30: tests run many slices on a small database) are read from the
+ * acx_knn_search, 16 .. 2^30: tests run many slices on a small database) and ACX_MOMENTS_SLICE_ROWS (rows per slice of
+ * acx_moments, 16 .. 2^30, for the same purpose) are read from the
  * environment once, at the first acx_create; this re-reads them (tests force every tile shape through it and require
  * bit-identical results).  Launches never touch the environment.  No reference counterpart. */
 ACX_API int acx_tuning_refresh(void);
