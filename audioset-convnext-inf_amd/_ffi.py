@@ -266,6 +266,9 @@ SIGNATURES = {
     "acx_eigh": (_c_int, [_vp, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_pca_transform": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
     "acx_pca_inverse": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
+    "acx_ranking_workspace_bytes": (_c_int, [_c_i64, _c_int, _c_i64, ctypes.POINTER(_c_sz)]),
+    "acx_ranking_metrics": (_c_int, [_vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _c_sz, _vp]),
     "acx_frontend_info": (_c_int, [_vp, _pint, ctypes.POINTER(ctypes.c_float), _pint]),
     "acx_set_frontend": (_c_int, [_vp, _c_int]),
     "acx_tuning_refresh": (_c_int, []),
@@ -552,6 +555,24 @@ def weighted_metrics(scores, ld_scores, target, target_dtype, ld_target, n, clas
     """acx_weighted_metrics on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
     check(lib().acx_weighted_metrics(scores, int(ld_scores), target, int(target_dtype), int(ld_target), int(n), int(classes),
                                      weights, int(ld_w), int(replicates), ap, auc, dprime, status, ws[0], int(ws[1]), stream))
+
+
+RANK_N_POS, RANK_COVERAGE, RANK_BAD_PAIRS, RANK_HITS = 0, 1, 2, 3     # enum acx_ranking_count: the columns of row_counts
+RANK_COUNTS = 4                               # ACX_RANK_COUNTS
+RANK_WAVE_MAX_CLASSES = 1024                  # ACX_RANK_WAVE_MAX_CLASSES: up to here a wave ranks a row, beyond a workgroup
+
+
+def ranking_workspace_bytes(rows, classes, slice_rows=0):
+    """Workspace of acx_ranking_metrics for `rows` rows of `classes` scores in slices of slice_rows (0: the default; host only)."""
+    return _query(lib().acx_ranking_workspace_bytes, _c_sz, int(rows), int(classes), int(slice_rows))
+
+
+def ranking_metrics(scores, ld_s, target, target_dtype, ld_t, rows, classes, k, slice_rows, row_counts, row_psum, class_count,
+                    class_psum, status, ws, stream):
+    """acx_ranking_metrics on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes) of ranking_workspace_bytes."""
+    check(lib().acx_ranking_metrics(scores, int(ld_s), target, int(target_dtype), int(ld_t), int(rows), int(classes), int(k),
+                                    int(slice_rows), row_counts, row_psum, class_count, class_psum, status, ws[0], int(ws[1]),
+                                    stream))
 
 
 FIT_BAD_INDEX = 1                              # bit of the status word of acx_head_fit_step / acx_head_fit_grad

@@ -288,6 +288,11 @@ def main():
         thresholds = op.threshold.cpu().numpy()
         print("val F1 at per-class thresholds: macro %.3f  micro %.3f  (mAP %.3f; %d of %d classes without a positive never fire)"
               % (op.macro()["f"], op.micro()["f"], fit.history[-1]["mAP"], int(np.isinf(thresholds).sum()), len(names)))
+        # the per-clip view of the same scores: what multi-label benchmarks outside AudioSet report (lwlrap: DCASE 2019 Task 2)
+        from audioset_convnext_inf_amd.pytorch.ranking import ranking_metrics
+        rank = ranking_metrics(target[va], probs)
+        print("val lwlrap %.3f  LRAP %.3f  (coverage error %.2f, ranking loss %.4f)"
+              % (rank.lwlrap, rank.lrap, rank.coverage_error, rank.ranking_loss))
 
     os.makedirs(a.out, exist_ok=True)
     sd = {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}

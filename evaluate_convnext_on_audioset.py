@@ -7,6 +7,8 @@ gathered once at the end); a single process works too.
 Scores: --metrics gpu (default) computes the per-class statistics on each rank's GPU (pytorch/metrics.py, exact up to float64
 rounding); --metrics sklearn makes the reference's host calls.  --bootstrap R adds clip-level bootstrap confidence intervals
 (R resamples on the GPU, pytorch/metrics.py bootstrap_metrics) as one extra line per statistic; the sklearn path has none.
+--ranking adds the per-clip ranking metrics of the same scores (LRAP, lwlrap, coverage error, ranking loss, one-error; computed on
+the GPU, pytorch/ranking.py) after that report; without the flag the output is what it was.
 
 Data: either the reference's packed HDF5 files (needs h5py) or .npy shards (int16 waveforms (N,320000) +
 targets (N,527)).  Without data, --synthetic N scores a seeded synthetic set (sanity check of the plumbing
@@ -72,7 +74,7 @@ def evaluate(args):
     for name, shard in sets:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        kept = {} if args.bootstrap > 0 else None
+        kept = {} if args.bootstrap > 0 or args.ranking else None
         stats = evaluate_sharded(model, shard, batch_size=args.batch_size, metrics=args.metrics, keep=kept)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -82,13 +84,20 @@ def evaluate(args):
             print("Validate %s d-prime: %.3f" % (name, np.mean(stats["d_prime"])))
             print("(%d clips in %.2f s on %d GPU(s): %.1f clips/s incl. int16->fp32, H2D and metrics)"
                   % (len(shard), dt, world, len(shard) / dt))
-            if kept is not None:
+            if args.bootstrap > 0:
                 from audioset_convnext_inf_amd.pytorch.metrics import bootstrap_metrics
                 ci = bootstrap_metrics(kept["target"], kept["clipwise_output"], replicates=args.bootstrap, seed=args.seed,
                                        device=torch.device("cuda", local_rank))
                 for label, key in (("mAP", "mAP"), ("AUC", "auc"), ("d-prime", "d_prime")):
                     print("Validate %s %s %d%% CI: [%.3f, %.3f] (%d resamples)"
                           % (name, label, round(100 * ci["confidence"]), ci[key]["low"], ci[key]["high"], args.bootstrap))
+            if args.ranking:
+                from audioset_convnext_inf_amd.pytorch.ranking import ranking_metrics
+                r = ranking_metrics(kept["target"], kept["clipwise_output"], device=torch.device("cuda", local_rank))
+                print("Validate %s LRAP: %.3f" % (name, r.lrap))
+                print("Validate %s lwlrap: %.3f" % (name, r.lwlrap))
+                print("Validate %s coverage error: %.2f  ranking loss: %.4f  one-error: %.3f"
+                      % (name, r.coverage_error, r.ranking_loss, r.one_error))
 
 
 if __name__ == "__main__":
@@ -105,6 +114,9 @@ if __name__ == "__main__":
                    help="R > 0: also print 95%% percentile confidence intervals of mAP / AUC / d-prime from R clip-level bootstrap "
                         "resamples computed on the GPU (default 0: off).  Needs --metrics gpu: the sklearn path has no bootstrap")
     p.add_argument("--seed", type=int, default=0, help="seed of the bootstrap resamples")
+    p.add_argument("--ranking", action="store_true",
+                   help="also print the per-clip ranking metrics (LRAP, lwlrap, coverage error, ranking loss, one-error), computed "
+                        "on the GPU from the same scores (default: off)")
     args = p.parse_args()
     if args.bootstrap < 0:
         p.error("--bootstrap must be >= 0")

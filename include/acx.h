@@ -1255,6 +1255,41 @@ ACX_API int acx_pca_transform(const float* x, int64_t ld_x, int64_t n, int dim, 
 ACX_API int acx_pca_inverse(const float* z, int64_t ld_z, int64_t n, int k, const float* scale, const float* w, int64_t ld_w,
                             int dim, const float* mean, float* out, int64_t ld_o, void* stream);
 
+/* ---- ranking metrics: the classes of one clip ranked against each other ------------------------------------------------------
+ * What LRAP, lwlrap (DCASE 2019 Task 2), coverage error, label-ranking loss, one-error and precision / recall at k are made of
+ * (no reference counterpart; sklearn 1.7.2's label_ranking_average_precision_score, coverage_error and label_ranking_loss are
+ * the yardsticks): integer counts per (row, positive class).  For row i with scores s (classes) and a 0 / 1 target, and every
+ * positive class j -- scores compared as float32 with -0.0 == +0.0, denormals in their own order:
+ *   ge_j = #{c : s_c >= s_j}   pge_j = #{c positive : s_c >= s_j}   ord_j = #{c : s_c > s_j} + #{c < j : s_c == s_j}
+ * (ge is the rank with ties at their worst, sklearn's rule; ord is the place in the total order score descending, then class
+ * index ascending).  Per row: n_pos; psum = sum_j pge_j / ge_j, each quotient the correctly rounded float64 of the integer ratio,
+ * added in ASCENDING j; coverage = max_j ge_j (0 without positives); bad_pairs = sum_j (ge_j - pge_j), the (positive, negative)
+ * pairs not strictly ordered; hits_k = #{j : ord_j < k}.  Per class c: class_count[c] = rows in which c is positive, class_psum[c] =
+ * the sum over those rows of pge / ge, added in ASCENDING row.  No float atomics: the same inputs give the same bits on every run.
+ *   acx_ranking_metrics: scores (rows, classes) fp32 with row stride ld_s; target of target_dtype with row stride ld_t, as
+ *     acx_tagging_metrics takes them, with its DATA errors: a NaN or infinite score sets ACX_METRICS_NONFINITE, a target other
+ *     than 0 / 1 ACX_METRICS_BAD_TARGET in *status (cleared first); the outputs of such a row are unspecified, inside their
+ *     buffers.  1 <= classes <= ACX_MAX_CLASSES, 1 <= rows <= 2^30, 1 <= k <= classes.  row_counts: (rows, 4) int64 = n_pos,
+ *     coverage, bad_pairs, hits_k; row_psum (rows), class_count (classes), class_psum (classes).  The rows run in slices of
+ *     slice_rows (0: the default, 2^26 / (8 classes) rows and at least 256; at most 2^22 slices): a row pass writes the slice's
+ *     quotients to the workspace, 8 * classes bytes per slice row, and a column pass adds them onto class_psum / class_count; the
+ *     slices follow each other on `stream`.  The results do not depend on slice_rows.  Up to 1 024 classes a wave ranks a row,
+ *     four rows per workgroup; wider rows take a workgroup each.  The cost is O(n_pos * classes) per row: dense targets on very
+ *     wide heads are quadratic.
+ *   acx_ranking_workspace_bytes: 8 * classes * min(rows, slice rows), rounded up to 256 -- non-decreasing in slice_rows and
+ *     independent of rows beyond one slice (host only).
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable.  ARGUMENT errors
+ * return before any launch: ACX_ERR_ARG for a null pointer, a bad target_dtype, rows < 1, classes or k out of range, a row stride
+ * shorter than `classes`, slice_rows < 0 or too many slices; rows > 2^30 is ACX_ERR_UNSUPPORTED; a workspace too small or not
+ * 256-byte aligned is ACX_ERR_WORKSPACE. */
+enum acx_ranking_count { ACX_RANK_N_POS = 0, ACX_RANK_COVERAGE = 1, ACX_RANK_BAD_PAIRS = 2, ACX_RANK_HITS = 3 };
+#define ACX_RANK_COUNTS 4
+#define ACX_RANK_WAVE_MAX_CLASSES 1024
+ACX_API int acx_ranking_workspace_bytes(int64_t rows, int classes, int64_t slice_rows, size_t* out_bytes);
+ACX_API int acx_ranking_metrics(const float* scores, int64_t ld_s, const void* target, int target_dtype, int64_t ld_t, int64_t rows,
+                                int classes, int k, int64_t slice_rows, int64_t* row_counts, double* row_psum,
+                                int64_t* class_count, double* class_psum, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* Which evaluation of the STFT the frontend uses (round 6).  ACX_FRONTEND_AUTO (default): the FFT kernel when the stored buffers are
  * window x DFT, the dense contraction otherwise (acx_finalize above).  ACX_FRONTEND_DENSE: ALWAYS the dense contraction with the
  * stored `conv_real` / `conv_imag` weights -- the reference's own formulation (two Conv1d, convnext.py:179-187,298) -- 2.1 GFLOP
