@@ -100,6 +100,14 @@ class AcxSpecAug(ctypes.Structure):
     """struct acx_spec_aug: one clip's stripes of acx_augment_spec (64 bytes)."""
     _fields_ = [(k, ctypes.c_int32 * AUG_MAX_STRIPES) for k in ("t_bgn", "t_len", "f_bgn", "f_len")]
 
+
+class AcxDwconv7Plan(ctypes.Structure):
+    """struct acx_dwconv7_plan_t: what a column-kernel launch consists of (acx_test_dwconv7_plan)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_out", "s0", "k7", "n_seg", "n_items")]
+
+
+_pplan = ctypes.POINTER(AcxDwconv7Plan)
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -275,6 +283,11 @@ SIGNATURES = {
     "acx_test_fail_sub": (_c_int, [_vp, _c_int]),
     "acx_test_stage_tail": (_c_int, [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_sz, _vp]),
     "acx_test_stage_tail_scratch_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_test_dwconv7_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _pplan]),
+    "acx_test_dwconv7_varlen_plan": (_c_int, [_c_int, ctypes.POINTER(_c_i64), _c_int, _c_int, _pplan]),
+    "acx_test_dwconv7_form": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "acx_test_dwconv7_varlen": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _c_sz, _vp]),
+    "acx_test_dwconv7_varlen_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz)]),
     "acx_profile_enable": (_c_int, [_vp, _c_int]),
     "acx_profile_read": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64)]),
 }

@@ -299,6 +299,18 @@ constexpr size_t kDwSinkWindowBytes = 64 * 1024;      // >= a row's lane offsets
 constexpr size_t kDwSinkBytes = kDwSinkWindows * kDwSinkWindowBytes;
 int launch_dwconv_col(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H, int W,
                       int target_waves, hipStream_t s);
+// What a column-kernel launch consists of: segments of n_out = 7 k7 - s0 output rows of the Vt stacked rows, n_seg of them, six
+// wave columns each.  dw_col_segments is the ONE place that decides it (wps: waves per SIMD of the width's kernel; whole_groups:
+// the variable-length kernel, n_out a multiple of seven); dw_col_too_tall: the batch is beyond the kernel's multiply-high
+// division.  dwconv_col_plan / _varlen: the same for a stage's width, for the test-support entry points.
+struct DwColPlan { int n_out, s0, k7, n_seg, n_items; };
+DwColPlan dw_col_segments(long long Vt, int wps, int target_waves, bool whole_groups);
+bool dw_col_too_tall(int B, int H);
+int dwconv_col_plan(int W, int B, int H, int target_waves, DwColPlan* plan);
+int dwconv_col_plan_varlen(int stage, int vrows, int target_waves, DwColPlan* plan);
+// launch_dwconv's fp32 kernels with the form given: col = false the ring / tile kernel, true the column kernel at target_waves
+int launch_dwconv_form(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, int B, int H, int W, bool col,
+                       int target_waves, hipStream_t s);
 // matrix-pipe form for bf16 activations (dwconv_mfma.hip): weights rounded to bf16, fp32 accumulation; every launch size.
 // dwconv_mfma_pack: its weight operands (BlockW::dw_ops) from the depthwise weights as stored, [C][49]
 std::vector<uint16_t> dwconv_mfma_pack(const std::vector<float>& dw, int C);
@@ -392,7 +404,7 @@ int launch_dwconv_col_varlen(const void* x, void* y, const float* wt, const floa
 int launch_dwconv_mfma_varlen(const void* x, void* y, const void* dw_ops, const float* bias, void* sink, const VarGeom& vg,
                               int stage, int target_waves, hipStream_t s);
 int launch_dwconv_varlen(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, const VarGeom& vg, int stage,
-                         hipStream_t s, bool act_bf16);
+                         hipStream_t s, bool act_bf16, int target_waves = 0 /* 0: one wave per SIMD (fp32), ACX_DWM_WAVES per CU (bf16) */);
 int launch_pool_head_varlen(acx_ctx* c, const float* x, const VarGeom& vg, float* scene, float* logits, float* probs,
                             hipStream_t s);
 int launch_nhwc_to_nchw_varlen(acx_ctx* c, const float* x, float* out, const VarGeom& vg, hipStream_t s);

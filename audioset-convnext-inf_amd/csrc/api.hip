@@ -318,6 +318,72 @@ int acx_test_stage_tail(acx_ctx* c, int stage, float* x, float* out, int B, int 
     return ACX_OK;
 }
 
+static void export_plan(const DwColPlan& p, acx_dwconv7_plan_t* out) {
+    out->n_out = p.n_out; out->s0 = p.s0; out->k7 = p.k7; out->n_seg = p.n_seg; out->n_items = p.n_items;
+}
+
+int acx_test_dwconv7_plan(int stage, int B, int H, int target_waves, acx_dwconv7_plan_t* plan) {
+    if (!plan || stage < 0 || stage > 3 || B <= 0 || H <= 0 || target_waves <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_plan: bad argument");
+    DwColPlan p;
+    ACX_TRY(dwconv_col_plan(kStemW >> stage, B, H, target_waves, &p));
+    export_plan(p, plan);
+    return ACX_OK;
+}
+
+int acx_test_dwconv7_varlen_plan(int stage, const int64_t* lengths, int n, int target_waves, acx_dwconv7_plan_t* plan) {
+    if (!plan || stage < 0 || stage > 3 || target_waves <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen_plan: bad argument");
+    VarGeom vg;
+    size_t bytes = 0;
+    ACX_TRY(varlen_geometry(lengths, n, nullptr, &vg, &bytes));
+    DwColPlan p;
+    ACX_TRY(dwconv_col_plan_varlen(stage, vg.vrows[stage], target_waves, &p));
+    export_plan(p, plan);
+    return ACX_OK;
+}
+
+int acx_test_dwconv7_form(acx_ctx* c, int stage, int block, const float* x, float* y, float* stats, int B, int H, int Wd, int form,
+                          int target_waves, void* stream) {
+    ACX_TRY(need_ready(c));
+    ACX_TRY(check_stage(stage, block));
+    if (!x || !y || B <= 0 || H <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_form: bad argument");
+    if (Wd != (kStemW >> stage)) ACX_FAIL(ACX_ERR_SHAPE, "stage %d has width %d, got %d", stage, kStemW >> stage, Wd);
+    if (form != 0 && form != 1) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_form: form %d (expected 0: ring / tile, 1: column)", form);
+    if (form == 1) {
+        int cus = 0;
+        ACX_TRY(cu_count_of_current_device(&cus));
+        if (target_waves < 1 || target_waves > 4 * cus)
+            ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_form: target_waves %d (expected 1 .. %d)", target_waves, 4 * cus);
+        if (dw_col_too_tall(B, H)) ACX_FAIL(ACX_ERR_SHAPE, "acx_test_dwconv7_form: batch too tall for the column kernel (%d clips of %d rows)", B, H);
+    }
+    return launch_dwconv_form(c, c->blocks[stage][block], kDims[stage], x, y, stats, B, H, Wd, form == 1, target_waves, (hipStream_t)stream);
+}
+
+int acx_test_dwconv7_varlen_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes) {
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen_scratch_bytes: bad argument");
+    VarGeom vg;
+    return varlen_geometry(lengths, n, nullptr, &vg, out_bytes);
+}
+
+int acx_test_dwconv7_varlen(acx_ctx* c, int stage, int block, const void* x, void* y, const int64_t* lengths, int n, int target_waves,
+                            void* scratch, size_t scratch_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    ACX_TRY(check_stage(stage, block));
+    if (!x || !y || !scratch) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen: null pointer");
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    if (target_waves < 1 || target_waves > 8 * cus)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen: target_waves %d (expected 1 .. %d)", target_waves, 8 * cus);
+    VarGeom vg;
+    size_t need = 0;
+    ACX_TRY(varlen_geometry(lengths, n, (char*)scratch, &vg, &need));
+    if (scratch_bytes < need || ((uintptr_t)scratch & 255))
+        ACX_FAIL(ACX_ERR_WORKSPACE, "acx_test_dwconv7_varlen: scratch too small (%zu < %zu) or misaligned", scratch_bytes, need);
+    const bool ab = act_bf16(c, stage);
+    if (ab && stage > 2) ACX_FAIL(ACX_ERR_STATE, "acx_test_dwconv7_varlen: no bf16 activations in stage %d", stage);
+    ACX_TRY(launch_varlen_tables(lengths, vg, (hipStream_t)stream));
+    return launch_dwconv_varlen(c, c->blocks[stage][block], kDims[stage], x, y, nullptr, vg, stage, (hipStream_t)stream, ab, target_waves);
+}
+
 int acx_profile_enable(acx_ctx* c, int on) {
     if (!c) ACX_FAIL(ACX_ERR_ARG, "null context");
     c->prof.on = on != 0;

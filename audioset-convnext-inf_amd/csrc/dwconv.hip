@@ -647,7 +647,7 @@ static bool use_col_kernel(const acx_ctx* c, int B, int H, int W, int* target_wa
     if (cu_count_of_current_device(&cus) != ACX_OK) return false;
     *target_waves = 4 * cus / inflight_ways();
     const long long Vt = (long long)B * (H + 3) - 3;
-    if ((Vt + 16ll * (H + 3) + 64) * (H + 3) >= 0xffffffffll) return false;   // beyond the multiply-high division of the column kernel: the ring kernel chunks
+    if (dw_col_too_tall(B, H)) return false;   // beyond the multiply-high division of the column kernel: the ring kernel chunks
     if (force == 1) return true;
     // rows of the stacked batch per wave segment (dwconv_col.hip: one wave per SIMD in stages 0-1, two in stages 2-3)
     const bool two = W <= 14;
@@ -670,10 +670,19 @@ int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, fl
         const int per_cu = tuning().dwm_waves.load(std::memory_order_relaxed);
         return launch_dwconv_mfma(x, y, w.dw_ops, w.dwb, c->d_dw_sink, B, H, W, (per_cu ? per_cu : 8) * cus / inflight_ways(), s);
     }
+    int target_waves = 0;
+    const bool col = model_shape && use_col_kernel(c, B, H, W, &target_waves);
+    return launch_dwconv_form(c, w, C, x, y, stats, B, H, W, col, target_waves, s);
+}
+
+// The fp32 kernels with the form given (launch_dwconv: chosen by launch size; acx_test_dwconv7_form: by the caller).
+int launch_dwconv_form(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, int B, int H, int W, bool col,
+                       int target_waves, hipStream_t s) {
     {
         ProfScope ps(c, ACX_K_DWCONV, s);
-        int rc, target_waves = 0;
-        if (model_shape && use_col_kernel(c, B, H, W, &target_waves)) {
+        int rc;
+        if (col) {
+            if (!c || !c->d_dw_sink || C != 96 * 56 / (W > 0 ? W : 1)) ACX_FAIL(ACX_ERR_STATE, "dwconv7: the column kernel needs a context and a stage's shape");
             rc = launch_dwconv_col(x, y, w.dw, w.dwb, c->d_dw_sink, B, H, W, target_waves, s);
             ACX_TRY(rc);
             if (stats) ACX_TRY(launch_rowstats(c, reinterpret_cast<const float*>(y), stats, (int64_t)B * H * W, C, s));
@@ -702,7 +711,7 @@ namespace acx {
 // form for bf16 activations -- the forms give the same bits as the uniform launcher's choices (ACX_DW_STREAM tests), and only
 // they know the per-clip row tables.
 int launch_dwconv_varlen(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, const VarGeom& vg, int stage,
-                         hipStream_t s, bool act_bf16) {
+                         hipStream_t s, bool act_bf16, int target_waves) {
     if (!c || !c->d_dw_sink) ACX_FAIL(ACX_ERR_STATE, "dwconv7 (variable length): no context");
     if (C != kDims[stage]) ACX_FAIL(ACX_ERR_SHAPE, "dwconv7 (variable length): stage %d has %d channels, got %d", stage, kDims[stage], C);
     ProfScope ps(c, ACX_K_DWCONV, s);
@@ -712,9 +721,9 @@ int launch_dwconv_varlen(acx_ctx* c, const BlockW& w, int C, const void* x, void
         if (stats) ACX_FAIL(ACX_ERR_STATE, "dwconv7: row statistics are computed from fp32 activations only");
         if (!w.dw_ops || stage > 2) ACX_FAIL(ACX_ERR_STATE, "dwconv7: bf16 activations need the matrix-pipe kernel and its packed weights (stages 0-2)");
         const int per_cu = tuning().dwm_waves.load(std::memory_order_relaxed);
-        return launch_dwconv_mfma_varlen(x, y, w.dw_ops, w.dwb, c->d_dw_sink, vg, stage, (per_cu ? per_cu : 8) * cus, s);
+        return launch_dwconv_mfma_varlen(x, y, w.dw_ops, w.dwb, c->d_dw_sink, vg, stage, target_waves > 0 ? target_waves : (per_cu ? per_cu : 8) * cus, s);
     }
-    ACX_TRY(launch_dwconv_col_varlen(x, y, w.dw, w.dwb, c->d_dw_sink, vg, stage, 4 * cus, s));
+    ACX_TRY(launch_dwconv_col_varlen(x, y, w.dw, w.dwb, c->d_dw_sink, vg, stage, target_waves > 0 ? target_waves : 4 * cus, s));
     if (stats) ACX_TRY(launch_rowstats(c, reinterpret_cast<const float*>(y), stats, (int64_t)vg.rows[stage] * (kStemW >> stage), C, s));
     return ACX_OK;
 }

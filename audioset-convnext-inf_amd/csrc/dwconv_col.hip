@@ -398,9 +398,50 @@ __global__ __launch_bounds__(256, WPS) void dwconv7_col_kernel(const void* __res
 #undef ACX_DWC_FLAGS
 }
 
-// target_waves: how many waves the launch should consist of (one per SIMD of the CUs it may use).  Every wave takes a
-// segment of 7 k output rows of the stacked batch (the rotation has seven phases: the first and the last six steps then sit at
-// fixed phases and are compiled with their reduced kernel-row ranges).
+// ---- the plan of a launch (host arithmetic only; acx_test_dwconv7_plan reports it) ------------------------------------------------
+constexpr int kDwColUnits = 6;                                      // wave columns per image row, every stage (DwColCfg::kUnits)
+constexpr int dw_col_wps(int W) { return W <= 14 ? 2 : 1; }         // waves per SIMD: launch_dwconv_col's table below
+
+// exactness of v / (H + 3) by multiply-high needs (stacked rows + 9 (H + 3) + slack) * (H + 3) < 2^32
+bool dw_col_too_tall(int B, int H) {
+    const long long Vt = (long long)B * (H + 3) - 3;
+    return (Vt + 16ll * (H + 3) + 64) * (H + 3) >= 0xffffffffll;
+}
+
+// target_waves: how many waves the launch should consist of (one per SIMD of the CUs it may use).  Every wave takes a segment
+// of n_out = ceil(rows / segments) output rows of the stacked batch; the kernel instantiation for n_out's remainder modulo the
+// rotation's seven phases (S0) runs it.  whole_groups (a variable-length batch): segments of a multiple of seven rows, S0 = 0.
+DwColPlan dw_col_segments(long long Vt, int wps, int target_waves, bool whole_groups) {
+    long long segs = (long long)target_waves * wps / kDwColUnits;
+    if (segs < 1) segs = 1;
+    long long n_out = (Vt + segs - 1) / segs;                          // output rows per segment
+    const long long nmin = wps == 2 ? 7 : kDwColMinRows;
+    if (n_out < nmin) n_out = nmin;
+    if (whole_groups) n_out = (n_out + 6) / 7 * 7;
+    DwColPlan p;
+    p.n_out = (int)n_out;
+    p.s0 = (int)((7 - n_out % 7) % 7);
+    p.k7 = (int)((n_out + p.s0) / 7);
+    p.n_seg = (int)((Vt + n_out - 1) / n_out);
+    p.n_items = p.n_seg * kDwColUnits;
+    return p;
+}
+
+int dwconv_col_plan(int W, int B, int H, int target_waves, DwColPlan* plan) {
+    if (W != 56 && W != 28 && W != 14 && W != 7) ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: unsupported width %d (expected 56/28/14/7)", W);
+    if (dw_col_too_tall(B, H)) ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: batch too tall for one launch (%d clips of %d rows)", B, H);
+    *plan = dw_col_segments((long long)B * (H + 3) - 3, dw_col_wps(W), target_waves, false);
+    return ACX_OK;
+}
+
+int dwconv_col_plan_varlen(int stage, int vrows, int target_waves, DwColPlan* plan) {
+    if (stage < 0 || stage > 3) ACX_FAIL(ACX_ERR_ARG, "dwconv7: no stage %d", stage);
+    *plan = dw_col_segments((long long)vrows - 3, dw_col_wps(kStemW >> stage), target_waves, true);
+    return ACX_OK;
+}
+
+// Every wave takes a virtual segment of 7 k7 output rows of the stacked batch (the rotation has seven phases: the first and the
+// last six steps then sit at fixed phases and are compiled with their reduced kernel-row ranges).
 template <int W, int R, int WPS, int S0>
 static int launch_dw_col_s0(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H, int k7, int n_items, hipStream_t s) {
     using Cfg = DwColCfg<W, R>;
@@ -413,27 +454,17 @@ static int launch_dw_col_s0(const void* x, void* y, const float* wt, const float
     return ACX_OK;
 }
 
-// target_waves: how many waves the launch should consist of (one per SIMD of the CUs it may use).  Every wave takes a segment
-// of n_out = ceil(rows / segments) output rows of the stacked batch; the kernel instantiation for n_out's remainder modulo the
-// rotation's seven phases (S0) runs it.
 // variable-length batch: segments of a multiple of seven rows (the S0 = 0 instantiation only)
 template <int W, int R, int WPS>
 static int launch_dw_col_var(const void* x, void* y, const float* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
                              int target_waves, hipStream_t s) {
     using Cfg = DwColCfg<W, R>;
-    const long long Vt = (long long)vg.vrows[stage] - 3;
-    long long segs = (long long)target_waves * WPS / Cfg::kUnits;
-    if (segs < 1) segs = 1;
-    long long n_out = (Vt + segs - 1) / segs;
-    const long long nmin = WPS == 2 ? 7 : kDwColMinRows;
-    if (n_out < nmin) n_out = nmin;
-    n_out = (n_out + 6) / 7 * 7;
-    const long long n_seg = (Vt + n_out - 1) / n_out;
-    const int n_items = (int)(n_seg * Cfg::kUnits);
+    static_assert(Cfg::kUnits == kDwColUnits && WPS == dw_col_wps(W), "dw_col_segments plans for this kernel");
+    const DwColPlan p = dw_col_segments((long long)vg.vrows[stage] - 3, WPS, target_waves, true);
     static DeviceOnce once;
     ACX_TRY(set_max_dynamic_lds(once, &dwconv7_col_kernel<W, R, WPS, 0, true>, Cfg::kLdsBytes));
-    launch_kernel(&dwconv7_col_kernel<W, R, WPS, 0, true>, dim3((unsigned)((n_items + 3) / 4)), dim3(256), Cfg::kLdsBytes, s,
-        x, y, wt, bias, sink, vg.B, 0, (int)(n_out / 7), n_items, 0u, vg.vbits[stage], vg.vwords[stage], vg.vclip[stage],
+    launch_kernel(&dwconv7_col_kernel<W, R, WPS, 0, true>, dim3((unsigned)((p.n_items + 3) / 4)), dim3(256), Cfg::kLdsBytes, s,
+        x, y, wt, bias, sink, vg.B, 0, p.k7, p.n_items, 0u, vg.vbits[stage], vg.vwords[stage], vg.vclip[stage],
         vg.roff[stage], vg.vrows[stage]);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
@@ -443,20 +474,12 @@ template <int W, int R, int WPS>
 static int launch_dw_col_cfg(const void* x, void* y, const float* wt, const float* bias, void* sink, int B, int H,
                              int target_waves, hipStream_t s) {
     using Cfg = DwColCfg<W, R>;
-    const long long Vt = (long long)B * (H + 3) - 3;
-    // exactness of v / (H + 3) by multiply-high needs (stacked rows + 9 (H + 3) + slack) * (H + 3) < 2^32
-    if ((Vt + 16ll * (H + 3) + 64) * (H + 3) >= 0xffffffffll)
+    static_assert(Cfg::kUnits == kDwColUnits && WPS == dw_col_wps(W), "dw_col_segments plans for this kernel");
+    if (dw_col_too_tall(B, H))
         ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: batch too tall for one launch (%d clips of %d rows)", B, H);
-    long long segs = (long long)target_waves * WPS / Cfg::kUnits;
-    if (segs < 1) segs = 1;
-    long long n_out = (Vt + segs - 1) / segs;                          // output rows per segment
-    const long long nmin = WPS == 2 ? 7 : kDwColMinRows;
-    if (n_out < nmin) n_out = nmin;
-    const int s0 = (int)((7 - n_out % 7) % 7);
-    const int k7 = (int)((n_out + s0) / 7);
-    const long long n_seg = (Vt + n_out - 1) / n_out;
-    const int n_items = (int)(n_seg * Cfg::kUnits);
-    switch (s0) {
+    const DwColPlan p = dw_col_segments((long long)B * (H + 3) - 3, WPS, target_waves, false);
+    const int k7 = p.k7, n_items = p.n_items;
+    switch (p.s0) {
         case 0: return launch_dw_col_s0<W, R, WPS, 0>(x, y, wt, bias, sink, B, H, k7, n_items, s);
         case 1: return launch_dw_col_s0<W, R, WPS, 1>(x, y, wt, bias, sink, B, H, k7, n_items, s);
         case 2: return launch_dw_col_s0<W, R, WPS, 2>(x, y, wt, bias, sink, B, H, k7, n_items, s);

@@ -1331,6 +1331,30 @@ ACX_API int acx_test_fail_sub(acx_ctx* ctx, int sub);
 ACX_API int acx_test_stage_tail(acx_ctx* ctx, int stage, float* x, float* out, int B, int H, int W, void* scratch,
                         size_t scratch_bytes, void* stream);
 ACX_API int acx_test_stage_tail_scratch_bytes(int stage, int B, int H, int W, size_t* out_bytes);
+/* Test support: the depthwise kernels per FORM.  The column-streaming kernel (dwconv_col.hip) cuts the stacked batch into segments
+ * of n_out output rows and runs the instantiation for s0 = (7 - n_out % 7) % 7 on groups of seven rows (k7 of them), n_seg
+ * segments x 6 wave columns = n_items waves; which one a launch gets depends on the batch, the clip length, the CU count and the
+ * sub-batches in flight.  acx_test_dwconv7_plan reports what launch_dwconv_col would launch for B clips of H rows in `stage` at
+ * `target_waves` (host arithmetic only: no context, no device; ACX_ERR_SHAPE where the kernel's multiply-high division refuses
+ * the batch); acx_test_dwconv7_varlen_plan the same for the packed clips of `lengths` (samples), where n_out is a multiple of 7.
+ * Both call the function the launchers call.  No reference counterpart. */
+typedef struct acx_dwconv7_plan_t {
+    int n_out, s0, k7, n_seg, n_items;
+} acx_dwconv7_plan_t;
+ACX_API int acx_test_dwconv7_plan(int stage, int B, int H, int target_waves, acx_dwconv7_plan_t* plan);
+ACX_API int acx_test_dwconv7_varlen_plan(int stage, const int64_t* lengths, int n, int target_waves, acx_dwconv7_plan_t* plan);
+/* acx_dwconv7 with the form chosen by the caller: form = 0 the ring / tile kernel of that width, form = 1 the column-streaming
+ * kernel with `target_waves` (1 .. 4 x CUs) in place of 4 x CUs / sub-batches in flight (ignored by form 0).  stats as in
+ * acx_dwconv7.  Everything is checked before the first launch. */
+ACX_API int acx_test_dwconv7_form(acx_ctx* ctx, int stage, int block, const float* x, float* y, float* stats, int B, int H, int W,
+                          int form, int target_waves, void* stream);
+/* The depthwise conv of ONE stage of a packed batch as acx_forward_varlen queues it: builds the tables of `lengths` (n clips, in
+ * samples, host) in `scratch` (>= acx_test_dwconv7_varlen_scratch_bytes, 256-byte aligned), then runs the variable-length launcher
+ * at `target_waves` (1 .. 8 x CUs).  x, y: the clips' rows of that stage back to back, NHWC -- fp32, or bf16 in stages 0-2 under
+ * ACX_PREC_BF16_ACT (the matrix-pipe kernel). */
+ACX_API int acx_test_dwconv7_varlen(acx_ctx* ctx, int stage, int block, const void* x, void* y, const int64_t* lengths, int n,
+                            int target_waves, void* scratch, size_t scratch_bytes, void* stream);
+ACX_API int acx_test_dwconv7_varlen_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes);
 
 /* ---- measurement: per-kernel-class device time, HIP events on the launch stream ------------ */
 ACX_API int acx_profile_enable(acx_ctx* ctx, int on);
