@@ -267,6 +267,11 @@ SIGNATURES = {
     "acx_kmeans_min_distance": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
     "acx_kmeans_sample": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_kmeans_seed": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
+    "acx_cluster_scores_workspace_bytes": (_c_int, [_c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_silhouette": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _c_sz, _vp]),
+    "acx_cluster_dispersion": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_contingency": (_c_int, [_vp, _c_int, _vp, _c_int, _c_i64, _vp, _vp, _vp]),
     "acx_moments_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_moments": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
     "acx_gram_f64": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp]),
@@ -835,6 +840,35 @@ def kmeans_seed(x, ld_x, x_inv_norm, n, dim, metric, clusters, u, picked, center
     """acx_kmeans_seed on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
     check(lib().acx_kmeans_seed(x, int(ld_x), x_inv_norm, int(n), int(dim), int(metric), int(clusters), u, picked, centers,
                                 int(ld_c), status, ws[0], int(ws[1]), stream))
+
+
+# bits of the status words of acx_silhouette / acx_cluster_dispersion / acx_contingency
+CLUSTER_NONFINITE, CLUSTER_DEGENERATE, CLUSTER_BAD_LABEL, CLUSTER_BAD_ROW = 1, 2, 4, 8
+CLUSTER_MAX_SPLITS = 16                        # ACX_CLUSTER_MAX_SPLITS
+CONTINGENCY_MAX_CELLS = 1 << 24                # ACX_CONTINGENCY_MAX_CELLS
+
+
+def cluster_scores_workspace_bytes(n, dim, clusters):
+    """Workspace of acx_silhouette / acx_cluster_dispersion (host only)."""
+    return _query(lib().acx_cluster_scores_workspace_bytes, _c_sz, int(n), int(dim), int(clusters))
+
+
+def silhouette(x, ld_x, x_inv_norm, n, dim, metric, labels, clusters, rows, n_rows, a, b, nearest, s, cluster_mean, mean, status, ws,
+               stream):
+    """acx_silhouette on raw device pointers (ctypes.c_void_p); rows and cluster_mean may be None; ws: (pointer, bytes)."""
+    check(lib().acx_silhouette(x, int(ld_x), x_inv_norm, int(n), int(dim), int(metric), labels, int(clusters), rows, int(n_rows), a, b,
+                               nearest, s, cluster_mean, mean, status, ws[0], int(ws[1]), stream))
+
+
+def cluster_dispersion(x, ld_x, n, dim, labels, clusters, counts, means, within_sq, within_dist, grand_mean, status, ws, stream):
+    """acx_cluster_dispersion on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_cluster_dispersion(x, int(ld_x), int(n), int(dim), labels, int(clusters), counts, means, within_sq, within_dist,
+                                       grand_mean, status, ws[0], int(ws[1]), stream))
+
+
+def contingency(a, ka, b, kb, n, table, status, stream):
+    """acx_contingency on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_contingency(a, int(ka), b, int(kb), int(n), table, status, stream))
 
 
 MAX_EVENT_MEDIAN = 101                        # ACX_MAX_EVENT_MEDIAN

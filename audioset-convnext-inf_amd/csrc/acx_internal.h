@@ -446,6 +446,15 @@ inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 constexpr long long kF32MaxRows = 1LL << 30;
 // x non-null and 16-byte aligned, dim a multiple of 4 in 4 .. ACX_KNN_MAX_DIM, ld a multiple of 4 and at least dim (knn.hip)
 int check_f32_rows(const char* who, const char* name, const float* x, int64_t ld, int dim);
+// The k-means partition for the cluster scores (kmeans.hip; cluster_scores.hip): counts[k] = rows of label k, start[k] = rows of
+// the labels below k, perm = the row indices sorted stably by label (ascending row inside a cluster); a label outside [0, K) is
+// in no cluster and sets ACX_KMEANS_BAD_LABEL in *status.  hist: km_hist_bytes(n, K) bytes of scratch.
+size_t km_hist_bytes(long long n, int K);
+void km_launch_partition(const int* labels, long long n, int K, int* hist, int* counts, int* start, int* perm, int* status,
+                         hipStream_t s);
+// sums (K, dim) float64: each cluster's rows summed as acx_kmeans_update sums them (unweighted)
+void km_launch_sums(const float* x, long long ld_x, int dim, int K, const int* perm, const int* start, const int* counts, double* sums,
+                    hipStream_t s);
 
 // ---- host code shared by api.hip, weights.hip, forward.hip and stream.hip ------------------------------------------------
 // bf16 activations in HBM for the stages that keep them (ACX_PREC_BF16_ACT, stages 0-2)

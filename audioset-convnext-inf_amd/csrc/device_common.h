@@ -72,6 +72,22 @@ __device__ __forceinline__ T wave_sum(T v) {
 // The partial results of a workgroup's four waves, added in wave order.
 __device__ __forceinline__ float sum4(float w0, float w1, float w2, float w3) { return ((w0 + w1) + w2) + w3; }
 
+// v summed over a workgroup of N threads in a fixed tree: red[t] += red[t + o] for o = N / 2, N / 4, .. 1 (the order depends on N
+// alone); every thread gets the result (kmeans.hip, cluster_scores.hip)
+template <class T, int N>
+__device__ __forceinline__ T km_block_sum(T v, T* red) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int o = N / 2; o >= 1; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // ---- finite or not ----------------------------------------------------------------------------------------------------------
 // NaN or an infinity (the largest finite float is the only bound: no fast-math assumption can fold the comparison away)
 constexpr float kF32Max = 3.4028234664e38f;

@@ -43,21 +43,6 @@ __device__ __forceinline__ bool km_skip(const acx_kmeans_state* st, int gate) {
     return false;
 }
 
-// v summed over the workgroup in a fixed tree (the order depends on blockDim alone); every thread gets the result
-template <class T, int N>
-__device__ __forceinline__ T km_block_sum(T v, T* red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int o = N / 2; o >= 1; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // ---- assignment ------------------------------------------------------------------------------------------------------------
 struct KmAssignP {
     const float* x; long long ld_x; long long n;
@@ -611,6 +596,26 @@ static void km_launch_update(const KmData& v, const int* labels, int* counts, ch
                   (const int*)perm, (const int*)start, (const int*)counts, v.dim, sums, st, gate);
     launch_kernel(&kmeans_finalize_kernel, dim3(v.K), dim3(256), 0, s, (const double*)sums, (const int*)counts, v.dim, v.cosine, v.c,
                   v.ld_c, shiftk, st, gate);
+}
+
+// The partition and the per-cluster sums for cluster_scores.hip (prototypes in acx_internal.h): the kernels above, ungated.
+size_t km_hist_bytes(long long n, int K) { return align_up((size_t)km_max_blocks(n) * K * sizeof(int)); }
+
+void km_launch_partition(const int* labels, long long n, int K, int* hist, int* counts, int* start, int* perm, int* status,
+                         hipStream_t s) {
+    const KmPart pt = km_part(n);
+    launch_kernel(&kmeans_hist_kernel, dim3(pt.nb), dim3(256), 0, s, labels, n, K, pt.rpb, hist, status, 1, (const acx_kmeans_state*)nullptr,
+                  (int)KM_ALWAYS);
+    launch_kernel(&kmeans_scan_kernel, dim3(1), dim3(1024), 0, s, hist, pt.nb, K, counts, start, (const acx_kmeans_state*)nullptr,
+                  (int)KM_ALWAYS);
+    launch_kernel(&kmeans_scatter_kernel, dim3(pt.nb), dim3(64), 0, s, labels, n, K, pt.rpb, (const int*)hist, (const int*)start, perm,
+                  km_bits(K), (const acx_kmeans_state*)nullptr, (int)KM_ALWAYS);
+}
+
+void km_launch_sums(const float* x, long long ld_x, int dim, int K, const int* perm, const int* start, const int* counts, double* sums,
+                    hipStream_t s) {
+    launch_kernel(&kmeans_sum_kernel, dim3(K, (dim + 255) / 256), dim3(256), 0, s, x, ld_x, (const float*)nullptr, perm, start, counts,
+                  dim, sums, (const acx_kmeans_state*)nullptr, (int)KM_ALWAYS);
 }
 
 static void km_launch_mindist(const KmData& v, const float* c, const int* pick, int first, float* d, unsigned* dmax, int* status,

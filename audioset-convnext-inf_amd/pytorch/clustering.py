@@ -6,6 +6,7 @@ embeddings that have no labels -- what `sklearn.cluster.KMeans(...).fit(emb)` do
     km.centers, km.labels, km.counts          # (K, dim) fp32, (n,) int64, (K,) int64 device tensors
     km.inertia, km.n_iter, km.converged       # 0-d device tensors
     km.predict(x), km.distances(x)            # labels / winner distances of new rows
+    km.silhouette(emb, sample=None)           # how good the clustering is (pytorch/cluster_scores.py)
     km.check()                                # the one call that synchronises
     km.save("km.npz"); KMeans.load("km.npz")
 
@@ -245,6 +246,13 @@ class KMeans:
         if self.metric == "cosine":
             return 1.0 + scores * rx
         return ((x * x).sum(dim=1) + scores).clamp_min(0.0)
+
+    def silhouette(self, x, sample=None, seed=0):
+        """The silhouette of the rows x (n, dim) this clustering was fitted on, under its labels and metric
+        (pytorch/cluster_scores.py: silhouette; sample, seed as there) -> cluster_scores.Silhouette."""
+        from . import cluster_scores
+        return cluster_scores.silhouette(x, self.labels, self.metric, clusters=self.centers.shape[0], sample=sample, seed=seed,
+                                         device=self.device)
 
     def check(self):
         """Synchronise: ValueError if the input held NaN or infinite values; RuntimeWarning (warnings.warn) for degenerate

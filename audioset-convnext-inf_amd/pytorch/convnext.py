@@ -951,6 +951,13 @@ class ConvNeXt(nn.Module):
             emb = torch.stack(extract(self, list(data), what="scene", pack=True, sample_rate=sample_rate)).to(dev)
         return kmeans(emb, clusters, device=dev, **kw)
 
+    def select_clusters(self, data, ks, sample_rate=None, **kw):
+        """Choose the number of clusters (pytorch/cluster_scores.py: select_clusters) over scene embeddings on the model's device:
+        `data` as cluster() takes it, one k-means fit per k of `ks`, each scored on the device; kw: criterion, metric, sample,
+        seed and the k-means arguments.  -> cluster_scores.ClusterSelection (scores, best_k, best, fits)."""
+        from .cluster_scores import select_clusters
+        return select_clusters(self._scene_rows(data, sample_rate), ks, device=self.head_audioset.weight.device, **kw)
+
     def _scene_rows(self, data, sample_rate):
         """`data` as build_index takes it -> (n, 768) scene embeddings: a 2-D tensor of embeddings as it is, a list of waveforms
         at `sample_rate` extracted first (extract(..., what="scene", pack=True))."""

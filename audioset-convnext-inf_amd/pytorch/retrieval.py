@@ -481,6 +481,23 @@ class EmbeddingIndex:
         return clustering._fit_rows(self._buf[:self._n], self.dim, self.inverse_norms if metric == "cosine" else None, clusters,
                                     metric, **kw)
 
+    def cluster_scores(self, km, sample=None, seed=0):
+        """How good a clustering of the stored rows is (pytorch/cluster_scores.py) with the index's own metric, as cluster()
+        takes it, reusing the index's inverse norms: km is a clustering.KMeans over these rows (or a (n,) tensor of labels in
+        [0, max + 1)).  -> cluster_scores.ClusterScores(silhouette, dispersion); sample, seed: as silhouette() takes them."""
+        from . import cluster_scores as cs
+        if self._n == 0:
+            raise ValueError("the index is empty")
+        metric = "cosine" if self.metric == "cosine" else "euclidean"
+        labels = getattr(km, "labels", km)
+        cs._check_sample(sample, self._n)
+        lab = cs._labels32(labels, self._n, self.device)
+        K = cs._clusters_of(lab, km.centers.shape[0] if hasattr(km, "centers") else None)
+        x = self._buf[:self._n]
+        sil = cs._silhouette_rows(x, self.inverse_norms if metric == "cosine" else None, lab, K, metric,
+                                  cs._sample_rows(self._n, sample, seed, self.device))
+        return cs.ClusterScores(sil, cs._dispersion_rows(x, self.dim, lab, K))
+
     def moments(self, ddof=1):
         """Mean and covariance of the stored rows in float64 (pytorch/statistics.py: moments) -> statistics.Moments."""
         from . import statistics

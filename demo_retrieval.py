@@ -6,6 +6,7 @@ ConvNeXt.search).
     python demo_retrieval.py --ckpt checkpoints/model.safetensors --data sounds/ --query dog.wav      # sounds/<class>/*.wav
     python demo_retrieval.py --synthetic                       # seeded weights and clips, no files needed
     python demo_retrieval.py --synthetic --clusters 8          # also k-means over the corpus: sizes, the clip nearest each centre
+    python demo_retrieval.py --synthetic --select-clusters 4,8,16     # choose k by the mean silhouette (--cluster-criterion ...)
     python demo_retrieval.py --synthetic --pca 16 [--whiten]   # also search a PCA-reduced copy of the index, against the full one
     python demo_retrieval.py --synthetic --int8 [--oversample 4] [--no-rerank]     # int8 index: coarse search, exact fp32 rerank
 
@@ -69,6 +70,9 @@ def main():
     ap.add_argument("--oversample", type=int, default=4, help="--int8: coarse candidates per neighbour asked for")
     ap.add_argument("--no-rerank", action="store_true", help="--int8: keep codes only and return the coarse scores")
     ap.add_argument("--clusters", type=int, default=0, help="also cluster the corpus into this many clusters (k-means on the GPU)")
+    ap.add_argument("--select-clusters", default="", help="choose the number of clusters among these, e.g. 10,20,50: one k-means fit "
+                    "per k, each scored on the GPU")
+    ap.add_argument("--cluster-criterion", default="silhouette", choices=("silhouette", "calinski_harabasz", "davies_bouldin"))
     ap.add_argument("--pca", type=int, default=0, help="also reduce the index to this many principal components (PCA on the GPU)")
     ap.add_argument("--whiten", action="store_true", help="--pca: whiten the reduced rows")
     a = ap.parse_args()
@@ -134,12 +138,24 @@ def main():
         # no labels needed: k-means over the stored rows with the index's metric, and the stored clip nearest to each centre
         km = index.cluster(a.clusters, seed=a.seed)
         _, nearest = index.search(km.centers, 1)
+        sil = (getattr(index, "exact", None) or index).cluster_scores(km).silhouette
         km.check()
         index.check()
-        print("k-means, %d clusters, %d iterations, inertia %.4g; sizes %s" % (a.clusters, int(km.n_iter), float(km.inertia),
-                                                                           km.counts.tolist()))
+        print("k-means, %d clusters, %d iterations, inertia %.4g, mean silhouette %.4f; sizes %s" % (
+            a.clusters, int(km.n_iter), float(km.inertia), float(sil), km.counts.tolist()))
         for c, j in enumerate(nearest[:, 0].tolist()):
             print("    cluster %d (%d clips): nearest %s (%s)" % (c, int(km.counts[c]), paths[j], names[int(label[j])]))
+
+    if a.select_clusters and a.int8 and a.no_rerank:
+        print("--select-clusters needs the fp32 rows: skipped with --no-rerank")
+    elif a.select_clusters:
+        # which k: one fit per candidate, scored where the rows are; the silhouette decides unless told otherwise
+        from audioset_convnext_inf_amd.pytorch.cluster_scores import select_clusters
+        rows = getattr(index, "exact", None) or index
+        sel = select_clusters(rows.embeddings, [int(k) for k in a.select_clusters.split(",")], criterion=a.cluster_criterion,
+                              metric="cosine" if a.metric == "cosine" else "euclidean", seed=a.seed)
+        print("%s per k: %s -> k = %d" % (a.cluster_criterion, ", ".join("%d: %.4f" % kv for kv in zip(sel.ks, sel.scores.tolist())),
+                                          sel.best_k))
 
     if a.pca and a.int8:
         print("--pca reduces the fp32 index: skipped with --int8")

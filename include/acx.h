@@ -1190,6 +1190,68 @@ ACX_API int acx_kmeans_seed(const float* x, int64_t ld_x, const float* x_inv_nor
                             const double* u, int32_t* picked, float* centers, int64_t ld_c, int32_t* status, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- cluster validation: silhouette, within-cluster dispersion, contingency tables ---------------------------------------------
+ * What says whether a clustering is good and which k to take (no reference counterpart; scikit-learn 1.7.2's silhouette_samples,
+ * calinski_harabasz_score, davies_bouldin_score and contingency-based scores are the yardsticks).  Stateless; every buffer is the
+ * caller's, on the device.  x (n, dim) fp32 with row stride ld_x and x_inv_norm under the rules of acx_kmeans_assign; labels (n)
+ * int32; 1 <= clusters <= ACX_KMEANS_MAX_CLUSTERS (clusters may exceed n), n <= 2^30; metric an acx_kmeans_metric.
+ * THE PARTITION: the row indices sorted stably by label (acx_kmeans_update's): cluster c owns the partition positions
+ * start_c .. start_c + count_c - 1, ascending row index inside it.  A label outside [0, clusters) puts its row in NO cluster and
+ * sets ACX_CLUSTER_BAD_LABEL.  Every float64 sum below runs over partition positions in a stated order: no float atomics, the same
+ * inputs give the same bits on every call.
+ *   acx_silhouette: PAIR DISTANCE in fp32.  EUCLIDEAN: d(i, j) = sqrt(max(fma(-2, dot_ij, xx_i + xx_j), 0)), the square root
+ *     correctly rounded, dot_ij the dot product of acx_knn_search / acx_kmeans_assign (one fixed order per pair) and xx_i = sum
+ *     x_i^2 in one fixed order per row.  COSINE: d = 1 - (dot_ij * rx_i) * rx_j with rx = x_inv_norm (rx = 0: d = 1).  The pair
+ *     (i, i) contributes exactly 0: it is left out by position, not by value.
+ *     For the queried rows -- rows (n_rows) int32 row indices, n_rows <= n, in any order, repeats allowed; NULL: every row in
+ *     order, n_rows ignored -- with L the row's label:  S(i, c) = sum over the positions of cluster c of (double)d(i, j);
+ *     a = S(i, L) / (count_L - 1) (0 when count_L == 1);  b = min over the non-empty c != L of S(i, c) / count_c, the lowest c
+ *     winning a tie, that c in nearest;  s = (b - a) / max(a, b), and s = 0 when count_L == 1 or max(a, b) == 0.  Empty clusters
+ *     are skipped.  THE ORDER of S(i, c): the positions 0 .. n - 1 are cut into ranges of `len` positions, len = 64 ceil(ceil(n / 64)
+ *     / ns) with ns = min(ACX_CLUSTER_MAX_SPLITS, ceil(n / 64), max(1, ceil(512 / ceil(n_rows / 256)))); inside a range the
+ *     distances of cluster c are added one by one in ascending position into a float64 that starts at 0, and S(i, c) is the
+ *     ranges' partial sums added in ascending range, starting from the first.  A function of (n, labels, n_rows) alone.
+ *     *mean = the mean of s over the queried rows that have a cluster; cluster_mean[c] (NULL: not wanted) = the mean over the
+ *     queried rows of label c, NaN when there are none.  Their order: with the queried rows numbered q = 0 .. n_rows - 1, partial t
+ *     = rows q = t, t + 256, ... in ascending order (t = 0 .. 255), then partial[t] += partial[t + o] for o = 128, 64, .. 1, then
+ *     one division by the count.
+ *     *status (cleared first): ACX_CLUSTER_NONFINITE -- a NaN or an infinity (or an overflow) in a queried row or in a row of a
+ *     cluster: the outputs of every row it reaches are NaN, nearest -1.  ACX_CLUSTER_BAD_LABEL -- some label is outside
+ *     [0, clusters): a queried row with such a label gets NaN / -1 and stays out of *mean.  ACX_CLUSTER_BAD_ROW -- an entry of
+ *     rows outside [0, n): the same.  ACX_CLUSTER_DEGENERATE -- fewer than two non-empty clusters: every s = 0, b = NaN,
+ *     nearest = -1.  The (n, n) distances are never written; the workspace holds (clusters + ACX_CLUSTER_MAX_SPLITS) float64 per
+ *     queried row.  a, b, s float64 (n_rows), nearest int32 (n_rows).
+ *   acx_cluster_dispersion: what Calinski-Harabasz and Davies-Bouldin are made of.  counts (clusters) int64; means (clusters, dim)
+ *     float64 = the cluster's float64 sums as acx_kmeans_update takes them (unweighted), divided by the count (an empty cluster: 0);
+ *     per row v = sum_j ((double)x_j - mean_j)^2, every product and sum rounded: lane l = 0 .. 63 takes columns 4 l .. 4 l + 3,
+ *     then + 256, ... in ascending order, the lanes join by the xor butterfly 32, 16, .. 1.  within_sq[c] = sum v, within_dist[c] =
+ *     sum sqrt(v) over the cluster's rows: position j of the cluster goes to partial j mod 4, each partial in ascending j, joined
+ *     as ((p0 + p1) + p2) + p3.  grand_mean (dim) = the clusters' sums added in ascending c, divided by the rows that have a
+ *     cluster.  ACX_CLUSTER_NONFINITE, ACX_CLUSTER_BAD_LABEL as above; ACX_CLUSTER_DEGENERATE for fewer than two non-empty clusters
+ *     (the outputs are written all the same).
+ *   acx_contingency: table (ka, kb) int64, cleared on `stream`, table[a_i][b_i] += 1 by integer atomics.  A pair with either label
+ *     out of range is counted nowhere and sets ACX_CLUSTER_BAD_LABEL.  ka * kb > ACX_CONTINGENCY_MAX_CELLS is ACX_ERR_UNSUPPORTED.
+ *   acx_cluster_scores_workspace_bytes: the workspace of acx_silhouette and acx_cluster_dispersion; non-decreasing in each
+ *     argument (host only).
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable.  ARGUMENT errors
+ * return a negative status before any launch, as for acx_kmeans_assign; n_rows outside 1 .. n is ACX_ERR_ARG. */
+#define ACX_CLUSTER_NONFINITE 1
+#define ACX_CLUSTER_DEGENERATE 2
+#define ACX_CLUSTER_BAD_LABEL 4
+#define ACX_CLUSTER_BAD_ROW 8
+#define ACX_CLUSTER_MAX_SPLITS 16
+#define ACX_CONTINGENCY_MAX_CELLS (1 << 24)
+ACX_API int acx_cluster_scores_workspace_bytes(int64_t n, int dim, int clusters, size_t* out_bytes);
+ACX_API int acx_silhouette(const float* x, int64_t ld_x, const float* x_inv_norm, int64_t n, int dim, int metric,
+                           const int32_t* labels, int clusters, const int32_t* rows, int64_t n_rows, double* a, double* b,
+                           int32_t* nearest, double* s, double* cluster_mean, double* mean, int32_t* status, void* ws,
+                           size_t ws_bytes, void* stream);
+ACX_API int acx_cluster_dispersion(const float* x, int64_t ld_x, int64_t n, int dim, const int32_t* labels, int clusters,
+                                   int64_t* counts, double* means, double* within_sq, double* within_dist, double* grand_mean,
+                                   int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_contingency(const int32_t* a, int ka, const int32_t* b, int kb, int64_t n, int64_t* table, int32_t* status,
+                            void* stream);
+
 /* ---- embedding statistics: float64 moments, Gram products, a symmetric eigensolver, PCA projection ------------------------------
  * Second-order statistics of a set of embeddings (no reference counterpart): what covariance, PCA / whitening, Mahalanobis
  * scores and the Frechet distance rest on.  Stateless; every buffer is the caller's, on the device.  1 <= dim <=
