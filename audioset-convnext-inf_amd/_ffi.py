@@ -293,6 +293,8 @@ SIGNATURES = {
     "acx_test_dwconv7_form": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
     "acx_test_dwconv7_varlen": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _c_sz, _vp]),
     "acx_test_dwconv7_varlen_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_test_stem": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _c_sz, _vp]),
+    "acx_test_stem_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_i64)]),
     "acx_profile_enable": (_c_int, [_vp, _c_int]),
     "acx_profile_read": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64)]),
 }

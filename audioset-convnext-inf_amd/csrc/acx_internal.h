@@ -288,7 +288,9 @@ int launch_logmel(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* 
                   float* dense_frames = nullptr, float* dense_spec = nullptr, const long long* wstart = nullptr);
 // act_bf16: the activation tensors named void* are bf16 (ACX_PREC_BF16_ACT, stages 0-2) instead of fp32; launch_dwconv then
 // takes the matrix-pipe kernel (dwconv_mfma.hip), which reads BlockW::dw_ops
-int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hipStream_t s, bool act_bf16 = false);
+// max_blocks: 0 = the launcher's own grid; 1 .. kStemMaxBlocks caps it (acx_test_stem: workgroups then walk more row pairs)
+constexpr int kStemMaxBlocks = 2048;
+int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hipStream_t s, bool act_bf16 = false, int max_blocks = 0);
 int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, int B, int H,
                   int W, hipStream_t s, bool act_bf16 = false);
 // column-streaming form (dwconv_col.hip): same bits as the kernels of dwconv.hip; `sink` (kDwSinkBytes, device) takes the
@@ -398,7 +400,7 @@ int launch_pcm16_to_f32(const short* in, float* out, long long n, hipStream_t s)
 // variable-length forms (vg: tables of acx_forward_varlen; same arithmetic per element as the uniform kernels)
 int launch_logmel_varlen(acx_ctx* c, const float* wav, const VarGeom& vg, float* out, hipStream_t s, float* dense_frames,
                          float* dense_spec);
-int launch_stem_varlen(acx_ctx* c, const float* in, const VarGeom& vg, void* out, hipStream_t s, bool act_bf16);
+int launch_stem_varlen(acx_ctx* c, const float* in, const VarGeom& vg, void* out, hipStream_t s, bool act_bf16, int max_blocks = 0);
 int launch_dwconv_col_varlen(const void* x, void* y, const float* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
                              int target_waves, hipStream_t s);
 int launch_dwconv_mfma_varlen(const void* x, void* y, const void* dw_ops, const float* bias, void* sink, const VarGeom& vg,

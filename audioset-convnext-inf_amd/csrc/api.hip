@@ -384,6 +384,35 @@ int acx_test_dwconv7_varlen(acx_ctx* c, int stage, int block, const void* x, voi
     return launch_dwconv_varlen(c, c->blocks[stage][block], kDims[stage], x, y, nullptr, vg, stage, (hipStream_t)stream, ab, target_waves);
 }
 
+int acx_test_stem_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes, int64_t* out_rows) {
+    if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "acx_test_stem_scratch_bytes: bad argument");
+    VarGeom vg;
+    ACX_TRY(varlen_geometry(lengths, n, nullptr, &vg, out_bytes));
+    if (out_rows) *out_rows = vg.rows[0];
+    return ACX_OK;
+}
+
+int acx_test_stem(acx_ctx* c, const float* feat, void* out, int B, int T, const int64_t* lengths, int n, int max_blocks, void* scratch,
+                  size_t scratch_bytes, void* stream) {
+    ACX_TRY(need_ready(c));
+    if (!feat || !out) ACX_FAIL(ACX_ERR_ARG, "acx_test_stem: null pointer");
+    if (max_blocks < 0 || max_blocks > kStemMaxBlocks)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_stem: max_blocks %d (expected 0: the launcher's grid, or 1 .. %d)", max_blocks, kStemMaxBlocks);
+    const bool ab = act_bf16(c, 0);
+    if (!lengths && n == 0) {
+        if (B < 1 || T < 1) ACX_FAIL(ACX_ERR_ARG, "acx_test_stem: %d clips of %d frames", B, T);
+        return launch_stem(c, feat, B, T, stage_h0(T), out, (hipStream_t)stream, ab, max_blocks);
+    }
+    if (!scratch) ACX_FAIL(ACX_ERR_ARG, "acx_test_stem: null pointer");
+    VarGeom vg;
+    size_t need = 0;
+    ACX_TRY(varlen_geometry(lengths, n, (char*)scratch, &vg, &need));
+    if (scratch_bytes < need || ((uintptr_t)scratch & 255))
+        ACX_FAIL(ACX_ERR_WORKSPACE, "acx_test_stem: scratch too small (%zu < %zu) or misaligned", scratch_bytes, need);
+    ACX_TRY(launch_varlen_tables(lengths, vg, (hipStream_t)stream));
+    return launch_stem_varlen(c, feat, vg, out, (hipStream_t)stream, ab, max_blocks);
+}
+
 int acx_profile_enable(acx_ctx* c, int on) {
     if (!c) ACX_FAIL(ACX_ERR_ARG, "null context");
     c->prof.on = on != 0;

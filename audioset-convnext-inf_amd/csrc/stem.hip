@@ -15,6 +15,9 @@
 // A channel still accumulates bias, then ky, kx ascending, one fused multiply-add per tap.  LayerNorm statistics by
 // xor-shuffles inside the 32-lane group.  A pixel leaves as one 384-byte run (12 bytes per lane; bf16: the even lane of a pair
 // stores both lanes' six channels).  0.90 MB in + 5.42 MB out per 10 s clip.
+// The walk: workgroup g takes row pairs g, g + G, g + 2 G, ... (G = the grid, at most kStemMaxBlocks), the outer loop two of them
+// per trip; only beyond 2 G pairs does a workgroup consume a staging register that was refilled inside the loop.  acx_test_stem
+// (api.hip) runs each of the four instantiations on its own and can cap G, so that tests walk many pairs on a few rows.
 #include "acx_internal.h"
 #include "device_common.h"
 
@@ -188,11 +191,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     }
 }
 
-int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hipStream_t s, bool act_bf16) {
+// the grid of a launch: one workgroup per row pair up to kStemMaxBlocks, or up to max_blocks where the caller caps it
+static long long stem_blocks(long long npairs, int max_blocks) {
+    const long long cap = max_blocks > 0 && max_blocks < kStemMaxBlocks ? max_blocks : kStemMaxBlocks;
+    return npairs < cap ? npairs : cap;
+}
+
+int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hipStream_t s, bool act_bf16, int max_blocks) {
     const long long nrows = (long long)B * H0;
     if (nrows >= (1LL << 31)) ACX_FAIL(ACX_ERR_SHAPE, "stem: %lld output rows do not fit the kernel's 32-bit row arithmetic", nrows);
     const long long npairs = (nrows + 1) / 2;
-    long long blocks = npairs < 2048 ? npairs : 2048;   // 8 resident workgroups per CU, every workgroup walks ~4 row pairs at B = 64
+    const long long blocks = stem_blocks(npairs, max_blocks);   // 8 resident workgroups per CU, every workgroup walks ~4 row pairs at B = 64
     ProfScope ps(c, ACX_K_STEM, s);
     const int* nil = nullptr;
     if (act_bf16)
@@ -205,10 +214,10 @@ int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hi
     return ACX_OK;
 }
 
-int launch_stem_varlen(acx_ctx* c, const float* in, const VarGeom& vg, void* out, hipStream_t s, bool act_bf16) {
+int launch_stem_varlen(acx_ctx* c, const float* in, const VarGeom& vg, void* out, hipStream_t s, bool act_bf16, int max_blocks) {
     const long long nrows = vg.rows[0];
     const long long npairs = (nrows + 1) / 2;
-    long long blocks = npairs < 2048 ? npairs : 2048;
+    const long long blocks = stem_blocks(npairs, max_blocks);
     ProfScope ps(c, ACX_K_STEM, s);
     if (act_bf16)
         launch_kernel(&stem_kernel<true, true>, dim3((unsigned)blocks), dim3(256), 0, s, in, 0, 0, nrows, c->d_stem_w, c->d_stem_b,

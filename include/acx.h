@@ -1417,6 +1417,19 @@ ACX_API int acx_test_dwconv7_form(acx_ctx* ctx, int stage, int block, const floa
 ACX_API int acx_test_dwconv7_varlen(acx_ctx* ctx, int stage, int block, const void* x, void* y, const int64_t* lengths, int n,
                             int target_waves, void* scratch, size_t scratch_bytes, void* stream);
 ACX_API int acx_test_dwconv7_varlen_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes);
+/* Test support: the stem kernel (K2) per FORM.  feat: the bn0'd log-mel rows, fp32; out: NHWC rows of 56 x 96 in the type the
+ * context's precision stores at stage 0 -- fp32, or raw bf16 under ACX_PREC_BF16_ACT -- with no conversion at the boundary.
+ *   uniform: lengths = NULL, n = 0: feat (B, T, 224) -> out (B, H0, 56, 96), H0 = (T + 4) / 4 + 1; scratch is not used.
+ *   packed : lengths = n clip lengths in samples (HOST array, each >= ACX_MIN_SAMPLES, n <= ACX_MAX_VARLEN_CLIPS); B and T are
+ *            ignored.  feat = the clips' frames back to back, out = their rows back to back.  The tables are built in `scratch`
+ *            (>= acx_test_stem_scratch_bytes, 256-byte aligned) as acx_forward_varlen builds them.
+ * max_blocks: 0 = the launcher's own grid (one workgroup per pair of output rows, at most 2048); 1 .. 2048 caps the grid below
+ * that, so that a workgroup walks many row pairs on a small tensor.  The result does not depend on it.
+ * Everything is checked before the first launch.  acx_test_stem_scratch_bytes needs no context; out_rows (may be NULL) receives
+ * the number of stage-0 rows of the packed clips.  No reference counterpart. */
+ACX_API int acx_test_stem(acx_ctx* ctx, const float* feat, void* out, int B, int T, const int64_t* lengths, int n, int max_blocks,
+                          void* scratch, size_t scratch_bytes, void* stream);
+ACX_API int acx_test_stem_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes, int64_t* out_rows);
 
 /* ---- measurement: per-kernel-class device time, HIP events on the launch stream ------------ */
 ACX_API int acx_profile_enable(acx_ctx* ctx, int on);

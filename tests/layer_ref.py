@@ -286,16 +286,16 @@ class Guarded:
 
     @classmethod
     def tensor(cls, t, device="cuda"):
-        """A float32 tensor with t's values inside a guarded buffer -> (guard, view)."""
-        g = cls(t.numel() * 4, device)
-        v = g.payload.view(torch.float32).view(t.shape)
+        """A tensor of t's type (float32, or a 16-bit payload such as bf16) with t's values inside a guarded buffer -> (guard, view)."""
+        g = cls(t.numel() * t.element_size(), device)
+        v = g.payload.view(t.dtype).view(t.shape)
         v.copy_(t)
         return g, v
 
     @classmethod
-    def filled(cls, shape, value=float("nan"), device="cuda"):
-        g = cls(int(np.prod(shape)) * 4, device)
-        v = g.payload.view(torch.float32).view(shape)
+    def filled(cls, shape, value=float("nan"), device="cuda", dtype=torch.float32):
+        g = cls(int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size(), device)
+        v = g.payload.view(dtype).view(shape)
         v.fill_(value)
         return g, v
 
