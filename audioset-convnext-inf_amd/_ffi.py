@@ -108,6 +108,14 @@ class AcxDwconv7Plan(ctypes.Structure):
 
 _pplan = ctypes.POINTER(AcxDwconv7Plan)
 
+
+class AcxDwconv7Bf16Plan(ctypes.Structure):
+    """struct acx_dwconv7_bf16_plan_t: what a launch of the matrix-pipe depthwise kernel consists of (acx_test_dwconv7_bf16_plan)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("rows", "steps", "n_seg", "n_groups", "grid", "too_tall")]
+
+
+_pplan16 = ctypes.POINTER(AcxDwconv7Bf16Plan)
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -292,6 +300,9 @@ SIGNATURES = {
     "acx_test_dwconv7_varlen_plan": (_c_int, [_c_int, ctypes.POINTER(_c_i64), _c_int, _c_int, _pplan]),
     "acx_test_dwconv7_form": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
     "acx_test_dwconv7_varlen": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _c_sz, _vp]),
+    "acx_test_dwconv7_bf16_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _pplan16]),
+    "acx_test_dwconv7_bf16_varlen_plan": (_c_int, [_c_int, ctypes.POINTER(_c_i64), _c_int, _c_int, _pplan16]),
+    "acx_test_dwconv7_bf16_form": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp]),
     "acx_test_dwconv7_varlen_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz)]),
     "acx_test_stem": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _c_sz, _vp]),
     "acx_test_stem_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_i64)]),

@@ -292,7 +292,7 @@ int launch_logmel(acx_ctx* c, const float* wav, int B, int64_t L, int T, float* 
 constexpr int kStemMaxBlocks = 2048;
 int launch_stem(acx_ctx* c, const float* in, int B, int T, int H0, void* out, hipStream_t s, bool act_bf16 = false, int max_blocks = 0);
 int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, int B, int H,
-                  int W, hipStream_t s, bool act_bf16 = false);
+                  int W, hipStream_t s, bool act_bf16 = false, int dwm_target_waves = 0 /* bf16: 0 = ACX_DWM_WAVES per CU of the launch's share */);
 // column-streaming form (dwconv_col.hip): same bits as the kernels of dwconv.hip; `sink` (kDwSinkBytes, device) takes the
 // stores of rows that are not part of the image; target_waves = waves the launch should spread over (one per SIMD)
 constexpr int kDwColMinRows = 16;            // output rows per wave segment below which the launch uses fewer waves
@@ -318,6 +318,12 @@ int launch_dwconv_form(acx_ctx* c, const BlockW& w, int C, const void* x, void* 
 std::vector<uint16_t> dwconv_mfma_pack(const std::vector<float>& dw, int C);
 int launch_dwconv_mfma(const void* x, void* y, const void* dw_ops, const float* bias, void* sink, int B, int H, int W,
                        int target_waves, hipStream_t s);
+// What a matrix-form launch consists of: n_seg segments of `rows` = 4 `steps` output rows of the Vt stacked rows, one (slice,
+// segment) group each -> n_groups, packed into `grid` workgroups.  dw_mfma_segments is the ONE place that decides it, for both
+// launchers; dw_mfma_too_tall: the batch is beyond the uniform kernel's multiply-high division.
+struct DwMfmaPlan { int rows, steps, n_seg, n_groups, grid; };
+int dw_mfma_segments(int W, long long Vt, int target_waves, DwMfmaPlan* plan);
+bool dw_mfma_too_tall(int B, int H);
 // element-wise fp32 <-> bf16 (the per-layer entry points of the C ABI keep fp32 tensors in every mode)
 int launch_convert_f32_to_bf16(const float* in, void* out, long long n, hipStream_t s);
 int launch_convert_bf16_to_f32(const void* in, float* out, long long n, hipStream_t s);

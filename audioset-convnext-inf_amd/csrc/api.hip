@@ -358,6 +358,44 @@ int acx_test_dwconv7_form(acx_ctx* c, int stage, int block, const float* x, floa
     return launch_dwconv_form(c, c->blocks[stage][block], kDims[stage], x, y, stats, B, H, Wd, form == 1, target_waves, (hipStream_t)stream);
 }
 
+static void export_plan(const DwMfmaPlan& p, bool too_tall, acx_dwconv7_bf16_plan_t* out) {
+    out->rows = p.rows; out->steps = p.steps; out->n_seg = p.n_seg; out->n_groups = p.n_groups; out->grid = p.grid;
+    out->too_tall = too_tall ? 1 : 0;
+}
+
+int acx_test_dwconv7_bf16_plan(int stage, int B, int H, int target_waves, acx_dwconv7_bf16_plan_t* plan) {
+    if (!plan || stage < 0 || stage > 2 || B <= 0 || H <= 0 || target_waves <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_bf16_plan: bad argument");
+    DwMfmaPlan p;
+    ACX_TRY(dw_mfma_segments(kStemW >> stage, (long long)B * (H + 3) - 3, target_waves, &p));
+    export_plan(p, dw_mfma_too_tall(B, H), plan);
+    return ACX_OK;
+}
+
+int acx_test_dwconv7_bf16_varlen_plan(int stage, const int64_t* lengths, int n, int target_waves, acx_dwconv7_bf16_plan_t* plan) {
+    if (!plan || stage < 0 || stage > 2 || target_waves <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_bf16_varlen_plan: bad argument");
+    VarGeom vg;
+    size_t bytes = 0;
+    ACX_TRY(varlen_geometry(lengths, n, nullptr, &vg, &bytes));
+    DwMfmaPlan p;
+    ACX_TRY(dw_mfma_segments(kStemW >> stage, (long long)vg.vrows[stage] - 3, target_waves, &p));
+    export_plan(p, false, plan);       // the packed kernel divides nothing: its cursors read the row tables
+    return ACX_OK;
+}
+
+int acx_test_dwconv7_bf16_form(acx_ctx* c, int stage, int block, const uint16_t* x, uint16_t* y, int B, int H, int Wd, int target_waves,
+                               void* stream) {
+    ACX_TRY(need_ready(c));
+    ACX_TRY(check_stage(stage, block));
+    if (!x || !y || B <= 0 || H <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_bf16_form: bad argument");
+    if (!act_bf16(c, stage)) ACX_FAIL(ACX_ERR_STATE, "acx_test_dwconv7_bf16_form: stage %d does not store bf16 activations at this precision", stage);
+    if (Wd != (kStemW >> stage)) ACX_FAIL(ACX_ERR_SHAPE, "stage %d has width %d, got %d", stage, kStemW >> stage, Wd);
+    int cus = 0;
+    ACX_TRY(cu_count_of_current_device(&cus));
+    if (target_waves < 1 || target_waves > 9 * cus)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_bf16_form: target_waves %d (expected 1 .. %d)", target_waves, 9 * cus);
+    return launch_dwconv(c, c->blocks[stage][block], kDims[stage], x, y, nullptr, B, H, Wd, (hipStream_t)stream, true, target_waves);
+}
+
 int acx_test_dwconv7_varlen_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes) {
     if (!out_bytes) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen_scratch_bytes: bad argument");
     VarGeom vg;
@@ -371,14 +409,15 @@ int acx_test_dwconv7_varlen(acx_ctx* c, int stage, int block, const void* x, voi
     if (!x || !y || !scratch) ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen: null pointer");
     int cus = 0;
     ACX_TRY(cu_count_of_current_device(&cus));
-    if (target_waves < 1 || target_waves > 8 * cus)
-        ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen: target_waves %d (expected 1 .. %d)", target_waves, 8 * cus);
+    const bool ab = act_bf16(c, stage);
+    const int max_waves = (ab ? 9 : 8) * cus;      // bf16 activations: the matrix-pipe kernel, up to ACX_DWM_WAVES = 9 per CU
+    if (target_waves < 1 || target_waves > max_waves)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_dwconv7_varlen: target_waves %d (expected 1 .. %d)", target_waves, max_waves);
     VarGeom vg;
     size_t need = 0;
     ACX_TRY(varlen_geometry(lengths, n, (char*)scratch, &vg, &need));
     if (scratch_bytes < need || ((uintptr_t)scratch & 255))
         ACX_FAIL(ACX_ERR_WORKSPACE, "acx_test_dwconv7_varlen: scratch too small (%zu < %zu) or misaligned", scratch_bytes, need);
-    const bool ab = act_bf16(c, stage);
     if (ab && stage > 2) ACX_FAIL(ACX_ERR_STATE, "acx_test_dwconv7_varlen: no bf16 activations in stage %d", stage);
     ACX_TRY(launch_varlen_tables(lengths, vg, (hipStream_t)stream));
     return launch_dwconv_varlen(c, c->blocks[stage][block], kDims[stage], x, y, nullptr, vg, stage, (hipStream_t)stream, ab, target_waves);

@@ -656,7 +656,7 @@ static bool use_col_kernel(const acx_ctx* c, int B, int H, int W, int* target_wa
 }
 
 int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, float* stats, int B, int H,
-                  int W, hipStream_t s, bool act_bf16) {
+                  int W, hipStream_t s, bool act_bf16, int dwm_target_waves) {
     const bool model_shape = C == 96 * 56 / (W > 0 ? W : 1);
     if (act_bf16) {
         // bf16 activations (stages 0-2 of "bf16a"): the matrix-pipe kernel, at every launch size -- its arithmetic (bf16 weights,
@@ -668,7 +668,8 @@ int launch_dwconv(acx_ctx* c, const BlockW& w, int C, const void* x, void* y, fl
         int cus = 0;
         ACX_TRY(cu_count_of_current_device(&cus));
         const int per_cu = tuning().dwm_waves.load(std::memory_order_relaxed);
-        return launch_dwconv_mfma(x, y, w.dw_ops, w.dwb, c->d_dw_sink, B, H, W, (per_cu ? per_cu : 8) * cus / inflight_ways(), s);
+        return launch_dwconv_mfma(x, y, w.dw_ops, w.dwb, c->d_dw_sink, B, H, W,
+                                  dwm_target_waves > 0 ? dwm_target_waves : (per_cu ? per_cu : 8) * cus / inflight_ways(), s);
     }
     int target_waves = 0;
     const bool col = model_shape && use_col_kernel(c, B, H, W, &target_waves);

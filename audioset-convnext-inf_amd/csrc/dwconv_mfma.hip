@@ -375,23 +375,51 @@ __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const void* __restric
     }
 }
 
-template <int W>
-static int launch_dw_mfma_w(const void* x, void* y, const void* wt, const float* bias, void* sink, int B, int H, int target_waves, hipStream_t s) {
-    using G = DwmGeom<W>;
+// ---- the plan of a launch (host arithmetic only; acx_test_dwconv7_bf16_plan reports it) -------------------------------------------
+// exactness of v / (H + 3) by multiply-high, up to the rows the last segment requests
+bool dw_mfma_too_tall(int B, int H) {
     const long long Vt = (long long)B * (H + 3) - 3;
-    if ((2 * Vt + 16ll * (H + 3) + 64) * (H + 3) >= 0xffffffffll)      // exactness of v / (H + 3) by multiply-high, up to the rows the last segment requests
-        ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: batch too tall for one launch (%d clips of %d rows)", B, H);
+    return (2 * Vt + 16ll * (H + 3) + 64) * (H + 3) >= 0xffffffffll;
+}
+
+// target_waves: how many waves the launch should consist of.  The Vt stacked rows are cut into segments of `rows` output rows (a
+// multiple of four, at least eight), one per (slice, segment) group of kStrips waves; kGroups groups make a workgroup.  The ONE
+// place that decides it, for uniform and variable-length batches.
+template <int W>
+static DwMfmaPlan dw_mfma_segments_w(long long Vt, int target_waves) {
+    using G = DwmGeom<W>;
     long long segs = target_waves / (G::kStrips * G::kSlices);
     if (segs < 1) segs = 1;
     long long rows = (Vt + segs - 1) / segs;
     rows = (rows + 3) / 4 * 4;
     if (rows < 8) rows = 8;
     const long long n_seg = (Vt + rows - 1) / rows;
-    const int n_groups = (int)(n_seg * G::kSlices);
+    DwMfmaPlan p;
+    p.rows = (int)rows;
+    p.steps = (int)(rows / 4);
+    p.n_seg = (int)n_seg;
+    p.n_groups = (int)(n_seg * G::kSlices);
+    p.grid = (p.n_groups + G::kGroups - 1) / G::kGroups;
+    return p;
+}
+
+int dw_mfma_segments(int W, long long Vt, int target_waves, DwMfmaPlan* plan) {
+    switch (W) {
+        case 56: *plan = dw_mfma_segments_w<56>(Vt, target_waves); return ACX_OK;
+        case 28: *plan = dw_mfma_segments_w<28>(Vt, target_waves); return ACX_OK;
+        case 14: *plan = dw_mfma_segments_w<14>(Vt, target_waves); return ACX_OK;
+        default: ACX_FAIL(ACX_ERR_SHAPE, "dwconv7 (matrix form): unsupported width %d (expected 56/28/14)", W);
+    }
+}
+
+template <int W>
+static int launch_dw_mfma_w(const void* x, void* y, const void* wt, const float* bias, void* sink, int B, int H, int target_waves, hipStream_t s) {
+    if (dw_mfma_too_tall(B, H)) ACX_FAIL(ACX_ERR_SHAPE, "dwconv7: batch too tall for one launch (%d clips of %d rows)", B, H);
+    const DwMfmaPlan p = dw_mfma_segments_w<W>((long long)B * (H + 3) - 3, target_waves);
     static DeviceOnce once;
     ACX_TRY(set_max_dynamic_lds(once, &dwconv7_mfma_kernel<W, false>, kCuLdsBytes));
-    launch_kernel(&dwconv7_mfma_kernel<W, false>, dim3((unsigned)((n_groups + G::kGroups - 1) / G::kGroups)), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
-        x, y, wt, bias, sink, B, H, (int)(rows / 4), n_groups, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u,
+    launch_kernel(&dwconv7_mfma_kernel<W, false>, dim3((unsigned)p.grid), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
+        x, y, wt, bias, sink, B, H, p.steps, p.n_groups, (unsigned)(0x100000000ull / (unsigned)(H + 3)) + 1u,
         (const int*)nullptr, (const int*)nullptr, 0);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
@@ -401,19 +429,11 @@ static int launch_dw_mfma_w(const void* x, void* y, const void* wt, const float*
 template <int W>
 static int launch_dw_mfma_var(const void* x, void* y, const void* wt, const float* bias, void* sink, const VarGeom& vg, int stage,
                               int target_waves, hipStream_t s) {
-    using G = DwmGeom<W>;
-    const long long Vt = (long long)vg.vrows[stage] - 3;
-    long long segs = target_waves / (G::kStrips * G::kSlices);
-    if (segs < 1) segs = 1;
-    long long rows = (Vt + segs - 1) / segs;
-    rows = (rows + 3) / 4 * 4;
-    if (rows < 8) rows = 8;
-    const long long n_seg = (Vt + rows - 1) / rows;
-    const int n_groups = (int)(n_seg * G::kSlices);
+    const DwMfmaPlan p = dw_mfma_segments_w<W>((long long)vg.vrows[stage] - 3, target_waves);
     static DeviceOnce once;
     ACX_TRY(set_max_dynamic_lds(once, &dwconv7_mfma_kernel<W, true>, kCuLdsBytes));
-    launch_kernel(&dwconv7_mfma_kernel<W, true>, dim3((unsigned)((n_groups + G::kGroups - 1) / G::kGroups)), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
-        x, y, wt, bias, sink, vg.B, 0, (int)(rows / 4), n_groups, 0u, vg.roff[stage], vg.vclip[stage], vg.vrows[stage]);
+    launch_kernel(&dwconv7_mfma_kernel<W, true>, dim3((unsigned)p.grid), dim3(512), kCuLdsBytes /* CU-exclusive */, s,
+        x, y, wt, bias, sink, vg.B, 0, p.steps, p.n_groups, 0u, vg.roff[stage], vg.vclip[stage], vg.vrows[stage]);
     ACX_HIP(hipGetLastError());
     return ACX_OK;
 }

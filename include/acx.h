@@ -1413,10 +1413,26 @@ ACX_API int acx_test_dwconv7_form(acx_ctx* ctx, int stage, int block, const floa
 /* The depthwise conv of ONE stage of a packed batch as acx_forward_varlen queues it: builds the tables of `lengths` (n clips, in
  * samples, host) in `scratch` (>= acx_test_dwconv7_varlen_scratch_bytes, 256-byte aligned), then runs the variable-length launcher
  * at `target_waves` (1 .. 8 x CUs).  x, y: the clips' rows of that stage back to back, NHWC -- fp32, or bf16 in stages 0-2 under
- * ACX_PREC_BF16_ACT (the matrix-pipe kernel). */
+ * ACX_PREC_BF16_ACT (the matrix-pipe kernel, `target_waves` 1 .. 9 x CUs: what ACX_DWM_WAVES can ask for). */
 ACX_API int acx_test_dwconv7_varlen(acx_ctx* ctx, int stage, int block, const void* x, void* y, const int64_t* lengths, int n,
                             int target_waves, void* scratch, size_t scratch_bytes, void* stream);
 ACX_API int acx_test_dwconv7_varlen_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes);
+/* Test support: the matrix-pipe depthwise kernel of ACX_PREC_BF16_ACT (dwconv_mfma.hip, stages 0-2) per launch shape.  It cuts the
+ * stacked batch into n_seg segments of `rows` = 4 `steps` output rows (a multiple of four, at least eight); every segment is
+ * n_groups / n_seg (slice, segment) groups of waves, packed into `grid` workgroups.  acx_test_dwconv7_bf16_plan reports what the
+ * launcher would launch for B clips of H rows in `stage` (0 .. 2) at `target_waves`, and in too_tall whether the launcher's guard
+ * (the kernel's multiply-high division) refuses the batch -- host arithmetic only: no context, no device;
+ * acx_test_dwconv7_bf16_varlen_plan the same for the packed clips of `lengths` (samples; too_tall is 0: the packed kernel divides
+ * nothing).  Both call the functions the launchers call.  No reference counterpart. */
+typedef struct acx_dwconv7_bf16_plan_t {
+    int rows, steps, n_seg, n_groups, grid, too_tall;
+} acx_dwconv7_bf16_plan_t;
+ACX_API int acx_test_dwconv7_bf16_plan(int stage, int B, int H, int target_waves, acx_dwconv7_bf16_plan_t* plan);
+ACX_API int acx_test_dwconv7_bf16_varlen_plan(int stage, const int64_t* lengths, int n, int target_waves, acx_dwconv7_bf16_plan_t* plan);
+/* acx_dwconv7_bf16 with `target_waves` (1 .. 9 x CUs, the range ACX_DWM_WAVES = 2 .. 9 and the sub-batches in flight can produce)
+ * in place of the shipped setting.  Refuses whatever acx_dwconv7_bf16 refuses; everything is checked before the launch. */
+ACX_API int acx_test_dwconv7_bf16_form(acx_ctx* ctx, int stage, int block, const uint16_t* x, uint16_t* y, int B, int H, int W,
+                               int target_waves, void* stream);
 /* Test support: the stem kernel (K2) per FORM.  feat: the bn0'd log-mel rows, fp32; out: NHWC rows of 56 x 96 in the type the
  * context's precision stores at stage 0 -- fp32, or raw bf16 under ACX_PREC_BF16_ACT -- with no conversion at the boundary.
  *   uniform: lengths = NULL, n = 0: feat (B, T, 224) -> out (B, H0, 56, 96), H0 = (T + 4) / 4 + 1; scratch is not used.

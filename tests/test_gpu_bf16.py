@@ -156,8 +156,23 @@ def test_dwconv_matrix_kernel_segmentation_is_invisible(ctx16, model16):
     if model16.precision != "bf16a":
         pytest.skip("bf16 activations only")
     refresh = _ffi.lib().acx_tuning_refresh
-    s, B = 2, 5
+    s = 2
     C, W, H = DIMS[s], 56 >> s, 252 >> s
+    # The smallest batch that the four settings cut differently ON THIS DEVICE, from the launcher's own arithmetic
+    # (acx_test_dwconv7_bf16_plan): 256 CUs, B = 16: 7 / 3 / 2 / 2 steps.  (At B = 5 all four gave one and the same launch.)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def steps(B):
+        p = _ffi.AcxDwconv7Bf16Plan()
+        out = []
+        for per_cu in (2, 5, 9, 8):
+            _ffi.check(_ffi.lib().acx_test_dwconv7_bf16_plan(s, B, H, per_cu * cus, ctypes.byref(p)))
+            assert not p.too_tall
+            out.append(p.steps)
+        return out
+    B = next(b for b in range(2, 129) if len(set(steps(b))) >= 3)
+    print("segmentation test: %d CUs, B = %d: %s steps at ACX_DWM_WAVES = 2 / 5 / 9 / default" % (cus, B, steps(B)))
+    assert len(set(steps(B))) >= 3
     x = (torch.randn(B, H, W, C, generator=torch.Generator().manual_seed(99)) * 2.0).to(torch.bfloat16).cuda()
     ref = _dw_bf16(ctx16, s, 2, x, B, H, W)
     try:
