@@ -280,6 +280,18 @@ SIGNATURES = {
                                 _vp, _c_sz, _vp]),
     "acx_cluster_dispersion": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_contingency": (_c_int, [_vp, _c_int, _vp, _c_int, _c_i64, _vp, _vp, _vp]),
+    "acx_radius_workspace_bytes": (_c_int, [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_radius_slices": (_c_int, [_c_i64, _c_i64, _c_int, _pint]),
+    "acx_radius_row_sumsq": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp]),
+    "acx_radius_count": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _vp, _vp,
+                                  _vp, _c_sz, _vp]),
+    "acx_radius_neighbors": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _c_int,
+                                      _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_radius_emit": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _c_int,
+                                 _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_graph_components": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_int, _c_int, _vp]),
+    "acx_dbscan_workspace_bytes": (_c_int, [_c_i64, ctypes.POINTER(_c_sz)]),
+    "acx_dbscan_labels": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _c_int, _vp]),
     "acx_moments_workspace_bytes": (_c_int, [_c_i64, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_moments": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
     "acx_gram_f64": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp]),
@@ -882,6 +894,69 @@ def cluster_dispersion(x, ld_x, n, dim, labels, clusters, counts, means, within_
 def contingency(a, ka, b, kb, n, table, status, stream):
     """acx_contingency on raw device pointers (ctypes.c_void_p)."""
     check(lib().acx_contingency(a, int(ka), b, int(kb), int(n), table, status, stream))
+
+
+# ---- radius search, components, DBSCAN (acx_radius_*, acx_graph_components, acx_dbscan_labels) ---------------------------------
+RADIUS_DOT, RADIUS_COSINE, RADIUS_EUCLIDEAN = 0, 1, 2          # enum acx_radius_metric
+RADIUS_METRICS = {"dot": RADIUS_DOT, "cosine": RADIUS_COSINE, "euclidean": RADIUS_EUCLIDEAN}
+RADIUS_SELF_NONE, RADIUS_SELF_EXCLUDE, RADIUS_SELF_INCLUDE = 0, 1, 2     # enum acx_radius_self
+# bits of the status words of the acx_radius_* / acx_graph_components / acx_dbscan_labels calls
+RADIUS_NONFINITE, RADIUS_OVERFLOW, GRAPH_BAD_INDEX, GRAPH_NOT_CONVERGED = 1, 2, 4, 8
+RADIUS_MAX_SLICES = 64                         # ACX_RADIUS_MAX_SLICES
+GRAPH_MAX_ROUNDS = 4096                        # ACX_GRAPH_MAX_ROUNDS
+
+
+def radius_workspace_bytes(nq, n, slices=0):
+    """Workspace of acx_radius_count (slices = 0) / acx_radius_neighbors (host only)."""
+    return _query(lib().acx_radius_workspace_bytes, _c_sz, int(nq), int(n), int(slices))
+
+
+def radius_slices(nq, n, slices=0):
+    """The ranges of database rows acx_radius_count / acx_radius_neighbors cut (host only)."""
+    return _query(lib().acx_radius_slices, _c_int, int(nq), int(n), int(slices))
+
+
+def radius_row_sumsq(x, ld, n, dim, xx, stream):
+    """acx_radius_row_sumsq on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_radius_row_sumsq(x, int(ld), int(n), int(dim), xx, stream))
+
+
+def radius_count(q, ld_q, q_aux, nq, d, ld_d, d_aux, n, dim, metric, level, self_mode, counts, status, ws, stream):
+    """acx_radius_count on raw device pointers (ctypes.c_void_p); aux None for the dot metric; ws: (pointer, bytes)."""
+    check(lib().acx_radius_count(q, int(ld_q), q_aux, int(nq), d, int(ld_d), d_aux, int(n), int(dim), int(metric), float(level),
+                                 int(self_mode), counts, status, ws[0], int(ws[1]), stream))
+
+
+def radius_neighbors(q, ld_q, q_aux, nq, d, ld_d, d_aux, n, dim, metric, level, self_mode, slices, offsets, indices, values, capacity,
+                     total, status, ws, stream):
+    """acx_radius_neighbors on raw device pointers (ctypes.c_void_p); values may be None; ws: (pointer, bytes)."""
+    check(lib().acx_radius_neighbors(q, int(ld_q), q_aux, int(nq), d, int(ld_d), d_aux, int(n), int(dim), int(metric), float(level),
+                                     int(self_mode), int(slices), offsets, indices, values, int(capacity), total, status, ws[0],
+                                     int(ws[1]), stream))
+
+
+def radius_emit(q, ld_q, q_aux, nq, d, ld_d, d_aux, n, dim, metric, level, self_mode, slices, offsets, indices, values, capacity, total,
+                status, ws, stream):
+    """acx_radius_emit on raw device pointers (ctypes.c_void_p): the emit pass on the workspace an acx_radius_neighbors call left."""
+    check(lib().acx_radius_emit(q, int(ld_q), q_aux, int(nq), d, int(ld_d), d_aux, int(n), int(dim), int(metric), float(level),
+                                int(self_mode), int(slices), offsets, indices, values, int(capacity), total, status, ws[0], int(ws[1]),
+                                stream))
+
+
+def graph_components(offsets, indices, n, labels, status, max_rounds, resume, stream):
+    """acx_graph_components on raw device pointers (ctypes.c_void_p)."""
+    check(lib().acx_graph_components(offsets, indices, int(n), labels, status, int(max_rounds), 1 if resume else 0, stream))
+
+
+def dbscan_workspace_bytes(n):
+    """Workspace of acx_dbscan_labels (host only)."""
+    return _query(lib().acx_dbscan_workspace_bytes, _c_sz, int(n))
+
+
+def dbscan_labels(offsets, indices, n, min_samples, labels, core, clusters, status, ws, max_rounds, stream):
+    """acx_dbscan_labels on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_dbscan_labels(offsets, indices, int(n), int(min_samples), labels, core, clusters, status, ws[0], int(ws[1]),
+                                  int(max_rounds), stream))
 
 
 MAX_EVENT_MEDIAN = 101                        # ACX_MAX_EVENT_MEDIAN

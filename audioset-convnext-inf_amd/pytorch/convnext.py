@@ -958,6 +958,18 @@ class ConvNeXt(nn.Module):
         from .cluster_scores import select_clusters
         return select_clusters(self._scene_rows(data, sample_rate), ks, device=self.head_audioset.weight.device, **kw)
 
+    def find_duplicates(self, data, threshold=0.95, sample_rate=None, **kw):
+        """The groups of near-duplicate clips (pytorch/neighbors.py: duplicate_groups) over scene embeddings on the model's device:
+        `data` as cluster() takes it; kw: metric, max_rounds.  -> neighbors.DuplicateGroups (labels, sizes, keep, pairs, groups())."""
+        from .neighbors import duplicate_groups
+        return duplicate_groups(self._scene_rows(data, sample_rate), threshold, device=self.head_audioset.weight.device, **kw)
+
+    def dbscan(self, data, eps, min_samples=5, sample_rate=None, **kw):
+        """Density clustering (pytorch/neighbors.py: dbscan) over scene embeddings on the model's device: `data` as cluster() takes
+        it; kw: metric, max_rounds.  -> neighbors.DBSCANResult (labels with -1 for noise, core, counts, clusters)."""
+        from .neighbors import dbscan
+        return dbscan(self._scene_rows(data, sample_rate), eps, min_samples, device=self.head_audioset.weight.device, **kw)
+
     def _scene_rows(self, data, sample_rate):
         """`data` as build_index takes it -> (n, 768) scene embeddings: a 2-D tensor of embeddings as it is, a list of waveforms
         at `sample_rate` extracted first (extract(..., what="scene", pack=True))."""

@@ -498,6 +498,45 @@ class EmbeddingIndex:
                                   cs._sample_rows(self._n, sample, seed, self.device))
         return cs.ClusterScores(sil, cs._dispersion_rows(x, self.dim, lab, K))
 
+    # ---- radius search (pytorch/neighbors.py), with the index's own metric and inverse norms
+    def _radius_self(self):
+        if self._n == 0:
+            raise ValueError("the index is empty")
+        return self._buf[:self._n], self.inverse_norms
+
+    def radius(self, queries=None, threshold=0.9, values=True, slices=0):
+        """The stored rows whose score (the index's metric) with each query is at least `threshold`, as a CSR list in ascending row
+        index -> neighbors.RadiusNeighbors.  queries None: a self-join, every row against the others.  The values have the bits
+        search() gives the same pair."""
+        from . import neighbors as nb
+        d, rd = self._radius_self()
+        level = float(nb.level_of(threshold, self.metric))
+        with torch.cuda.device(self.device):
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if queries is None:
+                q, rq, mode = d, rd, _ffi.RADIUS_SELF_EXCLUDE
+            else:
+                _check_2d(queries, "queries")
+                q, mode = _rows(queries, self.device, self.dim, "queries"), _ffi.RADIUS_SELF_NONE
+                if q.shape[0] < 1:
+                    raise ValueError("the queries have no rows")
+                rq = row_norms(q, status) if self.metric == "cosine" else None
+            return nb._neighbors_rows(q, rq, d, rd, self.metric, level, mode, status, values, slices)
+
+    def duplicates(self, threshold=0.95, max_rounds=None):
+        """The groups of near-duplicate stored rows (score of at least `threshold`) -> neighbors.DuplicateGroups."""
+        from . import neighbors as nb
+        d, rd = self._radius_self()
+        return nb._groups_rows(d, rd, self.metric, float(nb.level_of(threshold, self.metric)), max_rounds or nb.MAX_ROUNDS)
+
+    def dbscan(self, eps, min_samples=5, max_rounds=None):
+        """DBSCAN over the stored rows with the index's metric: two rows are neighbours when their score is at least `eps`
+        (cosine: scikit-learn's cosine distance 1 - eps) -> neighbors.DBSCANResult."""
+        from . import neighbors as nb
+        nb._check_min_samples(min_samples)
+        d, rd = self._radius_self()
+        return nb._dbscan_rows(d, rd, self.metric, float(nb.level_of(eps, self.metric)), min_samples, max_rounds or nb.MAX_ROUNDS)
+
     def moments(self, ddof=1):
         """Mean and covariance of the stored rows in float64 (pytorch/statistics.py: moments) -> statistics.Moments."""
         from . import statistics

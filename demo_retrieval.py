@@ -7,6 +7,8 @@ ConvNeXt.search).
     python demo_retrieval.py --synthetic                       # seeded weights and clips, no files needed
     python demo_retrieval.py --synthetic --clusters 8          # also k-means over the corpus: sizes, the clip nearest each centre
     python demo_retrieval.py --synthetic --select-clusters 4,8,16     # choose k by the mean silhouette (--cluster-criterion ...)
+    python demo_retrieval.py --synthetic --duplicates 0.95     # groups of near-duplicate clips (radius search + components)
+    python demo_retrieval.py --synthetic --dbscan 0.6,5        # density clustering: no k, an explicit noise set (EPS,MIN_SAMPLES)
     python demo_retrieval.py --synthetic --pca 16 [--whiten]   # also search a PCA-reduced copy of the index, against the full one
     python demo_retrieval.py --synthetic --int8 [--oversample 4] [--no-rerank]     # int8 index: coarse search, exact fp32 rerank
 
@@ -73,6 +75,10 @@ def main():
     ap.add_argument("--select-clusters", default="", help="choose the number of clusters among these, e.g. 10,20,50: one k-means fit "
                     "per k, each scored on the GPU")
     ap.add_argument("--cluster-criterion", default="silhouette", choices=("silhouette", "calinski_harabasz", "davies_bouldin"))
+    ap.add_argument("--duplicates", type=float, default=None, metavar="THRESHOLD",
+                    help="also list the groups of clips whose score (--metric) with each other is at least THRESHOLD")
+    ap.add_argument("--dbscan", default="", metavar="EPS,MIN_SAMPLES",
+                    help="also cluster the corpus by density: neighbours are the clips with a score (--metric) of at least EPS")
     ap.add_argument("--pca", type=int, default=0, help="also reduce the index to this many principal components (PCA on the GPU)")
     ap.add_argument("--whiten", action="store_true", help="--pca: whiten the reduced rows")
     a = ap.parse_args()
@@ -156,6 +162,25 @@ def main():
                               metric="cosine" if a.metric == "cosine" else "euclidean", seed=a.seed)
         print("%s per k: %s -> k = %d" % (a.cluster_criterion, ", ".join("%d: %.4f" % kv for kv in zip(sel.ks, sel.scores.tolist())),
                                           sel.best_k))
+
+    if (a.duplicates is not None or a.dbscan) and a.int8 and a.no_rerank:
+        print("--duplicates / --dbscan need the fp32 rows: skipped with --no-rerank")
+    elif a.duplicates is not None or a.dbscan:
+        rows = index if getattr(index, "exact", None) is None else index.exact
+        if a.duplicates is not None:
+            # which clips are (nearly) the same recording: a radius self-join, then the components of its graph
+            dup = rows.duplicates(a.duplicates).check()
+            groups = dup.groups()
+            print("near-duplicates at %s >= %g: %d groups, %d of %d clips to keep" % (a.metric, a.duplicates, len(groups),
+                                                                                   int(dup.keep.sum()), len(rows)))
+            for g in groups[:8]:
+                print("    " + ", ".join("%s (%s)" % (paths[j], names[int(label[j])]) for j in g))
+        if a.dbscan:
+            eps, min_samples = a.dbscan.split(",")
+            db = rows.dbscan(float(eps), int(min_samples)).check()
+            sizes = torch.bincount(db.labels[~db.noise], minlength=int(db.clusters)).tolist()
+            print("DBSCAN at %s >= %s, min_samples %s: %d clusters, %d noise clips, %d core clips; sizes %s"
+                  % (a.metric, eps, min_samples, int(db.clusters), int(db.noise.sum()), int(db.core.sum()), sizes))
 
     if a.pca and a.int8:
         print("--pca reduces the fp32 index: skipped with --int8")

@@ -1252,6 +1252,86 @@ ACX_API int acx_cluster_dispersion(const float* x, int64_t ld_x, int64_t n, int 
 ACX_API int acx_contingency(const int32_t* a, int ka, const int32_t* b, int kb, int64_t n, int64_t* table, int32_t* status,
                             void* stream);
 
+/* ---- radius search, connected components, DBSCAN: which rows lie within a given distance of each other ---------------------------
+ * Neighbour lists by a threshold instead of a k (no reference counterpart; scikit-learn 1.7.2's radius_neighbors and
+ * DBSCAN(algorithm="brute") are the yardsticks).  Stateless; every buffer is the caller's, on the device.  q (nq, dim) and d (n, dim)
+ * fp32 with row strides ld_q / ld_d under the layout rules of acx_knn_search; nq, n <= 2^30.
+ * THE PAIR VALUE v(i, j) of query row i and database row j, in fp32:
+ *   ACX_RADIUS_DOT, ACX_RADIUS_COSINE: acx_knn_search's score of that pair with the SAME BITS -- its dot product (one fixed order
+ *     per pair, a function of dim alone), for COSINE then (dot * q_aux[i]) * d_aux[j] with aux = the inverse norms of
+ *     acx_knn_row_norms.  The pair is kept iff v >= level.
+ *   ACX_RADIUS_EUCLIDEAN: v = max(fma(-2, dot, q_aux[i] + d_aux[j]), 0) with aux = xx = sum x^2 in one fixed order per row
+ *     (acx_radius_row_sumsq): the squared distance acx_silhouette forms before its square root.  The pair is kept iff v <= level;
+ *     for a radius eps pass level = (float)(eps * eps), the product taken in double.
+ *   A NaN is never kept.  A non-finite dot product of a pair sets ACX_RADIUS_NONFINITE.  aux is NULL (ignored) for ACX_RADIUS_DOT.
+ * SELF-JOINS (self_mode != ACX_RADIUS_SELF_NONE; the queries are the database rows, nq == n): the pair (i, i) is decided by
+ *   position, not by arithmetic: kept with ACX_RADIUS_SELF_INCLUDE, dropped with ACX_RADIUS_SELF_EXCLUDE.  DOT and EUCLIDEAN
+ *   values are symmetric in their bits; COSINE is not ((dot * r_i) * r_j against (dot * r_j) * r_i), so everything built on a
+ *   list treats an edge as UNDIRECTED: {i, j} is an edge iff (i -> j) or (j -> i) is listed.
+ * THE LIST is CSR: offsets (nq + 1) int64, indices int32, values fp32 (NULL: not wanted); row i owns offsets[i] .. offsets[i + 1]
+ *   - 1, in ASCENDING database index.  A pure function of the inputs: no atomically appended rows, the same bytes on every call
+ *   and for every slicing.
+ *   acx_radius_count: counts[i] int32 = the kept pairs of query i.  One fused kernel over (tiles of 256 queries) x (ranges of
+ *     database rows): each 64 x 64 tile of dot products goes straight to keep bits; neither the (nq, n) values nor a mask are
+ *     written.  The ranges: len = 64 ceil(ceil(n / 64) / ns) rows each, ns = min(slices, ACX_RADIUS_MAX_SLICES, ceil(n / 64)),
+ *     slices = 0 standing for the ns in that span with the smallest ceil(ceil(nq / 256) ceil(n / len) / 256) len -- the rows the
+ *     busiest of 256 compute units streams -- and the largest such ns among equals (acx_radius_slices returns the number of ranges).
+ *   acx_radius_neighbors: the count pass per (query, range), an exclusive scan in (query, range) order that writes offsets and
+ *     *total = offsets[nq], and the emit pass (the same kernel body).  total > capacity sets ACX_RADIUS_OVERFLOW: entries at
+ *     positions >= capacity are not written (every store is guarded), offsets and *total stay valid, so the caller can size a
+ *     second call.  capacity = 0 (indices may be NULL then) runs the count and the scan only.
+ *   acx_radius_emit: the emit pass alone, with the arguments of an acx_radius_neighbors call that has run on the same workspace
+ *     (its counts and their scan are read from there; offsets and *total are not written) and a capacity of its own: count with
+ *     capacity 0, read *total, allocate, emit -- two tile passes in all.  The overflow bit is set or cleared against the new
+ *     capacity; the other bits stay.
+ *   acx_graph_components: labels[i] int32 = the smallest row index of i's connected component in the UNDIRECTED graph of a
+ *     self-join list (n rows; offsets non-decreasing from 0, the caller's promise) -- unique, so every schedule gives the same
+ *     bits.  Edge-parallel hooking by integer atomicMin plus pointer jumping, in rounds; max_rounds (1 .. ACX_GRAPH_MAX_ROUNDS)
+ *     rounds are QUEUED, the stop is decided on the device and the launches after it return at once.  Labels not stable after
+ *     max_rounds: ACX_GRAPH_NOT_CONVERGED; resume != 0 continues from the labels given (a forest with labels[i] <= i; any other
+ *     entry restarts its node) instead of labels[i] = i.  An index outside [0, n) sets ACX_GRAPH_BAD_INDEX and that edge is
+ *     skipped.  While the call is queued, bits 29 and 30 of *status are its own; its last kernel clears them.
+ *   acx_dbscan_labels: DBSCAN from a self-join list made with ACX_RADIUS_SELF_INCLUDE.  core[i] = (offsets[i + 1] - offsets[i] >=
+ *     min_samples); clusters = the components of the core-core edges, numbered 0, 1, .. in ascending order of their smallest core
+ *     index; a row that is not core takes the SMALLEST cluster number among its core neighbours (undirected), -1 if it has none.
+ *     These are scikit-learn's labels, border rows included (it expands cluster c completely before it starts c + 1).
+ *     *clusters int32 = the number of clusters.  Status bits as acx_graph_components.
+ *   acx_radius_row_sumsq: xx[i] = sum x_i^2 (fp32, one fixed order per row).
+ *   acx_radius_workspace_bytes (acx_radius_count: slices = 0), acx_dbscan_workspace_bytes: host only, non-decreasing in nq / n.
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable; *status and
+ * *total are cleared by a kernel of the call.  ARGUMENT errors return a negative status before any launch, as for acx_knn_search;
+ * in addition ACX_ERR_ARG: a NaN level, a bad metric or self_mode, a self-join with nq != n, slices outside 0 ..
+ * ACX_RADIUS_MAX_SLICES, capacity < 0, min_samples < 1, max_rounds outside 1 .. ACX_GRAPH_MAX_ROUNDS; nq or n > 2^30 is
+ * ACX_ERR_UNSUPPORTED. */
+enum acx_radius_metric { ACX_RADIUS_DOT = 0, ACX_RADIUS_COSINE = 1, ACX_RADIUS_EUCLIDEAN = 2 };
+enum acx_radius_self { ACX_RADIUS_SELF_NONE = 0, ACX_RADIUS_SELF_EXCLUDE = 1, ACX_RADIUS_SELF_INCLUDE = 2 };
+#define ACX_RADIUS_NONFINITE 1
+#define ACX_RADIUS_OVERFLOW 2
+#define ACX_GRAPH_BAD_INDEX 4
+#define ACX_GRAPH_NOT_CONVERGED 8
+#define ACX_RADIUS_MAX_SLICES 64
+#define ACX_GRAPH_MAX_ROUNDS 4096
+ACX_API int acx_radius_workspace_bytes(int64_t nq, int64_t n, int slices, size_t* out_bytes);
+ACX_API int acx_radius_slices(int64_t nq, int64_t n, int slices, int* out_slices);
+ACX_API int acx_radius_row_sumsq(const float* x, int64_t ld, int64_t n, int dim, float* xx, void* stream);
+ACX_API int acx_radius_count(const float* q, int64_t ld_q, const float* q_aux, int64_t nq, const float* d, int64_t ld_d,
+                             const float* d_aux, int64_t n, int dim, int metric, float level, int self_mode, int32_t* counts,
+                             int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_radius_neighbors(const float* q, int64_t ld_q, const float* q_aux, int64_t nq, const float* d, int64_t ld_d,
+                                 const float* d_aux, int64_t n, int dim, int metric, float level, int self_mode, int slices,
+                                 int64_t* offsets, int32_t* indices, float* values, int64_t capacity, int64_t* total,
+                                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_radius_emit(const float* q, int64_t ld_q, const float* q_aux, int64_t nq, const float* d, int64_t ld_d,
+                            const float* d_aux, int64_t n, int dim, int metric, float level, int self_mode, int slices,
+                            const int64_t* offsets, int32_t* indices, float* values, int64_t capacity, const int64_t* total,
+                            int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_graph_components(const int64_t* offsets, const int32_t* indices, int64_t n, int32_t* labels, int32_t* status,
+                                 int max_rounds, int resume, void* stream);
+ACX_API int acx_dbscan_workspace_bytes(int64_t n, size_t* out_bytes);
+ACX_API int acx_dbscan_labels(const int64_t* offsets, const int32_t* indices, int64_t n, int min_samples, int32_t* labels,
+                              uint8_t* core, int32_t* clusters, int32_t* status, void* ws, size_t ws_bytes, int max_rounds,
+                              void* stream);
+
 /* ---- embedding statistics: float64 moments, Gram products, a symmetric eigensolver, PCA projection ------------------------------
  * Second-order statistics of a set of embeddings (no reference counterpart): what covariance, PCA / whitening, Mahalanobis
  * scores and the Frechet distance rest on.  Stateless; every buffer is the caller's, on the device.  1 <= dim <=
