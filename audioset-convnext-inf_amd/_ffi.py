@@ -116,6 +116,46 @@ class AcxDwconv7Bf16Plan(ctypes.Structure):
 
 _pplan16 = ctypes.POINTER(AcxDwconv7Bf16Plan)
 
+# acx_test_forward_plan: the workspace plan of a forward as data (include/acx.h, ACX_PLAN_*)
+PLAN_DRIVERS = {"uniform": 0, "features": 1, "windows": 2, "varlen": 3, "augmented": 4}
+PLAN_TAILS = {"logits": 0, "scene": 1, "frame": 2, "segment": 3, "segment_embeddings": 4}
+PLAN_REGIONS = ("tables", "feat", "x0", "x1", "x2", "x3", "y", "hidden", "stats", "aug_wave", "aug_feat", "aug_mix", "aug_frames",
+                "aug_spec")
+PLAN_TENANTS = ("dense_frames", "dense_spec", "ln_rows", "mlp_bf16_hidden", "mlp_bf16_rows", "hidden_act", "row_stats", "xnorm",
+                "segment_emb", "scene_rows")
+PLAN_PHASES = ("frontend", "block", "downsample", "tail")
+PLAN_MAX_TENANTS, PLAN_MAX_WAYS = 40, 4
+
+
+class AcxPlanRegion(ctypes.Structure):
+    """struct acx_plan_region_t"""
+    _fields_ = [("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
+class AcxPlanTenant(ctypes.Structure):
+    """struct acx_plan_tenant_t"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("kind", "region", "phase", "stage", "block")] + [
+        ("operands", ctypes.c_uint32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
+class AcxPlanSub(ctypes.Structure):
+    """struct acx_plan_sub_t: one sub-batch of a forward's plan"""
+    _fields_ = [("clips", ctypes.c_int32), ("n_tenants", ctypes.c_int32), ("base", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("regions", AcxPlanRegion * len(PLAN_REGIONS)), ("tenants", AcxPlanTenant * PLAN_MAX_TENANTS)]
+
+
+class AcxForwardPlan(ctypes.Structure):
+    """struct acx_forward_plan_t"""
+    _fields_ = [("n_subs", ctypes.c_int32), ("reserved", ctypes.c_int32), ("total", ctypes.c_uint64), ("promised", ctypes.c_uint64),
+                ("subs", AcxPlanSub * PLAN_MAX_WAYS)]
+
+
+class AcxForwardPlanQuery(ctypes.Structure):
+    """struct acx_forward_plan_query_t"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("precision", "dense", "classes", "head_path", "driver", "tail", "ways", "B",
+                                              "has_wave_plan", "has_lambda")] + [
+        ("L", ctypes.c_int64), ("lengths", ctypes.POINTER(ctypes.c_int64))]
+
 # name -> (restype, argtypes); mirrors include/acx.h one to one
 SIGNATURES = {
     "acx_last_error": (ctypes.c_char_p, []),
@@ -318,6 +358,7 @@ SIGNATURES = {
     "acx_test_dwconv7_varlen_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz)]),
     "acx_test_stem": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _c_sz, _vp]),
     "acx_test_stem_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_i64)]),
+    "acx_test_forward_plan": (_c_int, [ctypes.POINTER(AcxForwardPlanQuery), ctypes.POINTER(AcxForwardPlan)]),
     "acx_profile_enable": (_c_int, [_vp, _c_int]),
     "acx_profile_read": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64)]),
 }
@@ -373,6 +414,19 @@ def _query(fn, ctype, *args):
     out = ctype()
     check(fn(*args, ctypes.byref(out)))
     return out.value
+
+
+def forward_plan(precision, driver="uniform", tail="logits", B=1, L=MIN_SAMPLES, lengths=None, dense=False, classes=NUM_CLASSES,
+                 head_path=0, ways=1, wave=False, lam=False, out=None):
+    """acx_test_forward_plan -> AcxForwardPlan (filled into `out` when given: a sweep reuses one).  No context, no device."""
+    q = AcxForwardPlanQuery(PRECISIONS[precision], int(dense), classes, head_path, PLAN_DRIVERS[driver], PLAN_TAILS[tail], ways,
+                            len(lengths) if lengths is not None else B, int(wave), int(lam), L, None)
+    if lengths is not None:
+        keep = (ctypes.c_int64 * len(lengths))(*lengths)
+        q.lengths = ctypes.cast(keep, ctypes.POINTER(ctypes.c_int64))
+    plan = out if out is not None else AcxForwardPlan()
+    check(lib().acx_test_forward_plan(ctypes.byref(q), ctypes.byref(plan)))
+    return plan
 
 
 def stream_ptr(device):

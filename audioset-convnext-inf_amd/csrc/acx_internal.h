@@ -488,11 +488,48 @@ inline BlockScratch carve_block_scratch(size_t pix, int C, size_t off) {
     b.end = off;
     return b;
 }
+// The capacity of the three regions in bytes.  The forward carves them once, for stage 0, and every later stage -- and every
+// tenant below -- lives in them; a per-layer entry point carves them for its own stage.  kNoCap: a capacity the caller cannot
+// state (acx_downsample takes its scratch as a bare pointer).
+constexpr size_t kNoCap = ~(size_t)0;
+struct ScratchCap { size_t y, hidden, stats; };
+inline ScratchCap scratch_cap(const BlockScratch& b) { return ScratchCap{b.hidden - b.y, b.stats - b.hidden, b.end - b.stats}; }
+
+// ---- the tenants of the forward's workspace: what each needs, in bytes -------------------------------------------------------
+// ONE definition each.  The driver (run_forward, run_block, run_downsample, carve_augmented) checks them against the capacity of
+// the region they are lent, on the host and before the first launch; acx_test_forward_plan reports the same numbers, and
+// tests/test_forward_plan_cpu.py sweeps them over every shape ("The workspace plan").
+// the dense-DFT frontend's frames [n][1024] and spectrum [n][kDenseN], fp32, of n mel frames
+inline size_t need_dense_frames(size_t n) { return n * kNFFT * 4; }
+inline size_t need_dense_spec(size_t n) { return n * kDenseN * 4; }
+// the LayerNorm rows the last block of a stage hands the downsample GEMM: S16 (two fp16 halves per element) or bf16 rows padded
+// to 64 channels, M pixels of C channels
+inline size_t need_ln_rows(int precision, size_t M, int C) {
+    return precision == ACX_PREC_F32_SPLIT ? M * C * 4 : M * (size_t)pad64(C) * 2;
+}
+// run_mlp_bf16: the bf16 hidden activation [M][4C] at offset 0, then the bf16 LayerNorm rows [M][Cp] behind it
+inline size_t need_mlp_bf16_hidden(size_t M, int C) { return M * 4 * C * 2; }
+inline size_t need_mlp_bf16_rows(size_t M, int C) { return M * (size_t)pad64(C) * 2; }
+inline size_t mlp_bf16_rows_offset(size_t M, int C) { return align_up(need_mlp_bf16_hidden(M, C)); }
+// the two-GEMM MLP of the fp32 arithmetics: the hidden activation [M][4C] (fp32, or S16 of the same size), the LayerNorm
+// statistics [M][2] (fp32 only)
+inline size_t need_hidden_act(size_t M, int C) { return M * 4 * C * 4; }
+inline size_t need_row_stats(size_t M) { return M * 2 * 4; }
+// the downsample's normalised input rows when no block wrote them: fp32 / S16 [M][C], bf16 [M][Cp]
+inline size_t need_xnorm(int precision, size_t M, int C) {
+    return precision == ACX_PREC_F32 || precision == ACX_PREC_F32_SPLIT ? M * C * 4 : M * (size_t)pad64(C) * 2;
+}
+// acx_block under ACX_PREC_BF16_ACT: the block's x as bf16 [pix][C], lent the `hidden` scratch of its own stage
+inline size_t need_act_bf16(size_t pix, int C) { return pix * C * 2; }
+// the segment tail's embeddings [rows][768] and the class-tiled head's scene rows [B][768], fp32
+inline size_t need_segment_emb(size_t rows) { return rows * kDims[3] * 4; }
+inline size_t need_scene_rows(size_t B) { return B * kDims[3] * 4; }
 // one block / one downsample layer (forward.hip), shared by the forward and the per-layer entry points
 // vg: a variable-length batch (acx_forward_varlen) -- B = 1 and H = the stage's total rows then, so that M counts every pixel;
 // only the depthwise conv needs the per-clip tables
-int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, int B, int H, int Wd, hipStream_t st,
-              void* ln_out = nullptr, const VarGeom* vg = nullptr);
+// cap: the bytes y, hidden and stats hold -- the block's tenants are checked against it before anything is launched
+int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, const ScratchCap& cap, int B, int H, int Wd,
+              hipStream_t st, void* ln_out = nullptr, const VarGeom* vg = nullptr);
 // the last block of stage s can write the downsample conv's operand rows (ln_out) instead of x
 bool block_can_emit_ln(const acx_ctx* c, int s);
 // have_ln: xnorm already holds the normalised S16 rows (written by the last block of the previous stage)
@@ -500,8 +537,18 @@ bool block_can_emit_ln(const acx_ctx* c, int s);
 // point keeps fp32)
 // vg: a variable-length batch -- B = 1 and H = the input stage's total rows; the output rows and the gather come from the tables
 // (a clip of odd height drops its last row, as the stride-2 conv does)
-int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, int B, int H, int Wd, hipStream_t st,
-                   bool have_ln = false, bool out_bf16 = false, const VarGeom* vg = nullptr);
+// xnorm_cap: the bytes xnorm holds (kNoCap: unknown to the caller)
+int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, size_t xnorm_cap, int B, int H, int Wd,
+                   hipStream_t st, bool have_ln = false, bool out_bf16 = false, const VarGeom* vg = nullptr);
+// The carve-up of acx_forward_augmented's workspace (augment.hip): the augmented waveform (with a waveform plan), the feature map
+// of all B clips, the mixed map of B / 2 clips (with lambdas), the dense-DFT frontend's frames and spectrum of B clips (dense: a
+// context whose frontend is the dense contraction; need_dense_frames / need_dense_spec), then the workspace of the forward over
+// the clips that remain (fwd bytes from `fwd` on).
+struct AugWs { size_t wave, feat, mix, frames, spec, fwd, total; };
+int carve_augmented(bool dense, int B, int64_t L, bool wave, bool lam, int mode, AugWs* w);
+// its five regions (ACX_PLAN_AUG_WAVE ..) and the tenants of its own frontend (`frames` mel frames), shared by driver and hook
+struct AugFront { acx_plan_region_t regions[5]; int n_tenants; acx_plan_tenant_t tenants[2]; };
+void augmented_front(const AugWs& w, bool dense, size_t frames, AugFront* f);
 // The uniform forward of B clips of L samples with the batch split (acx_forward; arguments checked by the caller).  wstart: the
 // window table of acx_forward_windows / acx_stream_forward, written on `st` by the caller -- clip b's samples start at
 // wav + wstart[b], sub-batch i gets its slice of the table and the whole of wav.  seg: the segment tail instead of `mode`'s.
@@ -509,7 +556,11 @@ int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, 
 // frontend launch is skipped and sub-batch i's stem reads its slice of them.
 struct SegTail;
 int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws, hipStream_t st,
-                    const long long* wstart, const SegTail* seg = nullptr, const float* feat_in = nullptr);
+                    const long long* wstart, const SegTail* seg = nullptr, const float* feat_in = nullptr, bool plans_checked = false);
+// ACX_ERR_STATE when a tenant of the plans forward_uniform would run for this batch (unsplit and split) does not fit its region.
+// Host arithmetic.  forward_uniform calls it first thing; a driver that launches something of its own in front of forward_uniform
+// calls it before that and passes plans_checked = true, so that every plan is checked once and before anything is launched.
+int check_uniform_plans(const acx_ctx* c, int B, int64_t L, int mode, const SegTail* seg, bool feat_in);
 // null pointers / mode / logits-needs-out1, in the entry points' words (forward.hip)
 int check_forward_args(const char* who, const void* wav, const float* out0, const float* out1, const void* ws, int mode);
 

@@ -214,14 +214,18 @@ int acx_block(acx_ctx* c, int stage, int block, float* x, int B, int H, int Wd, 
     float* hidden = (float*)(ws + b.hidden);
     float* stats = (float*)(ws + b.stats);
     if (act_bf16(c, stage)) {
-        // The ABI keeps fp32 tensors; the block itself runs on bf16 activations: x is rounded to bf16 into the (otherwise idle)
-        // hidden scratch, dwconv + fused MLP read and write bf16 there, and the result is widened back into x.
+        // The ABI keeps fp32 tensors; the block itself runs on bf16 activations: x is rounded to bf16 into the hidden scratch
+        // (need_act_bf16; the fused MLP of stages 0-2 puts nothing there: run_block has no tenant of `hidden` without ln_out),
+        // dwconv + fused MLP read and write bf16 there, and the result is widened back into x.
         const long long n = (long long)pix * kDims[stage];
+        if (need_act_bf16(pix, kDims[stage]) > scratch_cap(b).hidden)
+            ACX_FAIL(ACX_ERR_STATE, "acx_block: the bf16 copy of x needs %zu bytes of `hidden`, which holds %zu", need_act_bf16(pix, kDims[stage]),
+                     scratch_cap(b).hidden);
         ACX_TRY(launch_convert_f32_to_bf16(x, hidden, n, (hipStream_t)stream));
-        ACX_TRY(run_block(c, stage, block, hidden, y, hidden, stats, B, H, Wd, (hipStream_t)stream));
+        ACX_TRY(run_block(c, stage, block, hidden, y, hidden, stats, scratch_cap(b), B, H, Wd, (hipStream_t)stream));
         return launch_convert_bf16_to_f32(hidden, x, n, (hipStream_t)stream);
     }
-    return run_block(c, stage, block, x, y, hidden, stats, B, H, Wd, (hipStream_t)stream);
+    return run_block(c, stage, block, x, y, hidden, stats, scratch_cap(b), B, H, Wd, (hipStream_t)stream);
 }
 
 int acx_downsample(acx_ctx* c, int i, const float* x, float* out, float* scratch, int B, int H, int Wd, void* stream) {
@@ -229,7 +233,7 @@ int acx_downsample(acx_ctx* c, int i, const float* x, float* out, float* scratch
     if (i < 1 || i > 3) ACX_FAIL(ACX_ERR_ARG, "acx_downsample: layer index %d (expected 1..3)", i);
     if (!x || !out || !scratch || B <= 0) ACX_FAIL(ACX_ERR_ARG, "acx_downsample: bad argument");
     if (H < 2 || Wd < 2) ACX_FAIL(ACX_ERR_SHAPE, "acx_downsample: kernel size can't be greater than actual input size (%dx%d)", H, Wd);
-    return run_downsample(c, i, x, out, scratch, B, H, Wd, (hipStream_t)stream);
+    return run_downsample(c, i, x, out, scratch, kNoCap, B, H, Wd, (hipStream_t)stream);      // (the ABI passes no size)
 }
 
 int acx_pool_head(acx_ctx* c, const float* x, int B, int H3, float* scene, float* logits, float* probs, void* stream) {
@@ -310,10 +314,11 @@ int acx_test_stage_tail(acx_ctx* c, int stage, float* x, float* out, int B, int 
         xs = (float*)(ws + t.xb);
         ACX_TRY(launch_convert_f32_to_bf16(x, xs, (long long)B * H * Wd * kDims[stage], st));
     }
-    ACX_TRY(run_block(c, stage, last, xs, y, hidden, stats, B, H, Wd, st, have_ln ? (void*)hidden : nullptr));
+    const ScratchCap cap = scratch_cap(t.blk);
+    ACX_TRY(run_block(c, stage, last, xs, y, hidden, stats, cap, B, H, Wd, st, have_ln ? (void*)hidden : nullptr));
     const bool ob = act_bf16(c, stage + 1);
     float* os = ob ? (float*)(ws + t.outb) : out;
-    ACX_TRY(run_downsample(c, stage + 1, xs, os, have_ln ? hidden : y, B, H, Wd, st, have_ln, ob));
+    ACX_TRY(run_downsample(c, stage + 1, xs, os, have_ln ? hidden : y, have_ln ? cap.hidden : cap.y, B, H, Wd, st, have_ln, ob));
     if (ob) return launch_convert_bf16_to_f32(os, out, (long long)B * (H / 2) * (Wd / 2) * kDims[stage + 1], st);
     return ACX_OK;
 }

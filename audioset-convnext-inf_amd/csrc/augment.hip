@@ -165,23 +165,34 @@ static int check_aug_shape(const char* who, int B, int64_t L) {
     return ACX_OK;
 }
 
-// The carve-up of acx_forward_augmented's workspace: the augmented waveform (with a waveform plan), the feature map of all B
-// clips, the mixed map of B / 2 clips (with lambdas), the dense-DFT frontend's scratch for B clips (a context whose frontend is
-// the dense contraction), then the workspace of the forward over the clips that remain.
-struct AugWs { size_t wave, feat, mix, frames, spec, fwd, total; };
-static int carve_augmented(const acx_ctx* c, int B, int64_t L, bool wave, bool lam, int mode, AugWs* w) {
+// (AugWs: acx_internal.h.  The frames and the spectrum own regions here, sized by the tenants' own definitions.)
+int carve_augmented(bool dense, int B, int64_t L, bool wave, bool lam, int mode, AugWs* w) {
     const size_t T = (size_t)(L / kHop + 1);
     size_t off = 0;
     w->wave = off; if (wave) off += align_up((size_t)B * L * 4);
     w->feat = off; off += align_up((size_t)B * T * kMels * 4);
     w->mix = off; if (lam) off += align_up((size_t)(B / 2) * T * kMels * 4);
-    w->frames = off; if (c->dense_stft) off += align_up((size_t)B * T * kNFFT * 4);
-    w->spec = off; if (c->dense_stft) off += align_up((size_t)B * T * kDenseN * 4);
+    w->frames = off; if (dense) off += align_up(need_dense_frames((size_t)B * T));
+    w->spec = off; if (dense) off += align_up(need_dense_spec((size_t)B * T));
     size_t fwd = 0;
-    ACX_TRY(acx_workspace_bytes(c, lam ? B / 2 : B, L, mode, &fwd));
+    ACX_TRY(acx_workspace_bytes(nullptr, lam ? B / 2 : B, L, mode, &fwd));       // (it reads no context)
     w->fwd = off;
     w->total = off + fwd;
     return ACX_OK;
+}
+
+// What acx_forward_augmented puts in front of the nested forward, as data: its five regions (wave, feat, mix, frames, spectrum) and
+// the two tenants of its own frontend.  The driver takes the frames and spectrum pointers from here, acx_test_forward_plan reports it.
+void augmented_front(const AugWs& w, bool dense, size_t frames, AugFront* f) {
+    const size_t cut[6] = {w.wave, w.feat, w.mix, w.frames, w.spec, w.fwd};
+    for (int i = 0; i < 5; ++i) f->regions[i] = acx_plan_region_t{cut[i], cut[i + 1] - cut[i]};
+    f->n_tenants = 0;
+    if (!dense) return;
+    const uint32_t ops = (1u << ACX_PLAN_AUG_WAVE) | (1u << ACX_PLAN_AUG_FEAT);
+    f->tenants[f->n_tenants++] = acx_plan_tenant_t{ACX_PLAN_DENSE_FRAMES, ACX_PLAN_AUG_FRAMES, ACX_PLAN_PHASE_FRONTEND, -1, -1, ops, 0,
+                                                   need_dense_frames(frames)};
+    f->tenants[f->n_tenants++] = acx_plan_tenant_t{ACX_PLAN_DENSE_SPEC, ACX_PLAN_AUG_SPEC, ACX_PLAN_PHASE_FRONTEND, -1, -1, ops, 0,
+                                                   need_dense_spec(frames)};
 }
 
 static int check_augmented_shape(const char* who, int B, int64_t L, bool lam, int mode) {
@@ -259,7 +270,7 @@ int acx_workspace_bytes_augmented(const acx_ctx* c, int B, int64_t L, int has_wa
     ACX_TRY(check_augmented_shape("acx_workspace_bytes_augmented", B, L, has_lambda != 0, mode));
     ACX_TRY(need_ready(c));
     AugWs w;
-    ACX_TRY(carve_augmented(c, B, L, has_wave_plan != 0, has_lambda != 0, mode, &w));
+    ACX_TRY(carve_augmented(c->dense_stft, B, L, has_wave_plan != 0, has_lambda != 0, mode, &w));
     *out_bytes = w.total;
     return ACX_OK;
 }
@@ -271,8 +282,9 @@ int acx_forward_augmented(acx_ctx* c, const float* wav, int B, int64_t L, const 
     ACX_TRY(check_augmented_shape("acx_forward_augmented", B, L, lambda != nullptr, mode));
     ACX_TRY(need_ready(c));
     AugWs w;
-    ACX_TRY(carve_augmented(c, B, L, wave_plan != nullptr, lambda != nullptr, mode, &w));
+    ACX_TRY(carve_augmented(c->dense_stft, B, L, wave_plan != nullptr, lambda != nullptr, mode, &w));
     ACX_TRY(check_workspace(workspace, workspace_bytes, w.total));
+    ACX_TRY(check_uniform_plans(c, lambda ? B / 2 : B, L, mode, nullptr, true));       // (before the first launch)
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int T = (int)(L / kHop + 1);
@@ -283,8 +295,16 @@ int acx_forward_augmented(acx_ctx* c, const float* wav, int B, int64_t L, const 
         x = aug;
     }
     float* feat = (float*)(ws + w.feat);
-    ACX_TRY(launch_logmel(c, x, B, L, T, feat, true, st, c->dense_stft ? (float*)(ws + w.frames) : nullptr,
-                          c->dense_stft ? (float*)(ws + w.spec) : nullptr));
+    AugFront front;
+    augmented_front(w, c->dense_stft, (size_t)B * T, &front);
+    auto lies = [&](int kind) -> float* {          // (null without the dense frontend: the FFT frontend needs no scratch)
+        for (int i = 0; i < front.n_tenants; ++i) {
+            const acx_plan_tenant_t& t = front.tenants[i];
+            if (t.kind == kind) return (float*)(ws + front.regions[t.region - ACX_PLAN_AUG_WAVE].offset + t.offset);
+        }
+        return nullptr;
+    };
+    ACX_TRY(launch_logmel(c, x, B, L, T, feat, true, st, lies(ACX_PLAN_DENSE_FRAMES), lies(ACX_PLAN_DENSE_SPEC)));
     int Bf = B;
     if (lambda) {
         float* mix = (float*)(ws + w.mix);
@@ -295,7 +315,7 @@ int acx_forward_augmented(acx_ctx* c, const float* wav, int B, int64_t L, const 
         ACX_TRY(launch_augment_spec(feat, B, T, spec_plan, nullptr, feat, st));
     }
     // everything above is queued on `st` in front of the fork event of the batch split: every sub-batch sees the finished rows
-    return forward_uniform(c, nullptr, Bf, L, mode, out0, out1, ws + w.fwd, st, nullptr, nullptr, feat);
+    return forward_uniform(c, nullptr, Bf, L, mode, out0, out1, ws + w.fwd, st, nullptr, nullptr, feat, true);
 }
 
 }  // extern "C"

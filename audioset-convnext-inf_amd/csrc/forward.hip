@@ -25,6 +25,118 @@ struct Plan {          // the geometry of one forward and its workspace carve-up
     size_t total;
 };
 
+// ---- the plan as data ------------------------------------------------------------------------------------------------------------
+// What a plan depends on beside its geometry: the context's settings in a forward, the query's in acx_test_forward_plan.
+struct PlanEnv { int precision; bool dense, tiled_head; };
+
+// One tenant: `need` bytes from byte `offset` of region `region` (ACX_PLAN_*), used in one phase of the forward; operands: the
+// regions (bit r = region r) that phase reads or writes in their own role while the tenant is live.
+struct Tenant { int kind, region, phase, stage, block; unsigned operands; size_t offset, need; };
+struct TenantList {
+    int n = 0;
+    Tenant t[ACX_PLAN_MAX_TENANTS];
+    void add(int kind, int region, int phase, int stage, int block, unsigned operands, size_t offset, size_t need) {
+        if (n < ACX_PLAN_MAX_TENANTS) t[n] = Tenant{kind, region, phase, stage, block, operands, offset, need};
+        ++n;                            // (an overflow is reported by whoever reads the list)
+    }
+};
+
+static const char* const kTenantNames[ACX_PLAN_TENANT_KINDS] = {
+    "dense frames", "dense spectrum", "LayerNorm rows", "bf16 hidden activation", "bf16 LayerNorm rows of the MLP",
+    "hidden activation", "LayerNorm statistics", "downsample xnorm", "segment embeddings", "scene rows"};
+static const char* const kRegionNames[ACX_PLAN_REGIONS] = {
+    "tables", "feat", "x0", "x1", "x2", "x3", "y", "hidden", "stats", "augmented wave", "augmented feat", "augmented mix",
+    "augmented frames", "augmented spectrum"};
+
+static constexpr unsigned region_bit(int r) { return 1u << r; }
+
+// the tail of a forward as one number: enum acx_mode, then ACX_PLAN_TAIL_SEG_OUTPUT / _SEG_EMBED
+static int tail_of(int mode, const SegTail* seg);
+
+// Every tenant of the forward of geometry g, in launch order.  run_forward lends exactly these: the pointers it passes on are
+// region start + offset of the entries here, and it refuses a plan in which one does not fit.
+static void forward_tenants(const PlanEnv& e, const Geom& g, int tail, bool feat_in, TenantList* l) {
+    l->n = 0;
+    const unsigned tab = region_bit(ACX_PLAN_TABLES);
+    const size_t Bp = g.vg ? 1 : (size_t)g.B;             // (a variable-length batch: T and Hs are the sums over its clips)
+    if (e.dense && !feat_in) {
+        const unsigned ops = tab | region_bit(ACX_PLAN_FEAT);
+        l->add(ACX_PLAN_DENSE_FRAMES, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_FRONTEND, -1, -1, ops, 0, need_dense_frames(Bp * g.T));
+        l->add(ACX_PLAN_DENSE_SPEC, ACX_PLAN_Y, ACX_PLAN_PHASE_FRONTEND, -1, -1, ops, 0, need_dense_spec(Bp * g.T));
+    }
+    for (int s = 0; s < 4; ++s) {
+        const int C = kDims[s];
+        const size_t M = Bp * g.Hs[s] * (kStemW >> s);
+        if (s > 0) {
+            const size_t Min = Bp * g.Hs[s - 1] * (kStemW >> (s - 1));
+            const unsigned ops = tab | region_bit(ACX_PLAN_X0 + s - 1) | region_bit(ACX_PLAN_X0 + s);
+            if (e.precision != ACX_PREC_F32)
+                l->add(ACX_PLAN_LN_ROWS, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_DOWNSAMPLE, s, -1, ops, 0, need_ln_rows(e.precision, Min, kDims[s - 1]));
+            else
+                l->add(ACX_PLAN_XNORM, ACX_PLAN_Y, ACX_PLAN_PHASE_DOWNSAMPLE, s, -1, ops, 0, need_xnorm(e.precision, Min, kDims[s - 1]));
+        }
+        for (int j = 0; j < kDepths[s]; ++j) {
+            const unsigned ops = tab | region_bit(ACX_PLAN_X0 + s) | region_bit(ACX_PLAN_Y);
+            const bool last = j == kDepths[s] - 1 && s < 3;
+            if (e.precision == ACX_PREC_F32) {
+                if (mlp_fused_supported(C)) continue;
+                l->add(ACX_PLAN_HIDDEN_ACT, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_BLOCK, s, j, ops, 0, need_hidden_act(M, C));
+                l->add(ACX_PLAN_ROW_STATS, ACX_PLAN_STATS, ACX_PLAN_PHASE_BLOCK, s, j, ops, 0, need_row_stats(M));
+            } else if (e.precision == ACX_PREC_F32_SPLIT) {
+                if (mlp_fused_split_supported(C) || mlp_fused_wide_supported(C)) {
+                    if (last) l->add(ACX_PLAN_LN_ROWS, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_BLOCK, s, j, ops, 0, need_ln_rows(e.precision, M, C));
+                } else {
+                    l->add(ACX_PLAN_HIDDEN_ACT, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_BLOCK, s, j, ops, 0, need_hidden_act(M, C));
+                }
+            } else if (mlp_fused_wide_bf16_supported(C)) {
+                if (last) l->add(ACX_PLAN_LN_ROWS, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_BLOCK, s, j, ops, 0, need_ln_rows(e.precision, M, C));
+            } else {
+                l->add(ACX_PLAN_MLP_BF16_HIDDEN, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_BLOCK, s, j, ops, 0, need_mlp_bf16_hidden(M, C));
+                l->add(ACX_PLAN_MLP_BF16_ROWS, ACX_PLAN_HIDDEN, ACX_PLAN_PHASE_BLOCK, s, j, ops, mlp_bf16_rows_offset(M, C),
+                       need_mlp_bf16_rows(M, C));
+            }
+        }
+    }
+    const unsigned ops = tab | region_bit(ACX_PLAN_X0 + 3);
+    if (tail == ACX_PLAN_TAIL_SEG_OUTPUT)
+        l->add(ACX_PLAN_SEGMENT_EMB, ACX_PLAN_FEAT, ACX_PLAN_PHASE_TAIL, -1, -1, ops, 0, need_segment_emb(Bp * g.Hs[3]));
+    else if (tail == ACX_MODE_LOGITS && e.tiled_head)
+        l->add(ACX_PLAN_SCENE_ROWS, ACX_PLAN_FEAT, ACX_PLAN_PHASE_TAIL, -1, -1, ops, 0, need_scene_rows((size_t)g.B));
+}
+
+// The regions of plan p as (offset, bytes): a region holds everything up to the next one's first byte.  `base`: where the plan's
+// byte 0 lies in what is reported; tables: the bytes in front of feat (the tables of a variable-length batch).
+static void plan_regions(const Plan& p, size_t base, size_t tables, acx_plan_region_t* r) {
+    for (int i = 0; i < ACX_PLAN_REGIONS; ++i) r[i] = acx_plan_region_t{0, 0};
+    r[ACX_PLAN_TABLES] = acx_plan_region_t{base, tables};
+    const size_t cut[8] = {p.off_feat, p.off_x[0], p.off_x[1], p.off_x[2], p.off_x[3], p.scr.y, p.scr.hidden, p.scr.stats};
+    for (int i = 0; i < 8; ++i) r[ACX_PLAN_FEAT + i] = acx_plan_region_t{base + cut[i], (i < 7 ? cut[i + 1] : p.scr.end) - cut[i]};
+}
+
+// ACX_ERR_STATE when a tenant of plan p does not fit the region it is lent.  Host arithmetic, before the first launch.
+static int check_tenants(const Plan& p, const TenantList& l) {
+    if (l.n > ACX_PLAN_MAX_TENANTS) ACX_FAIL(ACX_ERR_STATE, "workspace plan: %d tenants (at most %d)", l.n, ACX_PLAN_MAX_TENANTS);
+    acx_plan_region_t r[ACX_PLAN_REGIONS];
+    plan_regions(p, 0, p.off_feat, r);
+    for (int i = 0; i < l.n; ++i) {
+        const Tenant& t = l.t[i];
+        if (t.offset + t.need > r[t.region].bytes)
+            ACX_FAIL(ACX_ERR_STATE,
+                     "workspace plan: the %s (stage %d, block %d) need %zu bytes from byte %zu of `%s`, which holds %zu "
+                     "(%d clips, %d frames, rows %d / %d / %d / %d)", kTenantNames[t.kind], t.stage, t.block, t.need, t.offset,
+                     kRegionNames[t.region], (size_t)r[t.region].bytes, p.g.B, p.g.T, p.g.Hs[0], p.g.Hs[1], p.g.Hs[2], p.g.Hs[3]);
+    }
+    return ACX_OK;
+}
+
+// one tenant against the capacity its caller states (run_block, run_downsample: also reached from the per-layer entry points)
+static int tenant_fits(int kind, const char* region, size_t offset, size_t need, size_t cap, int64_t M, int C) {
+    if (cap != kNoCap && offset + need > cap)
+        ACX_FAIL(ACX_ERR_STATE, "workspace plan: the %s need %zu bytes from byte %zu of `%s`, which holds %zu (%lld pixels of %d channels)",
+                 kTenantNames[kind], need, offset, region, cap, (long long)M, C);
+    return ACX_OK;
+}
+
 // frames mel frames and rows[s] image rows at stage s in all, from byte `off` of the workspace on; the block scratch is stage 0's
 static void carve_workspace(size_t frames, const size_t rows[4], size_t off, Plan* p) {
     p->off_feat = off; off += align_up(frames * kMels * 4);
@@ -78,12 +190,14 @@ int check_workspace_for(const char* who, const void* ptr, size_t bytes, size_t n
 }
 
 // bf16 precision: y -> fp32 LayerNorm -> bf16 rows; pwconv1 + GELU -> bf16 hidden; pwconv2 + residual -> fp32 x.
-// Both bf16 arrays live in the `hidden` scratch (sized for the fp32 hidden activation): [M][4C] then [M][Cp].
-static int run_mlp_bf16(acx_ctx* c, const BlockW& bw, int C, const float* y, float* x, float* hidden, int64_t M,
+// Both bf16 arrays live in the `hidden` scratch: need_mlp_bf16_hidden at its head, need_mlp_bf16_rows from mlp_bf16_rows_offset on.
+static int run_mlp_bf16(acx_ctx* c, const BlockW& bw, int C, const float* y, float* x, float* hidden, size_t hidden_cap, int64_t M,
                         hipStream_t st) {
     const int Cp = pad64(C);
+    ACX_TRY(tenant_fits(ACX_PLAN_MLP_BF16_HIDDEN, "hidden", 0, need_mlp_bf16_hidden((size_t)M, C), hidden_cap, M, C));
+    ACX_TRY(tenant_fits(ACX_PLAN_MLP_BF16_ROWS, "hidden", mlp_bf16_rows_offset((size_t)M, C), need_mlp_bf16_rows((size_t)M, C), hidden_cap, M, C));
     char* hb = reinterpret_cast<char*>(hidden);
-    char* yb = hb + align_up((size_t)M * 4 * C * 2);
+    char* yb = hb + mlp_bf16_rows_offset((size_t)M, C);
     ACX_TRY(launch_layernorm_rows_bf16(c, y, yb, M, C, st));
     GemmBf16Args g1{};
     g1.A = yb; g1.Wt = bw.w1h; g1.bias = bw.b1; g1.out = hb; g1.M = M; g1.N = 4 * C; g1.Kp = Cp; g1.lda = Cp;
@@ -97,8 +211,9 @@ static int run_mlp_bf16(acx_ctx* c, const BlockW& bw, int C, const float* y, flo
 
 // split precision: y -> fp32 LayerNorm -> S16 rows IN PLACE (row-local); pwconv1 + GELU -> S16 hidden;
 // pwconv2 + residual -> fp32 x.  Same bytes per element as the fp32 path.
-static int run_mlp_split(acx_ctx* c, const BlockW& bw, int C, float* y, float* x, float* hidden, int64_t M,
+static int run_mlp_split(acx_ctx* c, const BlockW& bw, int C, float* y, float* x, float* hidden, size_t hidden_cap, int64_t M,
                          hipStream_t st) {
+    ACX_TRY(tenant_fits(ACX_PLAN_HIDDEN_ACT, "hidden", 0, need_hidden_act((size_t)M, C), hidden_cap, M, C));
     ACX_TRY(launch_layernorm_rows_split(c, y, y, M, C, st));
     GemmSplitArgs g1{};
     g1.A = y; g1.Wt = bw.w1s; g1.bias = bw.b1; g1.out = hidden; g1.M = M; g1.N = 4 * C; g1.K = C;
@@ -114,11 +229,13 @@ static int run_mlp_split(acx_ctx* c, const BlockW& bw, int C, float* y, float* x
 // MLP kernels of stages 0-2 in the 16-bit arithmetics (LNOUT epilogue).  x of that stage is then NOT updated by its last block.
 bool block_can_emit_ln(const acx_ctx* c, int s) { return s < 3 && c->precision != ACX_PREC_F32; }
 
-int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, int B, int H, int Wd, hipStream_t st,
-              void* ln_out, const VarGeom* vg) {
+int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float* stats, const ScratchCap& cap, int B, int H, int Wd,
+              hipStream_t st, void* ln_out, const VarGeom* vg) {
     const int C = kDims[s];
     const BlockW& bw = c->blocks[s][j];
     const int64_t M = (int64_t)B * H * Wd;
+    // (ln_out is the head of `hidden` in every caller)
+    if (ln_out) ACX_TRY(tenant_fits(ACX_PLAN_LN_ROWS, "hidden", 0, need_ln_rows(c->precision, (size_t)M, C), cap.hidden, M, C));
     auto launch_dw = [&](float* row_stats, bool ab) {
         if (vg) return launch_dwconv_varlen(c, bw, C, x, y, row_stats, *vg, s, st, ab);
         return launch_dwconv(c, bw, C, x, y, row_stats, B, H, Wd, st, ab);
@@ -129,6 +246,8 @@ int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float
                 ACX_TRY(launch_dw(nullptr, false));      // LN statistics are computed in-kernel
                 return launch_mlp_fused(c, bw, C, y, x, M, st);
             }
+            ACX_TRY(tenant_fits(ACX_PLAN_HIDDEN_ACT, "hidden", 0, need_hidden_act((size_t)M, C), cap.hidden, M, C));
+            ACX_TRY(tenant_fits(ACX_PLAN_ROW_STATS, "stats", 0, need_row_stats((size_t)M), cap.stats, M, C));
             ACX_TRY(launch_dw(stats, false));
             GemmArgs g1{};
             g1.A = y; g1.Wt = bw.w1; g1.bias = bw.b1; g1.out = hidden; g1.stats = stats; g1.colsum = bw.w1sum; g1.M = M; g1.N = 4 * C; g1.K = C;
@@ -144,21 +263,26 @@ int run_block(acx_ctx* c, int s, int j, float* x, float* y, float* hidden, float
             if (mlp_fused_split_supported(C)) return launch_mlp_fused_split(c, bw, C, y, x, M, st, ln_out);
             if (mlp_fused_wide_supported(C)) return launch_mlp_fused_wide(c, bw, C, y, x, M, st, ln_out);
             if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
-            return run_mlp_split(c, bw, C, y, x, hidden, M, st);
+            return run_mlp_split(c, bw, C, y, x, hidden, cap.hidden, M, st);
         default: {                                                              // bf16, bf16a
             const bool ab = act_bf16(c, s);         // x and y of this stage are bf16 tensors in HBM
             ACX_TRY(launch_dw(nullptr, ab));
             if (mlp_fused_wide_bf16_supported(C)) return launch_mlp_fused_wide_bf16(c, bw, C, y, x, M, st, ln_out, pad64(C), ab);
             if (ln_out) ACX_FAIL(ACX_ERR_STATE, "run_block: LayerNorm output requested from a two-GEMM stage");
-            return run_mlp_bf16(c, bw, C, y, x, hidden, M, st);
+            return run_mlp_bf16(c, bw, C, y, x, hidden, cap.hidden, M, st);
         }
     }
 }
 
-int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, int B, int H, int Wd, hipStream_t st,
-                   bool have_ln, bool out_bf16, const VarGeom* vg) {
+int run_downsample(acx_ctx* c, int i, const float* x, float* out, float* xnorm, size_t xnorm_cap, int B, int H, int Wd,
+                   hipStream_t st, bool have_ln, bool out_bf16, const VarGeom* vg) {
     const int Ci = kDims[i - 1], Co = kDims[i];
     const DownW& d = c->down[i];
+    {
+        const int64_t Min = (int64_t)B * H * Wd;
+        if (have_ln) ACX_TRY(tenant_fits(ACX_PLAN_LN_ROWS, "hidden", 0, need_ln_rows(c->precision, (size_t)Min, Ci), xnorm_cap, Min, Ci));
+        else ACX_TRY(tenant_fits(ACX_PLAN_XNORM, "y", 0, need_xnorm(c->precision, (size_t)Min, Ci), xnorm_cap, Min, Ci));
+    }
     const int* irow = vg ? vg->irow[i] : nullptr;
     const int64_t Mout = vg ? (int64_t)vg->rows[i] * (Wd / 2) : (int64_t)B * (H / 2) * (Wd / 2);
     switch (c->precision) {
@@ -290,14 +414,41 @@ struct SegTail {
     float* clip;        // ACX_SEG_OUTPUT: (clips, N) maximum over segments, or null
 };
 
-// ACX_SEG_EMBED: the segment embeddings go straight to out0.  ACX_SEG_OUTPUT: they go to `feat` (idle since the stem; 768 S <=
-// 24 (T + 8) <= 224 T floats per clip), the head reads them there.  roff3 / maxS: a variable-length batch (B clips, rows rows).
+static int tail_of(int mode, const SegTail* seg) {
+    if (!seg) return mode;
+    return seg->what == ACX_SEG_EMBED ? ACX_PLAN_TAIL_SEG_EMBED : ACX_PLAN_TAIL_SEG_OUTPUT;
+}
+
+// ACX_SEG_EMBED: the segment embeddings go straight to out0.  ACX_SEG_OUTPUT: they go to `feat` (idle since the stem; the tenant
+// ACX_PLAN_SEGMENT_EMB, need_segment_emb), the head reads them there.  roff3 / maxS: a variable-length batch (B clips, rows rows).
 static int run_segment_tail(acx_ctx* c, const SegTail& sg, const float* x3, int B, int S, long long rows, float* feat, float* out0,
                             float* out1, const int* roff3, int maxS, hipStream_t st) {
     if (sg.what == ACX_SEG_EMBED) return launch_segment_pool(c, x3, B, S, sg.pool, out0, roff3, maxS, st);
     ACX_TRY(launch_segment_pool(c, x3, B, S, sg.pool, feat, roff3, maxS, st));
     ACX_TRY(launch_segment_head(c, feat, rows, out0, out1, st));
     if (sg.clip) return launch_segment_clipmax(out1, B, S, c->num_classes, sg.clip, roff3, st);
+    return ACX_OK;
+}
+
+// The tenants of plan p under context c against their regions (check_tenants).  Every plan is checked ONCE, by its driver and before
+// that driver launches anything: forward_varlen_impl for its packed plan, forward_uniform for the unsplit and the split plans --
+// unless its caller launches something of its own first (window table, stream table, the augmentations) and therefore has called
+// check_uniform_plans already (plans_checked).  run_forward takes its pointers from the list and checks nothing again.
+static int check_plan(const acx_ctx* c, const Plan& p, int mode, const SegTail* seg, bool feat_in) {
+    const PlanEnv env{c->precision, c->dense_stft, head_tiled(c)};
+    TenantList tl;
+    forward_tenants(env, p.g, tail_of(mode, seg), feat_in, &tl);
+    return check_tenants(p, tl);
+}
+int check_uniform_plans(const acx_ctx* c, int B, int64_t L, int mode, const SegTail* seg, bool feat_in) {
+    Plan p;
+    ACX_TRY(make_plan(B, L, &p));                   // (the unsplit plan too: a split falls back to it inside a stream capture)
+    ACX_TRY(check_plan(c, p, mode, seg, feat_in));
+    const int ways = split_ways_for(c, B);
+    for (int i = 0; ways > 1 && i < ways; ++i) {
+        ACX_TRY(make_plan(split_part(B, ways, i), L, &p));
+        ACX_TRY(check_plan(c, p, mode, seg, feat_in));
+    }
     return ACX_OK;
 }
 
@@ -317,30 +468,55 @@ static int run_forward(acx_ctx* c, const float* wav, const Plan& p, int mode, fl
     float* hidden = (float*)(ws + p.scr.hidden);
     float* stats = (float*)(ws + p.scr.stats);
     const int Bp = vg ? 1 : g.B;            // batch of the pointwise launches
+    const ScratchCap cap = scratch_cap(p.scr);
 
-    // (dense-DFT fallback: frames in `hidden`, spectrum in `y` -- both idle until the first block, both large enough:
-    // T * 4096 <= H0 * 86016 and T * 4 kDenseN <= H0 * 21504 bytes per clip with H0 >= (T + 1) / 4; the per-clip bounds hold
-    // for the sums of a variable-length batch)
+    // feat, y, hidden and stats are carved for the stem and for stage 0 and then lent to tenants they were not sized for
+    // (forward_tenants lists them; their needs are the need_* definitions of acx_internal.h).  Whether each fits was checked by the
+    // driver before anything was launched (check_plan), and over every shape by tests/test_forward_plan_cpu.py through
+    // acx_test_forward_plan; here the list says where each one lies.
+    const PlanEnv env{c->precision, c->dense_stft, head_tiled(c)};
+    TenantList tl;
+    forward_tenants(env, g, tail_of(mode, seg), feat_in != nullptr, &tl);
+    acx_plan_region_t reg[ACX_PLAN_REGIONS];
+    plan_regions(p, 0, p.off_feat, reg);
+    // where the plan puts a tenant (null: this forward has no such tenant) -- the pointers below come from the list that was checked
+    auto at = [&](int kind, int phase, int stage, int block) -> float* {
+        for (int i = 0; i < tl.n; ++i) {
+            const Tenant& t = tl.t[i];
+            if (t.kind == kind && t.phase == phase && t.stage == stage && t.block == block)
+                return (float*)(ws + reg[t.region].offset + t.offset);
+        }
+        return nullptr;
+    };
+    float* dense_frames = at(ACX_PLAN_DENSE_FRAMES, ACX_PLAN_PHASE_FRONTEND, -1, -1);
+    float* dense_spec = at(ACX_PLAN_DENSE_SPEC, ACX_PLAN_PHASE_FRONTEND, -1, -1);
+    // (the launchers want scratch pointers whatever the frontend: they are read by the dense-DFT frontend only)
+    if (!dense_frames) dense_frames = hidden;
+    if (!dense_spec) dense_spec = y;
+    // (dense-DFT fallback: frames in `hidden`, spectrum in `y`, both idle until the first block -- ACX_PLAN_DENSE_FRAMES / _SPEC)
     if (vg) {
-        ACX_TRY(launch_logmel_varlen(c, wav, *vg, feat, st, hidden, y));
+        ACX_TRY(launch_logmel_varlen(c, wav, *vg, feat, st, dense_frames, dense_spec));
         ACX_TRY(launch_stem_varlen(c, feat, *vg, x[0], st, act_bf16(c, 0)));
     } else {
-        if (!feat_in) ACX_TRY(launch_logmel(c, wav, g.B, g.L, g.T, feat, true, st, hidden, y, g.wstart));
+        if (!feat_in) ACX_TRY(launch_logmel(c, wav, g.B, g.L, g.T, feat, true, st, dense_frames, dense_spec, g.wstart));
         ACX_TRY(launch_stem(c, feat_in ? feat_in : feat, g.B, g.T, g.Hs[0], x[0], st, act_bf16(c, 0)));
     }
     for (int s = 0; s < 4; ++s) {
         const int Wd = kStemW >> s;
         // The last block of stages 0-2 writes LayerNorm(x) as GEMM operand rows (S16 / bf16) instead of x: nothing else
-        // reads that x (convnext.py:270-273).  The rows go to the `hidden` scratch (idle in the fused stages), never to
-        // y: the block kernel reads y -- with a tile of look-ahead -- while it writes them, and bf16 rows are shorter
-        // than the fp32 rows they would overwrite.
+        // reads that x (convnext.py:270-273).  The rows go to the `hidden` scratch (idle in the fused stages; the tenant
+        // ACX_PLAN_LN_ROWS, need_ln_rows), never to y: the block kernel reads y -- with a tile of look-ahead -- while it
+        // writes them, and bf16 rows are shorter than the fp32 rows they would overwrite.  Without them (fp32) the
+        // downsample normalises x into y (ACX_PLAN_XNORM, need_xnorm).
         if (s > 0) {
             const bool have_ln = block_can_emit_ln(c, s - 1);
-            ACX_TRY(run_downsample(c, s, x[s - 1], x[s], have_ln ? hidden : y, Bp, g.Hs[s - 1], Wd * 2, st, have_ln, act_bf16(c, s), vg));
+            float* xnorm = at(have_ln ? ACX_PLAN_LN_ROWS : ACX_PLAN_XNORM, ACX_PLAN_PHASE_DOWNSAMPLE, s, -1);
+            ACX_TRY(run_downsample(c, s, x[s - 1], x[s], xnorm, have_ln ? cap.hidden : cap.y, Bp, g.Hs[s - 1], Wd * 2, st, have_ln,
+                                   act_bf16(c, s), vg));
         }
         for (int j = 0; j < kDepths[s]; ++j) {
-            void* ln_out = (j == kDepths[s] - 1 && block_can_emit_ln(c, s)) ? (void*)hidden : nullptr;
-            ACX_TRY(run_block(c, s, j, x[s], y, hidden, stats, Bp, g.Hs[s], Wd, st, ln_out, vg));
+            void* ln_out = (j == kDepths[s] - 1 && block_can_emit_ln(c, s)) ? (void*)at(ACX_PLAN_LN_ROWS, ACX_PLAN_PHASE_BLOCK, s, j) : nullptr;
+            ACX_TRY(run_block(c, s, j, x[s], y, hidden, stats, cap, Bp, g.Hs[s], Wd, st, ln_out, vg));
         }
     }
     const int H3 = g.Hs[3];
@@ -349,28 +525,31 @@ static int run_forward(acx_ctx* c, const float* wav, const Plan& p, int mode, fl
         return launch_pool_head(c, x[3], g.B, H3, scene, logits, probs, st);
     };
     if (seg) {
-        if (vg) return run_segment_tail(c, *seg, x[3], g.B, 0, H3, feat, out0, out1, vg->roff[3], vg->maxH[3], st);
-        return run_segment_tail(c, *seg, x[3], g.B, H3, (long long)g.B * H3, feat, out0, out1, nullptr, H3, st);
+        float* emb = at(ACX_PLAN_SEGMENT_EMB, ACX_PLAN_PHASE_TAIL, -1, -1);           // (null with ACX_SEG_EMBED: not used then)
+        if (vg) return run_segment_tail(c, *seg, x[3], g.B, 0, H3, emb, out0, out1, vg->roff[3], vg->maxH[3], st);
+        return run_segment_tail(c, *seg, x[3], g.B, H3, (long long)g.B * H3, emb, out0, out1, nullptr, H3, st);
     }
     if (mode == ACX_MODE_FRAME) {
         if (vg) return launch_nhwc_to_nchw_varlen(c, x[3], out0, *vg, st);
         return launch_nhwc_to_nchw(c, x[3], out0, g.B, H3, kStemW >> 3, kDims[3], st);
     }
     if (mode == ACX_MODE_SCENE) return pool_head(out0, nullptr, nullptr);
-    if (head_tiled(c)) {       // wide head: scene rows into `feat` (idle since the stem, >= 24 x 224 floats per clip), then the head
-        ACX_TRY(pool_head(feat, nullptr, nullptr));
-        return launch_head_tiled(c, feat, g.B, out0, out1, st);
+    if (env.tiled_head) {       // wide head: scene rows into `feat` (idle since the stem; ACX_PLAN_SCENE_ROWS, need_scene_rows), then the head
+        float* scene = at(ACX_PLAN_SCENE_ROWS, ACX_PLAN_PHASE_TAIL, -1, -1);
+        ACX_TRY(pool_head(scene, nullptr, nullptr));
+        return launch_head_tiled(c, scene, g.B, out0, out1, st);
     }
     return pool_head(nullptr, out0, out1);
 }
 
 int forward_uniform(acx_ctx* c, const float* wav, int B, int64_t L, int mode, float* out0, float* out1, char* ws, hipStream_t st,
-                    const long long* wstart, const SegTail* seg, const float* feat_in) {
+                    const long long* wstart, const SegTail* seg, const float* feat_in, bool plans_checked) {
     // Clips are independent: a large batch runs as sub-batches on separate streams (fork/join with events, so the call
     // still looks like one unit of work on `stream` and stays graph-capturable).  Per-kernel event profiling runs
     // un-split to keep launch durations clean.  The kernels of the 16-bit arithmetics are CU-exclusive -- nothing
     // shares a CU with them -- but a second stream's workgroups take the CUs their tail rounds and launch boundaries
     // leave idle: +4 % (fp32_split) / +11 % (bf16a) at B = 64.
+    if (!plans_checked) ACX_TRY(check_uniform_plans(c, B, L, mode, seg, feat_in != nullptr));
     const int ways = split_ways_for(c, B);
     acx_ctx::Aux aux;
     bool have_aux = false;
@@ -468,11 +647,13 @@ static int forward_windows_impl(acx_ctx* c, const float* wav, const int64_t* len
     size_t need = 0;
     ACX_TRY(acx_workspace_bytes_windows(c, count, window, mode, &need));
     ACX_TRY(check_workspace(workspace, workspace_bytes, need));
+    ACX_TRY(check_uniform_plans(c, count, window, mode, seg, false));
     hipStream_t st = (hipStream_t)stream;
     long long* wstart = (long long*)workspace;
     // on the caller's stream, before forward_uniform records the fork event: every sub-batch reads its slice after it
     ACX_TRY(launch_window_table(lengths, R, window, hop, first, count, wstart, st));
-    return forward_uniform(c, wav, count, window, mode, out0, out1, (char*)workspace + align_up((size_t)count * 8), st, wstart, seg);
+    return forward_uniform(c, wav, count, window, mode, out0, out1, (char*)workspace + align_up((size_t)count * 8), st, wstart, seg,
+                           nullptr, true);
 }
 
 static int forward_varlen_impl(acx_ctx* c, const float* wav, const int64_t* lengths, int B, int mode, float* out0, float* out1,
@@ -482,6 +663,7 @@ static int forward_varlen_impl(acx_ctx* c, const float* wav, const int64_t* leng
     Plan p;
     ACX_TRY(make_plan_varlen(lengths, B, (char*)workspace, &vg, &p));
     ACX_TRY(check_workspace(workspace, workspace_bytes, p.total));
+    ACX_TRY(check_plan(c, p, mode, seg, false));
     ACX_TRY(launch_varlen_tables(lengths, vg, (hipStream_t)stream));
     return run_forward(c, wav, p, mode, out0, out1, (char*)workspace, (hipStream_t)stream, seg);
 }
@@ -696,6 +878,91 @@ int acx_segment_timeline(const float* probs, int classes, const int64_t* lengths
             ACX_FAIL(ACX_ERR_SHAPE, "acx_segment_timeline: recording %d of %lld samples is shorter than the %d a clip needs", r,
                      (long long)lengths[r], ACX_MIN_SAMPLES);
     return launch_segment_timeline(probs, classes, lengths, R, window, hop, reduce, out, (hipStream_t)stream);
+}
+
+// ---- test support: the plan as data ------------------------------------------------------------------------------------------
+static void export_sub(const Plan& p, size_t base, size_t tables, const TenantList& l, acx_plan_sub_t* out) {
+    out->clips = p.g.B;
+    out->base = base;
+    out->bytes = p.total;
+    plan_regions(p, base, tables, out->regions);
+    out->n_tenants = l.n;
+    for (int i = 0; i < l.n; ++i) {
+        const Tenant& t = l.t[i];
+        out->tenants[i] = acx_plan_tenant_t{t.kind, t.region, t.phase, t.stage, t.block, t.operands, t.offset, t.need};
+    }
+}
+
+int acx_test_forward_plan(const acx_forward_plan_query_t* q, acx_forward_plan_t* out) {
+    if (!q || !out) ACX_FAIL(ACX_ERR_ARG, "acx_test_forward_plan: null pointer");
+    if (q->precision < ACX_PREC_F32 || q->precision > ACX_PREC_BF16_ACT || q->classes < 1 || q->classes > ACX_MAX_CLASSES ||
+        q->head_path < 0 || q->head_path > 2 || q->driver < ACX_PLAN_UNIFORM || q->driver > ACX_PLAN_AUGMENTED || q->tail < 0 ||
+        q->tail > ACX_PLAN_TAIL_SEG_EMBED || q->ways < 1 || q->ways > acx_ctx::kMaxSplitWays)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_forward_plan: bad query");
+    const bool pre = q->driver == ACX_PLAN_FEATURES || q->driver == ACX_PLAN_AUGMENTED;      // the trunk is handed its feature map
+    if (pre && q->tail > ACX_MODE_FRAME) ACX_FAIL(ACX_ERR_ARG, "acx_test_forward_plan: the features and augmented drivers have no segment tail");
+    const bool lam = q->driver == ACX_PLAN_AUGMENTED && q->has_lambda;
+    if (lam && (q->B & 1)) ACX_FAIL(ACX_ERR_ARG, "acx_test_forward_plan: mixup needs an even batch");
+    const int mode = q->tail <= ACX_MODE_FRAME ? q->tail : ACX_MODE_LOGITS;
+    const PlanEnv env{q->precision, q->dense != 0, q->head_path == 2 || (q->head_path == 0 && q->classes >= kHeadTiledMin)};
+    std::memset(out, 0, sizeof(*out));
+    TenantList l;
+    if (q->driver == ACX_PLAN_VARLEN) {
+        if (q->ways != 1) ACX_FAIL(ACX_ERR_ARG, "acx_test_forward_plan: a variable-length batch runs unsplit");
+        VarGeom vg;
+        Plan p;
+        ACX_TRY(make_plan_varlen(q->lengths, q->B, nullptr, &vg, &p));
+        forward_tenants(env, p.g, q->tail, false, &l);
+        if (l.n > ACX_PLAN_MAX_TENANTS) ACX_FAIL(ACX_ERR_STATE, "acx_test_forward_plan: %d tenants", l.n);
+        export_sub(p, 0, p.off_feat, l, &out->subs[0]);
+        out->n_subs = 1;
+        out->total = p.total;
+        size_t promised = 0;
+        ACX_TRY(acx_workspace_bytes_varlen(nullptr, q->lengths, q->B, mode, &promised));
+        out->promised = promised;
+        return ACX_OK;
+    }
+    const int Bf = lam ? q->B / 2 : q->B;
+    if (q->ways > 1 && Bf < q->ways * kSplitMinClips)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_forward_plan: %d ways need %d clips (got %d)", q->ways, q->ways * kSplitMinClips, Bf);
+    // what lies in front of the (sub-)batches of forward_uniform
+    size_t front = 0, promised = 0;
+    acx_plan_sub_t& s0 = out->subs[0];
+    AugWs aw{};
+    if (q->driver == ACX_PLAN_WINDOWS) {
+        front = align_up((size_t)q->B * 8);
+        ACX_TRY(acx_workspace_bytes_windows(nullptr, q->B, q->L, mode, &promised));
+    } else if (q->driver == ACX_PLAN_AUGMENTED) {
+        ACX_TRY(carve_augmented(env.dense, q->B, q->L, q->has_wave_plan != 0, lam, mode, &aw));
+        front = aw.fwd;
+        promised = aw.total;
+    } else {
+        ACX_TRY(acx_workspace_bytes(nullptr, q->B, q->L, mode, &promised));
+    }
+    size_t off = front;
+    for (int i = 0; i < q->ways; ++i) {
+        Plan p;
+        ACX_TRY(make_plan(q->ways > 1 ? split_part(Bf, q->ways, i) : Bf, q->L, &p));
+        forward_tenants(env, p.g, q->tail, pre, &l);
+        if (l.n + 2 > ACX_PLAN_MAX_TENANTS) ACX_FAIL(ACX_ERR_STATE, "acx_test_forward_plan: %d tenants", l.n);
+        export_sub(p, off, 0, l, &out->subs[i]);
+        off += p.total;
+    }
+    out->n_subs = q->ways;
+    out->total = off;
+    out->promised = promised;
+    if (front) {                      // sub-batch 0 also owns what the driver put in front
+        s0.bytes += s0.base;
+        s0.base = 0;
+    }
+    if (q->driver == ACX_PLAN_WINDOWS) s0.regions[ACX_PLAN_TABLES] = acx_plan_region_t{0, front};
+    if (q->driver == ACX_PLAN_AUGMENTED) {
+        AugFront af;
+        augmented_front(aw, env.dense, (size_t)q->B * (size_t)(q->L / kHop + 1), &af);
+        for (int i = 0; i < 5; ++i) s0.regions[ACX_PLAN_AUG_WAVE + i] = af.regions[i];
+        for (int i = 0; i < af.n_tenants; ++i) s0.tenants[s0.n_tenants++] = af.tenants[i];
+    }
+    return ACX_OK;
 }
 
 }  // extern "C"

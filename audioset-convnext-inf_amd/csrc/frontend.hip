@@ -281,10 +281,10 @@ static int launch_logmel_dense(acx_ctx* c, const float* wav, int B, int64_t L, i
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (s != nullptr && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
             ACX_FAIL(ACX_ERR_STATE, "acx_logmel_bn0 (dense-DFT frontend) cannot run inside a stream capture: use acx_forward");
-        const size_t need = (size_t)nframes * (kNFFT + kDenseN) * 4;
+        const size_t need = need_dense_frames((size_t)nframes) + need_dense_spec((size_t)nframes);       // (acx_internal.h)
         ACX_HIP(hipMallocAsync(&call_scratch, need, s));
         frames = reinterpret_cast<float*>(call_scratch);
-        spec = frames + (size_t)nframes * kNFFT;
+        spec = reinterpret_cast<float*>(static_cast<char*>(call_scratch) + need_dense_frames((size_t)nframes));
     }
     struct ScratchFree {        // every exit below (error returns included) hands the bytes back behind the launches queued so far
         void* p; hipStream_t s;

@@ -545,6 +545,7 @@ int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* 
     size_t need = 0;
     ACX_TRY(acx_workspace_bytes_windows(st->ctx, count, L, mode, &need));
     ACX_TRY(check_workspace(workspace, workspace_bytes, need));
+    ACX_TRY(check_uniform_plans(st->ctx, count, L, mode, nullptr, false));        // (before the table launches below)
     hipStream_t s = (hipStream_t)stream;
     DeviceGuard dg(st->device);
     long long* wstart = (long long*)workspace;
@@ -558,7 +559,7 @@ int acx_stream_forward(acx_stream* st, int count, int mode, float* out0, float* 
         ACX_HIP(hipGetLastError());
     }
     const size_t head = align_up((size_t)count * 8);
-    ACX_TRY(forward_uniform(st->ctx, st->ring, count, L, mode, out0, out1, (char*)workspace + head, s, wstart));
+    ACX_TRY(forward_uniform(st->ctx, st->ring, count, L, mode, out0, out1, (char*)workspace + head, s, wstart, nullptr, nullptr, true));
     if (st->timeline) {
         // window j of slot i -> history row i Hw + j mod Hw; slot i's windows are listed in order from its win_done on
         std::vector<long long> next(st->slots, -1), row(count);

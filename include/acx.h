@@ -1526,6 +1526,64 @@ ACX_API int acx_test_dwconv7_bf16_form(acx_ctx* ctx, int stage, int block, const
 ACX_API int acx_test_stem(acx_ctx* ctx, const float* feat, void* out, int B, int T, const int64_t* lengths, int n, int max_blocks,
                           void* scratch, size_t scratch_bytes, void* stream);
 ACX_API int acx_test_stem_scratch_bytes(const int64_t* lengths, int n, size_t* out_bytes, int64_t* out_rows);
+/* Test support: the workspace plan of a forward as data -- host arithmetic only: no context, no device.  A forward carves its
+ * workspace into REGIONS (the tables of a window / variable-length batch, feat, x of the four stages, and y, hidden, stats sized
+ * for one block of stage 0; acx_forward_augmented puts five regions of its own in front) and then lends those regions to TENANTS
+ * they were not sized for: the dense-DFT frontend's frames and spectrum, the LayerNorm rows the last block of a stage hands the
+ * downsample, the arrays of the two-GEMM MLPs, the fp32 downsample's normalised rows, the segment embeddings, the scene rows of
+ * the class-tiled head.  The forward computes every tenant's need with the definitions this call reports (need_* of
+ * csrc/acx_internal.h) and refuses with ACX_ERR_STATE, before its first launch, a plan in which one does not fit.
+ *   query : precision (enum acx_precision), dense (the dense-DFT frontend), classes, head_path (0: by class count, 1: fused, 2:
+ *           class-tiled -- ACX_HEAD_PATH), driver, tail (enum acx_mode, or ACX_PLAN_TAIL_SEG_OUTPUT / _SEG_EMBED: the acx_forward_
+ *           segments* calls; the features and augmented drivers take the three modes), ways (sub-batches, 1 .. 4; more than one
+ *           needs 8 clips per sub-batch and a driver other than VARLEN), B clips of L samples (WINDOWS: B windows of L samples;
+ *           VARLEN: the B entries of `lengths`; AUGMENTED: B clips going in, B / 2 into the trunk with has_lambda), and
+ *           has_wave_plan / has_lambda of acx_forward_augmented.
+ *   plan  : per sub-batch its clips, its first byte and size, every region as (offset, bytes) and every tenant as (kind, region,
+ *           offset inside the region, bytes needed, phase: frontend / block `block` of `stage` / the downsample in front of `stage`
+ *           / tail, operands: bit r set = the phase reads or writes region r in its own role).  All offsets count from the first
+ *           byte of the workspace; a region that a plan does not have has 0 bytes; the regions in front of the nested forward
+ *           (window table, acx_forward_augmented's five) are reported with sub-batch 0.  total: the last byte any sub-batch
+ *           uses; promised: what the driver's acx_workspace_bytes* call returns for the batch.
+ * No reference counterpart. */
+enum { ACX_PLAN_UNIFORM = 0, ACX_PLAN_FEATURES = 1, ACX_PLAN_WINDOWS = 2, ACX_PLAN_VARLEN = 3, ACX_PLAN_AUGMENTED = 4 };
+enum { ACX_PLAN_TAIL_SEG_OUTPUT = 3, ACX_PLAN_TAIL_SEG_EMBED = 4 };
+enum {
+    ACX_PLAN_TABLES = 0, ACX_PLAN_FEAT = 1, ACX_PLAN_X0 = 2, ACX_PLAN_Y = 6, ACX_PLAN_HIDDEN = 7, ACX_PLAN_STATS = 8,
+    ACX_PLAN_AUG_WAVE = 9, ACX_PLAN_AUG_FEAT = 10, ACX_PLAN_AUG_MIX = 11, ACX_PLAN_AUG_FRAMES = 12, ACX_PLAN_AUG_SPEC = 13,
+    ACX_PLAN_REGIONS = 14
+};
+enum {
+    ACX_PLAN_DENSE_FRAMES = 0, ACX_PLAN_DENSE_SPEC = 1, ACX_PLAN_LN_ROWS = 2, ACX_PLAN_MLP_BF16_HIDDEN = 3, ACX_PLAN_MLP_BF16_ROWS = 4,
+    ACX_PLAN_HIDDEN_ACT = 5, ACX_PLAN_ROW_STATS = 6, ACX_PLAN_XNORM = 7, ACX_PLAN_SEGMENT_EMB = 8, ACX_PLAN_SCENE_ROWS = 9,
+    ACX_PLAN_TENANT_KINDS = 10
+};
+enum { ACX_PLAN_PHASE_FRONTEND = 0, ACX_PLAN_PHASE_BLOCK = 1, ACX_PLAN_PHASE_DOWNSAMPLE = 2, ACX_PLAN_PHASE_TAIL = 3 };
+#define ACX_PLAN_MAX_TENANTS 40
+#define ACX_PLAN_MAX_WAYS 4
+typedef struct acx_plan_region_t { uint64_t offset, bytes; } acx_plan_region_t;
+typedef struct acx_plan_tenant_t {
+    int32_t kind, region, phase, stage, block;
+    uint32_t operands;
+    uint64_t offset, bytes;
+} acx_plan_tenant_t;
+typedef struct acx_plan_sub_t {
+    int32_t clips, n_tenants;
+    uint64_t base, bytes;
+    acx_plan_region_t regions[ACX_PLAN_REGIONS];
+    acx_plan_tenant_t tenants[ACX_PLAN_MAX_TENANTS];
+} acx_plan_sub_t;
+typedef struct acx_forward_plan_t {
+    int32_t n_subs, reserved;
+    uint64_t total, promised;
+    acx_plan_sub_t subs[ACX_PLAN_MAX_WAYS];
+} acx_forward_plan_t;
+typedef struct acx_forward_plan_query_t {
+    int32_t precision, dense, classes, head_path, driver, tail, ways, B, has_wave_plan, has_lambda;
+    int64_t L;
+    const int64_t* lengths;
+} acx_forward_plan_query_t;
+ACX_API int acx_test_forward_plan(const acx_forward_plan_query_t* query, acx_forward_plan_t* plan);
 
 /* ---- measurement: per-kernel-class device time, HIP events on the launch stream ------------ */
 ACX_API int acx_profile_enable(acx_ctx* ctx, int on);

@@ -300,11 +300,13 @@ class Guarded:
         return g, v
 
     @classmethod
-    def scratch(cls, nbytes, device="cuda"):
-        """Scratch prefilled with 0xFF bytes (NaN as fp32, fp16 and bf16) -> (guard, uint8 view)."""
+    def scratch(cls, nbytes, device="cuda", fill=0xFF):
+        """Scratch prefilled with `fill` bytes -- 0xFF: NaN as fp32, fp16 and bf16; 0x7F: 3.4e38 as fp32 and bf16, NaN as fp16, a
+        value no fmaxf drops -> (guard, uint8 view)."""
         g = cls((nbytes + 3) // 4 * 4, device)
-        g.payload.fill_(-1)
-        return g, g.payload.view(torch.uint8)
+        view = g.payload.view(torch.uint8)
+        view.fill_(fill)
+        return g, view
 
     def intact(self):
         front = self.buf[:GUARD_WORDS]

@@ -97,23 +97,24 @@ def raw_forward(model, packed, lengths, mode, ws, out0, out1):
 
 
 def test_nan_workspace_and_canary_tail(synth_sd):
-    """Nothing reads unwritten workspace as zeros (it starts as NaN), nothing writes past acx_workspace_bytes_varlen."""
+    """Nothing reads unwritten workspace (it starts as 0xFF bytes -- NaN -- and again as 0x7F bytes -- 3.4e38, which no fmaxf drops:
+    tests/forward_guard.py), nothing writes outside the acx_workspace_bytes_varlen bytes, the packed input or the outputs: canaries
+    lie directly at both ends of each."""
+    import forward_guard as fg
     model = make_model(synth_sd, "bf16a")
     lengths = [7361, 23000, L10 + 319, 16000]
     clips = clips_of(lengths, seed=500)
     packed = torch.cat(clips)
     ctx = model.native_context(packed.device)
     need = ctx.workspace_bytes_varlen(lengths, _ffi.MODE_LOGITS)
-    tail = 1 << 16
-    ws = torch.full((need + tail,), 0xFF, dtype=torch.uint8, device="cuda")     # every fp32 word a NaN
-    ws_view = ws[:need]
-    logits = torch.empty((4, 527), device="cuda")
-    probs = torch.empty((4, 527), device="cuda")
-    _ffi.check(raw_forward(model, packed, lengths, _ffi.MODE_LOGITS, ws_view, logits, probs))
-    torch.cuda.synchronize()
-    assert bool((ws[need:] == 0xFF).all())
+
+    def call(ws, ins, outs):
+        assert ws.numel() == need
+        return raw_forward(model, ins[0], lengths, _ffi.MODE_LOGITS, ws, outs[0], outs[1])
+    logits, probs = fg.run_guarded(need, [packed], [(4, 527), (4, 527)], call)
     for i, c in enumerate(clips):
         assert torch.equal(logits[i], model(c[None])["clipwise_logits"][0]), i
+        assert torch.equal(probs[i], model(c[None])["clipwise_output"][0]), i
 
 
 def test_graph_capture_replay(synth_sd):
