@@ -232,6 +232,8 @@ SIGNATURES = {
     "acx_pcm16_to_f32": (_c_int, [_vp, _vp, _c_i64, _vp]),
     "acx_stream_schedule": (_c_int, [_c_i64, _c_i64, _c_int, _c_i64, _c_int, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64),
                                      ctypes.POINTER(_c_i64)]),
+    "acx_stream_geometry": (_c_int, [_c_i64, _c_i64, _c_int, _c_i64, _c_int] + [ctypes.POINTER(_c_i64)] * 4),
+    "acx_test_stream_poison": (_c_int, [_vp, _c_int, _vp]),
     "acx_stream_create": (_c_int, [_vp, _c_int, _c_i64, _c_i64, _c_int, _c_i64, _c_int, ctypes.POINTER(_vp)]),
     "acx_stream_destroy": (None, [_vp]),
     "acx_stream_push": (_c_int, [_vp, _vp, _pint, ctypes.POINTER(_c_i64), _c_int, _vp]),
@@ -1119,5 +1121,13 @@ def stream_schedule(window, hop, orig_hz, pushed, closed):
     only): `pushed` input samples at orig_hz, the recording open or closed."""
     v = [_c_i64(), _c_i64(), _c_i64()]
     check(lib().acx_stream_schedule(int(window), int(hop), int(orig_hz), int(pushed), 1 if closed else 0,
+                                    *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def stream_geometry(window, hop, orig_hz, max_push, timeline):
+    """(adv, C, Ch, Hw): the per-slot sizes acx_stream_create derives from its arguments (acx_stream_geometry; host only)."""
+    v = [_c_i64() for _ in range(4)]
+    check(lib().acx_stream_geometry(int(window), int(hop), int(orig_hz), int(max_push), 1 if timeline else 0,
                                     *[ctypes.byref(x) for x in v]))
     return tuple(x.value for x in v)

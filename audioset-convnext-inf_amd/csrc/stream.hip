@@ -92,6 +92,26 @@ static long long str_rows(const StrGeom& g, long long R, bool closed) {
     return x > 0 ? (x + g.H - 1) / g.H : 0;
 }
 
+// The sizes of one slot's device state (host only; acx_stream_create allocates exactly these, acx_stream_geometry reports them):
+//   adv  the largest 32 kHz advance of one push of max_push input samples, or of a close (the outputs that read past the end);
+//   C    the mirrored ring: a window plus one advance, so no pending window is overwritten;
+//   Ch   the input history (0 at 32 kHz): one push behind the oldest input the first output that is not final yet reads;
+//   Hw   the probability history (0 without a timeline): every window under a row that is not final yet, plus one advance.
+struct StrSizes {
+    long long adv = 0, C = 0, Ch = 0, Hw = 0;
+};
+static int str_sizes(const StrGeom& g, int64_t max_push, bool timeline, const char* who, StrSizes* z) {
+    if (max_push < 1 || max_push > 0x7fffffffLL)
+        ACX_FAIL(ACX_ERR_ARG, "%s: max_push of %lld samples (expected 1 .. 2^31 - 1)", who, (long long)max_push);
+    const bool res = g.orig != kModelRate;
+    z->adv = res ? ((max_push + g.qmax + 1 + 2LL * g.of) * g.nf + g.of - 1) / g.of + 2 : max_push;
+    z->C = (g.W + z->adv + 63) / 64 * 64;
+    z->Ch = res ? (max_push + g.qmax + g.width + g.of + 64 + 63) / 64 * 64 : 0;
+    z->Hw = timeline ? (g.W + z->adv) / g.H + 4 : 0;
+    if (z->C > 0x7fffffffLL) ACX_FAIL(ACX_ERR_ARG, "%s: window + max_push exceed 2^31 samples at 32 kHz", who);
+    return ACX_OK;
+}
+
 // ---- kernels --------------------------------------------------------------------------------------------------------------
 struct StrAppend {
     int n, mirror;
@@ -340,6 +360,20 @@ int acx_stream_schedule(int64_t window, int64_t hop, int orig_hz, int64_t pushed
     return ACX_OK;
 }
 
+int acx_stream_geometry(int64_t window, int64_t hop, int orig_hz, int64_t max_push, int timeline, int64_t* adv, int64_t* ring,
+                        int64_t* history, int64_t* rows) {
+    if (timeline != 0 && timeline != 1) ACX_FAIL(ACX_ERR_ARG, "acx_stream_geometry: timeline must be 0 or 1 (got %d)", timeline);
+    StrGeom g;
+    ACX_TRY(str_geom(window, hop, orig_hz, &g));
+    StrSizes z;
+    ACX_TRY(str_sizes(g, max_push, timeline != 0, "acx_stream_geometry", &z));
+    if (adv) *adv = z.adv;
+    if (ring) *ring = z.C;
+    if (history) *history = z.Ch;
+    if (rows) *rows = z.Hw;
+    return ACX_OK;
+}
+
 // the handle's rows are `classes` wide: a context finalized since with another N must not get them
 static int check_classes(const acx_stream* st, const char* who) {
     if (st->ctx->num_classes != st->classes)
@@ -357,15 +391,10 @@ int acx_stream_create(acx_ctx* c, int slots, int64_t window, int64_t hop, int or
     if (timeline != 0 && timeline != 1) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: timeline must be 0 or 1 (got %d)", timeline);
     StrGeom g;
     ACX_TRY(str_geom(window, hop, orig_hz, &g));
-    if (max_push < 1 || max_push > 0x7fffffffLL)
-        ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: max_push of %lld samples (expected 1 .. 2^31 - 1)", (long long)max_push);
+    StrSizes z;
+    ACX_TRY(str_sizes(g, max_push, timeline != 0, "acx_stream_create", &z));
     const bool res = orig_hz != kModelRate;
-    // the largest 32 kHz advance of one push, or of a close (the outputs that read past the end)
-    const long long adv = res ? ((max_push + g.qmax + 1 + 2LL * g.of) * g.nf + g.of - 1) / g.of + 2 : max_push;
-    const long long C = (window + adv + 63) / 64 * 64;
-    const long long Ch = res ? (max_push + g.qmax + g.width + g.of + 64 + 63) / 64 * 64 : 0;
-    const long long Hw = timeline ? (window + adv) / hop + 4 : 0;
-    if (C > 0x7fffffffLL) ACX_FAIL(ACX_ERR_ARG, "acx_stream_create: window + max_push exceed 2^31 samples at 32 kHz");
+    const long long adv = z.adv, C = z.C, Ch = z.Ch, Hw = z.Hw;
     const size_t ring_b = sizeof(float) * 2 * (size_t)C * slots, hin_b = sizeof(float) * (size_t)Ch * slots;
     const size_t hist_b = sizeof(float) * (size_t)Hw * c->num_classes * slots;
     acx_stream* st = new acx_stream();
@@ -408,6 +437,29 @@ void acx_stream_destroy(acx_stream* st) {
     }
     if (st->rs) acx_resampler_destroy(st->rs);
     delete st;
+}
+
+int acx_test_stream_poison(acx_stream* st, int slot, void* stream) {
+    if (!st) ACX_FAIL(ACX_ERR_ARG, "acx_test_stream_poison: null handle");
+    if (slot < -1 || slot >= st->slots)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_stream_poison: slot %d out of range (-1, or 0 .. %d)", slot, st->slots - 1);
+    const int first = slot < 0 ? 0 : slot, last = slot < 0 ? st->slots : slot + 1;
+    for (int i = first; i < last; ++i) {
+        const acx_stream::Slot& x = st->s[i];
+        if (!x.closed && (x.in > 0 || x.out > 0))
+            ACX_FAIL(ACX_ERR_STATE, "acx_test_stream_poison: slot %d has an open recording", i);
+        if (st->busy(x))
+            ACX_FAIL(ACX_ERR_STATE, "acx_test_stream_poison: slot %d has windows or timeline rows that are not fetched yet", i);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    DeviceGuard dg(st->device);
+    const size_t n = (size_t)(last - first);
+    ACX_HIP(hipMemsetAsync(st->ring + (size_t)first * 2 * st->C, 0xFF, sizeof(float) * 2 * (size_t)st->C * n, s));
+    if (st->hin) ACX_HIP(hipMemsetAsync(st->hin + (size_t)first * st->Ch, 0xFF, sizeof(float) * (size_t)st->Ch * n, s));
+    if (st->hist)
+        ACX_HIP(hipMemsetAsync(st->hist + (size_t)first * st->Hw * st->classes, 0xFF,
+                               sizeof(float) * (size_t)st->Hw * st->classes * n, s));
+    return ACX_OK;
 }
 
 int acx_stream_push(acx_stream* st, const float* chunks, const int* slot, const int64_t* lengths, int n, void* stream) {

@@ -30,6 +30,14 @@ def schedule(window, hop, sample_rate, pushed, closed):
     return _ffi.stream_schedule(window, hop, rate, pushed, closed)
 
 
+def geometry(window, hop, sample_rate, max_push, timeline=True):
+    """(adv, C, Ch, Hw) of one slot of a handle with these arguments: the largest 32 kHz advance of one call, the samples of the
+    ring and of the input history, the windows of the probability history.  Window / hop in samples at 32 kHz, max_push in
+    input samples.  Host only (acx_stream_geometry)."""
+    rate = _rs.MODEL_RATE if sample_rate is None else _rs.check_rate(sample_rate)
+    return _ffi.stream_geometry(window, hop, rate, max_push, bool(timeline))
+
+
 class Stream:
     """One acx_stream handle on the model's device (see ConvNeXt.stream).  Clip-level outputs per window only: the segment-wise /
     frame-wise outputs of ConvNeXt.forward_segments are not part of live streams (run forward_windows(what="segment") on the
@@ -89,6 +97,11 @@ class Stream:
         if self._h is not None and self._h.value:
             _ffi.lib().acx_stream_destroy(self._h)
         self._h = None
+
+    def poison(self, slot=-1):
+        """Test support (acx_test_stream_poison): fill the device state of `slot` (-1: every slot) with 0xFF bytes."""
+        with torch.cuda.device(self.device):
+            _ffi.check(_ffi.lib().acx_test_stream_poison(self._h, int(slot), _ffi.stream_ptr(self.device)))
 
     def __del__(self):
         try:

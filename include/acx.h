@@ -482,6 +482,12 @@ ACX_API int acx_cross_trigger_rate(const int64_t* cross_triggers /* N*N */, cons
  *   acx_stream_schedule: *samples = R, *windows / *rows = the windows / rows emitted so far by a recording with `pushed` input
  *   samples, open (closed = 0) or closed (closed = 1).  Any output pointer may be NULL.
  *
+ * THE SIZES (host only: acx_stream_geometry gives them from the arguments of acx_stream_create, with the same argument checks;
+ * acx_stream_create allocates what the same function computes).  Per slot: *adv = the largest 32 kHz advance of one push of
+ * max_push input samples or of a close; *ring = C, the samples of the mirrored ring (2 C floats); *history = Ch, the samples of
+ * the input history (0 at 32 kHz); *rows = Hw, the windows of the probability history (0 without a timeline).  Any output
+ * pointer may be NULL.
+ *
  * acx_stream_create: needs a finalized ctx; allocates the device state on ctx's device and synchronises (call it outside any
  * capture): per slot a
  * 32 kHz ring of 2 (W + the largest 32 kHz advance of one push) samples, an input history when orig_hz != 32000, and with
@@ -508,6 +514,8 @@ ACX_API int acx_cross_trigger_rate(const int64_t* cross_triggers /* N*N */, cons
 typedef struct acx_stream acx_stream;
 ACX_API int acx_stream_schedule(int64_t window, int64_t hop, int orig_hz, int64_t pushed, int closed, int64_t* samples,
                                 int64_t* windows, int64_t* rows);
+ACX_API int acx_stream_geometry(int64_t window, int64_t hop, int orig_hz, int64_t max_push, int timeline, int64_t* adv,
+                                int64_t* ring, int64_t* history, int64_t* rows);
 ACX_API int acx_stream_create(acx_ctx* ctx, int slots, int64_t window, int64_t hop, int orig_hz, int64_t max_push, int timeline,
                               acx_stream** out);
 ACX_API void acx_stream_destroy(acx_stream* st);
@@ -1584,6 +1592,12 @@ typedef struct acx_forward_plan_query_t {
     const int64_t* lengths;
 } acx_forward_plan_query_t;
 ACX_API int acx_test_forward_plan(const acx_forward_plan_query_t* query, acx_forward_plan_t* plan);
+/* Test support: fill the device state of a live stream's slot -- its ring (2 C samples), its input history (Ch samples) and its
+ * probability history (Hw x classes) -- with 0xFF bytes on `stream`, so that a window or timeline row that touches a sample or a
+ * history row its own recording did not write comes out NaN instead of the zeros of acx_stream_create.  slot = -1: every slot.
+ * ACX_ERR_STATE while a listed slot has an open recording, or windows or rows that are not fetched yet (nothing is written
+ * then).  Changes nothing for callers who never call it.  No reference counterpart. */
+ACX_API int acx_test_stream_poison(acx_stream* st, int slot, void* stream);
 
 /* ---- measurement: per-kernel-class device time, HIP events on the launch stream ------------ */
 ACX_API int acx_profile_enable(acx_ctx* ctx, int on);

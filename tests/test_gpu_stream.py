@@ -11,10 +11,11 @@ import torch
 from audioset_convnext_inf_amd import _ffi, synth
 from audioset_convnext_inf_amd.pytorch.convnext import convnext_tiny
 
+from stream_cases import check_equal, run_stream
+
 pytestmark = pytest.mark.gpu
 SR = 32000
 W, H = 320000, 32000
-KEY = {"logits": "clipwise_logits", "scene": "scene", "frame": "frame"}
 
 
 @pytest.fixture(scope="module")
@@ -26,69 +27,6 @@ def make_model(sd, precision="fp32_split"):
     m = convnext_tiny(pretrained=False, strict=False, drop_path_rate=0.0, after_stem_dim=[252, 56], use_speed_perturb=False)
     m.load_state_dict(sd)
     return m.to("cuda").eval().set_precision(precision)
-
-
-def chunk_sizes(L, rng, max_push):
-    """Seeded random chunking: empty and one-sample chunks, primes, ordinary sizes and chunks longer than max_push."""
-    out, pos = [], 0
-    while pos < L:
-        c = rng.choice([0, 1, 7, 4099, 31991, 65537, rng.randrange(1, 3 * max_push), 2 * max_push + 13])
-        c = min(c, L - pos)
-        out.append(c)
-        pos += c
-    return out
-
-
-def run_stream(st, recs, rng, max_push, close=True, lead=()):
-    """Push every recording (slot i = recording i) in random chunks, all slots interleaved, then close; returns the calls'
-    dicts.  lead: chunk sizes per slot of the first calls, ahead of the random ones."""
-    heads = [[step[i] for step in lead] for i in range(len(recs))]
-    plans = [h + chunk_sizes(r.numel() - sum(h), rng, max_push) for h, r in zip(heads, recs)]
-    offs = [0] * len(recs)
-    results = []
-    for step in range(max(len(p) for p in plans)):
-        chunks = {}
-        for i, p in enumerate(plans):
-            if step < len(p):
-                chunks[i] = recs[i][offs[i]:offs[i] + p[step]]
-                offs[i] += p[step]
-        results.append(st.push(chunks))
-    if close:
-        results.append(st.close())
-    return results
-
-
-def gather(results, slot, what, timeline):
-    starts, rows, probs, tl, steps = [], [], [], [], []
-    for d in results:
-        m = (d["slot"] == slot).nonzero().flatten().tolist()
-        starts += d["starts"][m].tolist()
-        key = KEY[what]
-        if isinstance(d[key], list):
-            rows += [d[key][i] for i in m]
-        else:
-            rows += list(d[key][m])
-        if what == "logits":
-            probs += list(d["clipwise_output"][m])
-            if timeline:
-                t = (d["timeline_slot"] == slot).nonzero().flatten().tolist()
-                steps += d["timeline_step"][t].tolist()
-                tl += list(d["timeline"][t])
-    return starts, rows, probs, tl, steps
-
-
-def check_equal(model, recs, results, what="logits", timeline="mean", rate=None, slots=None):
-    for i, rec in enumerate(recs):
-        s = i if slots is None else slots[i]
-        ref = model.forward_windows(rec, window=W / SR, hop=H / SR, what=what, sample_rate=rate, timeline=timeline)
-        starts, rows, probs, tl, steps = gather(results, s, what, timeline)
-        assert torch.equal(torch.tensor(starts, dtype=torch.float64), ref["starts"]), (i, starts[:4], ref["starts"][:4])
-        assert torch.equal(torch.stack(rows), ref[KEY[what]]), i
-        if what == "logits":
-            assert torch.equal(torch.stack(probs), ref["clipwise_output"]), i
-            if timeline:
-                assert steps == list(range(ref["timeline"].shape[0])), i
-                assert torch.equal(torch.stack(tl), ref["timeline"]), i
 
 
 LENGTHS = [W - 1, W, W + 7, 3 * W + H // 2, 65 * SR]
@@ -109,7 +47,7 @@ def test_stream_equals_forward_windows(sd, precision, what, timeline, frontend):
     st = model.stream(slots=len(recs), window=W / SR, hop=H / SR, what=what, timeline=timeline, max_push=2.0)
     results = run_stream(st, recs, random.Random(zlib.crc32((precision + what + frontend).encode())), 2 * SR)
     assert all(d["short"] == [] for d in results)
-    check_equal(model, recs, results, what, timeline)
+    check_equal(model, recs, results, W, H, what, timeline)
 
 
 @pytest.mark.parametrize("rate,lengths", [
@@ -124,7 +62,7 @@ def test_stream_resampled(sd, rate, lengths):
     # after one second everywhere, slot 0 is pushed a single sample while the others get a normal chunk in the same call
     lead = [[rate] * len(recs), [1] + [rate // 2 + 7] * (len(recs) - 1)]
     results = run_stream(st, recs, random.Random(rate), 4 * rate, lead=lead)
-    check_equal(model, recs, results, rate=rate)
+    check_equal(model, recs, results, W, H, rate=rate)
 
 
 def test_stream_slot_reuse(sd):
@@ -133,8 +71,8 @@ def test_stream_slot_reuse(sd):
     st = model.stream(slots=2, window=W / SR, hop=H / SR)
     first = run_stream(st, [a], random.Random(1), 2 * SR)
     second = run_stream(st, [b], random.Random(2), 2 * SR)
-    check_equal(model, [a], first)
-    check_equal(model, [b], second)
+    check_equal(model, [a], first, W, H)
+    check_equal(model, [b], second, W, H)
     fresh = run_stream(model.stream(slots=2, window=W / SR, hop=H / SR), [b], random.Random(2), 2 * SR)
     for x, y in zip(second, fresh):
         assert torch.equal(x["clipwise_logits"], y["clipwise_logits"]) and torch.equal(x["timeline"], y["timeline"])
@@ -149,7 +87,7 @@ def test_stream_many_slots(sd):
     for d in results:
         assert d["slot"].tolist() == sorted(d["slot"].tolist())
     for i in (0, 1, 255, 256, 299):
-        check_equal(model, [recs[i]], results, slots=[i])
+        check_equal(model, [recs[i]], results, W, H, slots=[i])
 
 
 def test_stream_short(sd):
@@ -166,7 +104,7 @@ def test_stream_short(sd):
     assert torch.equal(d1["clipwise_logits"], ref["clipwise_logits"])
     assert torch.equal(d1["clipwise_output"], ref["clipwise_output"])
     assert (d1["timeline_slot"] == 0).sum() == 0
-    check_equal(model, [clip], [d0, d1], slots=[2])
+    check_equal(model, [clip], [d0, d1], W, H, slots=[2])
 
 
 def test_stream_two_handles_two_streams(sd):
@@ -188,8 +126,8 @@ def test_stream_two_handles_two_streams(sd):
     with torch.cuda.stream(s2):
         rb.append(sb.close())
     torch.cuda.synchronize()
-    check_equal(model, recs[:2], ra)
-    check_equal(model, recs[2:], rb)
+    check_equal(model, recs[:2], ra, W, H)
+    check_equal(model, recs[2:], rb, W, H)
 
 
 def test_stream_past_2_31_samples(sd):
