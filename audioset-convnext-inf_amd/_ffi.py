@@ -317,6 +317,14 @@ SIGNATURES = {
     "acx_kmeans_min_distance": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
     "acx_kmeans_sample": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "acx_kmeans_seed": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
+    "acx_gmm_workspace_bytes": (_c_int, [_c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
+    "acx_gmm_estep": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz,
+                               _vp]),
+    "acx_gmm_score": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "acx_gmm_mstep": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _c_int, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz,
+                               _vp]),
+    "acx_gmm_fit": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _c_sz, _vp]),
     "acx_cluster_scores_workspace_bytes": (_c_int, [_c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
     "acx_silhouette": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _c_sz, _vp]),
@@ -921,6 +929,54 @@ def kmeans_seed(x, ld_x, x_inv_norm, n, dim, metric, clusters, u, picked, center
     """acx_kmeans_seed on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
     check(lib().acx_kmeans_seed(x, int(ld_x), x_inv_norm, int(n), int(dim), int(metric), int(clusters), u, picked, centers,
                                 int(ld_c), status, ws[0], int(ws[1]), stream))
+
+
+GMM_DIAG, GMM_SPHERICAL = 0, 1                 # enum acx_gmm_covariance
+GMM_COVARIANCES = {"diag": GMM_DIAG, "spherical": GMM_SPHERICAL}
+GMM_NONFINITE, GMM_DEGENERATE = 1, 2           # bits of the status words of the acx_gmm_* calls
+
+
+class AcxGmmState(ctypes.Structure):
+    """struct acx_gmm_state: the device-side state of acx_gmm_fit (32 bytes)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("done", ctypes.c_int32), ("converged", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("lower_bound", ctypes.c_double), ("change", ctypes.c_double)]
+
+
+GMM_STATE_BYTES = ctypes.sizeof(AcxGmmState)           # 32
+
+
+def gmm_workspace_bytes(n, dim, components):
+    """Workspace of every acx_gmm_* call (host only)."""
+    return _query(lib().acx_gmm_workspace_bytes, _c_sz, int(n), int(dim), int(components))
+
+
+def gmm_estep(x, ld_x, n, dim, center, weights, means, variances, components, covariance_type, log_prob_norm, resp, ld_resp, labels,
+              log_prob_sum, status, ws, stream):
+    """acx_gmm_estep on raw device pointers (ctypes.c_void_p); center, resp and labels may be None; ws: (pointer, bytes)."""
+    check(lib().acx_gmm_estep(x, int(ld_x), int(n), int(dim), center, weights, means, variances, int(components), int(covariance_type),
+                              log_prob_norm, resp, int(ld_resp), labels, log_prob_sum, status, ws[0], int(ws[1]), stream))
+
+
+def gmm_score(x, ld_x, n, dim, center, weights, means, variances, components, covariance_type, log_prob_norm, labels, log_prob_sum,
+              status, ws, stream):
+    """acx_gmm_score on raw device pointers (ctypes.c_void_p); center and labels may be None; ws: (pointer, bytes)."""
+    check(lib().acx_gmm_score(x, int(ld_x), int(n), int(dim), center, weights, means, variances, int(components), int(covariance_type),
+                              log_prob_norm, labels, log_prob_sum, status, ws[0], int(ws[1]), stream))
+
+
+def gmm_mstep(x, ld_x, n, dim, center, resp, ld_resp, components, reg_covar, covariance_type, weights, means, variances, nk, status, ws,
+              stream):
+    """acx_gmm_mstep on raw device pointers (ctypes.c_void_p); center may be None; ws: (pointer, bytes)."""
+    check(lib().acx_gmm_mstep(x, int(ld_x), int(n), int(dim), center, resp, int(ld_resp), int(components), float(reg_covar),
+                              int(covariance_type), weights, means, variances, nk, status, ws[0], int(ws[1]), stream))
+
+
+def gmm_fit(x, ld_x, n, dim, weights, means, variances, components, covariance_type, max_iter, tol, reg_covar, center, labels,
+            log_prob_norm, state, status, ws, stream):
+    """acx_gmm_fit on raw device pointers (ctypes.c_void_p); ws: (pointer, bytes)."""
+    check(lib().acx_gmm_fit(x, int(ld_x), int(n), int(dim), weights, means, variances, int(components), int(covariance_type),
+                            int(max_iter), tol, float(reg_covar), center, labels, log_prob_norm, state, status, ws[0], int(ws[1]),
+                            stream))
 
 
 # bits of the status words of acx_silhouette / acx_cluster_dispersion / acx_contingency

@@ -970,6 +970,20 @@ class ConvNeXt(nn.Module):
         from .neighbors import dbscan
         return dbscan(self._scene_rows(data, sample_rate), eps, min_samples, device=self.head_audioset.weight.device, **kw)
 
+    def fit_gmm(self, data, components, sample_rate=None, **kw):
+        """A Gaussian mixture (pytorch/mixture.py: gmm) over scene embeddings on the model's device: `data` as cluster() takes it;
+        kw: covariance_type, init, n_init, max_iter, tol, reg_covar, seed and the *_init arguments.  -> mixture.GaussianMixture
+        (score_samples is the anomaly score of new clips)."""
+        from .mixture import gmm
+        return gmm(self._scene_rows(data, sample_rate), components, device=self.head_audioset.weight.device, **kw)
+
+    def select_components(self, data, ks, sample_rate=None, **kw):
+        """Choose the number of mixture components by BIC or AIC (pytorch/mixture.py: select_components) over scene embeddings on
+        the model's device: `data` as cluster() takes it, one fit per k of `ks`; kw: criterion and the gmm arguments.
+        -> mixture.ComponentSelection (scores, best_k, best, fits)."""
+        from .mixture import select_components
+        return select_components(self._scene_rows(data, sample_rate), ks, device=self.head_audioset.weight.device, **kw)
+
     def _scene_rows(self, data, sample_rate):
         """`data` as build_index takes it -> (n, 768) scene embeddings: a 2-D tensor of embeddings as it is, a list of waveforms
         at `sample_rate` extracted first (extract(..., what="scene", pack=True))."""

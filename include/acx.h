@@ -1198,6 +1198,70 @@ ACX_API int acx_kmeans_seed(const float* x, int64_t ld_x, const float* x_inv_nor
                             const double* u, int32_t* picked, float* centers, int64_t ld_c, int32_t* status, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- Gaussian mixtures over embeddings: EM with diagonal or spherical covariances, all decisions on the device ---------------------
+ * A density model with more than one mode (no reference counterpart; scikit-learn 1.7.2's GaussianMixture is the yardstick).
+ * Stateless; every buffer is the caller's, on the device.
+ *   x (n, dim) fp32 with row stride ld_x under the layout rules of acx_kmeans_assign: 16-byte aligned, strides multiples of 4, dim a
+ *   multiple of 4 in 4 .. ACX_KNN_MAX_DIM; 1 <= components <= ACX_KMEANS_MAX_CLUSTERS, n <= 2^30.
+ *   PARAMETERS, float64: weights (components), means (components, dim), variances (components, dim) for ACX_GMM_DIAG or
+ *   (components) for ACX_GMM_SPHERICAL, all contiguous.  center (dim) float64 is subtracted from rows and means before anything is
+ *   rounded to fp32 (NULL: zeros); a fit uses the column means.
+ * LOG-DENSITY of (row i, component k): with xc = x_i - center, mc = mean_k - center, a = 1 / v_k, b = mc / v_k,
+ *     lp = fp32(cst_k - D / 2),  D = sum_d [fp32(xc^2) fp32(a) + fp32(xc) fp32(-2 b)] in fp32,
+ *     cst_k = log w_k - (dim log 2 pi + sum log v + sum mc^2 a) / 2 in float64 (its sums in one fixed order; kept in float64
+ *     because its fp32 rounding would move every row of a component the same way), the last step one float64 fused multiply-add
+ *     and one rounding.  ACX_GMM_SPHERICAL takes the one variance of a component out of the sum for the same reason:
+ *     lp = fp32(cst_k - D / (2 v_k)) with D = sum_d [fp32(xc^2) + fp32(xc) fp32(-2 mc)] and v_k in float64;
+ *   the 2 dim long contraction on the f32 matrix instructions in ONE fixed order per pair (that of acx_knn_search over rows of
+ *   2 dim columns: the squares first).  A pair's log-density has the SAME BITS whatever n, components or the position of the row
+ *   or the component, and a row's outputs are a function of that row, center and the parameters alone.  The (n, components)
+ *   log-densities are never written.
+ *   acx_gmm_estep: clears *status.  With m_i = max_k lp and s_i = sum_k expf(lp - m_i) (fp32, an order that depends on components
+ *     alone): log_prob_norm[i] = m_i + logf(s_i) (never -0.0); resp[i * ld_resp + k] = expf(lp - m_i) / s_i (resp may be NULL);
+ *     labels[i] int32 (may be NULL) = the first component by log-density descending, then index ascending, -0.0 counting as +0.0;
+ *     *log_prob_sum = sum_i ((double)m_i + log((double)s_i)) in float64 in one fixed order: log_prob_norm before its rounding to
+ *     fp32 (a row whose log s_i is below half an ulp of m_i loses it in fp32 every time, which would bias the mean).  A
+ *     non-finite log-density (a NaN or +-inf in x, a zero weight or variance, an overflow) sets ACX_GMM_NONFINITE; a row whose
+ *     maximum is non-finite gets label -1.
+ *   acx_gmm_score: acx_gmm_estep without resp.
+ *   acx_gmm_mstep: clears *status.  scikit-learn's M-step from resp (n, components) fp32: N_k = sum_i r_ik + 10 * 2^-52, mean_k =
+ *     sum r xc / N_k + center, v_kd = sum r xc^2 / N_k - (sum r xc / N_k)^2 + reg_covar (SPHERICAL: the mean of v_kd over d),
+ *     w_k = N_k / n; nk (components) float64 = N_k.  The sums are float64, in an order that depends on (n, dim, components)
+ *     alone.  No float atomics: the same inputs give the same bits on every call.  N_k < 1 sets ACX_GMM_DEGENERATE; the
+ *     component's parameters are still the formula's.
+ *   acx_gmm_fit: the parameters hold the initial values and receive the result.  center (dim) <- the float64 column means of x in
+ *     a fixed order; the rows are centred ONCE into the workspace.  max_iter iterations (E-step, M-step, decide) are QUEUED;
+ *     after each the device writes *state: lower_bound = *log_prob_sum / n of the iteration's E-step, change = lower_bound
+ *     less the previous one (+inf in iteration 1), and sets done and converged when |change| < *tol (a float64 on the device);
+ *     every kernel of a later iteration returns at once.  ACX_GMM_NONFINITE stops the fit before the M-step.  One closing E-step
+ *     runs only if the last M-step ran, so labels (n) and log_prob_norm (n) belong to the returned parameters.
+ *     ACX_GMM_DEGENERATE may come from any iteration.
+ *   acx_gmm_workspace_bytes: the workspace of every call above; non-decreasing in each argument (host only).
+ * acx_forward's launch contract: everything in order on `stream`, no allocation, no synchronisation, capturable.  ARGUMENT errors
+ * return a negative status before any launch, as for acx_kmeans_assign; max_iter in 1 .. ACX_KMEANS_MAX_ITER. */
+enum acx_gmm_covariance { ACX_GMM_DIAG = 0, ACX_GMM_SPHERICAL = 1 };
+#define ACX_GMM_NONFINITE 1
+#define ACX_GMM_DEGENERATE 2
+typedef struct acx_gmm_state {
+    int32_t iterations, done, converged, reserved;
+    double lower_bound, change;
+} acx_gmm_state;
+ACX_API int acx_gmm_workspace_bytes(int64_t n, int dim, int components, size_t* out_bytes);
+ACX_API int acx_gmm_estep(const float* x, int64_t ld_x, int64_t n, int dim, const double* center, const double* weights,
+                          const double* means, const double* variances, int components, int covariance_type, float* log_prob_norm,
+                          float* resp, int64_t ld_resp, int32_t* labels, double* log_prob_sum, int32_t* status, void* ws,
+                          size_t ws_bytes, void* stream);
+ACX_API int acx_gmm_score(const float* x, int64_t ld_x, int64_t n, int dim, const double* center, const double* weights,
+                          const double* means, const double* variances, int components, int covariance_type, float* log_prob_norm,
+                          int32_t* labels, double* log_prob_sum, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_gmm_mstep(const float* x, int64_t ld_x, int64_t n, int dim, const double* center, const float* resp, int64_t ld_resp,
+                          int components, double reg_covar, int covariance_type, double* weights, double* means, double* variances,
+                          double* nk, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+ACX_API int acx_gmm_fit(const float* x, int64_t ld_x, int64_t n, int dim, double* weights, double* means, double* variances,
+                        int components, int covariance_type, int max_iter, const double* tol, double reg_covar, double* center,
+                        int32_t* labels, float* log_prob_norm, acx_gmm_state* state, int32_t* status, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* ---- cluster validation: silhouette, within-cluster dispersion, contingency tables ---------------------------------------------
  * What says whether a clustering is good and which k to take (no reference counterpart; scikit-learn 1.7.2's silhouette_samples,
  * calinski_harabasz_score, davies_bouldin_score and contingency-based scores are the yardsticks).  Stateless; every buffer is the
