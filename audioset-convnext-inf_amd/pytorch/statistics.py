@@ -145,8 +145,9 @@ def eigh_host(a, max_sweeps=DEFAULT_SWEEPS):
             apq = A[lo, hi]
             on = valid & (np.abs(apq) > thr)
             app, aqq = A[lo, lo], A[hi, hi]
-            theta = np.divide(aqq - app, 2.0 * apq, out=np.zeros(d), where=on)
-            t = np.where(theta < 0.0, -1.0, 1.0) / (np.abs(theta) + np.sqrt(1.0 + theta * theta))
+            with np.errstate(over="ignore"):                 # a pivot tiny against the diagonal gap: theta -> inf, t = 0, as on the device
+                theta = np.divide(aqq - app, 2.0 * apq, out=np.zeros(d), where=on)
+                t = np.where(theta < 0.0, -1.0, 1.0) / (np.abs(theta) + np.sqrt(1.0 + theta * theta))
             c1 = 1.0 / np.sqrt(1.0 + t * t)
             s = t * c1
             lower = idx == lo
