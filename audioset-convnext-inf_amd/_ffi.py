@@ -116,6 +116,12 @@ class AcxDwconv7Bf16Plan(ctypes.Structure):
 
 _pplan16 = ctypes.POINTER(AcxDwconv7Bf16Plan)
 
+
+class AcxResamplePlan(ctypes.Structure):
+    """struct acx_resample_plan_t: the tables and the tile form of a rate pair (acx_test_resample_plan)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("of", "nf", "width", "max_band", "per_thread", "lds_bytes", "outputs_per_tile",
+                                              "max_grid")]
+
 # acx_test_forward_plan: the workspace plan of a forward as data (include/acx.h, ACX_PLAN_*)
 PLAN_DRIVERS = {"uniform": 0, "features": 1, "windows": 2, "varlen": 3, "augmented": 4}
 PLAN_TAILS = {"logits": 0, "scene": 1, "frame": 2, "segment": 3, "segment_embeddings": 4}
@@ -369,6 +375,8 @@ SIGNATURES = {
     "acx_test_stem": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_int, _c_int, _vp, _c_sz, _vp]),
     "acx_test_stem_scratch_bytes": (_c_int, [ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_i64)]),
     "acx_test_forward_plan": (_c_int, [ctypes.POINTER(AcxForwardPlanQuery), ctypes.POINTER(AcxForwardPlan)]),
+    "acx_test_resample_plan": (_c_int, [_c_int, _c_int, ctypes.POINTER(AcxResamplePlan)]),
+    "acx_test_resample": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64), _c_int, _vp, _c_int, _vp]),
     "acx_profile_enable": (_c_int, [_vp, _c_int]),
     "acx_profile_read": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64)]),
 }
@@ -585,6 +593,13 @@ class Resampler:
         """wav: packed fp32 device tensor of the clips, lengths: <= MAX_VARLEN_CLIPS ints, out: packed output tensor."""
         lens = (_c_i64 * len(lengths))(*[int(n) for n in lengths])
         check(lib().acx_resample(self._h, ptr(wav), lens, len(lengths), ptr(out), stream_ptr(wav.device)))
+
+
+def resample_plan(orig_hz, new_hz):
+    """acx_test_resample_plan -> AcxResamplePlan: geometry, tile form and grid cap of orig_hz -> new_hz (host only)."""
+    plan = AcxResamplePlan()
+    check(lib().acx_test_resample_plan(int(orig_hz), int(new_hz), ctypes.byref(plan)))
+    return plan
 
 
 def resample_geometry(orig_hz, new_hz):

@@ -19,6 +19,7 @@ namespace acx {
 constexpr int kResMaxRate = 768000;
 constexpr long long kResMaxTable = 1LL << 22;           // nf * max_band floats
 constexpr size_t kResMaxLds = 56 * 1024;                // the staged input span (the prefix tables take 6 KiB more)
+constexpr int kResMaxGrid = 4096;                       // workgroups per launch; each walks tiles t, t + grid, ...
 
 struct ResPlan {
     int of, nf, width, max_band, per_thread;
@@ -217,8 +218,12 @@ void acx_resampler_destroy(acx_resampler* rs) {
     delete rs;
 }
 
-int acx_resample(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, void* stream) {
+// acx_resample; max_blocks caps the grid (acx_test_resample: a workgroup then walks many tiles of a small call)
+static int res_launch(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, void* stream,
+                      int max_blocks = kResMaxGrid) {
     if (!rs || !lengths || !out) ACX_FAIL(ACX_ERR_ARG, "acx_resample: null argument");
+    if (max_blocks < 1 || max_blocks > kResMaxGrid)
+        ACX_FAIL(ACX_ERR_ARG, "acx_test_resample: max_blocks = %d (expected 1 .. %d)", max_blocks, kResMaxGrid);
     if (B <= 0 || B > kVarMaxClips) ACX_FAIL(ACX_ERR_ARG, "acx_resample: %d clips (expected 1 .. %d)", B, kVarMaxClips);
     long long tiles = 0, samples = 0;
     const long long T = (long long)kResThreads * rs->per_thread;
@@ -234,10 +239,28 @@ int acx_resample(const acx_resampler* rs, const float* in, const int64_t* length
     if (samples > 0 && !in) ACX_FAIL(ACX_ERR_ARG, "acx_resample: in is null");
     if (tiles == 0) return ACX_OK;
     const ResGeom g{rs->of, rs->nf, rs->width, rs->per_thread};
-    const unsigned grid = (unsigned)std::min(tiles, 4096LL);
+    const unsigned grid = (unsigned)std::min(tiles, (long long)max_blocks);
     launch_kernel(&resample_kernel, dim3(grid), dim3(kResThreads), rs->lds_bytes, (hipStream_t)stream, packed_lens(lengths, B), g,
                   in, out, (const int2*)rs->band, (const float*)rs->taps);
     ACX_HIP(hipGetLastError());
+    return ACX_OK;
+}
+
+int acx_resample(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, void* stream) {
+    return res_launch(rs, in, lengths, B, out, stream);
+}
+
+int acx_test_resample(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, int max_blocks,
+                      void* stream) {
+    return res_launch(rs, in, lengths, B, out, stream, max_blocks);
+}
+
+int acx_test_resample_plan(int orig_hz, int new_hz, acx_resample_plan_t* plan) {
+    if (!plan) ACX_FAIL(ACX_ERR_ARG, "acx_test_resample_plan: plan is null");
+    ResPlan p;
+    ACX_TRY(res_plan(orig_hz, new_hz, &p));
+    *plan = acx_resample_plan_t{p.of, p.nf, p.width, p.max_band, p.per_thread, (int32_t)p.lds_bytes, kResThreads * p.per_thread,
+                                kResMaxGrid};
     return ACX_OK;
 }
 

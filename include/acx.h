@@ -1662,6 +1662,20 @@ ACX_API int acx_test_forward_plan(const acx_forward_plan_query_t* query, acx_for
  * ACX_ERR_STATE while a listed slot has an open recording, or windows or rows that are not fetched yet (nothing is written
  * then).  Changes nothing for callers who never call it.  No reference counterpart. */
 ACX_API int acx_test_stream_poison(acx_stream* st, int slot, void* stream);
+/* Test support: the resampler's launch plan as data, and its launch with the grid capped.  A workgroup forms tiles of
+ * outputs_per_tile = 256 per_thread consecutive outputs of one clip from an input span staged in lds_bytes of LDS; per_thread is 4,
+ * 2 or 1, the largest whose span  (outputs_per_tile - 1) of / nf + 2 width + 4  floats fits the kernel's LDS budget, and a call
+ * launches min(tiles, max_grid) workgroups, each walking tiles t, t + grid, ...  acx_test_resample_plan reports what
+ * acx_resampler_create would build for orig_hz -> new_hz, from the function it calls -- host arithmetic only, no device -- and
+ * refuses what it refuses (ACX_ERR_UNSUPPORTED where no form fits).  acx_test_resample is acx_resample with at most max_blocks
+ * (1 .. max_grid) workgroups, so that a workgroup walks many tiles of a small call; the result does not depend on it.  Everything
+ * is checked before the launch.  No reference counterpart. */
+typedef struct acx_resample_plan_t {
+    int32_t of, nf, width, max_band, per_thread, lds_bytes, outputs_per_tile, max_grid;
+} acx_resample_plan_t;
+ACX_API int acx_test_resample_plan(int orig_hz, int new_hz, acx_resample_plan_t* plan);
+ACX_API int acx_test_resample(const acx_resampler* rs, const float* in, const int64_t* lengths, int B, float* out, int max_blocks,
+                              void* stream);
 
 /* ---- measurement: per-kernel-class device time, HIP events on the launch stream ------------ */
 ACX_API int acx_profile_enable(acx_ctx* ctx, int on);

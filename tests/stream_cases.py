@@ -55,6 +55,11 @@ RATE_CASES = {
     44100: dict(max_push=441, recs=(4 * 22050 + 11, 3 * 22050)),
 }
 RATES = (32000, 8000, 11025, 16000, 44100, 48000, 96000, 44101)
+# The resampler's per_thread = 2 tile form (of / nf = 24: tests/resample_cases.py) under a live stream: 768 kHz, the API's
+# maximum, windows of 0.5 s every 0.25 s, odd push sizes.  Kept beside RATE_CASES and out of RATES: the CPU sweeps over RATES
+# build a table of every pushed count, which at 24 input samples per output would multiply their runtime; form_sim holds this
+# case's ring, input history, guard and covers at every call instead (tests/test_stream_cpu.py).
+FORM_CASE = dict(rate=768000, W=16000, H=8000, max_push=49999, recs=(7 * 384000 + 4801, 3 * 384000 + 77))
 
 
 def sweep_max_push(W, H, rate):
@@ -440,6 +445,18 @@ def rate_plans(rate):
     rng = random.Random(rate)
     lead = case.get("lead", 0)
     return [([lead] if lead else []) + scaled_chunk_sizes(L - lead, rng, case["max_push"]) for L in case["recs"]]
+
+
+def form_plans():
+    """the chunk lists of FORM_CASE: the seeded mix scaled to its odd max_push"""
+    rng = random.Random(FORM_CASE["rate"])
+    return [scaled_chunk_sizes(L, rng, FORM_CASE["max_push"]) for L in FORM_CASE["recs"]]
+
+
+def form_sim():
+    """FORM_CASE through Sim: the ring's mirror, a wrapped append, both append paths and a wrapped cover are all reached"""
+    c = FORM_CASE
+    return check_reach(simulate(Sim(c["W"], c["H"], c["rate"], c["max_push"], True, 64, "form"), form_plans()))
 
 
 def rate_sim(rate):

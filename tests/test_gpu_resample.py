@@ -4,7 +4,6 @@ forward_varlen(..., sample_rate=), extract(..., sample_rate=)).
 Correct means: every output sample within the error bound of an fp32 FMA chain of the float64 formula; every clip's bits the
 same however it is batched or packed; every forward with sample_rate= bit-identical to the forward of the resampled clips."""
 import ctypes
-import math
 
 import numpy as np
 import pytest
@@ -15,36 +14,17 @@ from audioset_convnext_inf_amd.pytorch.convnext import convnext_tiny
 from audioset_convnext_inf_amd.pytorch.extract_embeddings import extract
 from audioset_convnext_inf_amd.pytorch.resample import resample
 from audioset_convnext_inf_amd.utils.resample import resample as host_resample
+import resample_cases as rc
 
 pytestmark = pytest.mark.gpu
 RATES = (8000, 11025, 16000, 22050, 24000, 44100, 48000, 88200, 96000, 44101)
 
 
 def formula(x, orig):
-    """float64 y and sum |h_k x_k| over each output's band, and the band length (the stored band of acx_resample_taps)."""
-    g = math.gcd(orig, 32000)
-    of, nf = orig // g, 32000 // g
-    _, _, width, mb = _ffi.resample_geometry(orig, 32000)
-    start, count, _ = _ffi.resample_taps(orig, 32000)
-    start, count = np.array(start), np.array(count)
-    L = len(x)
-    N = _ffi.resampled_length(orig, 32000, L)
-    n = np.arange(N)
-    j, i = n // nf, n % nf
-    base = min(of, nf) * 0.99
-    y = np.zeros(N)
-    mag = np.zeros(N)
-    for r in range(mb):
-        k = start[i] + r
-        on = r < count[i]
-        m = j * of + k - width
-        xv = np.where(on & (m >= 0) & (m < L), x[np.clip(m, 0, max(L - 1, 0))], 0.0)
-        t = (-i / nf + (k - width) / of) * base
-        s = np.where(t == 0, 1.0, np.sin(np.pi * t) / np.where(t == 0, 1.0, np.pi * t))
-        h = np.where(on, (base / of) * s * np.cos(np.pi * t / 12) ** 2, 0.0)
-        y += h * xv
-        mag += np.abs(h * xv)
-    return y, mag, count[i]
+    """float64 y, sum |h_k x_k| over each output's band, and the band length: the independent reference of
+    tests/resample_cases.py, whose bands come from the definition and never from acx_resample_taps (the two are held equal at
+    these rates by tests/test_resample_cases_cpu.py)."""
+    return rc.reference(x, orig, 32000)
 
 
 def inputs(orig, L, seed):

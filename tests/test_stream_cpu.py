@@ -302,6 +302,21 @@ def test_rate_cases_reach_their_edges(rate):
     sc.rate_sim(rate)
 
 
+def test_form_case_reaches_its_edges():
+    """The 768 kHz case (the resampler's two-outputs-per-thread form, stream_cases.FORM_CASE): the same reach and the same checks
+    at every call, and schedule_def agrees with acx_stream_schedule at that rate wherever sampled."""
+    c = sc.FORM_CASE
+    sim = sc.form_sim()
+    assert all(n % 2 for n in (c["max_push"],) + c["recs"]) and any(n % 2 for plan in sc.form_plans() for n in plan)
+    nw = sum(stm.schedule(c["W"], c["H"], c["rate"], L, True)[1] for L in c["recs"])
+    assert sum(len(call) for call in sim.forwards) == nw
+    rng = random.Random(768)
+    for _ in range(12):
+        P = rng.randrange(0, max(c["recs"]))
+        for closed in (False, True):
+            assert sc.schedule_def(c["W"], c["H"], c["rate"], P, closed) == stm.schedule(c["W"], c["H"], c["rate"], P, closed)
+
+
 def test_schedule_def_is_the_schedule():
     """Sim counts with stream_cases.schedule_def, the restatement; it agrees with acx_stream_schedule wherever sampled."""
     rng = random.Random(5)
