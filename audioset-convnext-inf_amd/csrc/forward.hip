@@ -360,6 +360,20 @@ static int split_ways_for(const acx_ctx* c, int B) {
 static int split_part(int B, int ways, int i) { return B / ways + (i < B % ways ? 1 : 0); }
 
 static constexpr size_t kMaxAuxStreams = 16;
+// Is one of the set's side streams inside a stream capture?  A side stream joins the capture of its caller stream at the
+// fork and stays in it until the capture ENDS, also between two captured forwards, when nobody is queueing on the set
+// (users == 0).  Such a set must not serve another caller stream: its side streams would wait on a fork event that was
+// not captured, and the other caller's kernels would be recorded into the open graph instead of running.
+// A query that fails counts as capturing.
+static bool aux_capturing(const acx_ctx::Aux& a) {
+    for (hipStream_t s : a.streams) {
+        if (!s) continue;
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return true; }
+        if (cap != hipStreamCaptureStatusNone) return true;
+    }
+    return false;
+}
 // The fork/join set of caller stream `st`, pinned until release_aux().  *found = false (and nothing pinned) when the stream
 // has no set yet and one cannot be made now -- the first split forward on the stream happens inside a stream capture
 // (hipStreamCreate is illegal there; `with torch.cuda.graph(g): model(x)` captures on a private stream nobody can warm
@@ -372,10 +386,11 @@ static int get_aux(acx_ctx* c, hipStream_t st, acx_ctx::Aux* out, bool* found) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return ACX_OK;
         acx_ctx::AuxEntry e;
-        if (c->aux.size() >= kMaxAuxStreams) {          // drop the least recently used set nobody is queueing on
-            auto victim = c->aux.end();
+        if (c->aux.size() >= kMaxAuxStreams) {          // drop the least recently used set nobody is queueing on or capturing with
+            auto victim = c->aux.end();                 // (none eligible: the map grows past kMaxAuxStreams while captures are open)
             for (auto d = c->aux.begin(); d != c->aux.end(); ++d)
-                if (d->first != nullptr && d->second.users == 0 && (victim == c->aux.end() || d->second.stamp < victim->second.stamp))
+                if (d->first != nullptr && d->second.users == 0 && (victim == c->aux.end() || d->second.stamp < victim->second.stamp) &&
+                    !aux_capturing(d->second.a))
                     victim = d;
             if (victim != c->aux.end()) {
                 // retired, not destroyed: destroying a stream that still has work means synchronising it, which stalls every
@@ -388,9 +403,13 @@ static int get_aux(acx_ctx* c, hipStream_t st, acx_ctx::Aux* out, bool* found) {
                 c->aux.erase(victim);
             }
         }
-        if (!c->aux_retired.empty()) {
-            e.a = c->aux_retired.back();
-            c->aux_retired.pop_back();
+        // the most recently retired set that is not inside a capture (victims are checked above, so none should be: the pool
+        // is held to the same rule where a set is handed out, not only where it goes in); none eligible: a new set
+        auto r = c->aux_retired.end();
+        while (r != c->aux_retired.begin() && aux_capturing(*(r - 1))) --r;
+        if (r != c->aux_retired.begin()) {
+            e.a = *(r - 1);
+            c->aux_retired.erase(r - 1);
         } else {
             ACX_TRY(make_aux(&e.a));
         }

@@ -143,6 +143,8 @@ class ConvNeXt(nn.Module):
         self.frontend = os.environ.get("ACX_FRONTEND", "auto")       # set_frontend()
         if self.precision not in _ffi.PRECISIONS:
             raise ValueError("ACX_PRECISION must be one of %s" % sorted(_ffi.PRECISIONS))
+        if self.frontend not in _ffi.FRONTENDS:
+            raise ValueError("ACX_FRONTEND must be one of %s" % sorted(_ffi.FRONTENDS))
         self._ws = {}           # (device index, stream handle) -> workspace tensor: concurrent forwards on different
         #                         streams never share scratch memory (the reference module is re-entrant in eval).
         #                         Insertion-ordered, most recently used last; at most _WS_MAX_STREAMS entries are kept

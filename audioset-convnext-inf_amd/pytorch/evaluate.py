@@ -42,7 +42,11 @@ class _Stager(object):
     the library (acx_pcm16_to_f32: float(double(x) / 32767), the arithmetic of utilities.int16_to_float32, one kernel, 0.5 GB
     of traffic per 256 clips instead of torch's three element-wise passes); float32 batches are copied as they are.  A buffer
     comes up for rewriting kRing batches later; `to_pinned` first waits for the event recorded behind the asynchronous copy
-    that last READ it."""
+    that last READ it.
+    Order of every buffer: dev16 and dev32 are allocated on the caller's (compute) stream, `to_device`'s copy-stream tensors on the
+    copy stream with record_stream(compute); a fresh dev16 makes the copy stream wait for the compute stream once, ready[slot]
+    guards the pinned buffer (to_pinned) and the model's read (compute waits), dev16_read[slot] guards the int16 buffer's next
+    copy, dev32 is written and read on the compute stream alone; a sweep that fails returns its stager synchronised (forward())."""
     kReaders = 8
     kRing = 4           # two batches staged ahead + the one being staged + the one the copy engine reads
 
@@ -125,18 +129,26 @@ class _Stager(object):
             compute.wait_event(ready)
             dev.record_stream(compute)
             return pcm16_to_float32(dev) if dev.dtype == torch.int16 else dev
-        # int16 clips: device buffers of the stager's own (one int16 buffer per pinned slot, two float32 buffers the model reads in
+        # int16 clips: device buffers of the stager's own (one int16 buffer per pinned slot, three float32 buffers the model reads in
         # turn), allocated once.  Going through the caching allocator instead -- a 164 MB block made on the copy stream and freed on
         # the compute stream every batch -- cost the sweep 4 ms per batch of 256: the H2D copy did not overlap the model at all
         # (tools/sweep_timeline.py: 35.4 ms per batch against 31.2 resident, staging 1.9 ms and copy 3.1 ms of their own).
         n = host.numel()
         d16 = self.dev16[slot]
         if d16 is None or d16.numel() < n:
-            # (allocated on the CALLER's stream like d32 below, used on the copy stream behind explicit events: a replaced buffer
-            # goes back to the caching allocator only after the sweep's final synchronise has drained both streams -- forward())
+            # (allocated on the CALLER's stream like d32 below, used on the copy stream behind explicit events: a replaced buffer is
+            # marked as used by the copy stream too, so the caching allocator hands its block out again only when the work queued
+            # on both streams up to here has passed)
             if d16 is not None:
                 d16.record_stream(self.copy_stream)
             d16 = self.dev16[slot] = torch.empty(n, dtype=torch.int16, device=self.device)
+            # The caching allocator hands out a block in the CALLER's stream order: a kernel still queued there may yet read or
+            # write it, and the first use of d16 is the copy on the other stream -- which therefore waits for the caller's stream
+            # once, here.  That copy does not overlap the forward before it; it happens once per slot and growth,
+            # never in the steady state.  (Allocating under the copy stream with record_stream(compute) would keep that overlap,
+            # but d16 and d32 would then live in two allocator pools with two release rules; one rule -- the caller's stream
+            # owns every device buffer of the stager -- is worth one serialised copy per growth.)
+            self.copy_stream.wait_stream(compute)
         t = self.turn32
         self.turn32 = (t + 1) % len(self.dev32)
         d32 = self.dev32[t]
@@ -264,7 +276,6 @@ def forward(model, generator, return_input=False, return_target=False):
     output = {}
     device = next(model.parameters()).device
     model.eval()
-    stage = stager_for(device)
 
     def append(key, value):
         output.setdefault(key, []).append(value)
@@ -313,30 +324,39 @@ def forward(model, generator, return_input=False, return_target=False):
     # a pinned slot comes up again kRing batches later: the reader may be `depth` ahead, one batch is being staged and one is being
     # read by the copy engine
     assert _Stager.kRing >= kAheadDepth + 2, "pinned ring shorter than the read-ahead depth + 2"
-    it = _ahead(generator, prepare)
-    cur = next(it, None)
-    x_cur = device_input(*cur) if cur is not None else None
-    while cur is not None:
-        batch = cur[0]
-        with torch.no_grad():
-            batch_out = model(x_cur)
-        done = None
-        if device.type == "cuda":
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(device))
+    # The stager is checked out for the WHOLE sweep and goes back however the sweep ends -- the model, the reader or a fetch may
+    # raise at any batch: the reader is stopped first (it writes the pinned ring), then both streams are drained.
+    stage = stager_for(device)
+    it = None
+    try:
+        it = _ahead(generator, prepare)
         cur = next(it, None)
         x_cur = device_input(*cur) if cur is not None else None
-        if pending is not None:
-            collect(pending)                # waits for the PREVIOUS batch only (its own event, a side stream)
-        pending = (batch, batch_out, done)
-    try:
+        while cur is not None:
+            batch = cur[0]
+            with torch.no_grad():
+                batch_out = model(x_cur)
+            done = None
+            if device.type == "cuda":
+                done = torch.cuda.Event()
+                done.record(torch.cuda.current_stream(device))
+            cur = next(it, None)
+            x_cur = device_input(*cur) if cur is not None else None
+            if pending is not None:
+                collect(pending)                # waits for the PREVIOUS batch only (its own event, a side stream)
+            pending = (batch, batch_out, done)
         if pending is not None:
             collect(pending)
+        return {k: np.concatenate(v, axis=0) for k, v in output.items()}
     finally:
-        if device.type == "cuda":
-            torch.cuda.synchronize(device)      # the sweep has drained: the stager's buffers are idle when the next sweep takes them
-        release_stager(stage)
-    return {k: np.concatenate(v, axis=0) for k, v in output.items()}
+        try:
+            if it is not None:
+                it.close()      # joins the reader for at most 10 s (_ahead): one stuck longer, inside the caller's generator,
+                #                 can still write one batch into the pinned ring after the stager has gone back
+            if device.type == "cuda":
+                torch.cuda.synchronize(device)      # the sweep has drained: the stager's buffers are idle when the next sweep takes them
+        finally:
+            release_stager(stage)
 
 
 def calculate_statistics(target, clipwise_output):

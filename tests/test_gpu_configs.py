@@ -234,6 +234,55 @@ def test_many_caller_streams_recycle_fork_join_sets(synth_sd):
         assert torch.equal(oa, ref) and torch.equal(ob, ref)
 
 
+def test_open_capture_keeps_its_fork_join_set(synth_sd):
+    """between the forwards of an open stream capture nobody is queueing on the capturing stream's fork / join set
+    (users == 0), yet its side streams are inside the capture until it ends.  While a capture of a split forward on s0 is open,
+    a second thread runs the forward on 17 new streams: with the default stream's set and s0's the map is full at the 15th, and
+    s0's set is the least recently used one.  get_aux must pass it over (hipStreamIsCapturing on its side streams): every
+    thread result equals the serial one, the capture ends cleanly, its replay equals the eager result, and s0 works afterwards."""
+    import threading
+    m = make_model(synth_sd, "fp32_split")
+    w = synth.synth_waveforms(17, 7360, seed=44).cuda()           # 17 clips: two sub-batches, i.e. the fork / join path
+    ref = m(w)["clipwise_logits"].clone()
+    torch.cuda.synchronize()
+    s0 = torch.cuda.Stream()
+    with torch.cuda.stream(s0):                                   # warm-up: s0 gets its set, the capture below DOES split
+        eager = m(w)["clipwise_logits"].clone()
+    torch.cuda.synchronize()
+    assert torch.equal(eager, ref)
+    streams = [torch.cuda.Stream() for _ in range(17)]
+    outs, errors = [], []
+
+    def others():
+        try:
+            for s in streams:
+                with torch.cuda.stream(s):
+                    outs.append(m(w)["clipwise_logits"])
+            for s in streams:                                     # (each stream of its own: no device-wide wait beside a capture)
+                s.synchronize()
+        except BaseException as e:      # noqa: B902 -- reported by the main thread
+            errors.append(e)
+
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s0):
+        with torch.cuda.graph(g, stream=s0, capture_error_mode="thread_local"):
+            out = m(w)["clipwise_logits"]
+            t = threading.Thread(target=others)
+            t.start()
+            t.join()
+    torch.cuda.synchronize()
+    assert errors == [] and len(outs) == len(streams)
+    assert all(torch.equal(o, ref) for o in outs)
+    out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out, eager)
+    with torch.cuda.stream(s0):
+        later = m(w)["clipwise_logits"]
+    torch.cuda.synchronize()
+    assert torch.equal(later, ref)
+
+
 @pytest.mark.parametrize("precision", ["fp32_split", "bf16a"])
 def test_sub_batch_split_is_invisible(synth_sd, precision, monkeypatch):
     """acx_forward runs a batch as sub-batches on side streams (acx_sub_batches; default 2 from 16 clips up): whatever the
